@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Graph-HSCN hot-path benchmark on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W          (N=1)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = HSCN forward + criterion + backward over one Peptides-func-shaped
@@ -9,9 +9,15 @@ batch of 128 heterogeneous graphs per GPU (BASELINE.json configs[1]: K=16
 clusters, hidden 16, 3 layers, 10 classes), inputs resident in HBM, including
 the per-batch COO->CSR structure build.  Weak scaling: every rank owns its own
 128-graph shard; gradients are all-reduced (RCCL) as one flat buffer per step.
-Prints ONE JSON line on rank 0 (contract in the task statement) with the
-`roofline` of the local->local SpMM kernel and a `cpu_baseline` (the CPU oracle
-= restatement of the reference's PyG path, timed on this box's host cores).
+Prints ONE JSON line on rank 0: `value` (graphs/s) and `ms_per_step` of exactly
+--steps timed steps after --warmup untimed ones.  A plain run measures that and
+nothing else.  --full adds the secondary measurements to the same line: the
+`roofline` of the dominant kernel, a `cpu_baseline` (the CPU oracle =
+restatement of the reference's PyG path, timed on the host's cores), the spread
+over repeated regions, the other cluster-id regime, one step per replay, the
+streaming SpMM, stage A (sparse and dense routes), and for N > 1 the
+strong-scaling leg and the other all-reduce.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -105,6 +111,13 @@ def parse():
                          "B = 128, K = 64, MinCUT coarsening step on the dense MFMA route, with its MFMA roofline)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (roofline, CPU baseline, repeats, other cluster ids, one step "
+                         "per replay, streaming SpMM, stage A, strong scaling and all-reduce A/B); a plain run times the "
+                         "headline step alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (prediction, score, loss, parameter "
+                         "gradients, final virtual features; stage a: S, losses, gradients) as DIR/<name>.npy in float32")
     args = ap.parse_args()
     if args.steps_per_graph <= 0:
         args.steps_per_graph = max(d for d in range(1, 21) if args.steps % d == 0) if args.steps > 0 else 1
@@ -260,6 +273,29 @@ def capture(fn, warmup=3):
     return g
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float64 stays float64), 64 MB in all.  When they
+    do not fit, the smaller arrays are written whole and each larger one as a fixed sample of its elements
+    (flattened; indices drawn with seed 0 and sorted), so two runs with the same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        out[name] = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    left, n_left = DUMP_BUDGET_BYTES, len(out)
+    for name in sorted(out, key=lambda k: out[k].nbytes):
+        a = out[name]
+        share = left // n_left
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left, n_left = left - a.nbytes, n_left - 1
+
+
 class TimedStep:
     """One training step of stage C in the form the run asks for.  ``run(n)`` issues exactly n steps."""
 
@@ -270,6 +306,7 @@ class TimedStep:
         self.args, self.reducer = args, reducer
         self.fused = None
         self.multi, self.spg = None, 1
+        self.last = {}          # the autograd path's prediction / score / loss of its latest step (--dump-outputs)
         y = hb["local"].y
         x_dict, ei_dict = hb.x_dict, hb.edge_index_dict
         root_grad = torch.ones((), dtype=torch.float32, device=y.device)   # = loss.backward()'s implicit ones_like(loss)
@@ -284,8 +321,10 @@ class TimedStep:
             for p in model.parameters():
                 p.grad = None
             pred = model(x_dict, ei_dict, hb)
-            loss, _ = criterion(loss_fn, pred, y)
+            loss, score = criterion(loss_fn, pred, y)
             loss.backward(root_grad)
+            # detached: keeping an earlier step's autograd graph alive ties a later capture to its stream (replay.py)
+            self.last.update(pred=pred.detach(), score=score.detach(), loss=loss.detach())
             return loss
 
         def reduce():
@@ -368,6 +407,21 @@ class TimedStep:
                     reduce()
         self.run = run
 
+    def outputs(self, model):
+        """What a caller of the step receives from its latest run: prediction, score and loss, the parameter gradients
+        (by parameter name) and, on the graph-resident engine, the final virtual-node features."""
+        if self.fused is not None:
+            f = self.fused
+            out = {"pred": f.pred, "score": f.score, "loss": f.loss}
+            if f.virtual is not None and f.dims[1] > 0:
+                out["virtual"] = f.virtual[: f.dims[1]]
+        else:
+            out = dict(self.last)
+        for n, p in model.named_parameters():
+            if p.grad is not None:
+                out["grad." + n] = p.grad
+        return out
+
 
 def time_steps(ts, steps, warmup, barrier, settle_s=0.0, settle_steps=0):
     """`warmup` untimed steps, then exactly `steps` timed ones between two barriers.  settle_s (secondary legs only):
@@ -434,12 +488,14 @@ def stage_a_line(args):
                  else "hipGraph replay of the forward / backward launch pair + ordered fold (graph_hscn.step.ScnTrainStep)")
     else:
         one = torch.ones((), device=dev)
+        last = {}
 
         def eager_step():
             for p in scn.parameters():
                 p.grad = None
             S, mc, o, total = scn.forward_graphs(big, with_total=True)
             total.backward(one)
+            last.update(S=S.detach(), mc=mc.detach(), o=o.detach(), total=total.detach())
         step = eager_step
         issue = ("eager (layered operators + csrc/dense.hip through autograd)" if args.route == "dense" else
                  "eager (layered operators through autograd: the graphs do not fit the fused stage-A launch at this K)")
@@ -465,8 +521,18 @@ def stage_a_line(args):
     run_steps(args.steps, step, gm.replay if spg_a > 1 else None)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        if args.route == "sparse" and scn.resident_ok(big):
+            st.check()
+            names = {id(p): n for n, p in scn.named_parameters()}
+            outs = {"S": st.S, "losses": st.losses}          # {mincut, ortho, their sum}
+            outs.update({"grad." + names[id(p)]: g for p, g in st.param_grads})
+        else:
+            outs = {"S": last["S"], "losses": torch.stack([last["mc"], last["o"], last["total"]]).reshape(3)}
+            outs.update({"grad." + n: p.grad for n, p in scn.named_parameters() if p.grad is not None})
+        dump_outputs(args.dump_outputs, outs)
     cached = None
-    if args.route == "sparse" and scn.resident_ok(big):
+    if args.full and args.route == "sparse" and scn.resident_ok(big):
         # SURVEY.md 8(d), "MinCUT sparse (per graph)": bytes 4(n+1) + 4(e+n) + 4nK, each array touched once, forward;
         # the backward moves the same bytes again (x 2).  The step is latency-bound like stage C's (one workgroup per
         # graph, the working set of a batch is a few MB): the fraction says how far from a bandwidth problem it is.
@@ -477,7 +543,7 @@ def stage_a_line(args):
                     "unit": "GB/s", "frac": ab / t_step / 8e12, "traffic": None, "algorithmic_bytes_per_launch": ab,
                     "avg_launch_us": t_step * 1e6,
                     "note": "time = one replayed step (both launches); latency-bound, see DESIGN.md section 4"}
-    if args.route == "sparse" and scn.resident_ok(big) and st.one_launch:
+    if args.full and args.route == "sparse" and scn.resident_ok(big) and st.one_launch:
         # second, labelled figure: the batch's CSRs / out-degrees / A_hat x kept in HBM after the first visit
         # (hscn_scn_structure: what the stage-A loop does from its second epoch on; same results bit for bit)
         from graph_hscn.step import ScnStructurePool
@@ -498,7 +564,7 @@ def stage_a_line(args):
         assert torch.equal(st2.grads, st.grads) or st2.workspace is st.workspace
         cached = {"structure_build": "cached after the first visit (hscn_scn_structure)", "ms_per_step": 1e3 * dt2 / args.steps,
                   "graphs_per_s": B * args.steps / dt2}
-    if args.route == "dense":
+    if args.full and args.route == "dense":
         # the dominant launch: A S (a [n,n] x [n,K] product per graph) inside hscn_mincut_dense_ragged_fwd -- time the C call
         sizes = np.array([int(g.num_nodes) for g in graphs], dtype=np.float64)
         timer = KernelTimer(["hscn_mincut_dense_fwd", "hscn_mincut_dense_bwd", "hscn_mincut_dense_ragged_fwd",
@@ -569,7 +635,8 @@ def stage_a_line(args):
                             "fwd_call_us / frac_SAS_over_fwd_call; MFMA-busy from the PMC pass: profiles/r03_dense_mfma_busy.txt"}
     out = {"metric": f"graphs/sec (fwd+bwd) on {args.workload} stage A (MinCUT coarsening)", "value": B * args.steps / dt,
            "unit": "graphs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": args.full, "dtype": "f32",
+           "data": "synthetic",
            "config": {"workload": f"Graph-HSCN stage A (gcn_norm + SCN fwd + (mincut+ortho) bwd) on {args.workload}-shaped graphs",
                       "route": args.route, "graphs_per_gpu": B, "num_clusters": K, "nodes_per_gpu": N,
                       "edges_per_gpu": E, "nodes_per_graph": fixed_n, "step_issue": issue, "steps_per_graph": spg_a,
@@ -712,10 +779,14 @@ def main():
         ts.fused.check()
     if reducer is not None:
         reducer.check()          # a timed-out one-shot exchange would have left gradients unreduced
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts.outputs(model))
+
+    # everything below the headline runs under --full only
 
     # ---- spread: the same timed region again (exactly --steps steps each, max over ranks); `value` stays the first
     repeats = None
-    if args.repeats > 0:
+    if args.full and args.repeats > 0:
         reps = []
         for _ in range(args.repeats):
             d = time_steps(ts, args.steps, 0, barrier)
@@ -735,7 +806,7 @@ def main():
     # global batch on ONE GPU is measured here by rank 0 alone (the other ranks wait at the barrier), so the line can
     # be read either way: weak (value vs the 1-GPU line's value) or strong (one_gpu_ms_per_step / ms_per_step)
     strong = None
-    if world > 1 and not args.no_strong:
+    if args.full and world > 1 and not args.no_strong:
         if rank == 0:
             hbS = build_hetero_batch(shape, B * world, K, args.seed * 1000, dev, args.cluster_ids)[0].to(dev)
             if args.dtype == "f16":
@@ -755,7 +826,7 @@ def main():
     # ---- the same measurement with ONE step per hipGraph replay (what round 1 reported): the difference is the host's
     # replay overhead per graph launch, not kernel time
     single = None
-    if rank == 0 and world == 1 and not force_dist and args.mode == "graph" and spg > 1:
+    if args.full and rank == 0 and world == 1 and not force_dist and args.mode == "graph" and spg > 1:
         ts1 = TimedStep(args, model, hb, loss_fn, None, B, 1, spg_override=1)
         dt1 = time_steps(ts1, args.steps, args.warmup, barrier, settle_s=0.05)
         single = {"steps_per_graph": 1, "ms_per_step": 1e3 * dt1 / args.steps, "graphs_per_s": B * args.steps / dt1}
@@ -764,7 +835,7 @@ def main():
     # ---- the same step on the OTHER choice of cluster ids (one GPU only): the untrained SCN's argmax collapses to
     # ~3 clusters per graph, a trained assignment uses ~K -- the virtual branch's share of the step differs
     other_ids = None
-    if rank == 0 and world == 1 and not force_dist and not args.no_other_ids:
+    if args.full and rank == 0 and world == 1 and not force_dist and not args.no_other_ids:
         oc = "uniform" if args.cluster_ids == "scn_untrained" else "scn_untrained"
         hb2 = build_hetero_batch(shape, B, K, args.seed * 1000 + rank, dev, oc)[0].to(dev)
         if args.dtype == "f16":
@@ -778,7 +849,7 @@ def main():
 
     # ---- roofline of the dominant kernel: eager steps, HIP events around its C-ABI launch ----
     roofline = None
-    if rank == 0:
+    if args.full and rank == 0:
         import graph_hscn.engine as eng
         import graph_hscn.nn.functional as Fh
         import graph_hscn.step as stepmod
@@ -895,7 +966,7 @@ def main():
     # the same generator tiled to 4096 graphs, hidden 128 -- the shape where "HBM roofline" means something;
     # forward pass and backward pass (the same kernel on the source-keyed CSR), as 8(d) defines the figure
     streaming = None
-    if rank == 0 and not args.no_streaming_spmm:
+    if args.full and rank == 0 and not args.no_streaming_spmm:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_spmm
         streaming = bench_spmm.measure(32, 128, 20, dev=dev)
@@ -904,7 +975,7 @@ def main():
     # HBM traffic from PMC passes: separate rocprofv3 runs of this script (the counters cannot be read from inside
     # the process).  The newest profiles/rNN_pmc_traffic.json is used; it records the fingerprint of the kernel
     # sources it was collected from, and the line says whether that is still the code that is running
-    if rank == 0:
+    if args.full and rank == 0:
         import glob
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         from fingerprint import csrc_fingerprint
@@ -945,7 +1016,7 @@ def main():
     # ---- stage A (MinCUT coarsening: gcn_norm + SCN fwd + (mc+o) bwd) on the same graphs, fused engine,
     # one hipGraph replay per 128-graph step; reported beside the stage C headline
     stage_a = None
-    if rank == 0 and not args.no_stage_a:
+    if args.full and rank == 0 and not args.no_stage_a:
         from graph_hscn.data import Batch
         from graph_hscn.model.hscn import SCN
         from graph_hscn.step import ScnTrainStep
@@ -976,11 +1047,12 @@ def main():
     # ---- secondary line: BASELINE.json configs[3] -- the MinCUT coarsening step on PascalVOC-SP-shaped graphs (real
     # size spread, n in [395, 500]), 64 clusters, dense S^T A S route on the matrix cores, replayed from a hipGraph
     stage_a_dense = None
-    if rank == 0 and world == 1 and not args.no_stage_a_dense and args.dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_stage_a_dense and args.dtype == "f32":
         import copy
         a2 = copy.copy(args)
         a2.workload, a2.route, a2.stage, a2.batch, a2.mode = "pascalvoc_sp", "dense", "a", None, "graph"
         a2.steps, a2.warmup = max(20, min(args.steps, 100)), 10
+        a2.dump_outputs = None
         try:
             ln = stage_a_line(a2)
             stage_a_dense = {"metric": ln["metric"], "value": ln["value"], "unit": ln["unit"], "ms_per_step": ln["ms_per_step"],
@@ -989,7 +1061,7 @@ def main():
             stage_a_dense = {"error": str(e)[:300]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(hb_host, args, C, loss_fn, args.cpu_seconds)
 
     if rank == 0:
@@ -997,7 +1069,7 @@ def main():
             "metric": "graphs/sec (fwd+bwd) on Peptides-func batch=128" if args.workload == "peptides_func"
             else f"graphs/sec (fwd+bwd) on {args.workload}",
             "value": value, "unit": "graphs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": args.full,
             "dtype": "f32" if args.dtype == "f32" else "f16 storage (features + activations), f32 accumulate",
             "data": "synthetic",
             "config": {"workload": f"Graph-HSCN stage C (HSCN fwd+loss+bwd) on {args.workload}-shaped graphs",
@@ -1033,15 +1105,15 @@ def main():
         # ---- A/B of the exchange (N > 1): the OTHER all-reduce algorithm in a child job of its own, started after this
         # job's ranks have left the GPUs -- a failure there (it has never met real xGMI before this run) costs its
         # own entry, not this line
-        if world > 1 and not args.no_allreduce_ab and "HSCN_BENCH_AB_CHILD" not in os.environ:
+        if args.full and world > 1 and not args.no_allreduce_ab and "HSCN_BENCH_AB_CHILD" not in os.environ:
             other = "oneshot" if (args.allreduce == "rccl" or shared_gpus) else "rccl"
             os.environ["HSCN_BENCH_AB_CHILD"] = "1"
             argv = ["--gpus", str(world), "--steps", str(args.steps), "--warmup", str(args.warmup), "--allreduce", other,
                     "--workload", args.workload, "--hidden", str(args.hidden), "--layers", str(args.layers),
                     "--cluster-ids", args.cluster_ids, "--dtype", args.dtype, "--structure", args.structure,
                     "--steps-per-graph", str(args.steps_per_graph), "--seed", str(args.seed),
-                    "--no-cpu-baseline", "--no-streaming-spmm", "--no-stage-a", "--no-other-ids", "--no-strong",
-                    "--no-allreduce-ab"] + (["--batch", str(args.batch)] if args.batch else [])
+                    "--full", "--no-cpu-baseline", "--no-streaming-spmm", "--no-stage-a", "--no-other-ids",
+                    "--no-strong", "--no-allreduce-ab"] + (["--batch", str(args.batch)] if args.batch else [])
             t0 = time.perf_counter()
             rc, line, rest = launch_ranks(world, argv, timeout=240)
             ab = {"algorithm": other, "exit_code": rc, "wall_s": round(time.perf_counter() - t0, 1)}

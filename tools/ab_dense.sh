@@ -3,7 +3,7 @@
 #   tools/ab_dense.sh <tag> "NAME=ENV1=V1,ENV2=V2" ...   -> step / forward C call / backward C call per variant, 2 rounds
 OUT=$PWD/gpurun_out/${1:-abd}; shift
 mkdir -p $OUT
-A="--stage a --workload pascalvoc_sp --route dense --steps 100 --warmup 10"
+A="--stage a --workload pascalvoc_sp --route dense --steps 100 --warmup 10 --full"
 for r in 1 2; do
   for v in "$@"; do
     name=${v%%=*}; envs=${v#*=}; [ "$envs" = "$v" ] && envs=""

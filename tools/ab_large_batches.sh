@@ -3,7 +3,7 @@
 # beside the launch pair (HSCN_ONE_LAUNCH_LARGE_B=0: what B > 128 took before): us per step, default and uniform ids.
 OUT=$PWD/gpurun_out/${1:-large_b}
 mkdir -p $OUT
-Q="--no-cpu-baseline --no-streaming-spmm --no-stage-a --no-stage-a-dense"
+Q="--full --no-cpu-baseline --no-streaming-spmm --no-stage-a --no-stage-a-dense"
 for b in 192 256 512 1024 2048; do
   HSCN_ONE_LAUNCH_LARGE_B=0 python3 bench.py --batch $b $Q > $OUT/b${b}_pair.json 2> $OUT/err.txt || { tail -3 $OUT/err.txt; exit 1; }
   python3 bench.py --batch $b $Q > $OUT/b${b}_one.json 2> $OUT/err.txt || { tail -3 $OUT/err.txt; exit 1; }

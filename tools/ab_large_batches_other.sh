@@ -1,5 +1,5 @@
 OUT=$PWD/gpurun_out/lb2; mkdir -p $OUT
-Q="--no-cpu-baseline --no-streaming-spmm --no-stage-a --no-stage-a-dense"
+Q="--full --no-cpu-baseline --no-streaming-spmm --no-stage-a --no-stage-a-dense"
 for w in "pcqm_contact 2048" "pcqm_contact 4096" "peptides_struct 256" "peptides_struct 1024"; do
   set -- $w
   for v in 0 1; do

@@ -25,7 +25,7 @@ def main():
             for kv in envs:
                 k, v = kv.split("=", 1)
                 env[k] = v
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "400", "--warmup", "40", "--no-cpu-baseline",
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "400", "--warmup", "40", "--full", "--no-cpu-baseline",
                                   "--no-streaming-spmm", "--no-stage-a-dense", "--repeats", "4"] + extra, env=env, stdout=subprocess.PIPE,
                                  stderr=subprocess.DEVNULL, timeout=300)
             if out.returncode != 0:

@@ -4,7 +4,7 @@
 TAG=${1:-cfg}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--no-cpu-baseline --no-streaming-spmm --no-stage-a-dense --steps 200"
+COMMON="--full --no-cpu-baseline --no-streaming-spmm --no-stage-a-dense --steps 200"
 run() {  # name, args...
   name=$1; shift
   timeout -k 10 300 python bench.py "$@" $COMMON 2>/dev/null | tail -1 > $OUT/$name.json
@@ -33,9 +33,9 @@ run peptides_func_h32 --hidden 32 --no-stage-a
 run peptides_func_resident_structure --structure dataset-resident --no-stage-a
 HSCN_ONE_LAUNCH=0 run peptides_func_pair --no-stage-a
 for b in 64 256 512 1024; do run batch_$b --batch $b; done
-timeout -k 10 300 python bench.py --workload pascalvoc_sp --stage a --route dense --steps 50 --warmup 5 2>/dev/null | tail -1 > $OUT/stage_a_dense.json
-timeout -k 10 300 python bench.py --workload pascalvoc_sp --stage a --route sparse --steps 50 --warmup 5 2>/dev/null | tail -1 > $OUT/stage_a_sparse.json
-timeout -k 10 300 python bench.py --workload peptides_func --stage a --route sparse --steps 200 2>/dev/null | tail -1 > $OUT/stage_a_peptides.json
+timeout -k 10 300 python bench.py --workload pascalvoc_sp --stage a --route dense --steps 50 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/stage_a_dense.json
+timeout -k 10 300 python bench.py --workload pascalvoc_sp --stage a --route sparse --steps 50 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/stage_a_sparse.json
+timeout -k 10 300 python bench.py --workload peptides_func --stage a --route sparse --steps 200 --full 2>/dev/null | tail -1 > $OUT/stage_a_peptides.json
 python - $OUT <<'PY' >> $OUT/summary.txt
 import json, sys
 for n in ("stage_a_dense", "stage_a_sparse", "stage_a_peptides"):

@@ -4,7 +4,7 @@
 # variant, beside the 200-step default (run through gpurun from the repo root).
 OUT=$PWD/gpurun_out/${1:-drv}
 mkdir -p $OUT
-Q="--no-cpu-baseline --no-streaming-spmm --no-stage-a --no-other-ids --no-stage-a-dense"
+Q="--full --no-cpu-baseline --no-streaming-spmm --no-stage-a --no-other-ids --no-stage-a-dense"
 for r in 1 2 3; do
   python3 bench.py --steps 20 --warmup 5 $Q > $OUT/s20_$r.json 2> $OUT/err.txt || { tail -3 $OUT/err.txt; exit 1; }
   HSCN_BENCH_SPIN=1 python3 bench.py --steps 20 --warmup 5 $Q > $OUT/s20_spin_$r.json 2> $OUT/err.txt || { tail -3 $OUT/err.txt; exit 1; }

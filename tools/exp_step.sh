@@ -13,7 +13,7 @@ HSCN_LIB=$PWD/graph-hscn_amd/graph_hscn/lib/libhscn_diag.so timeout -k 10 300 py
 HSCN_LIB=$PWD/graph-hscn_amd/graph_hscn/lib/libhscn_diag.so timeout -k 10 300 python3 tools/diag_step.py uniform > $OUT/diag_uniform.txt 2> $OUT/diag_uniform.err || { tail -5 $OUT/diag_uniform.err; exit 1; }
 cat $OUT/diag_default.txt
 grep -A16 "virtual workgroup slowest" $OUT/diag_uniform.txt
-timeout -k 10 400 python3 bench.py --steps 400 --warmup 40 --no-cpu-baseline --no-streaming-spmm > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --steps 400 --warmup 40 --full --no-cpu-baseline --no-streaming-spmm > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

@@ -2,8 +2,8 @@
 """HBM traffic per kernel from two rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE, collected in
 separate runs with --kernel-trace only, as MI355X_MICROARCH.md prescribes).
 
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT_F -- python3 bench.py --mode eager ...
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT_W -- python3 bench.py --mode eager ...
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT_F -- python3 bench.py --mode eager --full ...
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT_W -- python3 bench.py --mode eager --full ...
   python tools/pmc_traffic.py fetch_counter_collection.csv write_counter_collection.csv out.json [commit]
 
 traffic_bytes = 2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024 (medians over launches): on gfx950 FETCH_SIZE

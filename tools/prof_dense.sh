@@ -6,7 +6,7 @@ TAG=${1:-dense}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-A="--stage a --workload pascalvoc_sp --route dense --steps 100 --warmup 10"
+A="--stage a --workload pascalvoc_sp --route dense --steps 100 --warmup 10 --full"
 python3 bench.py $A > $OUT/dense_u8.json 2> $OUT/dense_u8.err || { tail -5 $OUT/dense_u8.err; exit 1; }
 HSCN_DENSE_ADJ=f32 python3 bench.py $A > $OUT/dense_f32.json 2> $OUT/dense_f32.err || { tail -5 $OUT/dense_f32.err; exit 1; }
 HSCN_DENSE_ADJ=f32 HSCN_DENSE_AS=16 python3 bench.py $A > $OUT/dense_f32_16x16.json 2> $OUT/dense_f32_16x16.err || { tail -5 $OUT/dense_f32_16x16.err; exit 1; }

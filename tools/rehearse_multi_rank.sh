@@ -10,7 +10,7 @@ set -o pipefail
 TAG=${1:-rehearse}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--steps 200 --warmup 20 --no-cpu-baseline --no-streaming-spmm --no-stage-a --no-other-ids"
+COMMON="--steps 200 --warmup 20 --full --no-cpu-baseline --no-streaming-spmm --no-stage-a --no-other-ids"
 python3 bench.py --gpus 2 --steps 5 --warmup 1 > $OUT/refuse.json 2> $OUT/refuse.err
 echo "refusal exit code: $? (stdout bytes: $(wc -c < $OUT/refuse.json))" | tee $OUT/refuse.txt
 HSCN_BENCH_REHEARSAL=1 timeout -k 10 420 python3 bench.py --gpus 2 --allreduce oneshot $COMMON > $OUT/rehearsal_2ranks.json 2> $OUT/rehearsal_2ranks.err || { echo rehearsal failed; tail -20 $OUT/rehearsal_2ranks.err; exit 1; }

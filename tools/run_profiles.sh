@@ -2,7 +2,7 @@
 # The round's committed evidence, regenerated from ONE state of the sources (run through gpurun from the repo root,
 # with the commit id of that state: the GPU box has no .git):
 #   HSCN_COMMIT=$(git rev-parse --short HEAD) gpurun -- 'HSCN_COMMIT=... bash tools/run_profiles.sh r03'
-#   -> gpurun_out/<tag>/: bench.json (the default command), step_kernel_stats.csv (rocprofv3 --kernel-trace --stats of
+#   -> <tag>/ of the output folder: bench.json (the --full command), step_kernel_stats.csv (rocprofv3 --kernel-trace --stats of
 #      it), pmc_traffic.json (FETCH_SIZE / WRITE_SIZE passes, eager issue of the same launches; MI355X_MICROARCH.md
 #      prescribes the two counters in passes of their own, with --kernel-trace only), sq_counters.txt (two SQ passes)
 # Copy them to profiles/<tag>_* afterwards (tools/final_pass.sh does).
@@ -11,9 +11,9 @@ TAG=${1:-r03}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo bench done
-COMMON="--no-cpu-baseline --no-stage-a-dense --no-other-ids"
+COMMON="--full --no-cpu-baseline --no-stage-a-dense --no-other-ids"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 200 --warmup 20 $COMMON --no-streaming-spmm > $OUT/bench_traced.json 2> $OUT/trace.err || { tail -5 $OUT/trace.err; exit 1; }
 find $OUT/trace -name "*kernel_stats.csv" -exec cp {} $OUT/step_kernel_stats.csv \;
 echo stats done
