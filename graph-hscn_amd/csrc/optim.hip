@@ -13,6 +13,15 @@
 //   p   = p + (-(lr / (1 - beta1^t))) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))     (addcdiv_)
 // with the step-dependent scalars formed in double as Python does and rounded to float once.  The model family has
 // a few thousand parameters: one workgroup, so the step counter needs no second launch.
+//
+// hscn_adam_step_ex adds, in the same launch, torch.nn.utils.clip_grad_norm_(params, max_norm) in front of the update
+// (train/train.py:91-92) and optimizer.zero_grad() behind it (the accumulation loop's zeroing, train.py:94), and
+// hscn_clip_grad_norm_flat is the clip alone (for optimizers that are not this one).  The norm is the sum of g^2 in
+// double in a FIXED order -- per-thread partials, a butterfly over the wave, the 16 wave sums folded in wave order --
+// so it is bitwise the same from run to run; from there on torch's formulas (clip_grad.py::_clip_grads_with_norm_):
+//   norm = (float)sqrt(sum);  coef = min(reciprocal(norm + 1e-6f) * max_norm, 1);  g = g * coef
+// (`max_norm / t` on a tensor is t.reciprocal() * max_norm; the multiply happens at coef == 1 too, as in torch, and is
+// bitwise neutral there; a NaN / inf norm propagates as it does in torch).
 #include "hscn_common.h"
 
 namespace {
@@ -32,7 +41,39 @@ struct AdamArgs {
   int nseg, P, decoupled;
 };
 
-__global__ void __launch_bounds__(1024) k_adam_flat(const AdamArgs A) {
+// hscn_adam_step_ex: the plain step's arguments FIRST (the kernel reads its tables at the start of its argument block)
+struct AdamExArgs {
+  AdamArgs a;
+  float* grads;           // = a.grads, written: the clipped gradient, or 0 with `zero`
+  float* norm_out;        // [1] or NULL: the pre-clip norm (clip_grad_norm_'s return value)
+  float max_norm;
+  int clip, zero;
+};
+
+constexpr int FLAT_THREADS = 1024, FLAT_WAVES = FLAT_THREADS / HSCN_WAVE;
+
+// sum of g^2 over the flat buffer: `part` is this thread's partial (elements threadIdx.x + k * 1024); every thread
+// returns the same total, formed in the same order on every run.  `red`: FLAT_WAVES doubles of LDS.
+__device__ __forceinline__ double flat_sumsq(double part, double* red) {
+#pragma unroll
+  for (int o = HSCN_WAVE / 2; o > 0; o >>= 1) part += __shfl_xor(part, o);   // (a + b == b + a: all lanes agree)
+  if ((threadIdx.x & (HSCN_WAVE - 1)) == 0) red[threadIdx.x / HSCN_WAVE] = part;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < FLAT_WAVES; ++w) s += red[w];
+  return s;
+}
+
+__device__ __forceinline__ float clip_coef(double sumsq, float max_norm, float* norm_out) {
+  const float norm = (float)sqrt(sumsq);
+  if (norm_out && threadIdx.x == 0) norm_out[0] = norm;
+  const float c = (1.0f / (norm + 1e-6f)) * max_norm;
+  return c > 1.0f ? 1.0f : c;       // (torch.clamp(max=1): NaN stays NaN)
+}
+
+template <bool EX>
+__device__ __forceinline__ void adam_flat(const AdamArgs& A, const AdamExArgs& X) {
   // The segment tables go from the kernel arguments to LDS through ONE vector load per table entry (lane k reads
   // entry k of the argument block as plain memory), requested together with the thread's gradients and moments; a
   // thread then finds its element's tensor by a 5-step binary search in LDS.  (A select chain over the arguments
@@ -52,6 +93,21 @@ __global__ void __launch_bounds__(1024) k_adam_flat(const AdamArgs A) {
     const int i = threadIdx.x + u * 1024;
     const bool has = i < A.P;
     g0[u] = A.grads[has ? i : 0]; m0[u] = A.m[has ? i : 0]; v0[u] = A.v[has ? i : 0];
+  }
+  float coef = 1.0f;
+  if (EX && X.clip) {   // the norm first: every gradient is in registers (P <= 4096), the rest is read twice
+    __shared__ double red[FLAT_WAVES];
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < EPT; ++u)
+      if (threadIdx.x + u * 1024 < A.P) s += (double)g0[u] * (double)g0[u];
+    for (int i = threadIdx.x + EPT * 1024; i < A.P; i += 1024) {
+      const double g = A.grads[i];
+      s += g * g;
+    }
+    coef = clip_coef(flat_sumsq(s, red), X.max_norm, X.norm_out);   // (its barrier also publishes the tables)
+#pragma unroll
+    for (int u = 0; u < EPT; ++u) g0[u] = g0[u] * coef;
   }
   __syncthreads();
   auto addr = [&](int i) -> float* {
@@ -79,6 +135,11 @@ __global__ void __launch_bounds__(1024) k_adam_flat(const AdamArgs A) {
   const float w1 = (float)(1.0 - A.beta1), w2 = (float)(1.0 - A.beta2), b2f = (float)A.beta2;
   const float decay = (float)(1.0 - lr * A.wd), wdf = (float)A.wd, epsf = (float)A.eps;
   auto update = [&](float* pp, int i, float p, float g, float m, float v) {
+    if (EX) {
+      if (X.clip && i >= EPT * 1024) g = g * coef;
+      if (X.zero) X.grads[i] = 0.0f;
+      else if (X.clip) X.grads[i] = g;
+    }
     if (A.wd != 0.0) {
       if (A.decoupled) p = p * decay;
       else g = g + wdf * p;
@@ -105,19 +166,46 @@ __global__ void __launch_bounds__(1024) k_adam_flat(const AdamArgs A) {
   if (threadIdx.x == 0) { A.step[0] = t; A.pows[0] = b1t; A.pows[1] = b2t; }
 }
 
-}  // namespace
+__global__ void __launch_bounds__(1024) k_adam_flat(const AdamArgs A) { adam_flat<false>(A, AdamExArgs{}); }
 
-extern "C" int hscn_adam_step(float* const* params_host, const int32_t* seg_off_host, int nseg, const float* grads,
-                              float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
-                              const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, int decoupled,
-                              void* stream) {
+__global__ void __launch_bounds__(1024) k_adam_flat_ex(const AdamExArgs X) { adam_flat<true>(X.a, X); }
+
+// the clip alone, in place: one workgroup (the buffer is the same few thousand floats)
+__global__ void __launch_bounds__(1024) k_clip_grad_norm_flat(float* __restrict__ g, int P, float max_norm,
+                                                              float* norm_out) {
+  __shared__ double red[FLAT_WAVES];
+  constexpr int EPT = 4;
+  float g0[EPT];
+  double s = 0.0;
+#pragma unroll
+  for (int u = 0; u < EPT; ++u) {
+    const int i = threadIdx.x + u * 1024;
+    g0[u] = g[i < P ? i : 0];
+    if (i < P) s += (double)g0[u] * (double)g0[u];
+  }
+  for (int i = threadIdx.x + EPT * 1024; i < P; i += 1024) {
+    const double v = g[i];
+    s += v * v;
+  }
+  const float coef = clip_coef(flat_sumsq(s, red), max_norm, norm_out);
+#pragma unroll
+  for (int u = 0; u < EPT; ++u) {
+    const int i = threadIdx.x + u * 1024;
+    if (i < P) g[i] = g0[u] * coef;
+  }
+  for (int i = threadIdx.x + EPT * 1024; i < P; i += 1024) g[i] = g[i] * coef;
+}
+
+static int fill_adam_args(AdamArgs& A, float* const* params_host, const int32_t* seg_off_host, int nseg,
+                          const float* grads, float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev,
+                          double* beta_pows_dev, const double* lr_dev, double beta1, double beta2, double eps,
+                          double weight_decay, int decoupled) {
   if (nseg < 1 || nseg > ADAM_MAXSEG || P < 0 || P > (1 << 24)) return HSCN_E_UNSUPPORTED;
   if (!params_host || !seg_off_host || !grads || !exp_avg || !exp_avg_sq || !step_dev || !beta_pows_dev || !lr_dev)
     return HSCN_E_BADARG;
   if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
     return HSCN_E_BADARG;
-  if (P == 0) return 0;
-  AdamArgs A;
+  if (P == 0) return 0;   // (nothing to launch: the callers return before they do)
   for (int k = 0; k < ADAM_MAXSEG; ++k) { A.params[k] = k < nseg ? params_host[k] : nullptr; A.off[k] = k <= nseg ? seg_off_host[k] : 0; }
   A.off[ADAM_MAXSEG] = nseg == ADAM_MAXSEG ? seg_off_host[nseg] : 0;
   for (int k = 0; k < nseg; ++k)
@@ -126,7 +214,46 @@ extern "C" int hscn_adam_step(float* const* params_host, const int32_t* seg_off_
   A.grads = grads; A.m = exp_avg; A.v = exp_avg_sq; A.step = step_dev; A.pows = beta_pows_dev;
   A.lr = lr_dev; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps; A.wd = weight_decay; A.nseg = nseg; A.P = (int)P;
   A.decoupled = decoupled;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int hscn_adam_step(float* const* params_host, const int32_t* seg_off_host, int nseg, const float* grads,
+                              float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
+                              const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                              void* stream) {
+  AdamArgs A;
+  if (int rc = fill_adam_args(A, params_host, seg_off_host, nseg, grads, exp_avg, exp_avg_sq, P, step_dev, beta_pows_dev,
+                              lr_dev, beta1, beta2, eps, weight_decay, decoupled))
+    return rc;
+  if (P == 0) return 0;
   k_adam_flat<<<1, 1024, 0, hscn_stream(stream)>>>(A);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int hscn_adam_step_ex(float* const* params_host, const int32_t* seg_off_host, int nseg, float* grads,
+                                 float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
+                                 const double* lr_dev, double beta1, double beta2, double eps, double weight_decay,
+                                 int decoupled, float max_norm, float* norm_out, int zero_grads, void* stream) {
+  AdamExArgs X;
+  if (int rc = fill_adam_args(X.a, params_host, seg_off_host, nseg, grads, exp_avg, exp_avg_sq, P, step_dev,
+                              beta_pows_dev, lr_dev, beta1, beta2, eps, weight_decay, decoupled))
+    return rc;
+  if (!(max_norm > 0.0f) && max_norm != 0.0f) return HSCN_E_BADARG;   // (NaN / negative)
+  if (P == 0) return 0;
+  X.grads = grads; X.norm_out = norm_out; X.max_norm = max_norm; X.clip = max_norm > 0.0f; X.zero = zero_grads != 0;
+  k_adam_flat_ex<<<1, 1024, 0, hscn_stream(stream)>>>(X);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+extern "C" int hscn_clip_grad_norm_flat(float* grads, int64_t P, float max_norm, float* norm_out, void* stream) {
+  if (P < 0 || P > (1 << 24)) return HSCN_E_UNSUPPORTED;
+  if (!(max_norm > 0.0f) || (P > 0 && !grads)) return HSCN_E_BADARG;
+  if (P == 0) return 0;
+  k_clip_grad_norm_flat<<<1, 1024, 0, hscn_stream(stream)>>>(grads, (int)P, max_norm, norm_out);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -108,4 +108,43 @@ int hscn_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
                                          score, partials, grads, acts, sync, flag, job, structure, stream_);
 }
 
+// gradient accumulation over micro-batches (include/hscn.h: the *_acc entry points): the same launches, the fold adds
+// to `grads` instead of overwriting it (the loss column excepted)
+int hscn_resident_bwd_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                          const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
+                          const void* const* W_ll_host /* L */, const float* W1, const float* W2, const float* acts,
+                          const float* pooled, const float* z, const float* g_pred, const float* g_scale,
+                          const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n,
+                          int max_ell, float* partials /*[B][P]*/, float* grads /*[P]*/, int32_t* flag,
+                          const hscn_loss_tail* tail, void* stream_) {
+  return impl_resident_bwd<float>(x_local, ei_ll, E_ll, lptr, eptr_ll, N, B, F, H, L, C, head_act, W_ll_host, W1, W2,
+                                  acts, pooled, z, g_pred, g_scale, csr_rowptr_t, csr_col_t, dinv, max_n, max_ell,
+                                  partials, grads, flag, tail, stream_, 1);
+}
+
+int hscn_resident_bwd_with_virtual_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                                       const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
+                                       int head_act, const void* const* W_ll_host, const float* W1, const float* W2,
+                                       const float* acts, const float* pooled, const float* z, const float* g_pred,
+                                       const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
+                                       const float* dinv, int max_n, int max_ell, float* partials, float* grads,
+                                       int32_t* flag, const hscn_loss_tail* tail, const hscn_virtual_job* job,
+                                       void* stream_) {
+  return impl_resident_bwd_with_virtual<float>(x_local, ei_ll, E_ll, lptr, eptr_ll, N, B, F, H, L, C, head_act,
+                                               W_ll_host, W1, W2, acts, pooled, z, g_pred, g_scale, csr_rowptr_t,
+                                               csr_col_t, dinv, max_n, max_ell, partials, grads, flag, tail, job,
+                                               stream_, 1);
+}
+
+int hscn_resident_train_step_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                                 const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
+                                 const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
+                                 const float* b2, int max_n, int max_ell, const float* target, int loss_kind, float* pred,
+                                 float* score, float* partials, float* grads, float* acts, uint32_t* sync, int32_t* flag,
+                                 const hscn_virtual_job* job, const hscn_structure* structure, void* stream_) {
+  return impl_resident_train_step<float>(x_local, ei_ll, E_ll, lptr, eptr_ll, N, B, F, H, L, C, head_act,
+                                         layer_params_host, W1, b1, W2, b2, max_n, max_ell, target, loss_kind, pred,
+                                         score, partials, grads, acts, sync, flag, job, structure, stream_, 1);
+}
+
 }  // extern "C"

@@ -523,9 +523,12 @@ __device__ __forceinline__ bool wait_published(const uint32_t* word, uint32_t wa
 // on the backward launch -- sum of the per-graph loss terms times 1/count)
 // epoch (optional): the step counter of the one-launch training step (resident_step.h), advanced here -- after every
 // workgroup of that launch has finished, before the next step's launch starts
-__global__ void __launch_bounds__(256) k_param_reduce(const float* __restrict__ partials, float* __restrict__ out,
-                                                      int B, int P, int p_scaled, float scale,
-                                                      uint32_t* epoch = nullptr) {
+// ACC (k_param_reduce_acc, gradient accumulation over micro-batches): out[p] = out[p] + sum for every column but the
+// loss column -- the sum formed exactly as above and added last, autograd's `p.grad += new`; the loss column is still
+// overwritten (the loss of THIS micro-batch).
+template <bool ACC>
+__device__ __forceinline__ void param_reduce(const float* __restrict__ partials, float* __restrict__ out, int B, int P,
+                                             int p_scaled, float scale, uint32_t* epoch) {
   if (epoch && blockIdx.x == 0 && threadIdx.x == 0) epoch[0] = epoch[0] + 1u;
   __shared__ float red[8][32];
   const int pl = threadIdx.x & 31, sl = threadIdx.x >> 5;
@@ -555,8 +558,22 @@ __global__ void __launch_bounds__(256) k_param_reduce(const float* __restrict__ 
     float t = 0.f;
 #pragma unroll
     for (int q = 0; q < 8; ++q) t += red[q][pl];
-    out[p] = p == p_scaled ? t * scale : t;
+    if (p == p_scaled) out[p] = t * scale;
+    else if (ACC) out[p] = out[p] + t;
+    else out[p] = t;
   }
+}
+
+__global__ void __launch_bounds__(256) k_param_reduce(const float* __restrict__ partials, float* __restrict__ out,
+                                                      int B, int P, int p_scaled, float scale,
+                                                      uint32_t* epoch = nullptr) {
+  param_reduce<false>(partials, out, B, P, p_scaled, scale, epoch);
+}
+
+__global__ void __launch_bounds__(256) k_param_reduce_acc(const float* __restrict__ partials, float* __restrict__ out,
+                                                          int B, int P, int p_scaled, float scale,
+                                                          uint32_t* epoch = nullptr) {
+  param_reduce<true>(partials, out, B, P, p_scaled, scale, epoch);
 }
 
 

@@ -2339,7 +2339,7 @@ int impl_resident_bwd(const float* x_local, const int64_t* ei_ll, int64_t E_ll, 
                       const float* pooled, const float* z, const float* g_pred, const float* g_scale,
                       const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n,
                       int max_ell, float* partials /*[B][P]*/, float* grads /*[P]*/, int32_t* flag,
-                      const hscn_loss_tail* tail, void* stream_) {
+                      const hscn_loss_tail* tail, void* stream_, int accumulate = 0) {
   if (B < 0 || N < 0) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, 0, max_ell, 0)) return HSCN_E_UNSUPPORTED;
@@ -2357,7 +2357,10 @@ int impl_resident_bwd(const float* x_local, const int64_t* ei_ll, int64_t E_ll, 
     case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd<64, float>(A, B, st); break;
   }
   if (rc) return rc;
-  k_param_reduce<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count);
+  if (accumulate)
+    k_param_reduce_acc<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count);
+  else
+    k_param_reduce<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -2370,7 +2373,7 @@ int impl_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, i
                                    const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
                                    const float* dinv, int max_n, int max_ell, float* partials, float* grads,
                                    int32_t* flag, const hscn_loss_tail* tail, const hscn_virtual_job* job,
-                                   void* stream_) {
+                                   void* stream_, int accumulate = 0) {
   if (B < 0 || N < 0 || !job) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, job->max_v, max_ell, job->max_evv)) return HSCN_E_UNSUPPORTED;
@@ -2400,7 +2403,10 @@ int impl_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, i
     case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd_virtual<64, float>(Ab, Af, B, st); break;
   }
   if (rc) return rc;
-  k_param_reduce<<<hscn_blocks(Ab.P, 32), 256, 0, st>>>(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count);
+  if (accumulate)
+    k_param_reduce_acc<<<hscn_blocks(Ab.P, 32), 256, 0, st>>>(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count);
+  else
+    k_param_reduce<<<hscn_blocks(Ab.P, 32), 256, 0, st>>>(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -2455,7 +2461,7 @@ int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
                              const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
                              const float* b2, int max_n, int max_ell, const float* target, int loss_kind, float* pred,
                              float* score, float* partials, float* grads, float* acts, uint32_t* sync, int32_t* flag,
-                             const hscn_virtual_job* job, const hscn_structure* pre, void* stream_) {
+                             const hscn_virtual_job* job, const hscn_structure* pre, void* stream_, int accumulate = 0) {
   if (B < 0 || N < 0) return HSCN_E_BADARG;
   if (pre && (!pre->ll_rowptr_d || !pre->ll_rowptr_s || !pre->ll_dinv || (E_ll > 0 && (!pre->ll_col_d || !pre->ll_col_s))))
     return HSCN_E_BADARG;
@@ -2508,8 +2514,12 @@ int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
   k_param_reduce<<<HSCN_DIAG_REDUCE_BLOCKS, 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
                                                           S.ready ? sync : nullptr);
 #else
-  k_param_reduce<<<hscn_blocks(S.P, 32), 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
-                                                       S.ready ? sync : nullptr);
+  if (accumulate)
+    k_param_reduce_acc<<<hscn_blocks(S.P, 32), 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
+                                                             S.ready ? sync : nullptr);
+  else
+    k_param_reduce<<<hscn_blocks(S.P, 32), 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
+                                                         S.ready ? sync : nullptr);
 #endif
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;

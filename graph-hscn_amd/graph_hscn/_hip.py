@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("HSCN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libhscn.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 ACT = {"identity": 0, "relu": 1, "elu": 2, "tanh": 3}
 
 P = c_void_p
@@ -73,6 +73,9 @@ _SIGNATURES = {
                                               P, P, c_int, c_int, P, P, P, P, P, P, P, P]),
     "hscn_adam_step": (c_int, [P, P, c_int, P, P, P, c_int64, P, P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, c_int, P]),
+    "hscn_adam_step_ex": (c_int, [P, P, c_int, P, P, P, c_int64, P, P, P, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, c_int, c_float, P, c_int, P]),
+    "hscn_clip_grad_norm_flat": (c_int, [P, c_int64, c_float, P, P]),
     "hscn_resident_supported": (c_int, [c_int] * 8),
     "hscn_resident_param_count": (c_int64, [c_int] * 4),
     "hscn_resident_fwd": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64,
@@ -119,6 +122,10 @@ for _n in ("hscn_resident_fwd", "hscn_resident_bwd", "hscn_resident_fwd_with_vir
            "hscn_scn_resident_fwd", "hscn_scn_resident_bwd", "hscn_resident_train_step",
            "hscn_scn_resident_train_step", "hscn_scn_resident_train_epoch"):
     _SIGNATURES[_n + "_f16"] = _SIGNATURES[_n]
+# gradient-accumulating twins (include/hscn.h, ABI 19: *_acc): same argument lists
+for _n in ("hscn_resident_bwd", "hscn_resident_bwd_with_virtual", "hscn_resident_train_step"):
+    _SIGNATURES[_n + "_acc"] = _SIGNATURES[_n]
+    _SIGNATURES[_n + "_acc_f16"] = _SIGNATURES[_n]
 
 
 class HipExtensionMissing(RuntimeError):

@@ -197,7 +197,8 @@ class CapturedStep:
     cannot reach into it (tests/test_gpu_step.py)."""
 
     def __init__(self, model, static: StaticHeteroBatch, loss_fn: str, warmup: int = 3, optimizer=None, pre=None,
-                 one_launch: Optional[bool] = None, reducer=None, structure=None):
+                 one_launch: Optional[bool] = None, reducer=None, structure=None, accumulate: bool = False,
+                 max_norm: Optional[float] = None):
         """``one_launch``: passed to ``step.ResidentTrainStep`` (None: the one-launch step whenever the batch fits it;
         False: the forward + backward launch pair, whose gradients are bit-identical to the eager autograd path).
         ``reducer``: a ``distributed.FlatGradReducer``; its all-reduce of the flat gradient buffer (RCCL kernels are
@@ -216,7 +217,19 @@ class CapturedStep:
         The ``warmup`` eager iterations that precede the capture run the optimizer too (PyTorch's whole-network
         capture recipe); parameters and optimizer state are put back afterwards, IN PLACE (the captured launches
         hold their addresses): state that existed before is restored, state the warm-up created is zeroed (the
-        initial state of the Adam family)."""
+        initial state of the Adam family).
+        ``accumulate`` (the reference's ``batch_accumulation``, train/train.py:89-95): the step ADDS its gradients to
+        the flat buffer (``ResidentTrainStep(accumulate=True)``) and two graphs share every buffer: ``graph`` (the
+        boundary iteration: gather, step, all-reduce, clip, optimizer step, gradients zeroed -- by the optimizer's
+        own launch when it is an ``optim.FlatAdam(zero_grads=True)``) and ``micro_graph`` (gather and step only,
+        captured without warm-up runs of its own: parameters, optimizer state and the gather's counter end up as with
+        one capture).  ``replay(step_optimizer=False)`` replays the micro graph.  Without an optimizer both would be
+        the same graph: ``micro_graph`` is then ``graph`` and zeroing is the caller's.
+        ``max_norm``: ``clip_grad_norm_`` of the flat gradient between the all-reduce and the optimizer step as a
+        launch of its own (``optim.clip_grad_norm_flat``; ``clip_norm`` receives the pre-clip norm), for an
+        optimizer that is not a clipping ``FlatAdam``.
+        With neither, the one graph captured is the one captured before these modes existed."""
+        from .optim import clip_grad_norm_flat
         from .step import ResidentTrainStep
         self.model, self.static, self.loss_fn, self.optimizer = model, static, loss_fn, optimizer
         snap_p = snap_s = None
@@ -230,7 +243,8 @@ class CapturedStep:
         if "y" not in hb["local"]:
             raise ValueError("the static batch carries no targets")
         try:
-            self.step = ResidentTrainStep(model, hb, loss_fn, one_launch=one_launch, structure=structure)
+            self.step = ResidentTrainStep(model, hb, loss_fn, one_launch=one_launch, structure=structure,
+                                          accumulate=accumulate)
         except RuntimeError as e:
             raise RuntimeError("CapturedStep needs the graph-resident engine (the layered operators size their "
                                "work by tensor shapes, which a static-capacity batch does not carry): " + str(e)) from e
@@ -247,14 +261,27 @@ class CapturedStep:
             except (TypeError, ValueError):
                 pass
 
-        def step():
+        P = self.step.P
+        self.accumulate = bool(accumulate)
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.clip_norm = torch.full((1,), float("nan"), dtype=torch.float32, device=static.device) \
+            if self.max_norm is not None else None
+        zero_after = self.accumulate and optimizer is not None and not getattr(optimizer, "zero_grads", False)
+
+        def step(boundary: bool = True):
             if pre is not None:
                 pre(self.step) if pre_takes_step else pre()      # (DeviceHeteroDataset.gather_next(step))
             self.step.run()
+            if not boundary:
+                return
             if reducer is not None:
                 reducer.reduce(float(static.num_graphs), float(static.num_graphs * reducer.world_size))
+            if self.max_norm is not None:
+                clip_grad_norm_flat(self.step.grads[:P], self.max_norm, self.clip_norm)
             if optimizer is not None:
                 optimizer.step()
+            if zero_after:
+                self.step.grads[:P].zero_()
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -266,6 +293,11 @@ class CapturedStep:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             step()
+        self.micro_graph = self.graph
+        if self.accumulate and (optimizer is not None or reducer is not None or self.max_norm is not None):
+            self.micro_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.micro_graph):     # (recorded, not run: nothing to undo)
+                step(boundary=False)
         self.pred, self.loss, self.score = self.step.pred, self.step.loss, self.step.score
         # the gradient tensors the captured backward writes (a later eager step re-points ``p.grad`` elsewhere)
         self.grads = list(self.step.param_grads)
@@ -281,9 +313,15 @@ class CapturedStep:
                             if isinstance(v, Tensor):
                                 old = snap_s.get(id(p), {}).get(k)
                                 v.copy_(old) if old is not None else v.zero_()
+        if self.accumulate:        # the first micro-batch adds onto zeros, not onto the warm-up's gradients
+            self.step.grads.zero_()
+        if self.clip_norm is not None:
+            self.clip_norm.fill_(float("nan"))
 
-    def replay(self) -> Tensor:
-        self.graph.replay()
+    def replay(self, step_optimizer: bool = True) -> Tensor:
+        """One iteration on the next batch.  ``step_optimizer=False`` (with ``accumulate``): the micro graph --
+        the batch's gradients are added to the flat buffer, nothing else."""
+        (self.graph if step_optimizer else self.micro_graph).replay()
         return self.loss
 
     def bind_grads(self) -> None:

@@ -53,14 +53,18 @@ class ResidentTrainStep:
     kernels read the real per-graph ranges from the device-side segment tables."""
 
     def __init__(self, model, batch, loss_fn: str, target: Optional[Tensor] = None, one_launch: Optional[bool] = None,
-                 structure=None):
+                 structure=None, accumulate: bool = False):
         """``one_launch``: None = take the one-launch step (include/hscn.h: hscn_resident_train_step -- forward, loss
         tail and backward of a graph in one workgroup, nothing exported in between) whenever the graphs fit it,
         else the forward + backward launch pair; False = always the pair; True = insist (raises if unsupported).
         ``structure``: None = every step rebuilds the graphs' CSRs and degree norms in LDS from the COO slices
         (structure_build "per-step"); an ``engine.BatchStructure`` (or "batch" = ``batch.structure``, which
         ``engine.build_structure`` / ``DeviceHeteroDataset(resident_structure=True)`` attach) = the one-launch step
-        loads them (structure_build "dataset-resident": graph structure is epoch-invariant).  Same results."""
+        loads them (structure_build "dataset-resident": graph structure is epoch-invariant).  Same results.
+        ``accumulate``: gradient accumulation (the reference's ``batch_accumulation``, train/train.py:89-95): the
+        step's gradient fold ADDS to ``grads`` (include/hscn.h: the ``*_acc`` entry points -- the same launches), so
+        k runs leave ``((g1 + g2) + ...) + gk`` there, autograd's ``p.grad += new``; ``loss`` is still the loss of the
+        last run.  Whoever steps the optimizer zeroes ``grads`` afterwards (``optim.FlatAdam(zero_grads=True)``)."""
         from .model.hscn import HSCN, _act_name
         if not isinstance(model, HSCN):
             raise TypeError("ResidentTrainStep drives graph_hscn.model.hscn.HSCN")
@@ -87,6 +91,8 @@ class ResidentTrainStep:
             raise TypeError("node features must be float32 (train/train.py:79 casts them) or float16, local and "
                             "virtual alike")
         self._sfx = _engine.storage_suffix(sdt)
+        self.accumulate = bool(accumulate)
+        self._acc = "_acc" if self.accumulate else ""     # (the gradient-producing launch: its accumulating twin)
         self.ei = {k: ei_dict[k].contiguous() for k in (LL, VV, LV)}
         N, F = self.x_local.shape
         V = self.x_virtual.shape[0]
@@ -213,7 +219,7 @@ class ResidentTrainStep:
                     ptr(self.grads), ptr(m.flag), ctypes.byref(self._tail))
         if self.one_launch:
             with_v = self.idle_cus and self.virtual is not None
-            call("hscn_resident_train_step" + self._sfx, ptr(self.x_local), ptr(ei_ll), E_ll, ptr(m.lptr),
+            call("hscn_resident_train_step" + self._acc + self._sfx, ptr(self.x_local), ptr(ei_ll), E_ll, ptr(m.lptr),
                  ptr(m.eptr_ll), N, B, F, H, L, C, self.head_act, self._table, ptr(W1), ptr(b1), ptr(W2), ptr(b2),
                  m.max_n, m.max_ell, ptr(self.target), int(self.kind), ptr(self.pred), ptr(self.score),
                  ptr(self.partials), ptr(self.grads), ptr(self.acts) if with_v else None,
@@ -225,7 +231,7 @@ class ResidentTrainStep:
                  N, B, F, H, L, C, self.head_act, self._table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), m.max_n,
                  m.max_ell, ptr(self.acts), ptr(self.pooled), ptr(self.z), ptr(self.pred), ptr(self.score),
                  ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), ctypes.byref(self._job(None)), st)
-            call("hscn_resident_bwd_with_virtual" + self._sfx, *bwd_args, ctypes.byref(self._job(self.virtual)), st)
+            call("hscn_resident_bwd_with_virtual" + self._acc + self._sfx, *bwd_args, ctypes.byref(self._job(self.virtual)), st)
         else:
             cv = int(bool(self.model.compute_virtual))
             call("hscn_resident_fwd" + self._sfx, ptr(self.x_local), ptr(self.x_virtual), ptr(ei_ll), E_ll, ptr(self.ei[VV]),
@@ -234,7 +240,7 @@ class ResidentTrainStep:
                  self._table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), m.max_n, m.max_v, m.max_ell, m.max_evv, cv,
                  ptr(self.acts), ptr(self.pooled), ptr(self.z), ptr(self.pred), ptr(self.score),
                  ptr(self.virtual) if cv else None, ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), st)
-            call("hscn_resident_bwd" + self._sfx, *bwd_args, st)
+            call("hscn_resident_bwd" + self._acc + self._sfx, *bwd_args, st)
         return self.loss
 
     def check(self) -> None:

@@ -7,6 +7,13 @@ epochs, early stopping on the validation loss -- but the training split lives in
 the captured forward + loss + backward + optimizer step", and the host reads nothing back until the epoch ends.
 The last, shorter batch of an epoch (the reference's loader keeps it, loader/hetero_data.py:96-104) runs through
 the eager path on a host-collated batch with the same optimizer, so every graph is visited once per epoch.
+
+``OptimConfig.batch_accumulation`` (k) and ``clip_grad_norm`` are honoured as train/train.py:89-95 honours them: the
+optimizer steps on iterations with ``(it + 1) % k == 0 or it + 1 == num_batches`` (``optimizer_steps_at``) on the
+gradients summed since the last step, clipped to norm 1 first.  With k > 1 two graphs are captured over the same
+buffers: the micro-batch iteration (gather, then the step ADDING its gradients to the flat buffer) and the boundary
+iteration (the same, then all-reduce, clip, optimizer step, gradients zeroed); with ``optim.FlatAdam`` the clip and
+the zeroing ride on its one launch, so no iteration issues a launch it did not issue before.
 """
 from __future__ import annotations
 
@@ -19,13 +26,22 @@ from ..config.config import OPTIM_DICT
 from ..data import HeteroBatch, HeteroData
 from ..loader.device_dataset import DeviceHeteroDataset
 from ..loss import criterion
+from ..optim import clip_grad_norm_flat
 from ..replay import CapturedStep
 from .train import eval_epoch, is_eval_epoch
+
+CLIP_MAX_NORM = 1.0     # train/train.py:92 (the reference's nn.utils.clip_grad_norm_(params, 1.0))
+
+
+def optimizer_steps_at(it: int, num_batches: int, batch_accumulation: int) -> bool:
+    """Whether iteration ``it`` (0-based) of an epoch of ``num_batches`` batches steps the optimizer: every
+    ``batch_accumulation``-th batch and always the last one (train/train.py:89 -- ``train.train_epoch``)."""
+    return (it + 1) % batch_accumulation == 0 or it + 1 == num_batches
 
 
 def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroData], eval_loaders: Sequence, model,
                  batch_size: int, metric_fn: Optional[Callable] = None, seed: int = 0, reducer=None,
-                 flat_optimizer: bool = True) -> List[tuple]:
+                 flat_optimizer: bool = True, epoch_orders: Optional[list] = None) -> List[tuple]:
     """Returns ``[(mean train loss, train metric), ...]`` per epoch, like ``train.train``.  ``eval_loaders`` =
     ``[validation, test]`` loaders of host batches (evaluated with ``train.eval_epoch``).
 
@@ -34,17 +50,19 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
     ``reducer`` (built with ``equal_weights=True`` it averages with no scaling launch).
     The iteration stays ONE replay: forward + loss + backward, the RCCL all-reduce of the flat gradient buffer where
     the backward left it, the optimizer step -- all captured (an optimizer without a capturable step is stepped, and
-    the collective issued, outside the graph).  The eager tail batch is reduced the same way."""
+    the collective issued, outside the graph).  The eager tail batch is reduced the same way.
+
+    ``epoch_orders``: a list that receives every epoch's permutation of ``train_graphs`` as a host tensor (one
+    read-back per epoch, only when a list is passed): batch i of the epoch is ``order[i * B:(i + 1) * B]``, the
+    order ``train.train_epoch`` has to see to take the same steps."""
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("fit_resident runs on the MI355X HIP path: move the model to 'cuda'")
-    # what the captured iteration does not implement must not be dropped silently (train/train.py:89-95 honours both)
-    if int(getattr(optim_cfg, "batch_accumulation", 1) or 1) != 1:
-        raise NotImplementedError("fit_resident steps the optimizer every batch: batch_accumulation != 1 needs "
-                                  "train.train (the reference-shaped loop)")
-    if getattr(optim_cfg, "clip_grad_norm", False):
-        raise NotImplementedError("fit_resident has no gradient clipping between the captured backward and the "
-                                  "optimizer step: use train.train for clip_grad_norm")
+    k = int(getattr(optim_cfg, "batch_accumulation", 1) or 1)
+    if k < 1:
+        raise ValueError("batch_accumulation must be at least 1")
+    clip = bool(getattr(optim_cfg, "clip_grad_norm", False))
+    acc = k > 1
     G, B = len(train_graphs), int(batch_size)
     if G < B:
         raise ValueError("fewer training graphs than one batch")
@@ -54,7 +72,8 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
     flat = flat_optimizer and optim_cfg.optim_type in ("adam", "adamW")   # optim.FlatAdam: the update as ONE launch
     if flat:
         from ..optim import FlatAdam
-        optimizer = lambda st: FlatAdam.from_config(optim_cfg.optim_type, st.param_grads, st.grads, **kw)  # noqa: E731
+        fkw = dict(kw, max_norm=CLIP_MAX_NORM if clip else None, zero_grads=acc)    # clip + zeroing: in its launch
+        optimizer = lambda st: FlatAdam.from_config(optim_cfg.optim_type, st.param_grads, st.grads, **fkw)  # noqa: E731
         capturable = True
     else:
         try:
@@ -69,10 +88,29 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
     ds.new_epoch(gen)
     # the gather of the next permutation slice is captured in front of the step: a replay = next batch + iteration
     step = CapturedStep(model, ds.static, training_cfg.loss_fn, optimizer=optimizer if in_graph else None,
-                        pre=ds.gather_next, reducer=reducer if in_graph else None)
+                        pre=ds.gather_next, reducer=reducer if in_graph else None, accumulate=acc,
+                        max_norm=CLIP_MAX_NORM if clip and in_graph and not flat else None)
     if flat:
         optimizer = step.optimizer
+    flat_grads = step.step.grads[:step.step.P]         # every parameter gradient (the loss column excluded)
+    clip_norm = torch.zeros(1, dtype=torch.float32, device=dev) if clip and not in_graph else None
+
+    def boundary_outside_graph(weight: float):
+        """What the graph does not hold at a stepping iteration (a non-capturable optimizer; the eager tail)."""
+        if reducer is not None:
+            reducer.reduce(weight, weight * reducer.world_size)
+        if flat:
+            optimizer.step()                   # (clip and zeroing in the same launch)
+            return
+        if clip:
+            clip_grad_norm_flat(flat_grads, CLIP_MAX_NORM, clip_norm if clip_norm is not None else step.clip_norm)
+        optimizer.step()
+        if acc:
+            flat_grads.zero_()
+
     steps, tail = G // B, G % B
+    num_batches = steps + (1 if tail else 0)
+    legacy = not acc and not clip              # (the iteration exactly as before either setting existed)
     C = ds.C
     loss_log = torch.zeros(steps + (1 if tail else 0), dtype=torch.float32, device=dev)
     scores = torch.zeros(G, C, dtype=torch.float32, device=dev) if metric_fn else None
@@ -82,14 +120,22 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
         start = time.time()
         model.train()
         perm = ds.new_epoch(gen)               # permutation + batch counter on the device
+        if epoch_orders is not None:
+            epoch_orders.append(perm.cpu())
         if not in_graph:
             step.bind_grads()                  # (the eager tail of the previous epoch re-pointed p.grad)
         for i in range(steps):
-            step.replay()
-            if reducer is not None and not in_graph:
-                reducer.reduce(float(B), float(B * reducer.world_size))
-            if not in_graph:
-                optimizer.step()
+            if legacy:
+                step.replay()
+                if reducer is not None and not in_graph:
+                    reducer.reduce(float(B), float(B * reducer.world_size))
+                if not in_graph:
+                    optimizer.step()
+            else:
+                stepping = optimizer_steps_at(i, num_batches, k)
+                step.replay(step_optimizer=stepping)
+                if stepping and not in_graph:
+                    boundary_outside_graph(float(B))
             loss_log[i].copy_(step.loss)
             if metric_fn:
                 scores[i * B:(i + 1) * B].copy_(step.score)
@@ -100,9 +146,24 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
             pred = model(hb.x_dict, hb.edge_index_dict, hb)
             loss, score = criterion(training_cfg.loss_fn, pred, hb["local"].y)
             loss.backward()
-            if reducer is not None:
-                reducer.reduce(float(tail), float(tail * reducer.world_size))
-            optimizer.step_from_autograd() if flat else optimizer.step()
+            if legacy:
+                if reducer is not None:
+                    reducer.reduce(float(tail), float(tail * reducer.world_size))
+                optimizer.step_from_autograd() if flat else optimizer.step()
+            elif flat and reducer is None:
+                optimizer.step_from_autograd(accumulate=acc)     # (p.grad added to the window's sum; clip, zero)
+            else:
+                # the last batch steps (optimizer_steps_at); the window's earlier micro-batches are in the flat
+                # buffer: the tail's p.grad is added to them there, and p.grad points at the sum again
+                with torch.no_grad():
+                    for p, g in step.grads:
+                        if p.grad is None:
+                            if not acc:
+                                g.zero_()
+                        elif p.grad.data_ptr() != g.data_ptr():
+                            g.add_(p.grad) if acc else g.copy_(p.grad)
+                step.bind_grads()
+                boundary_outside_graph(float(tail))
             loss_log[steps].copy_(loss.detach())
             if metric_fn:
                 scores[steps * B:].copy_(score.detach())

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HSCN_ABI_VERSION 18
+#define HSCN_ABI_VERSION 19
 
 #define HSCN_E_BADARG (-1)   /* null pointer, negative size, unsupported width */
 #define HSCN_E_WORKSPACE (-2) /* workspace too small */
@@ -617,6 +617,60 @@ int hscn_resident_bwd_with_virtual_f16(const hscn_half* x_local, const int64_t* 
                                        const hscn_loss_tail* tail, const hscn_virtual_job* job, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * ABI 19: gradient accumulation over micro-batches (reference train/train.py:89-95: `batch_accumulation`, the
+ * optimizer steps every k-th batch on the SUM of their gradients).  The *_acc entry points are the launches of
+ * hscn_resident_bwd, hscn_resident_bwd_with_virtual, hscn_resident_train_step and their _f16 twins, argument for
+ * argument and launch for launch, except that the final fold ADDS each parameter column to `grads`:
+ *   grads[p] = grads[p] + sum_g partials[g][p]   (p < P: the sum formed exactly as in the plain entry point, added
+ *                                                  last -- autograd's `p.grad += new`, rounding for rounding)
+ * The loss column grads[P] (with a loss tail) is still overwritten: it is the loss of THIS micro-batch.  The caller
+ * zeroes `grads` where the reference calls optimizer.zero_grad() (hscn_adam_step_ex can do it in its launch).
+ * ------------------------------------------------------------------------- */
+int hscn_resident_bwd_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                          const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
+                          const void* const* W_ll_host /* L */, const float* W1, const float* W2, const float* acts,
+                          const float* pooled, const float* z, const float* g_pred, const float* g_scale,
+                          const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n,
+                          int max_ell, float* partials /*[B][P]*/, float* grads /*[P]*/, int32_t* flag,
+                          const hscn_loss_tail* tail, void* stream);
+int hscn_resident_bwd_with_virtual_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                                       const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
+                                       int head_act, const void* const* W_ll_host, const float* W1, const float* W2,
+                                       const float* acts, const float* pooled, const float* z, const float* g_pred,
+                                       const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
+                                       const float* dinv, int max_n, int max_ell, float* partials, float* grads,
+                                       int32_t* flag, const hscn_loss_tail* tail, const hscn_virtual_job* job,
+                                       void* stream);
+int hscn_resident_train_step_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                                 const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
+                                 const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
+                                 const float* b2, int max_n, int max_ell, const float* target, int loss_kind, float* pred,
+                                 float* score, float* partials, float* grads, float* acts, uint32_t* sync, int32_t* flag,
+                                 const hscn_virtual_job* job, const hscn_structure* structure, void* stream);
+int hscn_resident_bwd_acc_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                              const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
+                              const void* const* W_ll_host /* L */, const float* W1, const float* W2,
+                              const hscn_half* acts, const float* pooled, const float* z, const float* g_pred,
+                              const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
+                              const float* dinv, int max_n, int max_ell, float* partials /*[B][P]*/,
+                              float* grads /*[P]*/, int32_t* flag, const hscn_loss_tail* tail, void* stream);
+int hscn_resident_bwd_with_virtual_acc_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll,
+                                           const int32_t* lptr, const int32_t* eptr_ll, int64_t N, int64_t B, int F,
+                                           int H, int L, int C, int head_act, const void* const* W_ll_host,
+                                           const float* W1, const float* W2, const hscn_half* acts, const float* pooled,
+                                           const float* z, const float* g_pred, const float* g_scale,
+                                           const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv,
+                                           int max_n, int max_ell, float* partials, float* grads, int32_t* flag,
+                                           const hscn_loss_tail* tail, const hscn_virtual_job* job, void* stream);
+int hscn_resident_train_step_acc_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                                     const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
+                                     int head_act, const void* const* layer_params_host, const float* W1, const float* b1,
+                                     const float* W2, const float* b2, int max_n, int max_ell, const float* target,
+                                     int loss_kind, float* pred, float* score, float* partials, float* grads,
+                                     hscn_half* acts, uint32_t* sync, int32_t* flag, const hscn_virtual_job* job,
+                                     const hscn_structure* structure, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * a2/a4/a6  stage A, graph-resident engine: the body of the reference's clustering loop
  * (train/train_clustering.py:37-47) for a batch of RAW graphs in one launch --
  * gcn_norm(add_self_loops=True) folded into the CSR walk, SCN.forward for
@@ -780,6 +834,24 @@ int hscn_scn_resident_bwd_f16(const hscn_half* x, const int64_t* edge_index, int
 int hscn_adam_step(float* const* params_host, const int32_t* seg_off_host, int nseg, const float* grads,
                    float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
                    const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, int decoupled, void* stream);
+
+/* ABI 19: hscn_adam_step with, in the same launch, the two optimizer-side settings of the reference's loop
+ * (train/train.py:89-95):
+ *   max_norm > 0: torch.nn.utils.clip_grad_norm_(params, max_norm) over the flat gradient first -- the 2-norm as a
+ *     sum of g^2 in double in a fixed order (bitwise reproducible), then torch's formulas from the norm on:
+ *     norm = (float)sqrt(sum), coef = min(reciprocal(norm + 1e-6f) * max_norm, 1), g = g * coef for every element
+ *     (coef == 1 included; a non-finite norm propagates as in torch).  The clipped gradient is written back to
+ *     `grads` (what p.grad holds after torch's clip) and, if norm_out != NULL, the pre-clip norm to norm_out[0]
+ *     (clip_grad_norm_'s return value).  max_norm == 0: no clip.
+ *   zero_grads != 0: grads[0 .. P) = 0 after the update (optimizer.zero_grad(): the next micro-batch accumulates
+ *     onto zeros).
+ * hscn_clip_grad_norm_flat: the same norm and in-place scaling as a launch of its own (one workgroup), for
+ * optimizers that are not hscn_adam_step; max_norm > 0. */
+int hscn_adam_step_ex(float* const* params_host, const int32_t* seg_off_host, int nseg, float* grads,
+                      float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
+                      const double* lr_dev, double beta1, double beta2, double eps, double weight_decay,
+                      int decoupled, float max_norm, float* norm_out /*[1] or NULL*/, int zero_grads, void* stream);
+int hscn_clip_grad_norm_flat(float* grads, int64_t P, float max_norm, float* norm_out /*[1] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Normalisation layers of the MPNN baseline: torch.nn.LayerNorm(H) / torch.nn.BatchNorm1d(H) on [N, H] activations,
