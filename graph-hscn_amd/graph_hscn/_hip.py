@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("HSCN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libhscn.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 ACT = {"identity": 0, "relu": 1, "elu": 2, "tanh": 3}
 
 P = c_void_p
@@ -116,7 +116,15 @@ _SIGNATURES = {
     "hscn_allreduce_oneshot_flag_bytes": (c_size_t, [c_int64, c_int]),
     "hscn_allreduce_oneshot_chunks": (c_int64, [c_int64]),
     "hscn_allreduce_oneshot": (c_int, [P, c_int64, P, P, P, P, c_int, c_int, c_float, ctypes.c_uint32, P]),
+    # ABI 20: the MPNN baseline's one-launch step and forward (include/hscn.h)
+    "hscn_mpnn_supported": (c_int, [c_int] * 6),
+    "hscn_mpnn_param_count": (c_int64, [c_int] * 4),
+    "hscn_mpnn_train_step": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int,
+                                     c_int, P, c_int, c_float, P, P, P, P, P, c_float, c_uint64, P, P]),
+    "hscn_mpnn_forward": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int,
+                                  c_int, P, c_int, c_float, P, P, P, P, P, P]),
 }
+_SIGNATURES["hscn_mpnn_train_step_acc"] = _SIGNATURES["hscn_mpnn_train_step"]
 # IEEE-half storage twins (include/hscn.h: hscn_resident_*_f16): same argument lists
 for _n in ("hscn_resident_fwd", "hscn_resident_bwd", "hscn_resident_fwd_with_virtual", "hscn_resident_bwd_with_virtual",
            "hscn_scn_resident_fwd", "hscn_scn_resident_bwd", "hscn_resident_train_step",

@@ -179,3 +179,117 @@ class DeviceHeteroDataset:
         """Synchronising validity check of the gathers issued so far."""
         if int(self.flag.item()) & 8:
             raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")
+
+
+class StaticGraphBatch:
+    """Fixed-capacity device buffers of a homogeneous ``Batch`` (``.batch`` is the object to hand to
+    ``step.MPNNResidentTrainStep``): ``x`` [ncap, F], ``edge_index`` [2, ecap], ``batch`` [ncap], ``ptr`` / ``ptr32`` /
+    ``eptr32`` [B + 1], ``y`` [B, C], and the per-graph maxima that size the kernel's LDS.  Valid inside the per-graph
+    ranges of ``ptr32`` / ``eptr32`` only; the tail of every buffer is stale data of earlier, larger batches."""
+
+    def __init__(self, B: int, device, ncap: int, ecap: int, max_nodes: int, max_edges: int, F: int, C: Optional[int]):
+        from ..data import Batch
+        dev = torch.device(device)
+        self.device, self.num_graphs = dev, int(B)
+        self.N, self.E = max(int(ncap), 1), max(int(ecap), 1)
+        i64 = dict(dtype=torch.int64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        b = Batch(x=torch.zeros(self.N, F, dtype=torch.float32, device=dev),
+                  edge_index=torch.zeros(2, self.E, **i64), num_nodes=self.N)
+        b.y = torch.zeros(B, C, dtype=torch.float32, device=dev) if C else None
+        b.batch = torch.zeros(self.N, **i64)
+        b.ptr = torch.zeros(B + 1, **i64)
+        b.ptr32 = torch.zeros(B + 1, **i32)
+        b.eptr32 = torch.zeros(B + 1, **i32)
+        b.num_graphs = int(B)
+        b.max_nodes, b.max_edges = int(max_nodes), int(max_edges)
+        self.batch = b
+        # the (empty) virtual node type and vv / lv relations of the gather's output
+        self._v = {"x": torch.zeros(1, F, dtype=torch.float32, device=dev), "batch": torch.zeros(1, **i64),
+                   "ptr": torch.zeros(B + 1, **i64), "ptr32": torch.zeros(B + 1, **i32),
+                   "ei": [torch.zeros(2, 1, **i64) for _ in range(2)], "eptr32": [torch.zeros(B + 1, **i32) for _ in range(2)]}
+
+
+class DeviceGraphDataset:
+    """The homogeneous twin of ``DeviceHeteroDataset`` for the MPNN baseline: a list of ``Data`` graphs resident in
+    HBM, and ``gather(ids)`` / ``gather_next()`` writing the batch of graphs ``ids`` into the fixed-capacity buffers of
+    a ``StaticGraphBatch`` in ONE launch -- bit for bit what ``Batch.from_data_list`` builds (features cast to float32,
+    as train/train.py:79 casts them).  It is ``hscn_collate_gather`` over a hetero dataset whose virtual node type
+    has no nodes and whose vv / lv relations have no edges: every graph's virtual and vv / lv ranges are empty, so the
+    blocks of those parts copy nothing and write empty segment tables."""
+
+    def __init__(self, graphs: Sequence, device, batch_size: int):
+        from ..data import Batch
+        if not graphs:
+            raise ValueError("empty dataset")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.num_graphs = G = len(graphs)
+        self.batch_size = B = int(batch_size)
+        whole = Batch.from_data_list(graphs)                  # once, on the host: global ids + per-graph ranges
+        nptr = whole.ptr
+        eptr = whole.eptr32.to(torch.int64)
+        self.F = int(whole.x.size(1))
+        y = getattr(whole, "y", None)
+        self.C = None if y is None else int(y.size(1))
+        dev = self.device
+        sizes, esizes = nptr[1:] - nptr[:-1], eptr[1:] - eptr[:-1]
+        owner = torch.repeat_interleave(torch.arange(G), esizes)
+        ei = whole.edge_index
+        zeros_g = torch.zeros(G + 1, dtype=torch.int64)
+        self._t = {"x": whole.x.float().contiguous().to(dev), "xv": torch.zeros(1, self.F, device=dev),
+                   "y": None if y is None else y.float().contiguous().to(dev), "nptr": nptr.to(dev),
+                   "vptr": zeros_g.to(dev), "src0": (ei[0] - nptr[owner]).to(torch.int32).contiguous().to(dev),
+                   "dst0": (ei[1] - nptr[owner]).to(torch.int32).contiguous().to(dev), "eptr0": eptr.contiguous().to(dev),
+                   "none": torch.zeros(1, dtype=torch.int32, device=dev), "eptr_none": zeros_g.to(dev)}
+        self.static = StaticGraphBatch(B, dev, _top_sum(sizes, B), _top_sum(esizes, B), int(sizes.max()),
+                                       int(esizes.max()) if esizes.numel() else 0, self.F, self.C)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._perm: Optional[Tensor] = None
+        self._cursor: Optional[Tensor] = None
+        t, p = self._t, _hip.ptr
+        self._ds = _Dataset(p(t["x"]), p(t["xv"]), p(t["y"]), p(t["nptr"]), p(t["vptr"]),
+                            (ctypes.c_void_p * 3)(p(t["src0"]), p(t["none"]), p(t["none"])),
+                            (ctypes.c_void_p * 3)(p(t["dst0"]), p(t["none"]), p(t["none"])),
+                            (ctypes.c_void_p * 3)(p(t["eptr0"]), p(t["eptr_none"]), p(t["eptr_none"])),
+                            G, self.F, self.C or 0)
+        st, b, v = self.static, self.static.batch, self.static._v
+        self._out = _BatchOut(p(b.x), p(v["x"]), p(b.y) if self.C else None, p(b.ptr), p(v["ptr"]), p(b.ptr32),
+                              p(v["ptr32"]), p(b.batch), p(v["batch"]),
+                              (ctypes.c_void_p * 3)(p(b.edge_index), p(v["ei"][0]), p(v["ei"][1])),
+                              (ctypes.c_void_p * 3)(p(b.eptr32), p(v["eptr32"][0]), p(v["eptr32"][1])),
+                              st.N, 0, (ctypes.c_int64 * 3)(st.E, 1, 1))
+
+    def gather(self, ids: Tensor):
+        """Make ``self.static`` hold the batch of graphs ``ids`` (int64 ``[batch_size]`` on the device).  Asynchronous
+        on the current stream, capturable; returns ``self.static.batch``."""
+        if ids.dtype != torch.int64 or ids.device != self.device or ids.numel() != self.batch_size:
+            raise ValueError(f"ids must be int64 [{self.batch_size}] on {self.device}")
+        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(ids.contiguous()), self.batch_size,
+                  ctypes.byref(self._out), _hip.ptr(self.flag), None, None, _hip.stream())
+        return self.static.batch
+
+    def new_epoch(self, generator: Optional[torch.Generator] = None) -> Tensor:
+        """Draw the epoch's permutation on the device and rewind the batch counter (as ``DeviceHeteroDataset``)."""
+        if self._perm is None:
+            self._perm_buf = torch.zeros(self.num_graphs + self.batch_size, dtype=torch.int64, device=self.device)
+            self._perm = self._perm_buf[: self.num_graphs]
+            self._cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
+        torch.randperm(self.num_graphs, device=self.device, generator=generator, out=self._perm)
+        self._cursor.zero_()
+        return self._perm
+
+    def gather_next(self):
+        """Gather the next slice of the epoch's permutation and advance the device-side counter: no host argument
+        changes from step to step, so it can be captured in front of the training step."""
+        if self._perm is None:
+            raise RuntimeError("call new_epoch() first")
+        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(self._perm), self.batch_size,
+                  ctypes.byref(self._out), _hip.ptr(self.flag), _hip.ptr(self._cursor), None, _hip.stream())
+        return self.static.batch
+
+    def check(self) -> None:
+        """Synchronising validity check of the gathers issued so far."""
+        if int(self.flag.item()) & 8:
+            raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")

@@ -18,7 +18,9 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from .. import _hip
 from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig
+from ..nn.conv import GCNConv
 from ..nn import functional as Fh
 from ..nn.norm import BatchNorm1d, LayerNorm
 from ..nn.pool import global_mean_pool
@@ -44,8 +46,94 @@ class MPNN(nn.Module):
         self.activation = activation
         self.dropout = dropout
         self.dropout_seed: Optional[int] = None     # tests pin the mask; None = torch.initial_seed() + call counter
+        # execution engine of the forward: "layered" (per-operator kernels, the default), "auto" / "resident" (with
+        # gradients off, a qualifying Batch runs as ONE launch, include/hscn.h: hscn_mpnn_forward; "resident" raises
+        # with the reason when the model or batch does not qualify).  Training with gradients on stays layered; the
+        # fused training step is step.MPNNResidentTrainStep (autograd passes through the layered kernels).
+        self.engine = "layered"
+        self.last_engine: Optional[str] = None
+
+    def resident_reason(self, batch=None, need_grad: bool = False) -> Optional[str]:
+        """Why this model (and ``batch``, if given) cannot take the one-launch MPNN kernels, or None when it can."""
+        name = getattr(self.activation, "hscn_name", None)
+        if name not in ("relu", "elu", "identity", "tanh"):
+            return f"activation {name!r} (relu, elu, identity and tanh are supported)"
+        if self.use_batch_norm or self.use_layer_norm:
+            return "normalisation layers (use_batch_norm / use_layer_norm) are not part of the fused kernel"
+        for c in self.conv_layers:
+            if not isinstance(c, GCNConv) or not c.add_self_loops or c.bias is None:
+                return f"convolution {type(c).__name__} (only GCNConv(add_self_loops=True) with bias)"
+            if isinstance(c.lin.weight, nn.parameter.UninitializedParameter):
+                return "lazily sized convolution weights are not materialised yet"
+        L = self.num_layers
+        if L < 2 or len(self.conv_layers) != L:
+            return "fewer than two convolutions"
+        F, H, C = self.resident_dims()
+        if batch is None:
+            ok = _hip.lib().hscn_mpnn_supported(F, H, L, C, 0, 0)
+            return None if ok else f"widths F={F}, H={H}, C={C}, L={L} outside the kernel's envelope (H in {{16, 32}}, F <= H, C <= min(H, 16), L <= 8)"
+        for attr in ("ptr32", "eptr32", "max_nodes", "max_edges"):
+            if not hasattr(batch, attr):
+                return f"the batch carries no {attr} (graph_hscn.data.Batch.from_data_list builds it)"
+        y = getattr(batch, "y", None)
+        if y is not None and (y.dim() != 2 or y.size(1) != C):
+            return "class-index (multiclass) targets: the fused loss row takes [B, C] multilabel / regression targets"
+        x = batch.x
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != F:
+            return "node features must be a float32 [N, F] tensor on the HIP device"
+        if not _hip.lib().hscn_mpnn_supported(F, H, L, C, int(batch.max_nodes), int(batch.max_edges)):
+            return (f"widths F={F}, H={H}, C={C}, L={L} or the largest graph ({batch.max_nodes} nodes, "
+                    f"{batch.max_edges} edges) outside the kernel's envelope (160 KB of LDS)")
+        return None
+
+    def supported(self, batch=None) -> bool:
+        """Whether the one-launch MPNN kernels take this model (and ``batch``)."""
+        return self.resident_reason(batch) is None
+
+    def resident_dims(self):
+        first, last = self.conv_layers[0], self.conv_layers[-1]
+        return int(first.lin.weight.shape[1]), int(first.lin.weight.shape[0]), int(last.lin.weight.shape[0])
+
+    def resident_params(self):
+        """Parameters in the order the fused kernels take them: {W_l, b_l} per convolution (= ``parameters()``)."""
+        out = []
+        for c in self.conv_layers:
+            out += [c.lin.weight, c.bias]
+        return out
+
+    def _forward_resident(self, batch) -> Tensor:
+        from .. import engine as _engine
+        x = batch.x.contiguous()
+        ei = batch.edge_index.contiguous()
+        dev = x.device
+        F, H, C = self.resident_dims()
+        B = int(batch.num_graphs)
+        params = [p.detach().contiguous() for p in self.resident_params()]
+        table = _engine._ptr_table(params)
+        ptr32 = batch.ptr32 if batch.ptr32.device == dev else batch.ptr32.to(dev)
+        eptr32 = batch.eptr32 if batch.eptr32.device == dev else batch.eptr32.to(dev)
+        pred = torch.empty(B, C, dtype=torch.float32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        _hip.call("hscn_mpnn_forward", _hip.ptr(x), _hip.ptr(ei), ei.size(1), _hip.ptr(ptr32), _hip.ptr(eptr32),
+                  x.size(0), B, F, H, self.num_layers, C, _hip.ACT[self.activation.hscn_name], table,
+                  int(batch.max_nodes), int(batch.max_edges), None, 0, 0.0, _hip.ptr(pred), None, None, None,
+                  _hip.ptr(flag), _hip.stream())
+        self._resident_flag = flag     # nonzero: an edge outside its graph / a graph beyond the batch's maxima
+        return pred
 
     def forward(self, batch) -> Tensor:
+        if self.engine not in ("layered", "auto", "resident"):
+            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if self.engine != "layered" and not torch.is_grad_enabled():
+            reason = self.resident_reason(batch)
+            if reason is None and self.training and self.dropout > 0:
+                reason = "dropout in training mode (the forward-only launch is for evaluation)"
+            if reason is None:
+                self.last_engine = "resident"
+                return self._forward_resident(batch)
+            if self.engine == "resident":
+                raise RuntimeError(f"engine='resident' requested but the model / batch does not qualify: {reason}")
+        self.last_engine = "layered"
         x, edge_index, batch_vec = batch.x, batch.edge_index, batch.batch   # mpnn.py:50
         act_name = getattr(self.activation, "hscn_name", None)
         for i in range(self.num_layers - 1):

@@ -240,14 +240,22 @@ class CapturedStep:
                 snap_s = {id(p): {k: v.clone() for k, v in st.items() if isinstance(v, Tensor)}
                           for p, st in optimizer.state.items()}
         hb = static.batch
-        if "y" not in hb["local"]:
-            raise ValueError("the static batch carries no targets")
-        try:
-            self.step = ResidentTrainStep(model, hb, loss_fn, one_launch=one_launch, structure=structure,
-                                          accumulate=accumulate)
-        except RuntimeError as e:
-            raise RuntimeError("CapturedStep needs the graph-resident engine (the layered operators size their "
-                               "work by tensor shapes, which a static-capacity batch does not carry): " + str(e)) from e
+        from .model.mpnn import MPNN
+        if isinstance(model, MPNN):       # the MPNN baseline: ``loader.device_dataset.StaticGraphBatch``, one launch
+            from .step import MPNNResidentTrainStep
+            if getattr(hb, "y", None) is None:
+                raise ValueError("the static batch carries no targets")
+            self.step = MPNNResidentTrainStep(model, hb, loss_fn, accumulate=accumulate)
+        else:
+            if "y" not in hb["local"]:
+                raise ValueError("the static batch carries no targets")
+            try:
+                self.step = ResidentTrainStep(model, hb, loss_fn, one_launch=one_launch, structure=structure,
+                                              accumulate=accumulate)
+            except RuntimeError as e:
+                raise RuntimeError("CapturedStep needs the graph-resident engine (the layered operators size their "
+                                   "work by tensor shapes, which a static-capacity batch does not carry): "
+                                   + str(e)) from e
         self.step.bind_grads()
         model.last_engine = "resident"
         if make_flat:          # built here: it needs the step's flat gradient buffer

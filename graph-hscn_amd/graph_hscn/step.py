@@ -544,3 +544,109 @@ class ScnEpochRunner:
     def check(self) -> None:
         self.meta.check()
         self.optimizer.check()
+
+
+def _mpnn_default_seed0() -> int:
+    """``MPNN.dropout_seed = None``: one seed derived from ``torch.initial_seed()`` (as nn.functional.dropout derives
+    its default), taken once per step object; the device step counter moves it on from there."""
+    return (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
+
+
+class MPNNResidentTrainStep:
+    """``for p: p.grad = None; pred = model(batch); loss, score = criterion(loss_fn, pred, batch.y); loss.backward()``
+    for the MPNN baseline (model/mpnn.py with GCNConv) as ONE launch plus the gradient fold (include/hscn.h:
+    hscn_mpnn_train_step), on buffers allocated once -- ``ResidentTrainStep``'s outward contract.
+
+    Outputs refreshed by ``run()``: ``pred`` [B,C], ``score`` [B,C] (sigmoid), ``loss`` (0-dim), ``grads`` (flat, the
+    parameter gradients in ``model.parameters()`` order, then the loss).  ``bind_grads()`` points every ``p.grad`` at
+    its slice.  ``accumulate``: the fold ADDS to ``grads`` (``hscn_mpnn_train_step_acc``); ``loss`` is the last run's.
+
+    Dropout (``model.training`` and ``model.dropout > 0``): hidden layer i of the t-th ``run()`` (t = ``step_word``,
+    a device counter the fold advances) draws the mask nn.functional.dropout draws with seed ``seed0 + (L-1) t + i``;
+    ``seed0`` = ``model.dropout_seed``, or derived once from ``torch.initial_seed()`` when that is None.  A captured
+    step therefore draws new masks on every replay.
+
+    The batch may be a static fixed-capacity batch: tensor shapes are capacities then, the kernel reads the real
+    per-graph ranges from ``ptr32`` / ``eptr32``."""
+
+    def __init__(self, model, batch, loss_fn: str, target: Optional[Tensor] = None, accumulate: bool = False,
+                 seed0: Optional[int] = None, step_word: Optional[Tensor] = None):
+        from .model.mpnn import MPNN
+        if not isinstance(model, MPNN):
+            raise TypeError("MPNNResidentTrainStep drives graph_hscn.model.mpnn.MPNN")
+        reason = model.resident_reason(batch)
+        if reason is not None:
+            raise RuntimeError(f"the one-launch MPNN step does not take this model / batch: {reason}")
+        dev = batch.x.device
+        self.model, self.batch, self.loss_fn = model, batch, loss_fn
+        F, H, C = model.resident_dims()
+        L = model.num_layers
+        self.x = batch.x.contiguous()
+        self.ei = batch.edge_index.contiguous()
+        self.ptr32 = batch.ptr32 if batch.ptr32.device == dev else batch.ptr32.to(dev)
+        self.eptr32 = batch.eptr32 if batch.eptr32.device == dev else batch.eptr32.to(dev)
+        self.max_n, self.max_e = int(batch.max_nodes), int(batch.max_edges)
+        B = int(batch.num_graphs)
+        N = int(self.x.size(0))
+        self.dims = (N, F, H, L, C, B)
+        y = target if target is not None else batch.y
+        if y.dtype != torch.float32 or not y.is_contiguous() or y.device != dev:
+            raise TypeError("targets must be a contiguous float32 tensor on the batch's device")
+        self.kind = _loss_kind(loss_fn, (B, C), y)
+        self.target = y
+        self.act = _hip.ACT[model.activation.hscn_name]
+        self.accumulate = bool(accumulate)
+        self._params = [p.contiguous() for p in model.resident_params()]
+        self._table = _engine._ptr_table(self._params)
+        self.p = float(model.dropout) if (model.training and model.dropout > 0) else 0.0
+        if seed0 is None:
+            seed0 = model.dropout_seed if model.dropout_seed is not None else _mpnn_default_seed0()
+        self.seed0 = int(seed0) & 0xFFFFFFFFFFFFFFFF
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.pred = torch.empty(B, C, **f32)
+        self.score = torch.empty(B, C, **f32)
+        P = int(_hip.lib().hscn_mpnn_param_count(F, H, L, C))
+        self.P = P
+        self.partials = torch.empty(B, P + 1, **f32)
+        self.grads = torch.zeros(P + 1, **f32)
+        self.loss = self.grads[P:P + 1].view(())
+        # the step counter (uint32 on the device; shared with whoever else reads it, e.g. a captured batch gather)
+        self.step_word = step_word if step_word is not None else torch.zeros(1, dtype=torch.int32, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.inv_count = 1.0 / float(B * C)
+        views: List[Tuple[Tensor, Tensor]] = []
+        off = 0
+        for p in model.resident_params():
+            views.append((p, self.grads[off: off + p.numel()].view_as(p)))
+            off += p.numel()
+        assert off == P
+        self.param_grads = views
+
+    @property
+    def advances_sync(self) -> bool:
+        """Every ``run()`` adds one to ``step_word`` on the device."""
+        return True
+
+    def bind_grads(self) -> None:
+        has = {id(p) for p, _ in self.param_grads}
+        for p in self.model.parameters():
+            if id(p) not in has:
+                p.grad = None
+        for p, g in self.param_grads:
+            p.grad = g
+
+    def run(self) -> Tensor:
+        """Issue the step on the current stream; returns ``loss`` (valid once the stream has run)."""
+        N, F, H, L, C, B = self.dims
+        call("hscn_mpnn_train_step" + ("_acc" if self.accumulate else ""), ptr(self.x), ptr(self.ei), self.ei.size(1),
+             ptr(self.ptr32), ptr(self.eptr32), N, B, F, H, L, C, self.act, self._table, self.max_n, self.max_e,
+             ptr(self.target), int(self.kind), self.inv_count, ptr(self.pred), ptr(self.score), ptr(self.partials),
+             ptr(self.grads), ptr(self.step_word), self.p, self.seed0, ptr(self.flag), stream())
+        return self.loss
+
+    def check(self) -> None:
+        """Synchronising validity check of the launches issued so far."""
+        f = int(self.flag.item())
+        if f:
+            raise RuntimeError(f"the one-launch MPNN step flagged its batch (code {f}: 1 = an edge with an end outside "
+                               "its graph, 2 = a graph beyond the batch's node / edge maxima)")

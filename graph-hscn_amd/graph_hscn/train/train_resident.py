@@ -23,7 +23,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from ..config.config import OPTIM_DICT
-from ..data import HeteroBatch, HeteroData
+from ..data import Batch, HeteroBatch, HeteroData
 from ..loader.device_dataset import DeviceHeteroDataset
 from ..loss import criterion
 from ..optim import clip_grad_norm_flat
@@ -39,7 +39,7 @@ def optimizer_steps_at(it: int, num_batches: int, batch_accumulation: int) -> bo
     return (it + 1) % batch_accumulation == 0 or it + 1 == num_batches
 
 
-def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroData], eval_loaders: Sequence, model,
+def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_loaders: Sequence, model,
                  batch_size: int, metric_fn: Optional[Callable] = None, seed: int = 0, reducer=None,
                  flat_optimizer: bool = True, epoch_orders: Optional[list] = None) -> List[tuple]:
     """Returns ``[(mean train loss, train metric), ...]`` per epoch, like ``train.train``.  ``eval_loaders`` =
@@ -54,7 +54,11 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
 
     ``epoch_orders``: a list that receives every epoch's permutation of ``train_graphs`` as a host tensor (one
     read-back per epoch, only when a list is passed): batch i of the epoch is ``order[i * B:(i + 1) * B]``, the
-    order ``train.train_epoch`` has to see to take the same steps."""
+    order ``train.train_epoch`` has to see to take the same steps.
+
+    ``model`` may also be the MPNN baseline (``model.mpnn.MPNN``) with ``train_graphs`` a list of ``Data``: the
+    dataset is then a ``DeviceGraphDataset`` and the captured step ``step.MPNNResidentTrainStep`` (one launch + the
+    gradient fold); evaluation through ``train.eval_epoch`` takes the MPNN's forward-only launch."""
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("fit_resident runs on the MI355X HIP path: move the model to 'cuda'")
@@ -66,7 +70,13 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
     G, B = len(train_graphs), int(batch_size)
     if G < B:
         raise ValueError("fewer training graphs than one batch")
-    ds = DeviceHeteroDataset(train_graphs, dev, B)
+    from ..model.mpnn import MPNN
+    mpnn = isinstance(model, MPNN)      # the MPNN baseline on a list of Data: homogeneous device dataset, same loop
+    if mpnn:
+        from ..loader.device_dataset import DeviceGraphDataset
+        ds = DeviceGraphDataset(train_graphs, dev, B)
+    else:
+        ds = DeviceHeteroDataset(train_graphs, dev, B)
     opt_cls = OPTIM_DICT[optim_cfg.optim_type]
     kw = dict(lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay)
     flat = flat_optimizer and optim_cfg.optim_type in ("adam", "adamW")   # optim.FlatAdam: the update as ONE launch
@@ -139,12 +149,21 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
             loss_log[i].copy_(step.loss)
             if metric_fn:
                 scores[i * B:(i + 1) * B].copy_(step.score)
-                targets[i * B:(i + 1) * B].copy_(ds.static.batch["local"].y)
+                targets[i * B:(i + 1) * B].copy_(ds.static.batch.y if mpnn else ds.static.batch["local"].y)
         if tail:
-            hb = HeteroBatch.from_data_list([train_graphs[j] for j in perm[steps * B:].tolist()]).to(dev)
-            optimizer.zero_grad(set_to_none=True)
-            pred = model(hb.x_dict, hb.edge_index_dict, hb)
-            loss, score = criterion(training_cfg.loss_fn, pred, hb["local"].y)
+            tail_graphs = [train_graphs[j] for j in perm[steps * B:].tolist()]
+            if mpnn:                           # (the layered engine: gradients are on)
+                hb = Batch.from_data_list(tail_graphs).to(dev)
+                hb.x = hb.x.float()
+                optimizer.zero_grad(set_to_none=True)
+                pred = model(hb)
+                tail_y = hb.y
+            else:
+                hb = HeteroBatch.from_data_list(tail_graphs).to(dev)
+                optimizer.zero_grad(set_to_none=True)
+                pred = model(hb.x_dict, hb.edge_index_dict, hb)
+                tail_y = hb["local"].y
+            loss, score = criterion(training_cfg.loss_fn, pred, tail_y)
             loss.backward()
             if legacy:
                 if reducer is not None:
@@ -167,7 +186,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence[HeteroD
             loss_log[steps].copy_(loss.detach())
             if metric_fn:
                 scores[steps * B:].copy_(score.detach())
-                targets[steps * B:].copy_(hb["local"].y)
+                targets[steps * B:].copy_(tail_y)
             del pred, loss, score, hb
         mean_loss = float(loss_log.mean().item())                     # the epoch's only read-back
         perf = metric_fn(targets, scores) if metric_fn else float("nan")

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HSCN_ABI_VERSION 19
+#define HSCN_ABI_VERSION 20
 
 #define HSCN_E_BADARG (-1)   /* null pointer, negative size, unsupported width */
 #define HSCN_E_WORKSPACE (-2) /* workspace too small */
@@ -913,6 +913,51 @@ int64_t hscn_allreduce_oneshot_chunks(int64_t count);
 int hscn_allreduce_oneshot(float* flat, int64_t count, void* const* peer_slots_host /*[G]*/,
                            void* const* peer_flags_host /*[G]*/, uint32_t* epoch, uint32_t* status, int rank, int G,
                            float scale, uint32_t spin_limit, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * ABI 20: the MPNN baseline (reference model/mpnn.py:13-62 with conv = GCNConv, configs/GCN/peptides_func_GCN.yaml)
+ * as ONE training-step launch: workgroup g runs the forward of graph g, its loss row and the backward with the
+ * structure and every activation in LDS, then the fold (k_param_reduce) sums the per-graph partials.
+ *   hidden layer l < L-1: a = dropout(act(relu(A_hat a W_l^T + b_l))); last layer: pred = mean_i (A_hat a W^T + b)_i;
+ *   A_hat: GCN normalisation WITH self loops (the edge list's own loops are replaced, not doubled; isolated nodes
+ *   keep their own row).  act: HSCN_ACT_* (relu, elu, identity, tanh).
+ *   x [N,F] f32, edge_index int64 [2,E] batch numbering, graph g owns nodes [ptr32[g], ptr32[g+1]) and edges
+ *   [eptr32[g], eptr32[g+1]); params_host: HOST array of L x 2 device pointers {W_l [fout,fin], b_l [fout]}
+ *   (fin = F for l = 0 else H, fout = C for l = L-1 else H), the parameter order of graph_hscn.model.mpnn.MPNN.
+ *   target [B,C], loss_kind 0 = BCE with logits (multilabel), 1 = L1; inv_count = 1 / (B C).
+ *   pred, score (sigmoid, optional) [B,C]; partials [B, P+1]; grads [P+1]: dL/d params packed in parameter order,
+ *   grads[P] = the mean loss (P = hscn_mpnn_param_count).
+ *   Dropout p in [0, 1): the mask of hidden layer l is bitwise that of hscn_dropout over the batch's [N, H]
+ *   activation with seed seed0 + (L-1) t + l, t = step[0] (device word, read at launch, advanced by one by the fold:
+ *   a captured step draws new masks on every replay).  step may be NULL when p = 0 (t = 0; nothing advanced).
+ *   flag bit 1: an edge with an end outside its graph (dropped); bit 2: a graph beyond max_n / max_ell or the
+ *   arrays (its partials row is zeros).
+ * hscn_mpnn_train_step_acc: the same launches, the fold ADDS every parameter column to grads (as the ABI 19 *_acc
+ *   entry points; grads[P] is still the loss of this call).
+ * hscn_mpnn_forward: the forward alone (no dropout: evaluation / inference): pred, score (optional), and with a
+ *   target the per-graph loss-term sums loss_rows [B] and, if loss != NULL, the mean loss loss[0].
+ * hscn_mpnn_supported: H in {16, 32}, 1 <= F <= H, C <= min(H, 16), 2 <= L <= 8, and a layout of the largest graph
+ *   within 160 KB of LDS (H = 16: Peptides' 444 nodes).  Normalisation layers, other convolutions and class-index
+ *   targets are not this launch's (the Python layer reports them).
+ * ------------------------------------------------------------------------- */
+int hscn_mpnn_supported(int F, int H, int L, int C, int max_n, int max_ell);
+int64_t hscn_mpnn_param_count(int F, int H, int L, int C);
+int hscn_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
+                         const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
+                         const void* const* params_host /* L x 2 */, int max_n, int max_ell, const float* target,
+                         int loss_kind, float inv_count, float* pred, float* score /*or NULL*/,
+                         float* partials /*[B,P+1]*/, float* grads /*[P+1]*/, uint32_t* step /*or NULL if p = 0*/,
+                         float p, uint64_t seed0, int32_t* flag, void* stream);
+int hscn_mpnn_train_step_acc(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
+                             const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
+                             const void* const* params_host, int max_n, int max_ell, const float* target,
+                             int loss_kind, float inv_count, float* pred, float* score, float* partials, float* grads,
+                             uint32_t* step, float p, uint64_t seed0, int32_t* flag, void* stream);
+int hscn_mpnn_forward(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
+                      const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
+                      const void* const* params_host, int max_n, int max_ell, const float* target /*or NULL*/,
+                      int loss_kind, float inv_count, float* pred, float* score /*or NULL*/,
+                      float* loss_rows /*[B] or NULL*/, float* loss /*[1] or NULL*/, int32_t* flag, void* stream);
 
 #ifdef __cplusplus
 }
