@@ -6,31 +6,6 @@
 
 namespace {
 
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  c[0] = hi1 ^ c[1] ^ k0;
-  c[1] = lo1;
-  c[2] = hi0 ^ c[3] ^ k1;
-  c[3] = lo0;
-}
-
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t ctr, uint32_t (&c)[4]) {
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  c[0] = (uint32_t)ctr;
-  c[1] = (uint32_t)(ctr >> 32);
-  c[2] = 0u;
-  c[3] = 0u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
-// keep iff the 32-bit draw is >= p * 2^32 (threshold computed on the host in integers)
 __global__ void __launch_bounds__(256)
 k_dropout(const float* __restrict__ x, float* __restrict__ y, int64_t n, uint32_t threshold, float scale,
           uint64_t seed) {
@@ -57,9 +32,9 @@ k_dropout(const float* __restrict__ x, float* __restrict__ y, int64_t n, uint32_
 extern "C" int hscn_dropout(const float* x, float* y, int64_t count, float p, uint64_t seed, void* stream_) {
   if (count < 0 || !(p >= 0.f && p < 1.f) || (count > 0 && (!x || !y))) return HSCN_E_BADARG;
   if (count == 0) return 0;
-  const double t = (double)p * 4294967296.0;
-  const uint32_t threshold = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
-  const float scale = 1.0f / (1.0f - p);
+  uint32_t threshold;
+  float scale;
+  dropout_keep_rule(p, threshold, scale);
   unsigned nb = hscn_blocks((count + 3) / 4, 256);
   if (nb > 4096) nb = 4096;
   k_dropout<<<nb, 256, 0, hscn_stream(stream_)>>>(x, y, count, threshold, scale, seed);

@@ -60,6 +60,39 @@ __device__ __forceinline__ void criterion_elem(int kind, float x, float y, float
   }
 }
 
+// Philox-4x32-10: the four 32-bit draws of block `ctr` under key `seed` (hscn_dropout's generator)
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+  const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+  c[0] = hi1 ^ c[1] ^ k0;
+  c[1] = lo1;
+  c[2] = hi0 ^ c[3] ^ k1;
+  c[3] = lo0;
+}
+
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t ctr, uint32_t (&c)[4]) {
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  c[0] = (uint32_t)ctr;
+  c[1] = (uint32_t)(ctr >> 32);
+  c[2] = 0u;
+  c[3] = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// hscn_dropout's keep rule for a drop probability p in [0, 1): keep iff the draw is >= threshold = p 2^32 (computed
+// in integers), kept values times scale = 1 / (1 - p)
+static inline void dropout_keep_rule(float p, uint32_t& threshold, float& scale) {
+  const double t = (double)p * 4294967296.0;
+  threshold = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+  scale = 1.0f / (1.0f - p);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -576,5 +576,14 @@ __global__ void __launch_bounds__(256) k_param_reduce_acc(const float* __restric
   param_reduce<true>(partials, out, B, P, p_scaled, scale, epoch);
 }
 
+// The fold behind a gradient-producing launch: k_param_reduce, or its accumulating twin, over all P columns.
+inline void launch_param_fold(const float* partials, float* grads, int B, int P, int p_scaled, float scale,
+                              uint32_t* epoch, bool accumulate, hipStream_t st) {
+  if (accumulate)
+    k_param_reduce_acc<<<hscn_blocks(P, 32), 256, 0, st>>>(partials, grads, B, P, p_scaled, scale, epoch);
+  else
+    k_param_reduce<<<hscn_blocks(P, 32), 256, 0, st>>>(partials, grads, B, P, p_scaled, scale, epoch);
+}
+
 
 }  // namespace

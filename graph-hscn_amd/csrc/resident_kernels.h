@@ -2357,10 +2357,7 @@ int impl_resident_bwd(const float* x_local, const int64_t* ei_ll, int64_t E_ll, 
     case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd<64, float>(A, B, st); break;
   }
   if (rc) return rc;
-  if (accumulate)
-    k_param_reduce_acc<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count);
-  else
-    k_param_reduce<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count);
+  launch_param_fold(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count, nullptr, accumulate, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -2403,10 +2400,7 @@ int impl_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, i
     case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd_virtual<64, float>(Ab, Af, B, st); break;
   }
   if (rc) return rc;
-  if (accumulate)
-    k_param_reduce_acc<<<hscn_blocks(Ab.P, 32), 256, 0, st>>>(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count);
-  else
-    k_param_reduce<<<hscn_blocks(Ab.P, 32), 256, 0, st>>>(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count);
+  launch_param_fold(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count, nullptr, accumulate, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -2514,12 +2508,7 @@ int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
   k_param_reduce<<<HSCN_DIAG_REDUCE_BLOCKS, 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
                                                           S.ready ? sync : nullptr);
 #else
-  if (accumulate)
-    k_param_reduce_acc<<<hscn_blocks(S.P, 32), 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
-                                                             S.ready ? sync : nullptr);
-  else
-    k_param_reduce<<<hscn_blocks(S.P, 32), 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
-                                                         S.ready ? sync : nullptr);
+  launch_param_fold(partials, grads, (int)B, S.P, S.Pn, S.inv_count, S.ready ? sync : nullptr, accumulate, st);
 #endif
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;

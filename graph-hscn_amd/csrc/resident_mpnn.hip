@@ -52,29 +52,6 @@ struct MpnnArgs {
   float inv_count;
 };
 
-__device__ __forceinline__ void mpnn_philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  c[0] = hi1 ^ c[1] ^ k0;
-  c[1] = lo1;
-  c[2] = hi0 ^ c[3] ^ k1;
-  c[3] = lo0;
-}
-
-// component `comp` of the Philox-4x32-10 block (seed, ctr): csrc/dropout.hip's generator
-__device__ __forceinline__ uint32_t mpnn_philox(uint64_t seed, uint64_t ctr, int comp) {
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    mpnn_philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return comp == 0 ? c[0] : comp == 1 ? c[1] : comp == 2 ? c[2] : c[3];
-}
-
 struct MpnnLayout {
   size_t w, dinv, rowptr, col, rowptr_t, col_t, misc, red, buf, bufw, total;
   size_t ek, eo, tmp, cursor;   // CSR build staging (inside the buffers)
@@ -248,7 +225,10 @@ __global__ void __launch_bounds__(MPNN_RT) k_mpnn_step(const MpnnArgs A) {
         if (A.act == HSCN_ACT_TANH) a = tanhf(a);
         if (TRAIN && A.dropout) {
           const uint64_t gi = (uint64_t)(base + i) * H + o;
-          const uint32_t r = mpnn_philox(seed, gi >> 2, (int)(gi & 3));
+          uint32_t c[4];
+          philox4x32_10(seed, gi >> 2, c);
+          const int k = (int)(gi & 3);
+          const uint32_t r = k == 0 ? c[0] : k == 1 ? c[1] : k == 2 ? c[2] : c[3];
           a = r >= A.threshold ? a * A.scale : 0.f;
         }
         out[idx] = a;
@@ -415,18 +395,11 @@ int impl_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, c
     return rc;
   A.partials = partials; A.step = step; A.seed0 = seed0;
   A.dropout = p > 0.f ? 1 : 0;
-  {  // hscn_dropout's threshold and scale, computed the same way
-    const double th = (double)p * 4294967296.0;
-    A.threshold = th >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)th;
-    A.scale = 1.0f / (1.0f - p);
-  }
+  dropout_keep_rule(p, A.threshold, A.scale);
   hipStream_t st = hscn_stream(stream_);
   const int rc = H == 16 ? launch_mpnn<16, true>(A, B, st) : launch_mpnn<32, true>(A, B, st);
   if (rc) return rc;
-  if (accumulate)
-    k_param_reduce_acc<<<hscn_blocks(A.P + 1, 32), 256, 0, st>>>(partials, grads, (int)B, A.P + 1, A.P, inv_count, step);
-  else
-    k_param_reduce<<<hscn_blocks(A.P + 1, 32), 256, 0, st>>>(partials, grads, (int)B, A.P + 1, A.P, inv_count, step);
+  launch_param_fold(partials, grads, (int)B, A.P + 1, A.P, inv_count, step, accumulate, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -1659,7 +1659,7 @@ static int scn_step_impl(int f16, const float* x, const int64_t* edge_index, int
     HSCN_RETURN_IF_LAUNCH_FAILED();
   }
   if (B > 1) {
-    k_param_reduce<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, -1, 0.f);
+    launch_param_fold(partials, grads, (int)B, A.P, -1, 0.f, nullptr, false, st);
     HSCN_RETURN_IF_LAUNCH_FAILED();
   }
   return 0;
@@ -1725,7 +1725,7 @@ static int scn_bwd_impl(int f16, const float* x, const int64_t* edge_index, int6
   int rc = f16 ? (H == 16 ? launch_scn<16, half_t>(A, 1, st) : launch_scn<32, half_t>(A, 1, st))
                : (H == 16 ? launch_scn<16, float>(A, 1, st) : launch_scn<32, float>(A, 1, st));
   if (rc) return rc;
-  k_param_reduce<<<hscn_blocks(A.P, 32), 256, 0, st>>>(partials, grads, (int)B, A.P, -1, 0.f);
+  launch_param_fold(partials, grads, (int)B, A.P, -1, 0.f, nullptr, false, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -11,6 +11,7 @@ entry points in a single autograd Function.
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -178,6 +179,92 @@ def _cu_count(dev: torch.device) -> int:
     return _CUS[idx]
 
 
+def grad_views(flat: Tensor, shapes, P: int) -> List[Tensor]:
+    """Views of the flat gradient buffer a backward launch fills (the ``P`` parameter values in launch order, then
+    any loss column), one per shape in ``shapes``."""
+    views, off = [], 0
+    for s in shapes:
+        n = math.prod(s)
+        views.append(flat[off: off + n] if len(s) == 1 else flat[off: off + n].view(s))
+        off += n
+    assert off == P, "the parameter shapes do not tile the launch's gradient layout"
+    return views
+
+
+# --------------------------------------------------------------------------- #
+# stage C: the HSCN launches.  HSCNResidentFn (autograd) and step.ResidentTrainStep (preallocated buffers) both
+# issue them through these builders, so the two paths pass the same arguments by construction.
+#   dims = (N, V, F, H, L, C, B); table = _ptr_table of the 9 L layer parameters; head = (W1, b1, W2, b2);
+#   out = (acts, pooled, z, pred, score, (csr_rowptr, csr_col, dinv)), as hscn_buffers returns it
+# --------------------------------------------------------------------------- #
+def defers_virtual(compute_virtual, overlap, dims, dev) -> bool:
+    """The virtual branch runs as extra workgroups of the forward / backward pair (see HSCNResidentFn) -- which pays
+    only while they land on CUs the batch leaves idle: 2 B <= number of CUs."""
+    N, V, F, H, L, C, B = dims
+    return bool(compute_virtual and overlap and V > 0 and L >= 2 and 2 * B <= _cu_count(dev))
+
+
+def hscn_buffers(dev, sdt, dims, E_ll: int, E_lv: int, E_vv: int, score: bool, csr: bool, state: bool):
+    """``out`` of the launches (activations in the storage type ``sdt``; the sigmoid ``score`` with which the loss tail
+    can ride on the backward launch; the source-keyed CSR + degree norm the forward builds in LDS for the backward),
+    and the deferred virtual branch's state (its CSRs, degree norm and layer-0 output), or None."""
+    N, V, F, H, L, C, B = dims
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    out = (torch.empty(L, N, H, dtype=sdt, device=dev), torch.empty(B, H, **f32), torch.empty(B, H, **f32),
+           torch.empty(B, C, **f32), torch.empty(B, C, **f32) if score else None,
+           (torch.empty(N + B, **i32), torch.empty(max(E_ll, 1), **i32), torch.empty(max(N, 1), **f32)) if csr
+           else (None, None, None))
+    if not state:
+        return out, None
+    return out, (torch.empty(V + B, **i32), torch.empty(max(E_lv, 1), **i32), torch.empty(V + B, **i32),
+                 torch.empty(max(E_vv, 1), **i32), torch.empty(V, **f32), torch.empty(V, H, dtype=sdt, device=dev))
+
+
+def virtual_job(x_virtual, ei_vv, ei_lv, meta: ResidentMeta, table, slope: float, state, xv_out=None) -> _VirtualJob:
+    """include/hscn.h: hscn_virtual_job (``state`` = hscn_buffers' deferred state, or None)."""
+    return _VirtualJob(ptr(x_virtual), ptr(ei_vv), ei_vv.size(1), ptr(ei_lv), ei_lv.size(1), ptr(meta.vptr),
+                       ptr(meta.eptr_vv), ptr(meta.eptr_lv), ctypes.cast(table, ctypes.c_void_p), ptr(xv_out),
+                       x_virtual.shape[0], meta.max_v, meta.max_evv, slope,
+                       *([ptr(t) for t in state] if state is not None else [None] * 6))
+
+
+def launch_fwd(sfx, x_local, x_virtual, ei_ll, ei_vv, ei_lv, m: ResidentMeta, dims, head_act, slope, table, head,
+               compute_virtual, out, xv_out) -> None:
+    N, V, F, H, L, C, B = dims
+    W1, b1, W2, b2 = head
+    acts, pooled, z, pred, score, (csr_rp, csr_col, dinv) = out
+    call("hscn_resident_fwd" + sfx, ptr(x_local), ptr(x_virtual), ptr(ei_ll), ei_ll.size(1), ptr(ei_vv),
+         ei_vv.size(1), ptr(ei_lv), ei_lv.size(1), ptr(m.lptr), ptr(m.vptr), ptr(m.eptr_ll), ptr(m.eptr_vv),
+         ptr(m.eptr_lv), N, V, B, F, H, L, C, head_act, float(slope), table, ptr(W1), ptr(b1), ptr(W2), ptr(b2),
+         m.max_n, m.max_v, m.max_ell, m.max_evv, int(bool(compute_virtual)), ptr(acts), ptr(pooled), ptr(z),
+         ptr(pred), ptr(score), ptr(xv_out), ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), stream())
+
+
+def launch_fwd_with_virtual(sfx, x_local, ei_ll, m: ResidentMeta, dims, head_act, table, head, out, job) -> None:
+    N, V, F, H, L, C, B = dims
+    W1, b1, W2, b2 = head
+    acts, pooled, z, pred, score, (csr_rp, csr_col, dinv) = out
+    call("hscn_resident_fwd_with_virtual" + sfx, ptr(x_local), ptr(ei_ll), ei_ll.size(1), ptr(m.lptr),
+         ptr(m.eptr_ll), N, B, F, H, L, C, head_act, table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), m.max_n, m.max_ell,
+         ptr(acts), ptr(pooled), ptr(z), ptr(pred), ptr(score), ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag),
+         ctypes.byref(job), stream())
+
+
+def launch_bwd(sfx, x_local, ei_ll, m: ResidentMeta, dims, head_act, wll_table, W1, W2, acts, pooled, z, csr,
+               g_pred, g_scale, partials, grads, tail, job=None) -> None:
+    """``sfx``: "_acc" (the accumulating fold) and / or the storage suffix; ``job``: the deferred virtual branch's
+    layers 1.. ride on this launch (hscn_resident_bwd_with_virtual)."""
+    N, V, F, H, L, C, B = dims
+    args = (ptr(x_local), ptr(ei_ll), ei_ll.size(1), ptr(m.lptr), ptr(m.eptr_ll), N, B, F, H, L, C, head_act,
+            wll_table, ptr(W1), ptr(W2), ptr(acts), ptr(pooled), ptr(z), ptr(g_pred), ptr(g_scale), ptr(csr[0]),
+            ptr(csr[1]), ptr(csr[2]), m.max_n, m.max_ell, ptr(partials), ptr(grads), ptr(m.flag),
+            ctypes.byref(tail) if tail is not None else None)
+    if job is None:
+        call("hscn_resident_bwd" + sfx, *args, stream())
+    else:
+        call("hscn_resident_bwd_with_virtual" + sfx, *args, ctypes.byref(job), stream())
+
+
 class HSCNResidentFn(Function):
     """inputs: x_local, x_virtual, ei_ll, ei_vv, ei_lv, meta, cfg, then parameters in
     the order  [W_ll, b_ll, W_vv, b_vv, W_src, W_dst, att_src, att_dst, b_gat] x L,
@@ -197,8 +284,8 @@ class HSCNResidentFn(Function):
         head_act, slope, compute_virtual, keep_virtual, overlap = cfg
         L = (len(params) - 4) // 9
         params = [p.contiguous() for p in params]
-        W1, b1, W2, b2 = params[9 * L:]
-        H, C = W1.shape[0], W2.shape[0]
+        head = params[9 * L:]
+        H, C = head[0].shape[0], head[2].shape[0]
         x_local = x_local.contiguous()
         x_virtual = x_virtual.contiguous()
         sdt = x_local.dtype                       # storage type of features and activations: float32 or float16
@@ -207,51 +294,27 @@ class HSCNResidentFn(Function):
         sfx = storage_suffix(sdt)
         N, F = x_local.shape
         V = x_virtual.shape[0]
-        B = meta.num_graphs
+        dims = (N, V, F, H, L, C, meta.num_graphs)
         dev = x_local.device
         need_bwd = any(ctx.needs_input_grad[7:])   # False under no_grad
-        # (the extra workgroups pay only while they land on CUs the batch leaves idle: 2B <= number of CUs)
-        defer = bool(compute_virtual and overlap and V > 0 and need_bwd and not keep_virtual and L >= 2
-                     and 2 * B <= _cu_count(dev))
-        acts = torch.empty(L, N, H, dtype=sdt, device=dev)
-        pooled = torch.empty(B, H, dtype=torch.float32, device=dev)
-        z = torch.empty(B, H, dtype=torch.float32, device=dev)
-        pred = torch.empty(B, C, dtype=torch.float32, device=dev)
-        # sigmoid(pred) costs the head ten more stores; with it the loss tail can ride on the backward launch
-        score = torch.empty(B, C, dtype=torch.float32, device=dev) if need_bwd else None
+        defer = need_bwd and not keep_virtual and defers_virtual(compute_virtual, overlap, dims, dev)
+        out, state = hscn_buffers(dev, sdt, dims, ei_ll.size(1), ei_lv.size(1), ei_vv.size(1), score=need_bwd,
+                                  csr=need_bwd, state=defer)
         xv_out = torch.empty(max(V, 1), H, dtype=sdt, device=dev) if (compute_virtual and keep_virtual) else None
-        # source-keyed CSR + degree norm: built in LDS by the forward launch, reused by the backward launch
-        E_ll = ei_ll.size(1)
-        csr_rp = torch.empty(N + B, dtype=torch.int32, device=dev) if need_bwd else None
-        csr_col = torch.empty(max(E_ll, 1), dtype=torch.int32, device=dev) if need_bwd else None
-        dinv = torch.empty(max(N, 1), dtype=torch.float32, device=dev) if need_bwd else None
         table = _ptr_table(params[: 9 * L])
         ctx.virtual = None
         if defer:
-            E_lv, E_vv = ei_lv.size(1), ei_vv.size(1)
-            state = (torch.empty(V + B, dtype=torch.int32, device=dev), torch.empty(max(E_lv, 1), dtype=torch.int32, device=dev),
-                     torch.empty(V + B, dtype=torch.int32, device=dev), torch.empty(max(E_vv, 1), dtype=torch.int32, device=dev),
-                     torch.empty(V, dtype=torch.float32, device=dev), torch.empty(V, H, dtype=sdt, device=dev))
-            job = _VirtualJob(ptr(x_virtual), ptr(ei_vv), E_vv, ptr(ei_lv), E_lv, ptr(meta.vptr), ptr(meta.eptr_vv),
-                              ptr(meta.eptr_lv), ctypes.cast(table, ctypes.c_void_p), None, V, meta.max_v,
-                              meta.max_evv, float(slope), *[ptr(t) for t in state])
-            call("hscn_resident_fwd_with_virtual" + sfx, ptr(x_local), ptr(ei_ll), E_ll, ptr(meta.lptr), ptr(meta.eptr_ll),
-                 N, B, F, H, L, C, head_act, table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), meta.max_n, meta.max_ell,
-                 ptr(acts), ptr(pooled), ptr(z), ptr(pred), ptr(score), ptr(csr_rp), ptr(csr_col), ptr(dinv),
-                 ptr(meta.flag), ctypes.byref(job), stream())
+            launch_fwd_with_virtual(sfx, x_local, ei_ll, meta, dims, head_act, table, head, out,
+                                    virtual_job(x_virtual, ei_vv, ei_lv, meta, table, float(slope), state))
             # what the backward launch needs to run the rest of the virtual branch beside itself
             ctx.virtual = (x_virtual, ei_vv, ei_lv, params[: 9 * L], table, float(slope), state)
         else:
-            call("hscn_resident_fwd" + sfx, ptr(x_local), ptr(x_virtual), ptr(ei_ll), ei_ll.size(1), ptr(ei_vv),
-                 ei_vv.size(1), ptr(ei_lv), ei_lv.size(1), ptr(meta.lptr), ptr(meta.vptr), ptr(meta.eptr_ll),
-                 ptr(meta.eptr_vv), ptr(meta.eptr_lv), N, V, B, F, H, L, C, head_act, float(slope), table,
-                 ptr(W1), ptr(b1), ptr(W2), ptr(b2), meta.max_n, meta.max_v, meta.max_ell, meta.max_evv,
-                 int(bool(compute_virtual)), ptr(acts), ptr(pooled), ptr(z), ptr(pred), ptr(score), ptr(xv_out),
-                 ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(meta.flag), stream())
-        ctx.meta, ctx.head_act, ctx.dims = meta, head_act, (N, F, H, L, C, B)
+            launch_fwd(sfx, x_local, x_virtual, ei_ll, ei_vv, ei_lv, meta, dims, head_act, slope, table, head,
+                       compute_virtual, out, xv_out)
+        acts, pooled, z, pred, score, ctx.csr = out
+        ctx.meta, ctx.head_act, ctx.dims = meta, head_act, dims
         ctx.sfx = sfx
-        ctx.csr = (csr_rp, csr_col, dinv)
-        ctx.save_for_backward(x_local, ei_ll, acts, pooled, z, W1, W2, *[params[9 * l] for l in range(L)])
+        ctx.save_for_backward(x_local, ei_ll, acts, pooled, z, head[0], head[2], *[params[9 * l] for l in range(L)])
         ret_xv = xv_out if keep_virtual else None
         ctx.mark_non_differentiable(*[t for t in (ret_xv, score) if t is not None])
         ctx.set_materialize_grads(False)
@@ -263,7 +326,7 @@ class HSCNResidentFn(Function):
         if g_pred is None:
             return (None,) * (7 + 9 * ((len(W_ll))) + 4)
         meta: ResidentMeta = ctx.meta
-        N, F, H, L, C, B = ctx.dims
+        N, V, F, H, L, C, B = ctx.dims
         dev = x_local.device
         P = int(_hip.lib().hscn_resident_param_count(F, H, L, C))
         # the loss node hands its gradient over unevaluated: either (unscaled gradient, scalar) -- the launch
@@ -282,39 +345,25 @@ class HSCNResidentFn(Function):
         Pw = P + (1 if tail is not None else 0)
         partials = torch.empty(B, Pw, dtype=torch.float32, device=dev)
         grads = torch.empty(Pw, dtype=torch.float32, device=dev)
-        table = _ptr_table(list(W_ll))
-        args = (ptr(x_local), ptr(ei_ll), ei_ll.size(1), ptr(meta.lptr), ptr(meta.eptr_ll), N, B,
-                F, H, L, C, ctx.head_act, table, ptr(W1), ptr(W2), ptr(acts), ptr(pooled), ptr(z), ptr(g_pred),
-                ptr(g_scale), ptr(ctx.csr[0]), ptr(ctx.csr[1]), ptr(ctx.csr[2]), meta.max_n, meta.max_ell, ptr(partials),
-                ptr(grads), ptr(meta.flag), ctypes.byref(tail) if tail is not None else None)
         if tail_ref is not None:
             tail_ref.state.fill(grads[P:P + 1].view(()))      # the loss value, once this launch has run
+        job = xv = None
         if ctx.virtual is not None:
-            global last_deferred_virtual
             x_virtual, ei_vv, ei_lv, _keep, vtable, slope, state = ctx.virtual
-            V = x_virtual.shape[0]
             xv = torch.empty(max(V, 1), H, dtype=x_virtual.dtype, device=dev)
-            job = _VirtualJob(ptr(x_virtual), ptr(ei_vv), ei_vv.size(1), ptr(ei_lv), ei_lv.size(1), ptr(meta.vptr),
-                              ptr(meta.eptr_vv), ptr(meta.eptr_lv), ctypes.cast(vtable, ctypes.c_void_p), ptr(xv),
-                              V, meta.max_v, meta.max_evv, slope, *[ptr(t) for t in state])
-            call("hscn_resident_bwd_with_virtual" + ctx.sfx, *args, ctypes.byref(job), stream())
+            job = virtual_job(x_virtual, ei_vv, ei_lv, meta, vtable, slope, state, xv)
+        launch_bwd(ctx.sfx, x_local, ei_ll, meta, ctx.dims, ctx.head_act, _ptr_table(W_ll), W1, W2, acts, pooled, z,
+                   ctx.csr, g_pred, g_scale, partials, grads, tail, job)
+        if job is not None:
+            global last_deferred_virtual
             last_deferred_virtual = xv
             ctx.virtual = None
-        else:
-            call("hscn_resident_bwd" + ctx.sfx, *args, stream())
+        shapes = [s for l in range(L) for s in (W_ll[l].shape, (H,))] + [W1.shape, (H,), W2.shape, (C,)]
+        g = grad_views(grads, shapes, P)
         out: List[Optional[Tensor]] = [None] * (7 + 9 * L + 4)
-        off = 0
         for l in range(L):
-            fin = F if l == 0 else H
-            out[7 + 9 * l] = grads[off: off + H * fin].view(H, fin)
-            off += H * fin
-            out[7 + 9 * l + 1] = grads[off: off + H]
-            off += H
-        base = 7 + 9 * L
-        out[base] = grads[off: off + H * H].view(H, H); off += H * H
-        out[base + 1] = grads[off: off + H]; off += H
-        out[base + 2] = grads[off: off + C * H].view(C, H); off += C * H
-        out[base + 3] = grads[off: off + C]
+            out[7 + 9 * l: 9 + 9 * l] = g[2 * l: 2 * l + 2]
+        out[7 + 9 * L:] = g[2 * L:]
         return tuple(out)
 
 
@@ -361,6 +410,23 @@ def scn_meta(data, device) -> ScnMeta:
     return meta
 
 
+def launch_scn_fwd(sfx, x, ei, m: ScnMeta, dims, act, W, S, y, stats, ss, losses, ticket, ex=None) -> None:
+    """hscn_scn_resident_fwd.  dims = (N, F, H, K, B, E); W = the contiguous (W_rel, b_rel, W_root, W_mlp, b_mlp);
+    ex = the six buffers the forward exports for the backward (both CSRs, A_hat x, the out-degree), or None."""
+    N, F, H, K, B, E = dims
+    call("hscn_scn_resident_fwd" + sfx, ptr(x), ptr(ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
+         act, *[ptr(w) for w in W], m.max_n, m.max_e, ptr(S), ptr(y), ptr(stats), ptr(ss), ptr(losses), ptr(ticket),
+         *([ptr(t) for t in ex] if ex is not None else [None] * 6), ptr(m.flag), stream())
+
+
+def launch_scn_bwd(sfx, x, ei, m: ScnMeta, dims, act, W_mlp, S, y, stats, ss, g_mc, g_o, ex, partials,
+                   grads) -> None:
+    N, F, H, K, B, E = dims
+    call("hscn_scn_resident_bwd" + sfx, ptr(x), ptr(ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
+         act, ptr(W_mlp), ptr(S), ptr(y), ptr(stats), ptr(ss), ptr(g_mc), ptr(g_o), *[ptr(t) for t in ex], m.max_n,
+         m.max_e, ptr(partials), ptr(grads), ptr(m.flag), stream())
+
+
 class SCNResidentFn(Function):
     """(x, raw edge_index, meta, act, W_rel, b_rel, W_root, W_mlp, b_mlp) -> (S, mc_loss, o_loss, mc_loss + o_loss).
     The two losses are separate autograd outputs (0-dim views of one [2] buffer the launch fills), so
@@ -371,7 +437,7 @@ class SCNResidentFn(Function):
     def forward(ctx, x, edge_index, meta: ScnMeta, act: int, W_rel, b_rel, W_root, W_mlp, b_mlp):
         x = x.contiguous()
         edge_index = edge_index.contiguous()
-        W_rel, b_rel, W_root, W_mlp, b_mlp = (t.contiguous() for t in (W_rel, b_rel, W_root, W_mlp, b_mlp))
+        W = [t.contiguous() for t in (W_rel, b_rel, W_root, W_mlp, b_mlp)]
         N, F = x.shape
         H, K = W_rel.shape[0], W_mlp.shape[0]
         B = meta.num_graphs
@@ -394,13 +460,11 @@ class SCNResidentFn(Function):
             ex = (torch.empty(N + B, dtype=torch.int32, device=dev), torch.empty(max(E, 1), dtype=torch.int32, device=dev),
                   torch.empty(N + B, dtype=torch.int32, device=dev), torch.empty(max(E, 1), dtype=torch.int32, device=dev),
                   torch.empty(max(N, 1), 16, dtype=torch.float32, device=dev), torch.empty(max(N, 1), dtype=torch.float32, device=dev))
-        call("hscn_scn_resident_fwd" + ctx.sfx, ptr(x), ptr(edge_index) if E else None, E, ptr(meta.nptr), ptr(meta.eptr), N, B,
-             F, H, K, act, ptr(W_rel), ptr(b_rel), ptr(W_root), ptr(W_mlp), ptr(b_mlp), meta.max_n, meta.max_e,
-             ptr(S), ptr(y), ptr(stats), ptr(ss), ptr(losses), ptr(meta.ticket), *([ptr(t) for t in ex] if ex else [None] * 6),
-             ptr(meta.flag), stream())
+        ctx.dims = (N, F, H, K, B, E)
+        launch_scn_fwd(ctx.sfx, x, edge_index, meta, ctx.dims, act, W, S, y, stats, ss, losses, meta.ticket, ex)
         ctx.ex = ex
-        ctx.meta, ctx.act, ctx.dims = meta, act, (N, F, H, K, B, E)
-        ctx.save_for_backward(x, edge_index, W_mlp, S, y, stats, ss)
+        ctx.meta, ctx.act = meta, act
+        ctx.save_for_backward(x, edge_index, W[3], S, y, stats, ss)
         ctx.mark_non_differentiable(S)
         ctx.set_materialize_grads(False)
         return S, losses[0], losses[1], losses[2]
@@ -408,7 +472,6 @@ class SCNResidentFn(Function):
     @staticmethod
     def backward(ctx, gS, g_mc, g_o, g_total):
         x, edge_index, W_mlp, S, y, stats, ss = ctx.saved_tensors
-        meta: ScnMeta = ctx.meta
         N, F, H, K, B, E = ctx.dims
         dev = x.device
         P = int(_hip.lib().hscn_scn_resident_param_count(F, H, K))
@@ -419,13 +482,6 @@ class SCNResidentFn(Function):
             g_o = g_total if g_o is None else g_o + g_total
         g_mc = None if g_mc is None else g_mc.reshape(1).contiguous()
         g_o = None if g_o is None else g_o.reshape(1).contiguous()
-        call("hscn_scn_resident_bwd" + ctx.sfx, ptr(x), ptr(edge_index) if E else None, E, ptr(meta.nptr), ptr(meta.eptr), N, B,
-             F, H, K, ctx.act, ptr(W_mlp), ptr(S), ptr(y), ptr(stats), ptr(ss), ptr(g_mc), ptr(g_o), *[ptr(t) for t in ctx.ex], meta.max_n, meta.max_e,
-             ptr(partials), ptr(grads), ptr(meta.flag), stream())
-        o = 0
-        gW_rel = grads[o:o + H * F].view(H, F); o += H * F
-        gb_rel = grads[o:o + H]; o += H
-        gW_root = grads[o:o + H * F].view(H, F); o += H * F
-        gW_mlp = grads[o:o + K * H].view(K, H); o += K * H
-        gb_mlp = grads[o:o + K]
-        return None, None, None, None, gW_rel, gb_rel, gW_root, gW_mlp, gb_mlp
+        launch_scn_bwd(ctx.sfx, x, edge_index, ctx.meta, ctx.dims, ctx.act, W_mlp, S, y, stats, ss, g_mc, g_o, ctx.ex,
+                       partials, grads)
+        return (None,) * 4 + tuple(grad_views(grads, ((H, F), (H,), (H, F), (K, H), (K,)), P))

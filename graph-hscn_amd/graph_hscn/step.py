@@ -8,9 +8,9 @@ it is being captured: autograd binds every parameter's gradient-accumulation nod
 was first used on, and a node that an earlier eager step left alive ties the capture to that
 non-capturing stream -- ``capture_end`` then fails inside the HIP runtime (a host segfault, round 1:
 gpurun_out/t12.log, scn_dbg.log).  The classes here issue exactly the launches the autograd path
-issues -- same entry points, same arguments, bit-identical outputs (tests/test_gpu_step.py) -- into
-buffers allocated once, so a capture contains kernel nodes only and nothing of an earlier step can
-reach into it.
+issues -- through the same ``engine.launch_*`` builders, so same entry points and same arguments by
+construction, and bit-identical outputs (tests/test_gpu_step.py) -- into buffers allocated once, so
+a capture contains kernel nodes only and nothing of an earlier step can reach into it.
 
   ResidentTrainStep  stage C: zero grads -> HSCN.forward -> criterion -> backward
   ScnTrainStep       stage A: zero grads -> gcn_norm + SCN.forward -> (mc + o).backward
@@ -18,7 +18,7 @@ reach into it.
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -37,7 +37,19 @@ def _loss_kind(loss_fn: str, C_pred: Tuple[int, int], target: Tensor) -> int:
     return 0 if loss_fn == "cross_entropy" else 1
 
 
-class ResidentTrainStep:
+class _FlatGradStep:
+    def bind_grads(self) -> None:
+        """Point every ``p.grad`` at its slice of ``grads``; the model's other parameters get ``None``, as autograd
+        leaves them."""
+        has = {id(p) for p, _ in self.param_grads}
+        for p in self.model.parameters():
+            if id(p) not in has:
+                p.grad = None
+        for p, g in self.param_grads:
+            p.grad = g
+
+
+class ResidentTrainStep(_FlatGradStep):
     """``for p: p.grad = None; pred = model(x_dict, edge_index_dict, batch); loss, score =
     criterion(loss_fn, pred, batch["local"].y); loss.backward()`` on the graph-resident engine,
     issued by ``run()`` as two or three launches on the current stream.
@@ -105,22 +117,16 @@ class ResidentTrainStep:
             raise TypeError("targets must be a contiguous float32 tensor on the batch's device")
         self.kind = _loss_kind(loss_fn, (B, C), y)
         self.target = y
-        self._params = params
+        self._head = params[9 * L:]
         self._table = _engine._ptr_table(params[: 9 * L])
         self._wll_table = _engine._ptr_table([params[9 * l] for l in range(L)])
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.acts = torch.empty(L, N, H, dtype=sdt, device=dev)
-        self.pooled = torch.empty(B, H, **f32)
-        self.z = torch.empty(B, H, **f32)
-        self.pred = torch.empty(B, C, **f32)
-        self.score = torch.empty(B, C, **f32)
-        E_ll, E_vv, E_lv = (self.ei[k].size(1) for k in (LL, VV, LV))
-        self.csr = (torch.empty(N + B, **i32), torch.empty(max(E_ll, 1), **i32), torch.empty(max(N, 1), **f32))
-        self.virtual = torch.empty(max(V, 1), H, dtype=sdt, device=dev) if model.compute_virtual else None
         # the virtual branch rides on the two launches as extra workgroups while they land on idle CUs
+        self.defer = _engine.defers_virtual(model.compute_virtual, model.overlap_virtual, self.dims, dev)
+        self._out, self._state = _engine.hscn_buffers(dev, sdt, self.dims, *(self.ei[k].size(1) for k in (LL, LV, VV)),
+                                                      score=True, csr=True, state=self.defer)
+        self.acts, self.pooled, self.z, self.pred, self.score, self.csr = self._out
+        self.virtual = torch.empty(max(V, 1), H, dtype=sdt, device=dev) if model.compute_virtual else None
         cus = _engine._cu_count(dev)
-        self.defer = bool(model.compute_virtual and model.overlap_virtual and V > 0 and L >= 2 and 2 * B <= cus)
         # the one-launch step's virtual workgroups also fit beside small graphs' 4-wave workgroups (several per CU)
         per_cu = int(_hip.lib().hscn_resident_train_step_wgs_per_cu(F, H, L, C, meta.max_n, meta.max_ell, meta.max_v,
                                                                     meta.max_evv))
@@ -135,10 +141,6 @@ class ResidentTrainStep:
         large_b = _lb == "all" or (H == 16 and meta.max_n > 64 and _lb != "0")
         self.idle_cus = bool(model.compute_virtual and model.overlap_virtual and V > 0 and
                              (2 * B <= cus * max(per_cu, 1) or large_b))
-        self._state = None
-        if self.defer:
-            self._state = (torch.empty(V + B, **i32), torch.empty(max(E_lv, 1), **i32), torch.empty(V + B, **i32),
-                           torch.empty(max(E_vv, 1), **i32), torch.empty(V, **f32), torch.empty(V, H, dtype=sdt, device=dev))
         # one-launch step: the virtual branch rides as B more workgroups of the same launch when they land on idle
         # CUs (same condition as `defer`); a batch that fills the chip by itself keeps the launch pair (its virtual
         # branch shares the local workgroups there)
@@ -163,38 +165,18 @@ class ResidentTrainStep:
         self._sync = torch.zeros(32 + B, dtype=torch.int32, device=dev) if self.one_launch else None
         P = int(_hip.lib().hscn_resident_param_count(F, H, L, C))
         self.P = P
-        self.partials = torch.empty(B, P + 1, **f32)
-        self.grads = torch.zeros(P + 1, **f32)
+        self.partials = torch.empty(B, P + 1, dtype=torch.float32, device=dev)
+        self.grads = torch.zeros(P + 1, dtype=torch.float32, device=dev)
         self.loss = self.grads[P:P + 1].view(())
         self._tail = _engine._LossTail(ptr(self.pred), ptr(self.target), int(self.kind))
         # parameter -> slice of the flat gradient buffer (launch order: {W_ll, b_ll} per layer, W1, b1, W2, b2)
-        views: List[Tuple[Tensor, Tensor]] = []
-        off = 0
-        mparams = model._resident_params()
-        for l in range(L):
-            fin = F if l == 0 else H
-            views.append((mparams[9 * l], self.grads[off: off + H * fin].view(H, fin))); off += H * fin
-            views.append((mparams[9 * l + 1], self.grads[off: off + H])); off += H
-        for p, n in zip(mparams[9 * L:], (H * H, H, C * H, C)):
-            views.append((p, self.grads[off: off + n].view_as(p))); off += n
-        assert off == P
-        self.param_grads = views
-
-    def bind_grads(self) -> None:
-        has = {id(p) for p, _ in self.param_grads}
-        for p in self.model.parameters():
-            if id(p) not in has:
-                p.grad = None
-        for p, g in self.param_grads:
-            p.grad = g
+        mp = model._resident_params()
+        order = [p for l in range(L) for p in mp[9 * l: 9 * l + 2]] + list(mp[9 * L:])
+        self.param_grads = list(zip(order, _engine.grad_views(self.grads, [p.shape for p in order], P)))
 
     def _job(self, xv_out: Optional[Tensor]) -> "_engine._VirtualJob":
-        N, V, F, H, L, C, B = self.dims
-        m = self.meta
-        return _engine._VirtualJob(ptr(self.x_virtual), ptr(self.ei[VV]), self.ei[VV].size(1), ptr(self.ei[LV]),
-                                   self.ei[LV].size(1), ptr(m.vptr), ptr(m.eptr_vv), ptr(m.eptr_lv),
-                                   ctypes.cast(self._table, ctypes.c_void_p), ptr(xv_out), V, m.max_v, m.max_evv,
-                                   self.slope, *([ptr(t) for t in self._state] if self._state is not None else [None] * 6))
+        return _engine.virtual_job(self.x_virtual, self.ei[VV], self.ei[LV], self.meta, self._table, self.slope,
+                                   self._state, xv_out)
 
     @property
     def advances_sync(self) -> bool:
@@ -206,41 +188,30 @@ class ResidentTrainStep:
 
     def run(self) -> Tensor:
         """Issue the step on the current stream; returns ``loss`` (valid once the stream has run)."""
-        N, V, F, H, L, C, B = self.dims
         m = self.meta
-        W1, b1, W2, b2 = self._params[9 * L:]
-        st = stream()
         ei_ll = self.ei[LL]
-        E_ll = ei_ll.size(1)
-        csr_rp, csr_col, dinv = self.csr
-        bwd_args = (ptr(self.x_local), ptr(ei_ll), E_ll, ptr(m.lptr), ptr(m.eptr_ll), N, B, F, H, L, C,
-                    self.head_act, self._wll_table, ptr(W1), ptr(W2), ptr(self.acts), ptr(self.pooled), ptr(self.z),
-                    None, None, ptr(csr_rp), ptr(csr_col), ptr(dinv), m.max_n, m.max_ell, ptr(self.partials),
-                    ptr(self.grads), ptr(m.flag), ctypes.byref(self._tail))
         if self.one_launch:
+            N, V, F, H, L, C, B = self.dims
+            W1, b1, W2, b2 = self._head
             with_v = self.idle_cus and self.virtual is not None
-            call("hscn_resident_train_step" + self._acc + self._sfx, ptr(self.x_local), ptr(ei_ll), E_ll, ptr(m.lptr),
-                 ptr(m.eptr_ll), N, B, F, H, L, C, self.head_act, self._table, ptr(W1), ptr(b1), ptr(W2), ptr(b2),
-                 m.max_n, m.max_ell, ptr(self.target), int(self.kind), ptr(self.pred), ptr(self.score),
+            call("hscn_resident_train_step" + self._acc + self._sfx, ptr(self.x_local), ptr(ei_ll), ei_ll.size(1),
+                 ptr(m.lptr), ptr(m.eptr_ll), N, B, F, H, L, C, self.head_act, self._table, ptr(W1), ptr(b1), ptr(W2),
+                 ptr(b2), m.max_n, m.max_ell, ptr(self.target), int(self.kind), ptr(self.pred), ptr(self.score),
                  ptr(self.partials), ptr(self.grads), ptr(self.acts) if with_v else None,
                  ptr(self._sync) if with_v else None, ptr(m.flag),
                  ctypes.byref(self._job(self.virtual)) if with_v else None,
-                 ctypes.byref(self.structure.c) if self.structure is not None else None, st)
-        elif self.defer:
-            call("hscn_resident_fwd_with_virtual" + self._sfx, ptr(self.x_local), ptr(ei_ll), E_ll, ptr(m.lptr), ptr(m.eptr_ll),
-                 N, B, F, H, L, C, self.head_act, self._table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), m.max_n,
-                 m.max_ell, ptr(self.acts), ptr(self.pooled), ptr(self.z), ptr(self.pred), ptr(self.score),
-                 ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), ctypes.byref(self._job(None)), st)
-            call("hscn_resident_bwd_with_virtual" + self._acc + self._sfx, *bwd_args, ctypes.byref(self._job(self.virtual)), st)
+                 ctypes.byref(self.structure.c) if self.structure is not None else None, stream())
+            return self.loss
+        if self.defer:
+            _engine.launch_fwd_with_virtual(self._sfx, self.x_local, ei_ll, m, self.dims, self.head_act, self._table,
+                                            self._head, self._out, self._job(None))
         else:
-            cv = int(bool(self.model.compute_virtual))
-            call("hscn_resident_fwd" + self._sfx, ptr(self.x_local), ptr(self.x_virtual), ptr(ei_ll), E_ll, ptr(self.ei[VV]),
-                 self.ei[VV].size(1), ptr(self.ei[LV]), self.ei[LV].size(1), ptr(m.lptr), ptr(m.vptr),
-                 ptr(m.eptr_ll), ptr(m.eptr_vv), ptr(m.eptr_lv), N, V, B, F, H, L, C, self.head_act, self.slope,
-                 self._table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), m.max_n, m.max_v, m.max_ell, m.max_evv, cv,
-                 ptr(self.acts), ptr(self.pooled), ptr(self.z), ptr(self.pred), ptr(self.score),
-                 ptr(self.virtual) if cv else None, ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), st)
-            call("hscn_resident_bwd" + self._acc + self._sfx, *bwd_args, st)
+            _engine.launch_fwd(self._sfx, self.x_local, self.x_virtual, ei_ll, self.ei[VV], self.ei[LV], m, self.dims,
+                               self.head_act, self.slope, self._table, self._head, self.model.compute_virtual,
+                               self._out, self.virtual)
+        _engine.launch_bwd(self._acc + self._sfx, self.x_local, ei_ll, m, self.dims, self.head_act, self._wll_table,
+                           self._head[0], self._head[2], self.acts, self.pooled, self.z, self.csr, None, None,
+                           self.partials, self.grads, self._tail, self._job(self.virtual) if self.defer else None)
         return self.loss
 
     def check(self) -> None:
@@ -354,13 +325,8 @@ class ScnTrainStep:
             meta.ticket = ws.ticket
         self.S, self.y, self.stats, self.ss = ws.S[:N], ws.y[:N], ws.stats[:B], ws.ss[:B]
         self.losses, self.ex, self.partials, self.grads, self.one = ws.losses, ws.ex, ws.partials, ws.grads, ws.one
-        P = int(self.grads.numel())
-        views, off = [], 0
-        for p in self._mp:
-            views.append((p, self.grads[off: off + p.numel()].view_as(p)))
-            off += p.numel()
-        assert off == P
-        self.param_grads = views
+        self.param_grads = list(zip(self._mp, _engine.grad_views(self.grads, [p.shape for p in self._mp],
+                                                                  self.grads.numel())))
         self._one_args = {}
         self._cache = structure_pool.take(N, E, B) if (structure_pool is not None and self.one_launch) else None
 
@@ -379,68 +345,50 @@ class ScnTrainStep:
                 and all(p.is_contiguous() for p in self._mp)
                 and [id(p) for p in getattr(opt, "params", [])] == [id(p) for p in self._mp])
 
+    def _one_launch_args(self, W, opt) -> tuple:
+        """hscn_scn_resident_train_step's arguments but the stream (``W``: the five parameters, contiguous)."""
+        N, F, H, K, B, E = self.dims
+        m = self.meta
+        return (ptr(self.x), ptr(self.ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K, self.act,
+                *[ptr(w) for w in W], ptr(self.one), ptr(self.one), m.max_n, m.max_e, ptr(self.S), ptr(self.stats),
+                ptr(self.losses), ptr(m.ticket), ptr(self.partials), ptr(self.grads), ptr(m.flag),
+                ctypes.byref(opt.c) if opt is not None else None,
+                ctypes.byref(self._cache) if self._cache is not None else None)
+
     def run(self, opt=None) -> Tensor:
         """``opt``: ``optimizer.step()`` (train/train_clustering.py:50) in the tail of the same launch -- see
         ``fuses_optimizer``; the parameters are updated in place, ``grads`` still receives the gradient."""
-        if self.one_launch:
-            # the argument list of a step is the same every visit (device pointers of buffers allocated once, the
-            # parameters' own storage): built on the first call, per optimizer; a visit is then ONE foreign call
-            key = id(opt)
-            hit = self._one_args.get(key)
-            if hit is None or hit[0] != tuple(p.data_ptr() for p in self._mp):
-                if opt is not None and not self.fuses_optimizer(opt):
-                    raise ValueError("this step cannot carry the optimizer step (see ScnTrainStep.fuses_optimizer)")
-                N, F, H, K, B, E = self.dims
-                m = self.meta
-                W = [p if p.is_contiguous() else None for p in self._mp]
-                if any(w is None for w in W):
-                    hit = None          # (non-contiguous parameters: the slow path below makes copies every call)
-                else:
-                    hit = (tuple(p.data_ptr() for p in self._mp),
-                           (ptr(self.x), ptr(self.ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
-                            self.act, *[ptr(w) for w in W], ptr(self.one), ptr(self.one), m.max_n, m.max_e,
-                            ptr(self.S), ptr(self.stats), ptr(self.losses), ptr(m.ticket), ptr(self.partials),
-                            ptr(self.grads), ptr(m.flag), ctypes.byref(opt.c) if opt is not None else None,
-                            ctypes.byref(self._cache) if self._cache is not None else None))
-                    self._one_args[key] = hit
-            if hit is not None:
-                call("hscn_scn_resident_train_step" + self._sfx, *hit[1], stream())
-                if self._cache is not None:
-                    self._cache.ready = 1          # (read at issue time: the launch in flight saw 0 and exports)
-                return self.losses[2]
-        N, F, H, K, B, E = self.dims
-        m = self.meta
-        W_rel, b_rel, W_root, W_mlp, b_mlp = (p.contiguous() for p in self._mp)
-        st = stream()
-        eip = ptr(self.ei) if E else None
-        if opt is not None:
-            raise ValueError("this step cannot carry the optimizer step (see ScnTrainStep.fuses_optimizer)")
-        if self.one_launch:
-            call("hscn_scn_resident_train_step" + self._sfx, ptr(self.x), eip, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H,
-                 K, self.act, ptr(W_rel), ptr(b_rel), ptr(W_root), ptr(W_mlp), ptr(b_mlp), ptr(self.one),
-                 ptr(self.one), m.max_n, m.max_e, ptr(self.S), ptr(self.stats), ptr(self.losses), ptr(m.ticket),
-                 ptr(self.partials), ptr(self.grads), ptr(m.flag), None,
-                 ctypes.byref(self._cache) if self._cache is not None else None, st)
-            if self._cache is not None:
-                self._cache.ready = 1
+        if not self.one_launch:
+            if opt is not None:
+                raise ValueError("this step cannot carry the optimizer step (see ScnTrainStep.fuses_optimizer)")
+            W = [p.contiguous() for p in self._mp]
+            _engine.launch_scn_fwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act, W, self.S, self.y,
+                                   self.stats, self.ss, self.losses, self.meta.ticket, self.ex)
+            _engine.launch_scn_bwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act, W[3], self.S, self.y,
+                                   self.stats, self.ss, self.one, self.one, self.ex, self.partials, self.grads)
             return self.losses[2]
-        call("hscn_scn_resident_fwd" + self._sfx, ptr(self.x), eip, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K, self.act,
-             ptr(W_rel), ptr(b_rel), ptr(W_root), ptr(W_mlp), ptr(b_mlp), m.max_n, m.max_e, ptr(self.S), ptr(self.y),
-             ptr(self.stats), ptr(self.ss), ptr(self.losses), ptr(m.ticket), *[ptr(t) for t in self.ex], ptr(m.flag), st)
-        call("hscn_scn_resident_bwd" + self._sfx, ptr(self.x), eip, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K, self.act,
-             ptr(W_mlp), ptr(self.S), ptr(self.y), ptr(self.stats), ptr(self.ss), ptr(self.one), ptr(self.one),
-             *[ptr(t) for t in self.ex], m.max_n, m.max_e, ptr(self.partials), ptr(self.grads), ptr(m.flag), st)
+        # the argument list of a step is the same every visit (device pointers of buffers allocated once, the
+        # parameters' own storage): built on the first call, per optimizer; a visit is then ONE foreign call
+        key = id(opt)
+        hit = self._one_args.get(key)
+        if hit is None or hit[0] != tuple(p.data_ptr() for p in self._mp):
+            if opt is not None and not self.fuses_optimizer(opt):
+                raise ValueError("this step cannot carry the optimizer step (see ScnTrainStep.fuses_optimizer)")
+            if all(p.is_contiguous() for p in self._mp):
+                hit = self._one_args[key] = (tuple(p.data_ptr() for p in self._mp), self._one_launch_args(self._mp, opt))
+            else:                   # (non-contiguous parameters: copies, every call; opt is None, see fuses_optimizer)
+                W = [p.contiguous() for p in self._mp]
+                hit = (None, self._one_launch_args(W, None))
+        call("hscn_scn_resident_train_step" + self._sfx, *hit[1], stream())
+        if self._cache is not None:
+            self._cache.ready = 1          # (read at issue time: the launch in flight saw 0 and exports)
         return self.losses[2]
 
     def run_forward(self) -> Tensor:
         """The forward launch alone (the assignment pass, train/train_clustering.py:57-69): refreshes ``S``."""
-        N, F, H, K, B, E = self.dims
-        m = self.meta
-        W_rel, b_rel, W_root, W_mlp, b_mlp = (p.contiguous() for p in self._mp)
-        call("hscn_scn_resident_fwd" + self._sfx, ptr(self.x), ptr(self.ei) if E else None, E, ptr(m.nptr), ptr(m.eptr),
-             N, B, F, H, K, self.act, ptr(W_rel), ptr(b_rel), ptr(W_root), ptr(W_mlp), ptr(b_mlp), m.max_n, m.max_e,
-             ptr(self.S), ptr(self.y), ptr(self.stats), ptr(self.ss), ptr(self.losses), ptr(m.ticket),
-             *([None] * 6), ptr(m.flag), stream())
+        _engine.launch_scn_fwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act,
+                               [p.contiguous() for p in self._mp], self.S, self.y, self.stats, self.ss, self.losses,
+                               self.meta.ticket)
         return self.S
 
     def check(self) -> None:
@@ -502,12 +450,8 @@ class ScnEpochRunner:
                          torch.empty(max(E, 1), **i32), torch.empty(max(N, 1), 16, **f32), torch.empty(max(N, 1), **f32))
         P = int(_hip.lib().hscn_scn_resident_param_count(F, H, K))
         self.grads = torch.zeros(P, **f32)
-        views, off = [], 0
-        for p_ in self._mp:
-            views.append((p_, self.grads[off: off + p_.numel()].view_as(p_)))
-            off += p_.numel()
-        self.param_grads = views
-        self.optimizer = FlatAdam.from_config(optim_type, views, self.grads, lr, weight_decay)
+        self.param_grads = list(zip(self._mp, _engine.grad_views(self.grads, [p_.shape for p_ in self._mp], P)))
+        self.optimizer = FlatAdam.from_config(optim_type, self.param_grads, self.grads, lr, weight_decay)
         self._forward(export=True)                      # one launch: every graph's structure
         c = self._cache_t
         self._xpad = torch.zeros(max(N, 1), 16, **f32)  # the features as LDS holds them: float, 16 columns
@@ -515,14 +459,8 @@ class ScnEpochRunner:
         self._cache = _ScnStructC(ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(c[5]), ptr(self._xpad), 1)
 
     def _forward(self, export: bool) -> None:
-        N, F, H, K, G, E = self.dims
-        m = self.meta
-        W_rel, b_rel, W_root, W_mlp, b_mlp = self._mp
-        ex = [ptr(t) for t in self._cache_t] if export else [None] * 6
-        call("hscn_scn_resident_fwd" + self._sfx, ptr(self.x), ptr(self.ei) if E else None, E, ptr(m.nptr), ptr(m.eptr),
-             N, G, F, H, K, self.act, ptr(W_rel), ptr(b_rel), ptr(W_root), ptr(W_mlp), ptr(b_mlp), m.max_n, m.max_e,
-             ptr(self.S), ptr(self._y), ptr(self._stats), ptr(self._ss), ptr(self.losses), ptr(self._ticket), *ex,
-             ptr(m.flag), stream())
+        _engine.launch_scn_fwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act, self._mp, self.S, self._y,
+                               self._stats, self._ss, self.losses, self._ticket, self._cache_t if export else None)
 
     def run(self, visits: int) -> None:
         """``visits`` graph visits in dataset order (visit v takes graph v mod G).  One call; the launches are
@@ -552,7 +490,7 @@ def _mpnn_default_seed0() -> int:
     return (torch.initial_seed() * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & 0xFFFFFFFFFFFFFFFF
 
 
-class MPNNResidentTrainStep:
+class MPNNResidentTrainStep(_FlatGradStep):
     """``for p: p.grad = None; pred = model(batch); loss, score = criterion(loss_fn, pred, batch.y); loss.backward()``
     for the MPNN baseline (model/mpnn.py with GCNConv) as ONE launch plus the gradient fold (include/hscn.h:
     hscn_mpnn_train_step), on buffers allocated once -- ``ResidentTrainStep``'s outward contract.
@@ -614,26 +552,13 @@ class MPNNResidentTrainStep:
         self.step_word = step_word if step_word is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
         self.inv_count = 1.0 / float(B * C)
-        views: List[Tuple[Tensor, Tensor]] = []
-        off = 0
-        for p in model.resident_params():
-            views.append((p, self.grads[off: off + p.numel()].view_as(p)))
-            off += p.numel()
-        assert off == P
-        self.param_grads = views
+        mparams = model.resident_params()
+        self.param_grads = list(zip(mparams, _engine.grad_views(self.grads, [p.shape for p in mparams], P)))
 
     @property
     def advances_sync(self) -> bool:
         """Every ``run()`` adds one to ``step_word`` on the device."""
         return True
-
-    def bind_grads(self) -> None:
-        has = {id(p) for p, _ in self.param_grads}
-        for p in self.model.parameters():
-            if id(p) not in has:
-                p.grad = None
-        for p, g in self.param_grads:
-            p.grad = g
 
     def run(self) -> Tensor:
         """Issue the step on the current stream; returns ``loss`` (valid once the stream has run)."""
