@@ -372,8 +372,10 @@ __global__ void k_dense_adj_ragged(const int64_t* __restrict__ row, const int64_
 
 // the same counts as BYTES: adj8 [B, nmax, lda8], lda8 = nmax rounded up to 32 (16-byte loads of a row never leave
 // it), zero on entry -- a quarter of the float adjacency's bytes for the matrix-core products that stream it
-// (csrc/dense.hip k_adj_s).  A byte is bumped through an atomic add on its aligned word; a count that would pass
-// 255 (more than 255 parallel edges) raises flag bit 16 instead of carrying into the neighbour.
+// (csrc/dense.hip k_adj_s).  A byte is bumped through a compare-and-swap on its aligned word that never lets it wrap:
+// a count already at 255 (more than 255 parallel edges) stays at 255 and raises flag bit 16, and no other byte of the
+// word -- a neighbouring entry or row padding -- ever changes.  (A plain word add would carry the 256th edge into the
+// next byte.)
 __global__ void k_dense_adj_ragged_u8(const int64_t* __restrict__ row, const int64_t* __restrict__ col, int64_t E,
                                       const int32_t* __restrict__ nptr, const int32_t* __restrict__ gid, int64_t N,
                                       int64_t nmax, int64_t lda8, int mode, unsigned int* __restrict__ adjw,
@@ -397,8 +399,17 @@ __global__ void k_dense_adj_ragged_u8(const int64_t* __restrict__ row, const int
     return;
   }
   const unsigned sh = (unsigned)(o & 3) * 8u;
-  const unsigned old = atomicAdd(&adjw[o >> 2], 1u << sh);
-  if (((old >> sh) & 0xffu) == 0xffu && flag) atomicOr(flag, 16);
+  unsigned int* w = &adjw[o >> 2];
+  unsigned cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (;;) {
+    if (((cur >> sh) & 0xffu) == 0xffu) {
+      if (flag) atomicOr(flag, 16);
+      return;
+    }
+    const unsigned seen = atomicCAS(w, cur, cur + (1u << sh));
+    if (seen == cur) return;
+    cur = seen;
+  }
 }
 
 // gcn_norm's self-loop bookkeeping (PyG add_remaining_self_loops) with a STATIC output shape, so that

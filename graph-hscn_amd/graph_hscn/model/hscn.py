@@ -88,6 +88,21 @@ class SCN(nn.Module):
             self.mlp.append(Linear(out_channels, units))
             self.mlp.append(nn.Identity())
         self.mlp.append(Linear(out_channels, num_clusters))
+        # device flags of the ragged byte-adjacency route, OR-ed across the calls since the last check_adjacency():
+        # bit 16 = a pair of nodes had more than 255 parallel edges (its entry saturated at 255, so that call's
+        # losses are not the reference's).  Read at a point that synchronises anyway: the route never waits on the host.
+        self.register_buffer("adj_flag", torch.zeros(1, dtype=torch.int32), persistent=False)
+
+    def check_adjacency(self) -> None:
+        """Raise if a byte adjacency of a dense-route call since the previous check saturated, and clear the flag
+        (synchronises with the device).  Callers that run the byte route outside train_clustering call it where they
+        read results back."""
+        v = int(self.adj_flag.item())
+        if v:
+            self.adj_flag.zero_()
+        if v & 16:
+            raise OverflowError("dense MinCUT route: more than 255 parallel edges between two nodes saturated the byte "
+                                "adjacency, so the losses differ from the reference's (set HSCN_DENSE_ADJ=f32)")
 
     def _dense(self) -> bool:
         return self.mincut_route == "dense" or (self.mincut_route == "auto" and self.num_clusters >= 64)
@@ -197,11 +212,13 @@ class SCN(nn.Module):
                 # and the products that stream it move a quarter of the bytes; HSCN_DENSE_ADJ=f32 keeps floats)
                 as_bytes = os.environ.get("HSCN_DENSE_ADJ", "u8") != "f32"
                 want_sym = as_bytes and os.environ.get("HSCN_DENSE_SYM", "1") != "0"     # (A/B: 0 = always compute A^T S)
+                flag = self.adj_flag if as_bytes else None
                 if raw_edge_index is not None:
                     adj = to_dense_adj_ragged(raw_edge_index, node_ptr, node_graph, Bg, ng, raw=True, as_bytes=as_bytes,
-                                              symmetry=want_sym)
+                                              flag=flag, symmetry=want_sym)
                 else:
-                    adj = to_dense_adj_ragged(edge_index, node_ptr, node_graph, Bg, ng, as_bytes=as_bytes, symmetry=want_sym)
+                    adj = to_dense_adj_ragged(edge_index, node_ptr, node_graph, Bg, ng, as_bytes=as_bytes, flag=flag,
+                                              symmetry=want_sym)
                 # byte route: one pass flags the graphs whose adjacency is not symmetric; the others (undirected graphs:
                 # the norm) take the backward's A^T S from the forward's A S
                 asym = None

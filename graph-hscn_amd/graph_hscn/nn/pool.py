@@ -55,7 +55,8 @@ def to_dense_adj_ragged(edge_index: Tensor, nptr: Tensor, gid: Tensor, num_graph
     B, n = int(num_graphs), int(max_nodes)
     if as_bytes:
         # the counts as bytes, rows padded to a multiple of 32: what the batched dense route streams through the
-        # matrix cores (a quarter of the float adjacency's bytes; exact up to 255 parallel edges, flag bit 16 beyond)
+        # matrix cores (a quarter of the float adjacency's bytes; exact up to 255 parallel edges -- beyond that the
+        # entry stays at 255, no other byte changes, and bit 16 of ``flag`` (int32 [1], when given) is raised)
         # symmetry=True (as_bytes only): also returns asym int32 [B] -- 1 where a graph's adjacency is NOT symmetric
         # (hscn_dense_adj_asymmetry_u8); the flags live behind the adjacency in the same zero-filled allocation
         lda = (n + 31) // 32 * 32

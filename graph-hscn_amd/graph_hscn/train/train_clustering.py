@@ -192,4 +192,5 @@ def train_clustering(logger, dataset, model: SCN, model_cfg, optim_cfg, training
             else:
                 p = ptr.numpy()
                 cluster_all_lst.extend(ids[p[k]:p[k + 1]] for k in range(len(graphs)))
+    model.check_adjacency()                            # (the read-backs above have synchronised)
     return cluster_all_lst
