@@ -21,12 +21,14 @@ constexpr int CT = 256;
 // at 6.7 us either way -- cursor -> ids -> ranges -> data is four dependent trips to memory plus the launch itself.)
 template <int NT>
 __device__ __forceinline__ void slot_ranges(const int64_t* const (&p)[NT], const int64_t* __restrict__ ids, int j,
-                                            long long* red /*[NT][CT / 64]*/, long long (&off)[NT], long long (&size)[NT]) {
+                                            int64_t G, long long* red /*[NT][CT / 64]*/, long long (&off)[NT],
+                                            long long (&size)[NT]) {
   long long acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = 0;
   for (int q = threadIdx.x; q < j; q += CT) {
     const int64_t g = ids[q];
+    if (g < 0 || g >= G) continue;   // an id outside the dataset has no ranges to read; its own blocks raise the flag
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] += p[t][g + 1] - p[t][g];
   }
@@ -69,18 +71,18 @@ __global__ void __launch_bounds__(CT) k_collate_gather(const hscn_hetero_dataset
   if (part <= 1) {
     const int64_t* const tb[1] = {part == 0 ? D.nptr : D.vptr};
     long long o1[1], s1[1];
-    slot_ranges<1>(tb, ids, j, red, o1, s1);
+    slot_ranges<1>(tb, ids, j, D.G, red, o1, s1);
     if (part == 0) { on = o1[0]; n = s1[0]; } else { ov = o1[0]; nv = s1[0]; }
   } else if (part <= 4) {
     const int r = part - 2;
     const int64_t* const tb[3] = {D.nptr, D.vptr, D.eptr[r]};
     long long o3[3], s3[3];
-    slot_ranges<3>(tb, ids, j, red, o3, s3);
+    slot_ranges<3>(tb, ids, j, D.G, red, o3, s3);
     on = o3[0]; n = s3[0]; ov = o3[1]; nv = s3[1]; oe[r] = o3[2]; ne[r] = s3[2];
   } else {
     const int64_t* const tb[5] = {D.nptr, D.vptr, D.eptr[0], D.eptr[1], D.eptr[2]};
     long long o5[5], s5[5];
-    slot_ranges<5>(tb, ids, j, red, o5, s5);
+    slot_ranges<5>(tb, ids, j, D.G, red, o5, s5);
     on = o5[0]; n = s5[0]; ov = o5[1]; nv = s5[1];
     for (int r = 0; r < 3; ++r) { oe[r] = o5[2 + r]; ne[r] = s5[2 + r]; }
   }
@@ -147,7 +149,7 @@ __global__ void __launch_bounds__(CT) k_collate_structure(const hscn_hetero_data
   {
     const int64_t* const tb[2] = {part <= 1 ? D.nptr : D.vptr, D.eptr[r]};
     long long o2[2], s2[2];
-    slot_ranges<2>(tb, ids, j, red, o2, s2);
+    slot_ranges<2>(tb, ids, j, D.G, red, o2, s2);
     if (part <= 1) { on = o2[0]; n = s2[0]; } else { ov = o2[0]; nv = s2[0]; }
     oe = o2[1]; ne = s2[1];
   }

@@ -315,11 +315,13 @@ __global__ void k_argmax(const float* __restrict__ S, int64_t* __restrict__ ids,
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* r = S + i * K;
+  // Tensor.max(1)[1]: the first maximum wins a tie, and a NaN is greater than everything -- the first NaN of a row
+  // is its answer (once best is a NaN neither test below is true again)
   float best = r[0];
   int bi = 0;
   for (int k = 1; k < K; ++k) {
     float v = r[k];
-    if (v > best) { best = v; bi = k; }
+    if (v > best || (v != v && best == best)) { best = v; bi = k; }
   }
   ids[i] = bi;
 }
