@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("HSCN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libhscn.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 ACT = {"identity": 0, "relu": 1, "elu": 2, "tanh": 3}
 
 P = c_void_p
@@ -123,6 +123,10 @@ _SIGNATURES = {
                                      c_int, P, c_int, c_float, P, P, P, P, P, c_float, c_uint64, P, P]),
     "hscn_mpnn_forward": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int,
                                   c_int, P, c_int, c_float, P, P, P, P, P, P]),
+    # ABI 21: GATConv with the implicit self loop, narrow-row kernels (csrc/gat_loops.hip)
+    "hscn_gat_loop_fwd": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int, c_float, c_int, P]),
+    "hscn_gat_loop_bwd_dst": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int, c_float, P]),
+    "hscn_gat_loop_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_float, P]),
 }
 _SIGNATURES["hscn_mpnn_train_step_acc"] = _SIGNATURES["hscn_mpnn_train_step"]
 # IEEE-half storage twins (include/hscn.h: hscn_resident_*_f16): same argument lists

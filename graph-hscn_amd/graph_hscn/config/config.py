@@ -39,7 +39,10 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 }
 # config.py:19-23 also lists "gin": GINConv(dim, hidden, add_self_loops=...) raises a
 # TypeError in PyG (GINConv takes an nn, not channel counts), so only gcn/gat can be
-# built through build_conv_relation (model/hscn.py:117-125).
+# built through build_conv_relation (model/hscn.py:117-125).  Both also build the MPNN baseline
+# (model/mpnn.py:29-32 calls conv(in, out), i.e. add_self_loops=True): "gcn" through GCNConv's
+# explicit-loop relation, "gat" through GATConv's shared transform and implicit-loop kernels
+# (nn/conv.py, csrc/gat_loops.hip).  Only "gcn" qualifies for the one-launch MPNN step.
 CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv}
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
 DATASETS_NUM_FEATURES: dict[str, int] = {"peptides_func": 9, "peptides_struct": 9}

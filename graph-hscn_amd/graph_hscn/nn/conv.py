@@ -118,34 +118,65 @@ class GCNConv(nn.Module):
 
 
 class GATConv(nn.Module):
-    """PyG GATConv as built for local->virtual (model/hscn.py:85-87): bipartite
-    ``in_channels=(-1,-1)``, heads=1, negative_slope=0.2, dropout=0,
-    ``add_self_loops=False``."""
+    """PyG GATConv, heads=1, negative_slope=0.2, dropout=0, in its two uses:
+
+    * ``add_self_loops=False``: the bipartite local->virtual relation (model/hscn.py:85-87, ``in_channels=(-1,-1)``)
+      with two transforms ``lin_src`` / ``lin_dst`` (also for an int ``in_channels``);
+    * ``add_self_loops=True`` (PyG's default, what ``MPNN`` constructs: model/mpnn.py:29-32) with an int
+      ``in_channels``: a homogeneous graph, ONE transform (``lin_dst is lin_src``, as PyG builds it), input self
+      loops removed and one loop per node appended.  ``state_dict`` carries the shared weight under both
+      ``lin_src.weight`` and ``lin_dst.weight`` like PyG's; ``parameters()`` yields it once."""
 
     def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, heads: int = 1,
                  negative_slope: float = 0.2, add_self_loops: bool = True, cached: bool = False,
                  bias: bool = True):
         super().__init__()
-        if heads != 1 or add_self_loops:
-            raise NotImplementedError("the hot path builds GATConv with heads=1, add_self_loops=False")
-        if isinstance(in_channels, int):
-            in_channels = (in_channels, in_channels)
+        if heads != 1:
+            raise NotImplementedError("the hot path builds GATConv with heads=1")
+        if add_self_loops and not isinstance(in_channels, int):
+            raise NotImplementedError("GATConv(add_self_loops=True) is the homogeneous operator: int in_channels "
+                                      "(a bipartite relation has no self loops to add)")
+        self.add_self_loops = bool(add_self_loops)
         self.negative_slope = negative_slope
         self.out_channels = out_channels
-        self.lin_src = Linear(in_channels[0], out_channels, bias=False, weight_initializer="glorot")
-        self.lin_dst = Linear(in_channels[1], out_channels, bias=False, weight_initializer="glorot")
+        if self.add_self_loops:
+            self.lin_src = Linear(in_channels, out_channels, bias=False, weight_initializer="glorot")
+            self.lin_dst = self.lin_src
+        else:
+            if isinstance(in_channels, int):
+                in_channels = (in_channels, in_channels)
+            self.lin_src = Linear(in_channels[0], out_channels, bias=False, weight_initializer="glorot")
+            self.lin_dst = Linear(in_channels[1], out_channels, bias=False, weight_initializer="glorot")
         self.att_src = nn.Parameter(_glorot(torch.empty(1, 1, out_channels)))
         self.att_dst = nn.Parameter(_glorot(torch.empty(1, 1, out_channels)))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
 
     def forward(self, x: Union[Tensor, Tuple[Tensor, Tensor]], edge_index: Union[Tensor, Relation],
                 act: str = "identity") -> Tensor:
+        if self.add_self_loops:
+            return self._forward_loops(x, edge_index, act)
         x_src, x_dst = (x, x) if isinstance(x, Tensor) else x
         self.lin_src.materialize(x_src.size(-1), x_src)
         self.lin_dst.materialize(x_dst.size(-1), x_dst)
         rel = _relation(edge_index, x_src.size(0), x_dst.size(0), both=torch.is_grad_enabled())
         return Fh.GATConvFn.apply(x_src, x_dst, self.lin_src.weight, self.lin_dst.weight, self.att_src,
                                   self.att_dst, self.bias, rel, self.negative_slope, ACT[act])
+
+    def _forward_loops(self, x: Tensor, edge_index: Union[Tensor, Relation], act: str) -> Tensor:
+        """``edge_index`` (or the Relation) is the RAW edge list: the loops are this layer's to add."""
+        if not isinstance(x, Tensor):
+            raise TypeError("GATConv(add_self_loops=True) takes one node feature tensor")
+        self.lin_src.materialize(x.size(-1), x)
+        n = x.size(0)
+        both = torch.is_grad_enabled()
+        rel = _relation(edge_index, n, n, both=both)
+        if rel.num_src != n or rel.num_dst != n:
+            raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, x has {n} rows")
+        loops = None
+        if rel.max_in_degree > Fh.GAT_NARROW_MAX_DEGREE:    # one synchronising read per relation, then cached
+            loops = self_loop_relation_of(rel.edge_index, n, both=both)
+        return Fh.GATLoopFn.apply(x, self.lin_src.weight, self.att_src, self.att_dst, self.bias, rel, loops,
+                                  self.negative_slope, ACT[act])
 
 
 class HeteroConv(nn.Module):

@@ -293,6 +293,82 @@ class GATConvFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# GATConv, heads=1, homogeneous, add_self_loops=True, one shared transform (the MPNN baseline's "gat")
+# --------------------------------------------------------------------------- #
+# Dispatch of GATLoopFn, per call: a relation whose largest raw in-degree is at most this takes the narrow-row
+# kernels (csrc/gat_loops.hip, a lane group walks its row serially); above it the wave-per-row kernels of
+# csrc/gat.hip run over the explicit-loop relation.  Either side is correct at any degree; the value is the
+# measured crossover of forward + both backward launches on a Peptides-shaped batch of 128 with one hub row
+# (profiles/r05_gat_mpnn.json: at 10 the narrow trio is ahead by more than the spread, at 18 behind).
+GAT_NARROW_MAX_DEGREE = 10
+
+
+class GATLoopFn(Function):
+    """(x [N,F], W [H,F], att_src, att_dst, bias) -> act(GATConv(x, edge_index)) with PyG's self-loop handling.
+    ``rel`` is the relation of the RAW edge list (input loops are skipped in the kernels, each node's own term is added
+    last); ``rel_loops`` is None for the narrow-row kernels, or the relation over ``with_self_loops(edge_index)``
+    for the wave-per-row kernels."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, W: Tensor, att_src: Tensor, att_dst: Tensor, bias: Optional[Tensor],
+                rel: Relation, rel_loops: Optional[Relation], slope: float, act: int):
+        x, W, bias = _c(x), _c(W), _c(bias)
+        att_s, att_d = _c(att_src).view(-1), _c(att_dst).view(-1)
+        h, a_s = linear_raw(x, W, att=att_s)
+        H = h.shape[1]
+        a_d = linear_raw(h, att_d.view(1, H))[0].view(-1)
+        N, dev = h.shape[0], h.device
+        out = torch.empty(N, H, dtype=torch.float32, device=dev)
+        if rel_loops is None:
+            kept = torch.empty(max(N, 1), 2, dtype=torch.float32, device=dev)          # row max, exp-sum
+            call("hscn_gat_loop_fwd", ptr(rel.csr.rowptr), ptr(rel.csr.col), ptr(a_s), ptr(a_d), ptr(h), ptr(bias),
+                 ptr(kept), ptr(out), N, H, float(slope), act, stream())
+        else:
+            kept = torch.empty(max(rel_loops.num_edges, 1), dtype=torch.float32, device=dev)   # alpha per slot
+            call("hscn_gat_segment_fwd", ptr(rel_loops.csr.rowptr), ptr(rel_loops.csr.col), ptr(a_s), ptr(a_d),
+                 ptr(h), ptr(bias), ptr(kept), ptr(out), N, H, float(slope), 0, act, stream())
+        ctx.rel, ctx.rel_loops = rel, rel_loops
+        ctx.act, ctx.slope, ctx.has_bias = act, float(slope), bias is not None
+        ctx.save_for_backward(x, W, att_s, att_d, h, a_s, a_d, kept, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, W, att_s, att_d, h, a_s, a_d, kept, out = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        N, H = h.shape
+        dev = h.device
+        g = act_bwd_raw(_c(g), out, ctx.act)
+        gb = linear_bwd_w_raw(g, None, False, True)[1] if (ctx.has_bias and ctx.needs_input_grad[4]) else None
+        g_a = torch.empty(max(N, 1), 2, dtype=torch.float32, device=dev)    # {dL/da_src, dL/da_dst} per node
+        g_h = torch.empty(N, H, dtype=torch.float32, device=dev)
+        if ctx.rel_loops is None:
+            tsum = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+            call("hscn_gat_loop_bwd_dst", ptr(rel.csr.rowptr), ptr(rel.csr.col), ptr(a_s), ptr(a_d), ptr(h),
+                 ptr(kept), ptr(g), ptr(tsum), ptr(g_a), N, H, ctx.slope, stream())
+            call("hscn_gat_loop_bwd_src", ptr(rel.csr_t.rowptr), ptr(rel.csr_t.col), ptr(a_s), ptr(a_d), ptr(h),
+                 ptr(kept), ptr(tsum), ptr(g), ptr(att_s), ptr(att_d), ptr(g_a), ptr(g_h), N, H, ctx.slope, stream())
+            g_att = linear_bwd_w_raw(g_a[:N], h, True, False)[0]            # [2, H]: both attention vectors at once
+            g_att_s, g_att_d = g_att[0].view(1, 1, H), g_att[1].view(1, 1, H)
+        else:
+            lo: Relation = ctx.rel_loops
+            g_pre = torch.empty(max(lo.num_edges, 1), dtype=torch.float32, device=dev)
+            g_a_d = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+            g_a_s = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
+            call("hscn_gat_segment_bwd_dst", ptr(lo.csr.rowptr), ptr(lo.csr.col), ptr(a_s), ptr(a_d), ptr(h),
+                 ptr(kept), ptr(g), ptr(g_pre), ptr(g_a_d), N, H, ctx.slope, stream())
+            call("hscn_gat_segment_bwd_src", ptr(lo.csr_t.rowptr), ptr(lo.csr_t.col), ptr(lo.pos_t), ptr(kept),
+                 ptr(g_pre), ptr(g), ptr(att_s), ptr(g_a_s), ptr(g_h), N, H, stream())
+            g_h += linear_raw(g_a_d[:N].view(-1, 1), att_d.view(H, 1))[0]   # + g_a_dst (x) att_dst
+            g_att_s = linear_bwd_w_raw(g_a_s[:N].view(-1, 1), h, True, False)[0].view(1, 1, H)
+            g_att_d = linear_bwd_w_raw(g_a_d[:N].view(-1, 1), h, True, False)[0].view(1, 1, H)
+        gW = linear_bwd_w_raw(g_h, x, True, False)[0] if ctx.needs_input_grad[1] else None
+        gx = linear_raw(g_h, W, w_layout=1)[0] if ctx.needs_input_grad[0] else None
+        return (gx, gW, g_att_s if ctx.needs_input_grad[2] else None, g_att_d if ctx.needs_input_grad[3] else None,
+                gb, None, None, None, None)
+
+
+# --------------------------------------------------------------------------- #
 # global_mean_pool
 # --------------------------------------------------------------------------- #
 class SegmentMeanFn(Function):

@@ -103,6 +103,7 @@ class Relation:
             self.csr = build_csr(edge_index[1], edge_index[0], self.num_dst, self.num_src)
         self._pos_t: Optional[Tensor] = None
         self._dinv: Optional[Tensor] = None
+        self._max_in_degree: Optional[int] = None
 
     @property
     def csr_t(self) -> CSR:
@@ -131,6 +132,15 @@ class Relation:
             _hip.call("hscn_gcn_dinv", _hip.ptr(self.csr.rowptr), self.num_dst, _hip.ptr(d), _hip.stream())
             self._dinv = d
         return self._dinv
+
+    @property
+    def max_in_degree(self) -> int:
+        """Longest row of the target-keyed CSR (repeated edges and loops count).  Read off ``rowptr`` once -- one
+        synchronising copy, so a caller that captures launches asks before the capture -- then a host value."""
+        if self._max_in_degree is None:
+            rp = self.csr.rowptr
+            self._max_in_degree = int((rp[1:] - rp[:-1]).max().item()) if self.num_dst > 0 else 0
+        return self._max_in_degree
 
     def check(self) -> None:
         self.csr.check()

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HSCN_ABI_VERSION 20
+#define HSCN_ABI_VERSION 21
 
 #define HSCN_E_BADARG (-1)   /* null pointer, negative size, unsupported width */
 #define HSCN_E_WORKSPACE (-2) /* workspace too small */
@@ -186,6 +186,47 @@ int hscn_gat_segment_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, cons
                              const float* att_src /*[width]*/,
                              float* g_a_src /*[num_src]*/, float* g_h_src /*[num_src,width]*/,
                              int64_t num_src, int width, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * ABI 21: GATConv(in, out) of the MPNN baseline -- heads=1, homogeneous, add_self_loops=True, ONE shared
+ * transform h = x W^T feeding both attention dots (reference model/mpnn.py:29-32,52,59 with
+ * config/config.py:19-23 CONV_DICT["gat"]; PyG 2.2/2.3 GATConv).  Narrow-row kernels (csrc/gat_loops.hip): a row is
+ * owned by a lane group sized to the width, a wave covers several rows, each group walks its row serially.
+ *
+ * rowptr / col (and rowptr_t / col_t) are the stable CSRs of the RAW edge list keyed by target (by source), as
+ * hscn_csr_build_pair makes them, num_nodes rows each.  Entries with col == row are skipped in the kernel and the
+ * node's own term is added last: the result and the summation order are those of the bipartite operator over
+ * remove_self_loops + add_self_loops(edge_index), with nothing of data-dependent shape on the host.  Per target v,
+ * e over its kept in-entries followed by the loop v -> v:
+ *   z_e      = leaky_relu(a_src[src_e] + a_dst[v], slope)
+ *   alpha_e  = exp(z_e - max_v) / (sum_v exp(z_e - max_v) + 1e-16)
+ *   out[v,:] = act( sum_e alpha_e h[src_e,:] + bias )
+ * Nothing is kept per edge.  Caller-allocated hand-over buffers:
+ *   stat [num_nodes,2]  forward -> both backwards: {max_v, sum_v exp + 1e-16}; alpha is recomputed from it
+ *   tsum [num_nodes]    bwd_dst -> bwd_src: sum_e alpha_e (g[v,:] . h[src_e,:])
+ *   g_a  [num_nodes,2]  {dL/da_src[j], dL/da_dst[j]} interleaved: bwd_dst writes column 1, bwd_src reads it and
+ *                       writes column 0 (one [N,2]^T [N,width] product then gives both attention-vector gradients)
+ * Call order in the backward: hscn_gat_loop_bwd_dst, then hscn_gat_loop_bwd_src on the same stream.
+ *   g      = dL/d(pre-activation out) [num_nodes,width]
+ *   g_h[j,:] = sum_{e: src_e = j} alpha_e g[dst_e,:] + g_a[j,0] att_src + g_a[j,1] att_dst   (= dL/dh, complete)
+ * Rows of any in-degree are correct; width <= 256 when width % 4 == 0 (16-byte access), width <= 64 otherwise
+ * (HSCN_E_UNSUPPORTED beyond).  bias may be NULL.  Null pointers / negative sizes / an unknown act: HSCN_E_BADARG.
+ * ------------------------------------------------------------------------- */
+int hscn_gat_loop_fwd(const int32_t* rowptr, const int32_t* col,
+                      const float* a_src /*[num_nodes]*/, const float* a_dst /*[num_nodes]*/, const float* h,
+                      const float* bias /*or NULL*/, float* stat /*[num_nodes,2]*/, float* out,
+                      int64_t num_nodes, int width, float slope, int act, void* stream);
+int hscn_gat_loop_bwd_dst(const int32_t* rowptr, const int32_t* col,
+                          const float* a_src, const float* a_dst, const float* h, const float* stat,
+                          const float* g, float* tsum /*[num_nodes]*/, float* g_a /*[num_nodes,2], column 1*/,
+                          int64_t num_nodes, int width, float slope, void* stream);
+int hscn_gat_loop_bwd_src(const int32_t* rowptr_t, const int32_t* col_t,
+                          const float* a_src, const float* a_dst, const float* h, const float* stat,
+                          const float* tsum, const float* g,
+                          const float* att_src /*[width]*/, const float* att_dst /*[width]*/,
+                          float* g_a /*[num_nodes,2], column 0 written, column 1 read*/,
+                          float* g_h /*[num_nodes,width]*/,
+                          int64_t num_nodes, int width, float slope, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * a14  global_mean_pool (reference model/hscn.py:111).
