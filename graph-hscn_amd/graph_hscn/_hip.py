@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("HSCN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libhscn.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 ACT = {"identity": 0, "relu": 1, "elu": 2, "tanh": 3}
 
 P = c_void_p
@@ -127,6 +127,10 @@ _SIGNATURES = {
     "hscn_gat_loop_fwd": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int, c_float, c_int, P]),
     "hscn_gat_loop_bwd_dst": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int, c_float, P]),
     "hscn_gat_loop_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_float, P]),
+    # ABI 22: the SignNet node encoder's forward as one launch (csrc/signnet.hip)
+    "hscn_signnet_supported": (c_int, [c_int] * 12),
+    "hscn_signnet_encode": (c_int, [P, P, P, c_int64, P, P, c_int64, c_int64] + [c_int] * 9 + [P, c_int, c_int, P, P,
+                                    P, P]),
 }
 _SIGNATURES["hscn_mpnn_train_step_acc"] = _SIGNATURES["hscn_mpnn_train_step"]
 # IEEE-half storage twins (include/hscn.h: hscn_resident_*_f16): same argument lists

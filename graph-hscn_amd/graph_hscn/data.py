@@ -98,6 +98,24 @@ def _cat_targets(ys: Sequence[Tensor]) -> Tensor:
     return torch.cat([y.reshape(1) if y.dim() == 0 else y for y in ys], 0)
 
 
+# what a Batch holds that is not a per-node extra of its graphs
+_BATCH_KEYS = frozenset(["x", "edge_index", "y", "edge_weight", "num_nodes", "batch", "ptr", "num_graphs", "ptr32",
+                         "eptr32", "max_nodes", "max_edges"])
+
+
+def _node_extras(graphs: Sequence[Data], ns: Sequence[int]) -> List[str]:
+    """Names every graph of the list holds as a tensor whose first dimension is its node count (``eigvecs_sn [n, K]``,
+    ``eigvals_sn [n, K, 1]``, ...), in the first graph's order."""
+    out = []
+    for k in graphs[0].keys():
+        if k in _BATCH_KEYS:
+            continue
+        if all(k in g and isinstance(g._d[k], Tensor) and g._d[k].dim() >= 1 and g._d[k].size(0) == n
+               for g, n in zip(graphs, ns)):
+            out.append(k)
+    return out
+
+
 class Batch(Data):
     """Block-diagonal union of ``Data`` graphs (PyG ``Batch.from_data_list``)."""
 
@@ -126,6 +144,36 @@ class Batch(Data):
         out.eptr32 = eptr
         out.max_nodes = int(max(ns)) if ns else 0
         out.max_edges = int(max(es)) if es else 0
+        for k in _node_extras(graphs, ns) if graphs else []:     # per-node extras, concatenated like x
+            out._d[k] = torch.cat([g._d[k] for g in graphs], 0)
+        return out
+
+    def to_data_list(self) -> List[Data]:
+        """The inverse of ``from_data_list`` (PyG ``Batch.to_data_list``): per graph its rows of ``x`` and of every
+        per-node extra, its edges with the node offset removed, its edge weights and its target -- row ``i`` of a
+        ``[B, ...]`` target, or the graph's node range of a per-node one (``_cat_targets``)."""
+        B, N = int(self.num_graphs), int(self.num_nodes)
+        ptr = [int(v) for v in self.ptr.tolist()]
+        eptr = [int(v) for v in self.eptr32.tolist()]
+        y = self._d.get("y")
+        ew = self._d.get("edge_weight")
+        extras = [k for k, v in self._d.items()
+                  if k not in _BATCH_KEYS and isinstance(v, Tensor) and v.dim() >= 1 and v.size(0) == N]
+        per_graph_y = y is not None and y.size(0) == B
+        if y is not None and not per_graph_y and y.size(0) != N:
+            raise ValueError(f"target of {y.size(0)} rows belongs neither to {B} graphs nor to {N} nodes")
+        out = []
+        for i in range(B):
+            a, b = ptr[i], ptr[i + 1]
+            ea, eb = eptr[i], eptr[i + 1]
+            g = Data(x=self.x[a:b], edge_index=self.edge_index[:, ea:eb] - a, num_nodes=b - a)
+            if y is not None:
+                g.y = y[i:i + 1] if per_graph_y else y[a:b]
+            if ew is not None:
+                g.edge_weight = ew[ea:eb]
+            for k in extras:
+                g._d[k] = self._d[k][a:b]
+            out.append(g)
         return out
 
     @property

@@ -2,7 +2,9 @@
 (/root/reference/graph_hscn/encoder/signnet.py:11-381): ``MLP`` / ``GIN`` / ``GINDeepSigns`` / ``MaskedGINDeepSigns``
 / ``SignNetNodeEncoder``.  In the reference it runs ONCE per batch of the dataset, under ``no_grad``, with randomly
 initialised weights (train/train.py:29-51) -- pre-processing, SURVEY.md section 8(f)4 -- so this is a mirror of the
-interface on top of the library's operators, not a fused kernel:
+interface on top of the library's operators (the "layered" engine, the default).  ``SignNetNodeEncoder.engine`` =
+"auto" / "resident" runs a qualifying batch as ONE launch instead (csrc/signnet.hip, include/hscn.h:
+hscn_signnet_encode); ``compute_posenc`` builds its encoder with "auto".  The layered engine:
 
 * ``GINConv``: sum aggregation = the CSR gather-reduce of csrc/spmm.hip with unit weights (``hscn_spmm_csr_weighted``),
   for the 3-D eigenvector tensors ``[K, N, C]`` one pass over node rows of width K * C;
@@ -14,11 +16,14 @@ One deviation from the reference, without which nothing here could be constructe
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn as nn
 from torch import Tensor
 from torch.autograd import Function
 
+from .. import _hip
 from ..config.config import ACT_DICT
 from ..nn import BatchNorm1d, LayerNorm, Linear
 from ..nn import functional as Fh
@@ -220,11 +225,107 @@ class SignNetNodeEncoder(nn.Module):  # signnet.py:296-381
             self.sign_inv_net = GINDeepSigns(k=cfg.eigen_max_freqs, **common)
         else:
             self.sign_inv_net = MaskedGINDeepSigns(**common)
+        self._cfg_dims = dict(model=0 if model_type == "DeepSet" else 1, use_bn=int(bool(cfg.use_bn)),
+                              K=int(cfg.eigen_max_freqs), hidden=int(cfg.phi_hidden_dim), phi_out=int(cfg.phi_out_dim),
+                              layers=int(cfg.layers), post_layers=int(cfg.post_layers), dim_pe=int(dim_pe))
+        # execution engine of the forward: "layered" (per-operator kernels, the default), "auto" / "resident" (a
+        # qualifying batch runs as ONE launch, include/hscn.h: hscn_signnet_encode; "resident" raises with
+        # fused_reason's text when the encoder or batch does not qualify)
+        self.engine = "layered"
+        self.last_engine: Optional[str] = None
+
+    def _fused_dims(self):
+        """(model, use_bn, K, hidden, phi_out, layers, post_layers, dim_pe, dim_x, F) as hscn_signnet_supported reads
+        them; F / dim_x from linear_x (None when expand_x is off: the batch's feature width)."""
+        c = self._cfg_dims
+        if self.expand_x:
+            dx, F = int(self.linear_x.weight.shape[0]), int(self.linear_x.weight.shape[1])
+        else:
+            dx = F = None
+        return c["model"], c["use_bn"], c["K"], c["hidden"], c["phi_out"], c["layers"], c["post_layers"], c["dim_pe"], dx, F
+
+    def _fused_params(self):
+        """{W, b} per Linear in the order hscn_signnet_encode takes them."""
+        net = self.sign_inv_net
+        out = []
+        for conv in net.enc.layers:
+            for fc in conv.nn.fcs:
+                out += [fc.weight, fc.bias]
+        for fc in net.rho.fcs:
+            out += [fc.weight, fc.bias]
+        if self.expand_x:
+            out += [self.linear_x.weight, self.linear_x.bias]
+        return out
+
+    def fused_reason(self, batch) -> Optional[str]:
+        """Why ``batch`` cannot take the one-launch encoder (hscn_signnet_encode), or None when it can."""
+        model, use_bn, K, hid, po, layers, post, dpe, dx, F = self._fused_dims()
+        if model != 0:
+            return "model 'MLP' (the concatenation over frequencies) is not part of the fused kernel; 'DeepSet' is"
+        if use_bn:
+            return "use_bn: BatchNorm takes statistics across the whole batch, which one workgroup per graph cannot"
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return "gradients are on: the fused launch is a forward for torch.no_grad() (it has no backward)"
+        for attr in ("ptr32", "eptr32", "max_nodes", "max_edges", "num_graphs"):
+            if not hasattr(batch, attr):
+                return f"the batch carries no {attr} (graph_hscn.data.Batch.from_data_list builds it)"
+        x, vec = batch.x, batch.eigvecs_sn
+        if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or (F is not None and x.size(1) != F):
+            return "node features must be a float32 [N, F] tensor on the HIP device"
+        if not vec.is_cuda or vec.dtype != torch.float32 or vec.dim() != 2 or vec.size(0) != x.size(0):
+            return "eigvecs_sn must be a float32 [N, K] tensor on the HIP device"
+        if any(p.dtype != torch.float32 or p.device != x.device for p in self.parameters()):
+            return "the encoder's parameters must be float32 on the batch's device"
+        if F is None:
+            F = dx = int(x.size(1))
+        if not _hip.lib().hscn_signnet_supported(model, 0, F, int(vec.size(1)), hid, po, layers, post, dpe, dx,
+                                                 int(batch.max_nodes), int(batch.max_edges)):
+            return (f"widths F={F}, K={vec.size(1)}, hidden={hid}, phi_out={po}, dim_pe={dpe}, layers={layers}, "
+                    f"post_layers={post} or the largest graph ({batch.max_nodes} nodes, {batch.max_edges} edges) "
+                    "outside the kernel's envelope (160 KB of LDS)")
+        return None
+
+    def _forward_fused(self, batch):
+        from .. import engine as _engine
+        _, _, _, hid, po, layers, post, dpe, dx, F = self._fused_dims()
+        x = batch.x.contiguous()
+        vec = batch.eigvecs_sn.contiguous()
+        ei = batch.edge_index.contiguous()
+        dev = x.device
+        if F is None:
+            F = dx = int(x.size(1))
+        N, B = int(x.size(0)), int(batch.num_graphs)
+        params = [p.detach().contiguous() for p in self._fused_params()]
+        table = _engine._ptr_table(params)
+        ptr32 = batch.ptr32 if batch.ptr32.device == dev else batch.ptr32.to(dev)
+        eptr32 = batch.eptr32 if batch.eptr32.device == dev else batch.eptr32.to(dev)
+        out = torch.empty(N, dx + dpe, dtype=torch.float32, device=dev)
+        pe = torch.empty(N, dpe, dtype=torch.float32, device=dev) if self.pass_as_var else None
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        _hip.call("hscn_signnet_encode", _hip.ptr(x), _hip.ptr(vec), _hip.ptr(ei), ei.size(1), _hip.ptr(ptr32),
+                  _hip.ptr(eptr32), N, B, F, int(vec.size(1)), hid, po, layers, post, dpe, dx, int(self.expand_x),
+                  table, int(batch.max_nodes), int(batch.max_edges), _hip.ptr(out), _hip.ptr(pe), _hip.ptr(flag),
+                  _hip.stream())
+        self._resident_flag = flag     # nonzero: an edge outside its graph / a graph beyond the batch's maxima
+        batch.x = out
+        if self.pass_as_var:
+            batch.pe_SignNet = pe
+        return batch
 
     def forward(self, batch):
         if not (hasattr(batch, "eigvals_sn") and hasattr(batch, "eigvecs_sn")) or batch.eigvecs_sn is None:
             raise ValueError("Precomputed eigen values and vectors are required for SignNetNodeEncoder; "
                              "set config 'posenc_SignNet.enable' to True")
+        if self.engine not in ("layered", "auto", "resident"):
+            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if self.engine != "layered":
+            reason = self.fused_reason(batch)
+            if reason is None:
+                self.last_engine = "resident"
+                return self._forward_fused(batch)
+            if self.engine == "resident":
+                raise RuntimeError(f"engine='resident' requested but the encoder / batch does not qualify: {reason}")
+        self.last_engine = "layered"
         pos_enc = torch.nan_to_num(batch.eigvecs_sn.unsqueeze(-1).float(), nan=0.0)     # NaN padding -> 0 (signnet.py:361-363)
         pos_enc = self.sign_inv_net(pos_enc, batch.edge_index, batch.batch)
         h = self.linear_x(batch.x.to(torch.float32)) if self.expand_x else batch.x

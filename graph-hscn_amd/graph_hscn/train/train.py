@@ -21,6 +21,48 @@ def is_eval_epoch(epoch: int, max_epochs: int, eval_period: int) -> bool:  # tra
     return (epoch + 1) % eval_period == 0 or epoch == 0 or (epoch + 1) == max_epochs
 
 
+def get_each_data_from_batch(data_list: list) -> list:  # train/utils.py:9-14
+    """The graphs of a list of batches, in order."""
+    out = []
+    for batch in data_list:
+        out.extend(batch.to_data_list())
+    return out
+
+
+def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, device=None):  # train/train.py:29-51
+    """The positional-encoding stage in front of stage A: ONE ``SignNetNodeEncoder(pe_cfg, num_features,
+    pe_cfg.dim_emb)`` with its random initial weights (the reference never trains it) runs under ``no_grad`` over
+    every batch of every loader and replaces ``x`` by ``[linear_x(x) | pe]`` of width ``pe_cfg.dim_emb``.  Returns
+    ``(new_loaders, batches)``: ``batches`` is the flat list of encoded batches in loader order
+    (``get_each_data_from_batch`` turns it into graphs), and ``new_loaders[i]`` serves the encoded graphs of loader
+    ``i`` in batches of ``data_cfg.batch_size``, loader 0 shuffled and the others in order.
+
+    The encoder lives on ``device`` (default: "cuda" when available) and every batch is moved there; its engine is
+    "auto", so a qualifying batch takes the one-launch kernel (include/hscn.h: hscn_signnet_encode).  The encoder is
+    kept as ``compute_posenc.last_encoder`` for inspection."""
+    from ..data import DataLoader
+    from ..encoder.signnet import SignNetNodeEncoder
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    enc = SignNetNodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
+    enc.engine = "auto"
+    compute_posenc.last_encoder = enc
+    if logger is not None:
+        logger.info("Running PE for each loader...")
+    loaders_new, flat = [], []
+    with torch.no_grad():
+        for i, loader in enumerate(loaders):
+            data_list = []
+            for batch in loader:
+                batch = batch.to(device)
+                batch.x = batch.x.float()
+                data_list.append(enc(batch))
+            loaders_new.append(DataLoader(get_each_data_from_batch(data_list), batch_size=data_cfg.batch_size,
+                                          shuffle=(i == 0)))
+            flat.extend(data_list)
+    return loaders_new, flat
+
+
 def _run_batch(model, batch, device):
     if isinstance(model, HSCN):
         batch = batch.to(device)

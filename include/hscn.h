@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HSCN_ABI_VERSION 21
+#define HSCN_ABI_VERSION 22
 
 #define HSCN_E_BADARG (-1)   /* null pointer, negative size, unsupported width */
 #define HSCN_E_WORKSPACE (-2) /* workspace too small */
@@ -999,6 +999,39 @@ int hscn_mpnn_forward(const float* x, const int64_t* edge_index, int64_t E, cons
                       const void* const* params_host, int max_n, int max_ell, const float* target /*or NULL*/,
                       int loss_kind, float inv_count, float* pred, float* score /*or NULL*/,
                       float* loss_rows /*[B] or NULL*/, float* loss /*[1] or NULL*/, int32_t* flag, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * ABI 22: the SignNet node encoder's forward (graph_hscn/encoder/signnet.py: SignNetNodeEncoder; reference
+ * encoder/signnet.py:296-381, run once per batch under no_grad by compute_posenc) as ONE launch: workgroup g encodes
+ * graph g with its structure in LDS (csrc/signnet.hip).
+ *   eigvecs [N,K] f32 (NaN padding is read as 0), K independent channels of width 1;
+ *   phi = GIN(1, hidden, phi_out, layers): Lc = max(layers, 2) GINConv's, nn(x_i + sum_{j -> i} x_j) over the edge
+ *   list as given (repeated edges and loops count, nothing is added), nn = Linear(1, hidden), Lc - 2 times
+ *   Linear(hidden, hidden), then Linear(hidden, hidden) -> ReLU -> Linear(hidden, phi_out);
+ *   DeepSet: enc = sum over the frequencies k < min(K, n_graph) of phi(v_k) + phi(-v_k);
+ *   rho: post_layers Linear's with ReLU between them (phi_out -> hidden -> .. -> dim_pe; one layer: phi_out -> dim_pe);
+ *   out [N, dim_x + dim_pe] = [ x Wx^T + bx | pe ]  (expand_x = 0: the leading columns are x itself, dim_x = F);
+ *   pe [N, dim_pe]: optional second copy of the encoding (pass_as_var).
+ *   x [N,F] f32, edge_index int64 [2,E] batch numbering, graph g owns nodes [ptr32[g], ptr32[g+1]) and edges
+ *   [eptr32[g], eptr32[g+1]).  params_host: HOST array of device pointers {W, b} per Linear in module order: the Lc
+ *   Linear's in front of the ReLU, the one behind it, rho's post_layers, then (expand_x) linear_x.
+ *   flag bit 1: an edge with an end outside its graph (dropped); bit 2: a graph beyond max_n / max_e or the arrays
+ *   (the rows it names inside [0, N) are zeros).
+ * hscn_signnet_supported: model = HSCN_SIGNNET_DEEPSET (HSCN_SIGNNET_MLP, the concatenation over k, is refused),
+ *   use_bn = 0 (BatchNorm in training mode takes statistics across the whole batch), 1 <= F, dim_x <= 1024,
+ *   1 <= K <= 64, hidden, phi_out, dim_pe in [1, 64], layers and post_layers in [1, 8], and a layout of the largest
+ *   graph within 160 KB of LDS.  hscn_signnet_encode: HSCN_E_BADARG for null pointers / non-positive widths,
+ *   HSCN_E_UNSUPPORTED outside the envelope, both before any launch; B = 0 or N = 0 launches nothing.
+ * ------------------------------------------------------------------------- */
+#define HSCN_SIGNNET_DEEPSET 0
+#define HSCN_SIGNNET_MLP 1
+int hscn_signnet_supported(int model, int use_bn, int F, int K, int hidden, int phi_out, int layers, int post_layers,
+                           int dim_pe, int dim_x, int max_n, int max_e);
+int hscn_signnet_encode(const float* x, const float* eigvecs, const int64_t* edge_index, int64_t E,
+                        const int32_t* ptr32, const int32_t* eptr32, int64_t N, int64_t B, int F, int K, int hidden,
+                        int phi_out, int layers, int post_layers, int dim_pe, int dim_x, int expand_x,
+                        const void* const* params_host, int max_n, int max_e, float* out, float* pe /*or NULL*/,
+                        int32_t* flag, void* stream);
 
 #ifdef __cplusplus
 }
