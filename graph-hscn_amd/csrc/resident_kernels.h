@@ -2155,13 +2155,13 @@ int launch_bwd_virtual(BwdArgs& Ab, FwdArgs& Af, int64_t B, hipStream_t st) {
   return launch_bwd_virtual_rt<H, 1024, TS>(Ab, Af, B, lds, st);
 }
 
-int fill_fwd_args(FwdArgs& A, const float* x_local, const float* x_virtual, const int64_t* ei_ll, int64_t E_ll,
+int fill_fwd_args(FwdArgs& A, const void* x_local, const void* x_virtual, const int64_t* ei_ll, int64_t E_ll,
                   const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv, const int32_t* lptr,
                   const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv, const int32_t* eptr_lv,
                   int64_t N, int64_t V, int F, int H, int L, int C, int head_act, float slope,
                   const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
                   const float* b2, int max_n, int max_v, int max_ell, int max_evv, int compute_virtual,
-                  float* acts, float* pooled, float* z, float* pred, float* xv_out, int32_t* csr_rowptr_t,
+                  void* acts, float* pooled, float* z, float* pred, void* xv_out, int32_t* csr_rowptr_t,
                   int32_t* csr_col_t, float* dinv_out, int32_t* flag) {
   if (compute_virtual < 0 || compute_virtual > 2) return HSCN_E_BADARG;
   const bool vonly = compute_virtual == 2;
@@ -2171,7 +2171,7 @@ int fill_fwd_args(FwdArgs& A, const float* x_local, const float* x_virtual, cons
   if (vonly && (!xv_out || csr_rowptr_t || csr_col_t || dinv_out)) return HSCN_E_BADARG;
   if ((E_ll > 0 && !ei_ll && !vonly) || (compute_virtual && ((E_vv > 0 && !ei_vv) || (E_lv > 0 && !ei_lv) || !x_virtual)))
     return HSCN_E_BADARG;
-  A.x_local = x_local; A.x_virtual = x_virtual;
+  A.x_local = (const float*)x_local; A.x_virtual = (const float*)x_virtual;   // (the kernels read them as TS)
   A.ll_src = ei_ll; A.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
   A.vv_src = ei_vv; A.vv_dst = ei_vv ? ei_vv + E_vv : nullptr;
   A.lv_src = ei_lv; A.lv_dst = ei_lv ? ei_lv + E_lv : nullptr;
@@ -2185,7 +2185,7 @@ int fill_fwd_args(FwdArgs& A, const float* x_local, const float* x_virtual, cons
                         (const float*)q[8]};
   }
   A.W1 = W1; A.b1 = b1; A.W2 = W2; A.b2 = b2;
-  A.acts = acts; A.pooled = pooled; A.z = z; A.pred = pred; A.xv_out = xv_out; A.flag = flag;
+  A.acts = (float*)acts; A.pooled = pooled; A.z = z; A.pred = pred; A.xv_out = (float*)xv_out; A.flag = flag;
   A.score = nullptr;
   if ((csr_rowptr_t == nullptr) != (csr_col_t == nullptr) || (csr_rowptr_t == nullptr) != (dinv_out == nullptr))
     return HSCN_E_BADARG;
@@ -2266,22 +2266,23 @@ int launch_fwd_pair(FwdArgs& Al, FwdArgs& Av, int64_t B, hipStream_t st) {
   return 0;
 }
 
-int fill_bwd_args(BwdArgs& A, const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int fill_bwd_args(BwdArgs& A, const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                   const int32_t* eptr_ll, int64_t N, int F, int H, int L, int C, int head_act,
-                  const void* const* W_ll_host, const float* W1, const float* W2, const float* acts,
+                  const void* const* W_ll_host, const float* W1, const float* W2, const void* acts,
                   const float* pooled, const float* z, const float* g_pred, const float* g_scale,
                   const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n, int max_ell,
                   float* partials, float* grads, int32_t* flag) {
   if (!x_local || !lptr || !eptr_ll || !W_ll_host || !W1 || !W2 || !acts || !pooled || !z ||
       !partials || !grads || !csr_rowptr_t || !dinv || (E_ll > 0 && !csr_col_t))
     return HSCN_E_BADARG;
-  A.x_local = x_local; A.ll_src = ei_ll; A.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
+  A.x_local = (const float*)x_local; A.ll_src = ei_ll; A.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
   A.lptr = lptr; A.eptr_ll = eptr_ll;
   for (int l = 0; l < L; ++l) {
     if (!W_ll_host[l]) return HSCN_E_BADARG;
     A.W_ll[l] = (const float*)W_ll_host[l];
   }
-  A.W1 = W1; A.W2 = W2; A.acts = acts; A.pooled = pooled; A.z = z; A.g_pred = g_pred; A.g_scale = g_scale;
+  A.W1 = W1; A.W2 = W2; A.acts = (const float*)acts; A.pooled = pooled; A.z = z; A.g_pred = g_pred;
+  A.g_scale = g_scale;
   A.csr_rowptr_t = csr_rowptr_t; A.csr_col_t = csr_col_t; A.dinv_in = dinv;
   A.partials = partials; A.flag = flag; A.N = N; A.F = F; A.L = L; A.C = C; A.head_act = head_act;
   A.max_n = max_n; A.max_ell = max_ell; A.P = (int)hscn_resident_param_count(F, H, L, C);
@@ -2302,17 +2303,18 @@ int attach_tail(BwdArgs& A, const hscn_loss_tail* tail, int64_t B) {
 
 #include "resident_step.h"
 
-// ---- the C entry points, generic in the storage type (resident.hip: float, resident_f16.hip: half) ----
+// ---- the C entry points, generic in the storage type (resident.hip: float, resident_f16.hip: half): each takes
+// ---- the prototype include/hscn.h exports, so the exported function only selects the instantiation ----
 template <typename TS>
-int impl_resident_fwd(const float* x_local, const float* x_virtual, const int64_t* ei_ll, int64_t E_ll,
+int impl_resident_fwd(const void* x_local, const void* x_virtual, const int64_t* ei_ll, int64_t E_ll,
                       const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv,
                       const int32_t* lptr, const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv,
                       const int32_t* eptr_lv, int64_t N, int64_t V, int64_t B, int F, int H, int L, int C,
                       int head_act, float slope, const void* const* layer_params_host /* L x 9 */,
                       const float* W1, const float* b1, const float* W2, const float* b2, int max_n, int max_v,
-                      int max_ell, int max_evv, int compute_virtual, float* acts, float* pooled, float* z,
-                      float* pred, float* score, float* xv_out, int32_t* csr_rowptr_t, int32_t* csr_col_t,
-                      float* dinv_out, int32_t* flag, void* stream_) {
+                      int max_ell, int max_evv, int compute_virtual, void* acts, float* pooled, float* z,
+                      float* pred, float* score, void* xv_out, int32_t* csr_rowptr_t, int32_t* csr_col_t,
+                      float* dinv_out, int32_t* flag, int flags, void* stream_) {
   if (B < 0 || N < 0 || V < 0) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, max_v, max_ell, max_evv)) return HSCN_E_UNSUPPORTED;
@@ -2333,13 +2335,13 @@ int impl_resident_fwd(const float* x_local, const float* x_virtual, const int64_
 }
 
 template <typename TS>
-int impl_resident_bwd(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int impl_resident_bwd(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                       const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
-                      const void* const* W_ll_host /* L */, const float* W1, const float* W2, const float* acts,
+                      const void* const* W_ll_host /* L */, const float* W1, const float* W2, const void* acts,
                       const float* pooled, const float* z, const float* g_pred, const float* g_scale,
                       const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n,
                       int max_ell, float* partials /*[B][P]*/, float* grads /*[P]*/, int32_t* flag,
-                      const hscn_loss_tail* tail, void* stream_, int accumulate = 0) {
+                      const hscn_loss_tail* tail, int flags, void* stream_) {
   if (B < 0 || N < 0) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, 0, max_ell, 0)) return HSCN_E_UNSUPPORTED;
@@ -2357,20 +2359,21 @@ int impl_resident_bwd(const float* x_local, const int64_t* ei_ll, int64_t E_ll, 
     case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd<64, float>(A, B, st); break;
   }
   if (rc) return rc;
-  launch_param_fold(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count, nullptr, accumulate, st);
+  launch_param_fold(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count, nullptr,
+                    flags & HSCN_GRAD_ACCUMULATE, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
 template <typename TS>
-int impl_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int impl_resident_bwd_with_virtual(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                                    const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
                                    int head_act, const void* const* W_ll_host, const float* W1, const float* W2,
-                                   const float* acts, const float* pooled, const float* z, const float* g_pred,
+                                   const void* acts, const float* pooled, const float* z, const float* g_pred,
                                    const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
                                    const float* dinv, int max_n, int max_ell, float* partials, float* grads,
                                    int32_t* flag, const hscn_loss_tail* tail, const hscn_virtual_job* job,
-                                   void* stream_, int accumulate = 0) {
+                                   int flags, void* stream_) {
   if (B < 0 || N < 0 || !job) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, job->max_v, max_ell, job->max_evv)) return HSCN_E_UNSUPPORTED;
@@ -2384,7 +2387,7 @@ int impl_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, i
   if (int rc1 = fill_fwd_args(Af, x_local, job->x_virtual, nullptr, 0, job->ei_vv, job->E_vv, job->ei_lv,
                               job->E_lv, lptr, job->vptr, eptr_ll, job->eptr_vv, job->eptr_lv, N, job->V, F, H, L,
                               C, head_act, job->slope, job->layer_params_host, nullptr, nullptr, nullptr, nullptr,
-                              max_n, job->max_v, max_ell, job->max_evv, 2, const_cast<float*>(acts), nullptr,
+                              max_n, job->max_v, max_ell, job->max_evv, 2, const_cast<void*>(acts), nullptr,
                               nullptr, nullptr, job->xv_out, nullptr, nullptr, nullptr, flag))
     return rc1;
   if (job_has_state(job)) {   // the forward launch ran structure + layer 0 (hscn_resident_fwd_with_virtual)
@@ -2400,19 +2403,20 @@ int impl_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, i
     case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd_virtual<64, float>(Ab, Af, B, st); break;
   }
   if (rc) return rc;
-  launch_param_fold(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count, nullptr, accumulate, st);
+  launch_param_fold(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count, nullptr,
+                    flags & HSCN_GRAD_ACCUMULATE, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
 template <typename TS>
-int impl_resident_fwd_with_virtual(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int impl_resident_fwd_with_virtual(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                                    const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
                                    int head_act, const void* const* layer_params_host, const float* W1,
                                    const float* b1, const float* W2, const float* b2, int max_n, int max_ell,
-                                   float* acts, float* pooled, float* z, float* pred, float* score,
+                                   void* acts, float* pooled, float* z, float* pred, float* score,
                                    int32_t* csr_rowptr_t, int32_t* csr_col_t, float* dinv_out, int32_t* flag,
-                                   const hscn_virtual_job* job, void* stream_) {
+                                   const hscn_virtual_job* job, int flags, void* stream_) {
   if (B < 0 || N < 0 || !job) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (L < 2 || !job_has_state(job)) return HSCN_E_BADARG;
@@ -2450,12 +2454,12 @@ int impl_resident_fwd_with_virtual(const float* x_local, const int64_t* ei_ll, i
 
 // one-launch training step (resident_step.h).  sync: [0] = epoch word, [32 .. 32 + B) = per-graph publish counters.
 template <typename TS>
-int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int impl_resident_train_step(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                              const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
                              const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
                              const float* b2, int max_n, int max_ell, const float* target, int loss_kind, float* pred,
-                             float* score, float* partials, float* grads, float* acts, uint32_t* sync, int32_t* flag,
-                             const hscn_virtual_job* job, const hscn_structure* pre, void* stream_, int accumulate = 0) {
+                             float* score, float* partials, float* grads, void* acts, uint32_t* sync, int32_t* flag,
+                             const hscn_virtual_job* job, const hscn_structure* pre, int flags, void* stream_) {
   if (B < 0 || N < 0) return HSCN_E_BADARG;
   if (pre && (!pre->ll_rowptr_d || !pre->ll_rowptr_s || !pre->ll_dinv || (E_ll > 0 && (!pre->ll_col_d || !pre->ll_col_s))))
     return HSCN_E_BADARG;
@@ -2470,7 +2474,8 @@ int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
     return HSCN_E_BADARG;
   if (job && (!acts || !sync || !job->xv_out)) return HSCN_E_BADARG;
   StepArgs S;
-  S.x_local = x_local; S.ll_src = ei_ll; S.ll_dst = ei_ll ? ei_ll + E_ll : nullptr; S.lptr = lptr; S.eptr_ll = eptr_ll;
+  S.x_local = (const float*)x_local; S.ll_src = ei_ll; S.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
+  S.lptr = lptr; S.eptr_ll = eptr_ll;
   for (int l = 0; l < L; ++l) {
     const void* const* q = layer_params_host + (size_t)l * 9;
     if (!q[0] || !q[1]) return HSCN_E_BADARG;
@@ -2484,7 +2489,7 @@ int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
   S.pre_rp_d = pre ? pre->ll_rowptr_d : nullptr; S.pre_col_d = pre ? pre->ll_col_d : nullptr;
   S.pre_rp_s = pre ? pre->ll_rowptr_s : nullptr; S.pre_col_s = pre ? pre->ll_col_s : nullptr;
   S.pre_dinv = pre ? pre->ll_dinv : nullptr;
-  S.acts = (acts && L >= 2) ? acts : nullptr;
+  S.acts = (acts && L >= 2) ? (float*)acts : nullptr;
   S.ready = (job && S.acts) ? sync + 32 : nullptr;
   S.epoch = sync;
   FwdArgs V;
@@ -2508,7 +2513,8 @@ int impl_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t
   k_param_reduce<<<HSCN_DIAG_REDUCE_BLOCKS, 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
                                                           S.ready ? sync : nullptr);
 #else
-  launch_param_fold(partials, grads, (int)B, S.P, S.Pn, S.inv_count, S.ready ? sync : nullptr, accumulate, st);
+  launch_param_fold(partials, grads, (int)B, S.P, S.Pn, S.inv_count, S.ready ? sync : nullptr,
+                    flags & HSCN_GRAD_ACCUMULATE, st);
 #endif
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
@@ -2565,3 +2571,15 @@ inline int step_supported(int F, int H, int L, int C, int max_n, int max_ell, in
 }
 
 }  // namespace
+
+// The half instantiations of the five entry points above, for resident.hip to dispatch to under HSCN_STORE_F16
+// (defined in resident_f16.hip; the members carry the exported prototypes, so no argument list is written again).
+struct hscn_resident_f16_table {
+  decltype(&hscn_resident_fwd) fwd;
+  decltype(&hscn_resident_bwd) bwd;
+  decltype(&hscn_resident_bwd_with_virtual) bwd_with_virtual;
+  decltype(&hscn_resident_fwd_with_virtual) fwd_with_virtual;
+  decltype(&hscn_resident_train_step) train_step;
+};
+__attribute__((visibility("hidden"))) const hscn_resident_f16_table& hscn_resident_f16();
+__attribute__((visibility("hidden"))) bool hscn_resident_f16_takes(int H);

@@ -382,11 +382,16 @@ int fill_mpnn_args(MpnnArgs& A, const float* x, const int64_t* edge_index, int64
   return 0;
 }
 
-int impl_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
+}  // namespace
+
+extern "C" {
+
+int hscn_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
                          const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
                          const void* const* params_host, int max_n, int max_ell, const float* target, int loss_kind,
                          float inv_count, float* pred, float* score, float* partials, float* grads, uint32_t* step,
-                         float p, uint64_t seed0, int32_t* flag, void* stream_, bool accumulate) {
+                         float p, uint64_t seed0, int32_t* flag, int flags, void* stream_) {
+  if (flags & ~HSCN_GRAD_ACCUMULATE) return HSCN_E_BADARG;
   if (B < 0 || !target || !partials || !grads || !(p >= 0.f && p < 1.f)) return HSCN_E_BADARG;
   if (B == 0) return 0;
   MpnnArgs A;
@@ -399,33 +404,9 @@ int impl_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, c
   hipStream_t st = hscn_stream(stream_);
   const int rc = H == 16 ? launch_mpnn<16, true>(A, B, st) : launch_mpnn<32, true>(A, B, st);
   if (rc) return rc;
-  launch_param_fold(partials, grads, (int)B, A.P + 1, A.P, inv_count, step, accumulate, st);
+  launch_param_fold(partials, grads, (int)B, A.P + 1, A.P, inv_count, step, flags & HSCN_GRAD_ACCUMULATE, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int hscn_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
-                         const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
-                         const void* const* params_host, int max_n, int max_ell, const float* target, int loss_kind,
-                         float inv_count, float* pred, float* score, float* partials, float* grads, uint32_t* step,
-                         float p, uint64_t seed0, int32_t* flag, void* stream) {
-  return impl_mpnn_train_step(x, edge_index, E, ptr32, eptr32, N, B, F, H, L, C, act, params_host, max_n, max_ell,
-                              target, loss_kind, inv_count, pred, score, partials, grads, step, p, seed0, flag, stream,
-                              false);
-}
-
-int hscn_mpnn_train_step_acc(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
-                             const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
-                             const void* const* params_host, int max_n, int max_ell, const float* target,
-                             int loss_kind, float inv_count, float* pred, float* score, float* partials, float* grads,
-                             uint32_t* step, float p, uint64_t seed0, int32_t* flag, void* stream) {
-  return impl_mpnn_train_step(x, edge_index, E, ptr32, eptr32, N, B, F, H, L, C, act, params_host, max_n, max_ell,
-                              target, loss_kind, inv_count, pred, score, partials, grads, step, p, seed0, flag, stream,
-                              true);
 }
 
 int hscn_mpnn_forward(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,

@@ -1615,12 +1615,18 @@ int hscn_scn_resident_train_step_supported(int F, int H, int K, int max_n, int m
   return 1;
 }
 
-static int scn_step_impl(int f16, const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                         const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act, const float* W_rel,
-                         const float* b_rel, const float* W_root, const float* W_mlp, const float* b_mlp,
-                         const float* g_mc, const float* g_o, int max_n, int max_e, float* S, float* stats,
-                         float* losses, int32_t* ticket, float* partials, float* grads, int32_t* flag,
-                         const hscn_adam* opt, const hscn_scn_structure* cache, void* stream_) {
+// HSCN_STORE_F16 (all four launches below): IEEE-half storage of the node features x and of the saved hidden
+// activation y (include/hscn.h); S, the statistics, the exported aggregation A_hat x (an accumulator output) and every
+// gradient stay float.  ScnArgs types both as float*; the kernels read them as TS.
+int hscn_scn_resident_train_step(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
+                                 const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
+                                 const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
+                                 const float* b_mlp, const float* g_mc, const float* g_o, int max_n, int max_e,
+                                 float* S, float* stats, float* losses, int32_t* ticket, float* partials,
+                                 float* grads, int32_t* flag, const hscn_adam* opt,
+                                 const hscn_scn_structure* cache, int flags, void* stream_) {
+  if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
+  const int f16 = flags & HSCN_STORE_F16;
   if (B < 1 || N < 0 || E < 0) return HSCN_E_BADARG;
   if (cache && (!cache->rowptr_d || !cache->rowptr_s || !cache->agg || !cache->dout ||
                 (E > 0 && (!cache->col_d || !cache->col_s))))
@@ -1634,7 +1640,7 @@ static int scn_step_impl(int f16, const float* x, const int64_t* edge_index, int
       (B > 1 && !partials) || (E > 0 && !edge_index))
     return HSCN_E_BADARG;
   ScnArgs A{};
-  A.x = x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
+  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
   A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
   A.S = S; A.stats = stats; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act; A.g_mc = g_mc; A.g_o = g_o;
   A.losses = losses; A.ticket = ticket;
@@ -1665,13 +1671,15 @@ static int scn_step_impl(int f16, const float* x, const int64_t* edge_index, int
   return 0;
 }
 
-static int scn_fwd_impl(int f16, const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
+int hscn_scn_resident_fwd(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
                           const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
                           const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
-                          const float* b_mlp, int max_n, int max_e, float* S, float* y, float* stats, float* ss,
+                          const float* b_mlp, int max_n, int max_e, float* S, void* y, float* stats, float* ss,
                           float* losses, int32_t* ticket, int32_t* ex_rowptr_d, int32_t* ex_col_d,
                           int32_t* ex_rowptr_s, int32_t* ex_col_s, float* ex_agg, float* ex_dout, int32_t* flag,
-                          void* stream_) {
+                          int flags, void* stream_) {
+  if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
+  const int f16 = flags & HSCN_STORE_F16;
   if (B < 1 || N < 0 || E < 0) return HSCN_E_BADARG;
   if (!hscn_scn_resident_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_rel || !b_rel || !W_root || !W_mlp || !b_mlp || !S || !y || !stats || !ss ||
@@ -1683,9 +1691,9 @@ static int scn_fwd_impl(int f16, const float* x, const int64_t* edge_index, int6
     if (have != 0 && have != 6) return HSCN_E_BADARG;   // the structure is exported whole or not at all
   }
   ScnArgs A{};
-  A.x = x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
+  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
   A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
-  A.S = S; A.y = y; A.stats = stats; A.ss = ss; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act;
+  A.S = S; A.y = (float*)y; A.stats = stats; A.ss = ss; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act;
   A.ex_rowptr_d = ex_rowptr_d; A.ex_col_d = ex_col_d; A.ex_rowptr_s = ex_rowptr_s; A.ex_col_s = ex_col_s;
   A.ex_agg = ex_agg; A.ex_dout = ex_dout; A.losses = losses; A.ticket = ticket;
   A.max_n = max_n; A.max_e = max_e; A.B = (int)B; A.P = (int)scn_param_count(F, H, K);
@@ -1700,21 +1708,23 @@ static int scn_fwd_impl(int f16, const float* x, const int64_t* edge_index, int6
   return 0;
 }
 
-static int scn_bwd_impl(int f16, const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
+int hscn_scn_resident_bwd(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
                           const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                          const float* W_mlp, const float* S, const float* y, const float* stats, const float* ss,
+                          const float* W_mlp, const float* S, const void* y, const float* stats, const float* ss,
                           const float* g_mc, const float* g_o, const int32_t* ex_rowptr_d, const int32_t* ex_col_d,
                           const int32_t* ex_rowptr_s, const int32_t* ex_col_s, const float* ex_agg,
                           const float* ex_dout, int max_n, int max_e, float* partials, float* grads, int32_t* flag,
-                          void* stream_) {
+                          int flags, void* stream_) {
+  if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
+  const int f16 = flags & HSCN_STORE_F16;
   if (B < 1 || N < 0 || E < 0) return HSCN_E_BADARG;
   if (!hscn_scn_resident_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_mlp || !S || !y || !stats || !ss || !partials || !grads ||
       !ex_rowptr_d || !ex_rowptr_s || !ex_agg || !ex_dout || (E > 0 && (!ex_col_d || !ex_col_s)))
     return HSCN_E_BADARG;
   ScnArgs A{};
-  A.x = x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
-  A.W_mlp = W_mlp; A.S = const_cast<float*>(S); A.y = const_cast<float*>(y);
+  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
+  A.W_mlp = W_mlp; A.S = const_cast<float*>(S); A.y = (float*)const_cast<void*>(y);
   A.stats = const_cast<float*>(stats); A.ss = const_cast<float*>(ss); A.g_mc = g_mc; A.g_o = g_o;
   A.ex_rowptr_d = const_cast<int32_t*>(ex_rowptr_d); A.ex_col_d = const_cast<int32_t*>(ex_col_d);
   A.ex_rowptr_s = const_cast<int32_t*>(ex_rowptr_s); A.ex_col_s = const_cast<int32_t*>(ex_col_s);
@@ -1730,38 +1740,19 @@ static int scn_bwd_impl(int f16, const float* x, const int64_t* edge_index, int6
   return 0;
 }
 
-int hscn_scn_resident_fwd(const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                          const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                          const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
-                          const float* b_mlp, int max_n, int max_e, float* S, float* y, float* stats, float* ss,
-                          float* losses, int32_t* ticket, int32_t* ex_rowptr_d, int32_t* ex_col_d,
-                          int32_t* ex_rowptr_s, int32_t* ex_col_s, float* ex_agg, float* ex_dout, int32_t* flag,
-                          void* stream_) {
-  return scn_fwd_impl(0, x, edge_index, E, nptr, eptr, N, B, F, H, K, act, W_rel, b_rel, W_root, W_mlp, b_mlp, max_n,
-                      max_e, S, y, stats, ss, losses, ticket, ex_rowptr_d, ex_col_d, ex_rowptr_s, ex_col_s, ex_agg,
-                      ex_dout, flag, stream_);
-}
-int hscn_scn_resident_bwd(const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                          const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                          const float* W_mlp, const float* S, const float* y, const float* stats, const float* ss,
-                          const float* g_mc, const float* g_o, const int32_t* ex_rowptr_d, const int32_t* ex_col_d,
-                          const int32_t* ex_rowptr_s, const int32_t* ex_col_s, const float* ex_agg,
-                          const float* ex_dout, int max_n, int max_e, float* partials, float* grads, int32_t* flag,
-                          void* stream_) {
-  return scn_bwd_impl(0, x, edge_index, E, nptr, eptr, N, B, F, H, K, act, W_mlp, S, y, stats, ss, g_mc, g_o,
-                      ex_rowptr_d, ex_col_d, ex_rowptr_s, ex_col_s, ex_agg, ex_dout, max_n, max_e, partials, grads,
-                      flag, stream_);
-}
 // A whole run of the reference's stage-A loop (train/train_clustering.py:34-50) from ONE call: `visits` graph visits
 // in dataset order, each the one-launch step of ONE graph with the optimizer in its tail and the cached structure
 // (hscn_scn_resident_train_step(B = 1, opt, cache) on graph v mod G of a dataset laid out as one batch), issued
 // back to back by this host loop -- no Python between two visits -- or, when the model has at most 1024 parameters,
 // walked by ONE persistent workgroup (k_scn_epoch: weights in LDS, Adam moments in registers).
-static int scn_epoch_impl(int f16, const float* x, const int32_t* nptr, const int32_t* eptr, int64_t N, int64_t G,
-                          int64_t visits, int F, int H, int K, int act, float* W_rel, float* b_rel, float* W_root,
-                          float* W_mlp, float* b_mlp, const float* g_mc, const float* g_o, int max_n, int max_e,
-                          const hscn_scn_structure* cache, const hscn_adam* opt, float* grads, float* stats,
-                          float* losses, int32_t* ticket, int32_t* flag, void* stream_) {
+int hscn_scn_resident_train_epoch(const void* x, const int32_t* nptr, const int32_t* eptr, int64_t N, int64_t G,
+                                  int64_t visits, int F, int H, int K, int act, float* W_rel, float* b_rel,
+                                  float* W_root, float* W_mlp, float* b_mlp, const float* g_mc, const float* g_o,
+                                  int max_n, int max_e, const hscn_scn_structure* cache, const hscn_adam* opt,
+                                  float* grads, float* stats, float* losses, int32_t* ticket, int32_t* flag,
+                                  int flags, void* stream_) {
+  if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
+  const int f16 = flags & HSCN_STORE_F16;
   if (G < 1 || N < 0 || visits < 0) return HSCN_E_BADARG;
   if (!hscn_scn_resident_train_step_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_rel || !b_rel || !W_root || !W_mlp || !b_mlp || !grads || !stats || !losses || !ticket ||
@@ -1775,7 +1766,7 @@ static int scn_epoch_impl(int f16, const float* x, const int32_t* nptr, const in
       !(opt->weight_decay >= 0.0))
     return HSCN_E_BADARG;
   ScnArgs A{};
-  A.x = x;
+  A.x = (const float*)x;
   A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
   A.stats = stats; A.losses = losses; A.ticket = ticket; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act;
   A.g_mc = g_mc; A.g_o = g_o;
@@ -1822,70 +1813,6 @@ static int scn_epoch_impl(int f16, const float* x, const int32_t* nptr, const in
     if (rc) return rc;
   }
   return 0;
-}
-
-int hscn_scn_resident_train_epoch(const float* x, const int32_t* nptr, const int32_t* eptr, int64_t N, int64_t G,
-                                  int64_t visits, int F, int H, int K, int act, float* W_rel, float* b_rel,
-                                  float* W_root, float* W_mlp, float* b_mlp, const float* g_mc, const float* g_o,
-                                  int max_n, int max_e, const hscn_scn_structure* cache, const hscn_adam* opt,
-                                  float* grads, float* stats, float* losses, int32_t* ticket, int32_t* flag,
-                                  void* stream_) {
-  return scn_epoch_impl(0, x, nptr, eptr, N, G, visits, F, H, K, act, W_rel, b_rel, W_root, W_mlp, b_mlp, g_mc, g_o,
-                        max_n, max_e, cache, opt, grads, stats, losses, ticket, flag, stream_);
-}
-int hscn_scn_resident_train_epoch_f16(const hscn_half* x, const int32_t* nptr, const int32_t* eptr, int64_t N, int64_t G,
-                                      int64_t visits, int F, int H, int K, int act, float* W_rel, float* b_rel,
-                                      float* W_root, float* W_mlp, float* b_mlp, const float* g_mc,
-                                      const float* g_o, int max_n, int max_e, const hscn_scn_structure* cache,
-                                      const hscn_adam* opt, float* grads, float* stats, float* losses,
-                                      int32_t* ticket, int32_t* flag, void* stream_) {
-  return scn_epoch_impl(1, (const float*)x, nptr, eptr, N, G, visits, F, H, K, act, W_rel, b_rel, W_root, W_mlp, b_mlp,
-                        g_mc, g_o, max_n, max_e, cache, opt, grads, stats, losses, ticket, flag, stream_);
-}
-int hscn_scn_resident_train_step(const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                                 const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                                 const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
-                                 const float* b_mlp, const float* g_mc, const float* g_o, int max_n, int max_e,
-                                 float* S, float* stats, float* losses, int32_t* ticket, float* partials,
-                                 float* grads, int32_t* flag, const hscn_adam* opt,
-                                 const hscn_scn_structure* cache, void* stream_) {
-  return scn_step_impl(0, x, edge_index, E, nptr, eptr, N, B, F, H, K, act, W_rel, b_rel, W_root, W_mlp, b_mlp, g_mc,
-                       g_o, max_n, max_e, S, stats, losses, ticket, partials, grads, flag, opt, cache, stream_);
-}
-int hscn_scn_resident_train_step_f16(const hscn_half* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                                     const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                                     const float* W_rel, const float* b_rel, const float* W_root,
-                                     const float* W_mlp, const float* b_mlp, const float* g_mc, const float* g_o,
-                                     int max_n, int max_e, float* S, float* stats, float* losses, int32_t* ticket,
-                                     float* partials, float* grads, int32_t* flag, const hscn_adam* opt,
-                                     const hscn_scn_structure* cache, void* stream_) {
-  return scn_step_impl(1, (const float*)x, edge_index, E, nptr, eptr, N, B, F, H, K, act, W_rel, b_rel, W_root,
-                       W_mlp, b_mlp, g_mc, g_o, max_n, max_e, S, stats, losses, ticket, partials, grads, flag, opt,
-                       cache, stream_);
-}
-// IEEE-half storage of the node features x and of the saved hidden activation y (include/hscn.h); S, the
-// statistics, the exported aggregation A_hat x (an accumulator output) and every gradient stay float.
-int hscn_scn_resident_fwd_f16(const hscn_half* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                              const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                              const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
-                              const float* b_mlp, int max_n, int max_e, float* S, hscn_half* y, float* stats,
-                              float* ss, float* losses, int32_t* ticket, int32_t* ex_rowptr_d, int32_t* ex_col_d,
-                              int32_t* ex_rowptr_s, int32_t* ex_col_s, float* ex_agg, float* ex_dout, int32_t* flag,
-                              void* stream_) {
-  return scn_fwd_impl(1, (const float*)x, edge_index, E, nptr, eptr, N, B, F, H, K, act, W_rel, b_rel, W_root, W_mlp,
-                      b_mlp, max_n, max_e, S, (float*)y, stats, ss, losses, ticket, ex_rowptr_d, ex_col_d, ex_rowptr_s,
-                      ex_col_s, ex_agg, ex_dout, flag, stream_);
-}
-int hscn_scn_resident_bwd_f16(const hscn_half* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                              const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                              const float* W_mlp, const float* S, const hscn_half* y, const float* stats,
-                              const float* ss, const float* g_mc, const float* g_o, const int32_t* ex_rowptr_d,
-                              const int32_t* ex_col_d, const int32_t* ex_rowptr_s, const int32_t* ex_col_s,
-                              const float* ex_agg, const float* ex_dout, int max_n, int max_e, float* partials,
-                              float* grads, int32_t* flag, void* stream_) {
-  return scn_bwd_impl(1, (const float*)x, edge_index, E, nptr, eptr, N, B, F, H, K, act, W_mlp, S, (const float*)y,
-                      stats, ss, g_mc, g_o, ex_rowptr_d, ex_col_d, ex_rowptr_s, ex_col_s, ex_agg, ex_dout, max_n,
-                      max_e, partials, grads, flag, stream_);
 }
 
 }  // extern "C"

@@ -17,7 +17,10 @@ import torch
 _LIB_PATH = os.environ.get("HSCN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libhscn.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 22
+ABI_VERSION = 23
+# `flags` of the resident entry points (include/hscn.h)
+STORE_F16 = 1
+GRAD_ACCUMULATE = 2
 ACT = {"identity": 0, "relu": 1, "elu": 2, "tanh": 3}
 
 P = c_void_p
@@ -63,14 +66,14 @@ _SIGNATURES = {
     "hscn_scn_resident_supported": (c_int, [c_int] * 5),
     "hscn_scn_resident_param_count": (c_int64, [c_int] * 3),
     "hscn_scn_resident_fwd": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, P, P, P, P, P,
-                                      c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+                                      c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, P]),
     "hscn_scn_resident_bwd": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, P, P, P, P, P,
-                                      P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P]),
+                                      P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, c_int, P]),
     "hscn_scn_resident_train_step_supported": (c_int, [c_int] * 5),
     "hscn_scn_resident_train_step": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, P, P, P,
-                                             P, P, P, P, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
+                                             P, P, P, P, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int, P]),
     "hscn_scn_resident_train_epoch": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, P, P, P, P, P,
-                                              P, P, c_int, c_int, P, P, P, P, P, P, P, P]),
+                                              P, P, c_int, c_int, P, P, P, P, P, P, P, c_int, P]),
     "hscn_adam_step": (c_int, [P, P, c_int, P, P, P, c_int64, P, P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, c_int, P]),
     "hscn_adam_step_ex": (c_int, [P, P, c_int, P, P, P, c_int64, P, P, P, ctypes.c_double, ctypes.c_double,
@@ -80,17 +83,19 @@ _SIGNATURES = {
     "hscn_resident_param_count": (c_int64, [c_int] * 4),
     "hscn_resident_fwd": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64,
                                   c_int64, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int,
-                                  c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P]),
+                                  c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P]),
     "hscn_resident_bwd": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P,
-                                  P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
+                                  P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P, c_int, P]),
     "hscn_resident_fwd_with_virtual": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int,
-                                               c_int, P, P, P, P, P, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P]),
+                                               c_int, P, P, P, P, P, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int,
+                                               P]),
     "hscn_resident_bwd_with_virtual": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int,
-                                               c_int, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P, P, P]),
+                                               c_int, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, P, P, P, P, P,
+                                               c_int, P]),
     "hscn_resident_train_step_supported": (c_int, [c_int] * 8),
     "hscn_resident_train_step_wgs_per_cu": (c_int, [c_int] * 8),
     "hscn_resident_train_step": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P,
-                                         P, P, P, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P]),
+                                         P, P, P, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P, P, c_int, P]),
     "hscn_resident_structure": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int, c_int, c_int,
                                         c_int, P, P, P]),
     "hscn_collate_gather_structure": (c_int, [P, P, P, c_int64, P, P, P, P, P, P]),
@@ -120,7 +125,7 @@ _SIGNATURES = {
     "hscn_mpnn_supported": (c_int, [c_int] * 6),
     "hscn_mpnn_param_count": (c_int64, [c_int] * 4),
     "hscn_mpnn_train_step": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int,
-                                     c_int, P, c_int, c_float, P, P, P, P, P, c_float, c_uint64, P, P]),
+                                     c_int, P, c_int, c_float, P, P, P, P, P, c_float, c_uint64, P, c_int, P]),
     "hscn_mpnn_forward": (c_int, [P, P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int,
                                   c_int, P, c_int, c_float, P, P, P, P, P, P]),
     # ABI 21: GATConv with the implicit self loop, narrow-row kernels (csrc/gat_loops.hip)
@@ -132,17 +137,6 @@ _SIGNATURES = {
     "hscn_signnet_encode": (c_int, [P, P, P, c_int64, P, P, c_int64, c_int64] + [c_int] * 9 + [P, c_int, c_int, P, P,
                                     P, P]),
 }
-_SIGNATURES["hscn_mpnn_train_step_acc"] = _SIGNATURES["hscn_mpnn_train_step"]
-# IEEE-half storage twins (include/hscn.h: hscn_resident_*_f16): same argument lists
-for _n in ("hscn_resident_fwd", "hscn_resident_bwd", "hscn_resident_fwd_with_virtual", "hscn_resident_bwd_with_virtual",
-           "hscn_scn_resident_fwd", "hscn_scn_resident_bwd", "hscn_resident_train_step",
-           "hscn_scn_resident_train_step", "hscn_scn_resident_train_epoch"):
-    _SIGNATURES[_n + "_f16"] = _SIGNATURES[_n]
-# gradient-accumulating twins (include/hscn.h, ABI 19: *_acc): same argument lists
-for _n in ("hscn_resident_bwd", "hscn_resident_bwd_with_virtual", "hscn_resident_train_step"):
-    _SIGNATURES[_n + "_acc"] = _SIGNATURES[_n]
-    _SIGNATURES[_n + "_acc_f16"] = _SIGNATURES[_n]
-
 
 class HipExtensionMissing(RuntimeError):
     pass

@@ -87,9 +87,9 @@ def supported(F: int, H: int, L: int, C: int, meta: ResidentMeta, dtype=torch.fl
     return bool(_hip.lib().hscn_resident_supported(F, H, L, C, meta.max_n, meta.max_v, meta.max_ell, meta.max_evv))
 
 
-def storage_suffix(dtype) -> str:
-    """Entry-point suffix for the storage type of node features / activations (include/hscn.h)."""
-    return "_f16" if dtype == torch.float16 else ""
+def storage_flag(dtype) -> int:
+    """``flags`` bit for the storage type of node features / activations (include/hscn.h: HSCN_STORE_F16)."""
+    return _hip.STORE_F16 if dtype == torch.float16 else 0
 
 
 def _ptr_table(ts: List[Optional[Tensor]]):
@@ -228,41 +228,41 @@ def virtual_job(x_virtual, ei_vv, ei_lv, meta: ResidentMeta, table, slope: float
                        *([ptr(t) for t in state] if state is not None else [None] * 6))
 
 
-def launch_fwd(sfx, x_local, x_virtual, ei_ll, ei_vv, ei_lv, m: ResidentMeta, dims, head_act, slope, table, head,
+def launch_fwd(flags, x_local, x_virtual, ei_ll, ei_vv, ei_lv, m: ResidentMeta, dims, head_act, slope, table, head,
                compute_virtual, out, xv_out) -> None:
     N, V, F, H, L, C, B = dims
     W1, b1, W2, b2 = head
     acts, pooled, z, pred, score, (csr_rp, csr_col, dinv) = out
-    call("hscn_resident_fwd" + sfx, ptr(x_local), ptr(x_virtual), ptr(ei_ll), ei_ll.size(1), ptr(ei_vv),
+    call("hscn_resident_fwd", ptr(x_local), ptr(x_virtual), ptr(ei_ll), ei_ll.size(1), ptr(ei_vv),
          ei_vv.size(1), ptr(ei_lv), ei_lv.size(1), ptr(m.lptr), ptr(m.vptr), ptr(m.eptr_ll), ptr(m.eptr_vv),
          ptr(m.eptr_lv), N, V, B, F, H, L, C, head_act, float(slope), table, ptr(W1), ptr(b1), ptr(W2), ptr(b2),
          m.max_n, m.max_v, m.max_ell, m.max_evv, int(bool(compute_virtual)), ptr(acts), ptr(pooled), ptr(z),
-         ptr(pred), ptr(score), ptr(xv_out), ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), stream())
+         ptr(pred), ptr(score), ptr(xv_out), ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag), flags, stream())
 
 
-def launch_fwd_with_virtual(sfx, x_local, ei_ll, m: ResidentMeta, dims, head_act, table, head, out, job) -> None:
+def launch_fwd_with_virtual(flags, x_local, ei_ll, m: ResidentMeta, dims, head_act, table, head, out, job) -> None:
     N, V, F, H, L, C, B = dims
     W1, b1, W2, b2 = head
     acts, pooled, z, pred, score, (csr_rp, csr_col, dinv) = out
-    call("hscn_resident_fwd_with_virtual" + sfx, ptr(x_local), ptr(ei_ll), ei_ll.size(1), ptr(m.lptr),
+    call("hscn_resident_fwd_with_virtual", ptr(x_local), ptr(ei_ll), ei_ll.size(1), ptr(m.lptr),
          ptr(m.eptr_ll), N, B, F, H, L, C, head_act, table, ptr(W1), ptr(b1), ptr(W2), ptr(b2), m.max_n, m.max_ell,
          ptr(acts), ptr(pooled), ptr(z), ptr(pred), ptr(score), ptr(csr_rp), ptr(csr_col), ptr(dinv), ptr(m.flag),
-         ctypes.byref(job), stream())
+         ctypes.byref(job), flags, stream())
 
 
-def launch_bwd(sfx, x_local, ei_ll, m: ResidentMeta, dims, head_act, wll_table, W1, W2, acts, pooled, z, csr,
+def launch_bwd(flags, x_local, ei_ll, m: ResidentMeta, dims, head_act, wll_table, W1, W2, acts, pooled, z, csr,
                g_pred, g_scale, partials, grads, tail, job=None) -> None:
-    """``sfx``: "_acc" (the accumulating fold) and / or the storage suffix; ``job``: the deferred virtual branch's
-    layers 1.. ride on this launch (hscn_resident_bwd_with_virtual)."""
+    """``flags``: the storage flag, ``_hip.GRAD_ACCUMULATE`` (the accumulating fold) or both; ``job``: the deferred
+    virtual branch's layers 1.. ride on this launch (hscn_resident_bwd_with_virtual)."""
     N, V, F, H, L, C, B = dims
     args = (ptr(x_local), ptr(ei_ll), ei_ll.size(1), ptr(m.lptr), ptr(m.eptr_ll), N, B, F, H, L, C, head_act,
             wll_table, ptr(W1), ptr(W2), ptr(acts), ptr(pooled), ptr(z), ptr(g_pred), ptr(g_scale), ptr(csr[0]),
             ptr(csr[1]), ptr(csr[2]), m.max_n, m.max_ell, ptr(partials), ptr(grads), ptr(m.flag),
             ctypes.byref(tail) if tail is not None else None)
     if job is None:
-        call("hscn_resident_bwd" + sfx, *args, stream())
+        call("hscn_resident_bwd", *args, flags, stream())
     else:
-        call("hscn_resident_bwd_with_virtual" + sfx, *args, ctypes.byref(job), stream())
+        call("hscn_resident_bwd_with_virtual", *args, ctypes.byref(job), flags, stream())
 
 
 class HSCNResidentFn(Function):
@@ -291,7 +291,7 @@ class HSCNResidentFn(Function):
         sdt = x_local.dtype                       # storage type of features and activations: float32 or float16
         if x_virtual.dtype != sdt:
             raise TypeError("local and virtual node features must share one storage dtype")
-        sfx = storage_suffix(sdt)
+        flags = storage_flag(sdt)
         N, F = x_local.shape
         V = x_virtual.shape[0]
         dims = (N, V, F, H, L, C, meta.num_graphs)
@@ -304,16 +304,16 @@ class HSCNResidentFn(Function):
         table = _ptr_table(params[: 9 * L])
         ctx.virtual = None
         if defer:
-            launch_fwd_with_virtual(sfx, x_local, ei_ll, meta, dims, head_act, table, head, out,
+            launch_fwd_with_virtual(flags, x_local, ei_ll, meta, dims, head_act, table, head, out,
                                     virtual_job(x_virtual, ei_vv, ei_lv, meta, table, float(slope), state))
             # what the backward launch needs to run the rest of the virtual branch beside itself
             ctx.virtual = (x_virtual, ei_vv, ei_lv, params[: 9 * L], table, float(slope), state)
         else:
-            launch_fwd(sfx, x_local, x_virtual, ei_ll, ei_vv, ei_lv, meta, dims, head_act, slope, table, head,
+            launch_fwd(flags, x_local, x_virtual, ei_ll, ei_vv, ei_lv, meta, dims, head_act, slope, table, head,
                        compute_virtual, out, xv_out)
         acts, pooled, z, pred, score, ctx.csr = out
         ctx.meta, ctx.head_act, ctx.dims = meta, head_act, dims
-        ctx.sfx = sfx
+        ctx.flags = flags
         ctx.save_for_backward(x_local, ei_ll, acts, pooled, z, head[0], head[2], *[params[9 * l] for l in range(L)])
         ret_xv = xv_out if keep_virtual else None
         ctx.mark_non_differentiable(*[t for t in (ret_xv, score) if t is not None])
@@ -352,7 +352,7 @@ class HSCNResidentFn(Function):
             x_virtual, ei_vv, ei_lv, _keep, vtable, slope, state = ctx.virtual
             xv = torch.empty(max(V, 1), H, dtype=x_virtual.dtype, device=dev)
             job = virtual_job(x_virtual, ei_vv, ei_lv, meta, vtable, slope, state, xv)
-        launch_bwd(ctx.sfx, x_local, ei_ll, meta, ctx.dims, ctx.head_act, _ptr_table(W_ll), W1, W2, acts, pooled, z,
+        launch_bwd(ctx.flags, x_local, ei_ll, meta, ctx.dims, ctx.head_act, _ptr_table(W_ll), W1, W2, acts, pooled, z,
                    ctx.csr, g_pred, g_scale, partials, grads, tail, job)
         if job is not None:
             global last_deferred_virtual
@@ -410,21 +410,21 @@ def scn_meta(data, device) -> ScnMeta:
     return meta
 
 
-def launch_scn_fwd(sfx, x, ei, m: ScnMeta, dims, act, W, S, y, stats, ss, losses, ticket, ex=None) -> None:
+def launch_scn_fwd(flags, x, ei, m: ScnMeta, dims, act, W, S, y, stats, ss, losses, ticket, ex=None) -> None:
     """hscn_scn_resident_fwd.  dims = (N, F, H, K, B, E); W = the contiguous (W_rel, b_rel, W_root, W_mlp, b_mlp);
     ex = the six buffers the forward exports for the backward (both CSRs, A_hat x, the out-degree), or None."""
     N, F, H, K, B, E = dims
-    call("hscn_scn_resident_fwd" + sfx, ptr(x), ptr(ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
+    call("hscn_scn_resident_fwd", ptr(x), ptr(ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
          act, *[ptr(w) for w in W], m.max_n, m.max_e, ptr(S), ptr(y), ptr(stats), ptr(ss), ptr(losses), ptr(ticket),
-         *([ptr(t) for t in ex] if ex is not None else [None] * 6), ptr(m.flag), stream())
+         *([ptr(t) for t in ex] if ex is not None else [None] * 6), ptr(m.flag), flags, stream())
 
 
-def launch_scn_bwd(sfx, x, ei, m: ScnMeta, dims, act, W_mlp, S, y, stats, ss, g_mc, g_o, ex, partials,
+def launch_scn_bwd(flags, x, ei, m: ScnMeta, dims, act, W_mlp, S, y, stats, ss, g_mc, g_o, ex, partials,
                    grads) -> None:
     N, F, H, K, B, E = dims
-    call("hscn_scn_resident_bwd" + sfx, ptr(x), ptr(ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
+    call("hscn_scn_resident_bwd", ptr(x), ptr(ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K,
          act, ptr(W_mlp), ptr(S), ptr(y), ptr(stats), ptr(ss), ptr(g_mc), ptr(g_o), *[ptr(t) for t in ex], m.max_n,
-         m.max_e, ptr(partials), ptr(grads), ptr(m.flag), stream())
+         m.max_e, ptr(partials), ptr(grads), ptr(m.flag), flags, stream())
 
 
 class SCNResidentFn(Function):
@@ -444,7 +444,7 @@ class SCNResidentFn(Function):
         dev = x.device
         if x.dtype not in (torch.float32, torch.float16):
             raise TypeError("node features must be float32 or float16")
-        ctx.sfx = storage_suffix(x.dtype)
+        ctx.flags = storage_flag(x.dtype)
         S = torch.empty(N, K, dtype=torch.float32, device=dev)
         y = torch.empty(N, H, dtype=x.dtype, device=dev)        # saved hidden activation: the features' storage type
         stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
@@ -461,7 +461,7 @@ class SCNResidentFn(Function):
                   torch.empty(N + B, dtype=torch.int32, device=dev), torch.empty(max(E, 1), dtype=torch.int32, device=dev),
                   torch.empty(max(N, 1), 16, dtype=torch.float32, device=dev), torch.empty(max(N, 1), dtype=torch.float32, device=dev))
         ctx.dims = (N, F, H, K, B, E)
-        launch_scn_fwd(ctx.sfx, x, edge_index, meta, ctx.dims, act, W, S, y, stats, ss, losses, meta.ticket, ex)
+        launch_scn_fwd(ctx.flags, x, edge_index, meta, ctx.dims, act, W, S, y, stats, ss, losses, meta.ticket, ex)
         ctx.ex = ex
         ctx.meta, ctx.act = meta, act
         ctx.save_for_backward(x, edge_index, W[3], S, y, stats, ss)
@@ -482,6 +482,6 @@ class SCNResidentFn(Function):
             g_o = g_total if g_o is None else g_o + g_total
         g_mc = None if g_mc is None else g_mc.reshape(1).contiguous()
         g_o = None if g_o is None else g_o.reshape(1).contiguous()
-        launch_scn_bwd(ctx.sfx, x, edge_index, ctx.meta, ctx.dims, ctx.act, W_mlp, S, y, stats, ss, g_mc, g_o, ctx.ex,
+        launch_scn_bwd(ctx.flags, x, edge_index, ctx.meta, ctx.dims, ctx.act, W_mlp, S, y, stats, ss, g_mc, g_o, ctx.ex,
                        partials, grads)
         return (None,) * 4 + tuple(grad_views(grads, ((H, F), (H,), (H, F), (K, H), (K,)), P))

@@ -135,7 +135,7 @@ class SCN(nn.Module):
             meta = _engine.scn_meta(data, dev)
             x = data.x if data.x.is_cuda else data.x.to(dev)
             ei = data.edge_index if data.edge_index.is_cuda else data.edge_index.to(dev)
-            if x.dtype != torch.float16:      # (half features stay half: include/hscn.h, hscn_scn_resident_*_f16)
+            if x.dtype != torch.float16:      # (half features stay half: include/hscn.h, HSCN_STORE_F16)
                 x = x.float()
             S, mc, o, total = _engine.SCNResidentFn.apply(x, ei, meta, _engine.ACT[self.mp.act],
                                                           conv.lin_rel.weight, conv.lin_rel.bias, conv.lin_root.weight,

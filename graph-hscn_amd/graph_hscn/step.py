@@ -74,7 +74,7 @@ class ResidentTrainStep(_FlatGradStep):
         ``engine.build_structure`` / ``DeviceHeteroDataset(resident_structure=True)`` attach) = the one-launch step
         loads them (structure_build "dataset-resident": graph structure is epoch-invariant).  Same results.
         ``accumulate``: gradient accumulation (the reference's ``batch_accumulation``, train/train.py:89-95): the
-        step's gradient fold ADDS to ``grads`` (include/hscn.h: the ``*_acc`` entry points -- the same launches), so
+        step's gradient fold ADDS to ``grads`` (include/hscn.h: HSCN_GRAD_ACCUMULATE -- the same launches), so
         k runs leave ``((g1 + g2) + ...) + gk`` there, autograd's ``p.grad += new``; ``loss`` is still the loss of the
         last run.  Whoever steps the optimizer zeroes ``grads`` afterwards (``optim.FlatAdam(zero_grads=True)``)."""
         from .model.hscn import HSCN, _act_name
@@ -98,13 +98,14 @@ class ResidentTrainStep(_FlatGradStep):
         H, C = W1.shape[0], W2.shape[0]
         self.x_local = x_dict["local"].contiguous()
         self.x_virtual = x_dict["virtual"].contiguous()
-        sdt = self.x_local.dtype        # storage type of features and activations (include/hscn.h: *_f16 twins)
+        sdt = self.x_local.dtype        # storage type of features and activations (include/hscn.h: HSCN_STORE_F16)
         if sdt not in (torch.float32, torch.float16) or self.x_virtual.dtype != sdt:
             raise TypeError("node features must be float32 (train/train.py:79 casts them) or float16, local and "
                             "virtual alike")
-        self._sfx = _engine.storage_suffix(sdt)
+        self._store = _engine.storage_flag(sdt)
         self.accumulate = bool(accumulate)
-        self._acc = "_acc" if self.accumulate else ""     # (the gradient-producing launch: its accumulating twin)
+        # (the gradient-producing launch also carries the accumulation flag)
+        self._grad_flags = self._store | (_hip.GRAD_ACCUMULATE if self.accumulate else 0)
         self.ei = {k: ei_dict[k].contiguous() for k in (LL, VV, LV)}
         N, F = self.x_local.shape
         V = self.x_virtual.shape[0]
@@ -194,22 +195,22 @@ class ResidentTrainStep(_FlatGradStep):
             N, V, F, H, L, C, B = self.dims
             W1, b1, W2, b2 = self._head
             with_v = self.idle_cus and self.virtual is not None
-            call("hscn_resident_train_step" + self._acc + self._sfx, ptr(self.x_local), ptr(ei_ll), ei_ll.size(1),
+            call("hscn_resident_train_step", ptr(self.x_local), ptr(ei_ll), ei_ll.size(1),
                  ptr(m.lptr), ptr(m.eptr_ll), N, B, F, H, L, C, self.head_act, self._table, ptr(W1), ptr(b1), ptr(W2),
                  ptr(b2), m.max_n, m.max_ell, ptr(self.target), int(self.kind), ptr(self.pred), ptr(self.score),
                  ptr(self.partials), ptr(self.grads), ptr(self.acts) if with_v else None,
                  ptr(self._sync) if with_v else None, ptr(m.flag),
                  ctypes.byref(self._job(self.virtual)) if with_v else None,
-                 ctypes.byref(self.structure.c) if self.structure is not None else None, stream())
+                 ctypes.byref(self.structure.c) if self.structure is not None else None, self._grad_flags, stream())
             return self.loss
         if self.defer:
-            _engine.launch_fwd_with_virtual(self._sfx, self.x_local, ei_ll, m, self.dims, self.head_act, self._table,
+            _engine.launch_fwd_with_virtual(self._store, self.x_local, ei_ll, m, self.dims, self.head_act, self._table,
                                             self._head, self._out, self._job(None))
         else:
-            _engine.launch_fwd(self._sfx, self.x_local, self.x_virtual, ei_ll, self.ei[VV], self.ei[LV], m, self.dims,
+            _engine.launch_fwd(self._store, self.x_local, self.x_virtual, ei_ll, self.ei[VV], self.ei[LV], m, self.dims,
                                self.head_act, self.slope, self._table, self._head, self.model.compute_virtual,
                                self._out, self.virtual)
-        _engine.launch_bwd(self._acc + self._sfx, self.x_local, ei_ll, m, self.dims, self.head_act, self._wll_table,
+        _engine.launch_bwd(self._grad_flags, self.x_local, ei_ll, m, self.dims, self.head_act, self._wll_table,
                            self._head[0], self._head[2], self.acts, self.pooled, self.z, self.csr, None, None,
                            self.partials, self.grads, self._tail, self._job(self.virtual) if self.defer else None)
         return self.loss
@@ -303,7 +304,7 @@ class ScnTrainStep:
         self.meta = meta = _engine.scn_meta(data, dev)
         x = data.x if data.x.is_cuda else data.x.to(dev)
         self.x = (x if x.dtype == torch.float16 else x.float()).contiguous()
-        self._sfx = _engine.storage_suffix(self.x.dtype)
+        self._store = _engine.storage_flag(self.x.dtype)
         self.ei = (data.edge_index if data.edge_index.is_cuda else data.edge_index.to(dev)).contiguous()
         self.act = _engine.ACT[model.mp.act]
         self._mp = [conv.lin_rel.weight, conv.lin_rel.bias, conv.lin_root.weight, lin.weight, lin.bias]
@@ -346,7 +347,7 @@ class ScnTrainStep:
                 and [id(p) for p in getattr(opt, "params", [])] == [id(p) for p in self._mp])
 
     def _one_launch_args(self, W, opt) -> tuple:
-        """hscn_scn_resident_train_step's arguments but the stream (``W``: the five parameters, contiguous)."""
+        """hscn_scn_resident_train_step's arguments up to ``flags`` (``W``: the five parameters, contiguous)."""
         N, F, H, K, B, E = self.dims
         m = self.meta
         return (ptr(self.x), ptr(self.ei) if E else None, E, ptr(m.nptr), ptr(m.eptr), N, B, F, H, K, self.act,
@@ -362,9 +363,9 @@ class ScnTrainStep:
             if opt is not None:
                 raise ValueError("this step cannot carry the optimizer step (see ScnTrainStep.fuses_optimizer)")
             W = [p.contiguous() for p in self._mp]
-            _engine.launch_scn_fwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act, W, self.S, self.y,
+            _engine.launch_scn_fwd(self._store, self.x, self.ei, self.meta, self.dims, self.act, W, self.S, self.y,
                                    self.stats, self.ss, self.losses, self.meta.ticket, self.ex)
-            _engine.launch_scn_bwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act, W[3], self.S, self.y,
+            _engine.launch_scn_bwd(self._store, self.x, self.ei, self.meta, self.dims, self.act, W[3], self.S, self.y,
                                    self.stats, self.ss, self.one, self.one, self.ex, self.partials, self.grads)
             return self.losses[2]
         # the argument list of a step is the same every visit (device pointers of buffers allocated once, the
@@ -379,14 +380,14 @@ class ScnTrainStep:
             else:                   # (non-contiguous parameters: copies, every call; opt is None, see fuses_optimizer)
                 W = [p.contiguous() for p in self._mp]
                 hit = (None, self._one_launch_args(W, None))
-        call("hscn_scn_resident_train_step" + self._sfx, *hit[1], stream())
+        call("hscn_scn_resident_train_step", *hit[1], self._store, stream())
         if self._cache is not None:
             self._cache.ready = 1          # (read at issue time: the launch in flight saw 0 and exports)
         return self.losses[2]
 
     def run_forward(self) -> Tensor:
         """The forward launch alone (the assignment pass, train/train_clustering.py:57-69): refreshes ``S``."""
-        _engine.launch_scn_fwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act,
+        _engine.launch_scn_fwd(self._store, self.x, self.ei, self.meta, self.dims, self.act,
                                [p.contiguous() for p in self._mp], self.S, self.y, self.stats, self.ss, self.losses,
                                self.meta.ticket)
         return self.S
@@ -427,7 +428,7 @@ class ScnEpochRunner:
         self.meta = meta = _engine.scn_meta(big, dev)
         x = big.x if big.x.is_cuda else big.x.to(dev)
         self.x = (x if x.dtype == torch.float16 else x.float()).contiguous()
-        self._sfx = _engine.storage_suffix(self.x.dtype)
+        self._store = _engine.storage_flag(self.x.dtype)
         self.ei = (big.edge_index if big.edge_index.is_cuda else big.edge_index.to(dev)).contiguous()
         self.act = _engine.ACT[model.mp.act]
         self._mp = [conv.lin_rel.weight, conv.lin_rel.bias, conv.lin_root.weight, lin.weight, lin.bias]
@@ -459,7 +460,7 @@ class ScnEpochRunner:
         self._cache = _ScnStructC(ptr(c[0]), ptr(c[1]), ptr(c[2]), ptr(c[3]), ptr(c[4]), ptr(c[5]), ptr(self._xpad), 1)
 
     def _forward(self, export: bool) -> None:
-        _engine.launch_scn_fwd(self._sfx, self.x, self.ei, self.meta, self.dims, self.act, self._mp, self.S, self._y,
+        _engine.launch_scn_fwd(self._store, self.x, self.ei, self.meta, self.dims, self.act, self._mp, self.S, self._y,
                                self._stats, self._ss, self.losses, self._ticket, self._cache_t if export else None)
 
     def run(self, visits: int) -> None:
@@ -467,11 +468,11 @@ class ScnEpochRunner:
         asynchronous."""
         N, F, H, K, G, E = self.dims
         m = self.meta
-        call("hscn_scn_resident_train_epoch" + self._sfx, ptr(self.x), ptr(m.nptr), ptr(m.eptr), N, G, int(visits), F, H,
+        call("hscn_scn_resident_train_epoch", ptr(self.x), ptr(m.nptr), ptr(m.eptr), N, G, int(visits), F, H,
              K, self.act, *[ptr(p_) for p_ in self._mp], ptr(self._one), ptr(self._one), m.max_n, m.max_e,
              ctypes.byref(self._cache),
              ctypes.byref(self.optimizer.c), ptr(self.grads), ptr(self._stats), ptr(self.losses), ptr(self._ticket),
-             ptr(m.flag), stream())
+             ptr(m.flag), self._store, stream())
 
     def assign(self) -> Tensor:
         """The assignment pass (train/train_clustering.py:57-69) as ONE forward launch over the dataset: the soft
@@ -497,7 +498,7 @@ class MPNNResidentTrainStep(_FlatGradStep):
 
     Outputs refreshed by ``run()``: ``pred`` [B,C], ``score`` [B,C] (sigmoid), ``loss`` (0-dim), ``grads`` (flat, the
     parameter gradients in ``model.parameters()`` order, then the loss).  ``bind_grads()`` points every ``p.grad`` at
-    its slice.  ``accumulate``: the fold ADDS to ``grads`` (``hscn_mpnn_train_step_acc``); ``loss`` is the last run's.
+    its slice.  ``accumulate``: the fold ADDS to ``grads`` (HSCN_GRAD_ACCUMULATE); ``loss`` is the last run's.
 
     Dropout (``model.training`` and ``model.dropout > 0``): hidden layer i of the t-th ``run()`` (t = ``step_word``,
     a device counter the fold advances) draws the mask nn.functional.dropout draws with seed ``seed0 + (L-1) t + i``;
@@ -563,10 +564,11 @@ class MPNNResidentTrainStep(_FlatGradStep):
     def run(self) -> Tensor:
         """Issue the step on the current stream; returns ``loss`` (valid once the stream has run)."""
         N, F, H, L, C, B = self.dims
-        call("hscn_mpnn_train_step" + ("_acc" if self.accumulate else ""), ptr(self.x), ptr(self.ei), self.ei.size(1),
+        call("hscn_mpnn_train_step", ptr(self.x), ptr(self.ei), self.ei.size(1),
              ptr(self.ptr32), ptr(self.eptr32), N, B, F, H, L, C, self.act, self._table, self.max_n, self.max_e,
              ptr(self.target), int(self.kind), self.inv_count, ptr(self.pred), ptr(self.score), ptr(self.partials),
-             ptr(self.grads), ptr(self.step_word), self.p, self.seed0, ptr(self.flag), stream())
+             ptr(self.grads), ptr(self.step_word), self.p, self.seed0, ptr(self.flag),
+             _hip.GRAD_ACCUMULATE if self.accumulate else 0, stream())
         return self.loss
 
     def check(self) -> None:

@@ -34,11 +34,18 @@
 extern "C" {
 #endif
 
-#define HSCN_ABI_VERSION 22
+#define HSCN_ABI_VERSION 23
 
 #define HSCN_E_BADARG (-1)   /* null pointer, negative size, unsupported width */
 #define HSCN_E_WORKSPACE (-2) /* workspace too small */
 #define HSCN_E_UNSUPPORTED (-3)
+
+/* `flags` of the resident entry points (ABI 23; the last parameter before `stream`).  An entry point takes the bits
+ * its comment names and answers HSCN_E_BADARG for any other, before any launch.
+ *   HSCN_STORE_F16       node features and activations are IEEE half ("half storage", below at hscn_half)
+ *   HSCN_GRAD_ACCUMULATE the gradient fold adds to `grads` ("gradient accumulation", below) */
+#define HSCN_STORE_F16 1
+#define HSCN_GRAD_ACCUMULATE 2
 
 /* activation codes (reference graph_hscn/config/config.py:13-18 ACT_DICT) */
 #define HSCN_ACT_IDENTITY 0
@@ -479,22 +486,24 @@ typedef struct hscn_loss_tail {
 } hscn_loss_tail;
 int hscn_resident_supported(int F, int H, int L, int C, int max_n, int max_v, int max_ell, int max_evv);
 int64_t hscn_resident_param_count(int F, int H, int L, int C);
-int hscn_resident_fwd(const float* x_local, const float* x_virtual, const int64_t* ei_ll, int64_t E_ll,
+int hscn_resident_fwd(const void* x_local, const void* x_virtual, const int64_t* ei_ll, int64_t E_ll,
                       const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv,
                       const int32_t* lptr, const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv,
                       const int32_t* eptr_lv, int64_t N, int64_t V, int64_t B, int F, int H, int L, int C,
                       int head_act, float slope, const void* const* layer_params_host,
                       const float* W1, const float* b1, const float* W2, const float* b2, int max_n, int max_v,
-                      int max_ell, int max_evv, int compute_virtual, float* acts, float* pooled, float* z,
-                      float* pred, float* score /*[B,C] or NULL*/, float* xv_out, int32_t* csr_rowptr_t /*[N+B]*/,
-                      int32_t* csr_col_t /*[E_ll]*/, float* dinv /*[N]*/, int32_t* flag, void* stream);
-int hscn_resident_bwd(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                      int max_ell, int max_evv, int compute_virtual, void* acts, float* pooled, float* z,
+                      float* pred, float* score /*[B,C] or NULL*/, void* xv_out, int32_t* csr_rowptr_t /*[N+B]*/,
+                      int32_t* csr_col_t /*[E_ll]*/, float* dinv /*[N]*/, int32_t* flag,
+                      int flags /*HSCN_STORE_F16*/, void* stream);
+int hscn_resident_bwd(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                       const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
-                      const void* const* W_ll_host, const float* W1, const float* W2, const float* acts,
+                      const void* const* W_ll_host, const float* W1, const float* W2, const void* acts,
                       const float* pooled, const float* z, const float* g_pred, const float* g_scale /*[1] or NULL*/,
                       const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n,
                       int max_ell, float* partials /*[B,P]*/, float* grads /*[P]*/, int32_t* flag,
-                      const hscn_loss_tail* tail /*or NULL*/, void* stream);
+                      const hscn_loss_tail* tail /*or NULL*/, int flags /*HSCN_STORE_F16 | HSCN_GRAD_ACCUMULATE*/,
+                      void* stream);
 
 /* hscn_resident_bwd that also carries the virtual branch of the SAME step's forward: one launch
  * of 2B workgroups, even ones run the backward of graph g, odd ones what a compute_virtual = 2
@@ -529,21 +538,22 @@ typedef struct hscn_virtual_job {
 /* hscn_resident_fwd with compute_virtual = 0 (local chain + head, CSR export) whose launch also
  * carries, as odd workgroups, the first part of the virtual branch described by `job` (state
  * pointers required, L >= 2).  Pair it with hscn_resident_bwd_with_virtual on the same job. */
-int hscn_resident_fwd_with_virtual(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int hscn_resident_fwd_with_virtual(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                                    const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
                                    int head_act, const void* const* layer_params_host, const float* W1,
                                    const float* b1, const float* W2, const float* b2, int max_n, int max_ell,
-                                   float* acts, float* pooled, float* z, float* pred, float* score /*or NULL*/,
+                                   void* acts, float* pooled, float* z, float* pred, float* score /*or NULL*/,
                                    int32_t* csr_rowptr_t, int32_t* csr_col_t, float* dinv, int32_t* flag,
-                                   const hscn_virtual_job* job, void* stream);
-int hscn_resident_bwd_with_virtual(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+                                   const hscn_virtual_job* job, int flags /*HSCN_STORE_F16*/, void* stream);
+int hscn_resident_bwd_with_virtual(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                                    const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
                                    int head_act, const void* const* W_ll_host, const float* W1, const float* W2,
-                                   const float* acts, const float* pooled, const float* z, const float* g_pred,
+                                   const void* acts, const float* pooled, const float* z, const float* g_pred,
                                    const float* g_scale /*[1] or NULL*/, const int32_t* csr_rowptr_t,
                                    const int32_t* csr_col_t, const float* dinv, int max_n, int max_ell,
                                    float* partials /*[B,P]*/, float* grads /*[P]*/, int32_t* flag,
-                                   const hscn_loss_tail* tail /*or NULL*/, const hscn_virtual_job* job, void* stream);
+                                   const hscn_loss_tail* tail /*or NULL*/, const hscn_virtual_job* job,
+                                   int flags /*HSCN_STORE_F16 | HSCN_GRAD_ACCUMULATE*/, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * structure_build = "dataset-resident".  The reference rebuilds nothing because it has no structure to build
@@ -604,112 +614,42 @@ int hscn_resident_train_step_supported(int F, int H, int L, int C, int max_n, in
  * dispatched before its consumer and no local program waits on anybody -- and, for 16-wave workgroups at H = 16, faster
  * than the launch pair (the caller's choice: graph_hscn/step.py takes it there). */
 int hscn_resident_train_step_wgs_per_cu(int F, int H, int L, int C, int max_n, int max_ell, int max_v, int max_evv);
-int hscn_resident_train_step(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
+int hscn_resident_train_step(const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
                              const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
                              const void* const* layer_params_host /* L x 9 */, const float* W1, const float* b1,
                              const float* W2, const float* b2, int max_n, int max_ell, const float* target,
                              int loss_kind, float* pred, float* score /*or NULL*/, float* partials /*[B,P+1]*/,
-                             float* grads /*[P+1]*/, float* acts /*or NULL*/, uint32_t* sync /*or NULL*/,
+                             float* grads /*[P+1]*/, void* acts /*or NULL*/, uint32_t* sync /*or NULL*/,
                              int32_t* flag, const hscn_virtual_job* job /*or NULL*/,
-                             const hscn_structure* structure /*or NULL: build per step*/, void* stream);
+                             const hscn_structure* structure /*or NULL: build per step*/,
+                             int flags /*HSCN_STORE_F16 | HSCN_GRAD_ACCUMULATE*/, void* stream);
 
 /* ------------------------------------------------------------------------- *
- * BASELINE.json configs[4] ("fp16 feat + bf16 accum", PCQM-Contact): the four launches above with IEEE-half
- * STORAGE of node features and inter-layer activations.  The reference has no reduced-precision mode (no
- * autocast / half anywhere); these entry points replace the same call sites as their float
- * twins (model/hscn.py:102-114, train/train.py:76-87) for a caller that keeps `x` in half.
- *   half (hscn_half = the 16 bits of an IEEE binary16): x_local, x_virtual, acts, xv_out, and in `job`:
- *   x_virtual, xv_out, st_xv (declared float* there; they point to half arrays for these entry points);
- *   float: parameters, pooled, z, pred, score, degree norms, partials, grads.  Every sum accumulates in float
- *   registers (a superset of bf16 accumulation); an activation is rounded to half once, where it is produced.
- *   H in {16, 32}; everything else as documented for the float entry points.
+ * Half storage (HSCN_STORE_F16; BASELINE.json configs[4], "fp16 feat + bf16 accum", PCQM-Contact): the launches
+ * above and the stage-A launches below with IEEE-half STORAGE of node features and inter-layer activations.  The
+ * reference has no reduced-precision mode (no autocast / half anywhere); the flag serves the same call
+ * sites (model/hscn.py:102-114, train/train.py:76-87, train/train_clustering.py:37-50) for a caller that keeps `x`
+ * in half.  The arrays whose element type the flag selects are declared `void*`:
+ *   hscn_resident_*: x_local, x_virtual, acts, xv_out, and in `job`: x_virtual, xv_out, st_xv (declared float*
+ *     there; they point to hscn_half arrays under the flag);
+ *   hscn_scn_resident_*: x [N,F] and the saved hidden activation y [N,H].
+ *   float either way: parameters, pooled, z, pred, score, degree norms, S, stats, ss, losses, the exported
+ *   aggregation ex_agg, partials, grads.  Every sum accumulates in float registers (a superset of bf16
+ *   accumulation); an activation is rounded to half once, where it is produced.
+ *   H in {16, 32} (HSCN_E_UNSUPPORTED otherwise); everything else as documented without the flag.
  * ------------------------------------------------------------------------- */
-typedef uint16_t hscn_half;
-int hscn_resident_fwd_f16(const hscn_half* x_local, const hscn_half* x_virtual, const int64_t* ei_ll, int64_t E_ll,
-                          const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv,
-                          const int32_t* lptr, const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv,
-                          const int32_t* eptr_lv, int64_t N, int64_t V, int64_t B, int F, int H, int L, int C,
-                          int head_act, float slope, const void* const* layer_params_host /* L x 9 */,
-                          const float* W1, const float* b1, const float* W2, const float* b2, int max_n, int max_v,
-                          int max_ell, int max_evv, int compute_virtual, hscn_half* acts, float* pooled, float* z,
-                          float* pred, float* score, hscn_half* xv_out, int32_t* csr_rowptr_t, int32_t* csr_col_t,
-                          float* dinv_out, int32_t* flag, void* stream);
-int hscn_resident_bwd_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                          const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
-                          const void* const* W_ll_host /* L */, const float* W1, const float* W2,
-                          const hscn_half* acts, const float* pooled, const float* z, const float* g_pred,
-                          const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
-                          const float* dinv, int max_n, int max_ell, float* partials /*[B][P]*/,
-                          float* grads /*[P]*/, int32_t* flag, const hscn_loss_tail* tail, void* stream);
-int hscn_resident_fwd_with_virtual_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll,
-                                       const int32_t* lptr, const int32_t* eptr_ll, int64_t N, int64_t B, int F,
-                                       int H, int L, int C, int head_act, const void* const* layer_params_host,
-                                       const float* W1, const float* b1, const float* W2, const float* b2, int max_n,
-                                       int max_ell, hscn_half* acts, float* pooled, float* z, float* pred,
-                                       float* score, int32_t* csr_rowptr_t, int32_t* csr_col_t, float* dinv,
-                                       int32_t* flag, const hscn_virtual_job* job, void* stream);
-int hscn_resident_bwd_with_virtual_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll,
-                                       const int32_t* lptr, const int32_t* eptr_ll, int64_t N, int64_t B, int F,
-                                       int H, int L, int C, int head_act, const void* const* W_ll_host,
-                                       const float* W1, const float* W2, const hscn_half* acts, const float* pooled,
-                                       const float* z, const float* g_pred, const float* g_scale,
-                                       const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv,
-                                       int max_n, int max_ell, float* partials, float* grads, int32_t* flag,
-                                       const hscn_loss_tail* tail, const hscn_virtual_job* job, void* stream);
+typedef uint16_t hscn_half; /* the 16 bits of an IEEE binary16 */
 
 /* ------------------------------------------------------------------------- *
- * ABI 19: gradient accumulation over micro-batches (reference train/train.py:89-95: `batch_accumulation`, the
- * optimizer steps every k-th batch on the SUM of their gradients).  The *_acc entry points are the launches of
- * hscn_resident_bwd, hscn_resident_bwd_with_virtual, hscn_resident_train_step and their _f16 twins, argument for
- * argument and launch for launch, except that the final fold ADDS each parameter column to `grads`:
- *   grads[p] = grads[p] + sum_g partials[g][p]   (p < P: the sum formed exactly as in the plain entry point, added
+ * Gradient accumulation over micro-batches (HSCN_GRAD_ACCUMULATE; reference train/train.py:89-95:
+ * `batch_accumulation`, the optimizer steps every k-th batch on the SUM of their gradients).  hscn_resident_bwd,
+ * hscn_resident_bwd_with_virtual, hscn_resident_train_step and hscn_mpnn_train_step issue the same launches under
+ * the flag, except that the final fold ADDS each parameter column to `grads`:
+ *   grads[p] = grads[p] + sum_g partials[g][p]   (p < P: the sum formed exactly as without the flag, added
  *                                                  last -- autograd's `p.grad += new`, rounding for rounding)
  * The loss column grads[P] (with a loss tail) is still overwritten: it is the loss of THIS micro-batch.  The caller
  * zeroes `grads` where the reference calls optimizer.zero_grad() (hscn_adam_step_ex can do it in its launch).
  * ------------------------------------------------------------------------- */
-int hscn_resident_bwd_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                          const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
-                          const void* const* W_ll_host /* L */, const float* W1, const float* W2, const float* acts,
-                          const float* pooled, const float* z, const float* g_pred, const float* g_scale,
-                          const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n,
-                          int max_ell, float* partials /*[B][P]*/, float* grads /*[P]*/, int32_t* flag,
-                          const hscn_loss_tail* tail, void* stream);
-int hscn_resident_bwd_with_virtual_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                                       const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
-                                       int head_act, const void* const* W_ll_host, const float* W1, const float* W2,
-                                       const float* acts, const float* pooled, const float* z, const float* g_pred,
-                                       const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
-                                       const float* dinv, int max_n, int max_ell, float* partials, float* grads,
-                                       int32_t* flag, const hscn_loss_tail* tail, const hscn_virtual_job* job,
-                                       void* stream);
-int hscn_resident_train_step_acc(const float* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                                 const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
-                                 const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
-                                 const float* b2, int max_n, int max_ell, const float* target, int loss_kind, float* pred,
-                                 float* score, float* partials, float* grads, float* acts, uint32_t* sync, int32_t* flag,
-                                 const hscn_virtual_job* job, const hscn_structure* structure, void* stream);
-int hscn_resident_bwd_acc_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                              const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C, int head_act,
-                              const void* const* W_ll_host /* L */, const float* W1, const float* W2,
-                              const hscn_half* acts, const float* pooled, const float* z, const float* g_pred,
-                              const float* g_scale, const int32_t* csr_rowptr_t, const int32_t* csr_col_t,
-                              const float* dinv, int max_n, int max_ell, float* partials /*[B][P]*/,
-                              float* grads /*[P]*/, int32_t* flag, const hscn_loss_tail* tail, void* stream);
-int hscn_resident_bwd_with_virtual_acc_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll,
-                                           const int32_t* lptr, const int32_t* eptr_ll, int64_t N, int64_t B, int F,
-                                           int H, int L, int C, int head_act, const void* const* W_ll_host,
-                                           const float* W1, const float* W2, const hscn_half* acts, const float* pooled,
-                                           const float* z, const float* g_pred, const float* g_scale,
-                                           const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv,
-                                           int max_n, int max_ell, float* partials, float* grads, int32_t* flag,
-                                           const hscn_loss_tail* tail, const hscn_virtual_job* job, void* stream);
-int hscn_resident_train_step_acc_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                                     const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
-                                     int head_act, const void* const* layer_params_host, const float* W1, const float* b1,
-                                     const float* W2, const float* b2, int max_n, int max_ell, const float* target,
-                                     int loss_kind, float* pred, float* score, float* partials, float* grads,
-                                     hscn_half* acts, uint32_t* sync, int32_t* flag, const hscn_virtual_job* job,
-                                     const hscn_structure* structure, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * a2/a4/a6  stage A, graph-resident engine: the body of the reference's clustering loop
@@ -735,21 +675,22 @@ int hscn_resident_train_step_acc_f16(const hscn_half* x_local, const int64_t* ei
  * ------------------------------------------------------------------------- */
 int hscn_scn_resident_supported(int F, int H, int K, int max_n, int max_e);
 int64_t hscn_scn_resident_param_count(int F, int H, int K);
-int hscn_scn_resident_fwd(const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
+int hscn_scn_resident_fwd(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
                           const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
                           const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
-                          const float* b_mlp, int max_n, int max_e, float* S, float* y, float* stats, float* ss,
+                          const float* b_mlp, int max_n, int max_e, float* S, void* y, float* stats, float* ss,
                           float* losses /*[3]*/, int32_t* ticket /*[1] or NULL*/, int32_t* ex_rowptr_d /*[N+B]*/,
                           int32_t* ex_col_d /*[E]*/,
                           int32_t* ex_rowptr_s /*[N+B]*/, int32_t* ex_col_s /*[E]*/, float* ex_agg /*[N,16]*/,
-                          float* ex_dout /*[N]*/, int32_t* flag, void* stream);
-int hscn_scn_resident_bwd(const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
+                          float* ex_dout /*[N]*/, int32_t* flag, int flags /*HSCN_STORE_F16*/, void* stream);
+int hscn_scn_resident_bwd(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
                           const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                          const float* W_mlp, const float* S, const float* y, const float* stats, const float* ss,
+                          const float* W_mlp, const float* S, const void* y, const float* stats, const float* ss,
                           const float* g_mc /*[1] or NULL*/, const float* g_o /*[1] or NULL*/,
                           const int32_t* ex_rowptr_d, const int32_t* ex_col_d, const int32_t* ex_rowptr_s,
                           const int32_t* ex_col_s, const float* ex_agg, const float* ex_dout, int max_n, int max_e,
-                          float* partials /*[B,P]*/, float* grads /*[P]*/, int32_t* flag, void* stream);
+                          float* partials /*[B,P]*/, float* grads /*[P]*/, int32_t* flag,
+                          int flags /*HSCN_STORE_F16*/, void* stream);
 
 /* State and hyper-parameters of torch's Adam / AdamW for the one-launch optimizer step (hscn_adam_step, below) and for
  * the stage-A step that applies it in its own tail: exp_avg / exp_avg_sq [P] (flat parameter order, zero before the
@@ -794,14 +735,15 @@ typedef struct hscn_scn_structure {
  * cache != NULL: see hscn_scn_structure.
  * hscn_scn_resident_train_step_supported: the pair's conditions, K % 4 == 0, K <= 32 (H = 16) and max_n <= 512. */
 int hscn_scn_resident_train_step_supported(int F, int H, int K, int max_n, int max_e);
-int hscn_scn_resident_train_step(const float* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
+int hscn_scn_resident_train_step(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
                                  const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
                                  const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
                                  const float* b_mlp, const float* g_mc /*[1] or NULL*/, const float* g_o /*[1] or NULL*/,
                                  int max_n, int max_e, float* S /*[N,K] or NULL*/, float* stats /*[B,4]*/,
                                  float* losses /*[3]*/, int32_t* ticket /*[1] or NULL*/, float* partials /*[B,P]*/,
                                  float* grads /*[P]*/, int32_t* flag, const hscn_adam* opt /*or NULL*/,
-                                 const hscn_scn_structure* cache /*or NULL*/, void* stream);
+                                 const hscn_scn_structure* cache /*or NULL*/, int flags /*HSCN_STORE_F16*/,
+                                 void* stream);
 /* A whole run of the reference's stage-A loop (train/train_clustering.py:34-50: one optimizer step per graph, graph
  * after graph, epoch after epoch) from ONE call: `visits` graph visits in dataset order (visit v takes graph v mod G
  * of a dataset laid out as one block-diagonal batch: nptr / eptr [G+1]), each the launch of
@@ -813,52 +755,13 @@ int hscn_scn_resident_train_step(const float* x, const int64_t* edge_index, int6
  * opt's state are updated in place by every visit; g_mc / g_o: the upstream gradients of the two losses (device
  * scalars; the loop's loss mincut + ortho has both = 1); grads [P], stats [4], losses [3]: the last visit's; ticket:
  * a zeroed device int32.  hscn_scn_resident_train_step_supported says whether the shapes qualify. */
-int hscn_scn_resident_train_epoch(const float* x, const int32_t* nptr, const int32_t* eptr, int64_t N, int64_t G,
+int hscn_scn_resident_train_epoch(const void* x, const int32_t* nptr, const int32_t* eptr, int64_t N, int64_t G,
                                   int64_t visits, int F, int H, int K, int act, float* W_rel, float* b_rel,
                                   float* W_root, float* W_mlp, float* b_mlp, const float* g_mc /*[1]*/,
                                   const float* g_o /*[1]*/, int max_n, int max_e,
                                   const hscn_scn_structure* cache, const hscn_adam* opt, float* grads /*[P]*/,
                                   float* stats /*[4]*/, float* losses /*[3]*/, int32_t* ticket, int32_t* flag,
-                                  void* stream);
-int hscn_scn_resident_train_epoch_f16(const hscn_half* x, const int32_t* nptr, const int32_t* eptr, int64_t N,
-                                      int64_t G, int64_t visits, int F, int H, int K, int act, float* W_rel,
-                                      float* b_rel, float* W_root, float* W_mlp, float* b_mlp, const float* g_mc,
-                                      const float* g_o, int max_n, int max_e, const hscn_scn_structure* cache,
-                                      const hscn_adam* opt, float* grads, float* stats, float* losses,
-                                      int32_t* ticket, int32_t* flag, void* stream);
-int hscn_scn_resident_train_step_f16(const hscn_half* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                                     const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                                     const float* W_rel, const float* b_rel, const float* W_root,
-                                     const float* W_mlp, const float* b_mlp, const float* g_mc, const float* g_o,
-                                     int max_n, int max_e, float* S, float* stats, float* losses, int32_t* ticket,
-                                     float* partials, float* grads, int32_t* flag, const hscn_adam* opt,
-                                     const hscn_scn_structure* cache, void* stream);
-
-int hscn_resident_train_step_f16(const hscn_half* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                                 const int32_t* eptr_ll, int64_t N, int64_t B, int F, int H, int L, int C,
-                                 int head_act, const void* const* layer_params_host, const float* W1, const float* b1,
-                                 const float* W2, const float* b2, int max_n, int max_ell, const float* target,
-                                 int loss_kind, float* pred, float* score, float* partials, float* grads,
-                                 hscn_half* acts, uint32_t* sync, int32_t* flag, const hscn_virtual_job* job,
-                                 const hscn_structure* structure, void* stream);
-
-/* IEEE-half storage twins of the two stage-A launches (BASELINE.json configs[4]): x [N,F] and the saved hidden
- * activation y [N,H] are half (y rounded once, where it is produced); S, stats, ss, losses, the exported
- * aggregation ex_agg and all gradients stay float.  Same call sites as the float twins. */
-int hscn_scn_resident_fwd_f16(const hscn_half* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                              const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                              const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp,
-                              const float* b_mlp, int max_n, int max_e, float* S, hscn_half* y, float* stats,
-                              float* ss, float* losses /*[3]*/, int32_t* ticket, int32_t* ex_rowptr_d,
-                              int32_t* ex_col_d, int32_t* ex_rowptr_s, int32_t* ex_col_s, float* ex_agg,
-                              float* ex_dout, int32_t* flag, void* stream);
-int hscn_scn_resident_bwd_f16(const hscn_half* x, const int64_t* edge_index, int64_t E, const int32_t* nptr,
-                              const int32_t* eptr, int64_t N, int64_t B, int F, int H, int K, int act,
-                              const float* W_mlp, const float* S, const hscn_half* y, const float* stats,
-                              const float* ss, const float* g_mc, const float* g_o, const int32_t* ex_rowptr_d,
-                              const int32_t* ex_col_d, const int32_t* ex_rowptr_s, const int32_t* ex_col_s,
-                              const float* ex_agg, const float* ex_dout, int max_n, int max_e,
-                              float* partials /*[B,P]*/, float* grads /*[P]*/, int32_t* flag, void* stream);
+                                  int flags /*HSCN_STORE_F16*/, void* stream);
 
 /* ---------------------------------------------------------------------------
  * The optimizer step behind a resident training step as ONE launch: torch.optim.Adam / AdamW (the optimizers
@@ -973,8 +876,8 @@ int hscn_allreduce_oneshot(float* flat, int64_t count, void* const* peer_slots_h
  *   a captured step draws new masks on every replay).  step may be NULL when p = 0 (t = 0; nothing advanced).
  *   flag bit 1: an edge with an end outside its graph (dropped); bit 2: a graph beyond max_n / max_ell or the
  *   arrays (its partials row is zeros).
- * hscn_mpnn_train_step_acc: the same launches, the fold ADDS every parameter column to grads (as the ABI 19 *_acc
- *   entry points; grads[P] is still the loss of this call).
+ *   flags: HSCN_GRAD_ACCUMULATE = the same launches, the fold ADDS every parameter column to grads (as for the
+ *   hscn_resident_* entry points; grads[P] is still the loss of this call).
  * hscn_mpnn_forward: the forward alone (no dropout: evaluation / inference): pred, score (optional), and with a
  *   target the per-graph loss-term sums loss_rows [B] and, if loss != NULL, the mean loss loss[0].
  * hscn_mpnn_supported: H in {16, 32}, 1 <= F <= H, C <= min(H, 16), 2 <= L <= 8, and a layout of the largest graph
@@ -988,12 +891,7 @@ int hscn_mpnn_train_step(const float* x, const int64_t* edge_index, int64_t E, c
                          const void* const* params_host /* L x 2 */, int max_n, int max_ell, const float* target,
                          int loss_kind, float inv_count, float* pred, float* score /*or NULL*/,
                          float* partials /*[B,P+1]*/, float* grads /*[P+1]*/, uint32_t* step /*or NULL if p = 0*/,
-                         float p, uint64_t seed0, int32_t* flag, void* stream);
-int hscn_mpnn_train_step_acc(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
-                             const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
-                             const void* const* params_host, int max_n, int max_ell, const float* target,
-                             int loss_kind, float inv_count, float* pred, float* score, float* partials, float* grads,
-                             uint32_t* step, float p, uint64_t seed0, int32_t* flag, void* stream);
+                         float p, uint64_t seed0, int32_t* flag, int flags /*HSCN_GRAD_ACCUMULATE*/, void* stream);
 int hscn_mpnn_forward(const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
                       const int32_t* eptr32, int64_t N, int64_t B, int F, int H, int L, int C, int act,
                       const void* const* params_host, int max_n, int max_ell, const float* target /*or NULL*/,

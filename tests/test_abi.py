@@ -48,6 +48,78 @@ def test_error_strings_and_argument_checks_without_a_gpu():
     assert lib.hscn_resident_param_count(9, 16, 3, 10) == 9 * 16 + 16 + 2 * (256 + 16) + 256 + 16 + 160 + 10
 
 
+# The ten entry points that take `flags` (include/hscn.h, ABI 23): the bits each has a variant for, and a call that
+# launches nothing yet gets past the flag check -- {argument position: value} over NULL pointers and zero sizes
+# (_BUF: a host buffer standing in for a pointer the checks only compare with NULL) and what that call answers.
+_STORE_F16, _GRAD_ACCUMULATE = 1, 2
+_BUF = ctypes.create_string_buffer(512)
+_HERE = ctypes.addressof(_BUF)
+_FLAGGED = {
+    # B = 0 (nothing to do: 0) at H = 16
+    "hscn_resident_fwd": (_STORE_F16, {17: 16}, 0),
+    "hscn_resident_fwd_with_virtual": (_STORE_F16, {8: 16, -3: _HERE}, 0),                       # -3: job
+    "hscn_resident_bwd": (_STORE_F16 | _GRAD_ACCUMULATE, {8: 16}, 0),
+    "hscn_resident_bwd_with_virtual": (_STORE_F16 | _GRAD_ACCUMULATE, {8: 16, -3: _HERE}, 0),
+    "hscn_resident_train_step": (_STORE_F16 | _GRAD_ACCUMULATE, {}, 0),
+    # one graph of widths F = H = K = 0: HSCN_E_UNSUPPORTED
+    "hscn_scn_resident_fwd": (_STORE_F16, {6: 1}, -3),
+    "hscn_scn_resident_bwd": (_STORE_F16, {6: 1}, -3),
+    "hscn_scn_resident_train_step": (_STORE_F16, {6: 1}, -3),
+    "hscn_scn_resident_train_epoch": (_STORE_F16, {4: 1}, -3),
+    # B = 0 with the target, partials and grads it asks for first
+    "hscn_mpnn_train_step": (_GRAD_ACCUMULATE, {15: _HERE, 20: _HERE, 21: _HERE}, 0),
+}
+
+
+def _blank_call(lib, name, flags, at):
+    from graph_hscn import _hip
+    types = _hip._SIGNATURES[name][1]
+    assert types[-2] is ctypes.c_int and types[-1] is ctypes.c_void_p      # ..., int flags, void* stream
+    args = [None if t is ctypes.c_void_p else 0 for t in types]
+    for pos, v in at.items():
+        args[pos] = v
+    args[-2] = flags
+    return getattr(lib, name)(*args)
+
+
+def test_header_defines_the_flag_bits_the_binding_uses():
+    from graph_hscn import _hip
+    src = open(os.path.join(ROOT, "include", "hscn.h")).read()
+    assert int(re.search(r"#define HSCN_STORE_F16 (\d+)", src).group(1)) == _hip.STORE_F16 == _STORE_F16
+    assert int(re.search(r"#define HSCN_GRAD_ACCUMULATE (\d+)", src).group(1)) == _hip.GRAD_ACCUMULATE == _GRAD_ACCUMULATE
+    assert int(re.search(r"#define HSCN_ABI_VERSION (\d+)", src).group(1)) == _hip.ABI_VERSION == 23
+    # every entry point whose prototype has `int flags` is in the table above, and no other
+    body = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    flagged = re.findall(r"\b(hscn_[a-z0-9_]+)\s*\([^;{}]*\bint flags\s*,\s*void\* stream\)", body)
+    assert sorted(flagged) == sorted(_FLAGGED)
+
+
+def test_flags_without_a_variant_are_refused_before_any_launch():
+    from graph_hscn import _hip
+    lib = _hip.lib()
+    for name, (valid, at, rc) in _FLAGGED.items():
+        assert rc != -1
+        for ok in (0, _STORE_F16, _GRAD_ACCUMULATE, _STORE_F16 | _GRAD_ACCUMULATE):
+            if ok & ~valid == 0:
+                assert _blank_call(lib, name, ok, at) == rc, (name, ok)
+        # an undefined bit, alone or beside a valid one, and a defined bit this entry point has no variant for
+        for bad in (4, 1 << 30, -1, valid | 4) + tuple(b for b in (_STORE_F16, _GRAD_ACCUMULATE) if not valid & b):
+            assert _blank_call(lib, name, bad, at) == -1, (name, bad)                  # HSCN_E_BADARG
+
+
+def test_half_storage_is_unsupported_at_h64():
+    from graph_hscn import _hip
+    lib = _hip.lib()
+    # float storage takes H = 64 (B = 0: nothing to do), half storage does not (H in {16, 32})
+    for name, h_at in (("hscn_resident_fwd", 17), ("hscn_resident_bwd", 8), ("hscn_resident_fwd_with_virtual", 8),
+                       ("hscn_resident_bwd_with_virtual", 8)):
+        at = dict(_FLAGGED[name][1])
+        for H, rc16 in ((16, 0), (32, 0), (64, -3)):                                   # HSCN_E_UNSUPPORTED
+            at[h_at] = H
+            assert _blank_call(lib, name, 0, at) == 0, (name, H)
+            assert _blank_call(lib, name, _STORE_F16, at) == rc16, (name, H)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from graph_hscn import _hip
     monkeypatch.setattr(_hip, "_lib", None)

@@ -1,6 +1,6 @@
 """BASELINE.json configs[4]: Graph-HSCN on PCQM-Contact with half-precision feature storage ("fp16 feat +
 bf16 accum"): node features and inter-layer activations are IEEE half in HBM, every sum accumulates in float
-(csrc/resident_f16.hip, csrc/resident_scn.hip: hscn_*_f16).
+(csrc/resident_f16.hip, csrc/resident_scn.hip: the resident entry points under HSCN_STORE_F16).
 
 The reference has no reduced-precision mode, so the tolerance is derived, not inherited
 (DESIGN.md section 2b):
@@ -200,7 +200,7 @@ def test_half_storage_full_size_properties():
 
 
 def test_half_storage_stage_a_matches_emulating_oracle():
-    """Stage A on half features (hscn_scn_resident_*_f16): assignments, both losses, gradients against the float32
+    """Stage A on half features (HSCN_STORE_F16): assignments, both losses, gradients against the float32
     oracle with x and the hidden activation rounded to half; cluster ids equal wherever the oracle's top-2 margin
     exceeds one half ulp of the assignment scale."""
     from graph_hscn.data import Batch

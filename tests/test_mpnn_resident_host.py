@@ -49,6 +49,6 @@ def test_bad_arguments_are_refused_before_any_launch():
     lib = _lib()
     # a NULL pointer table / NULL targets: HSCN_E_BADARG, no launch
     assert lib.hscn_mpnn_train_step(None, None, 0, None, None, 0, 1, 9, 16, 3, 10, 1, None, 10, 10, None, 0, 0.1,
-                                    None, None, None, None, None, 0.0, 0, None, None) == -1
+                                    None, None, None, None, None, 0.0, 0, None, 0, None) == -1
     assert lib.hscn_mpnn_forward(None, None, 0, None, None, 0, 1, 9, 16, 3, 10, 1, None, 10, 10, None, 0, 0.1,
                                  None, None, None, None, None, None) == -1
