@@ -136,6 +136,10 @@ _SIGNATURES = {
     "hscn_signnet_supported": (c_int, [c_int] * 12),
     "hscn_signnet_encode": (c_int, [P, P, P, c_int64, P, P, c_int64, c_int64] + [c_int] * 9 + [P, c_int, c_int, P, P,
                                     P, P]),
+    # epoch metrics on the device (csrc/metrics.hip; additive to ABI 23)
+    "hscn_average_precision_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "hscn_average_precision": (c_int, [P, P, c_int64, c_int, P, P, P, P, P, c_size_t, P]),
+    "hscn_mean_absolute_error": (c_int, [P, P, c_int64, c_int, P, P, P]),
 }
 
 class HipExtensionMissing(RuntimeError):

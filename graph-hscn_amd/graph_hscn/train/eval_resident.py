@@ -1,0 +1,129 @@
+"""Evaluation of a split that lives in HBM (extension; the reference's evaluation is train/train.py:109-144,
+mirrored as ``train.eval_epoch``).
+
+``eval_epoch`` walks a host loader: every batch is collated in Python and copied to the device, every time, although
+the validation and test splits never change and are never shuffled, and the epoch metric then loops over the classes
+on the host.  ``DeviceEvaluator`` puts the split into a device dataset once; an evaluation is, per batch, one gather
+launch on a precomputed id slice, the model's forward-only resident launch and ``hscn_criterion_fwd``, then the mean
+of the per-batch losses and ONE metric launch (``metrics.average_precision_launch`` /
+``mean_absolute_error_launch``).  ``run()`` reads nothing back; ``evaluate()`` reads 32 bytes once.
+
+Same numbers as ``eval_epoch`` over an in-order loader of the same graphs and batch size: the batches are the same
+(the gather is bit for bit the host collation), the launches are the same, the loss is the same unweighted float32
+mean over the batches, the last, shorter one included (the reference's loader keeps it, loader/hetero_data.py:96-104).
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from ..data import Batch, HeteroBatch
+from ..loader.device_dataset import DeviceGraphDataset, DeviceHeteroDataset
+from ..loss import criterion
+from ..metrics import (MetricResult, average_precision_launch, mean_absolute_error_launch, metric_buffers,
+                       metric_value, read_packed)
+
+_GATHER_FAULT = 8      # loader.device_dataset: a graph id outside the dataset / a batch beyond the static capacity
+
+
+class EvalRun(NamedTuple):
+    """Device tensors of one evaluation: ``loss`` 0-dim float32 (mean of ``loss_log``), ``loss_log`` [num_batches],
+    ``scores`` / ``targets`` [G, C] in dataset order, ``metric`` the metric launch's ``MetricResult`` (or ``None``)."""
+    loss: torch.Tensor
+    loss_log: torch.Tensor
+    scores: torch.Tensor
+    targets: torch.Tensor
+    metric: Optional[MetricResult]
+
+
+class DeviceEvaluator:
+    """``graphs``: the split (``HeteroData`` for HSCN, ``Data`` for the MPNN baseline -- chosen as ``fit_resident``
+    chooses); ``metric``: "ap", "mae" or ``None`` (no metric launch, ``evaluate`` answers NaN for it)."""
+
+    def __init__(self, graphs: Sequence, model, loss_fn: str, batch_size: int, metric: Optional[str] = None):
+        if metric not in ("ap", "mae", None):
+            raise ValueError(f"metric must be 'ap', 'mae' or None, got {metric!r}")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("DeviceEvaluator runs on the MI355X HIP path: move the model to 'cuda'")
+        G = len(graphs)
+        if G < 1:
+            raise ValueError("empty split")
+        from ..model.mpnn import MPNN
+        self.mpnn = isinstance(model, MPNN)
+        self.model, self.loss_fn, self.metric = model, loss_fn, metric
+        self.num_graphs, self.batch_size = G, int(batch_size)
+        B = self.batch_size
+        self.steps, self.tail = G // B, G % B      # (a split smaller than one batch is its own tail)
+        self.num_batches = self.steps + (1 if self.tail else 0)
+        self.ds = None
+        if self.steps:
+            self.ds = (DeviceGraphDataset if self.mpnn else DeviceHeteroDataset)(graphs, dev, B)
+            ids = torch.arange(self.steps * B, dtype=torch.int64, device=dev)
+            self.ids = [ids[i * B:(i + 1) * B] for i in range(self.steps)]
+        self.tail_batch = None
+        if self.tail:                             # collated once, kept on the device
+            rest = list(graphs[self.steps * B:])
+            if self.mpnn:
+                self.tail_batch = Batch.from_data_list(rest).to(dev)
+                self.tail_batch.x = self.tail_batch.x.float()
+            else:
+                self.tail_batch = HeteroBatch.from_data_list(rest).to(dev)
+        y0 = self._y(self.tail_batch if self.tail else self.ds.static.batch)
+        C = self.C = int(y0.size(1))
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.scores = torch.zeros(G, C, **f32)
+        self.targets = torch.zeros(G, C, **f32)
+        self.loss_log = torch.zeros(self.num_batches, **f32)
+        # result [2] f64 | metric flags i32 | mean loss f32 | gather flag i32 | spare: what evaluate() reads, once
+        self.packed = torch.zeros(32, dtype=torch.uint8, device=dev)
+        self._loss = self.packed[20:24].view(torch.float32)
+        self._gather_flag = self.packed[24:28].view(torch.int32)
+        self.out = metric_buffers(metric, G, C, dev, self.packed) if metric else None
+
+    def _y(self, batch):
+        return batch.y if self.mpnn else batch["local"].y
+
+    def _batch(self, batch, lo: int, hi: int, i: int) -> None:
+        pred = self.model(batch) if self.mpnn else self.model(batch.x_dict, batch.edge_index_dict, batch)
+        true = self._y(batch)
+        loss, score = criterion(self.loss_fn, pred, true)
+        self.loss_log[i].copy_(loss)
+        self.scores[lo:hi].copy_(score)
+        self.targets[lo:hi].copy_(true)
+
+    @torch.no_grad()
+    def run(self) -> EvalRun:
+        """One evaluation of the split, enqueued on the current stream; no read-back."""
+        model, B = self.model, self.batch_size
+        was_training, engine = model.training, model.engine
+        model.eval()
+        model.engine = "resident"
+        try:
+            for i in range(self.steps):
+                self._batch(self.ds.gather(self.ids[i]), i * B, (i + 1) * B, i)
+            if self.tail:
+                self._batch(self.tail_batch, self.steps * B, self.num_graphs, self.steps)
+        finally:
+            model.engine = engine
+            model.train(was_training)
+        self._loss.copy_(self.loss_log.mean())          # float32, unweighted over the batches: eval_epoch's definition
+        if self.ds is not None:
+            self._gather_flag.copy_(self.ds.flag)
+        if self.metric == "ap":
+            average_precision_launch(self.targets, self.scores, out=self.out)
+        elif self.metric == "mae":
+            mean_absolute_error_launch(self.targets, self.scores, out=self.out)
+        return EvalRun(self._loss.view(()), self.loss_log, self.scores, self.targets, self.out)
+
+    def evaluate(self) -> Tuple[float, float]:
+        """``(mean loss, metric)`` as ``train.eval_epoch`` returns them: ``run()``, then ONE synchronising copy that
+        brings the loss, the metric, its flags and the dataset's gather flag (what ``ds.check()`` tests) together."""
+        self.run()
+        f64, i32 = read_packed(self.packed)
+        if int(i32[2]) & _GATHER_FAULT:
+            raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")
+        loss = float(i32[1:2].view(torch.float32)[0])
+        perf = metric_value(self.metric, float(f64[0]), int(i32[0])) if self.metric else float("nan")
+        return loss, perf

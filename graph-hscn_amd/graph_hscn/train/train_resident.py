@@ -41,7 +41,9 @@ def optimizer_steps_at(it: int, num_batches: int, batch_accumulation: int) -> bo
 
 def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_loaders: Sequence, model,
                  batch_size: int, metric_fn: Optional[Callable] = None, seed: int = 0, reducer=None,
-                 flat_optimizer: bool = True, epoch_orders: Optional[list] = None) -> List[tuple]:
+                 flat_optimizer: bool = True, epoch_orders: Optional[list] = None, *,
+                 eval_graphs: Optional[Sequence] = None, metric: Optional[str] = None,
+                 eval_history: Optional[list] = None) -> List[tuple]:
     """Returns ``[(mean train loss, train metric), ...]`` per epoch, like ``train.train``.  ``eval_loaders`` =
     ``[validation, test]`` loaders of host batches (evaluated with ``train.eval_epoch``).
 
@@ -58,7 +60,21 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
 
     ``model`` may also be the MPNN baseline (``model.mpnn.MPNN``) with ``train_graphs`` a list of ``Data``: the
     dataset is then a ``DeviceGraphDataset`` and the captured step ``step.MPNNResidentTrainStep`` (one launch + the
-    gradient fold); evaluation through ``train.eval_epoch`` takes the MPNN's forward-only launch."""
+    gradient fold); evaluation through ``train.eval_epoch`` takes the MPNN's forward-only launch.
+
+    Evaluation on the device (keyword-only; the defaults leave the loop as it was): ``eval_graphs`` =
+    ``(validation graphs, test graphs)`` puts the two splits into ``eval_resident.DeviceEvaluator``s built once before
+    the first epoch -- no host loader, collation or copy per evaluation -- and ``eval_loaders`` may then be ``None``.
+    ``metric`` = "ap" / "mae" computes the epoch metric, of the training split and of the evaluators, with the HIP
+    launches of ``metrics`` (one read-back brings the loss and the metric together) in place of a ``metric_fn``;
+    passing both is a ``ValueError``.  ``eval_history``: a list that receives ``(epoch, split, loss, perf)`` of every
+    evaluation."""
+    if metric is not None and metric_fn is not None:        # (argument checks come before anything touches a device)
+        raise ValueError("pass metric= (the HIP metric launch) or metric_fn=, not both")
+    if metric not in (None, "ap", "mae"):
+        raise ValueError(f"metric must be 'ap', 'mae' or None, got {metric!r}")
+    if eval_graphs is not None and len(eval_graphs) != 2:
+        raise ValueError("eval_graphs is the pair (validation graphs, test graphs)")
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("fit_resident runs on the MI355X HIP path: move the model to 'cuda'")
@@ -123,8 +139,20 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
     legacy = not acc and not clip              # (the iteration exactly as before either setting existed)
     C = ds.C
     loss_log = torch.zeros(steps + (1 if tail else 0), dtype=torch.float32, device=dev)
-    scores = torch.zeros(G, C, dtype=torch.float32, device=dev) if metric_fn else None
-    targets = torch.zeros(G, C, dtype=torch.float32, device=dev) if metric_fn else None
+    want_metric = metric_fn is not None or metric is not None
+    scores = torch.zeros(G, C, dtype=torch.float32, device=dev) if want_metric else None
+    targets = torch.zeros(G, C, dtype=torch.float32, device=dev) if want_metric else None
+    eval_metric_fn = metric_fn
+    if metric is not None:
+        from .. import metrics as _metrics
+        train_metric = _metrics.metric_buffers(metric, G, C, dev)
+        train_loss = train_metric.packed[20:24].view(torch.float32)     # beside result and flags: one read-back
+        launch = _metrics.average_precision_launch if metric == "ap" else _metrics.mean_absolute_error_launch
+        eval_metric_fn = _metrics.eval_ap_hip if metric == "ap" else _metrics.eval_mae_hip    # (host loaders)
+    evaluators = None
+    if eval_graphs is not None:
+        from .eval_resident import DeviceEvaluator
+        evaluators = [DeviceEvaluator(g, model, training_cfg.loss_fn, B, metric) for g in eval_graphs]
     history, best, stale = [], float("inf"), 0
     for epoch in range(training_cfg.epochs):
         start = time.time()
@@ -147,7 +175,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
                 if stepping and not in_graph:
                     boundary_outside_graph(float(B))
             loss_log[i].copy_(step.loss)
-            if metric_fn:
+            if want_metric:
                 scores[i * B:(i + 1) * B].copy_(step.score)
                 targets[i * B:(i + 1) * B].copy_(ds.static.batch.y if mpnn else ds.static.batch["local"].y)
         if tail:
@@ -184,18 +212,35 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
                 step.bind_grads()
                 boundary_outside_graph(float(tail))
             loss_log[steps].copy_(loss.detach())
-            if metric_fn:
+            if want_metric:
                 scores[steps * B:].copy_(score.detach())
                 targets[steps * B:].copy_(tail_y)
             del pred, loss, score, hb
-        mean_loss = float(loss_log.mean().item())                     # the epoch's only read-back
-        perf = metric_fn(targets, scores) if metric_fn else float("nan")
+        if metric is not None:
+            launch(targets, scores, out=train_metric)
+            train_loss.copy_(loss_log.mean())
+            f64, i32 = _metrics.read_packed(train_metric.packed)      # the epoch's only read-back
+            mean_loss = float(i32[1:2].view(torch.float32)[0])
+            perf = _metrics.metric_value(metric, float(f64[0]), int(i32[0]))
+        else:
+            mean_loss = float(loss_log.mean().item())                 # the epoch's only read-back
+            perf = metric_fn(targets, scores) if metric_fn else float("nan")
         history.append((mean_loss, perf))
         if logger is not None:
             logger.info(f"epoch {epoch} train loss {mean_loss:.5f} perf {perf:.5f} ({time.time() - start:.2f}s)")
         if is_eval_epoch(epoch, training_cfg.epochs, training_cfg.eval_period):
-            for split, loader in zip(["Validation", "Test"], eval_loaders):
-                vloss, _ = eval_epoch(epoch, logger, loader, model, training_cfg.loss_fn, metric_fn, split)
+            sources = evaluators if evaluators is not None else eval_loaders or []
+            for split, source in zip(["Validation", "Test"], sources):
+                if evaluators is not None:
+                    vloss, vperf = source.evaluate()
+                    if metric_fn is not None:
+                        vperf = metric_fn(source.targets, source.scores)
+                    if logger is not None:
+                        logger.info(f"epoch {epoch} {split} loss {vloss:.5f} perf {vperf:.5f}")
+                else:
+                    vloss, vperf = eval_epoch(epoch, logger, source, model, training_cfg.loss_fn, eval_metric_fn, split)
+                if eval_history is not None:
+                    eval_history.append((epoch, split, vloss, vperf))
                 if split == "Validation":
                     if reducer is not None and reducer.world_size > 1:
                         # every rank must take the same stop decision (the next collective would hang otherwise):

@@ -931,6 +931,38 @@ int hscn_signnet_encode(const float* x, const float* eigvecs, const int64_t* edg
                         const void* const* params_host, int max_n, int max_e, float* out, float* pe /*or NULL*/,
                         int32_t* flag, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Epoch metrics of the training / evaluation loop (reference graph_hscn/metrics.py:6-36, called on the whole
+ * epoch's [G, C] labels and scores at train/train.py:109-144) where the tensors live (csrc/metrics.hip).  Purely
+ * additive to ABI 23.
+ *
+ * hscn_average_precision: metrics.py:6-27 eval_ap = the mean over the valid classes of sklearn's
+ *   average_precision_score.  y_true, y_score [G, C] f32 row-major.  Per class c: rows whose label is NaN are
+ *   ignored; the class is VALID iff the remaining labels hold at least one 1 and at least one 0 (a label counts as
+ *   positive iff it equals 1).  A valid class's rows are ordered by score, descending; scores that compare equal
+ *   form one threshold run (-0.0 ties +0.0); AP = the float64 sum over runs of (recall_run - recall_prev) *
+ *   precision_run with precision = tp / n and recall = tp / P at the last row of the run.
+ *     ap [C] f64 (0 where the class is not valid), valid [C] i32,
+ *     result [2] f64 = { mean of ap over the valid classes, summed in class order; number of valid classes },
+ *     flags [1] i32: bit 0 = no valid class (result[0] is then 0), bit 1 = a NaN score in a labelled row of a valid
+ *     class (an invalid class takes no part in the metric, its scores are not examined).
+ *   One workgroup per class: 64-bit keys (inverted order-preserving image of the score << 1 | label bit), a
+ *   bitonic sort and a scan of the label bits in LDS for G <= 16384 (8 B per row, 128 KB of the CU's 160 KB), in
+ *   `workspace` (global memory, slower) beyond; then a one-wave launch folds the classes.  No atomics: the same
+ *   input gives the same bits.  hscn_average_precision_workspace_bytes(G, C): 256 bytes for G <= 16384.
+ *   HSCN_E_BADARG for null pointers, G < 1, C < 1 or G > 2^30; HSCN_E_WORKSPACE for a workspace too small; both
+ *   before any launch.
+ *
+ * hscn_mean_absolute_error: metrics.py:30-36 eval_mae = the float64 mean of |y_true - y_pred| over [G, C] (one
+ *   workgroup, per-thread strided sums folded by a fixed tree).  result [2] f64 = { mean, G * C },
+ *   flags [1] i32: bit 1 = a NaN prediction.
+ * ------------------------------------------------------------------------- */
+size_t hscn_average_precision_workspace_bytes(int64_t G, int C);
+int hscn_average_precision(const float* y_true, const float* y_score, int64_t G, int C, double* ap, int32_t* valid,
+                           double* result, int32_t* flags, void* workspace, size_t workspace_bytes, void* stream);
+int hscn_mean_absolute_error(const float* y_true, const float* y_pred, int64_t G, int C, double* result,
+                             int32_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
