@@ -140,6 +140,12 @@ _SIGNATURES = {
     "hscn_average_precision_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "hscn_average_precision": (c_int, [P, P, c_int64, c_int, P, P, P, P, P, c_size_t, P]),
     "hscn_mean_absolute_error": (c_int, [P, P, c_int64, c_int, P, P, P]),
+    # Laplacian PE statistics of a batch as one launch (csrc/lap_eig.hip; additive to ABI 23)
+    "hscn_lap_eig_supported": (c_int, [c_int, c_int]),
+    "hscn_lap_eig_lds_max_n": (c_int, []),
+    "hscn_lap_eig_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "hscn_lap_eig_stats": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, P, P, P,
+                                   c_size_t, P]),
 }
 
 class HipExtensionMissing(RuntimeError):

@@ -29,7 +29,8 @@ def get_each_data_from_batch(data_list: list) -> list:  # train/utils.py:9-14
     return out
 
 
-def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, device=None):  # train/train.py:29-51
+def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, device=None, *, stats=None,
+                   is_undirected: bool = True):  # train/train.py:29-51
     """The positional-encoding stage in front of stage A: ONE ``SignNetNodeEncoder(pe_cfg, num_features,
     pe_cfg.dim_emb)`` with its random initial weights (the reference never trains it) runs under ``no_grad`` over
     every batch of every loader and replaces ``x`` by ``[linear_x(x) | pe]`` of width ``pe_cfg.dim_emb``.  Returns
@@ -39,7 +40,15 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
 
     The encoder lives on ``device`` (default: "cuda" when available) and every batch is moved there; its engine is
     "auto", so a qualifying batch takes the one-launch kernel (include/hscn.h: hscn_signnet_encode).  The encoder is
-    kept as ``compute_posenc.last_encoder`` for inspection."""
+    kept as ``compute_posenc.last_encoder`` for inspection.
+
+    ``stats="device"``: a batch that arrives without ``eigvecs_sn`` gets its Laplacian statistics from
+    ``transform.compute_posenc_stats_device`` (``pe_cfg``'s Laplacian and normaliser settings, ``is_undirected`` as the
+    reference's loader passes it) on the encoder's device right before the encoder runs -- the PE stage of a batch is
+    then two launches with no host pre-processing.  ``stats=None`` (default): the graphs carry pre-computed
+    statistics, as in the reference."""
+    if stats not in (None, "device"):
+        raise ValueError(f"stats must be None or 'device', got {stats!r}")
     from ..data import DataLoader
     from ..encoder.signnet import SignNetNodeEncoder
     if device is None:
@@ -56,6 +65,9 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
             for batch in loader:
                 batch = batch.to(device)
                 batch.x = batch.x.float()
+                if stats == "device" and getattr(batch, "eigvecs_sn", None) is None:
+                    from ..transform.posenc import compute_posenc_stats_device
+                    compute_posenc_stats_device(batch, is_undirected, pe_cfg)
                 data_list.append(enc(batch))
             loaders_new.append(DataLoader(get_each_data_from_batch(data_list), batch_size=data_cfg.batch_size,
                                           shuffle=(i == 0)))

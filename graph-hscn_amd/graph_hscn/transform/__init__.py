@@ -1,4 +1,5 @@
-from .posenc import compute_posenc_stats, eigvec_normalizer, get_lap_decomp_stats
+from .posenc import (compute_posenc_stats, compute_posenc_stats_batched, compute_posenc_stats_device, eigvec_normalizer,
+                     get_lap_decomp_stats)
 from .pre_transform import pre_transform_in_memory
 
-__all__ = ["compute_posenc_stats", "eigvec_normalizer", "get_lap_decomp_stats", "pre_transform_in_memory"]
+__all__ = ["compute_posenc_stats", "compute_posenc_stats_batched", "compute_posenc_stats_device", "eigvec_normalizer", "get_lap_decomp_stats", "pre_transform_in_memory"]

@@ -963,6 +963,46 @@ int hscn_average_precision(const float* y_true, const float* y_score, int64_t G,
 int hscn_mean_absolute_error(const float* y_true, const float* y_pred, int64_t G, int C, double* result,
                              int32_t* flags, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Laplacian statistics of the SignNet positional encoding (reference transform/posenc.py:14-107:
+ * compute_posenc_stats, get_lap_decomp_stats, eigvec_normalizer) for a collated batch as ONE launch, one workgroup
+ * per graph (csrc/lap_eig.hip).  Purely additive to ABI 23.
+ *
+ * hscn_lap_eig_stats: edge_index int64 [2, E] in batch numbering; graph g owns nodes [nptr[g], nptr[g+1]) and edges
+ *   [eptr[g], eptr[g+1]) (int32, B + 1 entries each); max_n >= the largest graph's node count.
+ *   Laplacian: self loops dropped; is_undirected != 0: every listed edge adds 1 to A[row, col] (duplicates sum),
+ *   is_undirected = 0: A[r, c] = A[c, r] = 1 for every listed pair; degree = row sum; lap_norm HSCN_LAP_NONE: D - A,
+ *   HSCN_LAP_SYM: I - D^-1/2 A D^-1/2, HSCN_LAP_RW: I - D^-1 A (1/0 -> 0), in float32; the matrix decomposed is its
+ *   lower triangle mirrored (what numpy's eigh reads).  Decomposition: two-sided cyclic Jacobi in round-robin order
+ *   until the off-diagonal mass is at most 1e-15 of the squared Frobenius norm, at most 30 sweeps.
+ *   eigvecs [N, max_freqs] f32: per graph the max_freqs smallest eigenpairs in ascending order, each vector divided
+ *   by its HSCN_VECNORM_L1 / _L2 / _ABSMAX norm over the graph's nodes (clamped at 1e-12); eigvals [N, max_freqs]
+ *   f32: the eigenvalues clamped at 0, the same row for every node of the graph; columns from the graph's node count
+ *   on are NaN in both.
+ *   flag [1] i32, zeroed by the caller, only ever OR-ed into: bit 0 = a graph reached the sweep cap, bit 1 = an edge
+ *   with an end outside its graph (dropped), bit 2 = a graph larger than max_n or outside [0, N) (its rows are NaN).
+ *   Graphs of at most hscn_lap_eig_lds_max_n() nodes are decomposed in LDS, larger ones (up to 512) in their slab of
+ *   `workspace`: hscn_lap_eig_workspace_bytes(B, max_n) bytes, 0 when max_n fits LDS.  A workspace with 4 * B more
+ *   bytes than that receives every graph's sweep count (int32) in those last words.
+ *   No float atomics: the same input gives the same bits.
+ *   HSCN_E_BADARG for null pointers, negative sizes, max_freqs < 1, an unknown lap_norm / eigvec_norm or a workspace
+ *   smaller than asked; HSCN_E_UNSUPPORTED where hscn_lap_eig_supported is 0 (max_n > 512 or max_freqs > 64); both
+ *   before any launch.  B = 0 or N = 0 launches nothing.
+ * ------------------------------------------------------------------------- */
+#define HSCN_LAP_NONE 0
+#define HSCN_LAP_SYM 1
+#define HSCN_LAP_RW 2
+#define HSCN_VECNORM_L1 0
+#define HSCN_VECNORM_L2 1
+#define HSCN_VECNORM_ABSMAX 2
+int hscn_lap_eig_supported(int max_n, int max_freqs);
+int hscn_lap_eig_lds_max_n(void);
+size_t hscn_lap_eig_workspace_bytes(int64_t B, int max_n);
+int hscn_lap_eig_stats(const int64_t* edge_index, int64_t E, const int32_t* nptr, const int32_t* eptr, int64_t N,
+                       int64_t B, int max_n, int lap_norm, int is_undirected, int max_freqs, int eigvec_norm,
+                       float* eigvals, float* eigvecs, int32_t* flag, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
