@@ -43,7 +43,6 @@
 #include "hscn_common.h"
 #include "resident_common.h"
 #include <cstdio>
-#include <cstdlib>
 
 namespace {
 
@@ -999,7 +998,6 @@ __device__ __forceinline__ void hscn_fwd_body(const AT& A, const int g) {
       // not depend on who runs it, a cluster is finished by its last arriver in chunk order: same bits as before.
       int* ck_next = ck_arrive + cap_v;
       (void)G_;
-#ifndef HSCN_NO_QUAD_CLUSTERS
       if constexpr (H == 16) {
         // ---- many small clusters (a balanced assignment: K = 16 .. 32 clusters of a few members each) ----
         // One wave per cluster leaves most of the wave idle and takes nv / NW rounds.  Here a 16-lane DPP row owns a
@@ -1106,7 +1104,6 @@ __device__ __forceinline__ void hscn_fwd_body(const AT& A, const int g) {
           return;
         }
       }
-#endif
       for (;;) {
         int ck = 0;
         if (lane == 0) ck = __hip_atomic_fetch_add(ck_next, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2095,11 +2092,7 @@ int launch_fwd(FwdArgs& A, int64_t B, hipStream_t st) {
   }
   if (!ok) return HSCN_E_UNSUPPORTED;
   A.exp_dinv = A.exp;
-  static const int rt_env = getenv("HSCN_RT") ? atoi(getenv("HSCN_RT")) : 0;
-  int rc;
-  if (A.max_n <= 64 || rt_env == 256) rc = launch_fwd_rt<H, 256, TS>(A, B, lds, st);
-  else if (rt_env == 512 && sizeof(TS) == 4) rc = launch_fwd_rt<H, 512, float>(A, B, lds, st);
-  else rc = launch_fwd_rt<H, 1024, TS>(A, B, lds, st);
+  const int rc = A.max_n <= 64 ? launch_fwd_rt<H, 256, TS>(A, B, lds, st) : launch_fwd_rt<H, 1024, TS>(A, B, lds, st);
   if (rc) return rc;
   if (want_exp && !A.exp) {
     const size_t l2 = ((size_t)4 * A.max_ell + 2 * ((size_t)A.max_n + 1) + 16) * 4;
@@ -2124,9 +2117,7 @@ template <int H, typename TS>
 int launch_bwd(BwdArgs& A, int64_t B, hipStream_t st) {
   const size_t lds = pick_bwd_lds(A, H);
   if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  static const int rt_env = getenv("HSCN_RT") ? atoi(getenv("HSCN_RT")) : 0;
-  if (A.max_n <= 64 || rt_env == 256) return launch_bwd_rt<H, 256, TS>(A, B, lds, st);
-  if (rt_env == 512 && sizeof(TS) == 4) return launch_bwd_rt<H, 512, float>(A, B, lds, st);
+  if (A.max_n <= 64) return launch_bwd_rt<H, 256, TS>(A, B, lds, st);
   return launch_bwd_rt<H, 1024, TS>(A, B, lds, st);
 }
 
@@ -2509,13 +2500,8 @@ int impl_resident_train_step(const void* x_local, const int64_t* ei_ll, int64_t 
   hipStream_t st = hscn_stream(stream_);
   int rc = H == 16 ? launch_step<16, TS>(S, job ? &V : nullptr, st) : launch_step<32, TS>(S, job ? &V : nullptr, st);
   if (rc) return rc;
-#ifdef HSCN_DIAG_REDUCE_BLOCKS   // measurement builds only (tools/build_variant.sh): what the launch costs without its work
-  k_param_reduce<<<HSCN_DIAG_REDUCE_BLOCKS, 256, 0, st>>>(partials, grads, (int)B, S.P, S.Pn, S.inv_count,
-                                                          S.ready ? sync : nullptr);
-#else
   launch_param_fold(partials, grads, (int)B, S.P, S.Pn, S.inv_count, S.ready ? sync : nullptr,
                     flags & HSCN_GRAD_ACCUMULATE, st);
-#endif
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

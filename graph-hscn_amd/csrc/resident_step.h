@@ -182,12 +182,6 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   const Grp ALL{(int)threadIdx.x, RT, wave, NW};
   constexpr int WL = H * H + H;   // words per layer in wt
 
-#ifndef HSCN_CSR_ELL
-#define HSCN_CSR_ELL 1
-#endif
-#ifndef HSCN_BIAS0_COUNTS
-#define HSCN_BIAS0_COUNTS 1
-#endif
   // ---- prologue: every global input of the graph is requested before anything is consumed ----------------
   STAMP(0);
   constexpr int EPT = 2, XPT = 8;
@@ -303,11 +297,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     }
     if (bad && A.flag) atomicOr(A.flag, 2);
   }
-#if HSCN_CSR_ELL
   for (int i = threadIdx.x; i <= n; i += RT) { (ib + Y.cntA)[i] = 0; (ib + Y.cntT)[i] = 0; }
-#else
-  for (int i = threadIdx.x; i <= n; i += RT) { (ib + Y.cursorA)[i] = 0; (ib + Y.cursorT)[i] = 0; }
-#endif
   if (threadIdx.x == 0) { (ib + Y.wsum)[0] = 0; (ib + Y.wsum)[1] = 0; (ib + Y.ovf)[0] = 0; }   // fold sign-offs (H = 16 backward), export sign-offs
   {
     float* x0 = buf(0);
@@ -341,12 +331,11 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   // Molecule-like graphs (every row of at most ELL_D edges) take the two-barrier build of both CSRs; a graph with a
   // denser row takes the general one (four barriers after re-zeroing its counters).  Same arrays either way.
   // H = 16: the structure as 16-byte row records (one LDS load per row in every gather, no prefix sums in the build);
-  // HSCN_CSR_ELL=2 keeps the two-barrier CSR build (A/B), H = 32 always takes it (its two-phase backward walks CSRs)
+  // H = 32 always takes the two-barrier CSR build (its two-phase backward walks CSRs)
   bool e16 = false;
-#if HSCN_CSR_ELL
   if (!pre) {
     bool low;
-    if (H == 16 && HSCN_CSR_ELL == 1) {
+    if (H == 16) {
       low = build_ell16_pair(ib + Y.ek, ib + Y.eo, ne, n, reinterpret_cast<uint4*>(ib + Y.rowptr),
                              reinterpret_cast<uint4*>(ib + Y.recT), dinv, ib + Y.cntA, ib + Y.ellA, ib + Y.cntT,
                              ib + Y.ellT, ib + Y.ovf, RT);
@@ -372,24 +361,6 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       }
     }
   }
-#else
-  if (!pre) {
-    const int NA = NW / 2 > 0 ? NW / 2 : 1;
-    const bool inB = wave >= NA && NW > 1;
-    if (NW == 1) {
-      build_csr_lds(ib + Y.ek, ib + Y.eo, ne, n, rowptr, col, ib + Y.cursorA, ib + Y.tmpA, ALL, false);
-      build_csr_lds(ib + Y.eo, ib + Y.ek, ne, n, rowptr_t, col_t, ib + Y.cursorT, ib + Y.tmpT, ALL, false);
-      dinv_from_rowptr(rowptr, n, dinv, ALL);
-    } else if (!inB) {
-      const Grp GA{(int)threadIdx.x, NA * 64, wave, NA};
-      build_csr_lds(ib + Y.ek, ib + Y.eo, ne, n, rowptr, col, ib + Y.cursorA, ib + Y.tmpA, GA, false);
-      dinv_from_rowptr(rowptr, n, dinv, GA);
-    } else {
-      const Grp GB{(int)threadIdx.x - NA * 64, (NW - NA) * 64, wave - NA, NW - NA};
-      build_csr_lds(ib + Y.eo, ib + Y.ek, ne, n, rowptr_t, col_t, ib + Y.cursorT, ib + Y.tmpT, GB, false);
-    }
-  }
-#endif
   lds_barrier();
   STAMP(3);
   // ---- forward layers: A[l] -> A[l + 1], one barrier each ----------------------------------------------------
@@ -472,10 +443,6 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   STAMP(12);
   // ---- head + this graph's row of the loss tail (wave 0) ---------------------------------------------------
   float* aL = buf(L);
-#ifdef HSCN_EARLY_RAISE   // (A/B: the last hand-off signing off beside the head -- its wait for the write-through stores held the
-                          // head's barrier: 28.38 vs 28.12 us per step, uniform ids 28.40 vs 27.98)
-  if (hand && wave >= NC && NW > 1) raise(L - 1);
-#endif
   float* pol = vec;          // pooled
   float* zz = vec + 64;      // z = act(lin_1(pooled))
   float* gz = vec + 128;     // dL/d(lin_1 output, pre-activation)
@@ -599,11 +566,10 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   }
   lds_barrier();
   STAMP(13);
-#ifndef HSCN_EARLY_RAISE
   // the last hand-off signs off HERE, behind the head's barrier: the export waves own one row tile of the first backward
-  // layer where the first waves own two, so their wait for the write-through stores of a_{L-1} rides on slack
+  // layer where the first waves own two, so their wait for the write-through stores of a_{L-1} rides on slack (signing
+  // off beside the head held the head's barrier: 28.38 vs 28.12 us per step, uniform ids 28.40 vs 27.98)
   if (hand && wave >= NC && NW > 1) raise(L - 1);
-#endif
 
   // ================================ backward ======================================================
   // partial layout: per layer {W_ll [H*fin], b_ll [H]}, then W1 [H*H], b1 [H], W2 [C*H], b2 [C], loss column
@@ -670,7 +636,6 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     // The gradient of the last layer's output is never materialised: G_L[j][k] = a_L[j][k] > 0 ? gpool[k] / n : 0 is
     // applied where the first backward layer reads it (the same values as the masking pass of the launch pair).
     const float4 gq4 = *reinterpret_cast<const float4*>(gpn + 4 * lj);            // this lane's feature quarter (tile gather)
-    const float4 gb4 = *reinterpret_cast<const float4*>(gpn + 4 * (lane & 3));    // (bias sums)
     auto gl4 = [](const float4 a, const float4 q) {
       return make_float4(a.x > 0.f ? q.x : 0.f, a.y > 0.f ? q.y : 0.f, a.z > 0.f ? q.z : 0.f, a.w > 0.f ? q.w : 0.f);
     };
@@ -679,7 +644,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       off -= H * fin + H;
       const int oW = off, ob = off + H * fin;
       // bias-gradient partials of the layer of iteration j live in slot j % 3: iteration `it` folds slot it - 1, fills slot
-      // `it` (it = 0 only: the pass below) and -- in its tiles' epilogue -- slot it + 1 for the next layer
+      // `it` (it = 0 only: the counts below) and -- in its tiles' epilogue -- slot it + 1 for the next layer
       float* bredw = bred + (it % 3) * NW * H;
       float* bredn = bred + ((it + 1) % 3) * NW * H;
       float bsum = 0.f;       // this lane's share of the NEXT layer's bias gradient: column li of the rows it writes
@@ -710,28 +675,10 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
           if (lane == 0) __hip_atomic_fetch_add(fold_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       }
-      if (it == 0 && HSCN_BIAS0_COUNTS) {
+      if (it == 0) {
         // first backward layer: G[row][col] = a_L[row][col] > 0 ? gpn[col] : 0, so its column sum is gpn[col] times the
         // number of positive entries of the column -- which the forward's last layer counted in its epilogue (slot 1)
         if (lane < H) bredw[wave * H + lane] = (partp + NW * H)[wave * H + lane] * gpn[lane];
-      } else if (it == 0) {   // (-DHSCN_BIAS0_COUNTS=0: the row walk) bias gradient = column sums of G; later
-                       // layers' sums were left by the previous layer's tile epilogues, see `bsum`
-        const int slot = lane >> 2, f = (lane & 3) * 4;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = wave * 16 + slot; i < n; i += NW * 16) {
-          float4 v = *reinterpret_cast<const float4*>(Gc + i * H + f);
-          if (it == 0) v = gl4(v, gb4);
-          acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-        acc.x += __shfl_xor(acc.x, 32, 64); acc.y += __shfl_xor(acc.y, 32, 64);
-        acc.z += __shfl_xor(acc.z, 32, 64); acc.w += __shfl_xor(acc.w, 32, 64);
-        acc.x += __shfl_xor(acc.x, 16, 64); acc.y += __shfl_xor(acc.y, 16, 64);
-        acc.z += __shfl_xor(acc.z, 16, 64); acc.w += __shfl_xor(acc.w, 16, 64);
-        acc.x = row_ror_add<8>(acc.x); acc.y = row_ror_add<8>(acc.y);
-        acc.z = row_ror_add<8>(acc.z); acc.w = row_ror_add<8>(acc.w);
-        acc.x = row_ror_add<4>(acc.x); acc.y = row_ror_add<4>(acc.y);
-        acc.z = row_ror_add<4>(acc.z); acc.w = row_ror_add<4>(acc.w);
-        if (slot == 0) *reinterpret_cast<float4*>(bredw + wave * H + f) = acc;
       }
       float* Xl = buf(l);                           // the layer input a_l (l >= 1); becomes G_l tile by tile
       const float* Wl = wt + l * WL;
@@ -809,16 +756,10 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                   if (p + u < c) {
-#ifndef HSCN_BWD_SEPARATE   // fused multiply-add, as the forward's gather (26.82 -> 26.54 us per step); -DHSCN_BWD_SEPARATE:
-                            // product and sum rounded separately, the launch pair's values
+                    // fused multiply-add, as the forward's gather (26.82 -> 26.54 us per step against the launch
+                    // pair's separately rounded product and sum)
                     z.x = fmaf(ww[u], vv[u].x, z.x); z.y = fmaf(ww[u], vv[u].y, z.y);
                     z.z = fmaf(ww[u], vv[u].z, z.z); z.w = fmaf(ww[u], vv[u].w, z.w);
-#else
-                    z.x = add_rn(z.x, mul_rn(ww[u], vv[u].x));
-                    z.y = add_rn(z.y, mul_rn(ww[u], vv[u].y));
-                    z.z = add_rn(z.z, mul_rn(ww[u], vv[u].z));
-                    z.w = add_rn(z.w, mul_rn(ww[u], vv[u].w));
-#endif
                   }
                 }
               }
@@ -842,15 +783,8 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               if (p + u < t0) {
-#ifndef HSCN_BWD_SEPARATE
                 z.x = fmaf(ww[u], vv[u].x, z.x); z.y = fmaf(ww[u], vv[u].y, z.y);
                 z.z = fmaf(ww[u], vv[u].z, z.z); z.w = fmaf(ww[u], vv[u].w, z.w);
-#else
-                z.x = add_rn(z.x, mul_rn(ww[u], vv[u].x));
-                z.y = add_rn(z.y, mul_rn(ww[u], vv[u].y));
-                z.z = add_rn(z.z, mul_rn(ww[u], vv[u].z));
-                z.w = add_rn(z.w, mul_rn(ww[u], vv[u].w));
-#endif
               }
             }
           }
@@ -1038,9 +972,8 @@ int launch_step(StepArgs& S, FwdArgs* V, hipStream_t st) {
     if (lv > 160 * 1024) return HSCN_E_UNSUPPORTED;
     // 16-wave workgroups on graphs within StepVCaps: the virtual program with its LDS layout fixed at compile time
     // (hscn_fwd_body MODE 6: the layout's ~40 offsets are immediates instead of scalar registers -- 90 SGPR spills
-    // become 9); HSCN_STEP_FIXED_LAYOUT=0 keeps the run-time layout (A/B, and what larger graphs / more clusters take)
-    static const bool allow_fixed = !(getenv("HSCN_STEP_FIXED_LAYOUT") && atoi(getenv("HSCN_STEP_FIXED_LAYOUT")) == 0);
-    if (allow_fixed && S.max_n > 64 && V->max_n <= StepVCaps::N && V->max_v <= StepVCaps::V && V->max_evv <= StepVCaps::EVV &&
+    // become 9); larger graphs / more clusters keep the run-time layout
+    if (S.max_n > 64 && V->max_n <= StepVCaps::N && V->max_v <= StepVCaps::V && V->max_evv <= StepVCaps::EVV &&
         V->l_begin == 0 && V->l_end == V->L) {
       const size_t lf = fwd_layout(H, 1, StepVCaps::N, StepVCaps::V, 0, StepVCaps::EVV, 1, 0).total * 4;
       if (lf <= 160 * 1024) { fixed_layout = true; lv = lf; V->db = 1; }

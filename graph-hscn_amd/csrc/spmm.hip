@@ -52,20 +52,15 @@ __global__ void __launch_bounds__(SP_THREADS)
 k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ eid,
        const float* __restrict__ dinv_r, const float* __restrict__ dinv_c, const float* __restrict__ wts,
        const float* __restrict__ h, const float* __restrict__ bias, float* __restrict__ out,
-       int64_t num_rows, int width, int LPR, int RPB, int accumulate, int act, int64_t rows_per_block,
-       int xcd_map) {
+       int64_t num_rows, int width, int LPR, int RPB, int accumulate, int act, int64_t rows_per_block) {
   using V = Vec<VEC>;
   const int rl = threadIdx.x / LPR;
   const int f = (threadIdx.x - rl * LPR) * VEC * NV;
   if (rl >= RPB) return;
-  // rows_per_block > 0: every block owns one contiguous row range; with xcd_map the ranges of the
-  // blocks that share an XCD (blockIdx % 8, round-robin dispatch) are adjacent, so a gathered
-  // neighbour row is usually in that XCD's L2.  rows_per_block == 0: grid-stride over rows.
+  // rows_per_block > 0: every block owns one contiguous row range.  rows_per_block == 0: grid-stride over rows.
   int64_t r_begin, r_end, r_step;
   if (rows_per_block > 0) {
-    const int64_t nb = gridDim.x;
-    const int64_t vb = (xcd_map && nb % 8 == 0) ? ((int64_t)(blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8)
-                                                 : (int64_t)blockIdx.x;
+    const int64_t vb = blockIdx.x;
     r_begin = vb * rows_per_block + rl;
     r_end = vb * rows_per_block + rows_per_block;
     if (r_end > num_rows) r_end = num_rows;
@@ -115,7 +110,7 @@ __global__ void __launch_bounds__(SP_THREADS)
 k_spmm_pipe(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ eid,
             const float* __restrict__ dinv_r, const float* __restrict__ dinv_c, const float* __restrict__ wts,
             const float* __restrict__ h, const float* __restrict__ bias, float* __restrict__ out,
-            int64_t num_rows, int width, int LPR, int RPB, int accumulate, int act, int nt_store) {
+            int64_t num_rows, int width, int LPR, int RPB, int accumulate, int act) {
   using V = Vec<4>;
   constexpr int D = 4;
   const int rl = threadIdx.x / LPR;
@@ -183,13 +178,7 @@ k_spmm_pipe(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
       float4 a = acc[q];
       if (bias) a = V::add(a, bq[q]);
       if (accumulate) a = V::add(a, V::load(o + q * 4));
-      a = V::act(a, act);
-      if (nt_store) {
-        __builtin_nontemporal_store(a.x, o + q * 4 + 0); __builtin_nontemporal_store(a.y, o + q * 4 + 1);
-        __builtin_nontemporal_store(a.z, o + q * 4 + 2); __builtin_nontemporal_store(a.w, o + q * 4 + 3);
-      } else {
-        V::store(o + q * 4, a);
-      }
+      V::store(o + q * 4, V::act(a, act));
     }
     if (!more) break;
     r = rn; s = sn; t = tn;
@@ -202,7 +191,6 @@ template <int MODE>
 int launch_spmm(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* dinv_r,
                 const float* dinv_c, const float* wts, const float* h, const float* bias, float* out,
                 int64_t num_rows, int width, int accumulate, int act, hipStream_t st) {
-  static const int xcd_map = getenv("HSCN_SPMM_XCD") ? atoi(getenv("HSCN_SPMM_XCD")) : 0;
   static const int passes = getenv("HSCN_SPMM_PASSES") ? atoi(getenv("HSCN_SPMM_PASSES")) : 0;  // 0 = grid-stride
   static const int nv_env = getenv("HSCN_SPMM_NV") ? atoi(getenv("HSCN_SPMM_NV")) : 0;
   const int VEC = (width % 4 == 0) ? 4 : 1;
@@ -215,20 +203,18 @@ int launch_spmm(const int32_t* rowptr, const int32_t* col, const int32_t* eid, c
   if (LPR > SP_THREADS) return HSCN_E_UNSUPPORTED;
   const int RPB = SP_THREADS / LPR;
   static const int pipe = getenv("HSCN_SPMM_PIPE") ? atoi(getenv("HSCN_SPMM_PIPE")) : 1;
-  static const int nt = getenv("HSCN_SPMM_NT") ? atoi(getenv("HSCN_SPMM_NT")) : 0;
-  static const int nbmax = getenv("HSCN_SPMM_BLOCKS") ? atoi(getenv("HSCN_SPMM_BLOCKS")) : 8192;
   // measured (tools/ab_spmm.sh, 658 k rows): the pipelined form wins where a row is a few lanes -- H = 16: 3.55 -> 4.17
   // TB/s -- and loses where a lane group already keeps 1 KB in flight and registers decide the occupancy -- H = 128:
   // 4.42 -> 2.95 TB/s (4.05 with one piece per lane); HSCN_SPMM_PIPE=2 forces it at every width
   if ((pipe == 2 || (pipe == 1 && width <= 32)) && VEC == 4 && NV <= 2 && passes == 0) {
     int64_t nbp = (num_rows + RPB - 1) / RPB;
-    if (nbp > nbmax) nbp = nbmax;
+    if (nbp > 8192) nbp = 8192;
     if (NV == 2)
       k_spmm_pipe<MODE, 2><<<(unsigned)nbp, SP_THREADS, 0, st>>>(rowptr, col, eid, dinv_r, dinv_c, wts, h, bias, out, num_rows,
-                                                               width, LPR, RPB, accumulate, act, nt);
+                                                               width, LPR, RPB, accumulate, act);
     else
       k_spmm_pipe<MODE, 1><<<(unsigned)nbp, SP_THREADS, 0, st>>>(rowptr, col, eid, dinv_r, dinv_c, wts, h, bias, out, num_rows,
-                                                               width, LPR, RPB, accumulate, act, nt);
+                                                               width, LPR, RPB, accumulate, act);
     HSCN_RETURN_IF_LAUNCH_FAILED();
     return 0;
   }
@@ -245,7 +231,7 @@ int launch_spmm(const int32_t* rowptr, const int32_t* col, const int32_t* eid, c
   }
 #define HSCN_SPMM_LAUNCH(V_, N_)                                                                              \
   k_spmm<V_, MODE, N_><<<(unsigned)nb, SP_THREADS, 0, st>>>(rowptr, col, eid, dinv_r, dinv_c, wts, h, bias, out, \
-                                                            num_rows, width, LPR, RPB, accumulate, act, rpb, xcd_map)
+                                                            num_rows, width, LPR, RPB, accumulate, act, rpb)
   if (VEC == 4 && NV == 4) HSCN_SPMM_LAUNCH(4, 4);
   else if (VEC == 4 && NV == 2) HSCN_SPMM_LAUNCH(4, 2);
   else if (VEC == 4) HSCN_SPMM_LAUNCH(4, 1);

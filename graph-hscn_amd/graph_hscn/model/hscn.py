@@ -211,7 +211,7 @@ class SCN(nn.Module):
                 # (the adjacency as bytes: nobody outside this call sees it -- batched calls return None in its slot --
                 # and the products that stream it move a quarter of the bytes; HSCN_DENSE_ADJ=f32 keeps floats)
                 as_bytes = os.environ.get("HSCN_DENSE_ADJ", "u8") != "f32"
-                want_sym = as_bytes and os.environ.get("HSCN_DENSE_SYM", "1") != "0"     # (A/B: 0 = always compute A^T S)
+                want_sym = as_bytes
                 flag = self.adj_flag if as_bytes else None
                 if raw_edge_index is not None:
                     adj = to_dense_adj_ragged(raw_edge_index, node_ptr, node_graph, Bg, ng, raw=True, as_bytes=as_bytes,

@@ -18,6 +18,7 @@ a capture contains kernel nodes only and nothing of an earlier step can reach in
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -134,18 +135,14 @@ class ResidentTrainStep(_FlatGradStep):
         # ... and, H = 16, at ANY batch size: 2 B workgroups then take several rounds of the chip, local programs first
         # (block ids [0, B)), so a virtual workgroup's producer has always been dispatched before it; measured against the
         # launch pair at B = 256 / 512 / 1024: 47.9 / 86.2 / 163 us against 56.5 / 105 / 193 (profiles/r03_large_batches.txt).
-        # HSCN_ONE_LAUNCH_LARGE_B=0 restores the idle-CU rule.
-        import os
-        _lb = os.environ.get("HSCN_ONE_LAUNCH_LARGE_B", "1")     # ("all": H = 32 too -- measurement)
         # (graphs of the 4-wave class, n <= 64, keep the rule: PCQM-Contact at B = 2 048 / 4 096 runs 101 / 183 us as the
         # launch pair against 116 / 217)
-        large_b = _lb == "all" or (H == 16 and meta.max_n > 64 and _lb != "0")
+        large_b = H == 16 and meta.max_n > 64
         self.idle_cus = bool(model.compute_virtual and model.overlap_virtual and V > 0 and
                              (2 * B <= cus * max(per_cu, 1) or large_b))
         # one-launch step: the virtual branch rides as B more workgroups of the same launch when they land on idle
         # CUs (same condition as `defer`); a batch that fills the chip by itself keeps the launch pair (its virtual
         # branch shares the local workgroups there)
-        import os
         can = bool(_hip.lib().hscn_resident_train_step_supported(F, H, L, C, meta.max_n, meta.max_ell,
                                                                  meta.max_v if model.compute_virtual else 0,
                                                                  meta.max_evv if model.compute_virtual else 0))
@@ -417,7 +414,6 @@ class ScnEpochRunner:
         H, F = conv.lin_rel.weight.shape
         K = lin.weight.shape[0]
         meta = _engine.scn_meta(big, conv.lin_rel.weight.device)
-        P = int(_hip.lib().hscn_scn_resident_param_count(F, H, K))
         return bool(_hip.lib().hscn_scn_resident_train_step_supported(F, H, K, meta.max_n, meta.max_e))
 
     def __init__(self, model, big, optim_type: str, lr: float, weight_decay: float):
