@@ -9,6 +9,9 @@ epoch's permutation, itself a device tensor -- into the fixed-capacity buffers o
 ONE launch (``hscn_collate_gather``), bit for bit what ``HeteroBatch.from_data_list`` builds for the same list.
 An epoch is then ``perm = torch.randperm(G, device=...)`` and, per step, ``ds.gather(perm[i:i+B]);
 step.replay(); optimizer.step()`` with no host work that scales with the batch.
+
+``DeviceGraphDataset`` is the same for the MPNN baseline's homogeneous graphs.  Both are a ``_DeviceDataset``: the
+subclasses only lay their tables out as ``hscn_hetero_dataset`` / ``hscn_hetero_batch_out``.
 """
 from __future__ import annotations
 
@@ -45,7 +48,88 @@ def _top_sum(sizes: Tensor, k: int) -> int:
     return int(torch.topk(sizes, min(k, sizes.numel())).values.sum()) if sizes.numel() else 0
 
 
-class DeviceHeteroDataset:
+class _DeviceDataset:
+    """What the two datasets share: the gather launches and an epoch that walks by itself.  A subclass's constructor
+    calls this one first, then fills ``F``, ``C``, ``_t`` (its device tables), ``static`` (the fixed-capacity batch the
+    gathers write), ``_ds`` / ``_out`` (the two as the C structs) and, optionally, ``structure`` / ``_out_structure``
+    (per-graph structure gathered with every batch)."""
+
+    def __init__(self, graphs: Sequence, device, batch_size: int):
+        if not graphs:
+            raise ValueError("empty dataset")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.num_graphs = len(graphs)
+        self.batch_size = int(batch_size)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.structure = None
+        self._perm: Optional[Tensor] = None
+        self._cursor: Optional[Tensor] = None
+        self._counters: dict = {}      # id(step) -> (the step's per-step device counter, its value at epoch start, step)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self._t.values() if t is not None)
+
+    def _gather(self, ids: Tensor, cur, base):
+        """Batch ``ids[c * batch_size:(c + 1) * batch_size]`` into ``self.static``, c = ``*cur - *base`` (0 for None);
+        a ``cur`` without a ``base`` is the dataset's own cursor, which the gather proper advances."""
+        if self.structure is not None:        # (before the gather proper: that call advances the cursor)
+            _hip.call("hscn_collate_gather_structure", ctypes.byref(self._ds), ctypes.byref(self.structure.c),
+                      _hip.ptr(ids), self.batch_size, ctypes.byref(self._out), ctypes.byref(self._out_structure.c),
+                      _hip.ptr(self.flag), cur, base, _hip.stream())
+        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(ids), self.batch_size,
+                  ctypes.byref(self._out), _hip.ptr(self.flag), cur, base, _hip.stream())
+        return self.static.batch
+
+    def gather(self, ids: Tensor):
+        """Make ``self.static`` hold the batch of graphs ``ids`` (int64 ``[batch_size]`` on the device; order
+        kept).  Asynchronous on the current stream, capturable; returns ``self.static.batch``."""
+        if ids.dtype != torch.int64 or ids.device != self.device or ids.numel() != self.batch_size:
+            raise ValueError(f"ids must be int64 [{self.batch_size}] on {self.device}")
+        return self._gather(ids.contiguous(), None, None)
+
+    # ---- an epoch that walks by itself: the permutation and a batch counter live on the device ----------------
+    def new_epoch(self, generator: Optional[torch.Generator] = None) -> Tensor:
+        """Draw the epoch's permutation into the dataset's own buffer and rewind the batch counter.  Returns the
+        permutation (a device tensor; ``gather_next`` serves its first ``num_graphs // batch_size`` slices)."""
+        if self._perm is None:
+            # (one spare batch of valid ids behind the permutation: a replay too many reads those, not stray memory)
+            self._perm_buf = torch.zeros(self.num_graphs + self.batch_size, dtype=torch.int64, device=self.device)
+            self._perm = self._perm_buf[: self.num_graphs]
+            self._cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
+        torch.randperm(self.num_graphs, device=self.device, generator=generator, out=self._perm)
+        self._cursor.zero_()
+        for counter, base, _ in self._counters.values():   # steps with a counter of their own: this epoch's slices
+            base.copy_(counter)                            # count from its value now
+        return self._perm
+
+    def gather_next(self, step=None):
+        """Gather the next batch of the current epoch's permutation and advance the device-side counter, with no
+        host argument that changes from step to step, so the launches can be CAPTURED in front of the training step
+        (``CapturedStep(..., pre=ds.gather_next)``) -- a replay is then "next batch + iteration".
+        ``step``: the resident step the gather is captured with (``CapturedStep`` passes it).  When that step
+        keeps a per-step counter on the device (word 0 of the one-launch step's sync buffer, advanced by its gradient
+        fold), the gather reads its slice number off THAT counter (minus its value when the epoch began) and the
+        launch that would advance a counter of our own (4.5 us per iteration) does not exist."""
+        if self._perm is None:
+            raise RuntimeError("call new_epoch() first")
+        sync = getattr(step, "_sync", None) if step is not None else None
+        if sync is not None and getattr(step, "advances_sync", False):
+            ent = self._counters.get(id(step))
+            if ent is None:                      # (uint32 counter read as int32; the base is this epoch's start)
+                ent = self._counters[id(step)] = (sync[:1], sync[:1].clone(), step)
+            return self._gather(self._perm, _hip.ptr(ent[0]), _hip.ptr(ent[1]))
+        return self._gather(self._perm, _hip.ptr(self._cursor), None)
+
+    def check(self) -> None:
+        """Synchronising validity check of the gathers issued so far."""
+        if int(self.flag.item()) & 8:
+            raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")
+
+
+class DeviceHeteroDataset(_DeviceDataset):
     """``graphs``: the list ``generate_hetero_data`` returns (or any sequence of ``HeteroData`` with the
     local / virtual node types and the ll / vv / lv relations).  ``batch_size`` graphs per step."""
 
@@ -54,13 +138,7 @@ class DeviceHeteroDataset:
         ids) and degree norms in HBM -- built ONCE here by ``hscn_resident_structure`` over the dataset laid out as
         one batch -- and gather them with every batch (``static.batch.structure``), so that a step can load its
         structure instead of rebuilding it (``CapturedStep(..., structure="batch")``).  +~40 % dataset bytes."""
-        if not graphs:
-            raise ValueError("empty dataset")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.num_graphs = len(graphs)
-        self.batch_size = int(batch_size)
+        super().__init__(graphs, device, batch_size)
         whole = HeteroBatch.from_data_list(graphs)            # once, on the host: global ids + per-graph ranges
         nptr, vptr = whole["local"].ptr, whole["virtual"].ptr
         base = {"local": nptr, "virtual": vptr}
@@ -89,8 +167,6 @@ class DeviceHeteroDataset:
             {et: _top_sum(esizes[et], B) for et in _RELS},
             {"local": int(sizes["local"].max()), "virtual": int(sizes["virtual"].max())},
             {et: int(esizes[et].max()) if esizes[et].numel() else 0 for et in _RELS}, self.F, self.C)
-        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.structure = None
         if resident_structure:
             from ..engine import BatchStructure, build_structure
             self.structure = build_structure(whole.to(dev))              # one launch over all G graphs
@@ -98,9 +174,6 @@ class DeviceHeteroDataset:
             self._out_structure = BatchStructure(dev, st0.N, st0.V, B, st0.E[LL], st0.E[LV], st0.E[VV])
             st0.batch.structure = self._out_structure
             torch.cuda.synchronize(dev)                                   # (the int64 COO copy of `whole` may go now)
-        self._perm: Optional[Tensor] = None
-        self._cursor: Optional[Tensor] = None
-        self._counters: dict = {}      # id(step) -> (the step's per-step device counter, its value at epoch start, step)
         t = self._t
         p = _hip.ptr
         self._ds = _Dataset(p(t["x_local"]), p(t["x_virtual"]), p(t["y"]), p(t["nptr"]), p(t["vptr"]),
@@ -115,70 +188,6 @@ class DeviceHeteroDataset:
                               (ctypes.c_void_p * 3)(*[p(hb[et].edge_index) for et in _RELS]),
                               (ctypes.c_void_p * 3)(*[p(hb[et].ptr32) for et in _RELS]),
                               st.N, st.V, (ctypes.c_int64 * 3)(*[st.E[et] for et in _RELS]))
-
-    @property
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._t.values() if t is not None)
-
-    def gather(self, ids: Tensor) -> HeteroBatch:
-        """Make ``self.static`` hold the batch of graphs ``ids`` (int64 ``[batch_size]`` on the device; order
-        kept).  Asynchronous on the current stream, capturable; returns ``self.static.batch``."""
-        if ids.dtype != torch.int64 or ids.device != self.device or ids.numel() != self.batch_size:
-            raise ValueError(f"ids must be int64 [{self.batch_size}] on {self.device}")
-        ids = ids.contiguous()
-        if self.structure is not None:
-            _hip.call("hscn_collate_gather_structure", ctypes.byref(self._ds), ctypes.byref(self.structure.c),
-                      _hip.ptr(ids), self.batch_size, ctypes.byref(self._out), ctypes.byref(self._out_structure.c),
-                      _hip.ptr(self.flag), None, None, _hip.stream())
-        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(ids), self.batch_size,
-                  ctypes.byref(self._out), _hip.ptr(self.flag), None, None, _hip.stream())
-        return self.static.batch
-
-    # ---- an epoch that walks by itself: the permutation and a batch counter live on the device ----------------
-    def new_epoch(self, generator: Optional[torch.Generator] = None) -> Tensor:
-        """Draw the epoch's permutation into the dataset's own buffer and rewind the batch counter.  Returns the
-        permutation (a device tensor; ``gather_next`` serves its first ``num_graphs // batch_size`` slices)."""
-        if self._perm is None:
-            # (one spare batch of valid ids behind the permutation: a replay too many reads those, not stray memory)
-            self._perm_buf = torch.zeros(self.num_graphs + self.batch_size, dtype=torch.int64, device=self.device)
-            self._perm = self._perm_buf[: self.num_graphs]
-            self._cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
-        torch.randperm(self.num_graphs, device=self.device, generator=generator, out=self._perm)
-        self._cursor.zero_()
-        for counter, base, _ in self._counters.values():   # steps with a counter of their own: this epoch's slices
-            base.copy_(counter)                            # count from its value now
-        return self._perm
-
-    def gather_next(self, step=None) -> HeteroBatch:
-        """Gather the next batch of the current epoch's permutation and advance the device-side counter, with no
-        host argument that changes from step to step, so the launches can be CAPTURED in front of the training step
-        (``CapturedStep(..., pre=ds.gather_next)``) -- a replay is then "next batch + iteration".
-        ``step``: the ``ResidentTrainStep`` the gather is captured with (``CapturedStep`` passes it).  When that step
-        keeps a per-step counter on the device (word 0 of the one-launch step's sync buffer, advanced by its gradient
-        fold), the gather reads its slice number off THAT counter (minus its value when the epoch began) and the
-        launch that would advance a counter of our own (4.5 us per iteration) does not exist."""
-        if self._perm is None:
-            raise RuntimeError("call new_epoch() first")
-        sync = getattr(step, "_sync", None) if step is not None else None
-        if sync is not None and getattr(step, "advances_sync", False):
-            ent = self._counters.get(id(step))
-            if ent is None:                      # (uint32 counter read as int32; the base is this epoch's start)
-                ent = self._counters[id(step)] = (sync[:1], sync[:1].clone(), step)
-            cur, base = _hip.ptr(ent[0]), _hip.ptr(ent[1])
-        else:
-            cur, base = _hip.ptr(self._cursor), None
-        if self.structure is not None:        # (before the gather proper: that call advances the cursor)
-            _hip.call("hscn_collate_gather_structure", ctypes.byref(self._ds), ctypes.byref(self.structure.c),
-                      _hip.ptr(self._perm), self.batch_size, ctypes.byref(self._out),
-                      ctypes.byref(self._out_structure.c), _hip.ptr(self.flag), cur, base, _hip.stream())
-        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(self._perm), self.batch_size,
-                  ctypes.byref(self._out), _hip.ptr(self.flag), cur, base, _hip.stream())
-        return self.static.batch
-
-    def check(self) -> None:
-        """Synchronising validity check of the gathers issued so far."""
-        if int(self.flag.item()) & 8:
-            raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")
 
 
 class StaticGraphBatch:
@@ -210,23 +219,17 @@ class StaticGraphBatch:
                    "ei": [torch.zeros(2, 1, **i64) for _ in range(2)], "eptr32": [torch.zeros(B + 1, **i32) for _ in range(2)]}
 
 
-class DeviceGraphDataset:
-    """The homogeneous twin of ``DeviceHeteroDataset`` for the MPNN baseline: a list of ``Data`` graphs resident in
-    HBM, and ``gather(ids)`` / ``gather_next()`` writing the batch of graphs ``ids`` into the fixed-capacity buffers of
-    a ``StaticGraphBatch`` in ONE launch -- bit for bit what ``Batch.from_data_list`` builds (features cast to float32,
-    as train/train.py:79 casts them).  It is ``hscn_collate_gather`` over a hetero dataset whose virtual node type
+class DeviceGraphDataset(_DeviceDataset):
+    """The MPNN baseline's dataset: a list of ``Data`` graphs resident in HBM, gathered into the fixed-capacity buffers
+    of a ``StaticGraphBatch`` -- bit for bit what ``Batch.from_data_list`` builds (features cast to float32, as
+    train/train.py:79 casts them).  It is ``hscn_collate_gather`` over a hetero dataset whose virtual node type
     has no nodes and whose vv / lv relations have no edges: every graph's virtual and vv / lv ranges are empty, so the
     blocks of those parts copy nothing and write empty segment tables."""
 
     def __init__(self, graphs: Sequence, device, batch_size: int):
         from ..data import Batch
-        if not graphs:
-            raise ValueError("empty dataset")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.num_graphs = G = len(graphs)
-        self.batch_size = B = int(batch_size)
+        super().__init__(graphs, device, batch_size)
+        G, B = self.num_graphs, self.batch_size
         whole = Batch.from_data_list(graphs)                  # once, on the host: global ids + per-graph ranges
         nptr = whole.ptr
         eptr = whole.eptr32.to(torch.int64)
@@ -245,9 +248,6 @@ class DeviceGraphDataset:
                    "none": torch.zeros(1, dtype=torch.int32, device=dev), "eptr_none": zeros_g.to(dev)}
         self.static = StaticGraphBatch(B, dev, _top_sum(sizes, B), _top_sum(esizes, B), int(sizes.max()),
                                        int(esizes.max()) if esizes.numel() else 0, self.F, self.C)
-        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._perm: Optional[Tensor] = None
-        self._cursor: Optional[Tensor] = None
         t, p = self._t, _hip.ptr
         self._ds = _Dataset(p(t["x"]), p(t["xv"]), p(t["y"]), p(t["nptr"]), p(t["vptr"]),
                             (ctypes.c_void_p * 3)(p(t["src0"]), p(t["none"]), p(t["none"])),
@@ -260,36 +260,3 @@ class DeviceGraphDataset:
                               (ctypes.c_void_p * 3)(p(b.edge_index), p(v["ei"][0]), p(v["ei"][1])),
                               (ctypes.c_void_p * 3)(p(b.eptr32), p(v["eptr32"][0]), p(v["eptr32"][1])),
                               st.N, 0, (ctypes.c_int64 * 3)(st.E, 1, 1))
-
-    def gather(self, ids: Tensor):
-        """Make ``self.static`` hold the batch of graphs ``ids`` (int64 ``[batch_size]`` on the device).  Asynchronous
-        on the current stream, capturable; returns ``self.static.batch``."""
-        if ids.dtype != torch.int64 or ids.device != self.device or ids.numel() != self.batch_size:
-            raise ValueError(f"ids must be int64 [{self.batch_size}] on {self.device}")
-        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(ids.contiguous()), self.batch_size,
-                  ctypes.byref(self._out), _hip.ptr(self.flag), None, None, _hip.stream())
-        return self.static.batch
-
-    def new_epoch(self, generator: Optional[torch.Generator] = None) -> Tensor:
-        """Draw the epoch's permutation on the device and rewind the batch counter (as ``DeviceHeteroDataset``)."""
-        if self._perm is None:
-            self._perm_buf = torch.zeros(self.num_graphs + self.batch_size, dtype=torch.int64, device=self.device)
-            self._perm = self._perm_buf[: self.num_graphs]
-            self._cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
-        torch.randperm(self.num_graphs, device=self.device, generator=generator, out=self._perm)
-        self._cursor.zero_()
-        return self._perm
-
-    def gather_next(self):
-        """Gather the next slice of the epoch's permutation and advance the device-side counter: no host argument
-        changes from step to step, so it can be captured in front of the training step."""
-        if self._perm is None:
-            raise RuntimeError("call new_epoch() first")
-        _hip.call("hscn_collate_gather", ctypes.byref(self._ds), _hip.ptr(self._perm), self.batch_size,
-                  ctypes.byref(self._out), _hip.ptr(self.flag), _hip.ptr(self._cursor), None, _hip.stream())
-        return self.static.batch
-
-    def check(self) -> None:
-        """Synchronising validity check of the gathers issued so far."""
-        if int(self.flag.item()) & 8:
-            raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")

@@ -58,6 +58,7 @@ class FlatAdam:
                 raise ValueError("param_grads must tile the front of the flat gradient buffer in order")
             off += p.numel()
             offs.append(off)
+        self.param_grads = list(param_grads)
         self.params = [p for p, _ in param_grads]
         self.P = off
         self.grads = flat_grads
@@ -130,16 +131,7 @@ class FlatAdam:
     def collect_autograd(self, accumulate: bool = False) -> None:
         """The first half of ``step_from_autograd``: ``p.grad`` into the flat buffer (copied, or added with
         ``accumulate``), no step."""
-        off = 0
-        with torch.no_grad():
-            for p in self.params:
-                dst = self.grads[off: off + p.numel()].view_as(p)
-                if p.grad is None:
-                    if not accumulate:
-                        dst.zero_()
-                elif p.grad.data_ptr() != dst.data_ptr():
-                    dst.add_(p.grad) if accumulate else dst.copy_(p.grad)
-                off += p.numel()
+        collect_autograd(self.param_grads, accumulate)
 
     def check(self) -> None:
         """The parameter tensors are still the ones the pointer table was built from (``module.to()`` / a loaded
@@ -165,6 +157,18 @@ class FlatAdam:
         if optim_type == "adamW":
             return cls(param_grads, flat_grads, lr=lr, weight_decay=weight_decay, decoupled=True, **kw)
         return None
+
+
+def collect_autograd(param_grads: Sequence[Tuple[Tensor, Tensor]], accumulate: bool = False) -> None:
+    """``p.grad`` of an eager backward into ``g`` for every ``(p, g)``: copied (zeros for a parameter without a
+    gradient), or added with ``accumulate``; a ``p.grad`` that already is ``g`` is left alone."""
+    with torch.no_grad():
+        for p, g in param_grads:
+            if p.grad is None:
+                if not accumulate:
+                    g.zero_()
+            elif p.grad.data_ptr() != g.data_ptr():
+                g.add_(p.grad.view_as(g)) if accumulate else g.copy_(p.grad.view_as(g))
 
 
 def clip_grad_norm_flat(flat_grads: Tensor, max_norm: float, norm_out: Optional[Tensor] = None) -> None:

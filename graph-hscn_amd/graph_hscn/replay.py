@@ -153,32 +153,55 @@ class StaticHeteroBatch:
         return self.batch
 
 
+def _snapshot(params, optimizer):
+    """Copies of ``params`` and of the tensors in ``optimizer.state`` (none for an optimizer still to be built), for
+    ``_restore`` behind the warm-up steps that PyTorch's capture recipe asks for."""
+    state = getattr(optimizer, "state", None) or {}
+    return ([p.detach().clone() for p in params],
+            {id(p): {k: v.clone() for k, v in st.items() if isinstance(v, Tensor)} for p, st in state.items()})
+
+
+def _restore(params, optimizer, snap) -> None:
+    """Put parameters and optimizer state back IN PLACE (captured launches hold their addresses): the old value, or
+    zero for state the warm-up created -- the initial state of the Adam family."""
+    snap_p, snap_s = snap
+    with torch.no_grad():
+        for p, s0 in zip(params, snap_p):
+            p.copy_(s0)
+        if hasattr(optimizer, "reset_state"):          # optim.FlatAdam: built behind the snapshot, all state is new
+            optimizer.reset_state()
+            return
+        for p, st in optimizer.state.items():
+            for k, v in st.items():
+                if isinstance(v, Tensor):
+                    old = snap_s.get(id(p), {}).get(k)
+                    v.copy_(old) if old is not None else v.zero_()
+
+
+def _warm_up_and_capture(fn, warmup: int) -> "torch.cuda.CUDAGraph":
+    """PyTorch's capture recipe: ``warmup`` eager calls of ``fn`` on a side stream, then one captured call."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g
+
+
 def capture_optimizer_step(params, optimizer, warmup: int = 3) -> "torch.cuda.CUDAGraph":
     """``optimizer.step()`` (an optimizer built with ``capturable=True``; ``fused=True`` keeps it to one launch) on
     the gradient buffers ``p.grad`` points at NOW, as a hipGraph of its own.  The warm-up steps PyTorch's capture
     recipe asks for are undone: parameters and optimizer state are put back in place (state the warm-up created is
     zeroed: the initial state of the Adam family)."""
     params = list(params)
-    snap_p = [p.detach().clone() for p in params]
-    snap_s = {id(p): {k: v.clone() for k, v in st.items() if isinstance(v, Tensor)} for p, st in optimizer.state.items()}
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(warmup):
-            optimizer.step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        optimizer.step()
-    with torch.no_grad():
-        for p, s0 in zip(params, snap_p):
-            p.copy_(s0)
-        for p, st in optimizer.state.items():
-            for k, v in st.items():
-                if isinstance(v, Tensor):
-                    old = snap_s.get(id(p), {}).get(k)
-                    v.copy_(old) if old is not None else v.zero_()
+    snap = _snapshot(params, optimizer)
+    g = _warm_up_and_capture(optimizer.step, warmup)
+    _restore(params, optimizer, snap)
     return g
 
 
@@ -230,44 +253,17 @@ class CapturedStep:
         optimizer that is not a clipping ``FlatAdam``.
         With neither, the one graph captured is the one captured before these modes existed."""
         from .optim import clip_grad_norm_flat
-        from .step import ResidentTrainStep
+        from .train.batching import resident_step
         self.model, self.static, self.loss_fn, self.optimizer = model, static, loss_fn, optimizer
-        snap_p = snap_s = None
-        make_flat = callable(optimizer) and not hasattr(optimizer, "step")     # ``lambda step: optim.FlatAdam(...)``
-        if optimizer is not None:
-            snap_p = [p.detach().clone() for p in model.parameters()]
-            if not make_flat:
-                snap_s = {id(p): {k: v.clone() for k, v in st.items() if isinstance(v, Tensor)}
-                          for p, st in optimizer.state.items()}
-        hb = static.batch
-        from .model.mpnn import MPNN
-        if isinstance(model, MPNN):       # the MPNN baseline: ``loader.device_dataset.StaticGraphBatch``, one launch
-            from .step import MPNNResidentTrainStep
-            if getattr(hb, "y", None) is None:
-                raise ValueError("the static batch carries no targets")
-            self.step = MPNNResidentTrainStep(model, hb, loss_fn, accumulate=accumulate)
-        else:
-            if "y" not in hb["local"]:
-                raise ValueError("the static batch carries no targets")
-            try:
-                self.step = ResidentTrainStep(model, hb, loss_fn, one_launch=one_launch, structure=structure,
-                                              accumulate=accumulate)
-            except RuntimeError as e:
-                raise RuntimeError("CapturedStep needs the graph-resident engine (the layered operators size their "
-                                   "work by tensor shapes, which a static-capacity batch does not carry): "
-                                   + str(e)) from e
+        params = list(model.parameters())
+        snap = _snapshot(params, optimizer) if optimizer is not None else None
+        self.step = resident_step(model, static.batch, loss_fn, one_launch, structure, accumulate)
         self.step.bind_grads()
         model.last_engine = "resident"
-        if make_flat:          # built here: it needs the step's flat gradient buffer
-            optimizer = self.optimizer = optimizer(self.step)
+        if callable(optimizer) and not hasattr(optimizer, "step"):     # ``lambda step: optim.FlatAdam(...)``: built
+            optimizer = self.optimizer = optimizer(self.step)          # here, on the step's flat gradient buffer
 
-        pre_takes_step = False
-        if pre is not None:
-            import inspect
-            try:
-                pre_takes_step = "step" in inspect.signature(pre).parameters
-            except (TypeError, ValueError):
-                pass
+        pre_args = (self.step,)      # ``gather_next(step)``; () once ``pre`` has turned out to take no argument
 
         P = self.step.P
         self.accumulate = bool(accumulate)
@@ -277,8 +273,15 @@ class CapturedStep:
         zero_after = self.accumulate and optimizer is not None and not getattr(optimizer, "zero_grads", False)
 
         def step(boundary: bool = True):
+            nonlocal pre_args
             if pre is not None:
-                pre(self.step) if pre_takes_step else pre()      # (DeviceHeteroDataset.gather_next(step))
+                try:
+                    pre(*pre_args)
+                except TypeError as e:
+                    if not pre_args or e.__traceback__.tb_next is not None:     # (raised inside ``pre``)
+                        raise
+                    pre_args = ()
+                    pre()
             self.step.run()
             if not boundary:
                 return
@@ -291,16 +294,7 @@ class CapturedStep:
             if zero_after:
                 self.step.grads[:P].zero_()
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            step()
+        self.graph = _warm_up_and_capture(step, warmup)
         self.micro_graph = self.graph
         if self.accumulate and (optimizer is not None or reducer is not None or self.max_norm is not None):
             self.micro_graph = torch.cuda.CUDAGraph()
@@ -310,17 +304,7 @@ class CapturedStep:
         # the gradient tensors the captured backward writes (a later eager step re-points ``p.grad`` elsewhere)
         self.grads = list(self.step.param_grads)
         if optimizer is not None:
-            with torch.no_grad():
-                for p, s0 in zip(model.parameters(), snap_p):
-                    p.copy_(s0)
-                if make_flat:
-                    optimizer.reset_state()
-                else:
-                    for p, st in optimizer.state.items():
-                        for k, v in st.items():
-                            if isinstance(v, Tensor):
-                                old = snap_s.get(id(p), {}).get(k)
-                                v.copy_(old) if old is not None else v.zero_()
+            _restore(params, optimizer, snap)
         if self.accumulate:        # the first micro-batch adds onto zeros, not onto the warm-up's gradients
             self.step.grads.zero_()
         if self.clip_norm is not None:

@@ -1,0 +1,66 @@
+"""The one place that knows stage C's two batch kinds: ``HSCN`` takes a ``HeteroBatch`` (targets on the local node
+type); every other model -- the MPNN baseline -- a homogeneous ``Batch`` with float32 features (the reference casts
+them in its loop, train/train.py:79).  The eager loop, the captured loop, the device evaluator and
+``replay.CapturedStep`` all ask here."""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+from torch import Tensor
+
+from ..data import Batch, HeteroBatch
+from ..model.hscn import HSCN
+
+
+def is_hetero(model) -> bool:
+    return isinstance(model, HSCN)
+
+
+def targets(model, batch) -> Optional[Tensor]:
+    """The batch's targets, or ``None`` when it carries none."""
+    if is_hetero(model):
+        return batch["local"].y if "y" in batch["local"] else None
+    return getattr(batch, "y", None)
+
+
+def forward(model, batch) -> Tuple[Tensor, Tensor]:
+    """``(pred, targets)`` of ``model`` on a batch that is on the model's device."""
+    if is_hetero(model):
+        return model(batch.x_dict, batch.edge_index_dict, batch), batch["local"].y
+    return model(batch), batch.y
+
+
+def to_device(model, batch, device):
+    """A loader's batch where the HIP operators can take it."""
+    batch = batch.to(device)
+    if not is_hetero(model):
+        batch.x = batch.x.float()
+    return batch
+
+
+def collate(model, graphs: Sequence, device):
+    """Host collation of a graph list, onto ``device``."""
+    return to_device(model, (HeteroBatch if is_hetero(model) else Batch).from_data_list(graphs), device)
+
+
+def dataset_class(model):
+    """``loader.device_dataset``'s class for the graphs ``model`` trains on."""
+    from ..loader.device_dataset import DeviceGraphDataset, DeviceHeteroDataset
+    return DeviceHeteroDataset if is_hetero(model) else DeviceGraphDataset
+
+
+def resident_step(model, batch, loss_fn: str, one_launch: Optional[bool] = None, structure=None,
+                  accumulate: bool = False):
+    """The resident training step of ``model`` on a static batch (``step.ResidentTrainStep``, or the MPNN baseline's
+    one launch, which has neither a launch pair nor a structure to load)."""
+    from ..step import MPNNResidentTrainStep, ResidentTrainStep
+    if targets(model, batch) is None:
+        raise ValueError("the static batch carries no targets")
+    if not is_hetero(model):
+        return MPNNResidentTrainStep(model, batch, loss_fn, accumulate=accumulate)
+    try:
+        return ResidentTrainStep(model, batch, loss_fn, one_launch=one_launch, structure=structure,
+                                 accumulate=accumulate)
+    except RuntimeError as e:
+        raise RuntimeError("CapturedStep needs the graph-resident engine (the layered operators size their "
+                           "work by tensor shapes, which a static-capacity batch does not carry): " + str(e)) from e

@@ -18,11 +18,10 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from ..data import Batch, HeteroBatch
-from ..loader.device_dataset import DeviceGraphDataset, DeviceHeteroDataset
 from ..loss import criterion
 from ..metrics import (MetricResult, average_precision_launch, mean_absolute_error_launch, metric_buffers,
                        metric_value, read_packed)
+from . import batching
 
 _GATHER_FAULT = 8      # loader.device_dataset: a graph id outside the dataset / a batch beyond the static capacity
 
@@ -50,8 +49,6 @@ class DeviceEvaluator:
         G = len(graphs)
         if G < 1:
             raise ValueError("empty split")
-        from ..model.mpnn import MPNN
-        self.mpnn = isinstance(model, MPNN)
         self.model, self.loss_fn, self.metric = model, loss_fn, metric
         self.num_graphs, self.batch_size = G, int(batch_size)
         B = self.batch_size
@@ -59,18 +56,12 @@ class DeviceEvaluator:
         self.num_batches = self.steps + (1 if self.tail else 0)
         self.ds = None
         if self.steps:
-            self.ds = (DeviceGraphDataset if self.mpnn else DeviceHeteroDataset)(graphs, dev, B)
+            self.ds = batching.dataset_class(model)(graphs, dev, B)
             ids = torch.arange(self.steps * B, dtype=torch.int64, device=dev)
             self.ids = [ids[i * B:(i + 1) * B] for i in range(self.steps)]
-        self.tail_batch = None
-        if self.tail:                             # collated once, kept on the device
-            rest = list(graphs[self.steps * B:])
-            if self.mpnn:
-                self.tail_batch = Batch.from_data_list(rest).to(dev)
-                self.tail_batch.x = self.tail_batch.x.float()
-            else:
-                self.tail_batch = HeteroBatch.from_data_list(rest).to(dev)
-        y0 = self._y(self.tail_batch if self.tail else self.ds.static.batch)
+        # (the tail: collated once, kept on the device)
+        self.tail_batch = batching.collate(model, list(graphs[self.steps * B:]), dev) if self.tail else None
+        y0 = batching.targets(model, self.tail_batch if self.tail else self.ds.static.batch)
         C = self.C = int(y0.size(1))
         f32 = dict(dtype=torch.float32, device=dev)
         self.scores = torch.zeros(G, C, **f32)
@@ -82,12 +73,8 @@ class DeviceEvaluator:
         self._gather_flag = self.packed[24:28].view(torch.int32)
         self.out = metric_buffers(metric, G, C, dev, self.packed) if metric else None
 
-    def _y(self, batch):
-        return batch.y if self.mpnn else batch["local"].y
-
     def _batch(self, batch, lo: int, hi: int, i: int) -> None:
-        pred = self.model(batch) if self.mpnn else self.model(batch.x_dict, batch.edge_index_dict, batch)
-        true = self._y(batch)
+        pred, true = batching.forward(self.model, batch)
         loss, score = criterion(self.loss_fn, pred, true)
         self.loss_log[i].copy_(loss)
         self.scores[lo:hi].copy_(score)

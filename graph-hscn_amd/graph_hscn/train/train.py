@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from ..config.config import OPTIM_DICT
 from ..loss import criterion
-from ..model.hscn import HSCN
+from . import batching
 
 
 def is_eval_epoch(epoch: int, max_epochs: int, eval_period: int) -> bool:  # train/utils.py:1-6
@@ -76,13 +76,51 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
 
 
 def _run_batch(model, batch, device):
-    if isinstance(model, HSCN):
-        batch = batch.to(device)
-        return model(batch.x_dict, batch.edge_index_dict, batch), batch["local"].y
     # train.py:78-80 leaves the batch where the loader put it; the HIP operators take device tensors only
-    batch = batch.to(device)
-    batch.x = batch.x.float()
-    return model(batch), batch.y
+    return batching.forward(model, batching.to_device(model, batch, device))
+
+
+class EarlyStopping:
+    """The evaluation block of the epoch loops (train/train.py:196-211).  ``update(validation loss, epoch)`` is true
+    once the loss has not improved on its best by more than ``min_delta`` for ``patience`` evaluations in a row --
+    except on the last epoch, which ends the run anyway.  With a ``reducer`` of several ranks they first agree on the
+    mean of their losses (on ``device``): every rank must decide alike, or the next collective hangs."""
+
+    def __init__(self, training_cfg, reducer=None, device=None):
+        self.cfg, self.reducer, self.device = training_cfg, reducer, device
+        self.best, self.stale = float("inf"), 0
+
+    def update(self, loss: float, epoch: int) -> bool:
+        if self.reducer is not None and self.reducer.world_size > 1:
+            import torch.distributed as dist
+            t = torch.tensor([loss], dtype=torch.float64, device=self.device)
+            dist.all_reduce(t, group=self.reducer.group)
+            loss = float(t.item()) / self.reducer.world_size
+        if loss < self.best - self.cfg.min_delta:
+            self.best, self.stale = loss, 0
+        else:
+            self.stale += 1
+        return self.stale >= self.cfg.patience and epoch != self.cfg.epochs - 1
+
+    def evaluate(self, epoch: int, logger, model, sources, metric_fn, eval_history: Optional[list] = None) -> bool:
+        """Evaluate ``sources`` = (validation, test): host loaders through ``eval_epoch``, or
+        ``eval_resident.DeviceEvaluator``s.  Whether to stop."""
+        for split, source in zip(["Validation", "Test"], sources):
+            if hasattr(source, "evaluate"):
+                loss, perf = source.evaluate()
+                if metric_fn is not None:
+                    perf = metric_fn(source.targets, source.scores)
+                if logger is not None:
+                    logger.info(f"epoch {epoch} {split} loss {loss:.5f} perf {perf:.5f}")
+            else:
+                loss, perf = eval_epoch(epoch, logger, source, model, self.cfg.loss_fn, metric_fn, split)
+            if eval_history is not None:
+                eval_history.append((epoch, split, loss, perf))
+            if split == "Validation" and self.update(loss, epoch):
+                if logger is not None:
+                    logger.info("stopping early")
+                return True
+        return False
 
 
 def train_epoch(epoch, logger, loader, model, optimizer, loss_fn: str, metric_fn: Optional[Callable],
@@ -135,21 +173,12 @@ def eval_epoch(epoch, logger, loader, model, loss_fn: str, metric_fn: Optional[C
 def train(logger, optim_cfg, training_cfg, loaders, model, metric_fn: Optional[Callable] = None, reducer=None):
     optimizer = OPTIM_DICT[optim_cfg.optim_type](lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay,
                                                  params=model.parameters())
-    best, stale = float("inf"), 0
+    stopper = EarlyStopping(training_cfg)
     history = []
     for epoch in range(training_cfg.epochs):
         history.append(train_epoch(epoch, logger, loaders[0], model, optimizer, training_cfg.loss_fn, metric_fn,
                                    optim_cfg.batch_accumulation, optim_cfg.clip_grad_norm, reducer))
-        if is_eval_epoch(epoch, training_cfg.epochs, training_cfg.eval_period):
-            for split, loader in zip(["Validation", "Test"], loaders[1:]):
-                loss, _ = eval_epoch(epoch, logger, loader, model, training_cfg.loss_fn, metric_fn, split)
-                if split == "Validation":
-                    if loss < best - training_cfg.min_delta:
-                        best, stale = loss, 0
-                    else:
-                        stale += 1
-                    if stale >= training_cfg.patience and epoch != training_cfg.epochs - 1:
-                        if logger is not None:
-                            logger.info("stopping early")
-                        return history
+        if is_eval_epoch(epoch, training_cfg.epochs, training_cfg.eval_period) and \
+                stopper.evaluate(epoch, logger, model, loaders[1:], metric_fn):
+            break
     return history

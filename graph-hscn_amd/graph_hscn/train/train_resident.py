@@ -18,17 +18,17 @@ the zeroing ride on its one launch, so no iteration issues a launch it did not i
 from __future__ import annotations
 
 import time
+from types import SimpleNamespace
 from typing import Callable, List, Optional, Sequence
 
 import torch
 
 from ..config.config import OPTIM_DICT
-from ..data import Batch, HeteroBatch, HeteroData
-from ..loader.device_dataset import DeviceHeteroDataset
 from ..loss import criterion
-from ..optim import clip_grad_norm_flat
+from ..optim import clip_grad_norm_flat, collect_autograd
 from ..replay import CapturedStep
-from .train import eval_epoch, is_eval_epoch
+from . import batching
+from . import train as _train
 
 CLIP_MAX_NORM = 1.0     # train/train.py:92 (the reference's nn.utils.clip_grad_norm_(params, 1.0))
 
@@ -37,6 +37,62 @@ def optimizer_steps_at(it: int, num_batches: int, batch_accumulation: int) -> bo
     """Whether iteration ``it`` (0-based) of an epoch of ``num_batches`` batches steps the optimizer: every
     ``batch_accumulation``-th batch and always the last one (train/train.py:89 -- ``train.train_epoch``)."""
     return (it + 1) % batch_accumulation == 0 or it + 1 == num_batches
+
+
+def _make_optimizer(optim_cfg, model, flat: bool, clip: bool, acc: bool):
+    """``(optimizer, capturable)``.  ``flat`` (optim.FlatAdam: the update as ONE launch, clip and zeroing in it): a
+    callable ``step -> FlatAdam`` for ``CapturedStep`` to build on the step's flat gradient buffer."""
+    kw = dict(lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay)
+    if flat:
+        from ..optim import FlatAdam
+        fkw = dict(kw, max_norm=CLIP_MAX_NORM if clip else None, zero_grads=acc)
+        return (lambda st: FlatAdam.from_config(optim_cfg.optim_type, st.param_grads, st.grads, **fkw)), True
+    opt_cls = OPTIM_DICT[optim_cfg.optim_type]
+    try:
+        optimizer = opt_cls(model.parameters(), capturable=True, fused=True, **kw)
+    except (TypeError, RuntimeError):          # (Adagrad has neither switch: its step stays outside the graph)
+        optimizer = opt_cls(model.parameters(), **kw)
+    return optimizer, bool(optimizer.defaults.get("capturable", False))
+
+
+def _boundary_outside_graph(run, weight: float) -> None:
+    """What the graph does not hold at a stepping iteration (a non-capturable optimizer; the eager tail)."""
+    if run.reducer is not None:
+        run.reducer.reduce(weight, weight * run.reducer.world_size)
+    if run.clip_norm is not None:              # (an optim.FlatAdam clips and zeroes in its own launch)
+        clip_grad_norm_flat(run.flat_grads, CLIP_MAX_NORM, run.clip_norm)
+    run.optimizer.step()
+    if run.acc and not run.flat:
+        run.flat_grads.zero_()
+
+
+def _captured_epoch(run, steps: int, num_batches: int, record) -> None:
+    """The epoch's ``steps`` full batches: one replay each (next permutation slice + iteration)."""
+    if not run.in_graph:
+        run.step.bind_grads()                  # (the eager tail of the previous epoch re-pointed p.grad)
+    B, y = run.ds.batch_size, batching.targets(run.model, run.ds.static.batch)
+    for i in range(steps):
+        stepping = optimizer_steps_at(i, num_batches, run.k)
+        run.step.replay(step_optimizer=stepping)
+        if stepping and not run.in_graph:
+            _boundary_outside_graph(run, float(B))
+        record(i, i * B, run.step.loss, run.step.score, y)
+
+
+def _tail_step(run, graphs: Sequence, loss_fn: str, record, i: int, lo: int) -> None:
+    """The epoch's last, shorter batch: host-collated, through autograd, the same optimizer.  It is the epoch's last
+    iteration, so it steps (``optimizer_steps_at``)."""
+    hb = batching.collate(run.model, graphs, run.ds.device)
+    run.optimizer.zero_grad(set_to_none=True)
+    pred, y = batching.forward(run.model, hb)
+    loss, score = criterion(loss_fn, pred, y)
+    loss.backward()
+    # the window's earlier micro-batches are in the flat buffer: the tail's p.grad is added to them there (copied,
+    # without accumulation) and p.grad points at the buffer again -- what the reducer and the optimizer take
+    collect_autograd(run.step.grads, run.acc)
+    run.step.bind_grads()
+    _boundary_outside_graph(run, float(len(graphs)))
+    record(i, lo, loss.detach(), score.detach(), y)
 
 
 def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_loaders: Sequence, model,
@@ -60,7 +116,8 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
 
     ``model`` may also be the MPNN baseline (``model.mpnn.MPNN``) with ``train_graphs`` a list of ``Data``: the
     dataset is then a ``DeviceGraphDataset`` and the captured step ``step.MPNNResidentTrainStep`` (one launch + the
-    gradient fold); evaluation through ``train.eval_epoch`` takes the MPNN's forward-only launch.
+    gradient fold; ``batching`` picks both); evaluation through ``train.eval_epoch`` takes the MPNN's forward-only
+    launch.
 
     Evaluation on the device (keyword-only; the defaults leave the loop as it was): ``eval_graphs`` =
     ``(validation graphs, test graphs)`` puts the two splits into ``eval_resident.DeviceEvaluator``s built once before
@@ -86,62 +143,40 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
     G, B = len(train_graphs), int(batch_size)
     if G < B:
         raise ValueError("fewer training graphs than one batch")
-    from ..model.mpnn import MPNN
-    mpnn = isinstance(model, MPNN)      # the MPNN baseline on a list of Data: homogeneous device dataset, same loop
-    if mpnn:
-        from ..loader.device_dataset import DeviceGraphDataset
-        ds = DeviceGraphDataset(train_graphs, dev, B)
-    else:
-        ds = DeviceHeteroDataset(train_graphs, dev, B)
-    opt_cls = OPTIM_DICT[optim_cfg.optim_type]
-    kw = dict(lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay)
-    flat = flat_optimizer and optim_cfg.optim_type in ("adam", "adamW")   # optim.FlatAdam: the update as ONE launch
-    if flat:
-        from ..optim import FlatAdam
-        fkw = dict(kw, max_norm=CLIP_MAX_NORM if clip else None, zero_grads=acc)    # clip + zeroing: in its launch
-        optimizer = lambda st: FlatAdam.from_config(optim_cfg.optim_type, st.param_grads, st.grads, **fkw)  # noqa: E731
-        capturable = True
-    else:
-        try:
-            optimizer = opt_cls(model.parameters(), capturable=True, fused=True, **kw)
-        except (TypeError, RuntimeError):          # (Adagrad has neither switch: its step stays outside the graph)
-            optimizer = opt_cls(model.parameters(), **kw)
-        capturable = bool(optimizer.defaults.get("capturable", False))
-    in_graph = capturable      # the whole iteration -- backward, gradient all-reduce (if any), optimizer step -- is one graph
+    loss_fn = training_cfg.loss_fn
+    ds = batching.dataset_class(model)(train_graphs, dev, B)
+    flat = flat_optimizer and optim_cfg.optim_type in ("adam", "adamW")
+    # in_graph: the whole iteration -- backward, gradient all-reduce (if any), optimizer step -- is one graph
+    optimizer, in_graph = _make_optimizer(optim_cfg, model, flat, clip, acc)
     gen = torch.Generator(device=dev).manual_seed(seed)
     model.train()
     model.engine = "resident"
     ds.new_epoch(gen)
     # the gather of the next permutation slice is captured in front of the step: a replay = next batch + iteration
-    step = CapturedStep(model, ds.static, training_cfg.loss_fn, optimizer=optimizer if in_graph else None,
+    step = CapturedStep(model, ds.static, loss_fn, optimizer=optimizer if in_graph else None,
                         pre=ds.gather_next, reducer=reducer if in_graph else None, accumulate=acc,
                         max_norm=CLIP_MAX_NORM if clip and in_graph and not flat else None)
-    if flat:
-        optimizer = step.optimizer
-    flat_grads = step.step.grads[:step.step.P]         # every parameter gradient (the loss column excluded)
-    clip_norm = torch.zeros(1, dtype=torch.float32, device=dev) if clip and not in_graph else None
-
-    def boundary_outside_graph(weight: float):
-        """What the graph does not hold at a stepping iteration (a non-capturable optimizer; the eager tail)."""
-        if reducer is not None:
-            reducer.reduce(weight, weight * reducer.world_size)
-        if flat:
-            optimizer.step()                   # (clip and zeroing in the same launch)
-            return
-        if clip:
-            clip_grad_norm_flat(flat_grads, CLIP_MAX_NORM, clip_norm if clip_norm is not None else step.clip_norm)
-        optimizer.step()
-        if acc:
-            flat_grads.zero_()
+    clip_norm = step.clip_norm             # the pre-clip norm of the clip launch: the one in the graph, or, with the
+    if clip and not in_graph:              # optimizer outside it, _boundary_outside_graph's
+        clip_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+    run = SimpleNamespace(model=model, ds=ds, step=step, optimizer=step.optimizer if flat else optimizer,
+                          reducer=reducer, flat=flat, in_graph=in_graph, acc=acc, k=k, clip_norm=clip_norm,
+                          flat_grads=step.step.grads[:step.step.P])     # every parameter gradient (not the loss column)
 
     steps, tail = G // B, G % B
     num_batches = steps + (1 if tail else 0)
-    legacy = not acc and not clip              # (the iteration exactly as before either setting existed)
     C = ds.C
-    loss_log = torch.zeros(steps + (1 if tail else 0), dtype=torch.float32, device=dev)
+    loss_log = torch.zeros(num_batches, dtype=torch.float32, device=dev)
     want_metric = metric_fn is not None or metric is not None
     scores = torch.zeros(G, C, dtype=torch.float32, device=dev) if want_metric else None
     targets = torch.zeros(G, C, dtype=torch.float32, device=dev) if want_metric else None
+
+    def record(i: int, lo: int, loss, score, y) -> None:
+        loss_log[i].copy_(loss)
+        if want_metric:
+            scores[lo:lo + score.size(0)].copy_(score)
+            targets[lo:lo + y.size(0)].copy_(y)
+
     eval_metric_fn = metric_fn
     if metric is not None:
         from .. import metrics as _metrics
@@ -149,73 +184,22 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
         train_loss = train_metric.packed[20:24].view(torch.float32)     # beside result and flags: one read-back
         launch = _metrics.average_precision_launch if metric == "ap" else _metrics.mean_absolute_error_launch
         eval_metric_fn = _metrics.eval_ap_hip if metric == "ap" else _metrics.eval_mae_hip    # (host loaders)
-    evaluators = None
+    eval_sources = eval_loaders or []
     if eval_graphs is not None:
         from .eval_resident import DeviceEvaluator
-        evaluators = [DeviceEvaluator(g, model, training_cfg.loss_fn, B, metric) for g in eval_graphs]
-    history, best, stale = [], float("inf"), 0
+        eval_sources = [DeviceEvaluator(g, model, loss_fn, B, metric) for g in eval_graphs]
+        eval_metric_fn = metric_fn              # (the evaluators compute ``metric`` themselves)
+    stopper = _train.EarlyStopping(training_cfg, reducer, dev)
+    history = []
     for epoch in range(training_cfg.epochs):
         start = time.time()
         model.train()
         perm = ds.new_epoch(gen)               # permutation + batch counter on the device
         if epoch_orders is not None:
             epoch_orders.append(perm.cpu())
-        if not in_graph:
-            step.bind_grads()                  # (the eager tail of the previous epoch re-pointed p.grad)
-        for i in range(steps):
-            if legacy:
-                step.replay()
-                if reducer is not None and not in_graph:
-                    reducer.reduce(float(B), float(B * reducer.world_size))
-                if not in_graph:
-                    optimizer.step()
-            else:
-                stepping = optimizer_steps_at(i, num_batches, k)
-                step.replay(step_optimizer=stepping)
-                if stepping and not in_graph:
-                    boundary_outside_graph(float(B))
-            loss_log[i].copy_(step.loss)
-            if want_metric:
-                scores[i * B:(i + 1) * B].copy_(step.score)
-                targets[i * B:(i + 1) * B].copy_(ds.static.batch.y if mpnn else ds.static.batch["local"].y)
+        _captured_epoch(run, steps, num_batches, record)
         if tail:
-            tail_graphs = [train_graphs[j] for j in perm[steps * B:].tolist()]
-            if mpnn:                           # (the layered engine: gradients are on)
-                hb = Batch.from_data_list(tail_graphs).to(dev)
-                hb.x = hb.x.float()
-                optimizer.zero_grad(set_to_none=True)
-                pred = model(hb)
-                tail_y = hb.y
-            else:
-                hb = HeteroBatch.from_data_list(tail_graphs).to(dev)
-                optimizer.zero_grad(set_to_none=True)
-                pred = model(hb.x_dict, hb.edge_index_dict, hb)
-                tail_y = hb["local"].y
-            loss, score = criterion(training_cfg.loss_fn, pred, tail_y)
-            loss.backward()
-            if legacy:
-                if reducer is not None:
-                    reducer.reduce(float(tail), float(tail * reducer.world_size))
-                optimizer.step_from_autograd() if flat else optimizer.step()
-            elif flat and reducer is None:
-                optimizer.step_from_autograd(accumulate=acc)     # (p.grad added to the window's sum; clip, zero)
-            else:
-                # the last batch steps (optimizer_steps_at); the window's earlier micro-batches are in the flat
-                # buffer: the tail's p.grad is added to them there, and p.grad points at the sum again
-                with torch.no_grad():
-                    for p, g in step.grads:
-                        if p.grad is None:
-                            if not acc:
-                                g.zero_()
-                        elif p.grad.data_ptr() != g.data_ptr():
-                            g.add_(p.grad) if acc else g.copy_(p.grad)
-                step.bind_grads()
-                boundary_outside_graph(float(tail))
-            loss_log[steps].copy_(loss.detach())
-            if want_metric:
-                scores[steps * B:].copy_(score.detach())
-                targets[steps * B:].copy_(tail_y)
-            del pred, loss, score, hb
+            _tail_step(run, [train_graphs[j] for j in perm[steps * B:].tolist()], loss_fn, record, steps, steps * B)
         if metric is not None:
             launch(targets, scores, out=train_metric)
             train_loss.copy_(loss_log.mean())
@@ -228,35 +212,8 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
         history.append((mean_loss, perf))
         if logger is not None:
             logger.info(f"epoch {epoch} train loss {mean_loss:.5f} perf {perf:.5f} ({time.time() - start:.2f}s)")
-        if is_eval_epoch(epoch, training_cfg.epochs, training_cfg.eval_period):
-            sources = evaluators if evaluators is not None else eval_loaders or []
-            for split, source in zip(["Validation", "Test"], sources):
-                if evaluators is not None:
-                    vloss, vperf = source.evaluate()
-                    if metric_fn is not None:
-                        vperf = metric_fn(source.targets, source.scores)
-                    if logger is not None:
-                        logger.info(f"epoch {epoch} {split} loss {vloss:.5f} perf {vperf:.5f}")
-                else:
-                    vloss, vperf = eval_epoch(epoch, logger, source, model, training_cfg.loss_fn, eval_metric_fn, split)
-                if eval_history is not None:
-                    eval_history.append((epoch, split, vloss, vperf))
-                if split == "Validation":
-                    if reducer is not None and reducer.world_size > 1:
-                        # every rank must take the same stop decision (the next collective would hang otherwise):
-                        # the ranks agree on the mean of their validation losses
-                        import torch.distributed as dist
-                        t = torch.tensor([vloss], dtype=torch.float64, device=dev)
-                        dist.all_reduce(t, group=reducer.group)
-                        vloss = float(t.item()) / reducer.world_size
-                    if vloss < best - training_cfg.min_delta:
-                        best, stale = vloss, 0
-                    else:
-                        stale += 1
-                    if stale >= training_cfg.patience and epoch != training_cfg.epochs - 1:
-                        if logger is not None:
-                            logger.info("stopping early")
-                        ds.check()
-                        return history
+        if _train.is_eval_epoch(epoch, training_cfg.epochs, training_cfg.eval_period) and \
+                stopper.evaluate(epoch, logger, model, eval_sources, eval_metric_fn, eval_history):
+            break
     ds.check()
     return history

@@ -278,28 +278,26 @@ def test_fit_resident_accumulates_and_clips_like_train_epoch(monkeypatch):
     assert dist(model2, model) > 2e-4
 
 
-def test_fit_resident_accumulation_with_the_rccl_reducer_single_rank():
-    """k = 3 with the all-reduce captured in the boundary graph only: a world of one gives the parameters of the
-    single-process loop, bit for bit."""
+def _reducer_of_one_equals_no_reducer(cfg, num_train, epochs, port, flat_optimizer=True):
+    """fit_resident with a world-of-one RCCL reducer against the same run without a reducer: parameters bit for bit."""
     import torch.distributed as dist
-    from graph_hscn.config.config import OptimConfig, TrainingConfig
+    from graph_hscn.config.config import TrainingConfig
     from graph_hscn.data import DataLoader
     from graph_hscn.distributed import FlatGradReducer
     from graph_hscn.train.train_resident import fit_resident
-    hs = _data(40, 5, 1.0)
-    tc = TrainingConfig("hscn", "cross_entropy", "ap", epochs=3, eval_period=3, patience=50)
-    loaders = [DataLoader(hs[30:35], batch_size=5), DataLoader(hs[35:], batch_size=5)]
-    cfg = OptimConfig("adamW", batch_accumulation=3, clip_grad_norm=True, lr=0.01)
+    hs = _data(num_train + 10, 5, 1.0)
+    tc = TrainingConfig("hscn", "cross_entropy", "ap", epochs=epochs, eval_period=epochs, patience=50)
+    loaders = [DataLoader(hs[num_train:num_train + 5], batch_size=5), DataLoader(hs[num_train + 5:], batch_size=5)]
 
     def run(reducer_factory):
         m = _model()
-        fit_resident(None, cfg, tc, hs[:30], loaders, m, batch_size=8,
-                     reducer=reducer_factory(m) if reducer_factory else None)
+        fit_resident(None, cfg, tc, hs[:num_train], loaders, m, batch_size=8,
+                     reducer=reducer_factory(m) if reducer_factory else None, flat_optimizer=flat_optimizer)
         return [p.detach().clone() for p in m.parameters()]
 
     want = run(None)
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.environ["MASTER_PORT"] = "29583"
+    os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=DEV)
     try:
         got = run(lambda m: FlatGradReducer(m, single_rank_collective=True))
@@ -307,6 +305,25 @@ def test_fit_resident_accumulation_with_the_rccl_reducer_single_rank():
         dist.destroy_process_group()
     for a, b in zip(got, want):
         assert torch.equal(a, b)
+
+
+def test_fit_resident_accumulation_with_the_rccl_reducer_single_rank():
+    """k = 3 with the all-reduce captured in the boundary graph only: a world of one gives the parameters of the
+    single-process loop, bit for bit."""
+    from graph_hscn.config.config import OptimConfig
+    _reducer_of_one_equals_no_reducer(OptimConfig("adamW", batch_accumulation=3, clip_grad_norm=True, lr=0.01),
+                                      num_train=30, epochs=3, port=29583)
+
+
+@pytest.mark.parametrize("flat_optimizer", [True, False])
+def test_fit_resident_without_accumulation_or_clip_with_the_rccl_reducer_single_rank(flat_optimizer):
+    """k = 1, no clip: 20 graphs in batches of 8 are two captured batches and a 4-graph eager tail, whose gradients
+    are reduced in the flat buffer like the captured ones.  Bit for bit the run without a reducer, with the one-launch
+    AdamW and with torch's."""
+    from graph_hscn.config.config import OptimConfig
+    _reducer_of_one_equals_no_reducer(OptimConfig("adamW", batch_accumulation=1, clip_grad_norm=False, lr=0.01),
+                                      num_train=20, epochs=2, port=29584 + int(flat_optimizer),
+                                      flat_optimizer=flat_optimizer)
 
 
 def test_fit_resident_non_capturable_optimizer_accumulates_and_clips():

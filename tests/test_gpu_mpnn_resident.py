@@ -407,6 +407,29 @@ def test_device_graph_dataset_gather_is_batch_from_data_list():
     ds.check()
 
 
+def test_device_graph_dataset_self_walking_epoch_equals_explicit_gathers():
+    """gather_next() serves perm[0:B], perm[B:2B] of the epoch new_epoch() drew: bit for bit what gather() builds
+    from those slices (the homogeneous counterpart of test_gpu_device_dataset's test of the same name)."""
+    from graph_hscn.loader.device_dataset import DeviceGraphDataset
+    B = 8
+    ds = DeviceGraphDataset(_graphs("peptides_func", 20, seed=23), DEV, B)
+    with pytest.raises(RuntimeError):
+        ds.gather_next()
+    def valid(out):       # (behind the batch's own nodes / edges the static buffers hold stale data)
+        n, e = int(out.ptr32[-1]), int(out.eptr32[-1])
+        return {"x": out.x[:n].clone(), "edge_index": out.edge_index[:, :e].clone(), "ptr32": out.ptr32.clone(),
+                "eptr32": out.eptr32.clone(), "y": out.y.clone()}
+
+    perm = ds.new_epoch(torch.Generator(device=DEV).manual_seed(4)).clone()
+    got = [valid(ds.gather_next()) for _ in range(2)]
+    for i in range(2):
+        want = valid(ds.gather(perm[i * B:(i + 1) * B]))
+        for f in want:
+            assert torch.equal(got[i][f], want[f]), (i, f)
+    assert not torch.equal(got[0]["y"], got[1]["y"])            # (two batches, not one batch twice)
+    ds.check()
+
+
 def _mpnn_model(p):
     from graph_hscn.config.config import ACT_DICT, CONV_DICT
     from graph_hscn.model.mpnn import MPNN
