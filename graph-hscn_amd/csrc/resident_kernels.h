@@ -59,6 +59,12 @@ struct StepVCaps {
   static constexpr int N = 448, V = 32, EVV = V * (V + 1) / 2;
 };
 
+// capacities of the one-launch step's LOCAL program in its fixed-layout form (hscn_step_local LFIX): Peptides-sized
+// graphs (n <= 448, at most 1024 ll edges), the model's three layers, up to 16 classes; H = 16
+struct StepLCaps {
+  static constexpr int N = 448, ELL = 1024, L = 3, C = 16;
+};
+
 struct FwdArgs {
   const float* x_local;
   const float* x_virtual;

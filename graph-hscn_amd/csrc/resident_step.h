@@ -14,10 +14,15 @@
 // The per-graph loss gradient needs no other graph: d(mean loss)/d pred_g = criterion'(pred_g, y_g) / (B C); the
 // mean loss itself is one more column of the per-graph partials that k_param_reduce sums anyway.
 //
-// LDS: NB = max(L + 1, 3) buffers of n x H floats: A[0] = input features, A[l + 1] = output of layer l.  In the
-// backward the gradient G lives in A[L] (masked in place), GH = A_hat^T G in A[0] (the features are re-read from
-// HBM for layer 0's weight gradient into A[1], dead by then; L = 1 keeps them and uses A[2]).  H = 16: a 444-node
+// LDS: NB = max(L + 1, 3) buffers of n x H floats: A[0] = input features, A[l + 1] = output of layer l.
+// H = 16 (one-phase backward): G_l is written over a_l in place, and the zero-padded features stay in A[0] from the
+// prologue to layer 0's weight gradient -- nothing is read from HBM twice (the wave-private transposition scratch
+// borrows the partial-tile buffer in the first backward layer and A[L], dead by then, afterwards).  H = 32 (two-phase
+// backward): the gradient G lives in A[L] (masked in place), GH = A_hat^T G in A[0], and the features are re-read from
+// HBM for layer 0's weight gradient into A[1], dead by then; L = 1 keeps them and uses A[2].  H = 16: a 444-node
 // graph (Peptides' maximum) fits; H = 32 up to ~290 nodes; beyond that the caller takes the two-launch route.
+// A batch of 16-wave workgroups at H = 16 within StepLCaps runs the local program with this layout fixed at compile
+// time (hscn_step_local LFIX); every other batch sizes it from the arguments.
 //
 // The virtual branch (which cannot reach the prediction: DESIGN.md section 2) runs as B more workgroups of the same
 // launch (blocks B .. 2B-1, hscn_fwd_body MODE 2 over all layers).  Its layer l >= 1 reads the local activation
@@ -62,8 +67,8 @@ struct StepLayout {
   int NB;
   size_t bufw;  // words per n x H buffer
 };
-__host__ __device__ inline StepLayout step_layout(int H, int L, int C, int max_n, int max_ell) {
-  StepLayout Y;
+__host__ __device__ constexpr inline StepLayout step_layout(int H, int L, int C, int max_n, int max_ell) {
+  StepLayout Y{};
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
   auto up4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
@@ -151,7 +156,10 @@ __device__ void lin_mfma_wt_masked(const float* X, const float* Wt, float* Y, in
   }
 }
 
-template <int H, int RT, typename TS>
+// LFIX: the LDS layout and the layer count come from StepLCaps at compile time (launch_step takes this form for a batch
+// inside the caps): the layout's ~25 offsets, the buffer addresses and `wt + l * WL` are immediates instead of scalar
+// registers.  Same program, same bits; a batch outside the caps runs the run-time layout compiled in beside it.
+template <int H, int RT, typename TS, bool LFIX = false>
 __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) {
   static_assert(H <= 32, "the one-launch step uses the fused local layer (H <= 32)");
   extern __shared__ __align__(16) unsigned char smem[];
@@ -161,7 +169,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   const int n0 = A.lptr[g], n = A.lptr[g + 1] - n0;
   const int e0 = A.eptr_ll[g], ne = A.eptr_ll[g + 1] - e0;
   float* part = A.partials + (size_t)g * A.P;
-  const int F = A.F, L = A.L, C = A.C;
+  const int F = A.F, L = LFIX ? StepLCaps::L : A.L, C = A.C;
   const uint32_t ep8 = A.ready ? A.epoch[0] * 8u : 0u;
   if ((n > A.max_n) | (ne > A.max_ell) | (n < 0) | (ne < 0)) {
     if (threadIdx.x == 0 && A.flag) atomicOr(A.flag, 4);
@@ -170,7 +178,8 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     if (threadIdx.x == 0 && A.ready) __hip_atomic_store(A.ready + g, ep8 + 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
-  const StepLayout Y = step_layout(H, L, C, A.max_n, A.max_ell);
+  constexpr StepLayout YF = step_layout(H, StepLCaps::L, StepLCaps::C, StepLCaps::N, StepLCaps::ELL);
+  const StepLayout Y = LFIX ? YF : step_layout(H, L, C, A.max_n, A.max_ell);
   float* fb = reinterpret_cast<float*>(smem);
   int* ib = reinterpret_cast<int*>(smem);
   float* Abuf = fb + Y.A;
@@ -628,7 +637,6 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     int* fold_cnt = ib + Y.wsum;
     constexpr int NFW = NW < 4 ? NW : 4;            // waves that take part in a fold (threads 0 .. 255)
-    float* ght = buf(0);                            // dead after forward layer 0 (the features are re-read from HBM)
     float* Gc = aL;
     const int li = lane & 15, lj = lane >> 4;
     const int ntile = (n + 15) >> 4;
@@ -680,24 +688,19 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
         // number of positive entries of the column -- which the forward's last layer counted in its epilogue (slot 1)
         if (lane < H) bredw[wave * H + lane] = (partp + NW * H)[wave * H + lane] * gpn[lane];
       }
-      float* Xl = buf(l);                           // the layer input a_l (l >= 1); becomes G_l tile by tile
+      float* Xl = buf(l);                           // the layer input a_l (a_0: the zero-padded features); l >= 1: becomes G_l
       const float* Wl = wt + l * WL;
       float bw[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) bw[s] = l > 0 ? Wl[li * H + 4 * lj + s] : 0.f;   // W_l[4 lj + s][li]
       f32x4 accw = {0.f, 0.f, 0.f, 0.f};
-      float* sc = ght + wave * 256;
+      // the wave-private 16 x 16 transposition scratch never touches A[0] (layer 0's weight gradient reads the features
+      // there): it = 0 borrows the wave's own partial-tile slot -- empty until the wave parks accw in it below, read by
+      // nobody before the next barrier --, later iterations the wave's 256 words of A[L] (a_L is read in it = 0 only:
+      // G_L is applied on the fly; a wave owns a tile only if wave < ntile, and ntile * 256 <= bufw)
+      float* sc = (it == 0 ? red : aL) + wave * 256;
       const float* gq = Gc + 4 * lj;
-      auto xrows = [&](int rt_, float (&bx)[4]) {   // l == 0: the features, straight from HBM into the operand registers
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int row = rt_ * 16 + 4 * c + lj;
-          const bool okx = row < n && li < fin;
-          const float tx = ldf(xl_g, okx ? (size_t)(n0 + row) * fin + li : 0);
-          bx[c] = okx ? tx : 0.f;
-        }
-      };
-      auto finish = [&](int rt_, const float4 z, const float (&bx)[4]) {
+      auto finish = [&](int rt_, const float4 z) {
         const int r0 = rt_ * 16;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the previous tile's reads of the scratch are done
         *reinterpret_cast<float4*>(sc + li * 16 + 4 * lj) = z;
@@ -713,7 +716,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
         for (int c = 0; c < 4; ++c) {
           const int row = r0 + 4 * c + lj;
           const float av = sc[(4 * c + lj) * 16 + li];                       // GH[row][o = li]
-          const float bv = l == 0 ? bx[c] : (row < n ? Xl[row * H + li] : 0.f);   // a_l[row][k = li]
+          const float bv = row < n ? Xl[row * H + li] : 0.f;                 // a_l[row][k = li] (l = 0: zero past column F)
           accw = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, accw, 0, 0, 0);
         }
         if (l > 0) {
@@ -731,8 +734,6 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
         }
       };
       for (int rt = wave; rt < ntile; rt += NW) {
-        float bxA[4] = {0.f, 0.f, 0.f, 0.f};
-        if (l == 0) xrows(rt, bxA);
         const int i = rt * 16 + li;
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         if (e16) {
@@ -789,13 +790,14 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
             }
           }
         }
-        finish(rt, z, bxA);
+        finish(rt, z);
       }
       if (it > 0) {   // the folders of the previous layer's partial tiles have signed off (see above)
         while (__hip_atomic_load(fold_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < it * NFW)
           __builtin_amdgcn_s_sleep(1);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // (it = 0: the last tile's reads of the scratch in this slot are done)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[wave * 256 + (lj * 4 + r) * 16 + li] = accw[r];
       if (l > 0) {     // the wave's column sums of the G it has written (its tiles' rows): fold the four row groups
@@ -931,31 +933,33 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
 
 // grid = B (no virtual branch) or 2B: blocks [0, B) run the local program, blocks [B, 2B) the virtual branch
 // VMODE: 5 = the virtual program sizes its LDS layout from the arguments, 6 = from StepVCaps (compile time)
-template <int H, int RT, typename TS, int VMODE = 5>
+// LFIX: the local program takes its LDS layout and layer count from StepLCaps (compile time)
+template <int H, int RT, typename TS, int VMODE = 5, bool LFIX = false>
 __global__ void __launch_bounds__(RT) k_hscn_step(const StepArgs S, const FwdArgs V) {
-  if ((int)blockIdx.x < S.B) hscn_step_local<H, RT, TS>(S, blockIdx.x);
+  if ((int)blockIdx.x < S.B) hscn_step_local<H, RT, TS, LFIX>(S, blockIdx.x);
   else hscn_fwd_body<H, RT, VMODE, TS>(V, (int)blockIdx.x - S.B);
 }
-template <int H, int RT, typename TS>
+template <int H, int RT, typename TS, bool LFIX = false>
 __global__ void __launch_bounds__(RT) k_hscn_step_local(const StepArgs S) {
-  hscn_step_local<H, RT, TS>(S, blockIdx.x);
+  hscn_step_local<H, RT, TS, LFIX>(S, blockIdx.x);
 }
 
 inline size_t step_lds_bytes(int H, int L, int C, int max_n, int max_ell) {
   return step_layout(H, L, C, max_n, max_ell).total * 4;
 }
 
-template <int H, int RT, typename TS, int VMODE = 5>
+template <int H, int RT, typename TS, int VMODE = 5, bool LFIX = false>
 int launch_step_rt(const StepArgs& S, const FwdArgs* V, size_t lds, hipStream_t st) {
   if (V) {
     if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_hscn_step<H, RT, TS, VMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_hscn_step<H, RT, TS, VMODE><<<(unsigned)(2 * S.B), RT, lds, st>>>(S, *V);
+      (void)hipFuncSetAttribute((const void*)k_hscn_step<H, RT, TS, VMODE, LFIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+    k_hscn_step<H, RT, TS, VMODE, LFIX><<<(unsigned)(2 * S.B), RT, lds, st>>>(S, *V);
   } else {
     if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_hscn_step_local<H, RT, TS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute((const void*)k_hscn_step_local<H, RT, TS, LFIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds);
-    k_hscn_step_local<H, RT, TS><<<(unsigned)S.B, RT, lds, st>>>(S);
+    k_hscn_step_local<H, RT, TS, LFIX><<<(unsigned)S.B, RT, lds, st>>>(S);
   }
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
@@ -965,6 +969,12 @@ template <int H, typename TS>
 int launch_step(StepArgs& S, FwdArgs* V, hipStream_t st) {
   size_t lds = step_lds_bytes(H, S.L, S.C, S.max_n, S.max_ell);
   if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
+  // 16-wave workgroups at H = 16 on a batch within StepLCaps: the local program with its LDS layout and layer count
+  // fixed at compile time (hscn_step_local LFIX); anything else keeps the run-time layout
+  constexpr size_t lds_lfix = step_layout(H, StepLCaps::L, StepLCaps::C, StepLCaps::N, StepLCaps::ELL).total * 4;
+  static_assert(H != 16 || lds_lfix <= 160 * 1024, "the local program's fixed layout must fit a CU's LDS");
+  const bool local_fixed = H == 16 && S.max_n > 64 && S.max_n <= StepLCaps::N && S.max_ell <= StepLCaps::ELL &&
+                           S.L == StepLCaps::L && S.C <= StepLCaps::C;
   bool fixed_layout = false;
   if (V) {
     V->spec = 1; V->exp = 0; V->exp_dinv = 0;
@@ -988,6 +998,11 @@ int launch_step(StepArgs& S, FwdArgs* V, hipStream_t st) {
     }
   }
   if (S.max_n <= 64) return launch_step_rt<H, 256, TS>(S, V, lds, st);
+  if constexpr (H == 16) {
+    // the headline shape runs ONE fully specialised instantiation: both programs' layouts at compile time
+    if (local_fixed && (fixed_layout || !V))
+      return launch_step_rt<H, 1024, TS, 6, true>(S, V, lds > lds_lfix ? lds : lds_lfix, st);
+  }
   if (fixed_layout) return launch_step_rt<H, 1024, TS, 6>(S, V, lds, st);
   return launch_step_rt<H, 1024, TS>(S, V, lds, st);
 }

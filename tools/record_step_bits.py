@@ -1,0 +1,31 @@
+#!/usr/bin/env python3
+"""Record the bit-for-bit fixtures of tests/test_gpu_step_layouts.py from the library that is loaded:
+
+  [HSCN_LIB=<libhscn.so of the commit to record>] python tools/record_step_bits.py OUTDIR
+
+writes OUTDIR/step_bits_<case>.npz (prediction, score, flat gradients + loss, final virtual features of the one-launch
+step on the test's own inputs).  Run it on the build whose results a change must reproduce, then copy the files to
+tests/golden/."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "graph-hscn_amd")]
+import numpy as np
+
+from tests import test_gpu_step_layouts as T
+
+
+def main():
+    out = sys.argv[1]
+    os.makedirs(out, exist_ok=True)
+    for case in T.CASES:
+        model, d, _ = T.build_case(case)
+        one = T.run_one_launch(model, d)
+        bits = T.step_bits(one)
+        np.savez_compressed(os.path.join(out, f"step_bits_{T.case_id(case)}.npz"), **bits)
+        print(T.case_id(case), {k: v.shape for k, v in bits.items()}, flush=True)
+
+
+if __name__ == "__main__":
+    main()
