@@ -26,7 +26,7 @@
 
 namespace {
 
-constexpr int ADAM_MAXSEG = 32;   // the tables travel in the kernel arguments: no dependent load in front of the update
+constexpr int ADAM_MAXSEG = 64;   // the tables travel in the kernel arguments: no dependent load in front of the update
 
 struct AdamArgs {
   float* params[ADAM_MAXSEG];   // the parameter tensors, in the order of the flat buffers

@@ -146,6 +146,15 @@ _SIGNATURES = {
     "hscn_lap_eig_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "hscn_lap_eig_stats": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, P, P, P, P,
                                    c_size_t, P]),
+    # HSCN with the virtual -> local relation as one launch (csrc/resident_vl.hip; additive to ABI 23)
+    "hscn_vl_supported": (c_int, [c_int] * 8),
+    "hscn_vl_param_count": (c_int64, [c_int] * 4),
+    "hscn_vl_train_step": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
+                                   c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
+                                   P, c_int, c_float, P, P, P, P, P, P, c_int, P]),
+    "hscn_vl_forward": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
+                                c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
+                                P, c_int, c_float, P, P, P, P, P, P, P]),
 }
 
 class HipExtensionMissing(RuntimeError):

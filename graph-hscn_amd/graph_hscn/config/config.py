@@ -94,6 +94,9 @@ class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent
     num_clusters: int = NUM_CLUSTERS
     cluster_epochs: int = CLUSTER_EPOCHS
     mp_units: list = field(default_factory=lambda: [16])
+    # extension: the ("virtual", "to", "local") relation the reference never wired up (None: the reference's model,
+    # whose virtual branch does not reach the prediction; "GAT": model/hscn.py HSCN(vl_conv="GAT"))
+    vl_conv_type: Optional[str] = None
 
     def __post_init__(self):
         for v in (self.num_layers, self.hidden_channels):

@@ -79,7 +79,11 @@ def meta_from_batch(batch, device) -> Optional[ResidentMeta]:
     return meta
 
 
-def supported(F: int, H: int, L: int, C: int, meta: ResidentMeta, dtype=torch.float32) -> bool:
+def supported(F: int, H: int, L: int, C: int, meta: ResidentMeta, dtype=torch.float32, model=None) -> bool:
+    """``model`` (optional): refused with a RuntimeError that names the relation when it carries a convolution the
+    hscn_resident_* launches do not evaluate (``HSCN(vl_conv="GAT")``) -- they would silently drop it."""
+    if model is not None:
+        model._refuse_vl("the graph-resident engine (hscn_resident_*)")
     if dtype == torch.float16 and H > 32:
         return False                 # half storage: H in {16, 32} (csrc/resident_f16.hip)
     if dtype not in (torch.float32, torch.float16):

@@ -34,6 +34,8 @@ from .. import engine as _engine
 LL = ("local", "to", "local")
 VV = ("virtual", "to", "virtual")
 LV = ("local", "to", "virtual")
+VL = ("virtual", "to", "local")      # extension (HSCN(vl_conv="GAT")): the lv edge list reversed
+VL_NAME = "('virtual', 'to', 'local')"
 
 
 def _act_name(act) -> Optional[str]:
@@ -248,21 +250,31 @@ def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None) 
 
 class HSCN(nn.Module):
     def __init__(self, lv_conv: str, ll_conv: str, vv_conv: str, activation: Callable, num_features: int,
-                 hidden_channels: int, num_classes: int, num_layers: int) -> None:
+                 hidden_channels: int, num_classes: int, num_layers: int, vl_conv: Optional[str] = None) -> None:
+        """``vl_conv`` (extension; the default ``None`` is the reference's model, bit for bit): "GAT" gives every
+        layer a fourth convolution on the relation ("virtual", "to", "local") -- the lv edge list reversed, derived in
+        ``forward`` when the batch does not carry it -- so that the clusters act as long-range shortcuts and the
+        virtual branch reaches the prediction.  Every local node has exactly one such in-edge, so the attention weight
+        is exactly 1 and the relation computes ``lin_src(x_virtual)[cluster(i)] + bias``: its ``lin_dst``,
+        ``att_src`` and ``att_dst`` receive exactly zero gradients (zero, not ``None``).  The last layer's lv and vv
+        convolutions still do not reach ``pred`` (``grad`` stays ``None``).  Per type the relation outputs are summed
+        ``local = ll + vl`` and ``virtual = vv + lv``, then the reference's hard ReLU."""
         super().__init__()
+        if vl_conv is not None and vl_conv != "GAT":
+            raise ValueError(f"vl_conv must be None or 'GAT', not {vl_conv!r} (a bipartite GCNConv does not exist)")
+        self.vl_conv = vl_conv
         self.activation = activation
         self.convs = nn.ModuleList()
         for layer in range(num_layers):
             fin = num_features if layer == 0 else hidden_channels
-            conv = HeteroConv(
-                {
-                    LV: build_conv_relation(lv_conv, hidden_channels, fin),
-                    LL: build_conv_relation(ll_conv, hidden_channels, fin),
-                    VV: build_conv_relation(vv_conv, hidden_channels, fin),
-                },
-                aggr="sum",
-            )
-            self.convs.append(conv)
+            rels = {
+                LV: build_conv_relation(lv_conv, hidden_channels, fin),
+                LL: build_conv_relation(ll_conv, hidden_channels, fin),
+                VV: build_conv_relation(vv_conv, hidden_channels, fin),
+            }
+            if vl_conv is not None:
+                rels[VL] = build_conv_relation(vl_conv, hidden_channels, fin)
+            self.convs.append(HeteroConv(rels, aggr="sum"))
         self.lin_1 = Linear(hidden_channels, hidden_channels)
         self.lin_2 = Linear(hidden_channels, num_classes)
         # execution engine: "auto" picks the graph-resident fused kernels when the batch
@@ -275,8 +287,20 @@ class HSCN(nn.Module):
         self.last_virtual: Optional[Tensor] = None
         self.last_engine: Optional[str] = None
 
+    def _refuse_vl(self, what: str) -> None:
+        """The hscn_resident_* launches know three relations: they must refuse a model with a fourth, never drop it."""
+        extra = [k for conv in self.convs for k in conv.convs if k not in ("__".join(LV), "__".join(LL), "__".join(VV))]
+        if self.vl_conv is not None or extra:
+            raise RuntimeError(f"{what} does not take a model with the relation {VL_NAME} (vl_conv={self.vl_conv!r}): "
+                               "its launches evaluate ll, vv and lv only; this model's one-launch step is "
+                               "step.VLResidentTrainStep, its forward-only launch hscn_vl_forward")
+
     def _resident_plan(self, x_dict, edge_index_dict, batch):
         if self.engine == "layered":
+            return None
+        if self.vl_conv is not None:
+            if self.engine == "resident":
+                self._refuse_vl("the graph-resident engine (hscn_resident_*)")
             return None
         name = _act_name(self.activation)
         ok = (name in ACT_DICT and set(edge_index_dict) == {LL, VV, LV} and "local" in x_dict
@@ -301,6 +325,7 @@ class HSCN(nn.Module):
         cached = getattr(self, "_resident_cache", None)
         if cached is not None and cached[0] == key:
             return cached[1]
+        self._refuse_vl("the graph-resident engine (hscn_resident_*)")
         params = []
         for conv in self.convs:
             c = conv.convs
@@ -330,12 +355,133 @@ class HSCN(nn.Module):
             out._hscn_score = (score, out._version)
         return out
 
+    # ---- the model with the virtual -> local relation (vl_conv="GAT") ----
+    def vl_params(self):
+        """Parameters in the order the hscn_vl_* launches take them: per layer {W_ll, b_ll, W_vv, b_vv, lv: W_src,
+        W_dst, att_src, att_dst, b, vl: the same five}, then W1, b1, W2, b2."""
+        out = []
+        for conv in self.convs:
+            c = conv.convs
+            ll, vv, lv, vl = (c["__".join(k)] for k in (LL, VV, LV, VL))
+            out += [ll.lin.weight, ll.bias, vv.lin.weight, vv.bias]
+            for gat in (lv, vl):
+                out += [gat.lin_src.weight, gat.lin_dst.weight, gat.att_src, gat.att_dst, gat.bias]
+        return out + [self.lin_1.weight, self.lin_1.bias, self.lin_2.weight, self.lin_2.bias]
+
+    def vl_grad_order(self):
+        """The parameters in the order of the launch's flat gradient buffer: ``vl_params()`` with the last layer's
+        dead part (``vl_dead_params()``) moved behind the head, so that the live gradients tile the buffer's front."""
+        dead = {id(p) for p in self.vl_dead_params()}
+        allp = self.vl_params()
+        return [p for p in allp if id(p) not in dead] + [p for p in allp if id(p) in dead]
+
+    def vl_dead_params(self):
+        """The parameters the prediction does not depend on (autograd leaves their ``grad`` at None): the last layer's
+        vv and lv convolutions."""
+        vv, lv = (self.convs[-1].convs["__".join(k)] for k in (VV, LV))
+        return [vv.lin.weight, vv.bias, lv.lin_src.weight, lv.lin_dst.weight, lv.att_src, lv.att_dst, lv.bias]
+
+    def resident_reason(self, batch=None, x_dict=None) -> Optional[str]:
+        """Why this model (and ``batch``, if given) cannot take the one-launch hscn_vl_* kernels, or None when it
+        can.  ``hscn_vl_supported`` is the single source of truth for the sizes."""
+        from .._hip import lib
+        if self.vl_conv is None:
+            return f"the model has no {VL_NAME} relation (the hscn_resident_* launches serve the reference's model)"
+        if _act_name(self.activation) not in ACT_DICT:
+            return f"head activation {self.activation!r} (relu, elu, identity and tanh are supported)"
+        slopes = set()
+        for conv in self.convs:
+            c = conv.convs
+            if sorted(c) != sorted("__".join(k) for k in (LL, VV, LV, VL)):
+                return "relations other than ll, vv, lv and vl"
+            ll, vv, lv, vl = (c["__".join(k)] for k in (LL, VV, LV, VL))
+            if not (isinstance(ll, GCNConv) and isinstance(vv, GCNConv) and isinstance(lv, GATConv)
+                    and isinstance(vl, GATConv)) or ll.add_self_loops or vv.add_self_loops or lv.add_self_loops \
+                    or vl.add_self_loops or any(m.bias is None for m in (ll, vv, lv, vl)):
+                return "convolutions other than GCN (ll, vv) / GAT (lv, vl) without self loops, with bias"
+            slopes.add(float(lv.negative_slope))
+        if len(slopes) != 1:
+            return "the lv convolutions differ in negative_slope"
+        H, C, L = self.lin_1.out_channels, self.lin_2.out_channels, len(self.convs)
+        F = int(self.convs[0].convs["__".join(LL)].lin.weight.shape[1])
+        env = "H in {16, 32}, F <= H, C <= min(H, 16), 1 <= L <= 8"
+        if batch is None:
+            return None if lib().hscn_vl_supported(F, H, L, C, 0, 0, 0, 0) else \
+                f"widths F={F}, H={H}, C={C}, L={L} outside the kernel's envelope ({env})"
+        x_dict = x_dict if x_dict is not None else batch.x_dict
+        xl, xv = x_dict.get("local"), x_dict.get("virtual")
+        if xl is None or xv is None or not xl.is_cuda or xl.dtype != torch.float32 or xv.dtype != torch.float32 \
+                or xl.dim() != 2 or xl.size(1) != F or xv.size(1) != F:
+            return "node features must be float32 [N, F] / [V, F] tensors on the HIP device"
+        meta = _engine.meta_from_batch(batch, xl.device)
+        if meta is None:
+            return "the batch carries no per-graph segment tables (graph_hscn.data.HeteroBatch builds them)"
+        y = batch["local"].y if "y" in batch["local"] else None
+        if y is not None and (y.dim() != 2 or y.size(1) != C):
+            return "class-index (multiclass) targets: the fused loss row takes [B, C] multilabel / regression targets"
+        if not lib().hscn_vl_supported(F, H, L, C, meta.max_n, meta.max_v, meta.max_ell, meta.max_evv):
+            return (f"widths F={F}, H={H}, C={C}, L={L} or the largest graph ({meta.max_n} nodes, {meta.max_v} clusters, "
+                    f"{meta.max_ell} / {meta.max_evv} edges) outside the kernel's envelope ({env}, 160 KB of LDS)")
+        return None
+
+    def supported(self, batch=None) -> bool:
+        """Whether the one-launch hscn_vl_* kernels take this model (and ``batch``)."""
+        return self.resident_reason(batch) is None
+
+    def _forward_vl_resident(self, x_dict, edge_index_dict, batch) -> Tensor:
+        from .._hip import call, ptr, stream
+        xl, xv = x_dict["local"].contiguous(), x_dict["virtual"].contiguous()
+        dev = xl.device
+        meta = _engine.meta_from_batch(batch, dev)
+        ei = [edge_index_dict[k].contiguous() for k in (LL, VV, LV)]
+        params = [p.detach().contiguous() for p in self.vl_params()]
+        L = len(self.convs)
+        H, C = self.lin_1.out_channels, self.lin_2.out_channels
+        pred = torch.empty(meta.num_graphs, C, dtype=torch.float32, device=dev)
+        xv_out = torch.empty(max(xv.size(0), 1), H, dtype=torch.float32, device=dev) if self.keep_virtual else None
+        slope = float(self.convs[0].convs["__".join(LV)].negative_slope)
+        call("hscn_vl_forward", ptr(xl), ptr(xv), ptr(ei[0]), ei[0].size(1), ptr(ei[1]), ei[1].size(1), ptr(ei[2]),
+             ei[2].size(1), ptr(meta.lptr), ptr(meta.vptr), ptr(meta.eptr_ll), ptr(meta.eptr_vv), ptr(meta.eptr_lv),
+             xl.size(0), xv.size(0), meta.num_graphs, xl.size(1), H, L, C, _engine.ACT[_act_name(self.activation)], slope,
+             _engine._ptr_table(params[:14 * L]), *[ptr(p) for p in params[14 * L:]], meta.max_n, meta.max_v,
+             meta.max_ell, meta.max_evv, None, 0, 0.0, ptr(pred), None, None, None, ptr(xv_out), ptr(meta.flag), stream())
+        if xv_out is not None:
+            self.last_virtual = xv_out
+        return pred
+
+    def _forward_vl(self, x_dict, edge_index_dict, batch) -> Tensor:
+        if self.engine not in ("layered", "auto", "resident"):
+            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if not self.compute_virtual:
+            raise ValueError(f"compute_virtual=False is meaningless with the relation {VL_NAME}: the local update "
+                             "reads the virtual features of every layer")
+        if VL not in edge_index_dict:        # the data layer does not change: vl is lv reversed, appended last
+            edge_index_dict = dict(edge_index_dict)
+            edge_index_dict[VL] = edge_index_dict[LV].flip(0)
+        if self.engine != "layered":
+            if torch.is_grad_enabled():
+                if self.engine == "resident":
+                    self._refuse_vl("engine='resident' with gradients on (the hscn_resident_* autograd launches)")
+            else:
+                reason = self.resident_reason(batch, x_dict)
+                if reason is None:
+                    self.last_engine = "resident"
+                    return self._forward_vl_resident(x_dict, edge_index_dict, batch)
+                if self.engine == "resident":
+                    raise RuntimeError(f"engine='resident' requested but the model / batch does not qualify: {reason}")
+        return self._forward_layered(x_dict, edge_index_dict, batch)
+
     def forward(self, x_dict: Dict[str, Tensor], edge_index_dict: Dict[Tuple[str, str, str], Tensor],
                 batch) -> Tensor:
+        if self.vl_conv is not None:
+            return self._forward_vl(x_dict, edge_index_dict, batch)
         plan = self._resident_plan(x_dict, edge_index_dict, batch)
         if plan is not None:
             self.last_engine = "resident"
             return self._forward_resident(x_dict, edge_index_dict, *plan)
+        return self._forward_layered(x_dict, edge_index_dict, batch)
+
+    def _forward_layered(self, x_dict, edge_index_dict, batch) -> Tensor:
         self.last_engine = "layered"
         if x_dict["local"].dtype == torch.float16:
             raise RuntimeError("half-precision feature storage runs on the graph-resident engine only (H in {16, 32}, "
@@ -365,4 +511,5 @@ def build_hscn(model_cfg: HSCNConfig, num_features: int, num_classes: int) -> HS
         model_cfg.hidden_channels,
         num_classes,
         model_cfg.num_layers,
+        getattr(model_cfg, "vl_conv_type", None),
     )

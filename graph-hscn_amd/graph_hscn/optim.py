@@ -37,7 +37,7 @@ class FlatAdam:
     ``ResidentTrainStep.param_grads`` / ``ScnTrainStep.param_grads`` hold.  ``decoupled=True`` is ``AdamW``.
     ``amsgrad`` / ``maximize`` are not offered (the reference never sets them)."""
 
-    MAX_PARAMS = 32
+    MAX_PARAMS = 64
 
     def __init__(self, param_grads: Sequence[Tuple[Tensor, Tensor]], flat_grads: Tensor, lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,

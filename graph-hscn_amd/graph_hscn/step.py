@@ -81,6 +81,7 @@ class ResidentTrainStep(_FlatGradStep):
         from .model.hscn import HSCN, _act_name
         if not isinstance(model, HSCN):
             raise TypeError("ResidentTrainStep drives graph_hscn.model.hscn.HSCN")
+        model._refuse_vl("ResidentTrainStep (hscn_resident_*)")
         x_dict, ei_dict = batch.x_dict, batch.edge_index_dict
         dev = x_dict["local"].device
         if dev.type != "cuda":
@@ -573,3 +574,92 @@ class MPNNResidentTrainStep(_FlatGradStep):
         if f:
             raise RuntimeError(f"the one-launch MPNN step flagged its batch (code {f}: 1 = an edge with an end outside "
                                "its graph, 2 = a graph beyond the batch's node / edge maxima)")
+
+
+class VLResidentTrainStep(_FlatGradStep):
+    """``for p: p.grad = None; pred = model(x_dict, edge_index_dict, batch); loss, score = criterion(loss_fn, pred,
+    batch["local"].y); loss.backward()`` for ``HSCN(vl_conv="GAT")`` -- the model whose virtual branch reaches the
+    prediction through the ("virtual", "to", "local") relation -- as ONE launch plus the gradient fold (include/hscn.h:
+    hscn_vl_train_step), on buffers allocated once: ``MPNNResidentTrainStep``'s outward contract.
+
+    Outputs refreshed by ``run()``: ``pred`` [B,C], ``score`` [B,C] (sigmoid), ``loss`` (0-dim), ``grads`` (flat: the
+    gradients of ``model.vl_grad_order()`` in that order, then the loss).  ``param_grads`` covers exactly the parameters
+    autograd gives a gradient: vl's ``lin_dst`` / ``att_src`` / ``att_dst`` are in it (exact zeros), the last layer's
+    lv and vv convolutions are not (their columns of ``grads`` are zeros; ``bind_grads()`` leaves their ``.grad`` at
+    None).  ``accumulate``: the fold ADDS to ``grads``; ``loss`` is the last run's.
+
+    The batch may be a static fixed-capacity batch: tensor shapes are capacities then, the kernel reads the real
+    per-graph ranges from the segment tables."""
+
+    def __init__(self, model, batch, loss_fn: str, target: Optional[Tensor] = None, accumulate: bool = False):
+        from .model.hscn import HSCN, _act_name
+        if not isinstance(model, HSCN):
+            raise TypeError("VLResidentTrainStep drives graph_hscn.model.hscn.HSCN")
+        x_dict, ei_dict = batch.x_dict, batch.edge_index_dict
+        reason = model.resident_reason(batch, x_dict)
+        if reason is not None:
+            raise RuntimeError(f"the one-launch vl step does not take this model / batch: {reason}")
+        dev = x_dict["local"].device
+        self.model, self.batch, self.loss_fn = model, batch, loss_fn
+        self.meta = meta = _engine.meta_from_batch(batch, dev)
+        self.x_local = x_dict["local"].contiguous()
+        self.x_virtual = x_dict["virtual"].contiguous()
+        self.ei = [ei_dict[k].contiguous() for k in (LL, VV, LV)]
+        mparams = model.vl_params()
+        L = len(model.convs)
+        H, C = model.lin_1.out_channels, model.lin_2.out_channels
+        N, F = self.x_local.shape
+        V, B = int(self.x_virtual.shape[0]), meta.num_graphs
+        self.dims = (N, V, F, H, L, C, B)
+        y = target if target is not None else batch["local"].y
+        if y.dtype != torch.float32 or not y.is_contiguous() or y.device != dev:
+            raise TypeError("targets must be a contiguous float32 tensor on the batch's device")
+        self.kind = _loss_kind(loss_fn, (B, C), y)
+        self.target = y
+        self.head_act = _engine.ACT[_act_name(model.activation)]
+        self.slope = float(model.convs[0].convs["__".join(LV)].negative_slope)
+        self.accumulate = bool(accumulate)
+        self._params = [p.contiguous() for p in mparams]
+        self._table = _engine._ptr_table(self._params[:14 * L])
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.pred = torch.empty(B, C, **f32)
+        self.score = torch.empty(B, C, **f32)
+        P = int(_hip.lib().hscn_vl_param_count(F, H, L, C))
+        self.P = P
+        self.partials = torch.empty(B, P + 1, **f32)
+        self.grads = torch.zeros(P + 1, **f32)
+        self.loss = self.grads[P:P + 1].view(())
+        # the local activations x_1 .. x_{L-1} the backward reads again
+        self.workspace = torch.empty(max((L - 1) * N * H, 1), **f32)
+        self.inv_count = 1.0 / float(B * C)
+        dead = {id(p) for p in model.vl_dead_params()}
+        order = model.vl_grad_order()
+        views = _engine.grad_views(self.grads, [p.shape for p in order], P)
+        self.param_grads = [(p, g) for p, g in zip(order, views) if id(p) not in dead]
+
+    @property
+    def flag(self) -> Tensor:
+        return self.meta.flag
+
+    def run(self) -> Tensor:
+        """Issue the step on the current stream; returns ``loss`` (valid once the stream has run)."""
+        N, V, F, H, L, C, B = self.dims
+        m, ei = self.meta, self.ei
+        call("hscn_vl_train_step", ptr(self.x_local), ptr(self.x_virtual), ptr(ei[0]), ei[0].size(1), ptr(ei[1]),
+             ei[1].size(1), ptr(ei[2]), ei[2].size(1), ptr(m.lptr), ptr(m.vptr), ptr(m.eptr_ll), ptr(m.eptr_vv),
+             ptr(m.eptr_lv), N, V, B, F, H, L, C, self.head_act, self.slope, self._table,
+             *[ptr(p) for p in self._params[14 * L:]], m.max_n, m.max_v, m.max_ell, m.max_evv, ptr(self.target),
+             int(self.kind), self.inv_count, ptr(self.pred), ptr(self.score), ptr(self.partials), ptr(self.grads),
+             ptr(self.workspace), ptr(m.flag), int(self.accumulate), stream())
+        return self.loss
+
+    def check(self) -> None:
+        """Synchronising validity check of the launches issued so far."""
+        f = int(self.meta.flag.item())
+        if f & 2:
+            raise IndexError("an edge connects nodes of different graphs: the batch is not block-diagonal")
+        if f & 4:
+            raise ValueError("a graph exceeds the sizes the one-launch vl step was configured for")
+        if f & 16:
+            raise ValueError("a local node has more than one local -> virtual edge (the virtual -> local relation "
+                             "reads one cluster per node)")

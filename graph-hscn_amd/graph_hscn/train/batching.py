@@ -6,6 +6,7 @@ from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple
 
+import torch
 from torch import Tensor
 
 from ..data import Batch, HeteroBatch
@@ -26,6 +27,13 @@ def targets(model, batch) -> Optional[Tensor]:
 def forward(model, batch) -> Tuple[Tensor, Tensor]:
     """``(pred, targets)`` of ``model`` on a batch that is on the model's device."""
     if is_hetero(model):
+        if getattr(model, "vl_conv", None) is not None and torch.is_grad_enabled() and model.engine == "resident":
+            # the eager tail of a device loop: with gradients on this model runs through the layered operators
+            model.engine = "auto"
+            try:
+                return model(batch.x_dict, batch.edge_index_dict, batch), batch["local"].y
+            finally:
+                model.engine = "resident"
         return model(batch.x_dict, batch.edge_index_dict, batch), batch["local"].y
     return model(batch), batch.y
 
@@ -51,13 +59,15 @@ def dataset_class(model):
 
 def resident_step(model, batch, loss_fn: str, one_launch: Optional[bool] = None, structure=None,
                   accumulate: bool = False):
-    """The resident training step of ``model`` on a static batch (``step.ResidentTrainStep``, or the MPNN baseline's
-    one launch, which has neither a launch pair nor a structure to load)."""
-    from ..step import MPNNResidentTrainStep, ResidentTrainStep
+    """The resident training step of ``model`` on a static batch (``step.ResidentTrainStep``; the MPNN baseline's or
+    the vl model's one launch, which have neither a launch pair nor a structure to load)."""
+    from ..step import MPNNResidentTrainStep, ResidentTrainStep, VLResidentTrainStep
     if targets(model, batch) is None:
         raise ValueError("the static batch carries no targets")
     if not is_hetero(model):
         return MPNNResidentTrainStep(model, batch, loss_fn, accumulate=accumulate)
+    if getattr(model, "vl_conv", None) is not None:
+        return VLResidentTrainStep(model, batch, loss_fn, accumulate=accumulate)
     try:
         return ResidentTrainStep(model, batch, loss_fn, one_launch=one_launch, structure=structure,
                                  accumulate=accumulate)

@@ -773,7 +773,7 @@ int hscn_scn_resident_train_epoch(const void* x, const int32_t* nptr, const int3
  * step_dev: device float counter (incremented here); beta_pows_dev: device double [2] = {1, 1} before the first step
  * (beta1^t, beta2^t, kept as running products); lr_dev: device double (a scheduler may rewrite it);
  * decoupled != 0: AdamW's p *= 1 - lr * weight_decay instead of Adam's g += weight_decay * p.
- * nseg <= 32; one workgroup (the model family has a few thousand parameters in ~10 tensors).
+ * nseg <= 64; one workgroup (the model family has a few thousand parameters in ~10 tensors).
  * ------------------------------------------------------------------------- */
 int hscn_adam_step(float* const* params_host, const int32_t* seg_off_host, int nseg, const float* grads,
                    float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
@@ -1002,6 +1002,58 @@ int hscn_lap_eig_stats(const int64_t* edge_index, int64_t E, const int32_t* nptr
                        int64_t B, int max_n, int lap_norm, int is_undirected, int max_freqs, int eigvec_norm,
                        float* eigvals, float* eigvecs, int32_t* flag, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * HSCN with the opt-in virtual -> local relation (graph_hscn.model.hscn.HSCN(vl_conv="GAT"): a fourth HeteroConv
+ * entry the reference never wired up, with which the virtual branch reaches the prediction) as ONE training-step
+ * launch, one workgroup per graph, plus the gradient fold (csrc/resident_vl.hip).  Purely additive to ABI 23.
+ *   layer:  x_l' = relu((A_ll (x_l W_ll^T) + b_ll) + ((x_v W_vl,src^T)[c(i)] + b_vl))
+ *           x_v' = relu((A_vv (x_v W_vv^T) + b_vv) + (sum_{i in v} alpha_i (x_l W_lv,src^T)_i + b_lv))
+ *   A_* = GCN normalisation WITHOUT self loops over the edge list as given (in-degree; in-degree 0: the bias only);
+ *   alpha = GATConv's segment softmax of leaky_relu(a_src[i] + a_dst[v], slope) over the members of cluster v;
+ *   c(i) = the target of local node i's one local -> virtual edge (the virtual -> local edge list is that list
+ *   reversed, so its attention weight is exactly 1 and its lin_dst / att_src / att_dst get exactly zero gradients);
+ *   then the mean pool over local nodes, lin_1 -> head_act -> lin_2 and the loss row (loss_kind 0 = BCE with logits,
+ *   1 = L1; inv_count = 1 / (B C)).
+ *   x_local [N,F], x_virtual [V,F] f32; ei_* int64 [2,E_*] batch numbering; graph g owns local nodes
+ *   [lptr[g], lptr[g+1]), virtual nodes [vptr[g], ...) and the edge ranges eptr_*[g] .. eptr_*[g+1] (int32, B + 1).
+ *   layer_params_host: HOST array of L x 14 device pointers {W_ll, b_ll, W_vv, b_vv, lv: W_src, W_dst, att_src,
+ *   att_dst, b, vl: W_src, W_dst, att_src, att_dst, b} (W [H,fin], fin = F for layer 0 else H); W1, b1, W2, b2.
+ *   partials [B, P+1]; grads [P+1] = dL/d params, grads[P] = the mean loss (P = hscn_vl_param_count: every
+ *   parameter).  Column order: layers 0 .. L-2 in pointer order, the last layer's {W_ll, b_ll, vl: five}, W1, b1, W2,
+ *   b2, then the last layer's {W_vv, b_vv, lv: five} -- those do not reach the prediction, their columns are zeros,
+ *   and the live gradients tile the front of the buffer.  workspace: (L-1) N H floats (the local activations the backward reads again).
+ *   accumulate != 0: the fold ADDS every parameter column to grads (grads[P] is still the loss of this call).
+ *   flag: bit 2 = an edge with an end outside its graph (dropped), bit 4 = a graph beyond max_n / max_v / max_ell /
+ *   max_evv (or more local -> virtual edges than max_n) or the arrays (its rows are zeros), bit 16 = a local node with
+ *   more than one local -> virtual edge.  Fixed summation orders, no float atomics: the same input gives the same bits.
+ *   B = 0 launches nothing (0); a NULL target, partials or grads is HSCN_E_BADARG.
+ * hscn_vl_forward: the forward alone: pred, score (optional), with a target the per-graph loss-term sums loss_rows
+ *   [B] and, if loss != NULL, the mean loss; xv_out [V,H] (optional): the final virtual features (without it the last
+ *   layer's virtual update is skipped).
+ * hscn_vl_supported: H in {16, 32}, 1 <= F <= H, C <= min(H, 16), 1 <= L <= 8 and a layout of the largest graph within
+ *   160 KB of LDS (H = 16, L = 3: Peptides' 444 nodes with 16 clusters).
+ * ------------------------------------------------------------------------- */
+int hscn_vl_supported(int F, int H, int L, int C, int max_n, int max_v, int max_ell, int max_evv);
+int64_t hscn_vl_param_count(int F, int H, int L, int C);
+int hscn_vl_train_step(const float* x_local, const float* x_virtual, const int64_t* ei_ll, int64_t E_ll,
+                       const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv, const int32_t* lptr,
+                       const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv, const int32_t* eptr_lv,
+                       int64_t N, int64_t V, int64_t B, int F, int H, int L, int C, int head_act, float slope,
+                       const void* const* layer_params_host /* L x 14 */, const float* W1, const float* b1,
+                       const float* W2, const float* b2, int max_n, int max_v, int max_ell, int max_evv,
+                       const float* target, int loss_kind, float inv_count, float* pred, float* score /*or NULL*/,
+                       float* partials /*[B,P+1]*/, float* grads /*[P+1]*/, float* workspace /*[(L-1) N H]*/,
+                       int32_t* flag, int accumulate, void* stream);
+int hscn_vl_forward(const float* x_local, const float* x_virtual, const int64_t* ei_ll, int64_t E_ll,
+                    const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv, const int32_t* lptr,
+                    const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv, const int32_t* eptr_lv,
+                    int64_t N, int64_t V, int64_t B, int F, int H, int L, int C, int head_act, float slope,
+                    const void* const* layer_params_host /* L x 14 */, const float* W1, const float* b1,
+                    const float* W2, const float* b2, int max_n, int max_v, int max_ell, int max_evv,
+                    const float* target /*or NULL*/, int loss_kind, float inv_count, float* pred,
+                    float* score /*or NULL*/, float* loss_rows /*[B] or NULL*/, float* loss /*[1] or NULL*/,
+                    float* xv_out /*[V,H] or NULL*/, int32_t* flag, void* stream);
 
 #ifdef __cplusplus
 }
