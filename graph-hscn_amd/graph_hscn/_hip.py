@@ -152,10 +152,22 @@ _SIGNATURES = {
     "hscn_vl_train_step": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
                                    c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
                                    P, c_int, c_float, P, P, P, P, P, P, c_int, P]),
+    # schedules inside the optimizer launch and the one-launch Adagrad (csrc/optim.hip; additive to ABI 23);
+    # `sched`: ctypes.byref(LRScheduleC) or None
+    "hscn_adam_step_sched": (c_int, [P, P, c_int, P, P, P, c_int64, P, P, P, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, c_int, c_float, P, c_int, P, P, P]),
+    "hscn_adagrad_step": (c_int, [P, P, c_int, P, P, c_int64, P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                  c_float, P, c_int, P, P, P]),
     "hscn_vl_forward": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
                                 c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
                                 P, c_int, c_float, P, P, P, P, P, P, P]),
 }
+
+
+class LRScheduleC(ctypes.Structure):    # include/hscn.h: hscn_lr_schedule
+    _fields_ = [("kind", c_int), ("base_lr", ctypes.c_double), ("warmup_steps", c_int64), ("total_steps", c_int64),
+                ("period", c_int64), ("gamma", ctypes.c_double), ("min_factor", ctypes.c_double)]
+
 
 class HipExtensionMissing(RuntimeError):
     pass

@@ -45,6 +45,7 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 # (nn/conv.py, csrc/gat_loops.hip).  Only "gcn" qualifies for the one-launch MPNN step.
 CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv}
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
+SCHEDULERS = ("cosine_with_warmup", "linear_with_warmup", "step")  # extension: optim.SCHEDULE_KINDS
 DATASETS_NUM_FEATURES: dict[str, int] = {"peptides_func": 9, "peptides_struct": 9}
 
 
@@ -111,11 +112,27 @@ class OptimConfig:  # config.py:96-112
     clip_grad_norm: bool = CLIP_GRAD_NORM
     lr: float = LR
     weight_decay: float = WEIGHT_DECAY
+    # extension: a learning-rate schedule evaluated inside the one-launch optimizer (optim.LRSchedule; None: the
+    # reference's constant rate).  "cosine_with_warmup" / "linear_with_warmup": ``warmup_epochs`` of linear warm-up,
+    # then down to ``min_lr_factor * lr`` at the last epoch; "step": ``lr *= gamma`` every ``step_epochs`` epochs.
+    scheduler: Optional[str] = None
+    warmup_epochs: int = 0
+    step_epochs: int = 1
+    gamma: float = 1.0
+    min_lr_factor: float = 0.0
 
     def __post_init__(self):
-        for v in (self.lr, self.weight_decay):
+        for v in (self.lr, self.weight_decay, self.gamma, self.min_lr_factor):
             if v and not (0.0 <= v <= 1.0):
                 raise ValueError(f"{v} must be between 0.0 and 1.0.")
+        if self.scheduler not in (None,) + SCHEDULERS:
+            raise ValueError(f"scheduler must be one of {SCHEDULERS} or None, got {self.scheduler!r}")
+        if self.warmup_epochs < 0:
+            raise ValueError(f"{self.warmup_epochs} must be non-negative.")
+        if self.step_epochs < 1:
+            raise ValueError("step_epochs must be at least 1.")
+        if not self.gamma > 0.0:
+            raise ValueError("gamma must be in (0, 1].")
 
 
 @dataclass

@@ -171,6 +171,8 @@ def eval_epoch(epoch, logger, loader, model, loss_fn: str, metric_fn: Optional[C
 
 
 def train(logger, optim_cfg, training_cfg, loaders, model, metric_fn: Optional[Callable] = None, reducer=None):
+    if getattr(optim_cfg, "scheduler", None) is not None:      # (the reference's loop has a constant rate)
+        raise ValueError("OptimConfig.scheduler runs inside the one-launch optimizers: use train_resident.fit_resident")
     optimizer = OPTIM_DICT[optim_cfg.optim_type](lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay,
                                                  params=model.parameters())
     stopper = EarlyStopping(training_cfg)

@@ -13,7 +13,9 @@ optimizer steps on iterations with ``(it + 1) % k == 0 or it + 1 == num_batches`
 gradients summed since the last step, clipped to norm 1 first.  With k > 1 two graphs are captured over the same
 buffers: the micro-batch iteration (gather, then the step ADDING its gradients to the flat buffer) and the boundary
 iteration (the same, then all-reduce, clip, optimizer step, gradients zeroed); with ``optim.FlatAdam`` the clip and
-the zeroing ride on its one launch, so no iteration issues a launch it did not issue before.
+the zeroing ride on its one launch, so no iteration issues a launch it did not issue before.  All three members of
+``OPTIM_DICT`` have such a launch (``optim.FlatAdagrad`` for Adagrad), and ``OptimConfig.scheduler`` is evaluated
+inside it from the device step counter (``optim.LRSchedule``): the captured iteration stays one replay.
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ import torch
 
 from ..config.config import OPTIM_DICT
 from ..loss import criterion
-from ..optim import clip_grad_norm_flat, collect_autograd
+from ..optim import FLAT_OPTIMIZERS, clip_grad_norm_flat, collect_autograd
 from ..replay import CapturedStep
 from . import batching
 from . import train as _train
@@ -39,18 +41,34 @@ def optimizer_steps_at(it: int, num_batches: int, batch_accumulation: int) -> bo
     return (it + 1) % batch_accumulation == 0 or it + 1 == num_batches
 
 
-def _make_optimizer(optim_cfg, model, flat: bool, clip: bool, acc: bool):
-    """``(optimizer, capturable)``.  ``flat`` (optim.FlatAdam: the update as ONE launch, clip and zeroing in it): a
-    callable ``step -> FlatAdam`` for ``CapturedStep`` to build on the step's flat gradient buffer."""
+def schedule_from_config(optim_cfg, epochs: int, num_batches: int, batch_accumulation: int):
+    """``OptimConfig.scheduler`` (lengths in epochs) as an ``optim.LRSchedule`` in optimizer steps: an epoch of
+    ``num_batches`` batches steps on the iterations ``optimizer_steps_at`` names.  None without a scheduler."""
+    name = getattr(optim_cfg, "scheduler", None)
+    if name is None:
+        return None
+    from ..optim import LRSchedule
+    per_epoch = sum(optimizer_steps_at(i, num_batches, batch_accumulation) for i in range(num_batches))
+    return LRSchedule(name, warmup_steps=optim_cfg.warmup_epochs * per_epoch, total_steps=epochs * per_epoch,
+                      period=optim_cfg.step_epochs * per_epoch, gamma=optim_cfg.gamma,
+                      min_factor=optim_cfg.min_lr_factor, base_lr=optim_cfg.lr)
+
+
+def _make_optimizer(optim_cfg, model, flat: bool, clip: bool, acc: bool, schedule=None):
+    """``(optimizer, capturable)``.  ``flat`` (optim.FlatAdam / FlatAdagrad: the update as ONE launch, clip, zeroing
+    and ``schedule`` in it): a callable ``step -> optimizer`` for ``CapturedStep`` to build on the step's flat
+    gradient buffer."""
     kw = dict(lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay)
     if flat:
-        from ..optim import FlatAdam
+        from ..optim import flat_optimizer_from_config
         fkw = dict(kw, max_norm=CLIP_MAX_NORM if clip else None, zero_grads=acc)
-        return (lambda st: FlatAdam.from_config(optim_cfg.optim_type, st.param_grads, st.grads, **fkw)), True
+        if schedule is not None:
+            fkw["schedule"] = schedule
+        return (lambda st: flat_optimizer_from_config(optim_cfg.optim_type, st.param_grads, st.grads, **fkw)), True
     opt_cls = OPTIM_DICT[optim_cfg.optim_type]
     try:
         optimizer = opt_cls(model.parameters(), capturable=True, fused=True, **kw)
-    except (TypeError, RuntimeError):          # (Adagrad has neither switch: its step stays outside the graph)
+    except (TypeError, RuntimeError):          # (torch's Adagrad has neither switch: its step stays outside the graph)
         optimizer = opt_cls(model.parameters(), **kw)
     return optimizer, bool(optimizer.defaults.get("capturable", False))
 
@@ -59,7 +77,7 @@ def _boundary_outside_graph(run, weight: float) -> None:
     """What the graph does not hold at a stepping iteration (a non-capturable optimizer; the eager tail)."""
     if run.reducer is not None:
         run.reducer.reduce(weight, weight * run.reducer.world_size)
-    if run.clip_norm is not None:              # (an optim.FlatAdam clips and zeroes in its own launch)
+    if run.clip_norm is not None:              # (the one-launch optimizers clip and zero in their own launch)
         clip_grad_norm_flat(run.flat_grads, CLIP_MAX_NORM, run.clip_norm)
     run.optimizer.step()
     if run.acc and not run.flat:
@@ -99,7 +117,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
                  batch_size: int, metric_fn: Optional[Callable] = None, seed: int = 0, reducer=None,
                  flat_optimizer: bool = True, epoch_orders: Optional[list] = None, *,
                  eval_graphs: Optional[Sequence] = None, metric: Optional[str] = None,
-                 eval_history: Optional[list] = None) -> List[tuple]:
+                 eval_history: Optional[list] = None, run_info: Optional[dict] = None) -> List[tuple]:
     """Returns ``[(mean train loss, train metric), ...]`` per epoch, like ``train.train``.  ``eval_loaders`` =
     ``[validation, test]`` loaders of host batches (evaluated with ``train.eval_epoch``).
 
@@ -125,7 +143,14 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
     ``metric`` = "ap" / "mae" computes the epoch metric, of the training split and of the evaluators, with the HIP
     launches of ``metrics`` (one read-back brings the loss and the metric together) in place of a ``metric_fn``;
     passing both is a ``ValueError``.  ``eval_history``: a list that receives ``(epoch, split, loss, perf)`` of every
-    evaluation."""
+    evaluation.
+
+    ``optim_cfg.scheduler`` (with ``flat_optimizer=True`` only: torch's optimizers would need a host-side scheduler
+    step between replays) becomes an ``optim.LRSchedule`` in optimizer steps (``schedule_from_config``), evaluated
+    inside the optimizer's launch.  ``run_info``: a dict that receives ``optimizer``, ``flat``, ``in_graph`` (the whole
+    stepping iteration is one graph) and ``schedule`` of the run."""
+    if getattr(optim_cfg, "scheduler", None) is not None and not flat_optimizer:
+        raise ValueError("a scheduler runs inside the one-launch optimizers: it needs flat_optimizer=True")
     if metric is not None and metric_fn is not None:        # (argument checks come before anything touches a device)
         raise ValueError("pass metric= (the HIP metric launch) or metric_fn=, not both")
     if metric not in (None, "ap", "mae"):
@@ -145,9 +170,13 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
         raise ValueError("fewer training graphs than one batch")
     loss_fn = training_cfg.loss_fn
     ds = batching.dataset_class(model)(train_graphs, dev, B)
-    flat = flat_optimizer and optim_cfg.optim_type in ("adam", "adamW")
+    flat = flat_optimizer and optim_cfg.optim_type in FLAT_OPTIMIZERS
+    if getattr(optim_cfg, "scheduler", None) is not None and not flat:
+        raise ValueError(f"no one-launch optimizer for {optim_cfg.optim_type!r}: a scheduler cannot run")
+    num_batches = G // B + (1 if G % B else 0)
+    schedule = schedule_from_config(optim_cfg, training_cfg.epochs, num_batches, k)
     # in_graph: the whole iteration -- backward, gradient all-reduce (if any), optimizer step -- is one graph
-    optimizer, in_graph = _make_optimizer(optim_cfg, model, flat, clip, acc)
+    optimizer, in_graph = _make_optimizer(optim_cfg, model, flat, clip, acc, schedule)
     gen = torch.Generator(device=dev).manual_seed(seed)
     model.train()
     model.engine = "resident"
@@ -163,8 +192,10 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
                           reducer=reducer, flat=flat, in_graph=in_graph, acc=acc, k=k, clip_norm=clip_norm,
                           flat_grads=step.step.grads[:step.step.P])     # every parameter gradient (not the loss column)
 
+    if run_info is not None:
+        run_info.update(optimizer=run.optimizer, flat=flat, in_graph=in_graph, schedule=schedule)
+
     steps, tail = G // B, G % B
-    num_batches = steps + (1 if tail else 0)
     C = ds.C
     loss_log = torch.zeros(num_batches, dtype=torch.float32, device=dev)
     want_metric = metric_fn is not None or metric is not None

@@ -797,6 +797,51 @@ int hscn_adam_step_ex(float* const* params_host, const int32_t* seg_off_host, in
                       int decoupled, float max_norm, float* norm_out /*[1] or NULL*/, int zero_grads, void* stream);
 int hscn_clip_grad_norm_flat(float* grads, int64_t P, float max_norm, float* norm_out /*[1] or NULL*/, void* stream);
 
+/* A learning-rate schedule evaluated INSIDE the optimizer launch (additive to ABI 23): the record travels by value in
+ * the kernel arguments, the launch reads the device step counter it is about to increment (s = optimizer steps
+ * completed so far) and uses lr(s) = base_lr * f(s), f in double as Python would form it:
+ *   HSCN_LR_CONSTANT       no record: the launch reads the device lr word (the entry points treat it like NULL).
+ *   HSCN_LR_WARMUP_COSINE  s < warmup_steps: f = max(1e-6, s / max(1, warmup_steps)); else, with s clamped to
+ *                          total_steps: f = max(min_factor, 0.5 * (1 + cos(pi * (s - warmup_steps) / max(1, total_steps -
+ *                          warmup_steps)))).
+ *   HSCN_LR_WARMUP_LINEAR  the same warm-up, then f = max(min_factor, (total_steps - s) / max(1, total_steps -
+ *                          warmup_steps)), s clamped likewise.
+ *   HSCN_LR_STEP           f = gamma ^ floor(s / period), kept as a running product in sched_state_dev[0] (a device
+ *                          double, 1 before the first step; the launch multiplies it when s + 1 reaches a period).
+ * The launch writes the rate it used into the device lr word (behind its closing barrier, beside the counter), so the
+ * word always holds the last step's rate.  HSCN_E_BADARG: an unknown kind, base_lr or warmup_steps negative,
+ * total_steps < warmup_steps, period < 1, gamma outside (0, 1], min_factor negative or NaN. */
+#define HSCN_LR_CONSTANT 0
+#define HSCN_LR_WARMUP_COSINE 1
+#define HSCN_LR_WARMUP_LINEAR 2
+#define HSCN_LR_STEP 3
+typedef struct hscn_lr_schedule {
+  int kind;
+  double base_lr;
+  int64_t warmup_steps, total_steps, period;
+  double gamma, min_factor;
+} hscn_lr_schedule;
+
+/* hscn_adam_step_ex with a schedule: sched (HOST pointer; NULL or kind HSCN_LR_CONSTANT: exactly hscn_adam_step_ex),
+ * sched_state_dev: device double [1] (required with a schedule), lr_dev: written. */
+int hscn_adam_step_sched(float* const* params_host, const int32_t* seg_off_host, int nseg, float* grads,
+                         float* exp_avg, float* exp_avg_sq, int64_t P, float* step_dev, double* beta_pows_dev,
+                         double* lr_dev, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                         float max_norm, float* norm_out /*[1] or NULL*/, int zero_grads,
+                         const hscn_lr_schedule* sched /*or NULL*/, double* sched_state_dev /*[1]*/, void* stream);
+
+/* torch.optim.Adagrad (the third member of config.py's OPTIM_DICT) as ONE launch on the same flat layout, with the
+ * same optional clip in front (max_norm > 0) and zeroing behind (zero_grads != 0) and the same optional schedule:
+ * torch/optim/adagrad.py::_single_tensor_adagrad, operation for operation --
+ *   t = step + 1;  [weight_decay] g = g + wd * p;  clr = lr / (1 + (t - 1) * lr_decay)  (double, rounded to float once)
+ *   sum = sum + g * g;  std = sqrtf(sum) + eps;  p = p + (-clr) * (g / std)
+ * state_sum [P]: filled with initial_accumulator_value before the first step; step_dev: device float counter
+ * (incremented here); lr_dev: device double (written only with a schedule). */
+int hscn_adagrad_step(float* const* params_host, const int32_t* seg_off_host, int nseg, float* grads,
+                      float* state_sum, int64_t P, float* step_dev, double* lr_dev, double lr_decay, double eps,
+                      double weight_decay, float max_norm, float* norm_out /*[1] or NULL*/, int zero_grads,
+                      const hscn_lr_schedule* sched /*or NULL*/, double* sched_state_dev /*[1] or NULL*/, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Normalisation layers of the MPNN baseline: torch.nn.LayerNorm(H) / torch.nn.BatchNorm1d(H) on [N, H] activations,
  * reference graph_hscn/model/mpnn.py:34-44 (construction) and :53-56 (use after every hidden convolution).
