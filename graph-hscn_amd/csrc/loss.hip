@@ -3,6 +3,13 @@
 // sigmoid score, on the [B, C] prediction.  One launch produces the loss, the score and
 // dL/dpred (so the backward is a single scale), replacing ~8 elementwise/reduce launches
 // of a few microseconds each on a 1 280-element tensor.  Ordered block reduction: reproducible.
+//
+// The multiclass branch (loss.py:11-14: nll_loss(log_softmax(pred, -1), true) on class-index targets) is
+// k_softmax_nll: a row lives in an aligned group of W lanes, W the power of two that covers C (up to the wave), a
+// lane holds K columns W apart (K = 1 for C <= 64, 4 up to 256, 16 up to SNL_MAX_C), so a row is read once and its
+// maximum and its sum are lane-group shuffles.  A workgroup owns a slab of SNL_SLAB rows; R <= SNL_SLAB is ONE launch
+// (the [128, 10] prediction of a training step), beyond that every workgroup leaves its partial sum in the workspace
+// and a one-workgroup launch adds them in index order.  No float atomics: the same input gives the same bits.
 #include "hscn_common.h"
 
 namespace {
@@ -52,6 +59,98 @@ __global__ void k_scale(const float* __restrict__ g, const float* __restrict__ x
   for (; i < n; i += stride) y[i] = s * x[i];
 }
 
+constexpr int SNL_THREADS = 1024;   // 16 waves, as k_criterion
+constexpr int SNL_SLAB = 256;       // rows of a workgroup
+constexpr int SNL_MAX_C = 1024;     // 16 columns per lane of a 64-lane group
+constexpr int SNL_RANGE = 1, SNL_NAN = 2;   // bits of `flags` (include/hscn.h)
+
+int snl_group_width(int C) {
+  int w = 1;
+  while (w < C && w < 64) w <<= 1;
+  return w;
+}
+
+// sum of v over the workgroup in a fixed order (lanes: xor tree; waves: in index order), valid in thread 0
+__device__ __forceinline__ float snl_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < SNL_THREADS / 64; ++w) t += red[w];
+  }
+  return t;
+}
+
+// out = gridDim.x == 1 ? loss : the workspace's partial sums
+template <int K>
+__global__ void __launch_bounds__(SNL_THREADS) k_softmax_nll(const float* __restrict__ pred,
+                                                             const int64_t* __restrict__ target, int64_t R, int C,
+                                                             int W, float* __restrict__ out, float* __restrict__ logp,
+                                                             float* __restrict__ grad, int32_t* __restrict__ flags) {
+  __shared__ float red[SNL_THREADS / 64];
+  const int groups = SNL_THREADS / W;                   // rows in flight
+  const int g = threadIdx.x / W, j = threadIdx.x & (W - 1);
+  const int64_t row0 = (int64_t)blockIdx.x * SNL_SLAB;
+  const int64_t rows = R - row0 < SNL_SLAB ? R - row0 : SNL_SLAB;
+  const float inv = 1.0f / (float)R;
+  float acc = 0.f;
+  int f = 0;
+  // (every thread takes every pass: the shuffles below run with all lanes on; a row past the slab is masked)
+  for (int base = 0; base < rows; base += groups) {
+    const bool live = base + g < rows;
+    const int64_t r = row0 + (live ? base + g : 0);
+    const float* __restrict__ x_row = pred + r * C;
+    float x[K];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int c = j + k * W;
+      x[k] = c < C ? x_row[c] : -INFINITY;
+      if (x[k] != x[k]) f |= live ? SNL_NAN : 0;
+      m = fmaxf(m, x[k]);
+    }
+    m = group_max(m, W);
+    float e[K], s = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      e[k] = expf(x[k] - m);                            // (a padding column: exp(-inf) = 0)
+      s += e[k];
+    }
+    s = group_sum(s, W);
+    const float ls = logf(s), rs = 1.0f / s;
+    const int64_t t = target[r];
+    const bool in_range = t >= 0 && t < C;
+    if (live && !in_range) f |= SNL_RANGE;
+    if (!live) continue;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int c = j + k * W;
+      if (c >= C) continue;
+      const float lp = (x[k] - m) - ls;
+      const bool hit = in_range && c == (int)t;
+      if (logp) logp[r * C + c] = lp;
+      // a row whose target is out of range takes no part in the loss: no term, no gradient
+      grad[r * C + c] = in_range ? (e[k] * rs - (hit ? 1.f : 0.f)) * inv : 0.f;
+      if (hit) acc -= lp;
+    }
+  }
+  if (f) atomicOr(flags, f);
+  const float total = snl_block_sum(acc, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = gridDim.x == 1 ? total * inv : total;
+}
+
+// loss = (sum of the workgroups' partial sums, in index order) / R
+__global__ void __launch_bounds__(SNL_THREADS) k_softmax_nll_fold(const float* __restrict__ partials, int64_t n,
+                                                                  int64_t R, float* __restrict__ loss) {
+  __shared__ float red[SNL_THREADS / 64];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += SNL_THREADS) s += partials[i];
+  const float total = snl_block_sum(s, red);
+  if (threadIdx.x == 0) loss[0] = total * (1.0f / (float)R);
+}
+
 }  // namespace
 
 extern "C" {
@@ -71,6 +170,38 @@ int hscn_scale(const float* g, const float* x, float* y, int64_t count, void* st
   if (nb > 1024) nb = 1024;
   k_scale<<<nb, 256, 0, hscn_stream(stream_)>>>(g, x, y, count);
   HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+size_t hscn_softmax_nll_workspace_bytes(int64_t R, int C) {
+  if (R < 1 || C < 1 || C > SNL_MAX_C || R > ((int64_t)1 << 40)) return 0;
+  const int64_t nb = (R + SNL_SLAB - 1) / SNL_SLAB;
+  return nb > 1 ? (size_t)nb * sizeof(float) : 0;
+}
+
+int hscn_softmax_nll_fwd(const float* pred, const int64_t* target, int64_t R, int C, float* loss, float* logp,
+                         float* grad, int32_t* flags, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (R < 1 || C < 1 || C > SNL_MAX_C || R > ((int64_t)1 << 40) || !pred || !target || !loss || !grad || !flags)
+    return HSCN_E_BADARG;
+  const size_t need = hscn_softmax_nll_workspace_bytes(R, C);
+  if (need && !workspace) return HSCN_E_BADARG;
+  if (workspace_bytes < need) return HSCN_E_WORKSPACE;
+  const int64_t nb = (R + SNL_SLAB - 1) / SNL_SLAB;
+  if (nb > 0x7fffffff) return HSCN_E_BADARG;
+  const int W = snl_group_width(C);
+  float* out = nb == 1 ? loss : static_cast<float*>(workspace);
+  hipStream_t st = hscn_stream(stream_);
+  if (C <= 64)
+    k_softmax_nll<1><<<(unsigned)nb, SNL_THREADS, 0, st>>>(pred, target, R, C, W, out, logp, grad, flags);
+  else if (C <= 256)
+    k_softmax_nll<4><<<(unsigned)nb, SNL_THREADS, 0, st>>>(pred, target, R, C, W, out, logp, grad, flags);
+  else
+    k_softmax_nll<16><<<(unsigned)nb, SNL_THREADS, 0, st>>>(pred, target, R, C, W, out, logp, grad, flags);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  if (nb > 1) {
+    k_softmax_nll_fold<<<1, SNL_THREADS, 0, st>>>(out, nb, R, loss);
+    HSCN_RETURN_IF_LAUNCH_FAILED();
+  }
   return 0;
 }
 

@@ -16,6 +16,11 @@
 // bank is hit twice by a lane group): pass 1 counts the chunk's positives and those up to its last run end, two
 // block scans give every chunk the tp before it and the tp at the last run end before it (a max-scan: tp at run ends
 // never decreases), pass 2 adds the chunk's terms in row order, and a fixed tree adds the 1024 chunk sums.  No atomics.
+//
+// Class-index targets (accuracy, macro-F1): the [C, C] confusion matrix.  A thread takes a row, finds the first
+// maximal column and adds one to confusion[target][column] in the workgroup's LDS copy; the copies are added to the
+// global matrix entry by entry.  Integer adds only: any order gives the same matrix.  A one-workgroup launch then
+// reads the diagonal, the row sums and the column sums and writes accuracy and macro-F1 in float64, class by class.
 #include "hscn_common.h"
 
 namespace {
@@ -212,6 +217,81 @@ __global__ void __launch_bounds__(MT) k_mae(const float* __restrict__ y_true, co
   }
 }
 
+constexpr int MC_THREADS = 256;
+constexpr int MC_MAX_C = 128;                  // the confusion matrix fits 64 KB of LDS
+constexpr int MC_MAX_BLOCKS = 256;
+constexpr int MC_NAN = 2, MC_RANGE = 4;        // bits of `flags` (include/hscn.h)
+
+__global__ void __launch_bounds__(MC_THREADS) k_mc_zero(int32_t* __restrict__ confusion, int n,
+                                                        int32_t* __restrict__ flags) {
+  for (int i = blockIdx.x * MC_THREADS + threadIdx.x; i < n; i += gridDim.x * MC_THREADS) confusion[i] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) flags[0] = 0;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_mc_confusion(const int64_t* __restrict__ target,
+                                                             const float* __restrict__ score, int64_t G, int C,
+                                                             int32_t* __restrict__ confusion,
+                                                             int32_t* __restrict__ flags) {
+  extern __shared__ int32_t lds_conf[];
+  const int n = C * C;
+  for (int i = threadIdx.x; i < n; i += MC_THREADS) lds_conf[i] = 0;
+  __syncthreads();
+  int f = 0;
+  for (int64_t r = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x; r < G; r += (int64_t)gridDim.x * MC_THREADS) {
+    const float* __restrict__ row = score + r * C;
+    float best = row[0];
+    int arg = 0;
+    if (best != best) f |= MC_NAN;
+    for (int c = 1; c < C; ++c) {
+      const float v = row[c];
+      if (v != v) f |= MC_NAN;
+      if (v > best) { best = v; arg = c; }                 // strict: the first maximal column stays
+    }
+    const int64_t t = target[r];
+    if (t < 0 || t >= C) { f |= MC_RANGE; continue; }
+    atomicAdd(&lds_conf[(int)t * C + arg], 1);
+  }
+  if (f) atomicOr(flags, f);
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += MC_THREADS) {
+    const int v = lds_conf[i];
+    if (v) atomicAdd(&confusion[i], v);
+  }
+}
+
+// accuracy = trace / G; F1 of class c = 2 tp / (true_c + predicted_c), 0 where tp is 0; macro-F1 = the mean over the
+// classes with true_c + predicted_c > 0 (sklearn's labels = unique(y_true U y_pred)), added in class order
+__global__ void __launch_bounds__(MC_THREADS) k_mc_finish(const int32_t* __restrict__ confusion, int64_t G, int C,
+                                                          double* __restrict__ result,
+                                                          double* __restrict__ per_class) {
+  __shared__ int s_tp[MC_MAX_C], s_present[MC_MAX_C];
+  __shared__ double s_f1[MC_MAX_C];
+  for (int c = threadIdx.x; c < C; c += MC_THREADS) {
+    int64_t n_true = 0, n_pred = 0;
+    for (int k = 0; k < C; ++k) {
+      n_true += confusion[c * C + k];
+      n_pred += confusion[k * C + c];
+    }
+    const int tp = confusion[c * C + c];
+    const double f1 = tp > 0 ? 2.0 * (double)tp / (double)(n_true + n_pred) : 0.0;
+    s_tp[c] = tp;
+    s_present[c] = n_true + n_pred > 0;
+    s_f1[c] = f1;
+    per_class[c] = f1;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int64_t trace = 0;
+  int labels = 0;
+  double sum = 0.0;
+  for (int c = 0; c < C; ++c) {
+    trace += s_tp[c];
+    if (s_present[c]) { sum += s_f1[c]; ++labels; }
+  }
+  result[0] = (double)trace / (double)G;
+  result[1] = labels ? sum / (double)labels : 0.0;
+}
+
 int64_t ap_pow2(int64_t G) {
   int64_t n2 = 2;
   while (n2 < G) n2 <<= 1;
@@ -258,6 +338,24 @@ int hscn_mean_absolute_error(const float* y_true, const float* y_pred, int64_t G
                              int32_t* flags, void* stream_) {
   if (G < 1 || C < 1 || G > ((int64_t)1 << 30) || !y_true || !y_pred || !result || !flags) return HSCN_E_BADARG;
   k_mae<<<1, MT, 0, hscn_stream(stream_)>>>(y_true, y_pred, G * (int64_t)C, result, flags);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+int hscn_multiclass_metrics(const int64_t* target, const float* score, int64_t G, int C, int32_t* confusion,
+                            double* result, double* per_class, int32_t* flags, void* stream_) {
+  if (G < 1 || C < 1 || C > MC_MAX_C || G > ((int64_t)1 << 30) || !target || !score || !confusion || !result ||
+      !per_class || !flags)
+    return HSCN_E_BADARG;
+  hipStream_t st = hscn_stream(stream_);
+  const int n = C * C;
+  k_mc_zero<<<hscn_blocks(n, MC_THREADS), MC_THREADS, 0, st>>>(confusion, n, flags);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  unsigned nb = hscn_blocks(G, MC_THREADS);
+  if (nb > MC_MAX_BLOCKS) nb = MC_MAX_BLOCKS;
+  k_mc_confusion<<<nb, MC_THREADS, (size_t)n * sizeof(int32_t), st>>>(target, score, G, C, confusion, flags);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  k_mc_finish<<<1, MC_THREADS, 0, st>>>(confusion, G, C, result, per_class);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

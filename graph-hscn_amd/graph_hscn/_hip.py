@@ -158,6 +158,11 @@ _SIGNATURES = {
                                      ctypes.c_double, ctypes.c_double, c_int, c_float, P, c_int, P, P, P]),
     "hscn_adagrad_step": (c_int, [P, P, c_int, P, P, c_int64, P, P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                   c_float, P, c_int, P, P, P]),
+    # class-index targets: fused log-softmax + NLL, accuracy / macro-F1 (csrc/loss.hip, csrc/metrics.hip; additive
+    # to ABI 23)
+    "hscn_softmax_nll_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "hscn_softmax_nll_fwd": (c_int, [P, P, c_int64, c_int, P, P, P, P, P, c_size_t, P]),
+    "hscn_multiclass_metrics": (c_int, [P, P, c_int64, c_int, P, P, P, P, P]),
     "hscn_vl_forward": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
                                 c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
                                 P, c_int, c_float, P, P, P, P, P, P, P]),

@@ -156,6 +156,7 @@ class PEConfig:  # config.py:115-130 (defaults.py:19-28)
 class TrainingConfig:  # config.py:133-152
     model_type: str
     loss_fn: str
+    # "ap" / "mae" (the reference's two), or "accuracy" / "f1_macro" for class-index targets (graph_hscn.metrics)
     metric: str
     epochs: int = EPOCHS
     eval_period: int = EVAL_PERIOD

@@ -144,11 +144,17 @@ class DeviceHeteroDataset(_DeviceDataset):
         base = {"local": nptr, "virtual": vptr}
         self.F = int(whole["local"].x.size(1))
         y = whole["local"].y if "y" in whole["local"] else None
-        self.C = None if y is None else int(y.size(1))
+        # class-index targets (one integer per graph, data.py's collation of ``y = tensor([c])``): kept as int64 [G];
+        # the gather copies a graph's target row as float32 WORDS, so an int64 travels as a row of two, bit for bit
+        self.class_index = y is not None and y.dim() == 1 and not y.dtype.is_floating_point
+        self.C = None if (y is None or self.class_index) else int(y.size(1))
+        y_words = 2 if self.class_index else (self.C or 0)
         dev = self.device
+        if y is not None:
+            y = (y.to(torch.int64) if self.class_index else y.float()).contiguous().to(dev)
         self._t = {"x_local": whole["local"].x.float().contiguous().to(dev),
                    "x_virtual": whole["virtual"].x.float().contiguous().to(dev),
-                   "y": None if y is None else y.float().contiguous().to(dev),
+                   "y": y,
                    "nptr": nptr.to(dev), "vptr": vptr.to(dev)}
         sizes = {"local": nptr[1:] - nptr[:-1], "virtual": vptr[1:] - vptr[:-1]}
         esizes = {}
@@ -166,7 +172,8 @@ class DeviceHeteroDataset(_DeviceDataset):
             B, dev, _top_sum(sizes["local"], B), _top_sum(sizes["virtual"], B),
             {et: _top_sum(esizes[et], B) for et in _RELS},
             {"local": int(sizes["local"].max()), "virtual": int(sizes["virtual"].max())},
-            {et: int(esizes[et].max()) if esizes[et].numel() else 0 for et in _RELS}, self.F, self.C)
+            {et: int(esizes[et].max()) if esizes[et].numel() else 0 for et in _RELS}, self.F, self.C,
+            class_index=self.class_index)
         if resident_structure:
             from ..engine import BatchStructure, build_structure
             self.structure = build_structure(whole.to(dev))              # one launch over all G graphs
@@ -180,9 +187,9 @@ class DeviceHeteroDataset(_DeviceDataset):
                             (ctypes.c_void_p * 3)(*[p(t[f"src{r}"]) for r in range(3)]),
                             (ctypes.c_void_p * 3)(*[p(t[f"dst{r}"]) for r in range(3)]),
                             (ctypes.c_void_p * 3)(*[p(t[f"eptr{r}"]) for r in range(3)]),
-                            self.num_graphs, self.F, self.C or 0)
+                            self.num_graphs, self.F, y_words)
         hb, st = self.static.batch, self.static
-        self._out = _BatchOut(p(hb["local"].x), p(hb["virtual"].x), p(hb["local"].y) if self.C else None,
+        self._out = _BatchOut(p(hb["local"].x), p(hb["virtual"].x), p(hb["local"].y) if y_words else None,
                               p(hb["local"].ptr), p(hb["virtual"].ptr), p(hb["local"].ptr32), p(hb["virtual"].ptr32),
                               p(hb["local"].batch), p(hb["virtual"].batch),
                               (ctypes.c_void_p * 3)(*[p(hb[et].edge_index) for et in _RELS]),

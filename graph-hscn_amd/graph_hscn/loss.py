@@ -3,14 +3,23 @@
 On the device the multilabel BCE-with-logits and L1 branches are one fused HIP
 launch (loss + sigmoid score + dL/dpred, csrc/loss.hip) -- or none at all: a prediction
 of the graph-resident HSCN forward arrives with its score, and the loss and its gradient
-are evaluated inside the backward launch of the same step (``LazyLoss``); the multiclass branch
-(``true.ndim == 1``) and CPU tensors use the plain torch ops the reference
-uses.  Quirk kept: the L1 branch scores with ``sigmoid(pred)`` (loss.py:17-19)."""
+are evaluated inside the backward launch of the same step (``LazyLoss``).  The multiclass branch
+(``true.ndim == 1``: class-index targets) is one fused launch as well (log-softmax + NLL: loss, the
+log-probabilities it returns as the score, dL/dpred; ``hscn_softmax_nll_fwd``).  CPU tensors use the
+plain torch ops the reference uses.  Quirk kept: the L1 branch scores with ``sigmoid(pred)``
+(loss.py:17-19).
+
+A class index outside ``[0, C)`` raises ``IndexError`` in torch at once; the launch cannot raise, it
+sets a bit in a per-device flag word (``class_target_flags``) and leaves the row out of the loss.  The
+word is read -- one synchronising copy -- by ``check_class_targets(device)``, which raises the
+``IndexError`` and clears it: ``train.train_resident.fit_resident`` calls it at the end of every epoch's
+read-back, ``train.eval_resident.DeviceEvaluator.evaluate`` brings the word over with its loss and
+metric.  ``step.ResidentTrainStep`` keeps a word of its own, read by its ``check()``."""
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from ._hip import call, ptr, stream
+from ._hip import call, lib, ptr, stream
 
 
 class LazyScaled(torch.Tensor):
@@ -190,8 +199,87 @@ class _CriterionFn(Function):
         return LazyScaled(grad, g_loss.reshape(1).contiguous()), None, None
 
 
+# bits of hscn_softmax_nll_fwd's ``flags`` (include/hscn.h).  Only the first becomes an error here: a NaN prediction
+# makes the loss itself NaN, as in torch, so NAN_PRED is there for a caller that reads the word, nothing raises on it
+TARGET_OUT_OF_RANGE, NAN_PRED = 1, 2
+_NLL_FLAGS = {}
+
+
+def class_target_flags(device) -> torch.Tensor:
+    """The device's flag word [1] int32 that every multiclass ``criterion`` call ORs its bits into."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    t = _NLL_FLAGS.get(device)
+    if t is None:
+        t = _NLL_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def raise_for_class_flags(flags: int) -> None:
+    if flags & TARGET_OUT_OF_RANGE:
+        raise IndexError("Target out of bounds: a class index outside [0, C) reached the multiclass criterion")
+
+
+def check_class_targets(device) -> None:
+    """Synchronising: read and clear the device's flag word; ``IndexError`` if a multiclass ``criterion`` call since
+    the last check met a class index outside ``[0, C)`` (torch's own error for it, raised late).  A ``NAN_PRED`` bit
+    is cleared with it and raises nothing: the loss of that call is NaN already."""
+    word = class_target_flags(device)
+    f = int(word.item())
+    if f:
+        word.zero_()
+    raise_for_class_flags(f)
+
+
+def softmax_nll_workspace(R: int, C: int, device):
+    """The launch's scratch (None where it needs none: ``R`` up to one workgroup's rows)."""
+    nbytes = int(lib().hscn_softmax_nll_workspace_bytes(R, C))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def launch_softmax_nll(pred, true, loss, logp, grad, flags, workspace) -> None:
+    """``hscn_softmax_nll_fwd`` on ``pred`` [R, C] float32 / ``true`` [R] int64 into preallocated outputs."""
+    R, C = pred.shape
+    call("hscn_softmax_nll_fwd", ptr(pred), ptr(true), R, C, ptr(loss), ptr(logp), ptr(grad), ptr(flags),
+         ptr(workspace), workspace.numel() if workspace is not None else 0, stream())
+
+
+class _SoftmaxNllFn(Function):
+    """The multiclass branch: one launch for loss, log-probabilities and dL/dpred; the backward is a scale the
+    consumer may apply itself (``LazyScaled``), exactly as ``_CriterionFn``'s."""
+
+    @staticmethod
+    def forward(ctx, pred, true):
+        pred, true = pred.contiguous(), true.contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        # (the launch always writes dL/dpred -- include/hscn.h: only logp is optional -- so the buffer exists under
+        # no_grad too, where nothing reads it; it goes back to the caching allocator when forward returns)
+        logp, grad = torch.empty_like(pred), torch.empty_like(pred)
+        launch_softmax_nll(pred, true, loss, logp, grad, class_target_flags(pred.device),
+                           softmax_nll_workspace(pred.size(0), pred.size(1), pred.device))
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(logp)
+        ctx.set_materialize_grads(False)
+        return loss.view(()), logp
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_logp):
+        (grad,) = ctx.saved_tensors
+        if g_loss is None:
+            return None, None
+        return LazyScaled(grad, g_loss.reshape(1).contiguous()), None
+
+
+def _multiclass_on_device(pred: torch.Tensor, true: torch.Tensor) -> bool:
+    return (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and true.dtype == torch.int64
+            and true.device == pred.device and true.size(0) == pred.size(0) and pred.numel() > 0)
+
+
 def criterion(loss_fn: str, pred: torch.Tensor, true: torch.Tensor):
     multiclass = loss_fn == "cross_entropy" and pred.ndim > 1 and true.ndim == 1
+    if multiclass and _multiclass_on_device(pred, true):
+        return _SoftmaxNllFn.apply(pred, true)
     if pred.is_cuda and not multiclass and pred.dtype == torch.float32 and pred.shape == true.shape:
         kind = 0 if loss_fn == "cross_entropy" else 1
         true = true.float()

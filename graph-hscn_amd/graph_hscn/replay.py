@@ -48,7 +48,12 @@ class StaticHeteroBatch:
             raise ValueError("all batches must hold the same number of graphs (drop or pad the last one)")
         cap = lambda f: max(int(f(b)) for b in batches)
         y0 = batches[0]["local"].y if "y" in batches[0]["local"] else None
-        C = None if y0 is None else (int(y0.size(1)) if num_classes is None else int(num_classes))
+        # class-index targets (one integer per graph): ``y`` is int64 [G]; their C is the model's, not the batch's
+        self.class_index = y0 is not None and y0.dim() == 1 and not y0.dtype.is_floating_point
+        if y0 is None or self.class_index:
+            C = None
+        else:
+            C = int(y0.size(1)) if num_classes is None else int(num_classes)
         self._allocate(B.pop(), device, cap(lambda b: b["local"].num_nodes), cap(lambda b: b["virtual"].num_nodes),
                        {et: cap(lambda b, et=et: b[et].edge_index.size(1)) for et in (LL, VV, LV)},
                        {"local": cap(lambda b: b["local"].max_nodes), "virtual": cap(lambda b: b["virtual"].max_nodes)},
@@ -57,11 +62,14 @@ class StaticHeteroBatch:
 
     @classmethod
     def from_capacities(cls, num_graphs: int, device, num_nodes: int, num_virtual: int, num_edges: dict,
-                        max_nodes: dict, max_edges: dict, num_features: int, num_classes: Optional[int]):
+                        max_nodes: dict, max_edges: dict, num_features: int, num_classes: Optional[int],
+                        class_index: bool = False):
         """Buffers for batches of ``num_graphs`` graphs with at most the given totals (nodes, virtual nodes,
-        edges per relation) and per-graph maxima (what sizes the LDS of the graph-resident launches)."""
+        edges per relation) and per-graph maxima (what sizes the LDS of the graph-resident launches).
+        ``class_index``: the targets are one int64 class index per graph (``num_classes`` is not used then)."""
         self = cls.__new__(cls)
         self.feature_dtype = torch.float32
+        self.class_index = bool(class_index)
         self._allocate(num_graphs, device, num_nodes, num_virtual, num_edges, max_nodes, max_edges, num_features,
                        num_classes)
         return self
@@ -78,7 +86,9 @@ class StaticHeteroBatch:
         for nt, n in (("local", self.N), ("virtual", self.V)):
             fields += [(f"ptr_{nt}", torch.int64, (G + 1,)), (f"ptr32_{nt}", torch.int32, (G + 1,)),
                        (f"batch_{nt}", torch.int64, (n,))]
-        if C is not None:
+        if getattr(self, "class_index", False):
+            fields.append(("y", torch.int64, (G,)))
+        elif C is not None:
             fields.append(("y", torch.float32, (G, C)))
         for i, et in enumerate((LL, VV, LV)):
             fields += [(f"ei_{i}", torch.int64, (2, self.E[et])), (f"eptr_{i}", torch.int32, (G + 1,))]

@@ -55,6 +55,14 @@ class ResidentTrainStep(_FlatGradStep):
     criterion(loss_fn, pred, batch["local"].y); loss.backward()`` on the graph-resident engine,
     issued by ``run()`` as two or three launches on the current stream.
 
+    Class-index targets (``loss_fn="cross_entropy"`` with a contiguous int64 ``[B]`` target on the device: the
+    criterion's multiclass branch, loss.py:11-14) run as THREE launches: the forward launch of the pair,
+    ``hscn_softmax_nll_fwd`` on its prediction (loss, log-probabilities, dL/dpred), and the backward launch on that
+    dense ``g_pred`` with no loss tail.  ``score`` then holds the log-probabilities, ``loss`` is a buffer of its own
+    (the backward launch without a tail writes the ``P`` parameter columns of ``grads`` only), and a class index
+    outside ``[0, C)`` sets a bit in ``class_flags`` that ``check()`` turns into ``IndexError``.  The one-launch step
+    has no class-index loss row: ``one_launch=None`` resolves to this form, ``one_launch=True`` raises.
+
     Outputs (tensors that every ``run()`` refreshes in place): ``pred`` [B,C], ``score`` [B,C]
     (= sigmoid(pred), what ``criterion`` returns beside the loss), ``loss`` (0-dim), ``grads``
     (flat, the parameter gradients in launch order) and ``virtual`` (final virtual features, as
@@ -116,9 +124,20 @@ class ResidentTrainStep(_FlatGradStep):
         self.head_act = _engine.ACT[act_name]
         self.slope = float(model.convs[0].convs["__".join(LV)].negative_slope)
         y = target if target is not None else batch["local"].y
-        if y.dtype != torch.float32 or not y.is_contiguous() or y.device != dev:
-            raise TypeError("targets must be a contiguous float32 tensor on the batch's device")
-        self.kind = _loss_kind(loss_fn, (B, C), y)
+        self.class_index = bool(loss_fn == "cross_entropy" and y.dim() == 1 and y.dtype == torch.int64
+                                and y.is_contiguous() and y.device == dev)
+        if self.class_index:
+            if y.size(0) != B:
+                raise ValueError("class-index targets are one int64 per graph: [B]")
+            if one_launch:
+                raise RuntimeError("the one-launch step has no class-index loss row: class-index targets run as the "
+                                   "forward launch, hscn_softmax_nll_fwd and the backward launch (one_launch=None)")
+            one_launch = False
+            self.kind = None
+        else:
+            if y.dtype != torch.float32 or not y.is_contiguous() or y.device != dev:
+                raise TypeError("targets must be a contiguous float32 tensor on the batch's device")
+            self.kind = _loss_kind(loss_fn, (B, C), y)
         self.target = y
         self._head = params[9 * L:]
         self._table = _engine._ptr_table(params[: 9 * L])
@@ -126,7 +145,7 @@ class ResidentTrainStep(_FlatGradStep):
         # the virtual branch rides on the two launches as extra workgroups while they land on idle CUs
         self.defer = _engine.defers_virtual(model.compute_virtual, model.overlap_virtual, self.dims, dev)
         self._out, self._state = _engine.hscn_buffers(dev, sdt, self.dims, *(self.ei[k].size(1) for k in (LL, LV, VV)),
-                                                      score=True, csr=True, state=self.defer)
+                                                      score=not self.class_index, csr=True, state=self.defer)
         self.acts, self.pooled, self.z, self.pred, self.score, self.csr = self._out
         self.virtual = torch.empty(max(V, 1), H, dtype=sdt, device=dev) if model.compute_virtual else None
         cus = _engine._cu_count(dev)
@@ -167,7 +186,18 @@ class ResidentTrainStep(_FlatGradStep):
         self.partials = torch.empty(B, P + 1, dtype=torch.float32, device=dev)
         self.grads = torch.zeros(P + 1, dtype=torch.float32, device=dev)
         self.loss = self.grads[P:P + 1].view(())
-        self._tail = _engine._LossTail(ptr(self.pred), ptr(self.target), int(self.kind))
+        if self.class_index:
+            from .loss import softmax_nll_workspace
+            f32 = dict(dtype=torch.float32, device=dev)
+            self.score = torch.empty(B, C, **f32)                 # log-probabilities
+            self.g_pred = torch.empty(B, C, **f32)
+            self._loss1 = torch.zeros(1, **f32)
+            self.loss = self._loss1.view(())
+            self.class_flags = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._nll_ws = softmax_nll_workspace(B, C, dev)
+            self._tail = None
+        else:
+            self._tail = _engine._LossTail(ptr(self.pred), ptr(self.target), int(self.kind))
         # parameter -> slice of the flat gradient buffer (launch order: {W_ll, b_ll} per layer, W1, b1, W2, b2)
         mp = model._resident_params()
         order = [p for l in range(L) for p in mp[9 * l: 9 * l + 2]] + list(mp[9 * L:])
@@ -208,14 +238,27 @@ class ResidentTrainStep(_FlatGradStep):
             _engine.launch_fwd(self._store, self.x_local, self.x_virtual, ei_ll, self.ei[VV], self.ei[LV], m, self.dims,
                                self.head_act, self.slope, self._table, self._head, self.model.compute_virtual,
                                self._out, self.virtual)
+        g_pred = None
+        if self.class_index:
+            from .loss import launch_softmax_nll
+            launch_softmax_nll(self.pred, self.target, self._loss1, self.score, self.g_pred, self.class_flags,
+                               self._nll_ws)
+            g_pred = self.g_pred
         _engine.launch_bwd(self._grad_flags, self.x_local, ei_ll, m, self.dims, self.head_act, self._wll_table,
-                           self._head[0], self._head[2], self.acts, self.pooled, self.z, self.csr, None, None,
+                           self._head[0], self._head[2], self.acts, self.pooled, self.z, self.csr, g_pred, None,
                            self.partials, self.grads, self._tail, self._job(self.virtual) if self.defer else None)
         return self.loss
 
     def check(self) -> None:
-        """Synchronising validity check of the launches issued so far (block-diagonal batch, sizes)."""
+        """Synchronising validity check of the launches issued so far (block-diagonal batch, sizes; with class-index
+        targets also their range: ``IndexError``, the flag word is cleared)."""
         self.meta.check()
+        if self.class_index:
+            from .loss import raise_for_class_flags
+            f = int(self.class_flags.item())
+            if f:
+                self.class_flags.zero_()
+            raise_for_class_flags(f)
 
 
 class ScnWorkspace:

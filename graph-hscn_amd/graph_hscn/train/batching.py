@@ -24,6 +24,21 @@ def targets(model, batch) -> Optional[Tensor]:
     return getattr(batch, "y", None)
 
 
+def class_index_targets(y: Optional[Tensor]) -> bool:
+    """Whether ``y`` holds one class index per graph (the criterion's multiclass branch) rather than ``[B, C]``."""
+    return y is not None and y.dim() == 1 and not y.dtype.is_floating_point
+
+
+def score_width(model, y: Tensor) -> int:
+    """Columns of the score ``criterion`` returns for targets ``y``: ``y``'s own for ``[B, C]`` targets; for class
+    indices the width of the model's head (HSCN: ``lin_2``)."""
+    if not class_index_targets(y):
+        return int(y.size(1))
+    if not is_hetero(model):
+        raise ValueError("class-index targets are served for HSCN (the reference model) only")
+    return int(model.lin_2.out_channels)
+
+
 def forward(model, batch) -> Tuple[Tensor, Tensor]:
     """``(pred, targets)`` of ``model`` on a batch that is on the model's device."""
     if is_hetero(model):

@@ -19,8 +19,9 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from ..loss import criterion
-from ..metrics import (MetricResult, average_precision_launch, mean_absolute_error_launch, metric_buffers,
-                       metric_value, read_packed)
+from ..loss import raise_for_class_flags, class_target_flags
+from ..metrics import (CLASS_METRICS, METRICS, MetricResult, metric_buffers, metric_launch, metric_value, read_packed,
+                       result_index)
 from . import batching
 
 _GATHER_FAULT = 8      # loader.device_dataset: a graph id outside the dataset / a batch beyond the static capacity
@@ -28,7 +29,8 @@ _GATHER_FAULT = 8      # loader.device_dataset: a graph id outside the dataset /
 
 class EvalRun(NamedTuple):
     """Device tensors of one evaluation: ``loss`` 0-dim float32 (mean of ``loss_log``), ``loss_log`` [num_batches],
-    ``scores`` / ``targets`` [G, C] in dataset order, ``metric`` the metric launch's ``MetricResult`` (or ``None``)."""
+    ``scores`` / ``targets`` [G, C] in dataset order (class-index targets: ``targets`` int64 [G], ``scores`` the
+    log-probabilities), ``metric`` the metric launch's ``MetricResult`` (or ``None``)."""
     loss: torch.Tensor
     loss_log: torch.Tensor
     scores: torch.Tensor
@@ -38,11 +40,14 @@ class EvalRun(NamedTuple):
 
 class DeviceEvaluator:
     """``graphs``: the split (``HeteroData`` for HSCN, ``Data`` for the MPNN baseline -- chosen as ``fit_resident``
-    chooses); ``metric``: "ap", "mae" or ``None`` (no metric launch, ``evaluate`` answers NaN for it)."""
+    chooses); ``metric``: "ap", "mae", or -- for a split with class-index targets (HSCN only; C is the width of the
+    model's head) -- "accuracy" / "f1_macro", or ``None`` (no metric launch, ``evaluate`` answers NaN for it).  A class
+    index outside ``[0, C)`` is an ``IndexError`` of ``evaluate()``: the criterion's flag word comes over in the same
+    copy."""
 
     def __init__(self, graphs: Sequence, model, loss_fn: str, batch_size: int, metric: Optional[str] = None):
-        if metric not in ("ap", "mae", None):
-            raise ValueError(f"metric must be 'ap', 'mae' or None, got {metric!r}")
+        if metric not in METRICS + (None,):
+            raise ValueError(f"metric must be one of {METRICS} or None, got {metric!r}")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("DeviceEvaluator runs on the MI355X HIP path: move the model to 'cuda'")
@@ -62,15 +67,22 @@ class DeviceEvaluator:
         # (the tail: collated once, kept on the device)
         self.tail_batch = batching.collate(model, list(graphs[self.steps * B:]), dev) if self.tail else None
         y0 = batching.targets(model, self.tail_batch if self.tail else self.ds.static.batch)
-        C = self.C = int(y0.size(1))
+        self.class_index = batching.class_index_targets(y0)
+        if metric is not None and (metric in CLASS_METRICS) != self.class_index:
+            raise ValueError(f"metric {metric!r} does not fit the split's targets ('accuracy' / 'f1_macro' take class "
+                             "indices, 'ap' / 'mae' [G, C] targets)")
+        C = self.C = batching.score_width(model, y0)
         f32 = dict(dtype=torch.float32, device=dev)
         self.scores = torch.zeros(G, C, **f32)
-        self.targets = torch.zeros(G, C, **f32)
+        self.targets = torch.zeros(G, dtype=torch.int64, device=dev) if self.class_index else torch.zeros(G, C, **f32)
+        self._class_flags = class_target_flags(dev) if self.class_index else None
         self.loss_log = torch.zeros(self.num_batches, **f32)
-        # result [2] f64 | metric flags i32 | mean loss f32 | gather flag i32 | spare: what evaluate() reads, once
+        # result [2] f64 | metric flags i32 | mean loss f32 | gather flag i32 | class-target flags i32: what evaluate()
+        # reads, once
         self.packed = torch.zeros(32, dtype=torch.uint8, device=dev)
         self._loss = self.packed[20:24].view(torch.float32)
         self._gather_flag = self.packed[24:28].view(torch.int32)
+        self._target_flag = self.packed[28:32].view(torch.int32)
         self.out = metric_buffers(metric, G, C, dev, self.packed) if metric else None
 
     def _batch(self, batch, lo: int, hi: int, i: int) -> None:
@@ -98,10 +110,10 @@ class DeviceEvaluator:
         self._loss.copy_(self.loss_log.mean())          # float32, unweighted over the batches: eval_epoch's definition
         if self.ds is not None:
             self._gather_flag.copy_(self.ds.flag)
-        if self.metric == "ap":
-            average_precision_launch(self.targets, self.scores, out=self.out)
-        elif self.metric == "mae":
-            mean_absolute_error_launch(self.targets, self.scores, out=self.out)
+        if self._class_flags is not None:
+            self._target_flag.copy_(self._class_flags)
+        if self.metric is not None:
+            metric_launch(self.metric)(self.targets, self.scores, out=self.out)
         return EvalRun(self._loss.view(()), self.loss_log, self.scores, self.targets, self.out)
 
     def evaluate(self) -> Tuple[float, float]:
@@ -111,6 +123,10 @@ class DeviceEvaluator:
         f64, i32 = read_packed(self.packed)
         if int(i32[2]) & _GATHER_FAULT:
             raise IndexError("a graph id was outside the dataset (or a batch exceeded the static capacity)")
+        if int(i32[3]):
+            self._class_flags.zero_()
+            raise_for_class_flags(int(i32[3]))
         loss = float(i32[1:2].view(torch.float32)[0])
-        perf = metric_value(self.metric, float(f64[0]), int(i32[0])) if self.metric else float("nan")
+        perf = metric_value(self.metric, float(f64[result_index(self.metric)]), int(i32[0])) if self.metric \
+            else float("nan")
         return loss, perf

@@ -26,7 +26,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from ..config.config import OPTIM_DICT
-from ..loss import criterion
+from ..loss import check_class_targets, criterion
 from ..optim import FLAT_OPTIMIZERS, clip_grad_norm_flat, collect_autograd
 from ..replay import CapturedStep
 from . import batching
@@ -133,14 +133,15 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
     order ``train.train_epoch`` has to see to take the same steps.
 
     ``model`` may also be the MPNN baseline (``model.mpnn.MPNN``) with ``train_graphs`` a list of ``Data``: the
-    dataset is then a ``DeviceGraphDataset`` and the captured step ``step.MPNNResidentTrainStep`` (one launch + the
+    dataset is then a ``DeviceGraphDataset`` (``[B, C]`` targets only: the MPNN's and the vl model's one-launch steps
+    refuse class indices) and the captured step ``step.MPNNResidentTrainStep`` (one launch + the
     gradient fold; ``batching`` picks both); evaluation through ``train.eval_epoch`` takes the MPNN's forward-only
     launch.
 
     Evaluation on the device (keyword-only; the defaults leave the loop as it was): ``eval_graphs`` =
     ``(validation graphs, test graphs)`` puts the two splits into ``eval_resident.DeviceEvaluator``s built once before
     the first epoch -- no host loader, collation or copy per evaluation -- and ``eval_loaders`` may then be ``None``.
-    ``metric`` = "ap" / "mae" computes the epoch metric, of the training split and of the evaluators, with the HIP
+    ``metric`` = "ap" / "mae" (or, for class-index targets, "accuracy" / "f1_macro") computes the epoch metric, of the training split and of the evaluators, with the HIP
     launches of ``metrics`` (one read-back brings the loss and the metric together) in place of a ``metric_fn``;
     passing both is a ``ValueError``.  ``eval_history``: a list that receives ``(epoch, split, loss, perf)`` of every
     evaluation.
@@ -153,8 +154,9 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
         raise ValueError("a scheduler runs inside the one-launch optimizers: it needs flat_optimizer=True")
     if metric is not None and metric_fn is not None:        # (argument checks come before anything touches a device)
         raise ValueError("pass metric= (the HIP metric launch) or metric_fn=, not both")
-    if metric not in (None, "ap", "mae"):
-        raise ValueError(f"metric must be 'ap', 'mae' or None, got {metric!r}")
+    from .. import metrics as _metrics
+    if metric not in _metrics.METRICS + (None,):
+        raise ValueError(f"metric must be one of {_metrics.METRICS} or None, got {metric!r}")
     if eval_graphs is not None and len(eval_graphs) != 2:
         raise ValueError("eval_graphs is the pair (validation graphs, test graphs)")
     dev = next(model.parameters()).device
@@ -196,11 +198,19 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
         run_info.update(optimizer=run.optimizer, flat=flat, in_graph=in_graph, schedule=schedule)
 
     steps, tail = G // B, G % B
-    C = ds.C
+    y_static = batching.targets(model, ds.static.batch)
+    class_index = batching.class_index_targets(y_static)
+    if metric is not None and (metric in _metrics.CLASS_METRICS) != class_index:
+        raise ValueError(f"metric {metric!r} does not fit the targets ('accuracy' / 'f1_macro' take class indices, "
+                         "'ap' / 'mae' [G, C] targets)")
+    C = batching.score_width(model, y_static)
     loss_log = torch.zeros(num_batches, dtype=torch.float32, device=dev)
     want_metric = metric_fn is not None or metric is not None
     scores = torch.zeros(G, C, dtype=torch.float32, device=dev) if want_metric else None
-    targets = torch.zeros(G, C, dtype=torch.float32, device=dev) if want_metric else None
+    targets = None
+    if want_metric:
+        targets = torch.zeros(G, dtype=torch.int64, device=dev) if class_index else \
+            torch.zeros(G, C, dtype=torch.float32, device=dev)
 
     def record(i: int, lo: int, loss, score, y) -> None:
         loss_log[i].copy_(loss)
@@ -210,11 +220,10 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
 
     eval_metric_fn = metric_fn
     if metric is not None:
-        from .. import metrics as _metrics
         train_metric = _metrics.metric_buffers(metric, G, C, dev)
         train_loss = train_metric.packed[20:24].view(torch.float32)     # beside result and flags: one read-back
-        launch = _metrics.average_precision_launch if metric == "ap" else _metrics.mean_absolute_error_launch
-        eval_metric_fn = _metrics.eval_ap_hip if metric == "ap" else _metrics.eval_mae_hip    # (host loaders)
+        launch = _metrics.metric_launch(metric)
+        eval_metric_fn = _metrics.eval_hip(metric)                      # (host loaders)
     eval_sources = eval_loaders or []
     if eval_graphs is not None:
         from .eval_resident import DeviceEvaluator
@@ -236,7 +245,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
             train_loss.copy_(loss_log.mean())
             f64, i32 = _metrics.read_packed(train_metric.packed)      # the epoch's only read-back
             mean_loss = float(i32[1:2].view(torch.float32)[0])
-            perf = _metrics.metric_value(metric, float(f64[0]), int(i32[0]))
+            perf = _metrics.metric_value(metric, float(f64[_metrics.result_index(metric)]), int(i32[0]))
         else:
             mean_loss = float(loss_log.mean().item())                 # the epoch's only read-back
             perf = metric_fn(targets, scores) if metric_fn else float("nan")
@@ -247,4 +256,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
                 stopper.evaluate(epoch, logger, model, eval_sources, eval_metric_fn, eval_history):
             break
     ds.check()
+    if class_index:
+        step.step.check()                      # (class indices outside [0, C): the captured step's flag word ...
+        check_class_targets(dev)               # ... and the eager tail's, loss.class_target_flags)
     return history

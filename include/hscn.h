@@ -441,6 +441,27 @@ int hscn_criterion_fwd(const float* pred, const float* target, int64_t count, in
                        void* stream);
 int hscn_scale(const float* g /*[1]*/, const float* x, float* y, int64_t count, void* stream);
 
+/* The multiclass branch of the same criterion (loss.py:11-14: nll_loss(log_softmax(pred, -1), true), class-index
+ * targets, mean reduction, no class weights, no ignore_index), csrc/loss.hip.  Purely additive to ABI 23.
+ *   pred [R, C] f32 row-major, target [R] i64;  1 <= C <= 1024 (HSCN_E_BADARG beyond: a row is held by one 64-lane
+ *   group, 16 columns per lane), R >= 1 is not bounded by a workgroup (a per-node [N, C] prediction is served).
+ *   logp [R, C] (may be NULL) = pred - max - log sum exp(pred - max), the "score" the reference returns;
+ *   loss [1] = -(1/R) sum_r logp[r, target[r]];  grad [R, C] = (exp(logp) - onehot(target)) / R = dloss/dpred.
+ *   flags [1] i32: the call ORs bits IN (the caller zeroes the word when it wants a fresh reading):
+ *     bit 0 = a target outside [0, C) -- that row adds nothing to the loss, its gradient row is zero, its logp row
+ *     is still written, nothing is read out of bounds; bit 1 = a NaN in pred.
+ *   Rows map to aligned lane groups of the smallest power of two >= C (64 for C > 64); a workgroup owns 256 rows.
+ *   R <= 256 is ONE launch.  Beyond, every workgroup writes its partial sum to `workspace`
+ *   (hscn_softmax_nll_workspace_bytes(R, C) bytes: 4 per workgroup, 0 for R <= 256 -- workspace may then be NULL;
+ *   0 also for arguments the call refuses) and a one-workgroup launch adds them in index order.  No float atomics:
+ *   two calls on the same input give the same bits.  HSCN_E_BADARG for R < 1, C outside [1, 1024], a NULL pred,
+ *   target, loss, grad or flags, or a NULL workspace where one is needed; HSCN_E_WORKSPACE for one too small; all
+ *   before any launch. */
+size_t hscn_softmax_nll_workspace_bytes(int64_t R, int C);
+int hscn_softmax_nll_fwd(const float* pred, const int64_t* target, int64_t R, int C, float* loss /*[1]*/,
+                         float* logp /*[R,C] or NULL*/, float* grad /*[R,C]*/, int32_t* flags /*[1]*/,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * a10  HSCN.forward / backward, graph-resident engine
  * (reference model/hscn.py:102-114 with lv=GAT, ll=GCN, vv=GCN; the loop
@@ -1001,12 +1022,29 @@ int hscn_signnet_encode(const float* x, const float* eigvecs, const int64_t* edg
  * hscn_mean_absolute_error: metrics.py:30-36 eval_mae = the float64 mean of |y_true - y_pred| over [G, C] (one
  *   workgroup, per-thread strided sums folded by a fixed tree).  result [2] f64 = { mean, G * C },
  *   flags [1] i32: bit 1 = a NaN prediction.
+ *
+ * hscn_multiclass_metrics: accuracy and macro-F1 of class-index targets (the metrics of the criterion's multiclass
+ *   branch; scikit-learn's accuracy_score and f1_score(average="macro")).  target [G] i64, score [G, C] f32
+ *   row-major (any score that ranks the classes: logits, log-probabilities), 1 <= C <= 128 (the confusion matrix
+ *   fits 64 KB of LDS), G <= 2^30.  The predicted class of a row is its FIRST maximal column (numpy's argmax).
+ *     confusion [C, C] i32, rows = true class, columns = predicted class (zeroed by the call; integer adds, in LDS
+ *       per workgroup, then into this matrix: deterministic),
+ *     per_class [C] f64 = F1 of each class = 2 tp / (rows with that target + rows with that prediction), 0 where tp
+ *       is 0,
+ *     result [2] f64 = { accuracy = trace / G; macro-F1 = the mean of per_class over the classes that occur among
+ *       the targets or the predictions, added in class order },
+ *     flags [1] i32 (written by the call): bit 1 = a NaN score; bit 2 = a target outside [0, C) (the row is left
+ *       out of the matrix, G still divides).
+ *   Three launches on the stream (zero, count, finish).  HSCN_E_BADARG for null pointers, G < 1, G > 2^30 or C
+ *   outside [1, 128], before any launch.
  * ------------------------------------------------------------------------- */
 size_t hscn_average_precision_workspace_bytes(int64_t G, int C);
 int hscn_average_precision(const float* y_true, const float* y_score, int64_t G, int C, double* ap, int32_t* valid,
                            double* result, int32_t* flags, void* workspace, size_t workspace_bytes, void* stream);
 int hscn_mean_absolute_error(const float* y_true, const float* y_pred, int64_t G, int C, double* result,
                              int32_t* flags, void* stream);
+int hscn_multiclass_metrics(const int64_t* target, const float* score, int64_t G, int C, int32_t* confusion /*[C,C]*/,
+                            double* result /*[2]*/, double* per_class /*[C]*/, int32_t* flags /*[1]*/, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Laplacian statistics of the SignNet positional encoding (reference transform/posenc.py:14-107:
