@@ -163,6 +163,16 @@ _SIGNATURES = {
     "hscn_softmax_nll_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "hscn_softmax_nll_fwd": (c_int, [P, P, c_int64, c_int, P, P, P, P, P, c_size_t, P]),
     "hscn_multiclass_metrics": (c_int, [P, P, c_int64, c_int, P, P, P, P, P]),
+    # class weights / ignore_index of the multiclass criterion and the per-node head (csrc/loss.hip,
+    # csrc/node_head.hip; additive to ABI 23)
+    "hscn_class_weights": (c_int, [P, c_int64, c_int, c_int64, c_int, P, P, P, P, P, P]),
+    "hscn_softmax_nll_fwd_ex": (c_int, [P, P, c_int64, c_int, P, c_int64, P, P, P, P, P, P, c_size_t, P]),
+    "hscn_node_head_supported": (c_int, [c_int, c_int]),
+    "hscn_node_head_rows_per_workgroup": (c_int, []),
+    "hscn_node_head_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "hscn_node_head_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, P, P]),
+    "hscn_node_head_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, c_int, P,
+                                   c_size_t, P]),
     "hscn_vl_forward": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
                                 c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
                                 P, c_int, c_float, P, P, P, P, P, P, P]),

@@ -75,8 +75,12 @@ class MPNNConfig:  # config.py:49-73
     dropout: float = DROPOUT
     use_batch_norm: bool = USE_BATCH_NORM
     use_layer_norm: bool = USE_LAYER_NORM
+    # extension: "node" = one prediction per node (model/mpnn.py MPNN(task_level="node")); "graph": the reference
+    task_level: str = "graph"
 
     def __post_init__(self):
+        if self.task_level not in ("graph", "node"):
+            raise ValueError(f"task_level must be 'graph' or 'node', got {self.task_level!r}")
         if self.dropout and not (0.0 <= self.dropout <= 1.0):
             raise ValueError(f"{self.dropout} must be between 0.0 and 1.0.")
         for v in (self.num_layers, self.hidden_channels):
@@ -95,11 +99,16 @@ class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent
     num_clusters: int = NUM_CLUSTERS
     cluster_epochs: int = CLUSTER_EPOCHS
     mp_units: list = field(default_factory=lambda: [16])
+    # extension (keyword-only, so the positional order above and below is what it was): "node" = one prediction per
+    # local node (model/hscn.py HSCN(task_level="node")); "graph": the reference
+    task_level: str = field(default="graph", kw_only=True)
     # extension: the ("virtual", "to", "local") relation the reference never wired up (None: the reference's model,
     # whose virtual branch does not reach the prediction; "GAT": model/hscn.py HSCN(vl_conv="GAT"))
     vl_conv_type: Optional[str] = None
 
     def __post_init__(self):
+        if self.task_level not in ("graph", "node"):
+            raise ValueError(f"task_level must be 'graph' or 'node', got {self.task_level!r}")
         for v in (self.num_layers, self.hidden_channels):
             if v < 0:
                 raise ValueError(f"{v} must be non-negative.")

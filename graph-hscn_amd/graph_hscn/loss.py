@@ -6,7 +6,10 @@ of the graph-resident HSCN forward arrives with its score, and the loss and its 
 are evaluated inside the backward launch of the same step (``LazyLoss``).  The multiclass branch
 (``true.ndim == 1``: class-index targets) is one fused launch as well (log-softmax + NLL: loss, the
 log-probabilities it returns as the score, dL/dpred; ``hscn_softmax_nll_fwd``).  CPU tensors use the
-plain torch ops the reference uses.  Quirk kept: the L1 branch scores with ``sigmoid(pred)``
+plain torch ops the reference uses.  Class weights and ``ignore_index`` (``criterion(..., class_weight=,
+ignore_index=)``, ``loss_fn="weighted_cross_entropy"``: LRGB's per-batch weights) are two calls on the device --
+``hscn_class_weights`` leaves the counts, the weights and the denominator there, ``hscn_softmax_nll_fwd_ex`` divides by
+it -- and ``F.cross_entropy`` with the same weights on the CPU.  Quirk kept: the L1 branch scores with ``sigmoid(pred)``
 (loss.py:17-19).
 
 A class index outside ``[0, C)`` raises ``IndexError`` in torch at once; the launch cannot raise, it
@@ -276,8 +279,115 @@ def _multiclass_on_device(pred: torch.Tensor, true: torch.Tensor) -> bool:
             and true.device == pred.device and true.size(0) == pred.size(0) and pred.numel() > 0)
 
 
-def criterion(loss_fn: str, pred: torch.Tensor, true: torch.Tensor):
+CW_NONE, CW_GIVEN, CW_BATCH = 0, 1, 2       # `mode` of hscn_class_weights (include/hscn.h)
+_NO_IGNORE = -(1 << 63)                      # an ignore_index no int64 target written by a loader takes: nothing ignored
+
+
+def launch_class_weights(true, C, ignore_index, mode, weight_in, counts, weight, denom, flags) -> None:
+    """``hscn_class_weights`` on ``true`` [R] int64 into preallocated ``counts`` [C] int32, ``weight`` [C] float32 and
+    ``denom`` [1] float64."""
+    call("hscn_class_weights", ptr(true), true.numel(), C, ignore_index, mode, ptr(weight_in), ptr(counts), ptr(weight),
+         ptr(denom), ptr(flags), stream())
+
+
+def launch_softmax_nll_ex(pred, true, weight, ignore_index, denom, loss, logp, grad, flags, workspace) -> None:
+    """``hscn_softmax_nll_fwd_ex`` into preallocated outputs; ``denom`` is what ``launch_class_weights`` wrote."""
+    R, C = pred.shape
+    call("hscn_softmax_nll_fwd_ex", ptr(pred), ptr(true), R, C, ptr(weight), ignore_index, ptr(denom), ptr(loss),
+         ptr(logp), ptr(grad), ptr(flags), ptr(workspace), workspace.numel() if workspace is not None else 0, stream())
+
+
+def _weight_mode(class_weight, C, device):
+    """``(mode, weight_in)`` of ``hscn_class_weights`` for a ``class_weight`` of None, "batch" or a [C] tensor."""
+    if class_weight is None:
+        return CW_NONE, None
+    if isinstance(class_weight, str):
+        if class_weight != "batch":
+            raise ValueError(f"class_weight must be None, 'batch' or a [C] tensor, not {class_weight!r}")
+        return CW_BATCH, None
+    w = torch.as_tensor(class_weight)
+    if w.dim() != 1 or w.numel() != C:
+        raise ValueError(f"class_weight must have one entry per class ({C}), got shape {tuple(w.shape)}")
+    return CW_GIVEN, w.to(device=device, dtype=torch.float32).contiguous()
+
+
+class _WeightedSoftmaxNllFn(Function):
+    """The multiclass branch with class weights and / or ``ignore_index``: the counts, the weights and the
+    denominator stay on the device (``hscn_class_weights``), the fused row launch divides by it
+    (``hscn_softmax_nll_fwd_ex``); the backward is ``_SoftmaxNllFn``'s."""
+
+    @staticmethod
+    def forward(ctx, pred, true, mode, weight_in, ignore_index):
+        pred, true = pred.contiguous(), true.contiguous()
+        dev, (R, C) = pred.device, pred.shape
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        logp, grad = torch.empty_like(pred), torch.empty_like(pred)
+        counts = torch.empty(C, dtype=torch.int32, device=dev)
+        weight = torch.empty(C, dtype=torch.float32, device=dev)
+        denom = torch.empty(1, dtype=torch.float64, device=dev)
+        flags = class_target_flags(dev)
+        launch_class_weights(true, C, ignore_index, mode, weight_in, counts, weight, denom, flags)
+        launch_softmax_nll_ex(pred, true, None if mode == CW_NONE else weight, ignore_index, denom, loss, logp, grad,
+                              flags, softmax_nll_workspace(R, C, dev))
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(logp)
+        ctx.set_materialize_grads(False)
+        return loss.view(()), logp
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_logp):
+        (grad,) = ctx.saved_tensors
+        if g_loss is None:
+            return None, None, None, None, None
+        return LazyScaled(grad, g_loss.reshape(1).contiguous()), None, None, None, None
+
+
+def batch_class_weights(true: torch.Tensor, C: int, ignore_index=None) -> torch.Tensor:
+    """LRGB's ``weighted_cross_entropy`` weights in plain torch ops: with V the counted rows and n_c the rows of class
+    c, ``(V - n_c).float() / V`` on the classes present and 0 elsewhere."""
+    kept = true if ignore_index is None else true[true != ignore_index]
+    n = torch.bincount(kept, minlength=C)[:C]
+    V = int(kept.numel())
+    return (V - n).float() / V * (n > 0).float()
+
+
+def _weighted_cross_entropy_torch(pred, true, class_weight, ignore_index):
+    """The rule of the device path restated with torch ops (CPU tensors; the reference of the tests)."""
+    C = pred.size(-1)
+    if isinstance(class_weight, str):
+        if class_weight != "batch":
+            raise ValueError(f"class_weight must be None, 'batch' or a [C] tensor, not {class_weight!r}")
+        weight = batch_class_weights(true, C, ignore_index).to(pred.dtype)
+    else:
+        weight = None if class_weight is None else torch.as_tensor(class_weight).to(device=pred.device, dtype=pred.dtype)
+    logp = F.log_softmax(pred, dim=-1)
+    loss = F.cross_entropy(pred, true, weight=weight, ignore_index=-100 if ignore_index is None else ignore_index)
+    return loss, logp
+
+
+def criterion(loss_fn: str, pred: torch.Tensor, true: torch.Tensor, *, class_weight=None, ignore_index=None):
+    """``class_weight`` / ``ignore_index`` (extensions, class-index targets only): ``F.cross_entropy``'s ``weight``
+    and ``ignore_index``; ``class_weight="batch"`` derives the weights from the batch's own class counts (LRGB's
+    ``weighted_cross_entropy``), which ``loss_fn="weighted_cross_entropy"`` selects by itself."""
+    if loss_fn == "weighted_cross_entropy":
+        if true.ndim != 1 or pred.ndim != 2:
+            raise ValueError("weighted_cross_entropy takes class-index targets [R] and a prediction [R, C]")
+        loss_fn = "cross_entropy"
+        if class_weight is None:
+            class_weight = "batch"
     multiclass = loss_fn == "cross_entropy" and pred.ndim > 1 and true.ndim == 1
+    if class_weight is not None or ignore_index is not None:
+        if not multiclass:
+            raise ValueError("class_weight / ignore_index belong to the multiclass criterion (cross_entropy on "
+                             "class-index targets)")
+        if _multiclass_on_device(pred, true):
+            mode, weight_in = _weight_mode(class_weight, pred.size(1), pred.device)
+            return _WeightedSoftmaxNllFn.apply(pred, true, mode, weight_in,
+                                               _NO_IGNORE if ignore_index is None else int(ignore_index))
+        if pred.is_cuda:
+            raise RuntimeError("the weighted multiclass criterion on the device takes a float32 [R, C] prediction and "
+                               "int64 [R] targets on the same device")
+        return _weighted_cross_entropy_torch(pred, true, class_weight, ignore_index)
     if multiclass and _multiclass_on_device(pred, true):
         return _SoftmaxNllFn.apply(pred, true)
     if pred.is_cuda and not multiclass and pred.dtype == torch.float32 and pred.shape == true.shape:

@@ -96,7 +96,10 @@ def eval_f1_macro(y_true: torch.Tensor, y_pred: torch.Tensor) -> float:
     support = conf.sum(1) + conf.sum(0)                  # rows with that target + rows with that prediction
     present = support > 0
     f1 = torch.where(tp > 0, 2.0 * tp / support.clamp(min=1.0), torch.zeros_like(tp))
-    return float(f1[present].sum().item() / float(present.sum().item()))
+    total = 0.0
+    for v in f1[present].tolist():                       # in class order, as hscn_multiclass_metrics adds them
+        total += v
+    return total / float(present.sum().item())
 
 
 # ---- the same two metrics as HIP launches (csrc/metrics.hip; include/hscn.h) ------------------------------------------

@@ -250,8 +250,15 @@ def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None) 
 
 class HSCN(nn.Module):
     def __init__(self, lv_conv: str, ll_conv: str, vv_conv: str, activation: Callable, num_features: int,
-                 hidden_channels: int, num_classes: int, num_layers: int, vl_conv: Optional[str] = None) -> None:
-        """``vl_conv`` (extension; the default ``None`` is the reference's model, bit for bit): "GAT" gives every
+                 hidden_channels: int, num_classes: int, num_layers: int, vl_conv: Optional[str] = None,
+                 task_level: str = "graph") -> None:
+        """``task_level`` (extension; the default "graph" is the reference's model): "node" skips the mean pool and
+        applies the head ``lin_2(act(lin_1(.)))`` to every local node, returning ``[N, C]`` (``nn.head.NodeHead``: the
+        one-launch head where ``hscn_node_head_supported`` says so, else the two ``Linear`` modules).  The convolution
+        stack runs on the layered operators; the graph-resident launches, which end in the pooled head, refuse such a
+        model.
+
+        ``vl_conv`` (extension; the default ``None`` is the reference's model, bit for bit): "GAT" gives every
         layer a fourth convolution on the relation ("virtual", "to", "local") -- the lv edge list reversed, derived in
         ``forward`` when the batch does not carry it -- so that the clusters act as long-range shortcuts and the
         virtual branch reaches the prediction.  Every local node has exactly one such in-edge, so the attention weight
@@ -262,7 +269,10 @@ class HSCN(nn.Module):
         super().__init__()
         if vl_conv is not None and vl_conv != "GAT":
             raise ValueError(f"vl_conv must be None or 'GAT', not {vl_conv!r} (a bipartite GCNConv does not exist)")
+        if task_level not in ("graph", "node"):
+            raise ValueError(f"task_level must be 'graph' or 'node', not {task_level!r}")
         self.vl_conv = vl_conv
+        self.task_level = task_level
         self.activation = activation
         self.convs = nn.ModuleList()
         for layer in range(num_layers):
@@ -286,6 +296,19 @@ class HSCN(nn.Module):
         self.overlap_virtual = os.environ.get("HSCN_OVERLAP_VIRTUAL", "1") != "0"
         self.last_virtual: Optional[Tensor] = None
         self.last_engine: Optional[str] = None
+        self.node_head = None
+        if task_level == "node" and _act_name(activation) in ACT_DICT:
+            from ..nn.head import NodeHead
+            # (a plain object: the parameters stay lin_1 / lin_2 and the state_dict the graph-level model's)
+            self.node_head = NodeHead(self.lin_1, self.lin_2, _act_name(activation))
+
+    NODE_LEVEL_REASON = ("a node-level head (task_level='node'): the one-launch and graph-resident kernels end in the "
+                         "mean pool and the per-graph head, a per-node prediction runs on the layered operators")
+
+    def _refuse_node_level(self, what: str) -> None:
+        """The resident launches pool: they must refuse a node-level model, never pool silently."""
+        if self.task_level == "node":
+            raise RuntimeError(f"{what} does not take this model: {self.NODE_LEVEL_REASON}")
 
     def _refuse_vl(self, what: str) -> None:
         """The hscn_resident_* launches know three relations: they must refuse a model with a fourth, never drop it."""
@@ -297,6 +320,10 @@ class HSCN(nn.Module):
 
     def _resident_plan(self, x_dict, edge_index_dict, batch):
         if self.engine == "layered":
+            return None
+        if self.task_level == "node":
+            if self.engine == "resident":
+                self._refuse_node_level("engine='resident'")
             return None
         if self.vl_conv is not None:
             if self.engine == "resident":
@@ -385,6 +412,8 @@ class HSCN(nn.Module):
         """Why this model (and ``batch``, if given) cannot take the one-launch hscn_vl_* kernels, or None when it
         can.  ``hscn_vl_supported`` is the single source of truth for the sizes."""
         from .._hip import lib
+        if self.task_level == "node":
+            return self.NODE_LEVEL_REASON
         if self.vl_conv is None:
             return f"the model has no {VL_NAME} relation (the hscn_resident_* launches serve the reference's model)"
         if _act_name(self.activation) not in ACT_DICT:
@@ -452,13 +481,15 @@ class HSCN(nn.Module):
     def _forward_vl(self, x_dict, edge_index_dict, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if self.engine == "resident":
+            self._refuse_node_level("engine='resident'")
         if not self.compute_virtual:
             raise ValueError(f"compute_virtual=False is meaningless with the relation {VL_NAME}: the local update "
                              "reads the virtual features of every layer")
         if VL not in edge_index_dict:        # the data layer does not change: vl is lv reversed, appended last
             edge_index_dict = dict(edge_index_dict)
             edge_index_dict[VL] = edge_index_dict[LV].flip(0)
-        if self.engine != "layered":
+        if self.engine != "layered" and self.task_level != "node":
             if torch.is_grad_enabled():
                 if self.engine == "resident":
                     self._refuse_vl("engine='resident' with gradients on (the hscn_resident_* autograd launches)")
@@ -490,10 +521,15 @@ class HSCN(nn.Module):
         for conv in self.convs:
             x_dict = conv(x_dict, edge_index_dict)
             x_dict = {key: relu(x) for key, x in x_dict.items()}           # hscn.py:110 (hard-coded ReLU)
+        name = _act_name(self.activation)
+        if self.task_level == "node":                                      # the head on every local node: no pool
+            x = x_dict["local"]
+            if self.node_head is not None:
+                return self.node_head(x)
+            return self.lin_2(self.activation(self.lin_1(x)))
         local = batch["local"]
         size = getattr(batch, "num_graphs", None) or None
         x = global_mean_pool(x_dict["local"], local.batch, size)           # hscn.py:111
-        name = _act_name(self.activation)
         if name is not None:
             x = self.lin_1(x, act=name)                                    # hscn.py:112 fused epilogue
         else:
@@ -512,4 +548,5 @@ def build_hscn(model_cfg: HSCNConfig, num_features: int, num_classes: int) -> HS
         num_classes,
         model_cfg.num_layers,
         getattr(model_cfg, "vl_conv_type", None),
+        getattr(model_cfg, "task_level", "graph"),
     )

@@ -29,8 +29,13 @@ from ..nn.pool import global_mean_pool
 class MPNN(nn.Module):
     def __init__(self, conv: type, activation: Callable, num_features: int, hidden_channels: int,
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
-                 use_layer_norm: bool = False) -> None:
+                 use_layer_norm: bool = False, task_level: str = "graph") -> None:
+        """``task_level`` (extension; the default "graph" is the reference's model): "node" returns the last
+        convolution's ``[N, C]`` without the per-graph mean."""
         super().__init__()
+        if task_level not in ("graph", "node"):
+            raise ValueError(f"task_level must be 'graph' or 'node', not {task_level!r}")
+        self.task_level = task_level
         self.num_layers = num_layers
         self.conv_layers = nn.ModuleList()                                  # mpnn.py:27-32
         self.conv_layers.append(conv(num_features, hidden_channels))
@@ -55,6 +60,9 @@ class MPNN(nn.Module):
 
     def resident_reason(self, batch=None, need_grad: bool = False) -> Optional[str]:
         """Why this model (and ``batch``, if given) cannot take the one-launch MPNN kernels, or None when it can."""
+        if self.task_level == "node":
+            return ("a node-level head (task_level='node'): the one-launch kernels end in the per-graph mean, a "
+                    "per-node prediction runs on the layered operators")
         name = getattr(self.activation, "hscn_name", None)
         if name not in ("relu", "elu", "identity", "tanh"):
             return f"activation {name!r} (relu, elu, identity and tanh are supported)"
@@ -124,6 +132,8 @@ class MPNN(nn.Module):
     def forward(self, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if self.engine == "resident" and self.task_level == "node":
+            raise RuntimeError(f"engine='resident' does not take this model: {self.resident_reason()}")
         if self.engine != "layered" and not torch.is_grad_enabled():
             reason = self.resident_reason(batch)
             if reason is None and self.training and self.dropout > 0:
@@ -148,6 +158,8 @@ class MPNN(nn.Module):
             seed = None if self.dropout_seed is None else self.dropout_seed + i
             x = Fh.dropout(x, p=self.dropout, training=self.training, seed=seed)
         x = self.conv_layers[-1](x, edge_index)
+        if self.task_level == "node":
+            return x
         size = getattr(batch, "num_graphs", None)
         return global_mean_pool(x, batch_vec, size)                         # scatter_mean(x, batch, dim=0)
 
@@ -155,4 +167,4 @@ class MPNN(nn.Module):
 def build_mpnn(model_cfg: MPNNConfig, num_features: int, num_classes: int) -> MPNN:  # mpnn.py:65-78
     return MPNN(CONV_DICT[model_cfg.conv_type.lower()], ACT_DICT[model_cfg.activation.lower()], num_features,
                 model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.dropout,
-                model_cfg.use_batch_norm, model_cfg.use_layer_norm)
+                model_cfg.use_batch_norm, model_cfg.use_layer_norm, getattr(model_cfg, "task_level", "graph"))

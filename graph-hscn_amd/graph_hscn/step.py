@@ -89,6 +89,7 @@ class ResidentTrainStep(_FlatGradStep):
         from .model.hscn import HSCN, _act_name
         if not isinstance(model, HSCN):
             raise TypeError("ResidentTrainStep drives graph_hscn.model.hscn.HSCN")
+        model._refuse_node_level("ResidentTrainStep (hscn_resident_*)")
         model._refuse_vl("ResidentTrainStep (hscn_resident_*)")
         x_dict, ei_dict = batch.x_dict, batch.edge_index_dict
         dev = x_dict["local"].device

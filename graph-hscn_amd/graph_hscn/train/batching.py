@@ -31,16 +31,32 @@ def class_index_targets(y: Optional[Tensor]) -> bool:
 
 def score_width(model, y: Tensor) -> int:
     """Columns of the score ``criterion`` returns for targets ``y``: ``y``'s own for ``[B, C]`` targets; for class
-    indices the width of the model's head (HSCN: ``lin_2``)."""
+    indices the width of the model's head (HSCN: ``lin_2``; a node-level MPNN: its last convolution)."""
     if not class_index_targets(y):
         return int(y.size(1))
+    if not is_hetero(model) and node_level(model):
+        return int(model.resident_dims()[2])
     if not is_hetero(model):
         raise ValueError("class-index targets are served for HSCN (the reference model) only")
     return int(model.lin_2.out_channels)
 
 
+def node_level(model) -> bool:
+    return getattr(model, "task_level", "graph") == "node"
+
+
+def refuse_node_level(model, what: str) -> None:
+    """The one-launch and captured steps, ``fit_resident`` and ``DeviceEvaluator`` end in the per-graph pool: they
+    refuse a node-level model by name, before anything is launched or captured -- they never pool silently."""
+    if node_level(model):
+        raise RuntimeError(f"{what} does not take this model: {model.resident_reason()} (train.train runs it)")
+
+
 def forward(model, batch) -> Tuple[Tensor, Tensor]:
-    """``(pred, targets)`` of ``model`` on a batch that is on the model's device."""
+    """``(pred, targets)`` of ``model`` on a batch that is on the model's device.  A node-level model
+    (``task_level="node"``) answers ``[N, C]`` and the targets are the per-node labels."""
+    if node_level(model) and model.engine == "resident":
+        refuse_node_level(model, "engine='resident'")
     if is_hetero(model):
         if getattr(model, "vl_conv", None) is not None and torch.is_grad_enabled() and model.engine == "resident":
             # the eager tail of a device loop: with gradients on this model runs through the layered operators
@@ -77,6 +93,7 @@ def resident_step(model, batch, loss_fn: str, one_launch: Optional[bool] = None,
     """The resident training step of ``model`` on a static batch (``step.ResidentTrainStep``; the MPNN baseline's or
     the vl model's one launch, which have neither a launch pair nor a structure to load)."""
     from ..step import MPNNResidentTrainStep, ResidentTrainStep, VLResidentTrainStep
+    refuse_node_level(model, "the resident training step")
     if targets(model, batch) is None:
         raise ValueError("the static batch carries no targets")
     if not is_hetero(model):

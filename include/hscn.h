@@ -442,7 +442,7 @@ int hscn_criterion_fwd(const float* pred, const float* target, int64_t count, in
 int hscn_scale(const float* g /*[1]*/, const float* x, float* y, int64_t count, void* stream);
 
 /* The multiclass branch of the same criterion (loss.py:11-14: nll_loss(log_softmax(pred, -1), true), class-index
- * targets, mean reduction, no class weights, no ignore_index), csrc/loss.hip.  Purely additive to ABI 23.
+ * targets, mean reduction; class weights and ignore_index: hscn_softmax_nll_fwd_ex below), csrc/loss.hip.  Purely additive to ABI 23.
  *   pred [R, C] f32 row-major, target [R] i64;  1 <= C <= 1024 (HSCN_E_BADARG beyond: a row is held by one 64-lane
  *   group, 16 columns per lane), R >= 1 is not bounded by a workgroup (a per-node [N, C] prediction is served).
  *   logp [R, C] (may be NULL) = pred - max - log sum exp(pred - max), the "score" the reference returns;
@@ -461,6 +461,73 @@ size_t hscn_softmax_nll_workspace_bytes(int64_t R, int C);
 int hscn_softmax_nll_fwd(const float* pred, const int64_t* target, int64_t R, int C, float* loss /*[1]*/,
                          float* logp /*[R,C] or NULL*/, float* grad /*[R,C]*/, int32_t* flags /*[1]*/,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* Class weights and ignore_index of the multiclass criterion (F.cross_entropy(pred, true, weight=w, ignore_index=i);
+ * LRGB's weighted_cross_entropy), csrc/loss.hip.  Two calls; nothing is read back by the host.  Purely additive to
+ * ABI 23.
+ *
+ * hscn_class_weights: target [R] i64, 1 <= R < 2^31, 1 <= C <= 1024.  A row equal to ignore_index is not counted and
+ *   raises no flag; any other row outside [0, C) ORs bit 0 into flags (the word of hscn_softmax_nll_fwd) and is not
+ *   counted.
+ *     counts [C] i32 (zeroed by the call): rows per class -- a per-workgroup LDS histogram, then integer adds: any
+ *       order gives the same bits;
+ *     weight [C] f32: mode HSCN_CW_NONE = ones; HSCN_CW_GIVEN = weight_in [C] copied; HSCN_CW_BATCH = with V the
+ *       number of counted rows and n_c = counts[c]: (float)(V - n_c) / (float)V where n_c > 0, else 0 (float32
+ *       division, round to nearest: torch's (V - n).float() / V);
+ *     denom [1] f64 = sum_c n_c * weight[c], added in double in class order by one thread.
+ *   Three launches on the stream (zero, count, finish).  HSCN_E_BADARG for null pointers (weight_in may be NULL
+ *   unless mode is HSCN_CW_GIVEN), R or C outside their ranges or an unknown mode, before any launch.
+ *
+ * hscn_softmax_nll_fwd_ex: hscn_softmax_nll_fwd with weight [C] f32 (or NULL: ones), ignore_index and denom [1] f64,
+ *   the DEVICE value hscn_class_weights wrote for the same targets:
+ *     loss = sum over the counted rows of weight[target] * (-logp[r, target]) / denom;
+ *     grad row = weight[target] * (exp(logp) - onehot(target)) / denom for a counted row, zero for an ignored row or
+ *       one whose target is out of range (bit 0 of flags; an ignored row raises nothing); logp is written for every
+ *       row.
+ *   The same row mapping, workspace (hscn_softmax_nll_workspace_bytes) and ordered fold.  With weight = NULL and no
+ *   row ignored denom is R and loss, logp and grad are hscn_softmax_nll_fwd's, bit for bit.
+ *   denom == 0 (every row ignored, or every class present has weight 0 -- HSCN_CW_BATCH with one class present) is
+ *   what torch computes on the CPU, 0 / 0: the loss is NaN, the gradient of a counted row is NaN (0 * inf) and that
+ *   of an ignored row 0.
+ *   HSCN_E_BADARG / HSCN_E_WORKSPACE as hscn_softmax_nll_fwd, and HSCN_E_BADARG for a NULL denom. */
+#define HSCN_CW_NONE 0
+#define HSCN_CW_GIVEN 1
+#define HSCN_CW_BATCH 2
+int hscn_class_weights(const int64_t* target, int64_t R, int C, int64_t ignore_index, int mode,
+                       const float* weight_in /*[C] or NULL*/, int32_t* counts /*[C]*/, float* weight /*[C]*/,
+                       double* denom /*[1]*/, int32_t* flags /*[1]*/, void* stream);
+int hscn_softmax_nll_fwd_ex(const float* pred, const int64_t* target, int64_t R, int C,
+                            const float* weight /*[C] or NULL*/, int64_t ignore_index, const double* denom /*[1]*/,
+                            float* loss /*[1]*/, float* logp /*[R,C] or NULL*/, float* grad /*[R,C]*/,
+                            int32_t* flags /*[1]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The per-node head of a node-level model, pred = lin_2(act(lin_1(x))) on every row of x [N, H]
+ * (graph_hscn.nn.head.NodeHead; csrc/node_head.hip).  Purely additive to ABI 23.
+ *   x [N, H], W1 [H, H], b1 [H], W2 [C, H], b2 [C], pred / g_pred [N, C], all f32 row-major; act: HSCN_ACT_*.
+ * hscn_node_head_supported: the envelope, H in {16, 32, 64} and 1 <= C <= 64 (the single source of truth: the two
+ *   launches answer HSCN_E_UNSUPPORTED outside it).
+ * hscn_node_head_fwd: ONE launch, a lane per row, hscn_node_head_rows_per_workgroup() = 256 rows per workgroup; the
+ *   hidden row stays in registers, only pred is written.  N = 0 launches nothing.
+ * hscn_node_head_bwd: one launch plus one ordered fold.  scale [1] (or NULL = 1): a device scalar g_pred is multiplied
+ *   by on the way in (a loss.LazyScaled gradient is consumed unmultiplied).  The hidden row is recomputed from x.
+ *   g_x [N, H] (or NULL: not wanted); gW1 [H, H], gb1 [H], gW2 [C, H], gb2 [C].  Every workgroup (at most 256; a
+ *   workgroup strides over the 256-row tiles) sums its rows' parameter terms in row order and writes them to its row
+ *   of `workspace` (hscn_node_head_workspace_bytes(N, H, C) = workgroups * (H + C) * (H + 1) * 4; 0 for arguments the
+ *   call refuses); a one-workgroup launch adds the rows in workgroup order and stores the four gradients, or with
+ *   accumulate = 1 adds the sum last into what they hold.  No float atomics: the same input gives the same bits.
+ *   x and g_x are read and written as float4: both must be 16-byte aligned (rows of H floats keep the alignment).
+ * HSCN_E_BADARG: null pointers, an x or g_x that is not 16-byte aligned, an unknown act, accumulate outside {0, 1},
+ *   N < 0 (fwd) / N < 1 (bwd) or N > 2^31; HSCN_E_UNSUPPORTED outside the envelope, or where the device refuses the
+ *   backward's LDS (up to 97 KB at H = C = 64); HSCN_E_WORKSPACE for a workspace too small; all before any launch. */
+int hscn_node_head_supported(int H, int C);
+int hscn_node_head_rows_per_workgroup(void);
+size_t hscn_node_head_workspace_bytes(int64_t N, int H, int C);
+int hscn_node_head_fwd(const float* x, const float* W1, const float* b1, const float* W2, const float* b2, int64_t N,
+                       int H, int C, int act, float* pred, void* stream);
+int hscn_node_head_bwd(const float* x, const float* W1, const float* b1, const float* W2, const float* b2,
+                       const float* g_pred, const float* scale /*[1] or NULL*/, int64_t N, int H, int C, int act,
+                       float* g_x /*[N,H] or NULL*/, float* gW1, float* gb1, float* gW2, float* gb2, int accumulate,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * a10  HSCN.forward / backward, graph-resident engine
