@@ -173,6 +173,16 @@ _SIGNATURES = {
     "hscn_node_head_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, P, P]),
     "hscn_node_head_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, c_int, P,
                                    c_size_t, P]),
+    # link-level tasks: the pair decoder and the per-graph ranking metric (csrc/edge_head.hip; additive to ABI 23)
+    "hscn_pair_dot_supported": (c_int, [c_int]),
+    "hscn_pair_dot_pairs_per_workgroup": (c_int, [c_int]),
+    "hscn_pair_dot_fwd": (c_int, [P, P, c_int64, c_int64, c_int, P, P, P]),
+    "hscn_pair_dot_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
+    "hscn_pair_rank_supported": (c_int, [c_int, c_int]),
+    "hscn_pair_rank_lds_max_nodes": (c_int, [c_int]),
+    "hscn_pair_rank_max_workgroups": (c_int, []),
+    "hscn_pair_rank": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
+    "hscn_pair_rank_reduce": (c_int, [P, c_int64, c_int, P, P, P, P, P]),
     "hscn_vl_forward": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
                                 c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
                                 P, c_int, c_float, P, P, P, P, P, P, P]),

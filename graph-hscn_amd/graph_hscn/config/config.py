@@ -46,6 +46,7 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv}
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
 SCHEDULERS = ("cosine_with_warmup", "linear_with_warmup", "step")  # extension: optim.SCHEDULE_KINDS
+TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "graph" only
 DATASETS_NUM_FEATURES: dict[str, int] = {"peptides_func": 9, "peptides_struct": 9}
 
 
@@ -75,12 +76,13 @@ class MPNNConfig:  # config.py:49-73
     dropout: float = DROPOUT
     use_batch_norm: bool = USE_BATCH_NORM
     use_layer_norm: bool = USE_LAYER_NORM
-    # extension: "node" = one prediction per node (model/mpnn.py MPNN(task_level="node")); "graph": the reference
+    # extension: "node" = one prediction per node (model/mpnn.py MPNN(task_level="node")); "link" = one score per
+    # candidate pair of nodes, num_classes being the embedding width; "graph": the reference
     task_level: str = "graph"
 
     def __post_init__(self):
-        if self.task_level not in ("graph", "node"):
-            raise ValueError(f"task_level must be 'graph' or 'node', got {self.task_level!r}")
+        if self.task_level not in TASK_LEVELS:
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         if self.dropout and not (0.0 <= self.dropout <= 1.0):
             raise ValueError(f"{self.dropout} must be between 0.0 and 1.0.")
         for v in (self.num_layers, self.hidden_channels):
@@ -100,15 +102,16 @@ class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent
     cluster_epochs: int = CLUSTER_EPOCHS
     mp_units: list = field(default_factory=lambda: [16])
     # extension (keyword-only, so the positional order above and below is what it was): "node" = one prediction per
-    # local node (model/hscn.py HSCN(task_level="node")); "graph": the reference
+    # local node (model/hscn.py HSCN(task_level="node")); "link" = one score per candidate pair of local nodes,
+    # num_classes being the embedding width; "graph": the reference
     task_level: str = field(default="graph", kw_only=True)
     # extension: the ("virtual", "to", "local") relation the reference never wired up (None: the reference's model,
     # whose virtual branch does not reach the prediction; "GAT": model/hscn.py HSCN(vl_conv="GAT"))
     vl_conv_type: Optional[str] = None
 
     def __post_init__(self):
-        if self.task_level not in ("graph", "node"):
-            raise ValueError(f"task_level must be 'graph' or 'node', got {self.task_level!r}")
+        if self.task_level not in TASK_LEVELS:
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         for v in (self.num_layers, self.hidden_channels):
             if v < 0:
                 raise ValueError(f"{v} must be non-negative.")
@@ -165,7 +168,8 @@ class PEConfig:  # config.py:115-130 (defaults.py:19-28)
 class TrainingConfig:  # config.py:133-152
     model_type: str
     loss_fn: str
-    # "ap" / "mae" (the reference's two), or "accuracy" / "f1_macro" for class-index targets (graph_hscn.metrics)
+    # "ap" / "mae" (the reference's two), "accuracy" / "f1_macro" for class-index targets, or "mrr" / "hits@1" /
+    # "hits@3" / "hits@10" for a link-level model (graph_hscn.metrics)
     metric: str
     epochs: int = EPOCHS
     eval_period: int = EVAL_PERIOD

@@ -100,7 +100,51 @@ def _cat_targets(ys: Sequence[Tensor]) -> Tensor:
 
 # what a Batch holds that is not a per-node extra of its graphs
 _BATCH_KEYS = frozenset(["x", "edge_index", "y", "edge_weight", "num_nodes", "batch", "ptr", "num_graphs", "ptr32",
-                         "eptr32", "max_nodes", "max_edges"])
+                         "eptr32", "max_nodes", "max_edges", "edge_label_index", "edge_label", "pair_ptr32",
+                         "max_pairs"])
+
+
+def has_link_labels(store) -> bool:
+    """Whether a graph (or a node store) carries link labels: candidate pairs ``edge_label_index`` [2, P] with
+    their labels ``edge_label`` [P]."""
+    return "edge_label_index" in store and store.edge_label_index is not None
+
+
+def check_link_labels(graph) -> None:
+    """``ValueError`` unless ``graph`` (a ``Data``, or the ``"local"`` store of a hetero graph) carries well-formed
+    link labels: ``edge_label_index`` int64 [2, P] with ids in [0, num_nodes), ``edge_label`` float32 [P] in {0, 1},
+    and no ordered pair twice.  Integer work on the host, for where datasets are built; never in the step."""
+    if not has_link_labels(graph) or "edge_label" not in graph or graph.edge_label is None:
+        raise ValueError("a link-labelled graph carries edge_label_index and edge_label")
+    idx, lab = graph.edge_label_index, graph.edge_label
+    if not isinstance(idx, Tensor) or idx.dtype != torch.int64 or idx.dim() != 2 or idx.size(0) != 2:
+        raise ValueError("edge_label_index must be an int64 [2, P] tensor")
+    if not isinstance(lab, Tensor) or lab.dtype != torch.float32 or lab.dim() != 1 or lab.size(0) != idx.size(1):
+        raise ValueError("edge_label must be a float32 [P] tensor, one label per candidate pair")
+    n = int(graph.num_nodes)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n):
+        raise ValueError(f"edge_label_index holds node ids outside [0, {n})")
+    if not bool(((lab == 0) | (lab == 1)).all()):
+        raise ValueError("edge_label must hold 0 or 1")
+    if torch.unique(idx[0] * n + idx[1]).numel() != idx.size(1):
+        raise ValueError("edge_label_index holds a candidate pair twice")
+
+
+def _collate_link_labels(out, stores: Sequence, offsets) -> None:
+    """``edge_label_index`` (node offsets added), ``edge_label``, ``pair_ptr32`` and ``max_pairs`` of a batch onto
+    ``out``, when every graph carries link labels; a list in which only some do is refused."""
+    have = [has_link_labels(s) for s in stores]
+    if not any(have):
+        return
+    if not all(have):
+        raise ValueError("some graphs of the batch carry edge_label_index and some do not")
+    ps = [int(s.edge_label_index.size(1)) for s in stores]
+    out.edge_label_index = torch.cat([s.edge_label_index + int(o) for s, o in zip(stores, offsets)], 1)
+    out.edge_label = torch.cat([s.edge_label for s in stores], 0)
+    pptr = torch.zeros(len(ps) + 1, dtype=torch.int32)
+    pptr[1:] = torch.cumsum(torch.as_tensor(ps, dtype=torch.int64), 0).to(torch.int32)
+    out.pair_ptr32 = pptr                        # pairs of graph g are [pair_ptr32[g], pair_ptr32[g + 1])
+    out.max_pairs = int(max(ps)) if ps else 0
 
 
 def _node_extras(graphs: Sequence[Data], ns: Sequence[int]) -> List[str]:
@@ -146,6 +190,7 @@ class Batch(Data):
         out.max_edges = int(max(es)) if es else 0
         for k in _node_extras(graphs, ns) if graphs else []:     # per-node extras, concatenated like x
             out._d[k] = torch.cat([g._d[k] for g in graphs], 0)
+        _collate_link_labels(out, graphs, ptr[:-1].tolist())
         return out
 
     def to_data_list(self) -> List[Data]:
@@ -160,6 +205,8 @@ class Batch(Data):
         extras = [k for k, v in self._d.items()
                   if k not in _BATCH_KEYS and isinstance(v, Tensor) and v.dim() >= 1 and v.size(0) == N]
         per_graph_y = y is not None and y.size(0) == B
+        pairs = self._d.get("edge_label_index")
+        pptr = [int(v) for v in self.pair_ptr32.tolist()] if pairs is not None else None
         if y is not None and not per_graph_y and y.size(0) != N:
             raise ValueError(f"target of {y.size(0)} rows belongs neither to {B} graphs nor to {N} nodes")
         out = []
@@ -173,6 +220,9 @@ class Batch(Data):
                 g.edge_weight = ew[ea:eb]
             for k in extras:
                 g._d[k] = self._d[k][a:b]
+            if pairs is not None:
+                g.edge_label_index = pairs[:, pptr[i]:pptr[i + 1]] - a
+                g.edge_label = self.edge_label[pptr[i]:pptr[i + 1]]
             out.append(g)
         return out
 
@@ -244,6 +294,8 @@ class HeteroBatch(HeteroData):
             st.num_nodes = int(ptr[-1])
             if all("y" in g[nt] and g[nt].y is not None for g in graphs):
                 st.y = _cat_targets([g[nt].y for g in graphs])
+            if nt == "local":                       # link labels travel on the local node type
+                _collate_link_labels(st, [g[nt] for g in graphs], ptr[:-1].tolist())
         for et in graphs[0].edge_types:
             s, _, d = et
             off = torch.stack([ptrs[s][:-1], ptrs[d][:-1]], 0)  # [2, B]

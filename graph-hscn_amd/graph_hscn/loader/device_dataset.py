@@ -22,7 +22,7 @@ import torch
 from torch import Tensor
 
 from .. import _hip
-from ..data import HeteroBatch, HeteroData
+from ..data import HeteroBatch, HeteroData, has_link_labels
 from ..replay import LL, LV, VV, StaticHeteroBatch
 
 _RELS = (LL, VV, LV)     # include/hscn.h: relation order of hscn_hetero_dataset / hscn_hetero_batch_out
@@ -57,6 +57,11 @@ class _DeviceDataset:
     def __init__(self, graphs: Sequence, device, batch_size: int):
         if not graphs:
             raise ValueError("empty dataset")
+        for g in graphs:      # (the gather launches know nothing of candidate pairs: refuse, never drop them)
+            store = g["local"] if isinstance(g, HeteroData) else g
+            if has_link_labels(store):
+                raise ValueError(f"{type(self).__name__} does not carry link labels (edge_label_index / edge_label): "
+                                 "a link-level model trains from host loaders (train.train)")
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())

@@ -18,15 +18,17 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from ..data import Data, DataLoader, HeteroData
+from ..data import Data, DataLoader, HeteroData, has_link_labels
 
 LL = ("local", "to", "local")
 VV = ("virtual", "to", "virtual")
 LV = ("local", "to", "virtual")
 
 
-def hetero_from_clusters(data: Data, clusters_raw: Sequence[int], num_clusters: int) -> HeteroData:
-    """One graph of the loop body hetero_data.py:42-87."""
+def hetero_from_clusters(data: Data, clusters_raw: Sequence[int], num_clusters: int,
+                         task_level: str = "graph") -> HeteroData:
+    """One graph of the loop body hetero_data.py:42-87.  ``task_level="link"``: the graph's candidate pairs and their
+    labels (``edge_label_index`` / ``edge_label``, local node ids) travel on the local node type."""
     clusters_raw = np.asarray(clusters_raw).reshape(-1)
     n = int(data.num_nodes)
     if clusters_raw.shape[0] != n:
@@ -56,12 +58,17 @@ def hetero_from_clusters(data: Data, clusters_raw: Sequence[int], num_clusters: 
     h[LV].edge_index = torch.from_numpy(np.stack([np.arange(n), inv]).astype(np.int64))   # :80-86
     h["local"].num_nodes = n
     h["virtual"].num_nodes = U
+    if task_level == "link":
+        if not has_link_labels(data):
+            raise ValueError("task_level='link' needs graphs with edge_label_index / edge_label")
+        h["local"].edge_label_index = data.edge_label_index
+        h["local"].edge_label = data.edge_label
     return h
 
 
 def _check_task_level(data_cfg) -> None:
     level = getattr(data_cfg, "task_level", "graph")
-    if level not in ("graph", "node"):
+    if level not in ("graph", "node", "link"):
         raise NotImplementedError(f"task_level {level!r} (graph- and node-level tasks are served)")
 
 
@@ -69,7 +76,8 @@ def generate_hetero_data(cluster_lst: list, dataset, split_idx: Dict[str, torch.
                          logger=None) -> List[HeteroData]:
     """hetero_data.py:14-88: graphs come back ordered train || val || test.  ``task_level="node"`` (extension: the
     reference raises NotImplementedError for it) is the same per-graph transform; ``y`` is then one label per local
-    node and travels on the local node type as it is."""
+    node and travels on the local node type as it is.  ``task_level="link"`` copies the candidate pairs and their
+    labels onto the local node type (``hetero_from_clusters``)."""
     _check_task_level(data_cfg)
     out: List[HeteroData] = []
     for split_name in ("train", "val", "test"):
@@ -77,7 +85,8 @@ def generate_hetero_data(cluster_lst: list, dataset, split_idx: Dict[str, torch.
             logger.info(f"Generating heterogeneous dataset with virtual nodes for {split_name} split...")
         for i in split_idx[split_name]:
             i = int(i)
-            out.append(hetero_from_clusters(dataset[i], cluster_lst[i], model_cfg.num_clusters))
+            out.append(hetero_from_clusters(dataset[i], cluster_lst[i], model_cfg.num_clusters,
+                                            getattr(data_cfg, "task_level", "graph")))
     return out
 
 

@@ -33,7 +33,7 @@ class Shape:
     num_features: int
     feature_kind: str        # "atom" (int columns) | "normal" (float)
     num_classes: int
-    task: str                # "multilabel" | "regression" | "node_class" (one class index per NODE)
+    task: str                # "multilabel" | "regression" | "node_class" (one class index per NODE) | "link"
 
 
 SHAPES = {
@@ -52,6 +52,16 @@ SHAPES = {
 NODE_SHAPES = {
     "pascalvoc_sp_node": Shape("pascalvoc_sp_node", 479.0, 60.0, 395, 500, 2.827, 14, "normal", 21, "node_class"),
 }
+
+# Link-level shapes (``edge_label_index`` int64 [2, P] candidate pairs with ``edge_label`` float32 [P]; no ``y``), kept
+# apart as well: PCQM-Contact with the dataset's real task -- which pairs of atoms are in contact -- scored by a
+# per-graph MRR.  The graphs are "pcqm_contact"'s, node for node and edge for edge.
+LINK_SHAPES = {
+    "pcqm_contact_link": Shape("pcqm_contact_link", 30.0, 8.0, 9, 53, 1.013, 9, "atom", 1, "link"),
+}
+# an unordered candidate pair {u, v} is a contact with this probability, whatever the graph: about 3 % of the
+# candidates are positive, and a molecule of ten atoms (some 35 candidate pairs) has none one time in three
+LINK_POSITIVE_PROB = 0.03
 
 
 def _molecule_edges(rng: np.random.Generator, n: int, n_und: int) -> np.ndarray:
@@ -110,7 +120,42 @@ def _node_class_probs(num_classes: int) -> np.ndarray:
     return p / p.sum()
 
 
-def make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int] = None) -> Data:
+def _hop_distances(n: int, ei: np.ndarray) -> np.ndarray:
+    """[n, n] hop distances by a BFS from every node (n for unreachable)."""
+    adj = [[] for _ in range(n)]
+    for a, b in zip(ei[0].tolist(), ei[1].tolist()):
+        adj[a].append(b)
+    dist = np.full((n, n), n, dtype=np.int64)
+    for s in range(n):
+        dist[s, s] = 0
+        frontier = [s]
+        while frontier:
+            nxt = []
+            for a in frontier:
+                for b in adj[a]:
+                    if dist[s, b] == n:
+                        dist[s, b] = dist[s, a] + 1
+                        nxt.append(b)
+            frontier = nxt
+    return dist
+
+
+def _link_labels(rng: np.random.Generator, n: int, ei: np.ndarray, prob: float = None):
+    """Candidates: every ordered pair (u, v), u != v, at hop distance >= 2, in (u, v) order.  Labels are symmetric:
+    one draw per unordered pair serves (u, v) and (v, u)."""
+    dist = _hop_distances(n, ei)
+    u, v = np.nonzero(dist >= 2)                        # row-major: ascending (u, v); the diagonal has distance 0
+    draw = rng.random((n, n)) < (LINK_POSITIVE_PROB if prob is None else prob)
+    contact = np.triu(draw, 1)
+    contact = contact | contact.T
+    index = np.stack([u, v]).astype(np.int64)
+    return torch.from_numpy(index), torch.from_numpy(contact[u, v].astype(np.float32))
+
+
+def make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int] = None,
+               label_rng: Optional[np.random.Generator] = None) -> Data:
+    """``label_rng`` (link shapes): the generator of the label draws; ``make_dataset`` passes a stream of its own, so
+    that the graph stream ``rng`` is spent exactly as the graph-level shape spends it."""
     if n is None:
         n = int(np.clip(round(rng.normal(shape.n_mean, shape.n_std)), shape.n_min, shape.n_max))
     n_und = max(n - 1, int(round(shape.und_per_node * n)))
@@ -121,6 +166,10 @@ def make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int] = None) 
     else:
         ei = _lattice_edges(rng, n, n_und)
         x = torch.from_numpy(rng.normal(size=(n, shape.num_features)).astype(np.float32))
+    if shape.task == "link":
+        rng.normal(size=(1, shape.num_classes))         # the draw "pcqm_contact" spends on its target: same graphs after
+        index, label = _link_labels(label_rng if label_rng is not None else rng, n, ei)
+        return Data(x=x, edge_index=torch.from_numpy(ei), num_nodes=n, edge_label_index=index, edge_label=label)
     if shape.task == "node_class":
         y = torch.from_numpy(rng.choice(shape.num_classes, size=n, p=_node_class_probs(shape.num_classes)).astype(np.int64))
     elif shape.task == "multilabel":
@@ -132,6 +181,7 @@ def make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int] = None) 
 
 def make_dataset(name: str, num_graphs: int, seed: int = 0) -> List[Data]:
     """``num_graphs`` seeded graphs of the named LRGB shape."""
-    shape = SHAPES[name] if name in SHAPES else NODE_SHAPES[name]
+    shape = SHAPES[name] if name in SHAPES else (NODE_SHAPES[name] if name in NODE_SHAPES else LINK_SHAPES[name])
     rng = np.random.default_rng(seed)
-    return [make_graph(rng, shape) for _ in range(num_graphs)]
+    label_rng = np.random.default_rng([seed, 1]) if shape.task == "link" else None
+    return [make_graph(rng, shape, label_rng=label_rng) for _ in range(num_graphs)]

@@ -271,3 +271,232 @@ def eval_f1_macro_hip(y_true: torch.Tensor, y_pred: torch.Tensor) -> float:
 def eval_hip(metric: str):
     """``eval_<metric>_hip``."""
     return {"ap": eval_ap_hip, "mae": eval_mae_hip, "accuracy": eval_accuracy_hip, "f1_macro": eval_f1_macro_hip}[metric]
+
+
+# ---- link-level ranking metrics: per-graph MRR and Hits@K (csrc/edge_head.hip; DESIGN.md sections 4 and 8) -------------------
+# For every positive candidate pair (u, v) of a graph, its rank among the scores s(u, w) = <z_u, z_w> of the graph's
+# other nodes w.  With g negatives scoring higher and e scoring equal, rank = 1 + g + e / 2 (the mean of the optimistic
+# and the pessimistic rank); everything is kept as the integer rank2 = 2 g + e, so rank <= K is rank2 + 2 <= 2 K and
+# the reciprocal rank is 2 / (rank2 + 2).  ``filter``: 0 = the negatives are all nodes w != v (u itself and u's other
+# positive partners included); 1 = without the other positive partners of u ("filtered", the default of the
+# evaluation entry points); 2 = additionally without u itself.
+
+LINK_METRICS = ("mrr", "hits@1", "hits@3", "hits@10")
+FILTERS = (0, 1, 2)
+AVERAGINGS = ("graph", "pooled")
+# bits of the launches' flag word (include/hscn.h: HSCN_PAIR_*)
+PAIR_ID_OUT_OF_RANGE, PAIR_NAN_SCORE, PAIR_LABEL_NOT_BINARY, PAIR_BAD_SEGMENT, PAIR_NO_POSITIVE = 1, 2, 4, 8, 16
+_LINK_PACKED_BYTES = 48                # result [4] f64 | flags [1] i32 | 3 spare 32-bit words, ONE buffer = one copy
+
+
+def link_rank_counts(z: torch.Tensor, ptr: torch.Tensor, pair_ptr: torch.Tensor, pair_index: torch.Tensor,
+                     edge_label: torch.Tensor, filter: int, score=None):
+    """The restatement of ``hscn_pair_rank`` in plain torch ops: ``(rank2 [P] int32, per_graph [B, 5] float64)``.
+    ``z`` [N, D] is used in float64 unless it is float32 (then the scores are float32 products summed by torch);
+    ``ptr`` / ``pair_ptr`` [B + 1] node and pair ranges, ``pair_index`` [2, P] global node ids, ``edge_label`` [P].
+    ``rank2`` is -1 for a pair that is not a ranked positive; ``per_graph[g]`` = (sum of reciprocal ranks in pair
+    order, #rank <= 1, #rank <= 3, #rank <= 10, number of ranked positives).  A label outside {0, 1} is a
+    ``ValueError``, a pair that leaves its graph an ``IndexError``; a positive whose own score is NaN is not ranked.
+    ``score``: a function giving the [n, n] score matrix of a graph's rows ``z[nb:ne]`` in place of their product
+    (scores evaluated elsewhere, say by ``nn.head.pair_dot``, ranked by the integer rules here)."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+    z = z.detach()
+    if z.dtype != torch.float32:
+        z = z.to(torch.float64)
+    edge_label = edge_label.detach()
+    if not bool(((edge_label == 0) | (edge_label == 1)).all()):
+        raise ValueError("edge_label must hold 0 or 1")
+    dev = z.device
+    B, P = int(ptr.numel()) - 1, int(pair_index.size(1))
+    nodes, pairs = [int(v) for v in ptr.tolist()], [int(v) for v in pair_ptr.tolist()]
+    rank2 = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    per_graph = torch.zeros(B, 5, dtype=torch.float64, device=dev)
+    for g in range(B):
+        nb, ne, pb, pe = nodes[g], nodes[g + 1], pairs[g], pairs[g + 1]
+        n = ne - nb
+        idx = pair_index[:, pb:pe]
+        if idx.numel() and (int(idx.min()) < nb or int(idx.max()) >= ne):
+            raise IndexError(f"a candidate pair of graph {g} leaves its node range [{nb}, {ne})")
+        which = torch.nonzero(edge_label[pb:pe] == 1).flatten()
+        if which.numel() == 0:
+            continue
+        U, V = idx[0, which] - nb, idx[1, which] - nb
+        S = z[nb:ne] @ z[nb:ne].T if score is None else score(z[nb:ne]).to(dev)
+        rows = S[U]                                                       # [positives, n]: s(u, .)
+        k = torch.arange(which.numel(), device=dev)
+        spos = rows[k, V].unsqueeze(1)
+        neg = torch.ones(which.numel(), n, dtype=torch.bool, device=dev)
+        if filter >= 1:
+            positive = torch.zeros(n, n, dtype=torch.bool, device=dev)
+            positive[U, V] = True
+            neg &= ~positive[U]
+        if filter == 2:
+            neg[k, U] = False
+        neg[k, V] = False
+        gt = ((rows > spos) & neg).sum(1)
+        eq = ((rows == spos) & neg).sum(1)
+        r2 = (2 * gt + eq).to(torch.int32)
+        ranked = ~torch.isnan(spos.squeeze(1))
+        r2 = torch.where(ranked, r2, torch.full_like(r2, -1))
+        rank2[pb + which] = r2
+        total = 0.0
+        for v in r2[ranked].tolist():                                     # in pair order, as the kernel adds them
+            total += 2.0 / (v + 2)
+        rr = r2[ranked].to(torch.int64) + 2
+        per_graph[g] = torch.tensor([total, float((rr <= 2).sum()), float((rr <= 6).sum()), float((rr <= 20).sum()),
+                                     float(ranked.sum())], dtype=torch.float64)
+    return rank2, per_graph
+
+
+def link_means(per_graph: torch.Tensor, averaging: str = "graph"):
+    """(MRR, Hits@1, Hits@3, Hits@10) of a per-graph table.  "graph": per graph the mean over its positives, then the
+    mean over the graphs that have at least one, in graph order; "pooled": one mean over all positives."""
+    if averaging not in AVERAGINGS:
+        raise ValueError(f"averaging must be one of {AVERAGINGS}, got {averaging!r}")
+    sums, count = [0.0] * 4, 0
+    for row in per_graph.tolist():
+        if not row[4] > 0:
+            continue                                                      # a graph without positives is left out
+        for k in range(4):
+            sums[k] += row[k] if averaging == "pooled" else row[k] / row[4]
+        count += int(row[4]) if averaging == "pooled" else 1
+    if count == 0:
+        raise RuntimeError("No positive pair available. Cannot compute a ranking metric.")
+    return tuple(s / count for s in sums)
+
+
+def eval_link_ranks(z, ptr, pair_ptr, pair_index, edge_label, filter: int = 1, averaging: str = "graph"):
+    """(MRR, Hits@1, Hits@3, Hits@10) through ``link_rank_counts``."""
+    return link_means(link_rank_counts(z, ptr, pair_ptr, pair_index, edge_label, filter)[1], averaging)
+
+
+class LinkRankResult(NamedTuple):
+    """Device tensors of a ranking launch: ``rank2`` [P] int32, ``per_graph`` [B, 5] float64, and ``result`` [4]
+    float64 (MRR, Hits@1, Hits@3, Hits@10) with ``flags`` [1] int32, both views of ``packed``: one copy brings them
+    to the host."""
+    rank2: Optional[torch.Tensor]
+    per_graph: torch.Tensor
+    result: torch.Tensor
+    flags: torch.Tensor
+    packed: torch.Tensor
+
+
+def _link_packed(device, packed: Optional[torch.Tensor] = None):
+    if packed is None:
+        packed = torch.zeros(_LINK_PACKED_BYTES, dtype=torch.uint8, device=device)
+    return packed, packed[:32].view(torch.float64), packed[32:36].view(torch.int32)
+
+
+def pair_rank_supported(max_nodes: int, D: int) -> int:
+    """0: refused; 1: a graph of ``max_nodes`` nodes is ranked from LDS; 2: from global memory (the same kernel)."""
+    return int(_hip.lib().hscn_pair_rank_supported(int(max_nodes), int(D)))
+
+
+def pair_rank_launch(z: torch.Tensor, ptr32: torch.Tensor, pair_ptr32: torch.Tensor, structure, filter: int = 1,
+                     averaging: str = "graph", want_rank2: bool = True, packed: Optional[torch.Tensor] = None,
+                     acc_sum: Optional[torch.Tensor] = None, acc_count: Optional[torch.Tensor] = None,
+                     max_nodes: int = 0) -> LinkRankResult:
+    """Issue ``hscn_pair_rank`` and ``hscn_pair_rank_reduce`` on device tensors; nothing is read back.  ``structure``:
+    the batch's ``nn.head.PairStructure`` built with its labels; ``ptr32`` / ``pair_ptr32`` int32 [B + 1].
+    ``acc_sum`` [4] float64 / ``acc_count`` [1] int64: an epoch's running totals (``LinkRankAccumulator``); the flag
+    word of ``packed`` is ORed into, never cleared here (but for ``PAIR_NO_POSITIVE``, which a launch whose total
+    holds a positive takes back).  ``max_nodes``: the batch's largest graph, which sizes the launch's LDS (0: the whole
+    budget).  ``rank2`` is -1 wherever the kernel does not rank, pairs outside every graph's range included."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+    if averaging not in AVERAGINGS:
+        raise ValueError(f"averaging must be one of {AVERAGINGS}, got {averaging!r}")
+    if z.dim() != 2:
+        raise ValueError("z must be [N, D]")
+    _hip.ptr(z)                                        # (a CPU tensor: the package's no-CPU-fallback error)
+    if structure.edge_label is None:
+        raise ValueError("the PairStructure was built without labels")
+    if not _hip.lib().hscn_pair_dot_supported(int(z.size(1))):
+        raise RuntimeError(f"the ranking kernel takes an embedding width that is a multiple of 4 in [4, 64] "
+                           f"(hscn_pair_rank_supported), not D={z.size(1)}")
+    z = z.detach().to(torch.float32).contiguous()
+    if z.data_ptr() % 16:
+        z = z.clone()
+    dev = z.device
+    B, N, P = int(ptr32.numel()) - 1, int(z.size(0)), int(structure.num_pairs)
+    ptr32 = ptr32.to(device=dev, dtype=torch.int32).contiguous()
+    pair_ptr32 = pair_ptr32.to(device=dev, dtype=torch.int32).contiguous()
+    packed, result, flags = _link_packed(dev, packed)
+    rank2 = torch.full((P,), -1, dtype=torch.int32, device=dev) if want_rank2 else None
+    per_graph = torch.empty(B, 5, dtype=torch.float64, device=dev)
+    pos = structure.positives
+    _hip.call("hscn_pair_rank", _hip.ptr(z), _hip.ptr(ptr32), _hip.ptr(pair_ptr32), _hip.ptr(structure.index32),
+              _hip.ptr(structure.edge_label), _hip.ptr(pos.rowptr) if pos is not None else None,
+              _hip.ptr(pos.eid) if pos is not None else None, B, N, P, int(z.size(1)), int(filter), int(max_nodes),
+              _hip.ptr(rank2),
+              _hip.ptr(per_graph), _hip.ptr(flags), _hip.stream())
+    _hip.call("hscn_pair_rank_reduce", _hip.ptr(per_graph), B, AVERAGINGS.index(averaging), _hip.ptr(acc_sum),
+              _hip.ptr(acc_count), _hip.ptr(result), _hip.ptr(flags), _hip.stream())
+    return LinkRankResult(rank2, per_graph, result, flags, packed)
+
+
+def link_metric_values(result, flags: int):
+    """The four numbers of a ranking launch once ``result`` and ``flags`` are on the host, or the error its flags
+    stand for."""
+    if flags & (PAIR_ID_OUT_OF_RANGE | PAIR_BAD_SEGMENT):
+        raise IndexError("a candidate pair leaves its graph's node range")
+    if flags & PAIR_LABEL_NOT_BINARY:
+        raise ValueError("edge_label must hold 0 or 1")
+    if flags & PAIR_NAN_SCORE:
+        raise ValueError("Input contains NaN.")
+    if flags & PAIR_NO_POSITIVE:
+        raise RuntimeError("No positive pair available. Cannot compute a ranking metric.")
+    return tuple(float(v) for v in result[:4])
+
+
+def read_link_packed(packed: torch.Tensor):
+    """ONE synchronising copy of a ranking launch's packed buffer: (float64 [4], flags)."""
+    host = packed.cpu()
+    return host[:32].view(torch.float64), int(host[32:36].view(torch.int32)[0])
+
+
+def eval_link_ranks_hip(z, ptr32, pair_ptr32, structure, filter: int = 1, averaging: str = "graph",
+                        max_nodes: int = 0):
+    """``eval_link_ranks`` through the HIP launches and one read-back."""
+    f64, flags = read_link_packed(pair_rank_launch(z, ptr32, pair_ptr32, structure, filter, averaging,
+                                                   want_rank2=False, max_nodes=max_nodes).packed)
+    return link_metric_values(f64, flags)
+
+
+class LinkRankAccumulator:
+    """An epoch's ranking metric over several batches: every ``update`` launches on its batch and adds the batch's
+    graphs to running float64 sums and an int64 count on the device; ``result()`` is the one host copy."""
+
+    def __init__(self, filter: int = 1, averaging: str = "graph"):
+        if filter not in FILTERS:
+            raise ValueError(f"filter must be one of {FILTERS}, got {filter!r}")
+        if averaging not in AVERAGINGS:
+            raise ValueError(f"averaging must be one of {AVERAGINGS}, got {averaging!r}")
+        self.filter, self.averaging = filter, averaging
+        self.packed = self.acc_sum = self.acc_count = None
+
+    def reset(self) -> None:
+        for t in (self.packed, self.acc_sum, self.acc_count):
+            if t is not None:
+                t.zero_()
+
+    def update(self, z: torch.Tensor, batch) -> None:
+        """``z``: the model's [N, D] embeddings of ``batch`` (a ``Batch``, or a ``HeteroBatch`` whose local node type
+        carries the pairs), on the device."""
+        from .nn.head import PairStructure
+        store = batch["local"] if hasattr(batch, "node_types") else batch
+        if self.packed is None or self.packed.device != z.device:
+            self.packed = torch.zeros(_LINK_PACKED_BYTES, dtype=torch.uint8, device=z.device)
+            self.acc_sum = torch.zeros(4, dtype=torch.float64, device=z.device)
+            self.acc_count = torch.zeros(1, dtype=torch.int64, device=z.device)
+        pair_rank_launch(z, store.ptr32, store.pair_ptr32, PairStructure.of(store, z.size(0)), self.filter,
+                         self.averaging, want_rank2=False, packed=self.packed, acc_sum=self.acc_sum,
+                         acc_count=self.acc_count, max_nodes=int(store.max_nodes) if "max_nodes" in store else 0)
+
+    def result(self) -> dict:
+        """{"mrr", "hits@1", "hits@3", "hits@10"} of everything since the last ``reset`` (synchronising)."""
+        if self.packed is None:
+            raise RuntimeError("No positive pair available. Cannot compute a ranking metric.")
+        f64, flags = read_link_packed(self.packed)
+        return dict(zip(LINK_METRICS, link_metric_values(f64, flags)))

@@ -256,7 +256,9 @@ class HSCN(nn.Module):
         applies the head ``lin_2(act(lin_1(.)))`` to every local node, returning ``[N, C]`` (``nn.head.NodeHead``: the
         one-launch head where ``hscn_node_head_supported`` says so, else the two ``Linear`` modules).  The convolution
         stack runs on the layered operators; the graph-resident launches, which end in the pooled head, refuse such a
-        model.
+        model.  "link": ``num_classes`` is the embedding width D; ``embed`` is exactly the node-level model's forward
+        (the same ``NodeHead``, the same state_dict keys) and ``forward`` scores the batch's candidate pairs
+        ``batch["local"].edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P].
 
         ``vl_conv`` (extension; the default ``None`` is the reference's model, bit for bit): "GAT" gives every
         layer a fourth convolution on the relation ("virtual", "to", "local") -- the lv edge list reversed, derived in
@@ -269,8 +271,8 @@ class HSCN(nn.Module):
         super().__init__()
         if vl_conv is not None and vl_conv != "GAT":
             raise ValueError(f"vl_conv must be None or 'GAT', not {vl_conv!r} (a bipartite GCNConv does not exist)")
-        if task_level not in ("graph", "node"):
-            raise ValueError(f"task_level must be 'graph' or 'node', not {task_level!r}")
+        if task_level not in ("graph", "node", "link"):
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
         self.vl_conv = vl_conv
         self.task_level = task_level
         self.activation = activation
@@ -297,7 +299,7 @@ class HSCN(nn.Module):
         self.last_virtual: Optional[Tensor] = None
         self.last_engine: Optional[str] = None
         self.node_head = None
-        if task_level == "node" and _act_name(activation) in ACT_DICT:
+        if task_level != "graph" and _act_name(activation) in ACT_DICT:
             from ..nn.head import NodeHead
             # (a plain object: the parameters stay lin_1 / lin_2 and the state_dict the graph-level model's)
             self.node_head = NodeHead(self.lin_1, self.lin_2, _act_name(activation))
@@ -305,10 +307,16 @@ class HSCN(nn.Module):
     NODE_LEVEL_REASON = ("a node-level head (task_level='node'): the one-launch and graph-resident kernels end in the "
                          "mean pool and the per-graph head, a per-node prediction runs on the layered operators")
 
+    LINK_LEVEL_REASON = ("a link-level head (task_level='link'): the one-launch and graph-resident kernels end in the "
+                         "mean pool and the per-graph head, a score per candidate pair runs on the layered operators and "
+                         "the pair decoder")
+
     def _refuse_node_level(self, what: str) -> None:
-        """The resident launches pool: they must refuse a node-level model, never pool silently."""
+        """The resident launches pool: they must refuse a node-level or link-level model, never pool silently."""
         if self.task_level == "node":
             raise RuntimeError(f"{what} does not take this model: {self.NODE_LEVEL_REASON}")
+        if self.task_level == "link":
+            raise RuntimeError(f"{what} does not take this model: {self.LINK_LEVEL_REASON}")
 
     def _refuse_vl(self, what: str) -> None:
         """The hscn_resident_* launches know three relations: they must refuse a model with a fourth, never drop it."""
@@ -321,7 +329,7 @@ class HSCN(nn.Module):
     def _resident_plan(self, x_dict, edge_index_dict, batch):
         if self.engine == "layered":
             return None
-        if self.task_level == "node":
+        if self.task_level != "graph":
             if self.engine == "resident":
                 self._refuse_node_level("engine='resident'")
             return None
@@ -414,6 +422,8 @@ class HSCN(nn.Module):
         from .._hip import lib
         if self.task_level == "node":
             return self.NODE_LEVEL_REASON
+        if self.task_level == "link":
+            return self.LINK_LEVEL_REASON
         if self.vl_conv is None:
             return f"the model has no {VL_NAME} relation (the hscn_resident_* launches serve the reference's model)"
         if _act_name(self.activation) not in ACT_DICT:
@@ -489,7 +499,7 @@ class HSCN(nn.Module):
         if VL not in edge_index_dict:        # the data layer does not change: vl is lv reversed, appended last
             edge_index_dict = dict(edge_index_dict)
             edge_index_dict[VL] = edge_index_dict[LV].flip(0)
-        if self.engine != "layered" and self.task_level != "node":
+        if self.engine != "layered" and self.task_level == "graph":
             if torch.is_grad_enabled():
                 if self.engine == "resident":
                     self._refuse_vl("engine='resident' with gradients on (the hscn_resident_* autograd launches)")
@@ -504,6 +514,21 @@ class HSCN(nn.Module):
 
     def forward(self, x_dict: Dict[str, Tensor], edge_index_dict: Dict[Tuple[str, str, str], Tensor],
                 batch) -> Tensor:
+        out = self._forward(x_dict, edge_index_dict, batch)
+        if self.task_level == "link":                  # one score per candidate pair of the batch
+            from ..nn.head import PairStructure, pair_dot
+            local = batch["local"]
+            return pair_dot(out, local.edge_label_index, PairStructure.of(local, out.size(0)))
+        return out
+
+    def embed(self, x_dict: Dict[str, Tensor], edge_index_dict: Dict[Tuple[str, str, str], Tensor],
+              batch) -> Tensor:
+        """The [N, D] node embeddings a link-level model scores pairs with: the node-level model's forward."""
+        if self.task_level != "link":
+            raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
+        return self._forward(x_dict, edge_index_dict, batch)
+
+    def _forward(self, x_dict, edge_index_dict, batch) -> Tensor:
         if self.vl_conv is not None:
             return self._forward_vl(x_dict, edge_index_dict, batch)
         plan = self._resident_plan(x_dict, edge_index_dict, batch)
@@ -522,7 +547,7 @@ class HSCN(nn.Module):
             x_dict = conv(x_dict, edge_index_dict)
             x_dict = {key: relu(x) for key, x in x_dict.items()}           # hscn.py:110 (hard-coded ReLU)
         name = _act_name(self.activation)
-        if self.task_level == "node":                                      # the head on every local node: no pool
+        if self.task_level != "graph":                                     # the head on every local node: no pool
             x = x_dict["local"]
             if self.node_head is not None:
                 return self.node_head(x)

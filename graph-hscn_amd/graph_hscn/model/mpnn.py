@@ -31,10 +31,12 @@ class MPNN(nn.Module):
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
                  use_layer_norm: bool = False, task_level: str = "graph") -> None:
         """``task_level`` (extension; the default "graph" is the reference's model): "node" returns the last
-        convolution's ``[N, C]`` without the per-graph mean."""
+        convolution's ``[N, C]`` without the per-graph mean.  "link": ``num_classes`` is the embedding width D,
+        ``embed`` is that node-level output and ``forward`` scores the batch's candidate pairs
+        ``batch.edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P]."""
         super().__init__()
-        if task_level not in ("graph", "node"):
-            raise ValueError(f"task_level must be 'graph' or 'node', not {task_level!r}")
+        if task_level not in ("graph", "node", "link"):
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
         self.task_level = task_level
         self.num_layers = num_layers
         self.conv_layers = nn.ModuleList()                                  # mpnn.py:27-32
@@ -63,6 +65,9 @@ class MPNN(nn.Module):
         if self.task_level == "node":
             return ("a node-level head (task_level='node'): the one-launch kernels end in the per-graph mean, a "
                     "per-node prediction runs on the layered operators")
+        if self.task_level == "link":
+            return ("a link-level head (task_level='link'): the one-launch kernels end in the per-graph mean, a "
+                    "score per candidate pair runs on the layered operators and the pair decoder")
         name = getattr(self.activation, "hscn_name", None)
         if name not in ("relu", "elu", "identity", "tanh"):
             return f"activation {name!r} (relu, elu, identity and tanh are supported)"
@@ -130,9 +135,22 @@ class MPNN(nn.Module):
         return pred
 
     def forward(self, batch) -> Tensor:
+        out = self._forward(batch)
+        if self.task_level == "link":                  # one score per candidate pair of the batch
+            from ..nn.head import PairStructure, pair_dot
+            return pair_dot(out, batch.edge_label_index, PairStructure.of(batch, out.size(0)))
+        return out
+
+    def embed(self, batch) -> Tensor:
+        """The [N, D] node embeddings a link-level model scores pairs with: the node-level model's forward."""
+        if self.task_level != "link":
+            raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
+        return self._forward(batch)
+
+    def _forward(self, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
-        if self.engine == "resident" and self.task_level == "node":
+        if self.engine == "resident" and self.task_level != "graph":
             raise RuntimeError(f"engine='resident' does not take this model: {self.resident_reason()}")
         if self.engine != "layered" and not torch.is_grad_enabled():
             reason = self.resident_reason(batch)
@@ -158,7 +176,7 @@ class MPNN(nn.Module):
             seed = None if self.dropout_seed is None else self.dropout_seed + i
             x = Fh.dropout(x, p=self.dropout, training=self.training, seed=seed)
         x = self.conv_layers[-1](x, edge_index)
-        if self.task_level == "node":
+        if self.task_level != "graph":
             return x
         size = getattr(batch, "num_graphs", None)
         return global_mean_pool(x, batch_vec, size)                         # scatter_mean(x, batch, dim=0)

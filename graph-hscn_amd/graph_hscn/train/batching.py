@@ -19,6 +19,9 @@ def is_hetero(model) -> bool:
 
 def targets(model, batch) -> Optional[Tensor]:
     """The batch's targets, or ``None`` when it carries none."""
+    if link_level(model):
+        store = batch["local"] if is_hetero(model) else batch
+        return store.edge_label if "edge_label" in store else None
     if is_hetero(model):
         return batch["local"].y if "y" in batch["local"] else None
     return getattr(batch, "y", None)
@@ -52,11 +55,38 @@ def refuse_node_level(model, what: str) -> None:
         raise RuntimeError(f"{what} does not take this model: {model.resident_reason()} (train.train runs it)")
 
 
+def link_level(model) -> bool:
+    return getattr(model, "task_level", "graph") == "link"
+
+
+def refuse_link_level(model, what: str) -> None:
+    """The same for a link-level model: those launches know neither candidate pairs nor a pair decoder."""
+    if link_level(model):
+        raise RuntimeError(f"{what} does not take this model: {model.resident_reason()} (train.train runs it)")
+
+
+def link_forward(model, batch) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(scores, edge_label, z)`` of a link-level model: what ``forward`` answers plus the detached [N, D]
+    embeddings the scores were taken from, which the epoch's ranking metric is fed with."""
+    from ..nn.head import PairStructure, pair_dot
+    if model.engine == "resident":
+        refuse_link_level(model, "engine='resident'")
+    if is_hetero(model):
+        store, z = batch["local"], model.embed(batch.x_dict, batch.edge_index_dict, batch)
+    else:
+        store, z = batch, model.embed(batch)
+    scores = pair_dot(z, store.edge_label_index, PairStructure.of(store, z.size(0)))
+    return scores, store.edge_label, z.detach()
+
+
 def forward(model, batch) -> Tuple[Tensor, Tensor]:
     """``(pred, targets)`` of ``model`` on a batch that is on the model's device.  A node-level model
-    (``task_level="node"``) answers ``[N, C]`` and the targets are the per-node labels."""
+    (``task_level="node"``) answers ``[N, C]`` and the targets are the per-node labels; a link-level model
+    (``task_level="link"``) answers one score per candidate pair, ``[P]``, and the targets are ``edge_label``."""
     if node_level(model) and model.engine == "resident":
         refuse_node_level(model, "engine='resident'")
+    if link_level(model):
+        return link_forward(model, batch)[:2]
     if is_hetero(model):
         if getattr(model, "vl_conv", None) is not None and torch.is_grad_enabled() and model.engine == "resident":
             # the eager tail of a device loop: with gradients on this model runs through the layered operators
@@ -94,6 +124,7 @@ def resident_step(model, batch, loss_fn: str, one_launch: Optional[bool] = None,
     the vl model's one launch, which have neither a launch pair nor a structure to load)."""
     from ..step import MPNNResidentTrainStep, ResidentTrainStep, VLResidentTrainStep
     refuse_node_level(model, "the resident training step")
+    refuse_link_level(model, "the resident training step")
     if targets(model, batch) is None:
         raise ValueError("the static batch carries no targets")
     if not is_hetero(model):

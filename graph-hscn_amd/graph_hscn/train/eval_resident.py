@@ -49,6 +49,7 @@ class DeviceEvaluator:
         if metric not in METRICS + (None,):
             raise ValueError(f"metric must be one of {METRICS} or None, got {metric!r}")
         batching.refuse_node_level(model, "DeviceEvaluator")
+        batching.refuse_link_level(model, "DeviceEvaluator")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("DeviceEvaluator runs on the MI355X HIP path: move the model to 'cuda'")

@@ -75,9 +75,11 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
     return loaders_new, flat
 
 
-def _run_batch(model, batch, device):
-    # train.py:78-80 leaves the batch where the loader put it; the HIP operators take device tensors only
-    return batching.forward(model, batching.to_device(model, batch, device))
+def _link_metric_of(training_cfg) -> str:
+    """The ranking metric a link-level model reports under ``training_cfg`` ("mrr" unless it names another)."""
+    from ..metrics import LINK_METRICS
+    metric = getattr(training_cfg, "metric", None)
+    return metric if metric in LINK_METRICS else "mrr"
 
 
 class EarlyStopping:
@@ -113,7 +115,9 @@ class EarlyStopping:
                 if logger is not None:
                     logger.info(f"epoch {epoch} {split} loss {loss:.5f} perf {perf:.5f}")
             else:
-                loss, perf = eval_epoch(epoch, logger, source, model, self.cfg.loss_fn, metric_fn, split)
+                # (the keyword travels with a link-level model only: every other call is what it was)
+                extra = {"link_metric": _link_metric_of(self.cfg)} if batching.link_level(model) else {}
+                loss, perf = eval_epoch(epoch, logger, source, model, self.cfg.loss_fn, metric_fn, split, **extra)
             if eval_history is not None:
                 eval_history.append((epoch, split, loss, perf))
             if split == "Validation" and self.update(loss, epoch):
@@ -123,19 +127,58 @@ class EarlyStopping:
         return False
 
 
+def _link_ranks(model, metric_fn, link_metric):
+    """``(accumulator, name)`` for a link-level model, ``(None, None)`` for any other.  A per-graph rank is not a
+    function of concatenated targets and scores, so ``metric_fn(true, score)`` cannot express it and must be None for
+    such a model: the epoch functions read ``link_metric`` ("mrr" / "hits@1" / "hits@3" / "hits@10"; None = "mrr")
+    off a ``metrics.LinkRankAccumulator`` fed with the model's embeddings."""
+    if not batching.link_level(model):
+        if link_metric is not None:
+            raise ValueError("link_metric belongs to a link-level model (task_level='link')")
+        return None, None
+    from ..metrics import LINK_METRICS, LinkRankAccumulator
+    if metric_fn is not None:
+        raise ValueError("a link-level model is scored per graph: pass link_metric=, not metric_fn")
+    name = "mrr" if link_metric is None else link_metric
+    if name not in LINK_METRICS:
+        raise ValueError(f"a link-level model is scored by one of {LINK_METRICS}, not {link_metric!r}")
+    return LinkRankAccumulator(), name
+
+
+def _forward(model, batch, ranks):
+    """``(pred, targets)`` of one batch; a link-level model's embeddings go to the epoch's accumulator."""
+    if ranks is None:
+        return batching.forward(model, batch)
+    scores, labels, z = batching.link_forward(model, batch)
+    ranks.update(z, batch)
+    return scores, labels
+
+
+def _link_result(ranks, name, device) -> float:
+    """The epoch's ranking metric (one host copy), after the check of the pair decoder's own flag word."""
+    from ..nn.head import check_pair_ids
+    check_pair_ids(device)
+    return ranks.result()[name]
+
+
 def train_epoch(epoch, logger, loader, model, optimizer, loss_fn: str, metric_fn: Optional[Callable],
-                batch_accumulation: int, clip_grad_norm: bool, reducer=None):
+                batch_accumulation: int, clip_grad_norm: bool, reducer=None, link_metric: Optional[str] = None):
+    """``link_metric``: the ranking metric a link-level model reports (``_link_ranks``)."""
     start = time.time()
+    ranks, rank_name = _link_ranks(model, metric_fn, link_metric)
     model.train()
     optimizer.zero_grad()
     device = next(model.parameters()).device
     losses, y_true, y_pred = [], [], []
     num = len(loader)
     for it, batch in enumerate(loader):
-        pred, true = _run_batch(model, batch, device)
+        # train.py:78-80 leaves the batch where the loader put it; the HIP operators take device tensors only
+        batch = batching.to_device(model, batch, device)
+        pred, true = _forward(model, batch, ranks)
         loss, score = criterion(loss_fn, pred, true)
-        y_true.append(true)
-        y_pred.append(score.detach())
+        if ranks is None:
+            y_true.append(true)
+            y_pred.append(score.detach())
         losses.append(loss.detach())
         loss.backward()
         if (it + 1) % batch_accumulation == 0 or it + 1 == num:
@@ -146,25 +189,35 @@ def train_epoch(epoch, logger, loader, model, optimizer, loss_fn: str, metric_fn
             optimizer.step()
             optimizer.zero_grad()
     mean_loss = float(torch.stack(losses).mean().item())
-    perf = metric_fn(torch.cat(y_true), torch.cat(y_pred)) if metric_fn else float("nan")
+    if ranks is not None:
+        perf = _link_result(ranks, rank_name, device)
+    else:
+        perf = metric_fn(torch.cat(y_true), torch.cat(y_pred)) if metric_fn else float("nan")
     if logger is not None:
         logger.info(f"epoch {epoch} train loss {mean_loss:.5f} perf {perf:.5f} ({time.time() - start:.2f}s)")
     return mean_loss, perf
 
 
 @torch.no_grad()
-def eval_epoch(epoch, logger, loader, model, loss_fn: str, metric_fn: Optional[Callable], split: str):
+def eval_epoch(epoch, logger, loader, model, loss_fn: str, metric_fn: Optional[Callable], split: str,
+               link_metric: Optional[str] = None):
     model.eval()
     device = next(model.parameters()).device
+    ranks, rank_name = _link_ranks(model, metric_fn, link_metric)
     losses, y_true, y_pred = [], [], []
     for batch in loader:
-        pred, true = _run_batch(model, batch, device)
+        batch = batching.to_device(model, batch, device)
+        pred, true = _forward(model, batch, ranks)
         loss, score = criterion(loss_fn, pred, true)
-        y_true.append(true)
-        y_pred.append(score)
+        if ranks is None:
+            y_true.append(true)
+            y_pred.append(score)
         losses.append(loss)
     mean_loss = float(torch.stack(losses).mean().item())
-    perf = metric_fn(torch.cat(y_true), torch.cat(y_pred)) if metric_fn else float("nan")
+    if ranks is not None:
+        perf = _link_result(ranks, rank_name, device)
+    else:
+        perf = metric_fn(torch.cat(y_true), torch.cat(y_pred)) if metric_fn else float("nan")
     if logger is not None:
         logger.info(f"epoch {epoch} {split} loss {mean_loss:.5f} perf {perf:.5f}")
     return mean_loss, perf
@@ -175,11 +228,12 @@ def train(logger, optim_cfg, training_cfg, loaders, model, metric_fn: Optional[C
         raise ValueError("OptimConfig.scheduler runs inside the one-launch optimizers: use train_resident.fit_resident")
     optimizer = OPTIM_DICT[optim_cfg.optim_type](lr=optim_cfg.lr, weight_decay=optim_cfg.weight_decay,
                                                  params=model.parameters())
+    extra = {"link_metric": _link_metric_of(training_cfg)} if batching.link_level(model) else {}
     stopper = EarlyStopping(training_cfg)
     history = []
     for epoch in range(training_cfg.epochs):
         history.append(train_epoch(epoch, logger, loaders[0], model, optimizer, training_cfg.loss_fn, metric_fn,
-                                   optim_cfg.batch_accumulation, optim_cfg.clip_grad_norm, reducer))
+                                   optim_cfg.batch_accumulation, optim_cfg.clip_grad_norm, reducer, **extra))
         if is_eval_epoch(epoch, training_cfg.epochs, training_cfg.eval_period) and \
                 stopper.evaluate(epoch, logger, model, loaders[1:], metric_fn):
             break

@@ -160,6 +160,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
     if eval_graphs is not None and len(eval_graphs) != 2:
         raise ValueError("eval_graphs is the pair (validation graphs, test graphs)")
     batching.refuse_node_level(model, "fit_resident")
+    batching.refuse_link_level(model, "fit_resident")
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("fit_resident runs on the MI355X HIP path: move the model to 'cuda'")

@@ -1205,6 +1205,92 @@ int hscn_vl_forward(const float* x_local, const float* x_virtual, const int64_t*
                     float* score /*or NULL*/, float* loss_rows /*[B] or NULL*/, float* loss /*[1] or NULL*/,
                     float* xv_out /*[V,H] or NULL*/, int32_t* flag, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Link-level tasks: the pair decoder and the per-graph ranking metric (graph_hscn.nn.head.pair_dot,
+ * graph_hscn.metrics; csrc/edge_head.hip).  Purely additive to ABI 23.
+ *   z [N, D] f32 row-major, 16-byte aligned (rows move as float4); pair_index [2, P] i32, row 0 the source u, row 1
+ *   the target v, ids into z; N, P < 2^31.
+ * hscn_pair_dot_supported: the envelope, D a multiple of 4 with 4 <= D <= 64 (the single source of truth: the
+ *   launches answer HSCN_E_UNSUPPORTED outside it).  A lane group of D / 4 lanes rounded up to a power of two owns a
+ *   pair; hscn_pair_dot_pairs_per_workgroup(D) = 256 / that (0 outside the envelope).
+ * hscn_pair_dot_fwd: ONE launch, score[p] = sum_k z[u_p, k] z[v_p, k]: per lane a product and three fmaf over its four
+ *   columns in column order, then an xor-shuffle tree over the lane group, widest offset first -- an order that depends
+ *   on D alone.  A pair with an id outside [0, N) is not dereferenced: its score is 0 and HSCN_PAIR_ID_OUT_OF_RANGE is
+ *   ORed into flags [1] (the caller zeroes the word).  P = 0 launches nothing.
+ * hscn_pair_dot_bwd: ONE launch, g_z[i] = sum_{p: u_p = i} g_p z[v_p] + sum_{p: v_p = i} g_p z[u_p] with
+ *   g_p = g_score[p] (times scale [1], a device scalar, unless NULL): the node's by-source list first, then its
+ *   by-target list, one fmaf per incidence.  src_rowptr / dst_rowptr [N + 1] and src_perm / dst_perm [P] are the
+ *   stable CSRs of the pair list keyed by source / by target (perm = pair ids, ascending inside a row;
+ *   hscn_csr_build_pair's rowptr_t / eid_t and rowptr / eid); an entry outside [0, P), or whose other endpoint lies
+ *   outside [0, N), is skipped.  A pair (i, i) contributes 2 g z[i].  g_z [N, D] is written, not accumulated: a node
+ *   without incidences gets an exact zero row.  No float atomics: the same input gives the same bits.
+ *
+ * hscn_pair_rank: for every positive pair (edge_label[p] == 1) of every graph, its rank among the scores s(u, w) of
+ *   the graph's other nodes w, each score evaluated exactly as hscn_pair_dot_fwd evaluates it.  One workgroup per
+ *   graph (hscn_pair_rank_max_workgroups() at most, a workgroup strides over the graphs).
+ *     ptr [B + 1] i32 node ranges, pair_ptr [B + 1] i32 pair ranges, edge_label [P] f32;
+ *     pos_rowptr [N + 1] / pos_perm: the stable CSR of the POSITIVE pairs keyed by source (read for filter >= 1);
+ *     filter: HSCN_PAIR_FILTER_NONE     Neg(u, v) = every node w != v of the graph (u itself and u's other positive
+ *                                       partners included);
+ *             HSCN_PAIR_FILTER_POSITIVES  additionally without any w != v such that (u, w) is a positive candidate
+ *                                       (counted over all nodes, then subtracted over u's positive list: candidates
+ *                                       are distinct within a graph);
+ *             HSCN_PAIR_FILTER_POSITIVES_SELF  additionally without w == u.
+ *     With g = #{w in Neg: s(u, w) > s(u, v)} and e = #{... == ...}: rank2 [P] i32 (or NULL) = 2 g + e, that is
+ *     rank = 1 + g + e / 2, the mean of the optimistic and the pessimistic rank; -1 for every pair that is not ranked.
+ *     per_graph [B, 5] f64 = { sum 2 / (rank2 + 2) added in ascending pair id, #(rank <= 1), #(rank <= 3),
+ *     #(rank <= 10) as the integer comparisons rank2 + 2 <= 2 K, the number of ranked positives }.
+ *   flags [1] i32, ORed into (the caller zeroes the word): HSCN_PAIR_ID_OUT_OF_RANGE = a pair with an endpoint outside
+ *   its graph's node range; HSCN_PAIR_NAN_SCORE = a NaN score (a positive whose own score is NaN is not ranked, a NaN
+ *   competitor counts neither as greater nor as equal); HSCN_PAIR_LABEL_NOT_BINARY = a label outside {0, 1};
+ *   HSCN_PAIR_BAD_SEGMENT = a graph whose ptr / pair_ptr entries are not ascending inside [0, N] / [0, P] (its row of
+ *   per_graph is zeros).  None of these is dereferenced or counted.
+ *   hscn_pair_rank_supported(max_nodes, D): 0 outside hscn_pair_dot_supported's envelope; 1 when a graph of max_nodes
+ *   nodes is staged in LDS (up to hscn_pair_rank_lds_max_nodes(D) = 60 KB / (16 B * lane-group width) rows, row stride
+ *   = 4 * lane-group width floats); 2 when the same kernel reads its rows from global memory.  No workspace.
+ *   max_nodes: the node count of the batch's largest graph, which sizes the launch's LDS (16 B * lane-group width per
+ *   node instead of the whole 60 KB budget); 0 or less = unknown, the whole budget.  A graph with more nodes than
+ *   max_nodes is still served, from global memory.  A pair outside every graph's [pair_ptr[g], pair_ptr[g + 1]), or
+ *   of a graph flagged HSCN_PAIR_BAD_SEGMENT, is not visited: the caller presets rank2 (graph_hscn.metrics: -1).
+ * hscn_pair_rank_reduce: one small launch, result [4] f64 = { MRR, Hits@1, Hits@3, Hits@10 }.  HSCN_PAIR_AVG_GRAPH:
+ *   per graph the mean over its positives, then the mean over the graphs that have at least one, in graph order;
+ *   HSCN_PAIR_AVG_POOLED: one mean over all positives.  acc_sum [4] f64 / acc_count [1] i64 (both or neither): running
+ *   sums and count of an epoch -- the launch adds this table's graphs to them, in order, and divides the totals, so
+ *   several batches cost one host copy at the end and give the bits of one call on their union.  No positive at all:
+ *   result is 0 and HSCN_PAIR_NO_POSITIVE is ORed into flags; a call whose total holds a positive clears that one bit
+ *   (so an epoch's leading batches without positives leave nothing behind), every other bit is only ever ORed.
+ * HSCN_E_BADARG for null pointers, sizes negative or beyond 2^31 - 1, a misaligned z or g_z, an unknown filter or
+ * averaging; HSCN_E_UNSUPPORTED outside the envelope; both before any launch.
+ * ------------------------------------------------------------------------- */
+#define HSCN_PAIR_ID_OUT_OF_RANGE 1
+#define HSCN_PAIR_NAN_SCORE 2
+#define HSCN_PAIR_LABEL_NOT_BINARY 4
+#define HSCN_PAIR_BAD_SEGMENT 8
+#define HSCN_PAIR_NO_POSITIVE 16
+#define HSCN_PAIR_FILTER_NONE 0
+#define HSCN_PAIR_FILTER_POSITIVES 1
+#define HSCN_PAIR_FILTER_POSITIVES_SELF 2
+#define HSCN_PAIR_AVG_GRAPH 0
+#define HSCN_PAIR_AVG_POOLED 1
+int hscn_pair_dot_supported(int D);
+int hscn_pair_dot_pairs_per_workgroup(int D);
+int hscn_pair_dot_fwd(const float* z, const int32_t* pair_index, int64_t N, int64_t P, int D, float* score /*[P]*/,
+                      int32_t* flags /*[1]*/, void* stream);
+int hscn_pair_dot_bwd(const float* z, const int32_t* pair_index, const float* g_score /*[P]*/,
+                      const float* scale /*[1] or NULL*/, const int32_t* src_rowptr, const int32_t* src_perm,
+                      const int32_t* dst_rowptr, const int32_t* dst_perm, int64_t N, int64_t P, int D,
+                      float* g_z /*[N,D]*/, void* stream);
+int hscn_pair_rank_supported(int max_nodes, int D);
+int hscn_pair_rank_lds_max_nodes(int D);
+int hscn_pair_rank_max_workgroups(void);
+int hscn_pair_rank(const float* z, const int32_t* ptr, const int32_t* pair_ptr, const int32_t* pair_index,
+                   const float* edge_label, const int32_t* pos_rowptr, const int32_t* pos_perm, int64_t B, int64_t N,
+                   int64_t P, int D, int filter, int max_nodes, int32_t* rank2 /*[P] or NULL*/,
+                   double* per_graph /*[B,5]*/, int32_t* flags /*[1]*/, void* stream);
+int hscn_pair_rank_reduce(const double* per_graph, int64_t B, int averaging, double* acc_sum /*[4] or NULL*/,
+                          int64_t* acc_count /*[1] or NULL*/, double* result /*[4]*/, int32_t* flags /*[1]*/,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
