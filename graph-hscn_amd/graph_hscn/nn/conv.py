@@ -121,7 +121,10 @@ class GATConv(nn.Module):
     """PyG GATConv, heads=1, negative_slope=0.2, dropout=0, in its two uses:
 
     * ``add_self_loops=False``: the bipartite local->virtual relation (model/hscn.py:85-87, ``in_channels=(-1,-1)``)
-      with two transforms ``lin_src`` / ``lin_dst`` (also for an int ``in_channels``);
+      with two transforms ``lin_src`` / ``lin_dst`` (also for an int ``in_channels``) when called with a pair
+      ``(x_src, x_dst)``; called with ONE Tensor (a homogeneous relation built with ``ll_conv`` / ``vv_conv`` = "GAT")
+      ``lin_src`` transforms it for both roles, as PyG's forward does, and ``lin_dst`` is an unused parameter whose
+      gradient stays ``None`` (DESIGN.md, "GATConv on one tensor");
     * ``add_self_loops=True`` (PyG's default, what ``MPNN`` constructs: model/mpnn.py:29-32) with an int
       ``in_channels``: a homogeneous graph, ONE transform (``lin_dst is lin_src``, as PyG builds it), input self
       loops removed and one loop per node appended.  ``state_dict`` carries the shared weight under both
@@ -155,11 +158,15 @@ class GATConv(nn.Module):
                 act: str = "identity") -> Tensor:
         if self.add_self_loops:
             return self._forward_loops(x, edge_index, act)
-        x_src, x_dst = (x, x) if isinstance(x, Tensor) else x
+        homogeneous = isinstance(x, Tensor)
+        x_src, x_dst = (x, x) if homogeneous else x
         self.lin_src.materialize(x_src.size(-1), x_src)
         self.lin_dst.materialize(x_dst.size(-1), x_dst)
         rel = _relation(edge_index, x_src.size(0), x_dst.size(0), both=torch.is_grad_enabled())
-        return Fh.GATConvFn.apply(x_src, x_dst, self.lin_src.weight, self.lin_dst.weight, self.att_src,
+        # ONE Tensor (HeteroConv's call when source and target type coincide): PyG transforms it once,
+        # ``x_src = x_dst = lin_src(x)``; lin_dst keeps its state_dict entry, is not used and gets no gradient
+        W_dst = self.lin_src.weight if homogeneous else self.lin_dst.weight
+        return Fh.GATConvFn.apply(x_src, x_dst, self.lin_src.weight, W_dst, self.att_src,
                                   self.att_dst, self.bias, rel, self.negative_slope, ACT[act])
 
     def _forward_loops(self, x: Tensor, edge_index: Union[Tensor, Relation], act: str) -> Tensor:

@@ -176,16 +176,36 @@ class GATConv(nn.Module):
         self.att_src = nn.Parameter(glorot_(torch.empty(1, 1, out_channels)))
         self.att_dst = nn.Parameter(glorot_(torch.empty(1, 1, out_channels)))
         self.bias = nn.Parameter(torch.zeros(out_channels))
+        self.last_logits: Optional[Tensor] = None    # attention logits of the last call, before the leaky ReLU
+        self.term_hook = None                        # optional callable(alpha_src, alpha_dst, h_src, h_dst) per call
 
-    def forward(self, x: Tuple[Tensor, Tensor], edge_index: Tensor) -> Tensor:
-        x_src, x_dst = x
+    def forward(self, x, edge_index: Tensor) -> Tensor:
+        """``x``: a pair ``(x_src, x_dst)`` (the bipartite call, one transform per role) or ONE Tensor (the
+        homogeneous call ``HeteroConv`` makes when source and target type coincide).  PyG 2.2 / 2.3's published
+        ``GATConv.forward`` (torch_geometric/nn/conv/gat_conv.py) for a Tensor input reads
+
+            if isinstance(x, Tensor):
+                x_src = x_dst = self.lin_src(x).view(-1, H, C)
+
+        ONE transform, ``lin_src``, serves both roles; ``lin_dst`` is not touched -- it exists when ``in_channels`` is
+        a tuple, as build_conv_relation passes it (model/hscn.py:117-125), and its gradient stays ``None``.  Both
+        attention vectors are used (``att_dst`` on the same transformed rows).  ``last_logits`` keeps the attention
+        logits before the leaky ReLU for the tests' kink guard."""
         H, C = 1, self.out_channels
-        h_src = self.lin_src(x_src).view(-1, H, C)
-        h_dst = self.lin_dst(x_dst).view(-1, H, C)
+        if isinstance(x, Tensor):
+            x_dst = x
+            h_src = h_dst = self.lin_src(x).view(-1, H, C)
+        else:
+            x_src, x_dst = x
+            h_src = self.lin_src(x_src).view(-1, H, C)
+            h_dst = self.lin_dst(x_dst).view(-1, H, C)
         alpha_src = (h_src * self.att_src).sum(dim=-1)      # [N_src, 1]
         alpha_dst = (h_dst * self.att_dst).sum(dim=-1)      # [N_dst, 1]
         row, col = edge_index[0], edge_index[1]
         alpha = alpha_src.index_select(0, row) + alpha_dst.index_select(0, col)
+        self.last_logits = alpha.detach()
+        if self.term_hook is not None:       # tests/helpers.TermMagnitudes: the row terms of d att_src / d att_dst
+            self.term_hook(alpha_src, alpha_dst, h_src, h_dst)
         alpha = F.leaky_relu(alpha, self.negative_slope)
         alpha = segment_softmax(alpha, col, x_dst.size(0))  # [E, 1]
         msg = alpha.unsqueeze(-1) * h_src.index_select(0, row)  # [E,1,C]

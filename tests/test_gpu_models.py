@@ -1,5 +1,8 @@
 """SCN / HSCN through the HIP path vs the CPU oracle with identical weights:
-activations within 1e-5, cluster indices bit-exact (BASELINE.json north_star)."""
+activations within 1e-5, cluster indices bit-exact (BASELINE.json north_star).  Parameter gradients: float64 as the
+referee between the float32 oracle and HIP (helpers.referee_all; the method and the derived bound for gradients whose
+sums cancel are described in tests/test_gpu_layered_f64.py and helpers.TermMagnitudes), behind a kink guard on the
+float64 oracle."""
 import numpy as np
 import pytest
 import torch
@@ -7,7 +10,8 @@ import torch
 from oracle import hetero_data as OH
 from oracle import models as OM
 from oracle import pyg_ops as P
-from tests.helpers import ATOL, DEV, close, scale_close, hetero_batch
+from tests.helpers import (ATOL, DEV, close, oracle_twin, grads_of, hetero_batch, referee_all, scale_close,
+                           scn_step_in_dtype)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,8 +30,14 @@ class _Batch(dict):
         self["local"] = L()
 
 
+# the batches whose float64 oracle satisfies the kink guard (asserted below); ("pascalvoc_sp", 2) does not -- one of its
+# ~30 000 ReLU inputs lies 5.5e-6 from zero -- and keeps its earlier bar, with ("pascalvoc_sp", 1) as its sibling
+HSCN_GUARDED = {("peptides_func", 6), ("peptides_struct", 5), ("pcqm_contact", 9), ("pascalvoc_sp", 1)}
+
+
 @pytest.mark.parametrize("name,B,K,H,L,C", [("peptides_func", 6, 16, 16, 3, 10), ("peptides_struct", 5, 32, 32, 2, 11),
-                                            ("pcqm_contact", 9, 16, 16, 3, 1), ("pascalvoc_sp", 2, 64, 16, 2, 21)])
+                                            ("pcqm_contact", 9, 16, 16, 3, 1), ("pascalvoc_sp", 2, 64, 16, 2, 21),
+                                            ("pascalvoc_sp", 1, 64, 16, 2, 21)])
 def test_hscn_forward_backward_matches_oracle(name, B, K, H, L, C):
     from graph_hscn.config.config import ACT_DICT
     from graph_hscn.model.hscn import HSCN
@@ -48,11 +58,26 @@ def test_hscn_forward_backward_matches_oracle(name, B, K, H, L, C):
     g = torch.randn(B, C, generator=torch.Generator().manual_seed(1))
     out_o.backward(g)
     out_d.backward(g.to(DEV))
-    for (n_, po), (_, pp) in zip(om.named_parameters(), pm.named_parameters()):
+
+    def step(m, dtype):
+        m({k: v.to(dtype) for k, v in b["x_dict"].items()}, b["edge_index_dict"], b["batch_local"], B).backward(g.to(dtype))
+
+    # every HeteroConv's outputs feed the hard ReLU, lin_1 the head's
+    g64, kg, _ = oracle_twin(om, step, gates=lambda m: list(m.convs) + [m.lin_1])
+    what = f"HSCN {name} B={B} K={K} H={H} L={L}"
+    for (n_, po), (_, pp) in zip(om.named_parameters(), pm.named_parameters()):      # the earlier bar, every case
         if po.grad is None:
             assert pp.grad is None, n_
         else:
             assert close(pp.grad, po.grad, atol=1e-4, rtol=1e-3), n_
+    if (name, B) in HSCN_GUARDED:
+        kg.check(ATOL, 1e-5, what)
+        referee_all(grads_of(pm), grads_of(om), g64, what)        # every tensor by the referee; the None pattern included
+    else:
+        # a ReLU input of this batch comes closer to zero than 4 x the forward bar (the kink guard cannot be met at
+        # this size): the gates may differ between the evaluations, so the referee does not apply here;
+        # ("pascalvoc_sp", 1) is the sibling that is refereed
+        print(f"{what}: kink guard margin {kg.margin():.3e}: earlier bar only")
 
 
 def test_hscn_virtual_branch_activations_match():
@@ -93,8 +118,52 @@ def test_scn_single_graph_step_matches_oracle(K, act, units):
         assert close(S_d, S_o)
         assert abs(mc_d.item() - mc_o.item()) < ATOL and abs(o_d.item() - o_o.item()) < ATOL
         assert torch.equal(adj_d.cpu(), adj_o)
-        for (n_, po), (_, pp) in zip(om.named_parameters(), pm.named_parameters()):
-            assert close(pp.grad, po.grad, atol=1e-4, rtol=2e-3), n_
+        _scn_referee(om, pm, [g], act, f"SCN single graph K={K} {act} {units} n={g.num_nodes}")
+
+
+# (case, tensor) pairs that may pass by helpers.TermMagnitudes' a-priori bound where the referee rejects them, with the
+# reason their sum cancels; every other tensor passes the referee (method: tests/test_gpu_layered_f64.py)
+SCN_CANCELLING = {
+    "SCN single graph K=4 tanh [16] n=243":
+        {"p.mlp.0.bias": "MinCUT losses are ratios invariant to the assignment's scale; softmax cotangent rows sum to zero"},
+}
+
+
+def _scn_referee(om, pm, graphs, act, what, atol=1e-4, rtol=2e-3):
+    """Every parameter gradient of mean over ``graphs`` of (mc + o): at the earlier bar (atol, rtol) against the float32
+    oracle, and through the float64 referee; ReLU inputs of the message-passing stack guarded.  A case listed in
+    SCN_CANCELLING records the terms of its sums, and referee and derived bound together must reject a reference with
+    one edge removed for the tensors named there."""
+    for (n_, po), (_, pp) in zip(om.named_parameters(), pm.named_parameters()):
+        assert close(pp.grad, po.grad, atol=atol, rtol=rtol), n_
+
+    def step_on(gs):
+        def step(m, dtype):
+            tot = 0.0
+            for x, ei in gs:
+                _, mc, o = scn_step_in_dtype(m, x, ei)
+                tot = tot + (mc + o)
+            (tot / len(gs)).backward()
+        return step
+
+    gs = [(g.x, g.edge_index) for g in graphs]
+    cancelling = SCN_CANCELLING.get(what, {})
+    gates = (lambda m: [getattr(m.mp, f"module_{2 * i}") for i in range(m.mp._n)]) if act == "relu" else None
+    K = om.mlp[-1].out_features
+    extra = len(graphs) * (max(g.num_nodes for g in graphs) + K + 4) if cancelling else None
+    g64, kg, terms = oracle_twin(om, step_on(gs), gates=gates, chain_extra=extra)
+    kg.check(ATOL, 1e-5, what)
+    got, g32 = grads_of(pm), grads_of(om)
+    referee_all(got, g32, g64, what, terms=terms, cancelling=cancelling)
+    if cancelling:
+        x0, ei0 = gs[0]
+        E = ei0.size(1)
+        dropped = []
+        for e in sorted(set(torch.linspace(0, E - 1, min(E, 48)).long().tolist())):
+            keep = torch.ones(E, dtype=torch.bool)
+            keep[e] = False
+            dropped.append(oracle_twin(om, step_on([(x0, ei0[:, keep])] + gs[1:]), guard=False)[0])
+        terms.bound_teeth(got, g32, g64, dropped, list(cancelling), what)
 
 
 def test_cluster_assignment_bit_exact_over_many_graphs():
@@ -215,8 +284,7 @@ def test_scn_dense_mfma_route_matches_oracle_through_the_model(route, K):
         print(f"[dense route ids] K={K} n={g.num_nodes}: flips {flips} of {g.num_nodes}, smallest top-2 margin "
               f"{float(margin.min()):.3e}, nodes with margin <= 1e-5: {int((margin <= 1e-5).sum())}")
         assert flips == 0
-        for (n_, po), (_, pp) in zip(om.named_parameters(), pm.named_parameters()):
-            assert close(pp.grad, po.grad, atol=1e-4, rtol=2e-3), n_
+        _scn_referee(om, pm, [g], "elu", f"SCN dense route {route} K={K} n={g.num_nodes}")
     # equally sized graphs as one [B,n,n] batch through forward_graphs: losses = mean over the graphs
     from graph_hscn.data import Batch
     same = [graphs[0], graphs[2], graphs[3]]
@@ -282,8 +350,7 @@ def test_scn_dense_route_on_a_ragged_batch_matches_the_oracle_loop(K, sizes, adj
     print(f"[ragged dense] K={K} sizes={sizes}: flips {flips} of {S_ref.size(0)}, smallest top-2 margin "
           f"{float((top[:, 0] - top[:, 1]).min()):.3e}")
     assert flips == 0
-    for (n_, po), (_, pp) in zip(om.named_parameters(), pm.named_parameters()):
-        assert close(pp.grad, po.grad, atol=1e-4, rtol=2e-3), n_
+    _scn_referee(om, pm, graphs, "elu", f"SCN dense-ragged K={K} sizes={sizes} {adj_format} directed={directed}")
 
 
 def test_static_gcn_norm_equals_gcn_norm_in_every_aggregate():

@@ -1,11 +1,13 @@
 """HIP operators (through the C ABI) vs the CPU oracle, same seeded inputs.
-Float tolerance 1e-5 (BASELINE.json north_star); index work bit-exact."""
+Float tolerance 1e-5 (BASELINE.json north_star); index work bit-exact.  Gradients: float64 as the referee between the
+float32 oracle and HIP (helpers.referee; tests/test_gpu_layered_f64.py has the method), behind a kink guard on the
+float64 oracle where a ReLU or the GAT leaky-ReLU gates them."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import pyg_ops as P
-from tests.helpers import ATOL, DEV, close, rand_graph
+from tests.helpers import ATOL, DEV, RTOL, KinkGuard, close, oracle_twin, grads_of, rand_graph, referee_all
 
 pytestmark = pytest.mark.gpu
 
@@ -69,6 +71,13 @@ def test_linear_fwd_bwd(rows, i, o, act):
     yo = ACT[act](torch.nn.functional.linear(xo, Wo, bo))
     gy = torch.randn(rows, o, generator=g)
     yo.backward(gy)
+    x6, W6, b6 = (t.detach().double().requires_grad_() for t in (x, W, b))
+    pre6 = torch.nn.functional.linear(x6, W6, b6)
+    ACT[act](pre6).backward(gy.double())
+    if act == "relu":
+        kg = KinkGuard()
+        kg.watch("relu input", pre6)
+        kg.check(ATOL, RTOL, f"linear {rows}x{i}->{o}")
     xd, Wd, bd = (t.to(DEV).requires_grad_() for t in (x, W, b))
     yd = Fh.linear(xd, Wd, bd, act)
     yd.backward(gy.to(DEV))
@@ -76,6 +85,8 @@ def test_linear_fwd_bwd(rows, i, o, act):
     assert close(xd.grad, xo.grad, atol=1e-4, rtol=1e-4)
     assert close(Wd.grad, Wo.grad, atol=1e-4 * max(1, rows / 100), rtol=1e-4)
     assert close(bd.grad, bo.grad, atol=1e-4 * max(1, rows / 100), rtol=1e-4)
+    referee_all(grads_of(None, x=xd, W=Wd, b=bd), grads_of(None, x=xo, W=Wo, b=bo), grads_of(None, x=x6, W=W6, b=b6),
+                f"linear {rows}x{i}->{o} {act}")
 
 
 @pytest.mark.parametrize("n,e,fin,h,seed", [(40, 100, 9, 16, 0), (500, 1200, 16, 16, 1), (300, 900, 16, 32, 2),
@@ -97,10 +108,18 @@ def test_gcn_conv(n, e, fin, h, seed):
     gy = torch.randn(n, h, generator=g)
     yo.backward(gy)
     yd.backward(gy.to(DEV))
+    x6 = x.detach().double().requires_grad_()
+
+    def step(m, dtype):
+        m(x6, ei).backward(gy.to(dtype))
+        return {"x": x6.grad}
+
+    g64, _, _ = oracle_twin(oc, step)                     # a linear operator: no gate to guard
     assert close(yd, yo)
     assert close(xd.grad, xo.grad, atol=1e-4, rtol=1e-4)
     assert close(pc.lin.weight.grad, oc.lin.weight.grad, atol=1e-3, rtol=1e-4)
     assert close(pc.bias.grad, oc.bias.grad, atol=1e-3, rtol=1e-4)
+    referee_all(grads_of(pc, x=xd), grads_of(oc, x=xo), g64, f"GCNConv n={n} e={e} {fin}->{h}")
 
 
 def test_gcn_aggregation_is_bitwise_the_cpu_order():
@@ -117,6 +136,9 @@ def test_gcn_aggregation_is_bitwise_the_cpu_order():
     assert torch.equal(got.cpu(), want)
 
 
+GRAPH_CONV_SEED = 0
+
+
 @pytest.mark.parametrize("act", ["identity", "elu", "tanh", "relu"])
 def test_graph_conv_weighted(act):
     from graph_hscn.nn import GraphConv
@@ -124,6 +146,7 @@ def test_graph_conv_weighted(act):
     n, fin, h = 150, 9, 16
     ei = rand_graph(n, 320, 5, symmetric=True)
     ei2, w = P.gcn_norm(ei, None, n, add_self_loops=True)
+    torch.manual_seed(GRAPH_CONV_SEED)                   # the weights: committed, so that the kink guard below is pinned
     oc = P.GraphConv(fin, h)
     pc = GraphConv(fin, h).to(DEV)
     pc.load_state_dict(oc.state_dict())
@@ -135,10 +158,26 @@ def test_graph_conv_weighted(act):
     gy = torch.randn(n, h, generator=g)
     yo.backward(gy)
     yd.backward(gy.to(DEV))
+    x6 = x.detach().double().requires_grad_()
+    kg = KinkGuard()
+
+    def step(m, dtype):
+        pre = m(x6, ei2, w.to(dtype))
+        if act == "relu":
+            kg.watch("relu input", pre)
+        ACT[act](pre).backward(gy.to(dtype))
+        return {"x": x6.grad}
+
+    g64, _, _ = oracle_twin(oc, step)
+    kg.check(2e-5, RTOL, f"GraphConv symmetric {act}")
     assert close(yd, yo, atol=2e-5)
     assert close(xd.grad, xo.grad, atol=1e-4, rtol=1e-4)
     for k in ("lin_rel.weight", "lin_rel.bias", "lin_root.weight"):
         assert close(dict(pc.named_parameters())[k].grad, dict(oc.named_parameters())[k].grad, atol=2e-3, rtol=1e-4), k
+    referee_all(grads_of(pc, x=xd), grads_of(oc, x=xo), g64, f"GraphConv symmetric weighted {act}")
+
+
+GAT_SEEDS = {2: 12}        # case seed -> weight seed where the case's own does not satisfy the kink guard
 
 
 @pytest.mark.parametrize("ns,nd,e,fin,h,seed", [(30, 4, 30, 9, 16, 0), (400, 37, 400, 16, 16, 1), (400, 37, 1500, 16, 32, 2),
@@ -150,6 +189,7 @@ def test_gat_conv_bipartite(ns, nd, e, fin, h, seed):
         ei = torch.stack([torch.arange(ns), torch.randint(0, nd, (ns,), generator=g)])
     else:
         ei = torch.stack([torch.randint(0, ns, (e,), generator=g), torch.randint(0, nd, (e,), generator=g)])
+    torch.manual_seed(GAT_SEEDS.get(seed, seed))          # the weights: committed, so that the kink guard below is pinned
     oc = P.GATConv((fin, fin), h)
     with torch.no_grad():
         oc.bias.normal_()
@@ -163,12 +203,21 @@ def test_gat_conv_bipartite(ns, nd, e, fin, h, seed):
     gy = torch.randn(nd, h, generator=g)
     yo.backward(gy)
     yd.backward(gy.to(DEV))
+    xs6, xd6 = xs.detach().double().requires_grad_(), xd_.detach().double().requires_grad_()
+
+    def step(m, dtype):
+        m((xs6, xd6), ei).backward(gy.to(dtype))
+        return {"xs": xs6.grad, "xd": xd6.grad}
+
+    g64, kg, _ = oracle_twin(oc, step)
+    kg.check(2e-5, 1e-5, f"GATConv bipartite {ns}->{nd} e={e}")          # the attention logits against the leaky kink
     assert close(yd, yo, atol=2e-5, rtol=1e-5)
     assert close(xsd.grad, xso.grad, atol=1e-4, rtol=1e-3)
     assert close(xdd.grad, xdo.grad, atol=1e-4, rtol=1e-3)
     po, pp = dict(oc.named_parameters()), dict(pc.named_parameters())
     for k in po:
         assert close(pp[k].grad, po[k].grad, atol=2e-3, rtol=1e-3), k
+    referee_all(grads_of(pc, xs=xsd, xd=xdd), grads_of(oc, xs=xso, xd=xdo), g64, f"GATConv bipartite {ns}->{nd} e={e} H={h}")
 
 
 @pytest.mark.parametrize("h", [16, 10, 128])

@@ -232,3 +232,49 @@ def test_scn_state_dict_keys_follow_pyg_names():
     h = OM.HSCN("GAT", "GCN", "GCN", OM.ACT["relu"], 9, 16, 10, 3)
     assert sum(p.numel() for p in h.parameters()) == 3306
     assert "convs.0.convs.local__to__virtual.att_src" in h.state_dict()
+
+
+def test_gat_conv_on_one_tensor_uses_lin_src_for_both_roles():
+    """GATConv((2, 2), 2, add_self_loops=False) called with ONE tensor, as HeteroConv calls a relation whose source and
+    target type coincide: PyG's forward does ``x_src = x_dst = lin_src(x)``, so lin_dst -- set to -100 I here -- must not
+    show up anywhere and gets no gradient.  Worked by hand with lin_src = I (h = x), att_src = e_0, att_dst = e_1:
+
+        x = [[1, 0], [.5, 2], [-1, 1]]   a_src = x[:, 0] = [1, .5, -1]   a_dst = x[:, 1] = [0, 2, 1]
+        edges 0->2, 1->2, 2->0, 1->0; node 1 has no in-edge
+        node 2: logits 1 + 1 = 2 and .5 + 1 = 1.5          -> alpha = sigmoid(.5), 1 - sigmoid(.5)
+        node 0: logits -1 + 0 = -1 -> leaky -.2; .5 + 0 = .5 -> alpha = sigmoid(-.7), sigmoid(.7)
+        node 1: bias alone"""
+    conv = P.GATConv((2, 2), 2)
+    with torch.no_grad():
+        conv.lin_src.weight.copy_(torch.eye(2))
+        conv.lin_dst.weight.copy_(-100.0 * torch.eye(2))
+        conv.att_src.copy_(torch.tensor([1.0, 0.0]).view(1, 1, 2))
+        conv.att_dst.copy_(torch.tensor([0.0, 1.0]).view(1, 1, 2))
+        conv.bias.copy_(torch.tensor([0.5, -0.5]))
+    x = torch.tensor([[1.0, 0.0], [0.5, 2.0], [-1.0, 1.0]], requires_grad=True)
+    ei = torch.tensor([[0, 1, 2, 1], [2, 2, 0, 0]])
+    out = conv(x, ei)
+    sg = lambda v: 1.0 / (1.0 + math.exp(-v))
+    b = np.array([0.5, -0.5])
+    want = np.stack([sg(-0.7) * np.array([-1.0, 1.0]) + sg(0.7) * np.array([0.5, 2.0]) + b,
+                     b,
+                     sg(0.5) * np.array([1.0, 0.0]) + (1 - sg(0.5)) * np.array([0.5, 2.0]) + b])
+    assert np.allclose(out.detach().numpy(), want, atol=1e-6)
+    assert conv.last_logits.view(-1).tolist() == pytest.approx([2.0, 1.5, -1.0, 0.5])
+    out.sum().backward()
+    assert conv.lin_dst.weight.grad is None
+    assert conv.lin_src.weight.grad is not None and conv.att_dst.grad is not None and x.grad is not None
+    # backward, by hand: d sum(out) / d bias = the number of rows.  d sum(out) / d att_dst: at node 2 both logits are
+    # positive, so a_dst[2] shifts them alike and the softmax removes it (0); at node 0 the two logits sit on different
+    # sides of the leaky kink: alpha(2->0) = sigmoid(.2 (a_src[2] + a_dst[0]) - (a_src[1] + a_dst[0])), a_dst[0] = x[0] . att_dst,
+    # sum(out[0]) = alpha * sum(h[2]) + (1 - alpha) * sum(h[1]) + const = 2.5 (1 - alpha), hence
+    # d / d att_dst = -2.5 * sigmoid(.7) sigmoid(-.7) * (.2 - 1) * x[0] = [2 sigmoid(.7) sigmoid(-.7), 0]
+    assert conv.bias.grad.tolist() == [3.0, 3.0]
+    assert conv.att_dst.grad.view(-1).tolist() == pytest.approx([2 * sg(0.7) * sg(-0.7), 0.0], abs=1e-6)
+    # the pair call with the same tensor in both roles is the OTHER operator: lin_dst = -100 I enters the logits (a
+    # per-target shift, which the softmax would cancel, but it moves both of node 2's logits below the leaky kink)
+    pair = conv((x.detach(), x.detach()), ei)
+    assert not np.allclose(pair.detach().numpy(), want, atol=1e-3)
+    # HeteroConv hands a same-type relation one tensor and a bipartite one a pair
+    het = P.HeteroConv({("a", "to", "a"): conv})
+    assert torch.equal(het({"a": x.detach()}, {("a", "to", "a"): ei})["a"], out.detach())
