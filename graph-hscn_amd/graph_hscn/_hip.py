@@ -186,6 +186,10 @@ _SIGNATURES = {
     "hscn_vl_forward": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64,
                                 c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int, c_int, c_int, c_int,
                                 P, c_int, c_float, P, P, P, P, P, P, P]),
+    # random-walk structural encoding of a batch as one launch (csrc/rwse.hip; additive to ABI 23)
+    "hscn_rwse_supported": (c_int, [c_int, c_int]),
+    "hscn_rwse_tile": (c_int, []),
+    "hscn_rwse_stats": (c_int, [P, P, P, c_int64, c_int64, c_int, c_int, P, P, P]),
 }
 
 

@@ -165,6 +165,33 @@ class PEConfig:  # config.py:115-130 (defaults.py:19-28)
 
 
 @dataclass
+class RWSEConfig:
+    """Random-walk structural encoding (transform/rwse.py, encoder/rwse.py): ``ksteps`` return probabilities per node,
+    encoded to ``dim_pe`` columns by one Linear ("linear") or ``layers`` Linear + ReLU ("mlp"), optionally behind a
+    BatchNorm over the raw statistics; ``compute_posenc`` dispatches on the config's type."""
+    dim_in: int
+    dim_emb: int
+    dim_pe: int
+    ksteps: int = 20
+    model: str = "linear"
+    layers: int = 1
+    raw_norm: str = "none"
+    pass_as_var: bool = False
+
+    def __post_init__(self) -> None:
+        if self.ksteps < 1:
+            raise ValueError("ksteps must be at least 1.")
+        if self.model not in ("linear", "mlp"):
+            raise ValueError(f"model must be 'linear' or 'mlp', got {self.model!r}.")
+        if self.layers < 1:
+            raise ValueError("layers must be at least 1.")
+        if self.raw_norm not in ("none", "batchnorm"):
+            raise ValueError(f"raw_norm must be 'none' or 'batchnorm', got {self.raw_norm!r}.")
+        if self.dim_emb - self.dim_pe < 1:
+            raise ValueError(f"RWSE size {self.dim_pe} is too large for desired embedding size of {self.dim_emb}.")
+
+
+@dataclass
 class TrainingConfig:  # config.py:133-152
     model_type: str
     loss_fn: str

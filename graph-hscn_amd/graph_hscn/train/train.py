@@ -46,15 +46,27 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
     ``transform.compute_posenc_stats_device`` (``pe_cfg``'s Laplacian and normaliser settings, ``is_undirected`` as the
     reference's loader passes it) on the encoder's device right before the encoder runs -- the PE stage of a batch is
     then two launches with no host pre-processing.  ``stats=None`` (default): the graphs carry pre-computed
-    statistics, as in the reference."""
+    statistics, as in the reference.
+
+    A ``config.RWSEConfig`` as ``pe_cfg`` selects the random-walk structural encoding instead: the encoder is ONE
+    ``RWSENodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb)``, and a batch that arrives without ``rwse`` gets it from
+    ``transform.compute_rwse_stats_device`` right before the encoder runs, under ``stats=None`` and ``stats="device"``
+    alike (there is no precomputed-only mode: the statistics are one cheap launch).  Everything else is the same."""
     if stats not in (None, "device"):
         raise ValueError(f"stats must be None or 'device', got {stats!r}")
+    from ..config.config import RWSEConfig
     from ..data import DataLoader
     from ..encoder.signnet import SignNetNodeEncoder
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
-    enc = SignNetNodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
-    enc.engine = "auto"
+    rwse = isinstance(pe_cfg, RWSEConfig)
+    if rwse:
+        from ..encoder.rwse import RWSENodeEncoder
+        from ..transform.rwse import compute_rwse_stats_device
+        enc = RWSENodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
+    else:
+        enc = SignNetNodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
+        enc.engine = "auto"
     compute_posenc.last_encoder = enc
     if logger is not None:
         logger.info("Running PE for each loader...")
@@ -65,7 +77,10 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
             for batch in loader:
                 batch = batch.to(device)
                 batch.x = batch.x.float()
-                if stats == "device" and getattr(batch, "eigvecs_sn", None) is None:
+                if rwse:
+                    if getattr(batch, "rwse", None) is None:
+                        compute_rwse_stats_device(batch, is_undirected, pe_cfg)
+                elif stats == "device" and getattr(batch, "eigvecs_sn", None) is None:
                     from ..transform.posenc import compute_posenc_stats_device
                     compute_posenc_stats_device(batch, is_undirected, pe_cfg)
                 data_list.append(enc(batch))

@@ -1291,6 +1291,33 @@ int hscn_pair_rank_reduce(const double* per_graph, int64_t B, int averaging, dou
                           int64_t* acc_count /*[1] or NULL*/, double* result /*[4]*/, int32_t* flags /*[1]*/,
                           void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Random-walk structural encoding (RWSE) of a collated batch as ONE launch (graph_hscn.transform.rwse;
+ * csrc/rwse.hip): the eigensolver-free positional statistics.  Purely additive to ABI 23.
+ *
+ * hscn_rwse_stats: rowptr [N + 1] / col: the stable CSR of the batch's edge list keyed by SOURCE, in batch numbering
+ *   (hscn_csr_build(src, dst), or hscn_csr_build_pair's rowptr_t / col_t): row r lists the targets of r.  Graph g owns
+ *   nodes [nptr[g], nptr[g+1]) (int32, B + 1 entries); max_n >= the largest graph's node count.
+ *   A[r, c] = the number of listed edges r -> c (duplicates sum, self loops are KEPT -- the Laplacian launch drops
+ *   them); deg[r] = rowptr[r+1] - rowptr[r], the out-degree; P = D^-1 A, a row with deg 0 all zero.
+ *   rw [N, ksteps] f32: rw[i, k-1] = (P^k)[i, i], k = 1 .. ksteps; a node without out-edges gets zeros.
+ *   Evaluated on column vectors, q_0 = e_i, q_{t+1}[r] = (1 / deg[r]) * sum_{c in row r} q_t[c], rw[i, t] = q_{t+1}[i]:
+ *   the sum in CSR order with plain float32 adds, then one reciprocal and one multiply.  All terms are non-negative:
+ *   an entry whose exact value is 0 is exactly 0.  No float atomics: the same input gives the same bits.
+ *   One workgroup per (graph, tile of hscn_rwse_tile() start nodes), grid B x ceil(max_n / tile): the tile's vectors
+ *   live in LDS as a ping-pong pair q[node][tile], 2 * max_n * tile * 4 bytes (64 KB at 512 nodes), one barrier per
+ *   step; a tile past its graph's node count returns at once.  No workspace.
+ *   flag [1] i32, zeroed by the caller, only ever OR-ed into: bit 1 = a CSR entry outside its graph's node range (it
+ *   adds nothing to its sum), bit 2 = a graph larger than max_n or outside [0, N) (its rows are NaN); bit 0 is unused,
+ *   so the bits read as hscn_lap_eig_stats's.
+ *   HSCN_E_BADARG for null pointers, negative sizes or ksteps < 1; HSCN_E_UNSUPPORTED where hscn_rwse_supported is 0
+ *   (max_n outside [1, 512] or ksteps > 64); both before any launch.  B = 0 or N = 0 launches nothing.
+ * ------------------------------------------------------------------------- */
+int hscn_rwse_supported(int max_n, int ksteps);
+int hscn_rwse_tile(void);
+int hscn_rwse_stats(const int32_t* rowptr, const int32_t* col, const int32_t* nptr, int64_t N, int64_t B, int max_n,
+                    int ksteps, float* rw /*[N, ksteps]*/, int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
