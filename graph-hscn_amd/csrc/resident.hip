@@ -20,6 +20,31 @@ int hscn_resident_supported(int F, int H, int L, int C, int max_n, int max_v, in
   return 1;
 }
 
+// Host arithmetic only: the arguments' size fields go through plan_fwd / plan_bwd, the functions launch_fwd and
+// launch_bwd take their choices from.
+int hscn_resident_launch_plan(int F, int H, int L, int C, int max_n, int max_v, int max_ell, int max_evv,
+                              int want_export, int32_t* plan_host) {
+  if (!plan_host) return HSCN_E_BADARG;
+  if (!hscn_resident_supported(F, H, L, C, max_n, max_v, max_ell, max_evv)) return HSCN_E_UNSUPPORTED;
+  FwdArgs Af{};
+  Af.F = F; Af.L = L; Af.C = C; Af.max_n = max_n; Af.max_v = max_v; Af.max_ell = max_ell; Af.max_evv = max_evv;
+  BwdArgs Ab{};
+  Ab.F = F; Ab.L = L; Ab.C = C; Ab.max_n = max_n; Ab.max_ell = max_ell;
+  FwdPlan Pf;
+  BwdPlan Pb;
+  if (int rc = plan_fwd(Af, H, want_export != 0, Pf)) return rc;
+  if (int rc = plan_bwd(Ab, H, Pb)) return rc;
+  if (Pf.threads != Pb.threads) return HSCN_E_UNSUPPORTED;   // (one rule, resident_threads: cannot happen)
+  plan_host[HSCN_PLAN_THREADS] = Pf.threads;
+  plan_host[HSCN_PLAN_FWD_DB] = Af.db;
+  plan_host[HSCN_PLAN_FWD_EXP] = Af.exp;
+  plan_host[HSCN_PLAN_CSR_LAUNCH] = Pf.csr_launch;
+  plan_host[HSCN_PLAN_BWD_TWO] = Ab.two;
+  plan_host[HSCN_PLAN_FWD_LDS] = (int32_t)Pf.lds;
+  plan_host[HSCN_PLAN_BWD_LDS] = (int32_t)Pb.lds;
+  return 0;
+}
+
 int64_t hscn_resident_param_count(int F, int H, int L, int C) {
   int64_t P = 0;
   for (int l = 0; l < L; ++l) P += (int64_t)H * (l == 0 ? F : H) + H;

@@ -1940,6 +1940,45 @@ inline size_t pick_bwd_lds(BwdArgs& A, int H) {
 
 // Workgroup size: 16 waves (4 per SIMD) hide the LDS / global latency of the many short
 // phases; tiny graphs (PCQM-Contact, n <= 64) do not have the rows to feed them.
+inline int resident_threads(int max_n) { return max_n <= 64 ? 256 : 1024; }
+
+// ---- the launch plan: every size-dependent choice launch_fwd / launch_bwd make, taken HERE and nowhere else, so
+// hscn_resident_launch_plan (host arithmetic only) reports what the launches do rather than a restatement of it ----
+struct FwdPlan {
+  int threads;       // workgroup size
+  int csr_launch;    // the export was wanted and did not fit: k_ll_csr_t runs as a launch of its own
+  size_t lds;        // dynamic LDS of the forward launch (A.db / A.exp / A.exp_dinv are set in the arguments)
+  size_t csr_lds;    // dynamic LDS of k_ll_csr_t (0 without that launch)
+};
+// preference order: CSR export in the launch with double-buffered weights, then single-buffered (pick_fwd_lds), then
+// dropping the in-launch export (a separate light kernel builds it)
+inline int plan_fwd(FwdArgs& A, int H, bool want_exp, FwdPlan& P) {
+  bool ok = false;
+  P.lds = 0;
+  for (int e = 1; e >= 0 && !ok; --e) {
+    A.exp = (want_exp && e) ? 1 : 0;
+    P.lds = pick_fwd_lds(A, H);
+    ok = P.lds <= 160 * 1024;
+  }
+  if (!ok) return HSCN_E_UNSUPPORTED;
+  A.exp_dinv = A.exp;
+  P.threads = resident_threads(A.max_n);
+  P.csr_launch = (want_exp && !A.exp) ? 1 : 0;
+  P.csr_lds = P.csr_launch ? ((size_t)4 * A.max_ell + 2 * ((size_t)A.max_n + 1) + 16) * 4 : 0;
+  if (P.csr_lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
+  return 0;
+}
+struct BwdPlan {
+  int threads;
+  size_t lds;        // (A.two is set in the arguments)
+};
+inline int plan_bwd(BwdArgs& A, int H, BwdPlan& P) {
+  P.lds = pick_bwd_lds(A, H);
+  if (P.lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
+  P.threads = resident_threads(A.max_n);
+  return 0;
+}
+
 template <int H, int RT, int MODE, typename TS>
 int launch_fwd_mode(const FwdArgs& A, int64_t B, size_t lds, hipStream_t st) {
   if (lds > 64 * 1024)
@@ -2085,27 +2124,15 @@ __global__ void __launch_bounds__(256) k_structure(const StructArgs A) {
 
 template <int H, typename TS>
 int launch_fwd(FwdArgs& A, int64_t B, hipStream_t st) {
-  // preference order: concurrent wave groups + CSR export, then dropping the third n x H buffer,
-  // then dropping the in-launch export (a separate light kernel builds it)
-  const bool want_exp = A.csr_rowptr_t != nullptr;
-  size_t lds = 0;
-  bool ok = false;
   A.spec = A.compute_virtual ? 1 : 0;       // (the side-by-side wave groups cost no LDS any more)
-  for (int e = 1; e >= 0 && !ok; --e) {
-    A.exp = (want_exp && e) ? 1 : 0;
-    lds = pick_fwd_lds(A, H);
-    ok = lds <= 160 * 1024;
-  }
-  if (!ok) return HSCN_E_UNSUPPORTED;
-  A.exp_dinv = A.exp;
-  const int rc = A.max_n <= 64 ? launch_fwd_rt<H, 256, TS>(A, B, lds, st) : launch_fwd_rt<H, 1024, TS>(A, B, lds, st);
+  FwdPlan P;
+  if (int rc = plan_fwd(A, H, A.csr_rowptr_t != nullptr, P)) return rc;
+  const int rc = P.threads == 256 ? launch_fwd_rt<H, 256, TS>(A, B, P.lds, st) : launch_fwd_rt<H, 1024, TS>(A, B, P.lds, st);
   if (rc) return rc;
-  if (want_exp && !A.exp) {
-    const size_t l2 = ((size_t)4 * A.max_ell + 2 * ((size_t)A.max_n + 1) + 16) * 4;
-    if (l2 > 160 * 1024) return HSCN_E_UNSUPPORTED;
-    if (l2 > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_ll_csr_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-    k_ll_csr_t<<<(unsigned)B, 256, l2, st>>>(A);
+  if (P.csr_launch) {
+    if (P.csr_lds > 64 * 1024)
+      (void)hipFuncSetAttribute((const void*)k_ll_csr_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.csr_lds);
+    k_ll_csr_t<<<(unsigned)B, 256, P.csr_lds, st>>>(A);
     HSCN_RETURN_IF_LAUNCH_FAILED();
   }
   return 0;
@@ -2121,10 +2148,10 @@ int launch_bwd_rt(const BwdArgs& A, int64_t B, size_t lds, hipStream_t st) {
 }
 template <int H, typename TS>
 int launch_bwd(BwdArgs& A, int64_t B, hipStream_t st) {
-  const size_t lds = pick_bwd_lds(A, H);
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (A.max_n <= 64) return launch_bwd_rt<H, 256, TS>(A, B, lds, st);
-  return launch_bwd_rt<H, 1024, TS>(A, B, lds, st);
+  BwdPlan P;
+  if (int rc = plan_bwd(A, H, P)) return rc;
+  if (P.threads == 256) return launch_bwd_rt<H, 256, TS>(A, B, P.lds, st);
+  return launch_bwd_rt<H, 1024, TS>(A, B, P.lds, st);
 }
 
 template <int H, int RT, typename TS>
@@ -2148,7 +2175,7 @@ int launch_bwd_virtual(BwdArgs& Ab, FwdArgs& Af, int64_t B, hipStream_t st) {
   ok = lf <= 160 * 1024;
   if (!ok || lb > 160 * 1024) return HSCN_E_UNSUPPORTED;
   const size_t lds = lb > lf ? lb : lf;
-  if (Ab.max_n <= 64) return launch_bwd_virtual_rt<H, 256, TS>(Ab, Af, B, lds, st);
+  if (resident_threads(Ab.max_n) == 256) return launch_bwd_virtual_rt<H, 256, TS>(Ab, Af, B, lds, st);
   return launch_bwd_virtual_rt<H, 1024, TS>(Ab, Af, B, lds, st);
 }
 
@@ -2249,7 +2276,7 @@ int launch_fwd_pair(FwdArgs& Al, FwdArgs& Av, int64_t B, hipStream_t st) {
   if (!ok) return HSCN_E_UNSUPPORTED;
   if (!v_can) { Av.ll_src = nullptr; Av.ll_dst = nullptr; }
   const size_t lds = ll > lv ? ll : lv;
-  int rc = Al.max_n <= 64 ? launch_fwd_pair_rt<H, 256, TS>(Al, Av, B, lds, st)
+  int rc = resident_threads(Al.max_n) == 256 ? launch_fwd_pair_rt<H, 256, TS>(Al, Av, B, lds, st)
                           : launch_fwd_pair_rt<H, 1024, TS>(Al, Av, B, lds, st);
   if (rc) return rc;
   if (want_exp && !Al.exp && !v_can) {

@@ -17,7 +17,7 @@ import torch
 _LIB_PATH = os.environ.get("HSCN_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libhscn.so")
 _lib: Optional[ctypes.CDLL] = None
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 # `flags` of the resident entry points (include/hscn.h)
 STORE_F16 = 1
 GRAD_ACCUMULATE = 2
@@ -80,6 +80,7 @@ _SIGNATURES = {
                                   ctypes.c_double, ctypes.c_double, c_int, c_float, P, c_int, P]),
     "hscn_clip_grad_norm_flat": (c_int, [P, c_int64, c_float, P, P]),
     "hscn_resident_supported": (c_int, [c_int] * 8),
+    "hscn_resident_launch_plan": (c_int, [c_int] * 9 + [P]),
     "hscn_resident_param_count": (c_int64, [c_int] * 4),
     "hscn_resident_fwd": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64,
                                   c_int64, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int,
@@ -225,6 +226,22 @@ def lib() -> ctypes.CDLL:
         raise HipExtensionMissing(f"libhscn.so ABI {v} != expected {ABI_VERSION}")
     _lib = L
     return L
+
+
+PLAN_FIELDS = ("threads", "db", "exp", "csr_launch", "two", "fwd_lds", "bwd_lds")      # include/hscn.h: HSCN_PLAN_*
+
+
+def resident_launch_plan(F: int, H: int, L: int, C: int, max_n: int, max_v: int, max_ell: int, max_evv: int,
+                         want_export: bool = True) -> Optional[dict]:
+    """What hscn_resident_fwd / hscn_resident_bwd choose for these maxima (hscn_resident_launch_plan: host arithmetic,
+    no device needed): {"threads", "db", "exp", "csr_launch", "two", "fwd_lds", "bwd_lds"}, or None where
+    hscn_resident_supported answers 0."""
+    buf = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    rc = lib().hscn_resident_launch_plan(F, H, L, C, max_n, max_v, max_ell, max_evv, int(bool(want_export)), buf)
+    if rc == -3:
+        return None
+    check(rc, "hscn_resident_launch_plan")
+    return dict(zip(PLAN_FIELDS, (int(v) for v in buf)))
 
 
 def exported_symbols():

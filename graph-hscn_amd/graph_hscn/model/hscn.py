@@ -132,7 +132,13 @@ class SCN(nn.Module):
         ``with_total`` also ``mc_loss + o_loss`` (train_clustering.py:48), which the fused launch
         produces itself -- no add launch, and its backward reaches the kernel as one scalar."""
         dev = self.mp.module_0.lin_rel.weight.device
-        if self.resident_ok(data):
+        # the fused launch pair returns parameter gradients only: a differentiable input (something trainable feeds
+        # the features) takes the layered operators, which return its gradient
+        wants_x_grad = torch.is_grad_enabled() and data.x.requires_grad
+        if wants_x_grad and data.x.dtype == torch.float16:
+            raise RuntimeError("half-precision features that require grad: half storage runs on the fused stage-A "
+                               "launch only, and that launch returns no gradient for its input features")
+        if not wants_x_grad and self.resident_ok(data):
             conv, lin = self.mp.module_0, list(self.mlp)[0]
             meta = _engine.scn_meta(data, dev)
             x = data.x if data.x.is_cuda else data.x.to(dev)
@@ -336,6 +342,20 @@ class HSCN(nn.Module):
         if self.vl_conv is not None:
             if self.engine == "resident":
                 self._refuse_vl("the graph-resident engine (hscn_resident_*)")
+            return None
+        # the launch pair returns parameter gradients only (HSCNResidentFn.backward): with a differentiable feature
+        # input -- a trainable node encoder in front of the model -- "auto" takes the layered operators, which return
+        # that gradient, and "resident" refuses rather than cut the graph silently
+        if torch.is_grad_enabled() and any(isinstance(v, Tensor) and v.requires_grad for v in x_dict.values()):
+            which = sorted(k for k, v in x_dict.items() if isinstance(v, Tensor) and v.requires_grad)
+            if any(x_dict[k].dtype == torch.float16 for k in which):
+                raise RuntimeError(f"half-precision node features that require grad ({which}): half storage runs on "
+                                   "the graph-resident engine only, and that engine returns no gradient for its "
+                                   "feature inputs")
+            if self.engine == "resident":
+                raise RuntimeError(f"engine='resident' requested but the node features {which} require grad: the "
+                                   "graph-resident launches return no gradient for their feature inputs "
+                                   "(engine='auto' or 'layered' runs the layered operators, which do)")
             return None
         name = _act_name(self.activation)
         ok = (name in ACT_DICT and set(edge_index_dict) == {LL, VV, LV} and "local" in x_dict

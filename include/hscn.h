@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HSCN_ABI_VERSION 23
+#define HSCN_ABI_VERSION 24
 
 #define HSCN_E_BADARG (-1)   /* null pointer, negative size, unsupported width */
 #define HSCN_E_WORKSPACE (-2) /* workspace too small */
@@ -574,6 +574,27 @@ typedef struct hscn_loss_tail {
 } hscn_loss_tail;
 int hscn_resident_supported(int F, int H, int L, int C, int max_n, int max_v, int max_ell, int max_evv);
 int64_t hscn_resident_param_count(int F, int H, int L, int C);
+/* The size-dependent choices hscn_resident_fwd (compute_virtual 0 or 1) and hscn_resident_bwd make for these
+ * maxima (ABI 24): host arithmetic only, no stream and no launch, through the same functions the launches take
+ * them from.  want_export != 0: the forward is asked for the source-keyed CSR (csr_rowptr_t != NULL).  Fills
+ * plan_host[HSCN_PLAN_COUNT]; returns 0, HSCN_E_UNSUPPORTED where hscn_resident_supported answers 0, HSCN_E_BADARG
+ * for a NULL plan_host.
+ *   HSCN_PLAN_THREADS     threads per workgroup of both launches: 256 (max_n <= 64) or 1024
+ *   HSCN_PLAN_FWD_DB      1 = the forward keeps two weight buffers in LDS (H <= 32 and they fit)
+ *   HSCN_PLAN_FWD_EXP     1 = the forward launch builds and exports the source-keyed CSR itself
+ *   HSCN_PLAN_CSR_LAUNCH  1 = the export was wanted and did not fit: a light launch of its own builds it
+ *   HSCN_PLAN_BWD_TWO     1 = the backward works in two n x H buffers instead of three
+ *   HSCN_PLAN_FWD_LDS / HSCN_PLAN_BWD_LDS   dynamic LDS bytes of the two launches */
+#define HSCN_PLAN_THREADS 0
+#define HSCN_PLAN_FWD_DB 1
+#define HSCN_PLAN_FWD_EXP 2
+#define HSCN_PLAN_CSR_LAUNCH 3
+#define HSCN_PLAN_BWD_TWO 4
+#define HSCN_PLAN_FWD_LDS 5
+#define HSCN_PLAN_BWD_LDS 6
+#define HSCN_PLAN_COUNT 7
+int hscn_resident_launch_plan(int F, int H, int L, int C, int max_n, int max_v, int max_ell, int max_evv,
+                              int want_export, int32_t* plan_host);
 int hscn_resident_fwd(const void* x_local, const void* x_virtual, const int64_t* ei_ll, int64_t E_ll,
                       const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv,
                       const int32_t* lptr, const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv,

@@ -87,7 +87,7 @@ def test_header_defines_the_flag_bits_the_binding_uses():
     src = open(os.path.join(ROOT, "include", "hscn.h")).read()
     assert int(re.search(r"#define HSCN_STORE_F16 (\d+)", src).group(1)) == _hip.STORE_F16 == _STORE_F16
     assert int(re.search(r"#define HSCN_GRAD_ACCUMULATE (\d+)", src).group(1)) == _hip.GRAD_ACCUMULATE == _GRAD_ACCUMULATE
-    assert int(re.search(r"#define HSCN_ABI_VERSION (\d+)", src).group(1)) == _hip.ABI_VERSION == 23
+    assert int(re.search(r"#define HSCN_ABI_VERSION (\d+)", src).group(1)) == _hip.ABI_VERSION == 24
     # every entry point whose prototype has `int flags` is in the table above, and no other
     body = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     flagged = re.findall(r"\b(hscn_[a-z0-9_]+)\s*\([^;{}]*\bint flags\s*,\s*void\* stream\)", body)

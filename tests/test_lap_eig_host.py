@@ -23,7 +23,7 @@ def test_exports_are_in_header_library_and_binding():
         assert re.search(r"\b%s\s*\(" % name, src), name
         assert hasattr(lib, name), name
         assert name in _hip._SIGNATURES, name
-    assert lib.hscn_abi_version() == 23
+    assert lib.hscn_abi_version() == 24
     # the launch takes no `flags` word (tests/test_abi.py lists the entry points that do)
     assert not re.search(r"hscn_lap_eig_stats\s*\([^;{}]*\bint flags\s*,\s*void\* stream\)", src)
 

@@ -82,7 +82,7 @@ def test_binding_declares_the_new_symbols():
     for name in ("hscn_softmax_nll_fwd", "hscn_softmax_nll_workspace_bytes", "hscn_multiclass_metrics"):
         assert name in sig and name in _hip.exported_symbols()
     assert len(sig["hscn_softmax_nll_fwd"][1]) == 11 and len(sig["hscn_multiclass_metrics"][1]) == 9
-    assert _hip.ABI_VERSION == 23
+    assert _hip.ABI_VERSION == 24
     header = open(__import__("os").path.join(__import__("os").path.dirname(__file__), "..", "include", "hscn.h")).read()
     for name in ("hscn_softmax_nll_fwd(", "hscn_softmax_nll_workspace_bytes(", "hscn_multiclass_metrics("):
         assert name in header

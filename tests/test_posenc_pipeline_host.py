@@ -121,7 +121,7 @@ def test_pre_transform_in_memory():
 def test_abi_version_and_new_symbols():
     from graph_hscn import _hip
     lib = _hip.lib()
-    assert lib.hscn_abi_version() == 23 == _hip.ABI_VERSION
+    assert lib.hscn_abi_version() == 24 == _hip.ABI_VERSION
     assert {"hscn_signnet_supported", "hscn_signnet_encode"} <= set(_hip.exported_symbols())
 
 

@@ -23,7 +23,7 @@ def test_exports_are_in_header_library_and_binding():
         assert re.search(r"\b%s\s*\(" % name, src), name
         assert hasattr(lib, name), name
         assert name in _hip._SIGNATURES, name
-    assert lib.hscn_abi_version() == 23
+    assert lib.hscn_abi_version() == 24
 
 
 def test_envelope_and_tile():
