@@ -191,6 +191,13 @@ _SIGNATURES = {
     "hscn_rwse_supported": (c_int, [c_int, c_int]),
     "hscn_rwse_tile": (c_int, []),
     "hscn_rwse_stats": (c_int, [P, P, P, c_int64, c_int64, c_int, c_int, P, P, P]),
+    # GINEConv's aggregate with edge features (csrc/gine.hip; additive to ABI 23)
+    "hscn_gine_supported": (c_int, [c_int, c_int]),
+    "hscn_gine_long_row": (c_int, []),
+    "hscn_gine_chunk": (c_int, []),
+    "hscn_gine_aggregate_fwd": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int64, c_int64, c_int, c_int, P, P]),
+    "hscn_gine_aggregate_bwd_x": (c_int, [P, P, P, P, P, P, P, c_float, P, P, c_int64, c_int64, c_int, c_int, P, P]),
+    "hscn_gine_aggregate_bwd_msg": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int, P, P]),
 }
 
 

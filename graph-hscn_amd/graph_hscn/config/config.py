@@ -12,7 +12,7 @@ from typing import Callable, Optional
 
 from torch.optim import Adagrad, Adam, AdamW
 
-from ..nn.conv import GATConv, GCNConv
+from ..nn.conv import GINE, GATConv, GCNConv
 from ..nn.functional import Activation
 
 # defaults.py:1-39
@@ -43,7 +43,10 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 # (model/mpnn.py:29-32 calls conv(in, out), i.e. add_self_loops=True): "gcn" through GCNConv's
 # explicit-loop relation, "gat" through GATConv's shared transform and implicit-loop kernels
 # (nn/conv.py, csrc/gat_loops.hip).  Only "gcn" qualifies for the one-launch MPNN step.
-CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv}
+# "gine" (extension; "gin" stays absent, as it cannot be built in the reference either): the edge-aware baseline,
+# nn/conv.py GINE = GINEConv over Linear-ReLU-Linear (csrc/gine.hip).  It reads ``batch.edge_attr``, builds the MPNN
+# baseline only (the hetero graph carries no edge features: build_conv_relation refuses it) and runs layered.
+CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE}
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
 SCHEDULERS = ("cosine_with_warmup", "linear_with_warmup", "step")  # extension: optim.SCHEDULE_KINDS
 TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "graph" only

@@ -5,7 +5,7 @@ few container behaviours the hot path's callers use
 (/root/reference/graph_hscn/train/train.py:73-77, train_clustering.py:36-47,
 loader/hetero_data.py:62-87, loader/loader.py:48-60):
 
-  Data(x, edge_index, edge_weight, y, num_nodes), ``.to(device)``
+  Data(x, edge_index, edge_weight, y, num_nodes, edge_attr=[E, De]), ``.to(device)``
   HeteroData: ``h["local"].x``, ``h["local","to","local"].edge_index``,
               ``.x_dict``, ``.edge_index_dict``
   Batch / HeteroBatch ``.from_data_list`` with PyG collate semantics
@@ -101,7 +101,7 @@ def _cat_targets(ys: Sequence[Tensor]) -> Tensor:
 # what a Batch holds that is not a per-node extra of its graphs
 _BATCH_KEYS = frozenset(["x", "edge_index", "y", "edge_weight", "num_nodes", "batch", "ptr", "num_graphs", "ptr32",
                          "eptr32", "max_nodes", "max_edges", "edge_label_index", "edge_label", "pair_ptr32",
-                         "max_pairs"])
+                         "max_pairs", "edge_attr"])
 
 
 def has_link_labels(store) -> bool:
@@ -145,6 +145,23 @@ def _collate_link_labels(out, stores: Sequence, offsets) -> None:
     pptr[1:] = torch.cumsum(torch.as_tensor(ps, dtype=torch.int64), 0).to(torch.int32)
     out.pair_ptr32 = pptr                        # pairs of graph g are [pair_ptr32[g], pair_ptr32[g + 1])
     out.max_pairs = int(max(ps)) if ps else 0
+
+
+def _collate_edge_attr(out, graphs: Sequence) -> None:
+    """``edge_attr`` [sum E_i, De] of a batch onto ``out`` (row k belongs to edge ``edge_index[:, k]``), when every graph
+    carries edge features; a list in which only some do, or a malformed one, is refused."""
+    have = ["edge_attr" in g and g.edge_attr is not None for g in graphs]
+    if not any(have):
+        return
+    if not all(have):
+        raise ValueError("some graphs of the batch carry edge_attr and some do not")
+    for g in graphs:
+        ea = g.edge_attr
+        if not isinstance(ea, Tensor) or ea.dim() != 2:
+            raise ValueError("edge_attr must be an [E, De] tensor, one row per edge")
+        if ea.size(0) != g.edge_index.size(1):
+            raise ValueError(f"edge_attr has {ea.size(0)} rows, edge_index has {g.edge_index.size(1)} edges")
+    out.edge_attr = torch.cat([g.edge_attr for g in graphs], 0)
 
 
 def _node_extras(graphs: Sequence[Data], ns: Sequence[int]) -> List[str]:
@@ -191,17 +208,19 @@ class Batch(Data):
         for k in _node_extras(graphs, ns) if graphs else []:     # per-node extras, concatenated like x
             out._d[k] = torch.cat([g._d[k] for g in graphs], 0)
         _collate_link_labels(out, graphs, ptr[:-1].tolist())
+        _collate_edge_attr(out, graphs)
         return out
 
     def to_data_list(self) -> List[Data]:
         """The inverse of ``from_data_list`` (PyG ``Batch.to_data_list``): per graph its rows of ``x`` and of every
-        per-node extra, its edges with the node offset removed, its edge weights and its target -- row ``i`` of a
+        per-node extra, its edges with the node offset removed, its edge weights and edge features and its target -- row ``i`` of a
         ``[B, ...]`` target, or the graph's node range of a per-node one (``_cat_targets``)."""
         B, N = int(self.num_graphs), int(self.num_nodes)
         ptr = [int(v) for v in self.ptr.tolist()]
         eptr = [int(v) for v in self.eptr32.tolist()]
         y = self._d.get("y")
         ew = self._d.get("edge_weight")
+        ea_all = self._d.get("edge_attr")
         extras = [k for k, v in self._d.items()
                   if k not in _BATCH_KEYS and isinstance(v, Tensor) and v.dim() >= 1 and v.size(0) == N]
         per_graph_y = y is not None and y.size(0) == B
@@ -218,6 +237,8 @@ class Batch(Data):
                 g.y = y[i:i + 1] if per_graph_y else y[a:b]
             if ew is not None:
                 g.edge_weight = ew[ea:eb]
+            if ea_all is not None:
+                g.edge_attr = ea_all[ea:eb]
             for k in extras:
                 g._d[k] = self._d[k][a:b]
             if pairs is not None:

@@ -20,6 +20,10 @@ from ..data import Data
 
 # OGB atom feature cardinalities (9 integer columns)
 _ATOM_CARD = np.array([119, 5, 12, 12, 10, 6, 6, 2, 2])
+# OGB bond feature cardinalities (3 integer columns: bond type, stereo, conjugation)
+_BOND_CARD = np.array([5, 6, 2])
+# edge feature width of the "normal" (superpixel) shapes: float boundary statistics
+_NORMAL_EDGE_DIM = 2
 
 
 @dataclass(frozen=True)
@@ -152,10 +156,34 @@ def _link_labels(rng: np.random.Generator, n: int, ei: np.ndarray, prob: float =
     return torch.from_numpy(index), torch.from_numpy(contact[u, v].astype(np.float32))
 
 
+def _edge_features(rng: np.random.Generator, shape: Shape, ei: np.ndarray) -> torch.Tensor:
+    """One feature row per undirected bond, carried by both of its directions (the adjacent columns (i, j), (j, i) of
+    ``ei``): int64 [E, 3] bond columns for "atom" shapes, float32 [E, 2] for "normal" ones."""
+    m = ei.shape[1] // 2
+    if shape.feature_kind == "atom":
+        und = np.stack([rng.integers(0, c, size=m) for c in _BOND_CARD], 1).astype(np.int64)
+    else:
+        und = rng.normal(size=(m, _NORMAL_EDGE_DIM)).astype(np.float32)
+    return torch.from_numpy(np.repeat(und, 2, axis=0))
+
+
 def make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int] = None,
-               label_rng: Optional[np.random.Generator] = None) -> Data:
+               label_rng: Optional[np.random.Generator] = None, edge_features: bool = False,
+               edge_rng: Optional[np.random.Generator] = None) -> Data:
     """``label_rng`` (link shapes): the generator of the label draws; ``make_dataset`` passes a stream of its own, so
-    that the graph stream ``rng`` is spent exactly as the graph-level shape spends it."""
+    that the graph stream ``rng`` is spent exactly as the graph-level shape spends it.  ``edge_features``: the graph
+    also gets ``edge_attr`` (``_edge_features``), drawn from ``edge_rng`` -- a stream of its own again, so that the
+    graph is the same with and without them; without one, a generator seeded from the graph's edge count serves."""
+    g = _make_graph(rng, shape, n, label_rng)
+    if edge_features:
+        ei = g.edge_index.numpy()
+        g.edge_attr = _edge_features(edge_rng if edge_rng is not None else np.random.default_rng([ei.shape[1], 2]),
+                                     shape, ei)
+    return g
+
+
+def _make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int],
+                label_rng: Optional[np.random.Generator]) -> Data:
     if n is None:
         n = int(np.clip(round(rng.normal(shape.n_mean, shape.n_std)), shape.n_min, shape.n_max))
     n_und = max(n - 1, int(round(shape.und_per_node * n)))
@@ -179,9 +207,13 @@ def make_graph(rng: np.random.Generator, shape: Shape, n: Optional[int] = None,
     return Data(x=x, edge_index=torch.from_numpy(ei), y=y, num_nodes=n)
 
 
-def make_dataset(name: str, num_graphs: int, seed: int = 0) -> List[Data]:
-    """``num_graphs`` seeded graphs of the named LRGB shape."""
+def make_dataset(name: str, num_graphs: int, seed: int = 0, edge_features: bool = False) -> List[Data]:
+    """``num_graphs`` seeded graphs of the named LRGB shape.  ``edge_features``: every graph also carries
+    ``edge_attr``, drawn from a generator of its own (``[seed, 2]``): ``x``, ``edge_index`` and the targets are the
+    same bits with and without it."""
     shape = SHAPES[name] if name in SHAPES else (NODE_SHAPES[name] if name in NODE_SHAPES else LINK_SHAPES[name])
     rng = np.random.default_rng(seed)
     label_rng = np.random.default_rng([seed, 1]) if shape.task == "link" else None
-    return [make_graph(rng, shape, label_rng=label_rng) for _ in range(num_graphs)]
+    edge_rng = np.random.default_rng([seed, 2]) if edge_features else None
+    return [make_graph(rng, shape, label_rng=label_rng, edge_features=edge_features, edge_rng=edge_rng)
+            for _ in range(num_graphs)]

@@ -147,6 +147,18 @@ class MPNN(nn.Module):
             raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
         return self._forward(batch)
 
+    def _edge_attr(self, batch) -> Tensor:
+        """``batch.edge_attr`` for the layers with ``uses_edge_attr``: float32 [E, De] on the model's device."""
+        ea = getattr(batch, "edge_attr", None)
+        if ea is None:
+            raise ValueError("the model has edge-aware convolutions (conv_type 'gine') and the batch carries no "
+                             "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
+        dev = next(self.parameters()).device
+        if ea.dtype != torch.float32 or ea.device != dev:
+            raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
+                            f"{ea.device} (train.batching.to_device casts integer bond features)")
+        return ea
+
     def _forward(self, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
@@ -163,9 +175,14 @@ class MPNN(nn.Module):
                 raise RuntimeError(f"engine='resident' requested but the model / batch does not qualify: {reason}")
         self.last_engine = "layered"
         x, edge_index, batch_vec = batch.x, batch.edge_index, batch.batch   # mpnn.py:50
+        edge_attr = self._edge_attr(batch) if any(getattr(c, "uses_edge_attr", False) for c in self.conv_layers) else None
+
+        def conv(i, x, **kw):                                               # edge-aware layers also take edge_attr
+            c = self.conv_layers[i]
+            return c(x, edge_index, edge_attr, **kw) if getattr(c, "uses_edge_attr", False) else c(x, edge_index, **kw)
         act_name = getattr(self.activation, "hscn_name", None)
         for i in range(self.num_layers - 1):
-            x = self.conv_layers[i](x, edge_index, act="relu")              # F.relu(conv(x)) in the epilogue
+            x = conv(i, x, act="relu")                                      # F.relu(conv(x)) in the epilogue
             if self.use_batch_norm:
                 x = self.bns[i](x)                                          # mpnn.py:53-54
             if self.use_layer_norm:
@@ -175,7 +192,7 @@ class MPNN(nn.Module):
                 x = self.activation(x)
             seed = None if self.dropout_seed is None else self.dropout_seed + i
             x = Fh.dropout(x, p=self.dropout, training=self.training, seed=seed)
-        x = self.conv_layers[-1](x, edge_index)
+        x = conv(self.num_layers - 1, x)
         if self.task_level != "graph":
             return x
         size = getattr(batch, "num_graphs", None)

@@ -59,6 +59,15 @@ class Linear(nn.Module):
                                     dtype=torch.float32)
             self.reset_parameters()
 
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        # as torch_geometric.nn.Linear: a weight that is not materialised yet is listed as it is (it cannot be detached)
+        if isinstance(self.weight, nn.parameter.UninitializedParameter):
+            destination[prefix + "weight"] = self.weight
+            if self.bias is not None:
+                destination[prefix + "bias"] = self.bias if keep_vars else self.bias.detach()
+            return
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+
     def forward(self, x: Tensor, act: str = "identity") -> Tensor:
         self.materialize(x.size(-1), x)
         return Fh.linear(x, self.weight, self.bias, act)
@@ -184,6 +193,81 @@ class GATConv(nn.Module):
             loops = self_loop_relation_of(rel.edge_index, n, both=both)
         return Fh.GATLoopFn.apply(x, self.lin_src.weight, self.att_src, self.att_dst, self.bias, rel, loops,
                                   self.negative_slope, ACT[act])
+
+
+class ReLU(nn.Module):
+    """``torch.nn.ReLU`` on the HIP path: the parameter-free middle module of GINE's ``Sequential``."""
+
+    def forward(self, x: Tensor) -> Tensor:
+        return Fh.ActFn.apply(x, ACT["relu"])
+
+
+class GINEConv(nn.Module):
+    """PyG GINEConv with ``edge_dim`` given: ``out = nn((1 + eps) x_i + sum_{k: dst_k = i} relu(x[src_k] +
+    lin(edge_attr[k])))``, every edge as given (loops and repeated edges count).  ``lin = Linear(edge_dim, F)`` with
+    bias, F being the input width of the first ``Linear`` found in ``nn`` as in PyG; ``edge_dim=-1`` is materialised
+    on first use.  ``state_dict`` keys are PyG's: ``nn.*``, ``lin.weight``, ``lin.bias``, ``eps`` (a buffer).  The
+    aggregate is one HIP launch (csrc/gine.hip), ``nn`` runs through its own modules.
+
+    Not provided, refused by name: ``train_eps=True``, ``edge_dim=None`` (PyG's form without ``lin``, which needs
+    edge features as wide as x) and a gradient for ``edge_attr``."""
+
+    def __init__(self, nn_module: nn.Module, eps: float = 0.0, train_eps: bool = False, edge_dim: Optional[int] = None):
+        super().__init__()
+        if train_eps:
+            raise NotImplementedError("GINEConv(train_eps=True): the gradient of eps is not computed; eps is a buffer")
+        if edge_dim is None:
+            raise NotImplementedError("GINEConv(edge_dim=None) adds raw edge features to x; pass edge_dim (or -1) so "
+                                      "that they go through lin = Linear(edge_dim, in_channels)")
+        self.nn = nn_module
+        self.initial_eps = float(eps)
+        self.register_buffer("eps", torch.tensor([float(eps)]))
+        first = next((m for m in nn_module.modules() if isinstance(m, (Linear, nn.Linear))), None)
+        if first is None:
+            raise ValueError("GINEConv: no Linear found in nn to take the input width from")
+        in_channels = first.in_channels if isinstance(first, Linear) else first.in_features
+        if in_channels <= 0:
+            raise ValueError("GINEConv: the first Linear of nn is lazily sized; lin needs its input width")
+        self.in_channels = int(in_channels)
+        self.lin = Linear(edge_dim, self.in_channels)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if prefix + "eps" in state_dict:          # the launches take eps as a host value: no read-back per call
+            self.initial_eps = float(state_dict[prefix + "eps"].reshape(-1)[0])
+
+    def aggregate(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Tensor) -> Tensor:
+        if not isinstance(x, Tensor):
+            raise TypeError("GINEConv takes one node feature tensor")
+        if edge_attr is None:
+            raise ValueError("GINEConv needs edge_attr [E, edge_dim]")
+        if edge_attr.dim() != 2:
+            raise ValueError(f"edge_attr must be [E, edge_dim], got {tuple(edge_attr.shape)}")
+        self.lin.materialize(edge_attr.size(-1), x)
+        n = x.size(0)
+        # only a gradient w.r.t. x walks the source-keyed CSR
+        rel = _relation(edge_index, n, n, both=torch.is_grad_enabled() and x.requires_grad)
+        return Fh.GINEAggregateFn.apply(x, edge_attr, self.lin.weight, self.lin.bias, rel, self.initial_eps)
+
+    def forward(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Tensor) -> Tensor:
+        return self.nn(self.aggregate(x, edge_index, edge_attr))
+
+
+class GINE(GINEConv):
+    """GraphGPS's GINE layer, constructible from ``(in, out)`` like the other registry entries: a ``GINEConv`` over
+    ``Sequential(Linear(in, out), ReLU, Linear(out, out))``.  ``act`` is applied in the last Linear's epilogue."""
+
+    uses_edge_attr = True
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int = -1, eps: float = 0.0):
+        super().__init__(nn.Sequential(Linear(in_channels, out_channels), ReLU(), Linear(out_channels, out_channels)),
+                         eps=eps, train_eps=False, edge_dim=edge_dim)
+        self.out_channels = int(out_channels)
+
+    def forward(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Tensor,
+                act: str = "identity") -> Tensor:
+        z = self.aggregate(x, edge_index, edge_attr)
+        return self.nn[2](self.nn[0](z, act="relu"), act=act)     # the middle ReLU in the first Linear's epilogue
 
 
 class HeteroConv(nn.Module):

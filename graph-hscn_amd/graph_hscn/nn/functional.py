@@ -369,6 +369,79 @@ class GATLoopFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# GINEConv's aggregate: z_i = (1 + eps) x_i + sum_{k: dst_k = i} relu(x[src_k] + lin(edge_attr[k]))
+# --------------------------------------------------------------------------- #
+# csrc/gine.hip: a row of more than GINE_LONG_ROW slots (of either CSR: in-degree in the forward, out-degree in the
+# backward's source walk) is summed by a whole workgroup in chunks of GINE_CHUNK slots; both are the library's
+# constants (hscn_gine_long_row / hscn_gine_chunk, pinned equal in tests/test_edge_features_host.py).
+GINE_LONG_ROW = 256
+GINE_CHUNK = 64
+GINE_MAX_WIDTH = 512
+GINE_MAX_EDGE_DIM = 64
+
+
+class GINEAggregateFn(Function):
+    """(x [N, F], edge_attr [E, De], W [F, De], bias [F]) -> z [N, F] over ``rel`` (row k of ``edge_attr`` belongs to
+    edge k of ``rel.edge_index``).  Forward: one launch; nothing but the inputs is kept.  Backward: the gates are
+    recomputed; ``gx`` walks the source-keyed CSR and is computed only when ``x`` needs it; the gradients of ``W`` and
+    ``bias`` go through gm [E, F] (plain stores) and the ordered ``hscn_linear_bwd_w``.  A gradient for ``edge_attr``
+    does not exist and is refused, not returned as None."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, edge_attr: Tensor, W: Tensor, bias: Tensor, rel: Relation, eps: float):
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError(
+                "GINEConv: edge_attr requires a gradient (a trainable edge encoder in front of lin), which the "
+                "operator does not compute: d edge_attr[k] = lin.weight^T (gate_k * gz[dst_k]) is not implemented")
+        x, edge_attr, W, bias = _c(x), _c(edge_attr), _c(W), _c(bias)
+        N, F = x.shape
+        De = W.shape[1]
+        if not _hip.lib().hscn_gine_supported(F, De):
+            raise ValueError(f"GINEConv: width F={F}, edge_dim De={De} outside the kernel's envelope "
+                             f"(1 <= F <= {GINE_MAX_WIDTH}, 1 <= De <= {GINE_MAX_EDGE_DIM})")
+        if rel.num_src != N or rel.num_dst != N:
+            raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, x has {N} rows")
+        if edge_attr.dim() != 2 or edge_attr.size(0) != rel.num_edges or edge_attr.size(1) != De:
+            raise ValueError(f"edge_attr is {tuple(edge_attr.shape)}; the relation has {rel.num_edges} edges and "
+                             f"lin takes {De} edge features")
+        if W.shape[0] != F or bias.shape != (F,):
+            raise ValueError(f"lin maps to {W.shape[0]} columns, x has {F}")
+        E = rel.num_edges
+        csr = rel.csr
+        z = torch.empty(N, F, dtype=torch.float32, device=x.device)
+        call("hscn_gine_aggregate_fwd", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(x),
+             ptr(edge_attr) if E else None, ptr(W), ptr(bias), float(eps), ptr(z), N, E, F, De, ptr(csr.flag), stream())
+        ctx.rel, ctx.eps = rel, float(eps)
+        ctx.save_for_backward(x, edge_attr, W, bias)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz: Tensor):
+        x, edge_attr, W, bias = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        gz = _c(gz)
+        N, F = x.shape
+        De, E = W.shape[1], rel.num_edges
+        ea = ptr(edge_attr) if E else None
+        gx = gW = gb = None
+        if ctx.needs_input_grad[0]:
+            t = rel.csr_t
+            gx = torch.empty_like(x)
+            call("hscn_gine_aggregate_bwd_x", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(x), ea, ptr(W), ptr(bias),
+                 ctx.eps, ptr(gz), ptr(gx), N, E, F, De, ptr(rel.csr.flag), stream())
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            if E:
+                gm = torch.empty(E, F, dtype=torch.float32, device=x.device)
+                call("hscn_gine_aggregate_bwd_msg", ptr(rel.edge_index.contiguous()), ptr(x), ea, ptr(W), ptr(bias),
+                     ptr(gz), ptr(gm), N, E, F, De, ptr(rel.csr.flag), stream())
+                gW, gb = linear_bwd_w_raw(gm, edge_attr, ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+            else:                                   # no edge reaches lin: exact zeros, not None
+                gW = torch.zeros_like(W) if ctx.needs_input_grad[2] else None
+                gb = torch.zeros_like(bias) if ctx.needs_input_grad[3] else None
+        return gx, None, gW, gb, None, None
+
+
+# --------------------------------------------------------------------------- #
 # global_mean_pool
 # --------------------------------------------------------------------------- #
 class SegmentMeanFn(Function):

@@ -104,6 +104,9 @@ def to_device(model, batch, device):
     batch = batch.to(device)
     if not is_hetero(model):
         batch.x = batch.x.float()
+        edge_attr = getattr(batch, "edge_attr", None)
+        if edge_attr is not None:                   # OGB bond features are integers
+            batch.edge_attr = edge_attr.float()
     return batch
 
 

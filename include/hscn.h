@@ -1339,6 +1339,43 @@ int hscn_rwse_tile(void);
 int hscn_rwse_stats(const int32_t* rowptr, const int32_t* col, const int32_t* nptr, int64_t N, int64_t B, int max_n,
                     int ksteps, float* rw /*[N, ksteps]*/, int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * GINEConv's aggregate with edge features (PyG GINEConv with edge_dim; csrc/gine.hip).  Purely additive to ABI 23.
+ *
+ *   t_k = bias + W e_k                     e_k = edge_attr[k] (row k belongs to edge k of the edge list),  W [F, De]
+ *   z_i = (1 + eps) x_i + sum_{k: dst_k = i} relu(x[src_k] + t_k)        every listed edge counts (loops, repeats)
+ *
+ * hscn_gine_aggregate_fwd: ONE launch, z [N, F] from the target-keyed stable CSR (hscn_csr_build(dst, src), or
+ *   hscn_csr_build_pair's rowptr / col / eid): slot p of row i gathers x[col[p]] and the edge-feature row
+ *   edge_attr[eid[p]].  t_k is evaluated inside the gather; no [E, F] buffer is written.  Sums run in CSR slot order
+ *   with separately rounded multiply and add.  Rows of more than hscn_gine_long_row() slots are summed by a whole
+ *   workgroup in chunks of hscn_gine_chunk() slots, the chunk partials added in chunk order: the same input gives the
+ *   same bits.
+ * hscn_gine_aggregate_bwd_x: gx_j = (1 + eps) gz_j + sum_{k: src_k = j} [x_j + t_k > 0] gz[dst_k], ONE launch over the
+ *   source-keyed CSR (rowptr_t / col_t / eid_t); the gates are recomputed, nothing is kept by the forward.
+ * hscn_gine_aggregate_bwd_msg: gm [E, F], gm_k = [x[src_k] + t_k > 0] gz[dst_k] in edge order (edge_index int64
+ *   [2, E]), written once with plain stores.  d W = hscn_linear_bwd_w(gm, edge_attr), d bias its gb: ordered, no
+ *   float atomics.  An edge with a node id outside [0, N) gives a zero row and flag bit 0.
+ *   flag [1] i32, only ever OR-ed into (the CSR build's flag word serves): bit 0 as above, bit 1 = a CSR column
+ *   outside [0, N) or an eid outside [0, E) (the slot adds nothing; hscn_csr_build never produces one).
+ *   HSCN_E_BADARG for null pointers (col / eid / edge_attr may be NULL when E == 0) and negative sizes;
+ *   HSCN_E_UNSUPPORTED where hscn_gine_supported is 0 (F outside [1, 512] or De outside [1, 64]); both before any
+ *   launch.  N = 0 launches nothing.  No workspace, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_gine_supported(int F, int De);
+int hscn_gine_long_row(void);
+int hscn_gine_chunk(void);
+int hscn_gine_aggregate_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* x,
+                            const float* edge_attr, const float* W, const float* bias, float eps, float* z /*[N, F]*/,
+                            int64_t N, int64_t E, int F, int De, int32_t* flag /*[1]*/, void* stream);
+int hscn_gine_aggregate_bwd_x(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const float* x,
+                              const float* edge_attr, const float* W, const float* bias, float eps, const float* gz,
+                              float* gx /*[N, F]*/, int64_t N, int64_t E, int F, int De, int32_t* flag /*[1]*/,
+                              void* stream);
+int hscn_gine_aggregate_bwd_msg(const int64_t* edge_index, const float* x, const float* edge_attr, const float* W,
+                                const float* bias, const float* gz, float* gm /*[E, F]*/, int64_t N, int64_t E, int F,
+                                int De, int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
