@@ -198,6 +198,13 @@ _SIGNATURES = {
     "hscn_gine_aggregate_fwd": (c_int, [P, P, P, P, P, P, P, c_float, P, c_int64, c_int64, c_int, c_int, P, P]),
     "hscn_gine_aggregate_bwd_x": (c_int, [P, P, P, P, P, P, P, c_float, P, P, c_int64, c_int64, c_int, c_int, P, P]),
     "hscn_gine_aggregate_bwd_msg": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int, P, P]),
+    # global attention: block-diagonal multi-head self-attention (csrc/attention.hip; additive to ABI 24)
+    "hscn_attention_supported": (c_int, [c_int, c_int]),
+    "hscn_attention_tile": (c_int, []),
+    "hscn_attention_chunk": (c_int, []),
+    "hscn_attention_fwd": (c_int, [P, P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
+    "hscn_attention_bwd_q": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
+    "hscn_attention_bwd_kv": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, P, P, P]),
 }
 
 

@@ -93,6 +93,45 @@ class MPNNConfig:  # config.py:49-73
                 raise ValueError(f"{v} must be non-negative.")
 
 
+GPS_NORMS = ("layer", "batch", None)
+
+
+@dataclass
+class GPSConfig:
+    """The GPS model (extension; model/gps.py): ``num_layers`` GPS layers of width ``hidden_channels`` -- a local
+    convolution ``local_conv_type`` ("gcn", "gat", "gine" of CONV_DICT, or None: the plain Transformer layer) beside
+    per-graph self-attention of ``num_heads`` heads, then a feed-forward block -- behind a Linear node encoder.  The
+    head width ``hidden_channels / num_heads`` must be a multiple of 4 in [4, 64] and ``hidden_channels`` at most 512
+    (the attention kernel's envelope, csrc/attention.hip)."""
+    activation: str
+    local_conv_type: Optional[str] = "gine"
+    hidden_channels: int = HIDDEN_CHANNELS
+    num_layers: int = NUM_LAYERS
+    num_heads: int = 4
+    dropout: float = DROPOUT
+    norm: Optional[str] = "layer"
+    task_level: str = "graph"
+
+    def __post_init__(self):
+        if self.task_level not in TASK_LEVELS:
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        if self.dropout and not (0.0 <= self.dropout < 1.0):
+            raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
+        for v in (self.num_layers, self.hidden_channels, self.num_heads):
+            if v < 1:
+                raise ValueError(f"{v} must be positive.")
+        if self.local_conv_type is not None and self.local_conv_type.lower() not in CONV_DICT:
+            raise ValueError(f"local_conv_type must be one of {sorted(CONV_DICT)} or None, got {self.local_conv_type!r}")
+        if self.norm not in GPS_NORMS:
+            raise ValueError(f"norm must be 'layer', 'batch' or None, got {self.norm!r}")
+        if self.hidden_channels % self.num_heads:
+            raise ValueError(f"hidden_channels {self.hidden_channels} must be divisible by num_heads {self.num_heads}.")
+        dh = self.hidden_channels // self.num_heads
+        if dh % 4 or not 4 <= dh <= 64 or self.hidden_channels > 512:
+            raise ValueError(f"head width {dh} (hidden_channels / num_heads) must be a multiple of 4 in [4, 64] and "
+                             f"hidden_channels at most 512.")
+
+
 @dataclass
 class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent there)
     activation: str
@@ -196,6 +235,7 @@ class RWSEConfig:
 
 @dataclass
 class TrainingConfig:  # config.py:133-152
+    # "hscn" / "mpnn" (the reference's two: HSCNConfig / MPNNConfig) or "gps" (extension: GPSConfig, model/gps.py)
     model_type: str
     loss_fn: str
     # "ap" / "mae" (the reference's two), "accuracy" / "f1_macro" for class-index targets, or "mrr" / "hits@1" /

@@ -1,0 +1,133 @@
+"""The GPS model (extension; the reference has no global attention): ``Linear(F -> D)`` node encoder, ``num_layers``
+``nn.gps.GPSLayer`` s -- a local convolution beside per-graph multi-head self-attention -- and a head per task level:
+
+  * "graph": ``global_mean_pool -> Linear(D, D) -> activation -> Linear(D, C)`` (HSCN's head shape);
+  * "node":  the same two Linears per node, through ``nn.head.NodeHead`` where its kernels apply;
+  * "link":  ``embed()`` is the [N, C] output of the two Linears and ``forward`` scores ``batch.edge_label_index`` by
+    ``nn.head.pair_dot``, exactly as ``MPNN`` does.
+
+``local_conv=None`` is the plain Transformer (with a positional encoding in front: LRGB's "Transformer + LapPE").
+The model takes a homogeneous ``Batch`` and offers the surface ``train.batching`` and ``train.train`` use for one.  It
+runs on the layered operators only: there is no one-launch or captured form of global attention."""
+from __future__ import annotations
+
+from typing import Callable, Optional
+
+import torch
+import torch.nn as nn
+from torch import Tensor
+
+from ..config.config import ACT_DICT, GPSConfig
+from ..nn import functional as Fh
+from ..nn.conv import Linear
+from ..nn.gps import GPSLayer
+from ..nn.head import NodeHead
+from ..nn.pool import global_mean_pool
+
+RESIDENT_REASON = ("global attention (model/gps.py GPS): per-graph multi-head self-attention has no one-launch, "
+                   "resident or captured form; the model runs on the layered operators")
+
+
+class GPS(nn.Module):
+    layered_only = True      # train.batching.refuse_layered_only: the resident entry points refuse this model by name
+
+    def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
+                 local_conv: Optional[str] = "gine", activation: Optional[Callable] = None, dropout: float = 0.0,
+                 norm: Optional[str] = "layer", task_level: str = "graph") -> None:
+        super().__init__()
+        if task_level not in ("graph", "node", "link"):
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
+        if num_layers < 1:
+            raise ValueError("GPS needs at least one layer")
+        activation = ACT_DICT["relu"] if activation is None else activation
+        act = getattr(activation, "hscn_name", None)
+        if act is None:
+            raise ValueError("activation must be one of config.ACT_DICT's (it runs in a Linear's epilogue)")
+        self.task_level = task_level
+        self.num_layers = int(num_layers)
+        self.activation = activation
+        self.dropout = float(dropout)
+        self.dropout_seed: Optional[int] = None     # tests pin the masks (layer i draws with seeds + 4 i .. + 4 i + 3)
+        D = int(hidden_channels)
+        self.node_encoder = Linear(num_features, D)
+        self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act) for _ in range(num_layers))
+        self.lin_1 = Linear(D, D)
+        self.lin_2 = Linear(D, num_classes)
+        self._node_head = NodeHead(self.lin_1, self.lin_2, act)
+        # "layered"; "auto" runs layered too; "resident" raises with the reason when the model is called
+        self.engine = "layered"
+        self.last_engine: Optional[str] = None
+
+    # ---- the surface of a homogeneous model (train.batching, train.train) ----------------------------------------
+    def resident_reason(self, batch=None, need_grad: bool = False) -> str:
+        return RESIDENT_REASON
+
+    def supported(self, batch=None) -> bool:
+        return False
+
+    def head_width(self) -> int:
+        """Columns of the prediction (what ``batching.score_width`` asks for class-index targets)."""
+        return int(self.lin_2.out_channels)
+
+    def check_flags(self) -> None:
+        """Synchronising: raises if an attention launch since the last check met a graph larger than its batch's
+        ``max_nodes`` (``nn.functional.check_attention``).  ``train.train_epoch`` / ``eval_epoch`` call it once per
+        epoch, beside the read of the epoch's loss."""
+        Fh.check_attention(next(self.parameters()).device)
+
+    # ---- forward -----------------------------------------------------------------------------------------------
+    def _edge_attr(self, batch) -> Tensor:
+        """``batch.edge_attr`` for ``local_conv='gine'``: float32 [E, De] on the model's device (``MPNN._edge_attr``)."""
+        ea = getattr(batch, "edge_attr", None)
+        if ea is None:
+            raise ValueError("the model has edge-aware convolutions (local_conv 'gine') and the batch carries no "
+                             "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
+        dev = next(self.parameters()).device
+        if ea.dtype != torch.float32 or ea.device != dev:
+            raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
+                            f"{ea.device} (train.batching.to_device casts integer bond features)")
+        return ea
+
+    def _nodes(self, batch) -> Tensor:
+        """[N, D] after the last GPS layer."""
+        if self.engine not in ("layered", "auto", "resident"):
+            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if self.engine == "resident":
+            raise RuntimeError(f"engine='resident' does not take this model: {RESIDENT_REASON}")
+        self.last_engine = "layered"
+        edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
+        x = self.node_encoder(batch.x)
+        for i, layer in enumerate(self.layers):
+            layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
+            x = layer(x, batch.edge_index, batch, edge_attr)
+        return x
+
+    def _head(self, x: Tensor) -> Tensor:
+        h = Fh.linear_wide(x, self.lin_1.weight, self.lin_1.bias, self.activation.hscn_name)
+        return Fh.linear_wide(h, self.lin_2.weight, self.lin_2.bias)
+
+    def _forward(self, batch) -> Tensor:
+        x = self._nodes(batch)
+        if self.task_level == "graph":
+            x = global_mean_pool(x, batch.batch, getattr(batch, "num_graphs", None))
+            return self._head(x)
+        return self._node_head(x) if self._node_head.supported() else self._head(x)
+
+    def forward(self, batch) -> Tensor:
+        out = self._forward(batch)
+        if self.task_level == "link":
+            from ..nn.head import PairStructure, pair_dot
+            return pair_dot(out, batch.edge_label_index, PairStructure.of(batch, out.size(0)))
+        return out
+
+    def embed(self, batch) -> Tensor:
+        """The [N, C] node embeddings a link-level model scores pairs with."""
+        if self.task_level != "link":
+            raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
+        return self._forward(batch)
+
+
+def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:
+    return GPS(num_features, model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.num_heads,
+               model_cfg.local_conv_type, ACT_DICT[model_cfg.activation.lower()], model_cfg.dropout, model_cfg.norm,
+               model_cfg.task_level)

@@ -1,0 +1,106 @@
+"""Global attention: ``MultiheadSelfAttention`` is ``torch.nn.MultiheadAttention`` restricted to self-attention among
+the nodes of each graph of a collated batch, on the HIP path (csrc/attention.hip): no padding, no mask tensor.
+
+Parameters, their shapes, ``state_dict`` keys and the initialisation are torch's (``in_proj_weight`` [3D, D] xavier
+uniform, ``in_proj_bias`` and ``out_proj.bias`` zero, ``out_proj.weight`` kaiming uniform with a = sqrt 5), so weights
+move both ways with ``load_state_dict``.  Both projections run through the HIP ``linear`` (``linear_wide``: in column
+chunks where the weight is wider than the kernel's LDS image); the attention itself is
+``nn.functional.SelfAttentionFn``."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+import torch.nn as nn
+from torch import Tensor
+
+from . import functional as Fh
+
+
+class _OutProj(nn.Module):
+    """``out_proj`` of torch's module (a ``NonDynamicallyQuantizableLinear``): ``weight`` [D, D] and ``bias`` [D]."""
+
+    def __init__(self, embed_dim: int, bias: bool):
+        super().__init__()
+        self.in_features = self.out_features = embed_dim
+        self.weight = nn.Parameter(torch.empty(embed_dim, embed_dim))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(embed_dim))
+        else:
+            self.register_parameter("bias", None)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return Fh.linear_wide(x, self.weight, self.bias)
+
+
+class MultiheadSelfAttention(nn.Module):
+    """``forward(x, batch)``: x [N, D] float32 on the device, ``batch`` a ``graph_hscn.data.Batch`` (its ``ptr32`` and
+    ``max_nodes`` say which rows form a graph) -> [N, D].  ``forward(x, ptr32=..., max_nodes=...)`` takes the two
+    directly.
+
+    Not provided, refused by name: dropout on the attention weights, ``need_weights``, an attention bias or any mask
+    other than the graph boundary, an ``embed_dim`` that ``num_heads`` does not divide, a head width outside the
+    kernel's envelope, CPU tensors."""
+
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, dropout: float = 0.0):
+        super().__init__()
+        if embed_dim <= 0 or num_heads <= 0:
+            raise ValueError(f"embed_dim and num_heads must be greater than 0, got embed_dim={embed_dim} and "
+                             f"num_heads={num_heads} instead")
+        if embed_dim % num_heads != 0:
+            raise ValueError(f"embed_dim must be divisible by num_heads (got embed_dim={embed_dim}, "
+                             f"num_heads={num_heads})")
+        if dropout != 0.0:
+            raise NotImplementedError("MultiheadSelfAttention(dropout > 0): dropout on the attention weights is not "
+                                      "implemented (the weights never exist in memory); drop the layer's output instead")
+        head_dim = embed_dim // num_heads
+        if not (head_dim % 4 == 0 and Fh.ATTN_MIN_HEAD_DIM <= head_dim <= Fh.ATTN_MAX_HEAD_DIM
+                and embed_dim <= Fh.ATTN_MAX_WIDTH):
+            raise ValueError(f"MultiheadSelfAttention: embed_dim={embed_dim} with num_heads={num_heads} (head width "
+                             f"{head_dim}) is outside the kernel's envelope ({Fh.ATTN_ENVELOPE})")
+        self.embed_dim, self.num_heads, self.head_dim = int(embed_dim), int(num_heads), int(head_dim)
+        self.dropout = 0.0
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        if bias:
+            self.in_proj_bias = nn.Parameter(torch.empty(3 * embed_dim))
+        else:
+            self.register_parameter("in_proj_bias", None)
+        self.out_proj = _OutProj(embed_dim, bias)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        """torch's scheme in torch's order of draws (out_proj is built as a Linear first, then
+        ``MultiheadAttention._reset_parameters``): the same generator state gives the same weights."""
+        nn.init.kaiming_uniform_(self.out_proj.weight, a=math.sqrt(5))
+        if self.out_proj.bias is not None:
+            bound = 1.0 / math.sqrt(self.embed_dim)
+            nn.init.uniform_(self.out_proj.bias, -bound, bound)          # (Linear's draw; zeroed below, as torch does)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        if self.in_proj_bias is not None:
+            nn.init.constant_(self.in_proj_bias, 0.0)
+            nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def forward(self, x: Tensor, batch=None, *, ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None,
+                need_weights: bool = False, attn_mask=None, key_padding_mask=None, attn_bias=None) -> Tensor:
+        if need_weights:
+            raise NotImplementedError("MultiheadSelfAttention(need_weights=True): the attention weights are streamed "
+                                      "through LDS and never exist in memory")
+        for name, v in (("attn_mask", attn_mask), ("key_padding_mask", key_padding_mask), ("attn_bias", attn_bias)):
+            if v is not None:
+                raise NotImplementedError(f"MultiheadSelfAttention({name}=...): the only mask is the graph boundary "
+                                          "(ptr32); attention bias and other masks are not implemented")
+        if batch is not None:
+            if ptr32 is not None or max_nodes is not None:
+                raise ValueError("pass a Batch, or ptr32 and max_nodes, not both")
+            for attr in ("ptr32", "max_nodes"):
+                if not hasattr(batch, attr):
+                    raise ValueError(f"the batch carries no {attr} (graph_hscn.data.Batch.from_data_list builds it)")
+            ptr32, max_nodes = batch.ptr32, batch.max_nodes
+        if ptr32 is None or max_nodes is None:
+            raise ValueError("MultiheadSelfAttention needs the graph boundaries: a Batch, or ptr32 and max_nodes")
+        if x.dim() != 2 or x.size(1) != self.embed_dim:
+            raise ValueError(f"x must be [N, {self.embed_dim}], got {tuple(x.shape)}")
+        qkv = Fh.linear_wide(x, self.in_proj_weight, self.in_proj_bias)
+        out = Fh.SelfAttentionFn.apply(qkv, ptr32, int(max_nodes), self.num_heads)
+        return self.out_proj(out)

@@ -182,6 +182,25 @@ def linear(x: Tensor, W: Tensor, bias: Optional[Tensor] = None, act: str = "iden
     return y.view(*lead, W.shape[0])
 
 
+# hscn_linear_fwd keeps the whole [O, I] weight in LDS and answers HSCN_E_UNSUPPORTED above 160 KB (csrc/linear.hip:
+# `lds > 160 * 1024`); tests/test_attention_host.py pins the two values to each other through the library's answer
+LINEAR_MAX_WEIGHT_BYTES = 160 * 1024
+
+
+def linear_wide(x: Tensor, W: Tensor, bias: Optional[Tensor] = None, act: str = "identity") -> Tensor:
+    """``linear`` for a weight beyond the kernel's LDS-resident image (in * out * 4 bytes > 160 KB, e.g. the packed
+    [3D, D] attention projection from D = 117): the output columns are computed in chunks of whole weight rows, one
+    ``linear`` each (the activation is element-wise, so it stays in the epilogue), and concatenated."""
+    O, I = W.shape
+    if I * O * 4 <= LINEAR_MAX_WEIGHT_BYTES:
+        return linear(x, W, bias, act)
+    step = (LINEAR_MAX_WEIGHT_BYTES // (4 * I)) // 4 * 4
+    if step < 4:
+        raise ValueError(f"linear: {I} input columns are beyond the kernel's envelope")
+    parts = [linear(x, W[o:o + step], None if bias is None else bias[o:o + step], act) for o in range(0, O, step)]
+    return torch.cat(parts, -1)
+
+
 # --------------------------------------------------------------------------- #
 # GCNConv (unit weights, add_self_loops=False)
 # --------------------------------------------------------------------------- #
@@ -439,6 +458,92 @@ class GINEAggregateFn(Function):
                 gW = torch.zeros_like(W) if ctx.needs_input_grad[2] else None
                 gb = torch.zeros_like(bias) if ctx.needs_input_grad[3] else None
         return gx, None, gW, gb, None, None
+
+
+# --------------------------------------------------------------------------- #
+# Global attention: block-diagonal multi-head self-attention over a batch (csrc/attention.hip)
+# --------------------------------------------------------------------------- #
+ATTN_MIN_HEAD_DIM = 4
+ATTN_MAX_HEAD_DIM = 64
+ATTN_MAX_WIDTH = 512
+ATTN_GRAPH_TOO_LARGE = 4          # flag bit 2: a graph with more than max_nodes nodes (its rows are NaN)
+ATTN_ENVELOPE = (f"head width embed_dim / num_heads a multiple of 4 in [{ATTN_MIN_HEAD_DIM}, {ATTN_MAX_HEAD_DIM}], "
+                 f"num_heads >= 1, embed_dim <= {ATTN_MAX_WIDTH}")
+
+_ATTN_FLAGS = {}
+
+
+def attention_supported(heads: int, head_dim: int) -> bool:
+    return bool(_hip.lib().hscn_attention_supported(int(heads), int(head_dim)))
+
+
+def attention_flags(device) -> Tensor:
+    """The device's flag word [1] int32 that every attention launch ORs into; ``check_attention`` reads and clears it."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    t = _ATTN_FLAGS.get(device)
+    if t is None:
+        t = _ATTN_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def check_attention(device) -> None:
+    """Synchronising: ``ValueError`` if an attention launch since the last check met a graph larger than the
+    ``max_nodes`` it was given (that graph's rows are NaN)."""
+    word = attention_flags(device)
+    f = int(word.item())
+    if f:
+        word.zero_()
+    if f & ATTN_GRAPH_TOO_LARGE:
+        raise ValueError("self-attention: a graph has more nodes than the batch's max_nodes says; its rows are NaN")
+
+
+class SelfAttentionFn(Function):
+    """(qkv [N, 3D], ptr32 [B + 1] int32, max_nodes, heads) -> out [N, D]: every node attends to the nodes of its own
+    graph.  Forward: one launch; ``qkv``, ``out`` and the rows' log-sum-exp are kept.  Backward: two launches (the Q
+    third of ``g_qkv`` keyed by query, the K and V thirds keyed by key), only when ``qkv`` needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv: Tensor, ptr32: Tensor, max_nodes: int, heads: int):
+        qkv = _c(qkv)
+        if qkv.dim() != 2 or qkv.size(1) % (3 * heads) != 0:
+            raise ValueError(f"qkv must be [N, 3 * heads * head_dim], got {tuple(qkv.shape)} for {heads} heads")
+        N, D = qkv.size(0), qkv.size(1) // 3
+        dh = D // heads
+        if not attention_supported(heads, dh):
+            raise ValueError(f"self-attention: {heads} heads of width {dh} are outside the kernel's envelope "
+                             f"({ATTN_ENVELOPE})")
+        if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
+            raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
+        if ptr32.device != qkv.device:
+            raise RuntimeError(f"ptr32 is on {ptr32.device}, qkv on {qkv.device}: move the batch to the device once "
+                               "(Batch.to); the operator does not copy it on every call")
+        B = ptr32.numel() - 1
+        out = torch.empty(N, D, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(N, heads, dtype=torch.float32, device=qkv.device)
+        flag = attention_flags(qkv.device) if qkv.is_cuda else None
+        call("hscn_attention_fwd", ptr(qkv), ptr(ptr32), N, B, int(max_nodes), heads, dh, ptr(out), ptr(lse),
+             ptr(flag), stream())
+        ctx.dims = (N, B, int(max_nodes), heads, dh)
+        ctx.save_for_backward(qkv, ptr32, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out: Tensor):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        qkv, ptr32, out, lse = ctx.saved_tensors
+        N, B, max_nodes, heads, dh = ctx.dims
+        g_out = _c(g_out)
+        g_qkv = torch.empty_like(qkv)
+        delta = torch.empty_like(lse)
+        flag = attention_flags(qkv.device)
+        call("hscn_attention_bwd_q", ptr(qkv), ptr(out), ptr(lse), ptr(g_out), ptr(ptr32), N, B, max_nodes, heads, dh,
+             ptr(g_qkv), ptr(delta), ptr(flag), stream())
+        call("hscn_attention_bwd_kv", ptr(qkv), ptr(lse), ptr(delta), ptr(g_out), ptr(ptr32), N, B, max_nodes, heads,
+             dh, ptr(g_qkv), ptr(flag), stream())
+        return g_qkv, None, None, None
 
 
 # --------------------------------------------------------------------------- #

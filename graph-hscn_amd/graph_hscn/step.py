@@ -552,6 +552,8 @@ class MPNNResidentTrainStep(_FlatGradStep):
     def __init__(self, model, batch, loss_fn: str, target: Optional[Tensor] = None, accumulate: bool = False,
                  seed0: Optional[int] = None, step_word: Optional[Tensor] = None):
         from .model.mpnn import MPNN
+        from .train import batching
+        batching.refuse_layered_only(model, "the one-launch MPNN step")
         if not isinstance(model, MPNN):
             raise TypeError("MPNNResidentTrainStep drives graph_hscn.model.mpnn.MPNN")
         reason = model.resident_reason(batch)

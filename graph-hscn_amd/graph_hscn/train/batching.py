@@ -37,6 +37,8 @@ def score_width(model, y: Tensor) -> int:
     indices the width of the model's head (HSCN: ``lin_2``; a node-level MPNN: its last convolution)."""
     if not class_index_targets(y):
         return int(y.size(1))
+    if not is_hetero(model) and hasattr(model, "head_width"):        # (model/gps.py GPS: no resident_dims)
+        return int(model.head_width())
     if not is_hetero(model) and node_level(model):
         return int(model.resident_dims()[2])
     if not is_hetero(model):
@@ -52,6 +54,12 @@ def refuse_node_level(model, what: str) -> None:
     """The one-launch and captured steps, ``fit_resident`` and ``DeviceEvaluator`` end in the per-graph pool: they
     refuse a node-level model by name, before anything is launched or captured -- they never pool silently."""
     if node_level(model):
+        raise RuntimeError(f"{what} does not take this model: {model.resident_reason()} (train.train runs it)")
+
+
+def refuse_layered_only(model, what: str) -> None:
+    """The same for a model that has no resident form at all (``layered_only``: model/gps.py GPS, global attention)."""
+    if getattr(model, "layered_only", False):
         raise RuntimeError(f"{what} does not take this model: {model.resident_reason()} (train.train runs it)")
 
 
@@ -126,6 +134,7 @@ def resident_step(model, batch, loss_fn: str, one_launch: Optional[bool] = None,
     """The resident training step of ``model`` on a static batch (``step.ResidentTrainStep``; the MPNN baseline's or
     the vl model's one launch, which have neither a launch pair nor a structure to load)."""
     from ..step import MPNNResidentTrainStep, ResidentTrainStep, VLResidentTrainStep
+    refuse_layered_only(model, "the resident training step")
     refuse_node_level(model, "the resident training step")
     refuse_link_level(model, "the resident training step")
     if targets(model, batch) is None:

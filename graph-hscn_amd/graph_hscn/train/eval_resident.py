@@ -48,6 +48,7 @@ class DeviceEvaluator:
     def __init__(self, graphs: Sequence, model, loss_fn: str, batch_size: int, metric: Optional[str] = None):
         if metric not in METRICS + (None,):
             raise ValueError(f"metric must be one of {METRICS} or None, got {metric!r}")
+        batching.refuse_layered_only(model, "DeviceEvaluator")
         batching.refuse_node_level(model, "DeviceEvaluator")
         batching.refuse_link_level(model, "DeviceEvaluator")
         dev = next(model.parameters()).device

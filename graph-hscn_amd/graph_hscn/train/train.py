@@ -204,6 +204,8 @@ def train_epoch(epoch, logger, loader, model, optimizer, loss_fn: str, metric_fn
             optimizer.step()
             optimizer.zero_grad()
     mean_loss = float(torch.stack(losses).mean().item())
+    if hasattr(model, "check_flags"):              # (model/gps.py GPS: the attention launches' flag word)
+        model.check_flags()
     if ranks is not None:
         perf = _link_result(ranks, rank_name, device)
     else:
@@ -229,6 +231,8 @@ def eval_epoch(epoch, logger, loader, model, loss_fn: str, metric_fn: Optional[C
             y_pred.append(score)
         losses.append(loss)
     mean_loss = float(torch.stack(losses).mean().item())
+    if hasattr(model, "check_flags"):              # (model/gps.py GPS: the attention launches' flag word)
+        model.check_flags()
     if ranks is not None:
         perf = _link_result(ranks, rank_name, device)
     else:

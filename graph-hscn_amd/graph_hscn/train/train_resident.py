@@ -159,6 +159,7 @@ def fit_resident(logger, optim_cfg, training_cfg, train_graphs: Sequence, eval_l
         raise ValueError(f"metric must be one of {_metrics.METRICS} or None, got {metric!r}")
     if eval_graphs is not None and len(eval_graphs) != 2:
         raise ValueError("eval_graphs is the pair (validation graphs, test graphs)")
+    batching.refuse_layered_only(model, "fit_resident")
     batching.refuse_node_level(model, "fit_resident")
     batching.refuse_link_level(model, "fit_resident")
     dev = next(model.parameters()).device

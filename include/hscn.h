@@ -1376,6 +1376,45 @@ int hscn_gine_aggregate_bwd_msg(const int64_t* edge_index, const float* x, const
                                 const float* bias, const float* gz, float* gm /*[E, F]*/, int64_t N, int64_t E, int F,
                                 int De, int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Global attention: block-diagonal multi-head self-attention over a collated batch (csrc/attention.hip), the global
+ * half of a GPS layer.  Purely additive to ABI 24.
+ *
+ *   qkv [N, 3D] f32 row-major, the packed input projection: Q = columns [0, D), K = [D, 2D), V = [2D, 3D); head h owns
+ *   columns [h dh, (h + 1) dh) of each third (torch.nn.MultiheadAttention's layout); D = heads * dh; scale = dh^-1/2.
+ *   Node i of graph g attends to the nodes [ptr32[g], ptr32[g + 1]) of its graph, itself included:
+ *     out_i = sum_j p_ij v_j,   p_ij = exp(scale <q_i, k_j> - lse_i),   lse_i = log sum_j exp(scale <q_i, k_j>)
+ *
+ * hscn_attention_fwd: ONE launch; out [N, D], lse [N, heads].  A workgroup takes hscn_attention_tile() query rows of
+ *   one (graph, head) and streams the graph's keys and values through LDS in chunks of hscn_attention_chunk() keys with
+ *   an online softmax.  Nothing padded is ever written: memory is O(N D), and a graph may have any number of nodes.
+ *   A row depends on its own graph's rows only, in key and chunk order from the graph's first node: the same bits
+ *   wherever the graph stands in the batch.  A graph of one node gives out = v and lse = s_00 exactly.
+ * hscn_attention_bwd_q: ONE launch, query-keyed; recomputes p from lse.  Writes delta [N, heads], delta_i =
+ *   sum_d g_out_id out_id, and the Q third of g_qkv [N, 3D]: gQ_i = scale sum_j p_ij (<g_out_i, v_j> - delta_i) k_j.
+ * hscn_attention_bwd_kv: ONE launch, key-keyed, after hscn_attention_bwd_q (it reads delta).  Writes the K and V thirds
+ *   of g_qkv: gV_j = sum_i p_ij g_out_i, gK_j = scale sum_i p_ij (<g_out_i, v_j> - delta_i) q_i, i in row order.
+ *   g_qkv is written once with plain stores, no float atomics; it feeds hscn_linear_bwd_w and the input-gradient linear.
+ *   max_nodes sizes the grid (ceil(max_nodes / tile) workgroups per graph and head).  flag [1] i32, only ever OR-ed
+ *   into: bit 2 = a graph with more than max_nodes nodes, whose rows of every output are NaN.  Graph ranges are clamped
+ *   to [0, N].  An empty graph owns no rows.
+ *   HSCN_E_BADARG for negative sizes, N or B beyond 2^31 - 1, null pointers, or a qkv / out / g_out / g_qkv that is not
+ *   16-byte aligned; HSCN_E_UNSUPPORTED where hscn_attention_supported is 0 (it wants heads >= 1, dh % 4 == 0,
+ *   4 <= dh <= 64, heads * dh <= 512); both before any launch.  N = 0 or B = 0 launches nothing (0).  No workspace, no
+ *   host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_attention_supported(int heads, int dh);
+int hscn_attention_tile(void);
+int hscn_attention_chunk(void);
+int hscn_attention_fwd(const float* qkv, const int32_t* ptr32, int64_t N, int64_t B, int max_nodes, int heads, int dh,
+                       float* out /*[N, D]*/, float* lse /*[N, heads]*/, int32_t* flag /*[1]*/, void* stream);
+int hscn_attention_bwd_q(const float* qkv, const float* out, const float* lse, const float* g_out,
+                         const int32_t* ptr32, int64_t N, int64_t B, int max_nodes, int heads, int dh,
+                         float* g_qkv /*[N, 3D]*/, float* delta /*[N, heads]*/, int32_t* flag /*[1]*/, void* stream);
+int hscn_attention_bwd_kv(const float* qkv, const float* lse, const float* delta, const float* g_out,
+                          const int32_t* ptr32, int64_t N, int64_t B, int max_nodes, int heads, int dh,
+                          float* g_qkv /*[N, 3D]*/, int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
