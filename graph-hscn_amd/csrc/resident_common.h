@@ -206,6 +206,19 @@ __device__ __forceinline__ float row_matvec16(const float4& z, const float* Wt, 
     return acc;
   }
 }
+// the same chain with column r of the matrix already in registers: w[k] = Wt[k * 16 + r]
+template <int KQ = 0>
+__device__ __forceinline__ float row_matvec16(const float4& z, const float (&w)[16], float acc) {
+  if constexpr (KQ < 4) {
+    acc = fmaf(row_bcast<KQ>(z.x), w[4 * KQ + 0], acc);
+    acc = fmaf(row_bcast<KQ>(z.y), w[4 * KQ + 1], acc);
+    acc = fmaf(row_bcast<KQ>(z.z), w[4 * KQ + 2], acc);
+    acc = fmaf(row_bcast<KQ>(z.w), w[4 * KQ + 3], acc);
+    return row_matvec16<KQ + 1>(z, w, acc);
+  } else {
+    return acc;
+  }
+}
 // acc = fmaf(x_k, w[k], acc) for k = 0 .. N-1 in ascending order, x_k = the value of lane k of this lane's DPP row:
 // one row of a small matrix-vector product whose vector lives one element per lane
 template <int N, int K = 0>

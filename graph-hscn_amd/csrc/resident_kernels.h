@@ -1122,12 +1122,43 @@ __device__ __forceinline__ void hscn_fwd_body(const AT& A, const int g) {
         const int cs = s + c * 64, ce = (cs + 64 < t) ? cs + 64 : t;   // this wave's members
         const int p_own = cs + lane;
         const bool on = p_own < ce;
-        const float e_own = on ? leaky(a_s[col_lv[p_own]] + ad, A.slope) : -INFINITY;
-        float m, denom;
+        float e_own, m, denom;
+        // registers per lane that hold a cluster's logits: a cluster of the fixed layout's largest graph fits
+        constexpr int EK = (StepVCaps::N + 63) / 64;
         if (t - s <= 64) {
+          e_own = on ? leaky(a_s[col_lv[p_own]] + ad, A.slope) : -INFINITY;
           m = wave_max_dpp(e_own);
           denom = wave_sum_dpp(on ? expf(e_own - m) : 0.f) + 1e-16f;
+        } else if (t - s <= 64 * EK) {
+          // every chunk wave needs the whole cluster's max and denominator: the logits of members s + lane + 64 k are
+          // read ONCE -- all index reads in flight together, then all a_s reads -- and kept; the max takes them in any
+          // order (exact), the denominator in ascending k as the loops below do, and the wave's own members are
+          // register c
+          int jk[EK];
+          float ek[EK];
+#pragma unroll
+          for (int k = 0; k < EK; ++k) {
+            const int p = s + lane + 64 * k;
+            jk[k] = col_lv[p < t ? p : s];
+          }
+#pragma unroll
+          for (int k = 0; k < EK; ++k) ek[k] = a_s[jk[k]];
+          m = -INFINITY;
+          e_own = -INFINITY;
+#pragma unroll
+          for (int k = 0; k < EK; ++k) {
+            ek[k] = s + lane + 64 * k < t ? leaky(ek[k] + ad, A.slope) : -INFINITY;
+            m = fmaxf(m, ek[k]);
+            if (k == c) e_own = ek[k];
+          }
+          m = wave_max_dpp(m);
+          float sum = 0.f;
+#pragma unroll
+          for (int k = 0; k < EK; ++k)
+            if (s + lane + 64 * k < t) sum += expf(ek[k] - m);
+          denom = wave_sum_dpp(sum) + 1e-16f;
         } else {
+          e_own = on ? leaky(a_s[col_lv[p_own]] + ad, A.slope) : -INFINITY;
           m = -INFINITY;
           for (int p = s + lane; p < t; p += 64) m = fmaxf(m, leaky(a_s[col_lv[p]] + ad, A.slope));
           m = wave_max_dpp(m);
@@ -1182,6 +1213,20 @@ __device__ __forceinline__ void hscn_fwd_body(const AT& A, const int g) {
           acc.z = row_ror_add<4>(acc.z); acc.w = row_ror_add<4>(acc.w);
         }
         const int first = ck_first[v], cntv = ck_first[v + 1] - first;
+        // H = 16: what the finisher applies to the two aggregated rows -- column `lane & 15` of the two 16 x 16 matrices
+        // and the two biases -- does not depend on the rows: requested here, in front of the arrival counter
+        float wsr[16], wvr[16], bvr = 0.f, bgr = 0.f;
+        if constexpr (H == 16) {
+          const float* Ws = W + H * H;                     // Wt_src[k][o]
+          const float* Wv = W + 3 * H * H;                 // Wt_vv[k][o]
+#pragma unroll
+          for (int k = 0; k < 16; ++k) {
+            wsr[k] = Ws[k * 16 + (lane & 15)];
+            wvr[k] = Wv[k * 16 + (lane & 15)];
+          }
+          bvr = b_vv[lane & 15];
+          bgr = b_gat[lane & 15];
+        }
         if (slot == 0) *reinterpret_cast<float4*>(gpart + (size_t)ck * H + f) = acc;
         int arrived = 0;
         if (lane == 0)
@@ -1249,13 +1294,20 @@ __device__ __forceinline__ void hscn_fwd_body(const AT& A, const int g) {
             const float4 q = *reinterpret_cast<const float4*>(gpart + (size_t)(first + c2) * H + f);
             g.x += q.x; g.y += q.y; g.z += q.z; g.w += q.w;
           }
-          // the two aggregated input rows of cluster v go through this wave's H-word scratch one after the other
-          // (LDS executes a wave's operations in order: the lanes below read what these lanes wrote, and the
-          // second row lands after the first has been read)
+          // the two aggregated input rows of cluster v, four features per lane of slot 0.  H = 16 transforms them where
+          // they are; wider rows go through this wave's H-word scratch one after the other (LDS executes a wave's
+          // operations in order: the lanes below read what these lanes wrote, and the second row lands after the first
+          // has been read)
           z1r = g;                                         // z1 = sum_i alpha_i x_i
           z2r = a;                                         // z2 = sum_u norm_uv xv_u
         }
-        {
+        if constexpr (H == 16) {
+          // lanes 0 .. 3 of the first DPP row hold the four feature quarters of both rows: the operand form of
+          // row_matvec16, the same k-ascending fmaf chains as the scratch form below without its LDS round trips
+          const float og = row_matvec16(z1r, wsr, 0.f);
+          const float ov = row_matvec16(z2r, wvr, 0.f);
+          if (lane < 16) xvb[v * H + lane] = rnd<TS>(fmaxf((ov + bvr) + (og + bgr), 0.f));
+        } else {
           float* zw = zs + wave * H;
           const float* Ws = W + H * H;                     // Wt_src[k][o]
           const float* Wv = W + 3 * H * H;                 // Wt_vv[k][o]

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Record the bit-for-bit fixtures of tests/test_gpu_step_layouts.py from the library that is loaded:
+"""Record the bit-for-bit fixtures of tests/test_gpu_step_layouts.py -- or of the test module named as the second
+argument, e.g. tests.test_gpu_step_big_clusters -- from the library that is loaded:
 
-  [HSCN_LIB=<libhscn.so of the commit to record>] python tools/record_step_bits.py OUTDIR
+  [HSCN_LIB=<libhscn.so of the commit to record>] python tools/record_step_bits.py OUTDIR [MODULE]
 
-writes OUTDIR/step_bits_<case>.npz (prediction, score, flat gradients + loss, final virtual features of the one-launch
+The module provides CASES, case_id, build_case, run_one_launch and step_bits.  Writes OUTDIR/step_bits_<case>.npz (prediction, score, flat gradients + loss, final virtual features of the one-launch
 step on the test's own inputs).  Run it on the build whose results a change must reproduce, then copy the files to
 tests/golden/."""
 import os
@@ -11,9 +12,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "graph-hscn_amd")]
+import importlib
+
 import numpy as np
 
-from tests import test_gpu_step_layouts as T
+T = importlib.import_module(sys.argv[2] if len(sys.argv) > 2 else "tests.test_gpu_step_layouts")
 
 
 def main():
