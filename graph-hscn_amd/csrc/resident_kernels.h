@@ -42,7 +42,7 @@
 #pragma once
 #include "hscn_common.h"
 #include "resident_common.h"
-#include <cstdio>
+#include <type_traits>
 
 namespace {
 
@@ -1968,12 +1968,13 @@ __global__ void __launch_bounds__(RT) k_hscn_bwd_virtual(const BwdArgs Ab, const
   else hscn_bwd_body<H, RT, TS>(Ab, g);
 }
 
+
 inline size_t fwd_lds_bytes(int H, int C, int max_n, int max_v, int max_ell, int max_evv, int db, int exp) {
   return fwd_layout(H, C, max_n, max_v, max_ell, max_evv, db, exp).total * 4;
 }
 // double-buffered layer weights whenever the launch still fits a CU's LDS with them (H = 64: never, 64 KB)
 inline size_t pick_fwd_lds(FwdArgs& A, int H) {
-  A.db = (H <= 32 && fwd_lds_bytes(H, A.C, A.max_n, A.max_v, A.max_ell, A.max_evv, 1, A.exp) <= 160 * 1024) ? 1 : 0;
+  A.db = (H <= 32 && fwd_lds_bytes(H, A.C, A.max_n, A.max_v, A.max_ell, A.max_evv, 1, A.exp) <= LDS_CU_BYTES) ? 1 : 0;
   return fwd_lds_bytes(H, A.C, A.max_n, A.max_v, A.max_ell, A.max_evv, A.db, A.exp);
 }
 inline size_t bwd_lds_bytes(int H, int C, int max_n, int max_ell, int two) {
@@ -1983,7 +1984,7 @@ inline size_t bwd_lds_bytes(int H, int C, int max_n, int max_ell, int two) {
 inline size_t pick_bwd_lds(BwdArgs& A, int H) {
   A.two = 0;
   size_t lds = bwd_lds_bytes(H, A.C, A.max_n, A.max_ell, 0);
-  if (lds > 160 * 1024) {
+  if (lds > LDS_CU_BYTES) {
     A.two = 1;
     lds = bwd_lds_bytes(H, A.C, A.max_n, A.max_ell, 1);
   }
@@ -1994,59 +1995,6 @@ inline size_t pick_bwd_lds(BwdArgs& A, int H) {
 // phases; tiny graphs (PCQM-Contact, n <= 64) do not have the rows to feed them.
 inline int resident_threads(int max_n) { return max_n <= 64 ? 256 : 1024; }
 
-// ---- the launch plan: every size-dependent choice launch_fwd / launch_bwd make, taken HERE and nowhere else, so
-// hscn_resident_launch_plan (host arithmetic only) reports what the launches do rather than a restatement of it ----
-struct FwdPlan {
-  int threads;       // workgroup size
-  int csr_launch;    // the export was wanted and did not fit: k_ll_csr_t runs as a launch of its own
-  size_t lds;        // dynamic LDS of the forward launch (A.db / A.exp / A.exp_dinv are set in the arguments)
-  size_t csr_lds;    // dynamic LDS of k_ll_csr_t (0 without that launch)
-};
-// preference order: CSR export in the launch with double-buffered weights, then single-buffered (pick_fwd_lds), then
-// dropping the in-launch export (a separate light kernel builds it)
-inline int plan_fwd(FwdArgs& A, int H, bool want_exp, FwdPlan& P) {
-  bool ok = false;
-  P.lds = 0;
-  for (int e = 1; e >= 0 && !ok; --e) {
-    A.exp = (want_exp && e) ? 1 : 0;
-    P.lds = pick_fwd_lds(A, H);
-    ok = P.lds <= 160 * 1024;
-  }
-  if (!ok) return HSCN_E_UNSUPPORTED;
-  A.exp_dinv = A.exp;
-  P.threads = resident_threads(A.max_n);
-  P.csr_launch = (want_exp && !A.exp) ? 1 : 0;
-  P.csr_lds = P.csr_launch ? ((size_t)4 * A.max_ell + 2 * ((size_t)A.max_n + 1) + 16) * 4 : 0;
-  if (P.csr_lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  return 0;
-}
-struct BwdPlan {
-  int threads;
-  size_t lds;        // (A.two is set in the arguments)
-};
-inline int plan_bwd(BwdArgs& A, int H, BwdPlan& P) {
-  P.lds = pick_bwd_lds(A, H);
-  if (P.lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  P.threads = resident_threads(A.max_n);
-  return 0;
-}
-
-template <int H, int RT, int MODE, typename TS>
-int launch_fwd_mode(const FwdArgs& A, int64_t B, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_hscn_fwd<H, RT, MODE, TS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  k_hscn_fwd<H, RT, MODE, TS><<<(unsigned)B, RT, lds, st>>>(A);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
-template <int H, int RT, typename TS>
-int launch_fwd_rt(const FwdArgs& A, int64_t B, size_t lds, hipStream_t st) {
-  // one specialisation of the body per value of compute_virtual (see hscn_fwd_body: MODE)
-  if (A.compute_virtual == 0) return launch_fwd_mode<H, RT, 1, TS>(A, B, lds, st);
-  if (A.compute_virtual == 2) return launch_fwd_mode<H, RT, 0, TS>(A, B, lds, st);   // (first part or resumed: run time)
-  return launch_fwd_mode<H, RT, 3, TS>(A, B, lds, st);
-}
 // Source-keyed ll CSR + degree norm for the backward launch when the forward launch had no LDS
 // left to build them on the side (large graphs): a light kernel of its own, one workgroup per graph.
 __global__ void __launch_bounds__(256) k_ll_csr_t(const FwdArgs A) {
@@ -2174,85 +2122,246 @@ __global__ void __launch_bounds__(256) k_structure(const StructArgs A) {
   if (bad && A.flag) atomicOr(A.flag, 2);
 }
 
-template <int H, typename TS>
-int launch_fwd(FwdArgs& A, int64_t B, hipStream_t st) {
-  A.spec = A.compute_virtual ? 1 : 0;       // (the side-by-side wave groups cost no LDS any more)
-  FwdPlan P;
-  if (int rc = plan_fwd(A, H, A.csr_rowptr_t != nullptr, P)) return rc;
-  const int rc = P.threads == 256 ? launch_fwd_rt<H, 256, TS>(A, B, P.lds, st) : launch_fwd_rt<H, 1024, TS>(A, B, P.lds, st);
-  if (rc) return rc;
-  if (P.csr_launch) {
-    if (P.csr_lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_ll_csr_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.csr_lds);
-    k_ll_csr_t<<<(unsigned)B, 256, P.csr_lds, st>>>(A);
-    HSCN_RETURN_IF_LAUNCH_FAILED();
+#include "resident_step.h"
+
+// ---- the launch plan: every size-dependent choice of the five stage-C launch shapes (forward, backward, the forward
+// and the backward with virtual workgroups, the one-launch step), taken HERE and nowhere else.  A planner is host
+// arithmetic over the size fields of the argument blocks: it sets their choice fields (spec, exp, exp_dinv, db, two,
+// acq, the virtual block's max_ell) and returns what the launch needs beside them.  The launch_* functions below plan,
+// dispatch on the plan and launch; hscn_resident_launch_plan[_ex] (resident.hip) run the same planners over blocks
+// that hold the size fields only, so they report what the launches do rather than a restatement of it ----
+struct LaunchPlan {
+  int threads;       // workgroup size
+  size_t lds;        // dynamic LDS of the launch
+  // forward launches: the export was wanted and fits no workgroup of the launch, k_ll_csr_t runs as a launch of its own
+  int csr_launch;
+  size_t csr_lds;    // dynamic LDS of k_ll_csr_t (0 without that launch)
+  // the step, the instantiation launched: which of the two programs take their LDS layout at compile time
+  // (hscn_step_local LFIX / hscn_fwd_body MODE 6).  The local one only when the virtual one does too, or is absent.
+  bool local_fixed, virtual_fixed;
+};
+
+// the local chain's forward with the in-launch CSR export if it may have it and it fits, else without
+inline size_t pick_fwd_export(FwdArgs& A, int H, bool may_exp) {
+  A.exp = may_exp ? 1 : 0;
+  size_t lds = pick_fwd_lds(A, H);
+  if (A.exp && lds > LDS_CU_BYTES) {
+    A.exp = 0;
+    lds = pick_fwd_lds(A, H);
   }
-  return 0;
+  return lds;
 }
-template <int H, int RT, typename TS>
-int launch_bwd_rt(const BwdArgs& A, int64_t B, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_hscn_bwd<H, RT, TS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  k_hscn_bwd<H, RT, TS><<<(unsigned)B, RT, lds, st>>>(A);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
-template <int H, typename TS>
-int launch_bwd(BwdArgs& A, int64_t B, hipStream_t st) {
-  BwdPlan P;
-  if (int rc = plan_bwd(A, H, P)) return rc;
-  if (P.threads == 256) return launch_bwd_rt<H, 256, TS>(A, B, P.lds, st);
-  return launch_bwd_rt<H, 1024, TS>(A, B, P.lds, st);
+// k_ll_csr_t, the light kernel that builds the export when no workgroup of the forward launch does
+inline int plan_csr_launch(const FwdArgs& A, bool needed, LaunchPlan& P) {
+  P.csr_launch = needed ? 1 : 0;
+  P.csr_lds = needed ? ((size_t)4 * A.max_ell + 2 * ((size_t)A.max_n + 1) + 16) * 4 : 0;
+  return P.csr_lds > LDS_CU_BYTES ? HSCN_E_UNSUPPORTED : 0;
 }
 
-template <int H, int RT, typename TS>
-int launch_bwd_virtual_rt(const BwdArgs& Ab, const FwdArgs& Af, int64_t B, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_hscn_bwd_virtual<H, RT, TS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_hscn_bwd_virtual<H, RT, TS><<<(unsigned)(2 * B), RT, lds, st>>>(Ab, Af);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
+// preference order: CSR export in the launch with double-buffered weights, then single-buffered (pick_fwd_lds), then
+// dropping the in-launch export (k_ll_csr_t builds it)
+inline int plan_fwd(FwdArgs& A, int H, bool want_exp, LaunchPlan& P) {
+  A.spec = A.compute_virtual ? 1 : 0;       // (the side-by-side wave groups cost no LDS any more)
+  P.lds = pick_fwd_export(A, H, want_exp);
+  if (P.lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  A.exp_dinv = A.exp;
+  P.threads = resident_threads(A.max_n);
+  return plan_csr_launch(A, want_exp && !A.exp, P);
+}
+// The forward with virtual workgroups (k_hscn_fwd_pair).  The backward launch wants the ll CSR keyed by source and the
+// degree norm.  The local workgroup is the long pole of this launch, the virtual one has slack: the VIRTUAL workgroup
+// builds and exports the source-keyed CSR (it loads the ll edges for that alone; v_has_ll: it was handed them), the
+// local one only adds the degree norm it computes anyway.  Fallbacks when LDS is short: export from the local
+// workgroup, then k_ll_csr_t.
+inline int plan_fwd_pair(FwdArgs& Al, FwdArgs& Av, int H, bool want_exp, bool v_has_ll, LaunchPlan& P) {
+  // (a virtual-only workgroup is sized without ll edges unless it takes this job: Al.max_ell is the real bound)
+  const bool v_can = want_exp && v_has_ll &&
+                     fwd_lds_bytes(H, Av.C, Av.max_n, Av.max_v, Al.max_ell, Av.max_evv, 0, 1) <= LDS_CU_BYTES;
+  Av.max_ell = v_can ? Al.max_ell : 0;
+  if (!v_can) { Av.ll_src = nullptr; Av.ll_dst = nullptr; }
+  Al.spec = 0;
+  const size_t ll = pick_fwd_export(Al, H, want_exp && !v_can);
+  Al.exp_dinv = (Al.exp || v_can) ? 1 : 0;
+  Av.spec = 1;
+  Av.exp = v_can ? 1 : 0;
+  Av.exp_dinv = 0;
+  const size_t lv = pick_fwd_lds(Av, H);
+  if (ll > LDS_CU_BYTES || lv > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  P.lds = ll > lv ? ll : lv;
+  P.threads = resident_threads(Al.max_n);
+  return plan_csr_launch(Al, want_exp && !Al.exp && !v_can, P);
+}
+inline int plan_bwd(BwdArgs& A, int H, LaunchPlan& P) {
+  P.lds = pick_bwd_lds(A, H);
+  if (P.lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  P.threads = resident_threads(A.max_n);
   return 0;
 }
-template <int H, typename TS>
-int launch_bwd_virtual(BwdArgs& Ab, FwdArgs& Af, int64_t B, hipStream_t st) {
-  const size_t lb = pick_bwd_lds(Ab, H);
-  size_t lf = 0;
-  bool ok = false;
+// the backward with virtual workgroups (k_hscn_bwd_virtual): the larger of the two programs' LDS
+inline int plan_bwd_virtual(BwdArgs& Ab, FwdArgs& Af, int H, LaunchPlan& P) {
   Af.spec = 1;
   Af.exp = 0;
   Af.exp_dinv = 0;
-  lf = pick_fwd_lds(Af, H);
-  ok = lf <= 160 * 1024;
-  if (!ok || lb > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  const size_t lds = lb > lf ? lb : lf;
-  if (resident_threads(Ab.max_n) == 256) return launch_bwd_virtual_rt<H, 256, TS>(Ab, Af, B, lds, st);
-  return launch_bwd_virtual_rt<H, 1024, TS>(Ab, Af, B, lds, st);
+  const size_t lf = pick_fwd_lds(Af, H);
+  if (int rc = plan_bwd(Ab, H, P)) return rc;
+  if (lf > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  if (lf > P.lds) P.lds = lf;
+  return 0;
 }
 
-int fill_fwd_args(FwdArgs& A, const void* x_local, const void* x_virtual, const int64_t* ei_ll, int64_t E_ll,
-                  const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv, const int32_t* lptr,
-                  const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv, const int32_t* eptr_lv,
-                  int64_t N, int64_t V, int F, int H, int L, int C, int head_act, float slope,
-                  const void* const* layer_params_host, const float* W1, const float* b1, const float* W2,
-                  const float* b2, int max_n, int max_v, int max_ell, int max_evv, int compute_virtual,
-                  void* acts, float* pooled, float* z, float* pred, void* xv_out, int32_t* csr_rowptr_t,
-                  int32_t* csr_col_t, float* dinv_out, int32_t* flag) {
+// the widths the one-launch step is instantiated for
+inline bool step_takes_widths(int F, int H, int L, int C) {
+  return (H == 16 || H == 32) && F >= 1 && F <= H && L >= 1 && L <= MAXL && C >= 1 && C <= 4096;
+}
+constexpr size_t STEP_LFIX_LDS_BYTES = step_layout(16, StepLCaps::L, StepLCaps::C, StepLCaps::N, StepLCaps::ELL).total * 4;
+static_assert(STEP_LFIX_LDS_BYTES <= LDS_CU_BYTES, "the local program's fixed layout must fit a CU's LDS");
+// The one-launch step (k_hscn_step / k_hscn_step_local); V: the virtual job's block, NULL without one.
+inline int plan_step(const StepArgs& S, FwdArgs* V, int H, LaunchPlan& P) {
+  P.threads = resident_threads(S.max_n);
+  P.lds = step_lds_bytes(H, S.L, S.C, S.max_n, S.max_ell);
+  if (P.lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  const bool waves16 = P.threads == 1024;
+  P.virtual_fixed = false;
+  if (V) {
+    V->spec = 1; V->exp = 0; V->exp_dinv = 0;
+    size_t lv = pick_fwd_lds(*V, H);
+    if (lv > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+    // 16-wave workgroups on graphs within StepVCaps: the virtual program with its LDS layout fixed at compile time
+    // (hscn_fwd_body MODE 6: the layout's ~40 offsets are immediates instead of scalar registers -- 90 SGPR spills
+    // become 9); larger graphs / more clusters keep the run-time layout
+    if (waves16 && V->max_n <= StepVCaps::N && V->max_v <= StepVCaps::V && V->max_evv <= StepVCaps::EVV &&
+        V->l_begin == 0 && V->l_end == V->L) {
+      const size_t lf = fwd_lds_bytes(H, 1, StepVCaps::N, StepVCaps::V, 0, StepVCaps::EVV, 1, 0);
+      if (lf <= LDS_CU_BYTES) { P.virtual_fixed = true; lv = lf; V->db = 1; }
+    }
+    if (lv > P.lds) P.lds = lv;
+    if (waves16) {
+      // 16-wave workgroups: one per CU (the acquire-free consumer form is measured for exactly that): ask for more
+      // than half of a CU's LDS
+      if (P.lds < 81 * 1024) P.lds = 81 * 1024;
+    } else {
+      V->acq = 1;   // small graphs share CUs: the consumer acquires and uses plain loads (Guideline 16, R1 as written)
+    }
+  }
+  // 16-wave workgroups at H = 16 on a batch within StepLCaps: the local program with its LDS layout and layer count
+  // fixed at compile time (hscn_step_local LFIX) -- in ONE fully specialised instantiation, both programs' layouts at
+  // compile time (the headline shape); anything else keeps the local program's run-time layout
+  P.local_fixed = H == 16 && waves16 && S.max_n <= StepLCaps::N && S.max_ell <= StepLCaps::ELL &&
+                  S.L == StepLCaps::L && S.C <= StepLCaps::C && (P.virtual_fixed || !V);
+  if (P.local_fixed && P.lds < STEP_LFIX_LDS_BYTES) P.lds = STEP_LFIX_LDS_BYTES;
+  return 0;
+}
+
+// ---- the launches: plan, dispatch on threads / variant, launch (launch_with_lds: resident_common.h) ----
+// the hidden width as a template argument (f(std::integral_constant<int, H>{})), for the widths storage type TS is
+// instantiated at
+template <typename TS, typename F>
+int dispatch_width(int H, F&& f) {
+  switch (H) {
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: if constexpr (sizeof(TS) == 4) return f(std::integral_constant<int, 64>{}); else break;
+  }
+  return HSCN_E_UNSUPPORTED;
+}
+
+template <int H, int RT, typename TS>
+int launch_fwd_rt(const FwdArgs& A, int64_t B, size_t lds, hipStream_t st) {
+  // one specialisation of the body per value of compute_virtual (see hscn_fwd_body: MODE)
+  if (A.compute_virtual == 0) return launch_with_lds(k_hscn_fwd<H, RT, 1, TS>, (unsigned)B, RT, lds, st, A);
+  if (A.compute_virtual == 2)   // (first part or resumed: run time)
+    return launch_with_lds(k_hscn_fwd<H, RT, 0, TS>, (unsigned)B, RT, lds, st, A);
+  return launch_with_lds(k_hscn_fwd<H, RT, 3, TS>, (unsigned)B, RT, lds, st, A);
+}
+inline int launch_csr_t(const FwdArgs& A, int64_t B, const LaunchPlan& P, hipStream_t st) {
+  return P.csr_launch ? launch_with_lds(k_ll_csr_t, (unsigned)B, 256, P.csr_lds, st, A) : 0;
+}
+template <int H, typename TS>
+int launch_fwd(FwdArgs& A, int64_t B, hipStream_t st) {
+  LaunchPlan P;
+  if (int rc = plan_fwd(A, H, A.csr_rowptr_t != nullptr, P)) return rc;
+  const int rc = P.threads == 256 ? launch_fwd_rt<H, 256, TS>(A, B, P.lds, st) : launch_fwd_rt<H, 1024, TS>(A, B, P.lds, st);
+  return rc ? rc : launch_csr_t(A, B, P, st);
+}
+template <int H, typename TS>
+int launch_fwd_pair(FwdArgs& Al, FwdArgs& Av, int64_t B, hipStream_t st) {
+  LaunchPlan P;
+  if (int rc = plan_fwd_pair(Al, Av, H, Al.csr_rowptr_t != nullptr, Av.ll_src && Av.csr_rowptr_t, P)) return rc;
+  const FwdPair A{{Al, Av}};
+  const unsigned grid = (unsigned)(2 * B);
+  const int rc = P.threads == 256 ? launch_with_lds(k_hscn_fwd_pair<H, 256, TS>, grid, 256, P.lds, st, A)
+                                  : launch_with_lds(k_hscn_fwd_pair<H, 1024, TS>, grid, 1024, P.lds, st, A);
+  return rc ? rc : launch_csr_t(Al, B, P, st);
+}
+template <int H, typename TS>
+int launch_bwd(BwdArgs& A, int64_t B, hipStream_t st) {
+  LaunchPlan P;
+  if (int rc = plan_bwd(A, H, P)) return rc;
+  if (P.threads == 256) return launch_with_lds(k_hscn_bwd<H, 256, TS>, (unsigned)B, 256, P.lds, st, A);
+  return launch_with_lds(k_hscn_bwd<H, 1024, TS>, (unsigned)B, 1024, P.lds, st, A);
+}
+template <int H, typename TS>
+int launch_bwd_virtual(BwdArgs& Ab, FwdArgs& Af, int64_t B, hipStream_t st) {
+  LaunchPlan P;
+  if (int rc = plan_bwd_virtual(Ab, Af, H, P)) return rc;
+  const unsigned grid = (unsigned)(2 * B);
+  if (P.threads == 256) return launch_with_lds(k_hscn_bwd_virtual<H, 256, TS>, grid, 256, P.lds, st, Ab, Af);
+  return launch_with_lds(k_hscn_bwd_virtual<H, 1024, TS>, grid, 1024, P.lds, st, Ab, Af);
+}
+// grid = B local workgroups, then B virtual ones when there is a job
+template <int H, int RT, typename TS, int VMODE = 5, bool LFIX = false>
+int launch_step_rt(const StepArgs& S, const FwdArgs* V, size_t lds, hipStream_t st) {
+  if (V) return launch_with_lds(k_hscn_step<H, RT, TS, VMODE, LFIX>, (unsigned)(2 * S.B), RT, lds, st, S, *V);
+  return launch_with_lds(k_hscn_step_local<H, RT, TS, LFIX>, (unsigned)S.B, RT, lds, st, S);
+}
+template <int H, typename TS>
+int launch_step(const StepArgs& S, FwdArgs* V, hipStream_t st) {
+  LaunchPlan P;
+  if (int rc = plan_step(S, V, H, P)) return rc;
+  if (P.threads == 256) return launch_step_rt<H, 256, TS>(S, V, P.lds, st);
+  if constexpr (H == 16) {
+    if (P.local_fixed) return launch_step_rt<H, 1024, TS, 6, true>(S, V, P.lds, st);
+  }
+  if (P.virtual_fixed) return launch_step_rt<H, 1024, TS, 6>(S, V, P.lds, st);
+  return launch_step_rt<H, 1024, TS>(S, V, P.lds, st);
+}
+
+// ---- argument blocks ----
+// what a local launch says about its batch: every argument block of a step takes these from it
+struct LocalIn {
+  const void* x_local;
+  const int64_t* ei_ll; int64_t E_ll;   // [2,E_ll]
+  const int32_t *lptr, *eptr_ll;
+  int64_t N;
+  int F, L, C, head_act, max_n, max_ell;
+  int32_t* flag;
+};
+// head weights and outputs of a launch that runs the local chain (compute_virtual 0 / 1)
+struct LocalOut {
+  const float *W1, *b1, *W2, *b2;
+  float *pooled, *z, *pred, *score;
+  int32_t *csr_rowptr_t, *csr_col_t;
+  float* dinv_out;
+};
+// One FwdArgs from `in` and the virtual relations of `vj` (a caller's hscn_virtual_job, or hscn_resident_fwd's own
+// arguments in that form; its st_* are attach_state's).  o: all NULL for no head, no local outputs, no export.
+int fill_fwd_args(FwdArgs& A, const LocalIn& in, const hscn_virtual_job& vj, const void* const* layer_params_host,
+                  int compute_virtual, void* acts, void* xv_out, const LocalOut& o) {
   if (compute_virtual < 0 || compute_virtual > 2) return HSCN_E_BADARG;
   const bool vonly = compute_virtual == 2;
-  if (!x_local || !lptr || !vptr || !eptr_ll || !eptr_vv || !eptr_lv || !layer_params_host || !acts)
+  if (!in.x_local || !in.lptr || !vj.vptr || !in.eptr_ll || !vj.eptr_vv || !vj.eptr_lv || !layer_params_host || !acts)
     return HSCN_E_BADARG;
-  if (!vonly && (!W1 || !b1 || !W2 || !b2 || !pooled || !z || !pred)) return HSCN_E_BADARG;
-  if (vonly && (!xv_out || csr_rowptr_t || csr_col_t || dinv_out)) return HSCN_E_BADARG;
-  if ((E_ll > 0 && !ei_ll && !vonly) || (compute_virtual && ((E_vv > 0 && !ei_vv) || (E_lv > 0 && !ei_lv) || !x_virtual)))
+  if (!vonly && (!o.W1 || !o.b1 || !o.W2 || !o.b2 || !o.pooled || !o.z || !o.pred)) return HSCN_E_BADARG;
+  if (vonly && (!xv_out || o.csr_rowptr_t || o.csr_col_t || o.dinv_out)) return HSCN_E_BADARG;
+  if ((in.E_ll > 0 && !in.ei_ll && !vonly) ||
+      (compute_virtual && ((vj.E_vv > 0 && !vj.ei_vv) || (vj.E_lv > 0 && !vj.ei_lv) || !vj.x_virtual)))
     return HSCN_E_BADARG;
-  A.x_local = (const float*)x_local; A.x_virtual = (const float*)x_virtual;   // (the kernels read them as TS)
-  A.ll_src = ei_ll; A.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
-  A.vv_src = ei_vv; A.vv_dst = ei_vv ? ei_vv + E_vv : nullptr;
-  A.lv_src = ei_lv; A.lv_dst = ei_lv ? ei_lv + E_lv : nullptr;
-  A.lptr = lptr; A.vptr = vptr; A.eptr_ll = eptr_ll; A.eptr_vv = eptr_vv; A.eptr_lv = eptr_lv;
-  for (int l = 0; l < L; ++l) {
+  A.x_local = (const float*)in.x_local; A.x_virtual = vj.x_virtual;   // (the kernels read them as TS)
+  A.ll_src = in.ei_ll; A.ll_dst = in.ei_ll ? in.ei_ll + in.E_ll : nullptr;
+  A.vv_src = vj.ei_vv; A.vv_dst = vj.ei_vv ? vj.ei_vv + vj.E_vv : nullptr;
+  A.lv_src = vj.ei_lv; A.lv_dst = vj.ei_lv ? vj.ei_lv + vj.E_lv : nullptr;
+  A.lptr = in.lptr; A.vptr = vj.vptr; A.eptr_ll = in.eptr_ll; A.eptr_vv = vj.eptr_vv; A.eptr_lv = vj.eptr_lv;
+  for (int l = 0; l < in.L; ++l) {
     const void* const* q = layer_params_host + (size_t)l * 9;
     for (int k = 0; k < 9; ++k)
       if (!q[k] && (compute_virtual || k < 2)) return HSCN_E_BADARG;
@@ -2260,21 +2369,29 @@ int fill_fwd_args(FwdArgs& A, const void* x_local, const void* x_virtual, const 
                         (const float*)q[4], (const float*)q[5], (const float*)q[6], (const float*)q[7],
                         (const float*)q[8]};
   }
-  A.W1 = W1; A.b1 = b1; A.W2 = W2; A.b2 = b2;
-  A.acts = (float*)acts; A.pooled = pooled; A.z = z; A.pred = pred; A.xv_out = (float*)xv_out; A.flag = flag;
-  A.score = nullptr;
-  if ((csr_rowptr_t == nullptr) != (csr_col_t == nullptr) || (csr_rowptr_t == nullptr) != (dinv_out == nullptr))
+  A.W1 = o.W1; A.b1 = o.b1; A.W2 = o.W2; A.b2 = o.b2;
+  A.acts = (float*)acts; A.pooled = o.pooled; A.z = o.z; A.pred = o.pred; A.xv_out = (float*)xv_out; A.flag = in.flag;
+  A.score = o.score;
+  if ((o.csr_rowptr_t == nullptr) != (o.csr_col_t == nullptr) || (o.csr_rowptr_t == nullptr) != (o.dinv_out == nullptr))
     return HSCN_E_BADARG;
-  A.csr_rowptr_t = csr_rowptr_t; A.csr_col_t = csr_col_t; A.dinv_out = dinv_out;
-  A.N = N; A.V = V; A.F = F; A.L = L; A.C = C; A.head_act = head_act;
-  A.max_n = max_n; A.max_v = max_v; A.max_ell = vonly ? 0 : max_ell; A.max_evv = max_evv;
-  A.compute_virtual = compute_virtual; A.slope = slope; A.spec = 0; A.exp = 0; A.exp_dinv = 0; A.db = 0;
-  A.l_begin = 0; A.l_end = L;
+  A.csr_rowptr_t = o.csr_rowptr_t; A.csr_col_t = o.csr_col_t; A.dinv_out = o.dinv_out;
+  A.N = in.N; A.V = vj.V; A.F = in.F; A.L = in.L; A.C = in.C; A.head_act = in.head_act;
+  A.max_n = in.max_n; A.max_v = vj.max_v; A.max_ell = vonly ? 0 : in.max_ell; A.max_evv = vj.max_evv;
+  A.compute_virtual = compute_virtual; A.slope = vj.slope; A.spec = 0; A.exp = 0; A.exp_dinv = 0; A.db = 0;
+  A.l_begin = 0; A.l_end = in.L;
   A.ready = nullptr; A.epoch = nullptr; A.acq = 0;
   A.pre_rp_lv = A.pre_col_lv = A.pre_rp_vv = A.pre_col_vv = nullptr; A.pre_dinv_v = nullptr;
   A.vs_rowptr_lv = A.vs_col_lv = A.vs_rowptr_vv = A.vs_col_vv = nullptr;
   A.vs_dinv_v = A.vs_xv = nullptr;
   return 0;
+}
+// The block of a hscn_virtual_job's workgroups (compute_virtual = 2) beside a local launch described by `in`: they
+// read the local activations `acts` and write the virtual features to xv_out.  A virtual-only workgroup loads no ll
+// edges (plan_fwd_pair may hand it those of the CSR export).
+inline int virtual_job_args(FwdArgs& A, LocalIn in, const hscn_virtual_job* job, void* acts, void* xv_out) {
+  in.ei_ll = nullptr;
+  in.E_ll = 0;
+  return fill_fwd_args(A, in, *job, job->layer_params_host, 2, acts, xv_out, LocalOut{});
 }
 
 inline bool job_has_state(const hscn_virtual_job* j) {
@@ -2286,88 +2403,26 @@ inline void attach_state(FwdArgs& A, const hscn_virtual_job* j) {
   A.vs_dinv_v = j->st_dinv_v; A.vs_xv = j->st_xv;
 }
 
-template <int H, int RT, typename TS>
-int launch_fwd_pair_rt(const FwdArgs& Al, const FwdArgs& Av, int64_t B, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_hscn_fwd_pair<H, RT, TS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  FwdPair P;
-  P.a[0] = Al;
-  P.a[1] = Av;
-  k_hscn_fwd_pair<H, RT, TS><<<(unsigned)(2 * B), RT, lds, st>>>(P);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
-template <int H, typename TS>
-int launch_fwd_pair(FwdArgs& Al, FwdArgs& Av, int64_t B, hipStream_t st) {
-  // The backward launch wants the ll CSR keyed by source and the degree norm.  The local workgroup is the long
-  // pole of this launch, the virtual one has slack: the VIRTUAL workgroup builds and exports the source-keyed
-  // CSR (it loads the ll edges for that alone), the local one only adds the degree norm it computes anyway.
-  // Fallbacks when LDS is short: export from the local workgroup, then the light side kernel.
-  const bool want_exp = Al.csr_rowptr_t != nullptr;
-  size_t ll = 0, lv = 0;
-  bool ok = false;
-  // (a virtual-only workgroup is sized without ll edges unless it takes this job: Al.max_ell is the real bound)
-  const bool v_can = want_exp && Av.ll_src && Av.csr_rowptr_t &&
-                     fwd_lds_bytes(H, Av.C, Av.max_n, Av.max_v, Al.max_ell, Av.max_evv, 0, 1) <= 160 * 1024;
-  Av.max_ell = v_can ? Al.max_ell : 0;
-  for (int e = 1; e >= 0 && !ok; --e) {
-    Al.spec = 0;
-    Al.exp = (want_exp && e && !v_can) ? 1 : 0;
-    ll = pick_fwd_lds(Al, H);
-    ok = ll <= 160 * 1024;
-  }
-  if (!ok) return HSCN_E_UNSUPPORTED;
-  Al.exp_dinv = (Al.exp || v_can) ? 1 : 0;
-  ok = false;
-  Av.spec = 1;
-  Av.exp = v_can ? 1 : 0;
-  Av.exp_dinv = 0;
-  lv = pick_fwd_lds(Av, H);
-  ok = lv <= 160 * 1024;
-  if (!ok) return HSCN_E_UNSUPPORTED;
-  if (!v_can) { Av.ll_src = nullptr; Av.ll_dst = nullptr; }
-  const size_t lds = ll > lv ? ll : lv;
-  int rc = resident_threads(Al.max_n) == 256 ? launch_fwd_pair_rt<H, 256, TS>(Al, Av, B, lds, st)
-                          : launch_fwd_pair_rt<H, 1024, TS>(Al, Av, B, lds, st);
-  if (rc) return rc;
-  if (want_exp && !Al.exp && !v_can) {
-    const size_t l2 = ((size_t)4 * Al.max_ell + 2 * ((size_t)Al.max_n + 1) + 16) * 4;
-    if (l2 > 160 * 1024) return HSCN_E_UNSUPPORTED;
-    if (l2 > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_ll_csr_t, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-    k_ll_csr_t<<<(unsigned)B, 256, l2, st>>>(Al);
-    HSCN_RETURN_IF_LAUNCH_FAILED();
-  }
-  return 0;
-}
-
-int fill_bwd_args(BwdArgs& A, const void* x_local, const int64_t* ei_ll, int64_t E_ll, const int32_t* lptr,
-                  const int32_t* eptr_ll, int64_t N, int F, int H, int L, int C, int head_act,
-                  const void* const* W_ll_host, const float* W1, const float* W2, const void* acts,
-                  const float* pooled, const float* z, const float* g_pred, const float* g_scale,
-                  const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, int max_n, int max_ell,
-                  float* partials, float* grads, int32_t* flag) {
-  if (!x_local || !lptr || !eptr_ll || !W_ll_host || !W1 || !W2 || !acts || !pooled || !z ||
-      !partials || !grads || !csr_rowptr_t || !dinv || (E_ll > 0 && !csr_col_t))
+int fill_bwd_args(BwdArgs& A, const LocalIn& in, int H, const void* const* W_ll_host, const float* W1, const float* W2,
+                  const void* acts, const float* pooled, const float* z, const float* g_pred, const float* g_scale,
+                  const int32_t* csr_rowptr_t, const int32_t* csr_col_t, const float* dinv, float* partials,
+                  float* grads, const hscn_loss_tail* tail, int64_t B) {
+  if (!in.x_local || !in.lptr || !in.eptr_ll || !W_ll_host || !W1 || !W2 || !acts || !pooled || !z ||
+      !partials || !grads || !csr_rowptr_t || !dinv || (in.E_ll > 0 && !csr_col_t))
     return HSCN_E_BADARG;
-  A.x_local = (const float*)x_local; A.ll_src = ei_ll; A.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
-  A.lptr = lptr; A.eptr_ll = eptr_ll;
-  for (int l = 0; l < L; ++l) {
+  A.x_local = (const float*)in.x_local; A.ll_src = in.ei_ll; A.ll_dst = in.ei_ll ? in.ei_ll + in.E_ll : nullptr;
+  A.lptr = in.lptr; A.eptr_ll = in.eptr_ll;
+  for (int l = 0; l < in.L; ++l) {
     if (!W_ll_host[l]) return HSCN_E_BADARG;
     A.W_ll[l] = (const float*)W_ll_host[l];
   }
   A.W1 = W1; A.W2 = W2; A.acts = (const float*)acts; A.pooled = pooled; A.z = z; A.g_pred = g_pred;
   A.g_scale = g_scale;
   A.csr_rowptr_t = csr_rowptr_t; A.csr_col_t = csr_col_t; A.dinv_in = dinv;
-  A.partials = partials; A.flag = flag; A.N = N; A.F = F; A.L = L; A.C = C; A.head_act = head_act;
-  A.max_n = max_n; A.max_ell = max_ell; A.P = (int)hscn_resident_param_count(F, H, L, C);
+  A.partials = partials; A.flag = in.flag; A.N = in.N; A.F = in.F; A.L = in.L; A.C = in.C; A.head_act = in.head_act;
+  A.max_n = in.max_n; A.max_ell = in.max_ell; A.P = (int)hscn_resident_param_count(in.F, H, in.L, in.C);
   A.pred = nullptr; A.target = nullptr; A.loss_kind = 0; A.Pn = A.P; A.inv_count = 0.f;
-  return 0;
-}
-
-// upstream gradient: either given (g_pred) or computed by the launch from the loss tail
-int attach_tail(BwdArgs& A, const hscn_loss_tail* tail, int64_t B) {
+  // upstream gradient: either given (g_pred) or computed by the launch from the loss tail
   if (!tail) return A.g_pred ? 0 : HSCN_E_BADARG;
   if (!tail->pred || !tail->target || (tail->kind != 0 && tail->kind != 1)) return HSCN_E_BADARG;
   A.pred = tail->pred; A.target = tail->target; A.loss_kind = tail->kind;
@@ -2375,9 +2430,13 @@ int attach_tail(BwdArgs& A, const hscn_loss_tail* tail, int64_t B) {
   A.P = A.Pn + 1;                                     // partials rows and grads carry the loss column
   return 0;
 }
-
-
-#include "resident_step.h"
+// the gradient-producing launches end in the ordered fold of the per-graph partials
+inline int fold_bwd_partials(const BwdArgs& A, float* grads, int64_t B, int flags, hipStream_t st) {
+  launch_param_fold(A.partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count, nullptr,
+                    flags & HSCN_GRAD_ACCUMULATE, st);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
 
 // ---- the C entry points, generic in the storage type (resident.hip: float, resident_f16.hip: half): each takes
 // ---- the prototype include/hscn.h exports, so the exported function only selects the instantiation ----
@@ -2394,20 +2453,14 @@ int impl_resident_fwd(const void* x_local, const void* x_virtual, const int64_t*
   if (B < 0 || N < 0 || V < 0) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, max_v, max_ell, max_evv)) return HSCN_E_UNSUPPORTED;
+  const LocalIn in{x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, L, C, head_act, max_n, max_ell, flag};
+  const LocalOut out{W1, b1, W2, b2, pooled, z, pred, score, csr_rowptr_t, csr_col_t, dinv_out};
+  const hscn_virtual_job vj{(const float*)x_virtual, ei_vv, E_vv, ei_lv, E_lv, vptr, eptr_vv, eptr_lv, layer_params_host,
+                            (float*)xv_out, V, max_v, max_evv, slope};   // this call's virtual relations in a job's form
   FwdArgs A;
-  if (int rc = fill_fwd_args(A, x_local, x_virtual, ei_ll, E_ll, ei_vv, E_vv, ei_lv, E_lv, lptr, vptr, eptr_ll,
-                             eptr_vv, eptr_lv, N, V, F, H, L, C, head_act, slope, layer_params_host, W1, b1, W2,
-                             b2, max_n, max_v, max_ell, max_evv, compute_virtual, acts, pooled, z, pred, xv_out,
-                             csr_rowptr_t, csr_col_t, dinv_out, flag))
-    return rc;
-  A.score = score;
+  if (int rc = fill_fwd_args(A, in, vj, layer_params_host, compute_virtual, acts, xv_out, out)) return rc;
   hipStream_t st = hscn_stream(stream_);
-  switch (H) {
-    case 16: return launch_fwd<16, TS>(A, B, st);
-    case 32: return launch_fwd<32, TS>(A, B, st);
-    case 64: if constexpr (sizeof(TS) == 4) return launch_fwd<64, float>(A, B, st); else break;
-  }
-  return HSCN_E_UNSUPPORTED;
+  return dispatch_width<TS>(H, [&](auto h) { return launch_fwd<decltype(h)::value, TS>(A, B, st); });
 }
 
 template <typename TS>
@@ -2421,24 +2474,14 @@ int impl_resident_bwd(const void* x_local, const int64_t* ei_ll, int64_t E_ll, c
   if (B < 0 || N < 0) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, 0, max_ell, 0)) return HSCN_E_UNSUPPORTED;
+  const LocalIn in{x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, L, C, head_act, max_n, max_ell, flag};
   BwdArgs A;
-  if (int rc0 = fill_bwd_args(A, x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, H, L, C, head_act, W_ll_host, W1, W2,
-                              acts, pooled, z, g_pred, g_scale, csr_rowptr_t, csr_col_t, dinv, max_n, max_ell,
-                              partials, grads, flag))
+  if (int rc0 = fill_bwd_args(A, in, H, W_ll_host, W1, W2, acts, pooled, z, g_pred, g_scale, csr_rowptr_t, csr_col_t,
+                              dinv, partials, grads, tail, B))
     return rc0;
-  if (int rct = attach_tail(A, tail, B)) return rct;
   hipStream_t st = hscn_stream(stream_);
-  int rc = HSCN_E_UNSUPPORTED;
-  switch (H) {
-    case 16: rc = launch_bwd<16, TS>(A, B, st); break;
-    case 32: rc = launch_bwd<32, TS>(A, B, st); break;
-    case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd<64, float>(A, B, st); break;
-  }
-  if (rc) return rc;
-  launch_param_fold(partials, grads, (int)B, A.P, A.target ? A.Pn : -1, A.inv_count, nullptr,
-                    flags & HSCN_GRAD_ACCUMULATE, st);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  if (int rc = dispatch_width<TS>(H, [&](auto h) { return launch_bwd<decltype(h)::value, TS>(A, B, st); })) return rc;
+  return fold_bwd_partials(A, grads, B, flags, st);
 }
 
 template <typename TS>
@@ -2453,36 +2496,22 @@ int impl_resident_bwd_with_virtual(const void* x_local, const int64_t* ei_ll, in
   if (B < 0 || N < 0 || !job) return HSCN_E_BADARG;
   if (B == 0) return 0;
   if (!hscn_resident_supported(F, H, L, C, max_n, job->max_v, max_ell, job->max_evv)) return HSCN_E_UNSUPPORTED;
+  const LocalIn in{x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, L, C, head_act, max_n, max_ell, flag};
   BwdArgs Ab;
-  if (int rc0 = fill_bwd_args(Ab, x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, H, L, C, head_act, W_ll_host, W1,
-                              W2, acts, pooled, z, g_pred, g_scale, csr_rowptr_t, csr_col_t, dinv, max_n,
-                              max_ell, partials, grads, flag))
+  if (int rc0 = fill_bwd_args(Ab, in, H, W_ll_host, W1, W2, acts, pooled, z, g_pred, g_scale, csr_rowptr_t,
+                              csr_col_t, dinv, partials, grads, tail, B))
     return rc0;
-  if (int rct = attach_tail(Ab, tail, B)) return rct;
   FwdArgs Af;
-  if (int rc1 = fill_fwd_args(Af, x_local, job->x_virtual, nullptr, 0, job->ei_vv, job->E_vv, job->ei_lv,
-                              job->E_lv, lptr, job->vptr, eptr_ll, job->eptr_vv, job->eptr_lv, N, job->V, F, H, L,
-                              C, head_act, job->slope, job->layer_params_host, nullptr, nullptr, nullptr, nullptr,
-                              max_n, job->max_v, max_ell, job->max_evv, 2, const_cast<void*>(acts), nullptr,
-                              nullptr, nullptr, job->xv_out, nullptr, nullptr, nullptr, flag))
-    return rc1;
+  if (int rc1 = virtual_job_args(Af, in, job, const_cast<void*>(acts), job->xv_out)) return rc1;
   if (job_has_state(job)) {   // the forward launch ran structure + layer 0 (hscn_resident_fwd_with_virtual)
     if (L < 2) return HSCN_E_BADARG;
     attach_state(Af, job);
     Af.l_begin = 1;
   }
   hipStream_t st = hscn_stream(stream_);
-  int rc = HSCN_E_UNSUPPORTED;
-  switch (H) {
-    case 16: rc = launch_bwd_virtual<16, TS>(Ab, Af, B, st); break;
-    case 32: rc = launch_bwd_virtual<32, TS>(Ab, Af, B, st); break;
-    case 64: if constexpr (sizeof(TS) == 4) rc = launch_bwd_virtual<64, float>(Ab, Af, B, st); break;
-  }
-  if (rc) return rc;
-  launch_param_fold(partials, grads, (int)B, Ab.P, Ab.target ? Ab.Pn : -1, Ab.inv_count, nullptr,
-                    flags & HSCN_GRAD_ACCUMULATE, st);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  if (int rc = dispatch_width<TS>(H, [&](auto h) { return launch_bwd_virtual<decltype(h)::value, TS>(Ab, Af, B, st); }))
+    return rc;
+  return fold_bwd_partials(Ab, grads, B, flags, st);
 }
 
 template <typename TS>
@@ -2497,34 +2526,19 @@ int impl_resident_fwd_with_virtual(const void* x_local, const int64_t* ei_ll, in
   if (B == 0) return 0;
   if (L < 2 || !job_has_state(job)) return HSCN_E_BADARG;
   if (!hscn_resident_supported(F, H, L, C, max_n, job->max_v, max_ell, job->max_evv)) return HSCN_E_UNSUPPORTED;
+  const LocalIn in{x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, L, C, head_act, max_n, max_ell, flag};
+  const LocalOut out{W1, b1, W2, b2, pooled, z, pred, score, csr_rowptr_t, csr_col_t, dinv_out};
   FwdArgs Al, Av;
-  if (int rc0 = fill_fwd_args(Al, x_local, job->x_virtual, ei_ll, E_ll, job->ei_vv, job->E_vv, job->ei_lv,
-                              job->E_lv, lptr, job->vptr, eptr_ll, job->eptr_vv, job->eptr_lv, N, job->V, F, H, L,
-                              C, head_act, job->slope, layer_params_host, W1, b1, W2, b2, max_n, job->max_v,
-                              max_ell, job->max_evv, 0, acts, pooled, z, pred, nullptr, csr_rowptr_t, csr_col_t,
-                              dinv_out, flag))
-    return rc0;
-  Al.score = score;
+  if (int rc0 = fill_fwd_args(Al, in, *job, layer_params_host, 0, acts, nullptr, out)) return rc0;
   // virtual part 1: `acts` is not read by layer 0 (it takes the input features) but must be valid
-  if (int rc1 = fill_fwd_args(Av, x_local, job->x_virtual, nullptr, 0, job->ei_vv, job->E_vv, job->ei_lv,
-                              job->E_lv, lptr, job->vptr, eptr_ll, job->eptr_vv, job->eptr_lv, N, job->V, F, H, L,
-                              C, head_act, job->slope, job->layer_params_host, nullptr, nullptr, nullptr, nullptr,
-                              max_n, job->max_v, max_ell, job->max_evv, 2, acts, nullptr, nullptr, nullptr,
-                              job->xv_out ? job->xv_out : job->st_xv, nullptr, nullptr, nullptr, flag))
-    return rc1;
+  if (int rc1 = virtual_job_args(Av, in, job, acts, job->xv_out ? job->xv_out : job->st_xv)) return rc1;
   attach_state(Av, job);
-  Av.l_begin = 0;
-  Av.l_end = 1;
-  // what the virtual workgroup needs to build the backward's source-keyed ll CSR (launch_fwd_pair decides)
+  Av.l_end = 1;   // (layer 0 only)
+  // what the virtual workgroup needs to build the backward's source-keyed ll CSR (plan_fwd_pair decides)
   Av.ll_src = Al.ll_src; Av.ll_dst = Al.ll_dst;
   Av.csr_rowptr_t = csr_rowptr_t; Av.csr_col_t = csr_col_t;
   hipStream_t st = hscn_stream(stream_);
-  switch (H) {
-    case 16: return launch_fwd_pair<16, TS>(Al, Av, B, st);
-    case 32: return launch_fwd_pair<32, TS>(Al, Av, B, st);
-    case 64: if constexpr (sizeof(TS) == 4) return launch_fwd_pair<64, float>(Al, Av, B, st); else break;
-  }
-  return HSCN_E_UNSUPPORTED;
+  return dispatch_width<TS>(H, [&](auto h) { return launch_fwd_pair<decltype(h)::value, TS>(Al, Av, B, st); });
 }
 
 
@@ -2543,8 +2557,7 @@ int impl_resident_train_step(const void* x_local, const int64_t* ei_ll, int64_t 
                      (job->E_vv > 0 && !pre->vv_col)))
     return HSCN_E_BADARG;
   if (B == 0) return 0;
-  if (!(H == 16 || H == 32) || F < 1 || F > H || L < 1 || L > MAXL || C < 1 || C > 4096 || max_n < 0 || max_ell < 0)
-    return HSCN_E_UNSUPPORTED;
+  if (!step_takes_widths(F, H, L, C) || max_n < 0 || max_ell < 0) return HSCN_E_UNSUPPORTED;
   if (!x_local || !lptr || !eptr_ll || !layer_params_host || !W1 || !b1 || !W2 || !b2 || !target || !pred ||
       !partials || !grads || (E_ll > 0 && !ei_ll) || (loss_kind != 0 && loss_kind != 1))
     return HSCN_E_BADARG;
@@ -2570,12 +2583,8 @@ int impl_resident_train_step(const void* x_local, const int64_t* ei_ll, int64_t 
   S.epoch = sync;
   FwdArgs V;
   if (job) {
-    if (int rc1 = fill_fwd_args(V, x_local, job->x_virtual, nullptr, 0, job->ei_vv, job->E_vv, job->ei_lv, job->E_lv,
-                                lptr, job->vptr, eptr_ll, job->eptr_vv, job->eptr_lv, N, job->V, F, H, L, C, head_act,
-                                job->slope, job->layer_params_host, nullptr, nullptr, nullptr, nullptr, max_n,
-                                job->max_v, max_ell, job->max_evv, 2, acts, nullptr, nullptr, nullptr, job->xv_out,
-                                nullptr, nullptr, nullptr, flag))
-      return rc1;
+    const LocalIn in{x_local, ei_ll, E_ll, lptr, eptr_ll, N, F, L, C, head_act, max_n, max_ell, flag};
+    if (int rc1 = virtual_job_args(V, in, job, acts, job->xv_out)) return rc1;
     V.ready = S.ready; V.epoch = sync;
     if (pre) {
       V.pre_rp_lv = pre->lv_rowptr; V.pre_col_lv = pre->lv_col; V.pre_rp_vv = pre->vv_rowptr;
@@ -2589,56 +2598,6 @@ int impl_resident_train_step(const void* x_local, const int64_t* ei_ll, int64_t 
                     flags & HSCN_GRAD_ACCUMULATE, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
-}
-
-inline int impl_resident_structure(const int64_t* ei_ll, int64_t E_ll, const int64_t* ei_vv, int64_t E_vv,
-                                   const int64_t* ei_lv, int64_t E_lv, const int32_t* lptr, const int32_t* vptr,
-                                   const int32_t* eptr_ll, const int32_t* eptr_vv, const int32_t* eptr_lv, int64_t B,
-                                   int max_n, int max_v, int max_ell, int max_evv, const hscn_structure* out,
-                                   int32_t* flag, void* stream_) {
-  if (B < 0 || !out || max_n < 0 || max_v < 0 || max_ell < 0 || max_evv < 0) return HSCN_E_BADARG;
-  if (B == 0) return 0;
-  if (!lptr || !vptr || !eptr_ll || !eptr_vv || !eptr_lv || (E_ll > 0 && !ei_ll) || (E_vv > 0 && !ei_vv) ||
-      (E_lv > 0 && !ei_lv))
-    return HSCN_E_BADARG;
-  if (!out->ll_rowptr_d || !out->ll_rowptr_s || !out->ll_dinv || !out->lv_rowptr || !out->vv_rowptr || !out->vv_dinv ||
-      (E_ll > 0 && (!out->ll_col_d || !out->ll_col_s)) || (E_lv > 0 && !out->lv_col) || (E_vv > 0 && !out->vv_col))
-    return HSCN_E_BADARG;
-  StructArgs A;
-  A.ll_src = ei_ll; A.ll_dst = ei_ll ? ei_ll + E_ll : nullptr;
-  A.vv_src = ei_vv; A.vv_dst = ei_vv ? ei_vv + E_vv : nullptr;
-  A.lv_src = ei_lv; A.lv_dst = ei_lv ? ei_lv + E_lv : nullptr;
-  A.lptr = lptr; A.vptr = vptr; A.eptr_ll = eptr_ll; A.eptr_vv = eptr_vv; A.eptr_lv = eptr_lv;
-  A.out = *out; A.flag = flag; A.max_n = max_n; A.max_v = max_v; A.max_ell = max_ell; A.max_evv = max_evv;
-  const size_t lds = struct_lds_words(max_n, max_v, max_ell, max_evv) * 4;
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_structure, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_structure<<<(unsigned)B, 256, lds, hscn_stream(stream_)>>>(A);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
-
-// workgroups of the one-launch step that one CU takes at a time: 1 for 16-wave workgroups (they are not made to
-// share a CU), up to 4 for the 4-wave workgroups of small graphs (PCQM-Contact: n <= 64) when LDS allows
-inline int step_wgs_per_cu(int H, int L, int C, int max_n, int max_ell, int max_v, int max_evv) {
-  if (max_n > 64) return 1;
-  size_t lds = step_lds_bytes(H, L, C, max_n, max_ell);
-  if (max_v > 0) {
-    const size_t lv = fwd_lds_bytes(H, C, max_n, max_v, 0, max_evv, 1, 0);
-    if (lv > lds) lds = lv;
-  }
-  if (lds == 0) return 4;
-  const int by_lds = (int)((size_t)160 * 1024 / lds);
-  return by_lds < 1 ? 1 : (by_lds > 4 ? 4 : by_lds);
-}
-
-inline int step_supported(int F, int H, int L, int C, int max_n, int max_ell, int max_v, int max_evv) {
-  if (!(H == 16 || H == 32) || F < 1 || F > H || L < 1 || L > MAXL || C < 1 || C > 4096) return 0;
-  if (max_n < 0 || max_ell < 0 || max_v < 0 || max_evv < 0) return 0;
-  if (step_lds_bytes(H, L, C, max_n, max_ell) > 160 * 1024) return 0;
-  if (max_v > 0 && fwd_lds_bytes(H, C, max_n, max_v, 0, max_evv, 0, 0) > 160 * 1024) return 0;
-  return 1;
 }
 
 }  // namespace

@@ -156,7 +156,7 @@ __device__ void lin_mfma_wt_masked(const float* X, const float* Wt, float* Y, in
   }
 }
 
-// LFIX: the LDS layout and the layer count come from StepLCaps at compile time (launch_step takes this form for a batch
+// LFIX: the LDS layout and the layer count come from StepLCaps at compile time (plan_step chooses this form for a batch
 // inside the caps): the layout's ~25 offsets, the buffer addresses and `wt + l * WL` are immediates instead of scalar
 // registers.  Same program, same bits; a batch outside the caps runs the run-time layout compiled in beside it.
 template <int H, int RT, typename TS, bool LFIX = false>
@@ -946,63 +946,4 @@ __global__ void __launch_bounds__(RT) k_hscn_step_local(const StepArgs S) {
 
 inline size_t step_lds_bytes(int H, int L, int C, int max_n, int max_ell) {
   return step_layout(H, L, C, max_n, max_ell).total * 4;
-}
-
-template <int H, int RT, typename TS, int VMODE = 5, bool LFIX = false>
-int launch_step_rt(const StepArgs& S, const FwdArgs* V, size_t lds, hipStream_t st) {
-  if (V) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_hscn_step<H, RT, TS, VMODE, LFIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-    k_hscn_step<H, RT, TS, VMODE, LFIX><<<(unsigned)(2 * S.B), RT, lds, st>>>(S, *V);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_hscn_step_local<H, RT, TS, LFIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds);
-    k_hscn_step_local<H, RT, TS, LFIX><<<(unsigned)S.B, RT, lds, st>>>(S);
-  }
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
-}
-
-template <int H, typename TS>
-int launch_step(StepArgs& S, FwdArgs* V, hipStream_t st) {
-  size_t lds = step_lds_bytes(H, S.L, S.C, S.max_n, S.max_ell);
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  // 16-wave workgroups at H = 16 on a batch within StepLCaps: the local program with its LDS layout and layer count
-  // fixed at compile time (hscn_step_local LFIX); anything else keeps the run-time layout
-  constexpr size_t lds_lfix = step_layout(H, StepLCaps::L, StepLCaps::C, StepLCaps::N, StepLCaps::ELL).total * 4;
-  static_assert(H != 16 || lds_lfix <= 160 * 1024, "the local program's fixed layout must fit a CU's LDS");
-  const bool local_fixed = H == 16 && S.max_n > 64 && S.max_n <= StepLCaps::N && S.max_ell <= StepLCaps::ELL &&
-                           S.L == StepLCaps::L && S.C <= StepLCaps::C;
-  bool fixed_layout = false;
-  if (V) {
-    V->spec = 1; V->exp = 0; V->exp_dinv = 0;
-    size_t lv = pick_fwd_lds(*V, H);
-    if (lv > 160 * 1024) return HSCN_E_UNSUPPORTED;
-    // 16-wave workgroups on graphs within StepVCaps: the virtual program with its LDS layout fixed at compile time
-    // (hscn_fwd_body MODE 6: the layout's ~40 offsets are immediates instead of scalar registers -- 90 SGPR spills
-    // become 9); larger graphs / more clusters keep the run-time layout
-    if (S.max_n > 64 && V->max_n <= StepVCaps::N && V->max_v <= StepVCaps::V && V->max_evv <= StepVCaps::EVV &&
-        V->l_begin == 0 && V->l_end == V->L) {
-      const size_t lf = fwd_layout(H, 1, StepVCaps::N, StepVCaps::V, 0, StepVCaps::EVV, 1, 0).total * 4;
-      if (lf <= 160 * 1024) { fixed_layout = true; lv = lf; V->db = 1; }
-    }
-    if (lv > lds) lds = lv;
-    if (S.max_n > 64) {
-      // 16-wave workgroups: one per CU (the acquire-free consumer form is measured for exactly that): ask for more
-      // than half of a CU's LDS
-      if (lds < 81 * 1024) lds = 81 * 1024;
-    } else {
-      V->acq = 1;   // small graphs share CUs: the consumer acquires and uses plain loads (Guideline 16, R1 as written)
-    }
-  }
-  if (S.max_n <= 64) return launch_step_rt<H, 256, TS>(S, V, lds, st);
-  if constexpr (H == 16) {
-    // the headline shape runs ONE fully specialised instantiation: both programs' layouts at compile time
-    if (local_fixed && (fixed_layout || !V))
-      return launch_step_rt<H, 1024, TS, 6, true>(S, V, lds > lds_lfix ? lds : lds_lfix, st);
-  }
-  if (fixed_layout) return launch_step_rt<H, 1024, TS, 6>(S, V, lds, st);
-  return launch_step_rt<H, 1024, TS>(S, V, lds, st);
 }

@@ -81,6 +81,7 @@ _SIGNATURES = {
     "hscn_clip_grad_norm_flat": (c_int, [P, c_int64, c_float, P, P]),
     "hscn_resident_supported": (c_int, [c_int] * 8),
     "hscn_resident_launch_plan": (c_int, [c_int] * 9 + [P]),
+    "hscn_resident_launch_plan_ex": (c_int, [c_int] * 10 + [P]),
     "hscn_resident_param_count": (c_int64, [c_int] * 4),
     "hscn_resident_fwd": (c_int, [P, P, P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64,
                                   c_int64, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, c_int,
@@ -243,19 +244,39 @@ def lib() -> ctypes.CDLL:
 
 
 PLAN_FIELDS = ("threads", "db", "exp", "csr_launch", "two", "fwd_lds", "bwd_lds")      # include/hscn.h: HSCN_PLAN_*
+# hscn_resident_launch_plan_ex: HSCN_LAUNCH_* in this order, and the fields it adds to the seven above
+LAUNCHES = ("pair", "pair_virtual", "step", "step_virtual")
+PLAN_FIELDS_EX = PLAN_FIELDS + ("csr_lds", "v_db", "v_exp", "v_acq", "bwd_v_db", "local_fixed", "virtual_fixed",
+                                "fwd_local_need", "fwd_virtual_need", "bwd_local_need", "bwd_virtual_need")
 
 
 def resident_launch_plan(F: int, H: int, L: int, C: int, max_n: int, max_v: int, max_ell: int, max_evv: int,
-                         want_export: bool = True) -> Optional[dict]:
-    """What hscn_resident_fwd / hscn_resident_bwd choose for these maxima (hscn_resident_launch_plan: host arithmetic,
-    no device needed): {"threads", "db", "exp", "csr_launch", "two", "fwd_lds", "bwd_lds"}, or None where
-    hscn_resident_supported answers 0."""
-    buf = (ctypes.c_int32 * len(PLAN_FIELDS))()
-    rc = lib().hscn_resident_launch_plan(F, H, L, C, max_n, max_v, max_ell, max_evv, int(bool(want_export)), buf)
+                         want_export: bool = True, launch: str = "pair") -> Optional[dict]:
+    """What the graph-resident launches choose for these maxima (host arithmetic, no device needed), or None where
+    the launch shape does not take them.  launch = "pair": hscn_resident_fwd / hscn_resident_bwd through
+    hscn_resident_launch_plan, {"threads", "db", "exp", "csr_launch", "two", "fwd_lds", "bwd_lds"}.  Any other of
+    LAUNCHES ("pair_virtual": the pair with virtual workgroups; "step" / "step_virtual": the one-launch step without /
+    with a virtual job): every field of PLAN_FIELDS_EX through hscn_resident_launch_plan_ex."""
+    if launch == "pair":
+        buf = (ctypes.c_int32 * len(PLAN_FIELDS))()
+        rc = lib().hscn_resident_launch_plan(F, H, L, C, max_n, max_v, max_ell, max_evv, int(bool(want_export)), buf)
+        fields = PLAN_FIELDS
+    else:
+        rc, buf = resident_launch_plan_ex(LAUNCHES.index(launch), F, H, L, C, max_n, max_v, max_ell, max_evv, want_export)
+        fields = PLAN_FIELDS_EX
     if rc == -3:
         return None
     check(rc, "hscn_resident_launch_plan")
-    return dict(zip(PLAN_FIELDS, (int(v) for v in buf)))
+    return dict(zip(fields, (int(v) for v in buf)))
+
+
+def resident_launch_plan_ex(launch: int, F: int, H: int, L: int, C: int, max_n: int, max_v: int, max_ell: int,
+                            max_evv: int, want_export: bool = True):
+    """hscn_resident_launch_plan_ex as it is: (return code, the HSCN_PLAN_EX_COUNT fields; zeros unless the code is 0)."""
+    buf = (ctypes.c_int32 * len(PLAN_FIELDS_EX))()
+    rc = lib().hscn_resident_launch_plan_ex(launch, F, H, L, C, max_n, max_v, max_ell, max_evv, int(bool(want_export)),
+                                            buf)
+    return int(rc), [int(v) for v in buf]
 
 
 def exported_symbols():

@@ -578,7 +578,7 @@ int64_t hscn_resident_param_count(int F, int H, int L, int C);
  * maxima (ABI 24): host arithmetic only, no stream and no launch, through the same functions the launches take
  * them from.  want_export != 0: the forward is asked for the source-keyed CSR (csr_rowptr_t != NULL).  Fills
  * plan_host[HSCN_PLAN_COUNT]; returns 0, HSCN_E_UNSUPPORTED where hscn_resident_supported answers 0, HSCN_E_BADARG
- * for a NULL plan_host.
+ * for a NULL plan_host.  (The first seven fields of hscn_resident_launch_plan_ex(HSCN_LAUNCH_PAIR, ...).)
  *   HSCN_PLAN_THREADS     threads per workgroup of both launches: 256 (max_n <= 64) or 1024
  *   HSCN_PLAN_FWD_DB      1 = the forward keeps two weight buffers in LDS (H <= 32 and they fit)
  *   HSCN_PLAN_FWD_EXP     1 = the forward launch builds and exports the source-keyed CSR itself
@@ -595,6 +595,45 @@ int64_t hscn_resident_param_count(int F, int H, int L, int C);
 #define HSCN_PLAN_COUNT 7
 int hscn_resident_launch_plan(int F, int H, int L, int C, int max_n, int max_v, int max_ell, int max_evv,
                               int want_export, int32_t* plan_host);
+/* The same query over every stage-C launch shape (additive to ABI 24), `launch` one of
+ *   HSCN_LAUNCH_PAIR          hscn_resident_fwd + hscn_resident_bwd
+ *   HSCN_LAUNCH_PAIR_VIRTUAL  hscn_resident_fwd_with_virtual + hscn_resident_bwd_with_virtual (max_v / max_evv: the
+ *                             job's; the forward is taken to be handed a non-NULL ei_ll; L >= 2 is the entry point's
+ *                             own check, not looked at here)
+ *   HSCN_LAUNCH_STEP          hscn_resident_train_step without a job (max_v, max_evv and want_export are ignored)
+ *   HSCN_LAUNCH_STEP_VIRTUAL  hscn_resident_train_step with a job (want_export is ignored)
+ * Fills plan_host[HSCN_PLAN_EX_COUNT] (zeros where the launch shape is refused): the seven fields above, where the forward fields describe the LOCAL workgroup's
+ * argument block and the one-launch step reports its single launch as the forward (HSCN_PLAN_BWD_LDS = 0), then
+ *   HSCN_PLAN_CSR_LDS        dynamic LDS bytes of the light CSR launch (0 without it)
+ *   HSCN_PLAN_V_DB           the virtual workgroup of the forward / of the step keeps two weight buffers
+ *   HSCN_PLAN_V_EXP          1 = the forward's VIRTUAL workgroup builds and exports the source-keyed CSR
+ *   HSCN_PLAN_V_ACQ          1 = the step's virtual workgroup acquires the local activations (4-wave workgroups)
+ *   HSCN_PLAN_BWD_V_DB       the virtual workgroup of the backward keeps two weight buffers
+ *   HSCN_PLAN_LOCAL_FIXED / HSCN_PLAN_VIRTUAL_FIXED   the step's instantiation: 1 = that program takes its LDS layout
+ *                            at compile time (the local one only when the virtual one does too, or there is no job)
+ *   HSCN_PLAN_FWD_LOCAL_NEED / _FWD_VIRTUAL_NEED / _BWD_LOCAL_NEED / _BWD_VIRTUAL_NEED   bytes each workgroup program
+ *                            lays out in LDS for the argument block it is handed (0: no such program in the launch);
+ *                            a launch's LDS is at least both of its programs'.
+ * Returns 0; HSCN_E_UNSUPPORTED where hscn_resident_supported (pair) / hscn_resident_train_step_supported (step, with
+ * max_v = max_evv = 0 when there is no job) answers 0; HSCN_E_BADARG for a NULL plan_host or an unknown launch. */
+#define HSCN_LAUNCH_PAIR 0
+#define HSCN_LAUNCH_PAIR_VIRTUAL 1
+#define HSCN_LAUNCH_STEP 2
+#define HSCN_LAUNCH_STEP_VIRTUAL 3
+#define HSCN_PLAN_CSR_LDS 7
+#define HSCN_PLAN_V_DB 8
+#define HSCN_PLAN_V_EXP 9
+#define HSCN_PLAN_V_ACQ 10
+#define HSCN_PLAN_BWD_V_DB 11
+#define HSCN_PLAN_LOCAL_FIXED 12
+#define HSCN_PLAN_VIRTUAL_FIXED 13
+#define HSCN_PLAN_FWD_LOCAL_NEED 14
+#define HSCN_PLAN_FWD_VIRTUAL_NEED 15
+#define HSCN_PLAN_BWD_LOCAL_NEED 16
+#define HSCN_PLAN_BWD_VIRTUAL_NEED 17
+#define HSCN_PLAN_EX_COUNT 18
+int hscn_resident_launch_plan_ex(int launch, int F, int H, int L, int C, int max_n, int max_v, int max_ell,
+                                 int max_evv, int want_export, int32_t* plan_host);
 int hscn_resident_fwd(const void* x_local, const void* x_virtual, const int64_t* ei_ll, int64_t E_ll,
                       const int64_t* ei_vv, int64_t E_vv, const int64_t* ei_lv, int64_t E_lv,
                       const int32_t* lptr, const int32_t* vptr, const int32_t* eptr_ll, const int32_t* eptr_vv,

@@ -127,3 +127,68 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     import pytest
     with pytest.raises(_hip.HipExtensionMissing):
         _hip.lib()
+
+
+# What the five graph-resident entry points answer to calls that can never launch: every row keeps x_local NULL, so
+# whatever the order of checks, a call that got past all the others is refused for it.  Argument positions by name
+# (include/hscn.h); `job` / `structure`: a zeroed hscn_virtual_job / hscn_structure (_BUF) or NULL.
+_RESIDENT_POS = {
+    "hscn_resident_fwd": dict(B=15, F=16, H=17, L=18, C=19, max_n=27, max_ell=29),
+    "hscn_resident_fwd_with_virtual": dict(B=6, F=7, H=8, L=9, C=10, max_n=17, max_ell=18, job=28),
+    "hscn_resident_bwd": dict(B=6, F=7, H=8, L=9, C=10, max_n=23, max_ell=24),
+    "hscn_resident_bwd_with_virtual": dict(B=6, F=7, H=8, L=9, C=10, max_n=23, max_ell=24, job=29),
+    "hscn_resident_train_step": dict(B=6, F=7, H=8, L=9, C=10, max_n=17, max_ell=18, job=28, structure=29),
+}
+_FITS = dict(F=9, H=16, L=3, C=10, max_n=100, max_ell=200)          # inside every envelope
+
+
+def _job_with_state():
+    """A hscn_virtual_job whose six st_* members point somewhere (the forward with virtual workgroups asks for them)."""
+    from graph_hscn.engine import _VirtualJob
+    job = _VirtualJob()
+    for n in ("st_rowptr_lv", "st_col_lv", "st_rowptr_vv", "st_col_vv", "st_dinv_v", "st_xv"):
+        setattr(job, n, _HERE)
+    return job
+
+
+_JOB = _job_with_state()
+_STATE = ctypes.addressof(_JOB)
+# (row, arguments, flags, the codes of fwd / fwd_with_virtual / bwd / bwd_with_virtual / train_step): recorded from
+# the commit before the launch planners, 0 = nothing to do, -1 = HSCN_E_BADARG, -3 = HSCN_E_UNSUPPORTED
+_REFUSALS = [
+    ("B < 0", dict(_FITS, B=-1, job=_HERE), 0, (-1, -1, -1, -1, -1)),
+    ("B = 0", dict(_FITS, B=0, job=_HERE), 0, (0, 0, 0, 0, 0)),
+    ("B = 0, all widths zero", dict(B=0, job=_HERE), 0, (0, 0, 0, 0, 0)),
+    ("unsupported widths, B > 0", dict(_FITS, H=24, B=2, job=_HERE), 0, (-3, -1, -3, -3, -3)),
+    ("unsupported widths, B > 0, job with state", dict(_FITS, H=24, B=2, job=_STATE), 0, (-3, -3, -3, -3, -3)),
+    ("a graph beyond LDS, B > 0", dict(_FITS, max_n=5000, max_ell=10000, B=2, job=_STATE), 0, (-3, -3, -3, -3, -1)),
+    ("supported widths, B > 0", dict(_FITS, B=2, job=_HERE), 0, (-1, -1, -1, -1, -1)),
+    ("supported widths, B > 0, job with state", dict(_FITS, B=2, job=_STATE), 0, (-1, -1, -1, -1, -1)),
+    ("missing job, B > 0", dict(_FITS, B=2), 0, (-1, -1, -1, -1, -1)),
+    ("missing job, unsupported widths, B > 0", dict(_FITS, H=24, B=2), 0, (-3, -1, -3, -1, -3)),
+    ("missing job, B = 0", dict(_FITS, B=0), 0, (0, -1, 0, -1, 0)),
+    ("L < 2 with a job", dict(_FITS, L=1, B=2, job=_HERE), 0, (-1, -1, -1, -1, -1)),
+    ("L < 2 with a job with state, unsupported widths", dict(_FITS, H=24, L=1, B=2, job=_STATE), 0, (-3, -1, -3, -3, -3)),
+    ("structure with a missing member, B = 0", dict(_FITS, B=0, job=_HERE, structure=_HERE), 0, (0, 0, 0, 0, -1)),
+    ("structure with a missing member, no job, B = 0", dict(_FITS, B=0, structure=_HERE), 0, (0, -1, 0, -1, -1)),
+    ("half storage at H = 64, B > 0", dict(_FITS, H=64, B=2, job=_STATE), _STORE_F16, (-3, -3, -3, -3, -3)),
+    ("half storage at H = 64, B = 0", dict(_FITS, H=64, B=0, job=_STATE), _STORE_F16, (-3, -3, -3, -3, 0)),
+    ("float storage at H = 64, B > 0", dict(_FITS, H=64, B=2, job=_STATE), 0, (-1, -1, -1, -1, -3)),
+]
+
+
+def _refusal_codes(lib, args, flags):
+    out = []
+    for name, pos in _RESIDENT_POS.items():
+        at = {pos[k]: v for k, v in args.items() if k in pos}
+        assert 0 not in at                                                         # x_local stays NULL
+        out.append(_blank_call(lib, name, flags, at))
+    return tuple(out)
+
+
+def test_resident_entry_points_refuse_as_recorded():
+    from graph_hscn import _hip
+    lib = _hip.lib()
+    assert list(_RESIDENT_POS) == [n for n in _FLAGGED if n.startswith("hscn_resident_")]
+    for row, args, flags, codes in _REFUSALS:
+        assert _refusal_codes(lib, args, flags) == codes, row

@@ -44,7 +44,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_step_layouts import run_one_launch, step_bits  # noqa: F401  (the recorder takes them from here)
+from tests.test_gpu_step_layouts import run_one_launch, step_bits, step_variant  # noqa: F401  (the recorder takes them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -56,6 +56,17 @@ BATCHES = {
     "many": ((444, (65, 65, 65, 65, 65, 65, 54)), (320, (64, 128, 128))),
     "small": ((17, (17,)), (64, (17, 17, 15, 15))),
 }
+# What each batch is named for, found with the host query (hscn_resident_launch_plan_ex on the batch's maxima): threads
+# per workgroup; the virtual program's layout at compile time for 16-wave workgroups up to StepVCaps::N = 448 nodes, the
+# local program's beside it at L = 3 (StepLCaps::L; these graphs have at most 942 <= StepLCaps::ELL edges).
+def expected_variant(name, L):
+    if name == "small":
+        return dict(threads=256, local_fixed=0, virtual_fixed=0)
+    if name == "over":
+        return dict(threads=1024, local_fixed=0, virtual_fixed=0)
+    return dict(threads=1024, local_fixed=int(L == 3), virtual_fixed=1)
+
+
 # (batch, L, storage type)
 CASES = [("fixed", 3, "f32"), ("fixed", 2, "f32"), ("fixed", 3, "f16"), ("over", 3, "f32"), ("over", 2, "f32"),
          ("many", 3, "f32"), ("many", 2, "f32"), ("small", 3, "f32")]
@@ -124,6 +135,7 @@ def test_one_launch_step_big_clusters(case):
     pair.run()
     one = run_one_launch(model, d)
     assert one.virtual is not None and one.idle_cus
+    assert step_variant(one) == expected_variant(name, L), "the case runs the layout form it is named for"
     assert torch.equal(one.virtual, pair.virtual)
     assert pool_order_close(one.pred, pair.pred) and pool_order_close(one.score, pair.score)
     assert grads_close(one.grads[:-1], pair.grads[:-1], rel=1e-5) and pool_order_close(one.grads[-1], pair.grads[-1])

@@ -37,6 +37,27 @@ CASES = ([("mixed", L, F, v, "f32") for L in (1, 2, 3) for F in (9, 16) for v in
          + [("over", 3, 9, True, "f32"), ("over", 3, 16, False, "f32"), ("over", 3, 9, True, "f16")])
 
 
+# What each batch is named for, found with the host query (hscn_resident_launch_plan_ex; SIZES' maxima with K = 8 and
+# these graphs' edge counts): threads per workgroup, and whether the local / the virtual program takes its LDS layout at
+# compile time -- the local one at L = 3 only (StepLCaps::L), and with a virtual job only beside a fixed virtual program.
+def expected_variant(name, L, virt):
+    return {"small": dict(threads=256, local_fixed=0, virtual_fixed=0),
+            "mixed": dict(threads=1024, local_fixed=int(L == 3), virtual_fixed=int(virt)),
+            "over": dict(threads=1024, local_fixed=0, virtual_fixed=0)}[name]
+
+
+def step_variant(one):
+    """The instantiation ``one``'s launch takes, asked of the library for the batch's maxima."""
+    from graph_hscn import _hip
+    N, V, F, H, L, C, B = one.dims
+    m = one.meta
+    with_job = bool(one.idle_cus and one.virtual is not None)
+    plan = _hip.resident_launch_plan(F, H, L, C, m.max_n, m.max_v, m.max_ell, m.max_evv,
+                                     launch="step_virtual" if with_job else "step")
+    assert plan is not None, "the one-launch step takes this batch"
+    return {k: plan[k] for k in ("threads", "local_fixed", "virtual_fixed")}
+
+
 def case_id(case):
     b, L, F, v, dt = case
     return f"{b}_L{L}_F{F}_{'virt' if v else 'novirt'}_{dt}"
@@ -115,6 +136,7 @@ def test_one_launch_step_layout_forms(case):
     pair.run()
     one = run_one_launch(model, d)
     assert (one.virtual is not None) == virt
+    assert step_variant(one) == expected_variant(name, L, virt), "the case runs the layout form it is named for"
     if virt:
         assert one.idle_cus                                   # the virtual branch rides on its own workgroups
         assert torch.equal(one.virtual, pair.virtual)

@@ -117,3 +117,98 @@ def test_dropping_the_export_frees_forward_lds():
                 assert b["fwd_lds"] <= a["fwd_lds"], (n, v, ell, evv)
             hit += a["csr_launch"]
     assert hit, "some shape takes the separate CSR launch"
+
+
+# --------------------------------------------------------------------------- #
+# hscn_resident_launch_plan_ex: the same query over every stage-C launch shape
+# --------------------------------------------------------------------------- #
+def _recorder():
+    import os
+    import sys
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import record_resident_plans
+    return record_resident_plans
+
+
+def _recorded():
+    import os
+
+    import numpy as np
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resident_launch_plans.npz")) as f:
+        return f["rows"], [str(c) for c in f["columns"]]
+
+
+def test_query_reproduces_the_recorded_launches():
+    """tests/golden/resident_launch_plans.npz: what the launch functions of the commit before the planners did (template
+    arguments, threads, LDS, the argument blocks' choice fields, read off their launch sites) -- row for row."""
+    from graph_hscn import _hip
+    R = _recorder()
+    want, columns = _recorded()
+    assert columns == list(R.columns())
+    got = R.rows(_hip.resident_launch_plan_ex)
+    assert got.shape == want.shape and got.dtype == want.dtype
+    differ = (got != want).any(axis=1).nonzero()[0]
+    assert differ.size == 0, [(want[i].tolist(), got[i].tolist()) for i in differ[:5]]
+
+
+def test_selector_pair_rows_are_the_launch_plan():
+    from graph_hscn import _hip
+    lib = _hip.lib()
+    buf = (ctypes.c_int32 * len(_hip.PLAN_FIELDS))()
+    seen = set()
+    for F, H, L, C in WIDTHS:
+        for n, v, ell, evv in _shapes():
+            for want in (0, 1):
+                for i in range(len(buf)):
+                    buf[i] = -7
+                rc = lib.hscn_resident_launch_plan(F, H, L, C, n, v, ell, evv, want, buf)
+                rc_ex, ex = _hip.resident_launch_plan_ex(_hip.LAUNCHES.index("pair"), F, H, L, C, n, v, ell, evv, want)
+                assert rc == rc_ex and rc in (0, -3), (F, H, L, C, n, v, ell, evv, want)
+                seen.add(rc)
+                # the projection: the first seven fields; a refusal leaves the caller's buffer alone
+                assert list(buf) == (ex[:len(buf)] if rc == 0 else [-7] * len(buf)), (F, H, L, C, n, v, ell, evv, want)
+    assert seen == {0, -3}
+    assert _hip.resident_launch_plan_ex(4, 9, 16, 3, 10, 100, 8, 200, 36)[0] == -1          # unknown launch
+    assert _hip.resident_launch_plan_ex(-1, 9, 16, 3, 10, 100, 8, 200, 36)[0] == -1
+    assert lib.hscn_resident_launch_plan_ex(0, 9, 16, 3, 10, 100, 8, 200, 36, 1, None) == -1
+
+
+def test_launch_lds_covers_both_programs_and_fits_a_cu():
+    """Every supported row: a launch's LDS is at least what each of its workgroup programs lays out for the argument
+    block it is handed (the *_need fields: the kernels' own layout functions on the planned blocks), and at most a
+    CU's 160 KB.  The needs themselves are tied to the plain pair's LDS where the blocks coincide."""
+    from graph_hscn import _hip
+    rows, columns = _recorded()
+    ci = {c: i for i, c in enumerate(columns)}
+    n_ok = 0
+    for row in rows:
+        r = {c: int(row[ci[c]]) for c in columns}
+        if r["rc"] != 0:
+            assert r["rc"] == -3 and not any(row[ci["rc"] + 1:]), r
+            continue
+        n_ok += 1
+        assert 0 < r["fwd_local_need"] <= r["fwd_lds"] <= 160 * 1024, r
+        assert 0 <= r["fwd_virtual_need"] <= r["fwd_lds"], r
+        assert 0 <= r["bwd_local_need"] <= r["bwd_lds"] <= 160 * 1024 and 0 <= r["bwd_virtual_need"] <= r["bwd_lds"], r
+        assert 0 <= r["csr_lds"] <= 160 * 1024 and (r["csr_lds"] > 0) == (r["csr_launch"] == 1), r
+        launch = _hip.LAUNCHES[r["launch"]]
+        virtual = launch in ("pair_virtual", "step_virtual")
+        assert (r["fwd_virtual_need"] > 0) == virtual and (r["bwd_virtual_need"] > 0) == (launch == "pair_virtual"), r
+        assert (r["bwd_lds"] > 0) == (r["bwd_local_need"] > 0) == launch.startswith("pair"), r
+        if launch == "pair":
+            assert r["fwd_local_need"] == r["fwd_lds"] and r["bwd_local_need"] == r["bwd_lds"], r
+        if launch == "pair_virtual":
+            # the export happens in exactly one place when it is wanted, nowhere when it is not
+            assert r["exp"] + r["v_exp"] + r["csr_launch"] == r["want_export"], r
+            # the local block is the plain forward's at the same export choice; the backward is the plain backward
+            shape = (r["F"], r["H"], r["L"], r["C"], r["max_n"], r["max_v"], r["max_ell"], r["max_evv"])
+            p = _hip.resident_launch_plan(*shape, bool(r["exp"]))
+            assert (p["db"], p["exp"], p["fwd_lds"]) == (r["db"], r["exp"], r["fwd_local_need"]), (r, p)
+            assert (p["two"], p["bwd_lds"]) == (r["two"], r["bwd_local_need"]), (r, p)
+        if launch.startswith("step"):
+            assert r["local_fixed"] <= (r["virtual_fixed"] if virtual else 1), r
+            assert r["threads"] == 1024 or not (r["local_fixed"] or r["virtual_fixed"]), r
+            assert r["v_acq"] == (1 if virtual and r["threads"] == 256 else 0), r
+    assert n_ok > 1000
