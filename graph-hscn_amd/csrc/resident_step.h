@@ -229,8 +229,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     const bool ok = idx < n * H && k < F;
     xr[i] = 0.f;
     if (wbase + i * RT < n * H) {
-      const float t = ldf(xl_g, ok ? (size_t)(n0 + r) * F + k : 0);
-      xr[i] = ok ? t : 0.f;
+      xr[i] = ldf(xl_g, ok ? (size_t)(n0 + r) * F + k : 0);   // (raw: the padding is applied where the word is parked)
     }
   }
   // all layers' local->local weights, transposed on the way in: slot d = l*WL + k*H + o  <-  W_l[o][k]; bias behind
@@ -249,8 +248,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       const int k = q / H, o = q - k * H;
       const bool ok = inb && (isb || k < fin);
       const float* src = isb ? A.b_ll[ll] + (q - H * H) : A.W_ll[ll] + (ok ? o * fin + k : 0);
-      const float t = *(ok ? src : A.b_ll[0]);
-      wr[i] = ok ? t : 0.f;
+      wr[i] = *(ok ? src : A.b_ll[0]);   // (raw, as the features)
     }
   }
   // head weights W1 [H][H] | b1 [H] | W2 [C][H] | b2 [C] (natural layout), then this graph's target row
@@ -269,7 +267,10 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   const int HTT = HT + C;
   float hw0 = *haddr((int)threadIdx.x < HTT ? (int)threadIdx.x : 0);
   float hw1 = *haddr((int)threadIdx.x + RT < HTT ? (int)threadIdx.x + RT : 0);
-  // ---- consume: validate + stage the edges, park features and weights -------------------------------------
+  // ---- consume: validate + stage the edges ONLY.  Features, weights and head stay in registers over the structure
+  // build -- nothing computes on them before (a select on a loaded word would put its wait here) -- and are parked
+  // behind it (park_inputs, as hscn_fwd_body does): the build starts when the edges have arrived, not when the
+  // last prologue byte has.  None of their LDS words is touched by a build. ----------------------------------
   if (pre) {
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -308,12 +309,12 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   }
   for (int i = threadIdx.x; i <= n; i += RT) { (ib + Y.cntA)[i] = 0; (ib + Y.cntT)[i] = 0; }
   if (threadIdx.x == 0) { (ib + Y.wsum)[0] = 0; (ib + Y.wsum)[1] = 0; (ib + Y.ovf)[0] = 0; }   // fold sign-offs (H = 16 backward), export sign-offs
-  {
+  auto park_inputs = [&]() {
     float* x0 = buf(0);
 #pragma unroll
     for (int i = 0; i < XPT; ++i) {
       const int idx = threadIdx.x + i * RT;
-      if (idx < n * H) x0[idx] = xr[i];
+      if (idx < n * H) x0[idx] = idx % H < F ? xr[i] : 0.f;
     }
     for (int idx = threadIdx.x + XPT * RT; idx < n * H; idx += RT) {
       const int r = idx / H, k = idx - r * H;
@@ -322,7 +323,8 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
 #pragma unroll
     for (int i = 0; i < WPT; ++i) {
       const int d = threadIdx.x + i * RT;
-      if (d < WTOT) wt[d] = wr[i];
+      const int l = d / WL, q = d - l * WL;
+      if (d < WTOT) wt[d] = (q >= H * H || q / H < (l == 0 ? F : H)) ? wr[i] : 0.f;
     }
     for (int d = threadIdx.x + WPT * RT; d < WTOT; d += RT) {
       const int l = d / WL, q = d - l * WL;
@@ -333,7 +335,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     if ((int)threadIdx.x < HTT) headw[threadIdx.x] = hw0;
     if ((int)threadIdx.x + RT < HTT) headw[threadIdx.x + RT] = hw1;
     for (int idx = threadIdx.x + 2 * RT; idx < HTT; idx += RT) headw[idx] = *haddr(idx);
-  }
+  };
   lds_barrier();
   STAMP(1);
   // ---- structure: the two CSRs of the local->local relation side by side (four barriers each) -------------
@@ -370,6 +372,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       }
     }
   }
+  park_inputs();
   lds_barrier();
   STAMP(3);
   // ---- forward layers: A[l] -> A[l + 1], one barrier each ----------------------------------------------------
@@ -450,7 +453,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     raise(L - 1);
   }
   STAMP(12);
-  // ---- head + this graph's row of the loss tail (wave 0) ---------------------------------------------------
+  // ---- head (wave 0) + this graph's row of the loss tail (wave LW on the fast path) --------------------------
   float* aL = buf(L);
   float* pol = vec;          // pooled
   float* zz = vec + 64;      // z = act(lin_1(pooled))
@@ -468,10 +471,16 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   // waves' pool partials, a row and a column of W1 and of W2 per lane, biases, the target row) is requested in one
   // batch, and a vector element crosses lanes through a DPP row broadcast (one VALU operation), not through an LDS
   // round trip with a wavefront fence on either side.  Same fmaf chains in the same order as the general path below.
+  // The fast head runs on TWO waves.  Wave 0 computes only what the backward waits for (pool -> z -> pred -> d loss /
+  // d pred -> gz -> gpool / gpn); wave LW recomputes pool -> z -> pred through the same row_dot chains and the same
+  // criterion_elem -- the same bits -- and owns what the gradient chain never reads: the pred / score stores, the
+  // loss terms (log1p(exp(-|x|))), their ordered sum and the loss column.  (LW: a compute wave that owns one row tile
+  // of the last forward layer where the first waves own two; a one-wave workgroup does both on its only wave.)
   const bool fast_head = H == 16 && C <= 16;
-  if (threadIdx.x < 64) {
+  constexpr int LW = NW > 2 ? NW - 3 : NW - 1;
+  auto head_fast = [&](auto GRAD, auto LOSS) {
     const float cnt = (float)(n > 0 ? n : 1);
-    if (fast_head) {
+    {
       constexpr int HH = H <= 16 ? H : 16;
       const bool lh = lane < HH, lc = lane < C;
       const int lk = lh ? lane : 0, lcc = lc ? lane : 0;
@@ -485,10 +494,12 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
         const float4 b = *reinterpret_cast<const float4*>(W2l + lcc * H + 4 * k4);
         w2r[4 * k4] = b.x; w2r[4 * k4 + 1] = b.y; w2r[4 * k4 + 2] = b.z; w2r[4 * k4 + 3] = b.w;
       }
+      if constexpr (decltype(GRAD)::value) {
 #pragma unroll
-      for (int o = 0; o < HH; ++o) w1c[o] = W1l[o * H + lk];
+        for (int o = 0; o < HH; ++o) w1c[o] = W1l[o * H + lk];
 #pragma unroll
-      for (int c = 0; c < 16; ++c) w2c[c] = c < C ? W2l[c * H + lk] : 0.f;
+        for (int c = 0; c < 16; ++c) w2c[c] = c < C ? W2l[c * H + lk] : 0.f;
+      }
       const float bb1 = b1l[lk], bb2 = b2l[lcc], tgt = tgl[lcc];
       float s = 0.f;
 #pragma unroll
@@ -498,19 +509,33 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       const float pc = row_dot<HH>(zv, w2r, 0.f) + bb2;               // lane c: pred[c]
       float lt, sg, gg;
       criterion_elem(A.loss_kind, pc, tgt, A.inv_count, lt, sg, gg);   // same element code as k_criterion
-      if (lc) {
-        A.pred[(size_t)g * C + lane] = pc;
-        if (A.score) A.score[(size_t)g * C + lane] = sg;             // (= 1 / (1 + exp(-pred)), criterion_elem's)
+      if constexpr (decltype(LOSS)::value) {
+        if (lc) {
+          A.pred[(size_t)g * C + lane] = pc;
+          if (A.score) A.score[(size_t)g * C + lane] = sg;           // (= 1 / (1 + exp(-pred)), criterion_elem's)
+        }
+        lt = lc ? lt : 0.f;                                           // (lanes past C: exact zeros in the sum below)
+        const float sl = row_seq_sum<16>(lt, 0.f);                    // loss terms in class order
+        if (lane == 0) part[A.Pn] = sl;
       }
-      lt = lc ? lt : 0.f;                                             // (lanes past C: exact zeros in the sums below)
-      gg = lc ? gg : 0.f;
-      const float sl = row_seq_sum<16>(lt, 0.f);                      // loss terms in class order
-      const float gzv = row_dot<16>(gg, w2c, 0.f) * act_grad_from_output(zv, A.head_act);   // lane o
-      const float gpa = row_dot<HH>(gzv, w1c, 0.f);                   // lane k: d loss / d pooled[k]
-      if (lh) { pol[lane] = polv; zz[lane] = zv; gz[lane] = gzv; gpool[lane] = gpa; gpn[lane] = gpa / cnt; }
-      if (lc) gpl[lane] = gg;
-      if (lane == 0) part[A.Pn] = sl;
-    } else {
+      if constexpr (decltype(GRAD)::value) {
+        gg = lc ? gg : 0.f;
+        const float gzv = row_dot<16>(gg, w2c, 0.f) * act_grad_from_output(zv, A.head_act);   // lane o
+        const float gpa = row_dot<HH>(gzv, w1c, 0.f);                 // lane k: d loss / d pooled[k]
+        if (lh) { pol[lane] = polv; zz[lane] = zv; gz[lane] = gzv; gpool[lane] = gpa; gpn[lane] = gpa / cnt; }
+        if (lc) gpl[lane] = gg;
+      }
+    }
+  };
+  typedef std::integral_constant<bool, true> HeadOn;
+  typedef std::integral_constant<bool, false> HeadOff;
+  if (fast_head) {
+    if (NW == 1) { head_fast(HeadOn{}, HeadOn{}); }
+    else if (wave == 0) head_fast(HeadOn{}, HeadOff{});
+    else if (wave == LW) head_fast(HeadOff{}, HeadOn{});
+  } else if (threadIdx.x < 64) {
+    const float cnt = (float)(n > 0 ? n : 1);
+    {
     if (lane < H) {
       float s = 0.f;
 #pragma unroll

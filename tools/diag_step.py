@@ -59,7 +59,7 @@ def main():
         names[4 + l] = f"fwd L{l - 1} (+ publish)" if l else "(-)"
         keys.append(4 + l)
     names[12] = f"fwd L{Lyr - 1}"
-    names[13] = "head + loss row (wave 0)"
+    names[13] = "head + loss row"
     names[14] = "head bwd + mask"
     keys += [12, 13, 14]
     for l in range(Lyr - 1, -1, -1):          # H = 16: one phase per backward layer
