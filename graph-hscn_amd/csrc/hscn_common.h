@@ -20,6 +20,29 @@ static inline unsigned hscn_blocks(int64_t work, int per_block) {
   return (unsigned)(b < 1 ? 1 : b);
 }
 
+// LDS of a gfx950 CU, the most one workgroup can be given; and the LDS (static + dynamic) a kernel gets without asking
+constexpr size_t LDS_CU_BYTES = 160 * 1024;
+constexpr size_t LDS_NO_OPT_IN_BYTES = 64 * 1024;
+
+// One launch with `lds` bytes of dynamic LDS, for every kernel that can need more than a launch gets unasked: the
+// opt-in, the launch, the error check.  STATIC_LDS is what the kernel declares as __shared__ arrays of its own; it
+// counts towards the line but not into the request.  The attribute is requested on EVERY call that needs it: it belongs
+// to the current device's copy of the kernel, so nothing here remembers an earlier request.  A refused request is
+// answered here (HSCN_E_UNSUPPORTED, nothing launched), not by the launch that would follow; callers keep `lds` +
+// STATIC_LDS within LDS_CU_BYTES, which gfx950 grants.
+template <size_t STATIC_LDS = 0, typename... KA, typename... A>
+static int launch_with_lds(void (*kernel)(KA...), unsigned grid, int threads, size_t lds, hipStream_t st,
+                           const A&... args) {
+  if (lds + STATIC_LDS > LDS_NO_OPT_IN_BYTES &&
+      hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return HSCN_E_UNSUPPORTED;
+  }
+  kernel<<<grid, threads, lds, st>>>(args...);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
 // Separately rounded multiply / add: the CPU reference accumulates messages as
 // round(w*x) followed by round(acc + .) (torch index_add_), never a fused fma.
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }

@@ -42,7 +42,6 @@ constexpr int LE_MAX_N = 512;
 constexpr int LE_MAX_FREQS = 64;
 constexpr int LE_SWEEP_CAP = 30;
 constexpr double LE_TOL2 = 1e-15;              // off^2 <= LE_TOL2 * fro^2
-constexpr size_t LE_LDS_BYTES = 160 * 1024;
 constexpr int LE_FLAG_CAP = 1, LE_FLAG_EDGE = 2, LE_FLAG_GRAPH = 4;
 
 struct LeScratch {
@@ -59,7 +58,7 @@ __host__ __device__ inline size_t le_matrix_floats(int n) { return (size_t)le_ev
 
 int le_lds_max_n() {
   int n = 0;
-  while (n < LE_MAX_N && 2 * le_matrix_floats(n + 1) * 4 + sizeof(LeScratch) <= LE_LDS_BYTES) ++n;
+  while (n < LE_MAX_N && 2 * le_matrix_floats(n + 1) * 4 + sizeof(LeScratch) <= LDS_CU_BYTES) ++n;
   return n;
 }
 
@@ -331,12 +330,8 @@ int hscn_lap_eig_stats(const int64_t* edge_index, int64_t E, const int32_t* nptr
                  ? reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + need) : nullptr;
   const int n_lds = max_n < a.lds_max_n ? max_n : a.lds_max_n;
   const size_t lds = 2 * le_matrix_floats(n_lds) * sizeof(float);
-  if (lds + sizeof(LeScratch) > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_lap_eig_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int threads = max_n <= 64 ? 256 : 1024;
-  k_lap_eig_stats<<<(unsigned)B, threads, lds, hscn_stream(stream_)>>>(a);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  return launch_with_lds<sizeof(LeScratch)>(k_lap_eig_stats, (unsigned)B, threads, lds, hscn_stream(stream_), a);
 }
 
 }  // extern "C"

@@ -294,25 +294,15 @@ int hscn_linear_fwd(const float* x, const float* W, const float* bias, const flo
   if (LPR > LIN_THREADS) return HSCN_E_UNSUPPORTED;
   const int RPB = LIN_THREADS / LPR;
   size_t lds = (size_t)I * O * 4 * (x2 ? 2 : 1);
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
+  if (lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
   bool fuse_att = att && is_pow2(LPR) && LPR <= 64;
   if (att && !fuse_att && (bias || act != HSCN_ACT_IDENTITY || x2)) return HSCN_E_UNSUPPORTED;
   int64_t nb = (rows + RPB - 1) / RPB;
   if (nb > 2048) nb = 2048;
-  if (VEC == 4) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_linear<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_linear<4><<<(unsigned)nb, LIN_THREADS, lds, st>>>(x, W, bias, x2, W2, fuse_att ? att : nullptr,
-                                                         fuse_att ? a_out : nullptr, y, rows, I, O, w_layout,
-                                                         act, LPR, RPB);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_linear<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_linear<1><<<(unsigned)nb, LIN_THREADS, lds, st>>>(x, W, bias, x2, W2, fuse_att ? att : nullptr,
-                                                         fuse_att ? a_out : nullptr, y, rows, I, O, w_layout,
-                                                         act, LPR, RPB);
-  }
-  HSCN_RETURN_IF_LAUNCH_FAILED();
+  if (int rc = launch_with_lds(VEC == 4 ? k_linear<4> : k_linear<1>, (unsigned)nb, LIN_THREADS, lds, st, x, W, bias, x2,
+                               W2, fuse_att ? att : nullptr, fuse_att ? a_out : nullptr, y, rows, I, O, w_layout, act,
+                               LPR, RPB))
+    return rc;
   if (att && !fuse_att) {
     k_rowdot<<<hscn_blocks(rows, 256), 256, 0, st>>>(y, att, a_out, rows, O);
     HSCN_RETURN_IF_LAUNCH_FAILED();

@@ -27,6 +27,7 @@ namespace {
 
 constexpr int MT = 1024;                       // threads of a class workgroup
 constexpr int64_t AP_LDS_ROWS = 16384;         // keys that stay in LDS
+constexpr size_t AP_STATIC_LDS = 2 * MT * sizeof(int) + MT * sizeof(double);   // k_ap_class's ibuf and dbuf: 16 KB
 constexpr size_t AP_WS_HEAD = 256;             // workspace: per-class NaN-score words in front of the keys
 constexpr uint64_t KEY_NONE = ~0ull;
 
@@ -320,15 +321,14 @@ int hscn_average_precision(const float* y_true, const float* y_score, int64_t G,
   int32_t* nan_score = static_cast<int32_t*>(workspace);
   uint64_t* ws_keys = reinterpret_cast<uint64_t*>(static_cast<char*>(workspace) + head);
   hipStream_t st = hscn_stream(stream_);
-  if (n2 <= AP_LDS_ROWS) {
-    const size_t lds = (size_t)n2 * 8;
-    if (lds > 32 * 1024)         // (with the 16 KB of static scratch: beyond the 64 KB a launch gets unasked)
-      (void)hipFuncSetAttribute((const void*)k_ap_class<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_ap_class<true><<<(unsigned)C, MT, lds, st>>>(y_true, y_score, G, C, n2, ap, valid, nan_score, nullptr);
+  if (n2 <= AP_LDS_ROWS) {   // the keys (a power of two of them, 128 KB at the most) beside the kernel's static scratch
+    if (int rc = launch_with_lds<AP_STATIC_LDS>(k_ap_class<true>, (unsigned)C, MT, (size_t)n2 * 8, st, y_true, y_score,
+                                                G, C, n2, ap, valid, nan_score, nullptr))
+      return rc;
   } else {
     k_ap_class<false><<<(unsigned)C, MT, 0, st>>>(y_true, y_score, G, C, n2, ap, valid, nan_score, ws_keys);
+    HSCN_RETURN_IF_LAUNCH_FAILED();
   }
-  HSCN_RETURN_IF_LAUNCH_FAILED();
   k_ap_finish<<<1, 64, 0, st>>>(ap, valid, nan_score, C, result, flags);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;

@@ -231,11 +231,10 @@ int hscn_mincut_sparse_fwd(const float* logits, const float* x, const int32_t* r
     HSCN_RETURN_IF_LAUNCH_FAILED();
   }
   size_t lds = (size_t)(2 * K * K + K * Fx + 2 * MC_T * K + MC_T * Fx + MC_T + 2 * K + 4) * 4;
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_mincut_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_mincut_stats<<<(unsigned)num_graphs, MC_THREADS, lds, st>>>(S, x, rowptr, col, node_ptr, stats, ss,
-                                                                pooled_x, pooled_adj, K, Fx);
+  if (lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  if (int rc = launch_with_lds(k_mincut_stats, (unsigned)num_graphs, MC_THREADS, lds, st, S, x, rowptr, col, node_ptr,
+                               stats, ss, pooled_x, pooled_adj, K, Fx))
+    return rc;
   k_mincut_losses<<<1, 64, 0, st>>>(stats, losses, (int)num_graphs);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
@@ -249,13 +248,9 @@ int hscn_mincut_sparse_bwd(const float* S, const float* stats, const float* ss, 
   if (!S || !stats || !ss || !rowptr || !col || !rowptr_t || !col_t || !node_ptr || !g_losses || !g_logits)
     return HSCN_E_BADARG;
   size_t lds = (size_t)(K * K + 2 * MC_T * K + 4) * 4;
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_mincut_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_mincut_bwd<<<(unsigned)num_graphs, MC_THREADS, lds, hscn_stream(stream_)>>>(
-      S, stats, ss, rowptr, col, rowptr_t, col_t, node_ptr, g_losses, g_logits, K, (int)num_graphs);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  if (lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  return launch_with_lds(k_mincut_bwd, (unsigned)num_graphs, MC_THREADS, lds, hscn_stream(stream_), S, stats, ss, rowptr,
+                         col, rowptr_t, col_t, node_ptr, g_losses, g_logits, K, (int)num_graphs);
 }
 
 }  // extern "C"

@@ -277,23 +277,12 @@ int hscn_node_head_bwd(const float* x, const float* W1, const float* b1, const f
   const int G = nh_bwd_wgs(N);
   const size_t lds = nh_bwd_lds(H, C);            // at most 33 KB + 64 KB
   float* partial = static_cast<float*>(workspace);
-  // (the LDS opt-in belongs to the current device's copy of the kernel, so it is asked for on every call that needs
-  // it rather than once per process; a refusal is answered here, not by the launch that would follow)
-#define HSCN_NH_BWD(H_)                                                                                              \
-  do {                                                                                                               \
-    if (lds > 64 * 1024 &&                                                                                           \
-        hipFuncSetAttribute((const void*)k_node_head_bwd<H_>, hipFuncAttributeMaxDynamicSharedMemorySize,            \
-                            (int)lds) != hipSuccess) {                                                               \
-      (void)hipGetLastError();                                                                                       \
-      return HSCN_E_UNSUPPORTED;                                                                                     \
-    }                                                                                                                \
-    k_node_head_bwd<H_><<<G, NH_THREADS, lds, st>>>(x, W1, b1, W2, b2, g_pred, scale, N, C, act, g_x, partial);      \
-  } while (0)
-  if (H == 16) HSCN_NH_BWD(16);
-  else if (H == 32) HSCN_NH_BWD(32);
-  else HSCN_NH_BWD(64);
-#undef HSCN_NH_BWD
-  HSCN_RETURN_IF_LAUNCH_FAILED();
+  auto k = k_node_head_bwd<16>;
+  if (H == 32) k = k_node_head_bwd<32>;
+  else if (H == 64) k = k_node_head_bwd<64>;
+  if (int rc = launch_with_lds(k, (unsigned)G, NH_THREADS, lds, st, x, W1, b1, W2, b2, g_pred, scale, N, C, act, g_x,
+                               partial))
+    return rc;
   k_node_head_fold<<<1, NH_FOLD_THREADS, 0, st>>>(partial, G, H, C, gW1, gb1, gW2, gb2, accumulate);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;

@@ -6,10 +6,6 @@
 
 namespace {
 
-// LDS of a gfx950 CU, the most one workgroup can be given; and the dynamic LDS a kernel gets without asking
-constexpr size_t LDS_CU_BYTES = 160 * 1024;
-constexpr size_t LDS_NO_OPT_IN_BYTES = 64 * 1024;
-
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // ---- storage type of node features and inter-layer activations in HBM: float, or IEEE half (BASELINE.json
@@ -600,18 +596,6 @@ inline void launch_param_fold(const float* partials, float* grads, int B, int P,
     k_param_reduce_acc<<<hscn_blocks(P, 32), 256, 0, st>>>(partials, grads, B, P, p_scaled, scale, epoch);
   else
     k_param_reduce<<<hscn_blocks(P, 32), 256, 0, st>>>(partials, grads, B, P, p_scaled, scale, epoch);
-}
-
-// One launch with `lds` bytes of dynamic LDS: the opt-in above 64 KB, the launch, the error check.  The attribute is
-// requested on EVERY call that needs it: it belongs to the current device's copy of the kernel (node_head.hip), so
-// nothing here remembers an earlier request.
-template <typename... KA, typename... A>
-int launch_with_lds(void (*kernel)(KA...), unsigned grid, int threads, size_t lds, hipStream_t st, const A&... args) {
-  if (lds > LDS_NO_OPT_IN_BYTES)
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  kernel<<<grid, threads, lds, st>>>(args...);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
 }
 
 }  // namespace

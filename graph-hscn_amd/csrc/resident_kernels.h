@@ -2252,7 +2252,7 @@ inline int plan_step(const StepArgs& S, FwdArgs* V, int H, LaunchPlan& P) {
   return 0;
 }
 
-// ---- the launches: plan, dispatch on threads / variant, launch (launch_with_lds: resident_common.h) ----
+// ---- the launches: plan, dispatch on threads / variant, launch (launch_with_lds: hscn_common.h) ----
 // the hidden width as a template argument (f(std::integral_constant<int, H>{})), for the widths storage type TS is
 // instantiated at
 template <typename TS, typename F>

@@ -322,12 +322,8 @@ __global__ void __launch_bounds__(MPNN_RT) k_mpnn_step(const MpnnArgs A) {
 template <int H, bool TRAIN>
 int launch_mpnn(const MpnnArgs& A, int64_t B, hipStream_t st) {
   const size_t lds = mpnn_lds_bytes(H, A.L, A.max_n, A.max_ell);
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_mpnn_step<H, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_mpnn_step<H, TRAIN><<<(unsigned)B, MPNN_RT, lds, st>>>(A);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  if (lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  return launch_with_lds(k_mpnn_step<H, TRAIN>, (unsigned)B, MPNN_RT, lds, st, A);
 }
 
 int fill_mpnn_args(MpnnArgs& A, const float* x, const int64_t* edge_index, int64_t E, const int32_t* ptr32,
@@ -342,7 +338,7 @@ extern "C" {
 int hscn_mpnn_supported(int F, int H, int L, int C, int max_n, int max_ell) {
   if (!(H == 16 || H == 32) || F < 1 || F > H || L < 2 || L > MPNN_MAXL || C < 1 || C > H || C > 16) return 0;
   if (max_n < 0 || max_ell < 0 || max_n > (1 << 20) || max_ell > (1 << 22)) return 0;
-  return mpnn_lds_bytes(H, L, max_n, max_ell) <= 160 * 1024 ? 1 : 0;
+  return mpnn_lds_bytes(H, L, max_n, max_ell) <= LDS_CU_BYTES ? 1 : 0;
 }
 
 int64_t hscn_mpnn_param_count(int F, int H, int L, int C) {

@@ -18,6 +18,7 @@
 // add_remaining_self_loops does for unit weights.
 // Ordered reductions only; per-graph parameter-gradient partials + one ordered fold.
 #include <cstdlib>
+#include <type_traits>
 #include "hscn_common.h"
 #include "resident_common.h"
 
@@ -69,12 +70,16 @@ struct ScnArgs {
 typedef const __attribute__((address_space(4))) ScnArgs* ScnArgsK;
 __device__ __forceinline__ ScnArgsK late_args() { return late_args<ScnArgs>(0); }
 
+// the launch a layout is for: the forward, the backward, or both in one (the one-launch step and the persistent epoch)
+enum ScnMode : int { SCN_FWD = 0, SCN_BWD = 1, SCN_STEP = 2 };
+
 struct ScnLayout {
   size_t R1, R2, R3, dinv, dout, wt, red, vecs, rowptr_d, col_d, rowptr_s, col_s, cursor, tmp, cursor2, tmp2, wsum, ek,
       eo, ssl, total;
 };
 // R1: x | agg  (2 * n * FP), later S (n * K) in the forward; R2: y (n * H); R3 (backward): dS / dlogits (n * K)
-__host__ __device__ inline ScnLayout scn_layout(int H, int K, int max_n, int max_e, int bwd) {
+__host__ __device__ inline ScnLayout scn_layout(int H, int K, int max_n, int max_e, ScnMode mode) {
+  const bool back = mode != SCN_FWD;   // the launch has a backward half
   ScnLayout Y;
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
@@ -84,19 +89,19 @@ __host__ __device__ inline ScnLayout scn_layout(int H, int K, int max_n, int max
   // they take over are dead, so a Peptides graph of 444 nodes fits (x, agg AND S resident did not).
   constexpr size_t GSCR = 4096;
   const int KF = K > FP ? K : FP;
-  const size_t xa = (size_t)2 * max_n * FP, sk0 = (size_t)max_n * (bwd ? KF : K), sk = (bwd && sk0 < GSCR) ? GSCR : sk0;
+  const size_t xa = (size_t)2 * max_n * FP, sk0 = (size_t)max_n * (back ? KF : K), sk = (back && sk0 < GSCR) ? GSCR : sk0;
   const size_t sks = (size_t)max_n * K + GSCR;          // the one-launch step: S and, behind it, the tile scratch of S^T S
   // (forward launch: the per-wave S^T S tiles of scn_softmax are parked behind S as well when K <= 16)
-  const size_t r1f = (xa > sk ? xa : sk), r1s = (K <= 16 || bwd == 2) ? (r1f > sks ? r1f : sks) : r1f;
-  Y.R1 = take(bwd == 1 ? sk : r1s);
+  const size_t r1f = (xa > sk ? xa : sk), r1s = (K <= 16 || mode == SCN_STEP) ? (r1f > sks ? r1f : sks) : r1f;
+  Y.R1 = take(mode == SCN_BWD ? sk : r1s);
   const size_t st = (size_t)2 * (((size_t)max_e + 3) / 4 * 4);
-  const size_t yh0 = (size_t)max_n * H, yh = (!bwd && yh0 < GSCR) ? GSCR : yh0;
+  const size_t yh0 = (size_t)max_n * H, yh = (!back && yh0 < GSCR) ? GSCR : yh0;
   const size_t bs = (size_t)2 * (max_n + 1) + (size_t)2 * max_e + 16;   // the CSR builders' scratch (step: inside R3)
   Y.R2 = take(yh > st ? yh : st);                      // y; the staged COO slice overlays it first
   Y.ek = Y.R2;
   Y.eo = Y.R2 + ((size_t)max_e + 3) / 4 * 4;
-  size_t r3 = bwd == 2 ? (sk > bs ? sk : bs) : bwd ? sk : 0;
-  if (bwd == 2) {   // S | y | dlogits (contiguous) later hold the 16 waves' gradient partials of scn_bwd_tiles
+  size_t r3 = mode == SCN_STEP ? (sk > bs ? sk : bs) : mode == SCN_BWD ? sk : 0;
+  if (mode == SCN_STEP) {   // S | y | dlogits (contiguous) later hold the 16 waves' gradient partials of scn_bwd_tiles
     const size_t NT = ((size_t)K + 15) / 16, TD = (size_t)H / 16;
     const size_t need = 16 * ((NT * TD + 2 * TD) * 256 + 16 * NT + H), have = (o - Y.R1) + r3;
     if (have < need) r3 += need - have;
@@ -111,17 +116,17 @@ __host__ __device__ inline ScnLayout scn_layout(int H, int K, int max_n, int max
   Y.col_d = take(max_e);
   Y.rowptr_s = take(max_n + 1);
   Y.col_s = take(max_e);
-  Y.cursor = take(bwd ? 0 : max_n + 1);     // the backward loads the CSRs
-  Y.tmp = take(bwd ? 0 : max_e);
-  Y.cursor2 = take(bwd ? 0 : max_n + 1);
-  Y.tmp2 = take(bwd ? 0 : max_e);
-  if (bwd == 2) {   // the step builds them in R3 (dlogits are not live before the backward half)
+  Y.cursor = take(back ? 0 : max_n + 1);     // the backward loads the CSRs
+  Y.tmp = take(back ? 0 : max_e);
+  Y.cursor2 = take(back ? 0 : max_n + 1);
+  Y.tmp2 = take(back ? 0 : max_e);
+  if (mode == SCN_STEP) {   // the step builds them in R3 (dlogits are not live before the backward half)
     size_t q = Y.R3;
     auto sub = [&](size_t n) { size_t r = q; q += (n + 3) & ~(size_t)3; return r; };
     Y.cursor = sub(max_n + 1); Y.tmp = sub(max_e); Y.cursor2 = sub(max_n + 1); Y.tmp2 = sub(max_e);
   }
   Y.wsum = take(32);
-  Y.ssl = take(bwd ? (size_t)K * K : 0);   // the forward's S^T S, fetched with the rest of the front
+  Y.ssl = take(back ? (size_t)K * K : 0);   // the forward's S^T S, fetched with the rest of the front
   Y.total = o;
   return Y;
 }
@@ -862,7 +867,7 @@ __global__ void __launch_bounds__(SRT) k_scn_fwd(const ScnArgs A) {
     if (threadIdx.x == 0 && A.flag) atomicOr(A.flag, 4);
     return;
   }
-  const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, 0);
+  const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, SCN_FWD);
   float* fb = reinterpret_cast<float*>(smem);
   int* ib = reinterpret_cast<int*>(smem);
   float *xs = fb + Y.R1, *agg = xs + (size_t)A.max_n * FP, *Sl = fb + Y.R1, *yl = fb + Y.R2;
@@ -1257,7 +1262,7 @@ __global__ void __launch_bounds__(SRT) k_scn_bwd(const ScnArgs A) {
     for (int i = threadIdx.x; i < A.P; i += SRT) part[i] = 0.f;
     return;
   }
-  const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, 1);
+  const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, SCN_BWD);
   float* fb = reinterpret_cast<float*>(smem);
   int* ib = reinterpret_cast<int*>(smem);
   float* Sl = fb + Y.R1;                                   // S, and x once S is dead
@@ -1389,7 +1394,7 @@ __global__ void __launch_bounds__(SRT) k_scn_step(const ScnArgs A) {
     for (int i = threadIdx.x; i < A.P; i += SRT) part[i] = 0.f;
     return;
   }
-  const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, 2);
+  const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, SCN_STEP);
   float* fb = reinterpret_cast<float*>(smem);
   int* ib = reinterpret_cast<int*>(smem);
   float *xs = fb + Y.R1, *agg = xs + (size_t)A.max_n * FP, *Sl = fb + Y.R1, *yl = fb + Y.R2, *DL = fb + Y.R3;
@@ -1488,7 +1493,7 @@ __global__ void __launch_bounds__(SRT) k_scn_epoch(const ScnArgs A0) {
       A.K = K_; A.F = F_; A.max_n = mn; A.max_e = me; A.P = P_;
     }
     const int K = A.K;
-    const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, 2);
+    const ScnLayout Y = scn_layout(H, K, A.max_n, A.max_e, SCN_STEP);
     float* fb = reinterpret_cast<float*>(smem);
     int* ib = reinterpret_cast<int*>(smem);
     float *xs = fb + Y.R1, *agg = xs + (size_t)A.max_n * FP, *Sl = fb + Y.R1, *yl = fb + Y.R2, *DL = fb + Y.R3;
@@ -1562,29 +1567,67 @@ __global__ void k_scn_losses(const float* __restrict__ stats, float* __restrict_
 
 inline int64_t scn_param_count(int F, int H, int K) { return (int64_t)2 * H * F + H + (int64_t)K * H + K; }
 
-template <int H, typename TS>
-int launch_scn(ScnArgs& A, int bwd, hipStream_t st) {
-  const size_t lds = scn_layout(H, A.K, A.max_n, A.max_e, bwd).total * 4;
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (bwd == 2 && A.pre) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_scn_step<H, TS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_scn_step<H, TS, true><<<(unsigned)A.B, SRT, lds, st>>>(A);
-  } else if (bwd == 2) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_scn_step<H, TS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_scn_step<H, TS, false><<<(unsigned)A.B, SRT, lds, st>>>(A);
-  } else if (bwd) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_scn_bwd<H, TS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_scn_bwd<H, TS><<<(unsigned)A.B, SRT, lds, st>>>(A);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_scn_fwd<H, TS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_scn_fwd<H, TS><<<(unsigned)A.B, SRT, lds, st>>>(A);
-  }
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+inline size_t scn_lds_bytes(int H, int K, int max_n, int max_e, ScnMode mode) {
+  return scn_layout(H, K, max_n, max_e, mode).total * 4;
+}
+
+// the hidden width and the storage type as template arguments, f(std::integral_constant<int, H>{}, TS{}), for the four
+// combinations stage A is instantiated at
+template <typename F>
+int dispatch_scn(int H, bool f16, F&& f) {
+  const std::integral_constant<int, 16> h16;
+  const std::integral_constant<int, 32> h32;
+  if (H != 16 && H != 32) return HSCN_E_UNSUPPORTED;
+  return f16 ? (H == 16 ? f(h16, half_t{}) : f(h32, half_t{})) : (H == 16 ? f(h16, float{}) : f(h32, float{}));
+}
+
+// one workgroup per graph of the batch; the step's kernel comes in two forms, structure built or loaded (A.pre)
+int launch_scn(const ScnArgs& A, int H, bool f16, ScnMode mode, hipStream_t st) {
+  const size_t lds = scn_lds_bytes(H, A.K, A.max_n, A.max_e, mode);
+  if (lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  return dispatch_scn(H, f16, [&](auto h, auto ts) {
+    constexpr int HH = decltype(h)::value;
+    using TS = decltype(ts);
+    const auto k = mode == SCN_FWD   ? k_scn_fwd<HH, TS>
+                   : mode == SCN_BWD ? k_scn_bwd<HH, TS>
+                   : A.pre           ? k_scn_step<HH, TS, true>
+                                     : k_scn_step<HH, TS, false>;
+    return launch_with_lds(k, (unsigned)A.B, SRT, lds, st, A);
+  });
+}
+
+// the fields every entry point sets (NULL where a launch has no use for one); each adds what is its own
+ScnArgs scn_args(const void* x, const int64_t* edge_index, int64_t E, const int32_t* nptr, const int32_t* eptr,
+                 const float* W_rel, const float* b_rel, const float* W_root, const float* W_mlp, const float* b_mlp,
+                 int64_t N, int64_t B, int F, int H, int K, int act, int max_n, int max_e, float* stats, float* losses,
+                 int32_t* ticket, int32_t* flag) {
+  ScnArgs A{};
+  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
+  A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
+  A.N = N; A.F = F; A.K = K; A.act = act; A.max_n = max_n; A.max_e = max_e; A.B = (int)B;
+  A.P = (int)scn_param_count(F, H, K);
+  A.stats = stats; A.losses = losses; A.ticket = ticket; A.flag = flag;
+  return A;
+}
+
+bool adam_ok(const hscn_adam* opt) {
+  return opt->exp_avg && opt->exp_avg_sq && opt->step && opt->beta_pows && opt->lr && opt->beta1 >= 0.0 &&
+         opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0 && opt->eps >= 0.0 && opt->weight_decay >= 0.0;
+}
+void set_adam(ScnArgs& A, const hscn_adam* opt) {
+  A.adam_m = opt->exp_avg; A.adam_v = opt->exp_avg_sq; A.adam_step = opt->step; A.adam_pows = opt->beta_pows;
+  A.adam_lr = opt->lr; A.adam_b1 = opt->beta1; A.adam_b2 = opt->beta2; A.adam_eps = opt->eps;
+  A.adam_wd = opt->weight_decay; A.adam_decoupled = opt->decoupled;
+}
+
+// a structure block has its arrays; the column arrays may be missing only where the caller says so (no edges)
+bool structure_ok(const hscn_scn_structure* c, bool cols_may_be_null) {
+  return c->rowptr_d && c->rowptr_s && c->agg && c->dout && (cols_may_be_null || (c->col_d && c->col_s));
+}
+void set_structure(ScnArgs& A, const hscn_scn_structure* c) {
+  A.ex_rowptr_d = c->rowptr_d; A.ex_col_d = c->col_d; A.ex_rowptr_s = c->rowptr_s; A.ex_col_s = c->col_s;
+  A.ex_agg = c->agg; A.ex_dout = c->dout; A.ex_xpad = c->xpad;
+  A.pre = c->ready != 0;   // ready: load the structure an earlier visit exported; else build it and export
 }
 
 }  // namespace
@@ -1600,8 +1643,8 @@ int hscn_diag_set_stamp_buffer_scn(long long* buf) {   // this translation unit'
 int hscn_scn_resident_supported(int F, int H, int K, int max_n, int max_e) {
   if (!(H == 16 || H == 32) || F < 1 || F > FP || K < 1 || K > 64 || max_n < 0 || max_e < 0) return 0;
   if (SRT % H != 0) return 0;
-  if (scn_layout(H, K, max_n, max_e, 0).total * 4 > 160 * 1024) return 0;
-  if (scn_layout(H, K, max_n, max_e, 1).total * 4 > 160 * 1024) return 0;
+  if (scn_lds_bytes(H, K, max_n, max_e, SCN_FWD) > LDS_CU_BYTES) return 0;
+  if (scn_lds_bytes(H, K, max_n, max_e, SCN_BWD) > LDS_CU_BYTES) return 0;
   return 1;
 }
 
@@ -1611,7 +1654,7 @@ int hscn_scn_resident_train_step_supported(int F, int H, int K, int max_n, int m
   if (!hscn_scn_resident_supported(F, H, K, max_n, max_e)) return 0;
   // float4 rows of S; at most two 16-row tiles per wave; at most two accumulator tiles of dW_mlp per wave
   if ((K & 3) != 0 || max_n > 512 || ((K + 15) / 16) * (H / 16) > 2) return 0;
-  if (scn_layout(H, K, max_n, max_e, 2).total * 4 > 160 * 1024) return 0;
+  if (scn_lds_bytes(H, K, max_n, max_e, SCN_STEP) > LDS_CU_BYTES) return 0;
   return 1;
 }
 
@@ -1626,40 +1669,21 @@ int hscn_scn_resident_train_step(const void* x, const int64_t* edge_index, int64
                                  float* grads, int32_t* flag, const hscn_adam* opt,
                                  const hscn_scn_structure* cache, int flags, void* stream_) {
   if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
-  const int f16 = flags & HSCN_STORE_F16;
   if (B < 1 || N < 0 || E < 0) return HSCN_E_BADARG;
-  if (cache && (!cache->rowptr_d || !cache->rowptr_s || !cache->agg || !cache->dout ||
-                (E > 0 && (!cache->col_d || !cache->col_s))))
-    return HSCN_E_BADARG;
-  if (opt && (B != 1 || !opt->exp_avg || !opt->exp_avg_sq || !opt->step || !opt->beta_pows || !opt->lr ||
-              !(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0) || !(opt->eps >= 0.0) ||
-              !(opt->weight_decay >= 0.0)))
-    return HSCN_E_BADARG;
+  if (cache && !structure_ok(cache, E == 0)) return HSCN_E_BADARG;
+  if (opt && (B != 1 || !adam_ok(opt))) return HSCN_E_BADARG;
   if (!hscn_scn_resident_train_step_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_rel || !b_rel || !W_root || !W_mlp || !b_mlp || !stats || !losses || !grads ||
       (B > 1 && !partials) || (E > 0 && !edge_index))
     return HSCN_E_BADARG;
-  ScnArgs A{};
-  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
-  A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
-  A.S = S; A.stats = stats; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act; A.g_mc = g_mc; A.g_o = g_o;
-  A.losses = losses; A.ticket = ticket;
-  A.max_n = max_n; A.max_e = max_e; A.B = (int)B; A.P = (int)scn_param_count(F, H, K);
+  ScnArgs A = scn_args(x, edge_index, E, nptr, eptr, W_rel, b_rel, W_root, W_mlp, b_mlp, N, B, F, H, K, act, max_n,
+                       max_e, stats, losses, ticket, flag);
+  A.S = S; A.g_mc = g_mc; A.g_o = g_o;
   A.partials = B == 1 ? grads : partials;   // one graph: its partials are the gradients
-  if (cache) {   // ready: load the structure an earlier visit exported; else build it and export
-    A.ex_rowptr_d = cache->rowptr_d; A.ex_col_d = cache->col_d; A.ex_rowptr_s = cache->rowptr_s;
-    A.ex_col_s = cache->col_s; A.ex_agg = cache->agg; A.ex_dout = cache->dout; A.ex_xpad = cache->xpad;
-    A.pre = cache->ready != 0;
-  }
-  if (opt) {
-    A.adam_m = opt->exp_avg; A.adam_v = opt->exp_avg_sq; A.adam_step = opt->step; A.adam_pows = opt->beta_pows;
-    A.adam_lr = opt->lr; A.adam_b1 = opt->beta1; A.adam_b2 = opt->beta2; A.adam_eps = opt->eps;
-    A.adam_wd = opt->weight_decay; A.adam_decoupled = opt->decoupled;
-  }
+  if (cache) set_structure(A, cache);
+  if (opt) set_adam(A, opt);
   hipStream_t st = hscn_stream(stream_);
-  int rc = f16 ? (H == 16 ? launch_scn<16, half_t>(A, 2, st) : launch_scn<32, half_t>(A, 2, st))
-               : (H == 16 ? launch_scn<16, float>(A, 2, st) : launch_scn<32, float>(A, 2, st));
-  if (rc) return rc;
+  if (int rc = launch_scn(A, H, flags & HSCN_STORE_F16, SCN_STEP, st)) return rc;
   if (!ticket) {
     k_scn_losses<<<1, 64, 0, st>>>(stats, losses, (int)B);
     HSCN_RETURN_IF_LAUNCH_FAILED();
@@ -1679,7 +1703,6 @@ int hscn_scn_resident_fwd(const void* x, const int64_t* edge_index, int64_t E, c
                           int32_t* ex_rowptr_s, int32_t* ex_col_s, float* ex_agg, float* ex_dout, int32_t* flag,
                           int flags, void* stream_) {
   if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
-  const int f16 = flags & HSCN_STORE_F16;
   if (B < 1 || N < 0 || E < 0) return HSCN_E_BADARG;
   if (!hscn_scn_resident_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_rel || !b_rel || !W_root || !W_mlp || !b_mlp || !S || !y || !stats || !ss ||
@@ -1690,17 +1713,13 @@ int hscn_scn_resident_fwd(const void* x, const int64_t* edge_index, int64_t E, c
                      (ex_col_s != nullptr) + (ex_agg != nullptr) + (ex_dout != nullptr);
     if (have != 0 && have != 6) return HSCN_E_BADARG;   // the structure is exported whole or not at all
   }
-  ScnArgs A{};
-  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
-  A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
-  A.S = S; A.y = (float*)y; A.stats = stats; A.ss = ss; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act;
+  ScnArgs A = scn_args(x, edge_index, E, nptr, eptr, W_rel, b_rel, W_root, W_mlp, b_mlp, N, B, F, H, K, act, max_n,
+                       max_e, stats, losses, ticket, flag);
+  A.S = S; A.y = (float*)y; A.ss = ss;
   A.ex_rowptr_d = ex_rowptr_d; A.ex_col_d = ex_col_d; A.ex_rowptr_s = ex_rowptr_s; A.ex_col_s = ex_col_s;
-  A.ex_agg = ex_agg; A.ex_dout = ex_dout; A.losses = losses; A.ticket = ticket;
-  A.max_n = max_n; A.max_e = max_e; A.B = (int)B; A.P = (int)scn_param_count(F, H, K);
+  A.ex_agg = ex_agg; A.ex_dout = ex_dout;
   hipStream_t st = hscn_stream(stream_);
-  int rc = f16 ? (H == 16 ? launch_scn<16, half_t>(A, 0, st) : launch_scn<32, half_t>(A, 0, st))
-               : (H == 16 ? launch_scn<16, float>(A, 0, st) : launch_scn<32, float>(A, 0, st));
-  if (rc) return rc;
+  if (int rc = launch_scn(A, H, flags & HSCN_STORE_F16, SCN_FWD, st)) return rc;
   if (!ticket) {   // no ticket counter: the statistics are reduced by a launch of their own
     k_scn_losses<<<1, 64, 0, st>>>(stats, losses, (int)B);
     HSCN_RETURN_IF_LAUNCH_FAILED();
@@ -1716,25 +1735,20 @@ int hscn_scn_resident_bwd(const void* x, const int64_t* edge_index, int64_t E, c
                           const float* ex_dout, int max_n, int max_e, float* partials, float* grads, int32_t* flag,
                           int flags, void* stream_) {
   if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
-  const int f16 = flags & HSCN_STORE_F16;
   if (B < 1 || N < 0 || E < 0) return HSCN_E_BADARG;
   if (!hscn_scn_resident_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_mlp || !S || !y || !stats || !ss || !partials || !grads ||
       !ex_rowptr_d || !ex_rowptr_s || !ex_agg || !ex_dout || (E > 0 && (!ex_col_d || !ex_col_s)))
     return HSCN_E_BADARG;
-  ScnArgs A{};
-  A.x = (const float*)x; A.src = edge_index; A.dst = edge_index ? edge_index + E : nullptr; A.nptr = nptr; A.eptr = eptr;
-  A.W_mlp = W_mlp; A.S = const_cast<float*>(S); A.y = (float*)const_cast<void*>(y);
-  A.stats = const_cast<float*>(stats); A.ss = const_cast<float*>(ss); A.g_mc = g_mc; A.g_o = g_o;
+  ScnArgs A = scn_args(x, edge_index, E, nptr, eptr, nullptr, nullptr, nullptr, W_mlp, nullptr, N, B, F, H, K, act,
+                       max_n, max_e, const_cast<float*>(stats), nullptr, nullptr, flag);
+  A.S = const_cast<float*>(S); A.y = (float*)const_cast<void*>(y); A.ss = const_cast<float*>(ss);
+  A.g_mc = g_mc; A.g_o = g_o; A.partials = partials;
   A.ex_rowptr_d = const_cast<int32_t*>(ex_rowptr_d); A.ex_col_d = const_cast<int32_t*>(ex_col_d);
   A.ex_rowptr_s = const_cast<int32_t*>(ex_rowptr_s); A.ex_col_s = const_cast<int32_t*>(ex_col_s);
   A.ex_agg = const_cast<float*>(ex_agg); A.ex_dout = const_cast<float*>(ex_dout);
-  A.partials = partials; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act;
-  A.max_n = max_n; A.max_e = max_e; A.B = (int)B; A.P = (int)scn_param_count(F, H, K);
   hipStream_t st = hscn_stream(stream_);
-  int rc = f16 ? (H == 16 ? launch_scn<16, half_t>(A, 1, st) : launch_scn<32, half_t>(A, 1, st))
-               : (H == 16 ? launch_scn<16, float>(A, 1, st) : launch_scn<32, float>(A, 1, st));
-  if (rc) return rc;
+  if (int rc = launch_scn(A, H, flags & HSCN_STORE_F16, SCN_BWD, st)) return rc;
   launch_param_fold(partials, grads, (int)B, A.P, -1, 0.f, nullptr, false, st);
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
@@ -1752,54 +1766,37 @@ int hscn_scn_resident_train_epoch(const void* x, const int32_t* nptr, const int3
                                   float* grads, float* stats, float* losses, int32_t* ticket, int32_t* flag,
                                   int flags, void* stream_) {
   if (flags & ~HSCN_STORE_F16) return HSCN_E_BADARG;
-  const int f16 = flags & HSCN_STORE_F16;
+  const bool f16 = flags & HSCN_STORE_F16;
   if (G < 1 || N < 0 || visits < 0) return HSCN_E_BADARG;
   if (!hscn_scn_resident_train_step_supported(F, H, K, max_n, max_e)) return HSCN_E_UNSUPPORTED;
   if (!x || !nptr || !eptr || !W_rel || !b_rel || !W_root || !W_mlp || !b_mlp || !grads || !stats || !losses || !ticket ||
       !cache || !opt)
     return HSCN_E_BADARG;
-  if (!cache->ready || !cache->rowptr_d || !cache->rowptr_s || !cache->agg || !cache->dout || !cache->col_d ||
-      !cache->col_s)
-    return HSCN_E_BADARG;
-  if (!opt->exp_avg || !opt->exp_avg_sq || !opt->step || !opt->beta_pows || !opt->lr ||
-      !(opt->beta1 >= 0.0 && opt->beta1 < 1.0 && opt->beta2 >= 0.0 && opt->beta2 < 1.0) || !(opt->eps >= 0.0) ||
-      !(opt->weight_decay >= 0.0))
-    return HSCN_E_BADARG;
-  ScnArgs A{};
-  A.x = (const float*)x;
-  A.W_rel = W_rel; A.b_rel = b_rel; A.W_root = W_root; A.W_mlp = W_mlp; A.b_mlp = b_mlp;
-  A.stats = stats; A.losses = losses; A.ticket = ticket; A.flag = flag; A.N = N; A.F = F; A.K = K; A.act = act;
-  A.g_mc = g_mc; A.g_o = g_o;
-  A.max_n = max_n; A.max_e = max_e; A.B = 1; A.P = (int)scn_param_count(F, H, K); A.partials = grads;
-  A.ex_col_d = cache->col_d; A.ex_col_s = cache->col_s; A.ex_agg = cache->agg; A.ex_dout = cache->dout;
-  A.ex_xpad = cache->xpad; A.pre = 1;
-  A.adam_m = opt->exp_avg; A.adam_v = opt->exp_avg_sq; A.adam_step = opt->step; A.adam_pows = opt->beta_pows;
-  A.adam_lr = opt->lr; A.adam_b1 = opt->beta1; A.adam_b2 = opt->beta2; A.adam_eps = opt->eps;
-  A.adam_wd = opt->weight_decay; A.adam_decoupled = opt->decoupled;
+  if (!cache->ready || !structure_ok(cache, false)) return HSCN_E_BADARG;
+  if (!adam_ok(opt)) return HSCN_E_BADARG;
+  // a batch of ONE graph; nptr, eptr and the structure's row pointers stand at graph 0, where the persistent
+  // workgroup starts its walk of the dataset
+  ScnArgs A = scn_args(x, nullptr, 0, nptr, eptr, W_rel, b_rel, W_root, W_mlp, b_mlp, N, 1, F, H, K, act, max_n, max_e,
+                       stats, losses, ticket, flag);
+  A.g_mc = g_mc; A.g_o = g_o; A.partials = grads;
+  set_structure(A, cache);
+  set_adam(A, opt);
   hipStream_t st = hscn_stream(stream_);
   // the chain as launches of ONE persistent workgroup (k_scn_epoch; P <= 1024: a thread per parameter element), in
   // slices of 32 768 visits (~0.5 s) so that no launch runs long enough to look hung; HSCN_PERSISTENT_EPOCH=0 keeps the
   // launch per visit below (the same arithmetic, bit for bit)
   const char* pe = getenv("HSCN_PERSISTENT_EPOCH");
   if (A.P <= SRT && !(pe && pe[0] == '0')) {
-    A.nptr = nptr; A.eptr = eptr; A.ex_rowptr_d = cache->rowptr_d; A.ex_rowptr_s = cache->rowptr_s;
     A.G = (int)G;
-    const size_t lds = scn_layout(H, K, max_n, max_e, 2).total * 4;
-#define HSCN_EPOCH(H_, TS_)                                                                                    \
-  do {                                                                                                         \
-    if (lds > 64 * 1024)                                                                                       \
-      (void)hipFuncSetAttribute((const void*)k_scn_epoch<H_, TS_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                     \
-    k_scn_epoch<H_, TS_><<<1, SRT, lds, st>>>(A);                                                              \
-  } while (0)
+    const size_t lds = scn_lds_bytes(H, K, max_n, max_e, SCN_STEP);
     for (int64_t v0 = 0; v0 < visits; v0 += 32768) {
       A.visit0 = v0;
       A.visits = visits - v0 < 32768 ? visits - v0 : 32768;
-      if (f16) { if (H == 16) HSCN_EPOCH(16, half_t); else HSCN_EPOCH(32, half_t); }
-      else { if (H == 16) HSCN_EPOCH(16, float); else HSCN_EPOCH(32, float); }
-      HSCN_RETURN_IF_LAUNCH_FAILED();
+      const int rc = dispatch_scn(H, f16, [&](auto h, auto ts) {
+        return launch_with_lds(k_scn_epoch<decltype(h)::value, decltype(ts)>, 1u, SRT, lds, st, A);
+      });
+      if (rc) return rc;
     }
-#undef HSCN_EPOCH
     return 0;
   }
   for (int64_t v = 0; v < visits; ++v) {
@@ -1808,9 +1805,7 @@ int hscn_scn_resident_train_epoch(const void* x, const int32_t* nptr, const int3
     // structure keeps graph g's row pointers at nptr[g] + g: the + g travels in the base pointers
     A.nptr = nptr + g; A.eptr = eptr + g;
     A.ex_rowptr_d = cache->rowptr_d + g; A.ex_rowptr_s = cache->rowptr_s + g;
-    int rc = f16 ? (H == 16 ? launch_scn<16, half_t>(A, 2, st) : launch_scn<32, half_t>(A, 2, st))
-                 : (H == 16 ? launch_scn<16, float>(A, 2, st) : launch_scn<32, float>(A, 2, st));
-    if (rc) return rc;
+    if (int rc = launch_scn(A, H, f16, SCN_STEP, st)) return rc;
   }
   return 0;
 }

@@ -580,12 +580,8 @@ __global__ void __launch_bounds__(VL_RT) k_vl_step(const VlArgs A) {
 template <int H, bool TRAIN>
 int launch_vl(const VlArgs& A, int64_t B, hipStream_t st) {
   const size_t lds = vl_lds_bytes(H, A.L, A.max_n, A.max_v, A.max_ell, A.max_evv);
-  if (lds > 160 * 1024) return HSCN_E_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_vl_step<H, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_vl_step<H, TRAIN><<<(unsigned)B, VL_RT, lds, st>>>(A);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  if (lds > LDS_CU_BYTES) return HSCN_E_UNSUPPORTED;
+  return launch_with_lds(k_vl_step<H, TRAIN>, (unsigned)B, VL_RT, lds, st, A);
 }
 
 }  // namespace
@@ -597,7 +593,7 @@ int hscn_vl_supported(int F, int H, int L, int C, int max_n, int max_v, int max_
   if (max_n < 0 || max_v < 0 || max_ell < 0 || max_evv < 0 || max_n > (1 << 20) || max_v > (1 << 20) ||
       max_ell > (1 << 22) || max_evv > (1 << 22))
     return 0;
-  return vl_lds_bytes(H, L, max_n, max_v, max_ell, max_evv) <= 160 * 1024 ? 1 : 0;
+  return vl_lds_bytes(H, L, max_n, max_v, max_ell, max_evv) <= LDS_CU_BYTES ? 1 : 0;
 }
 
 int64_t hscn_vl_param_count(int F, int H, int L, int C) {

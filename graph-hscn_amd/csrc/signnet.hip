@@ -271,7 +271,7 @@ int hscn_signnet_supported(int model, int use_bn, int F, int K, int hidden, int 
   if (layers < 1 || layers > SN_MAXC || post_layers < 1 || post_layers > SN_MAXR) return 0;
   if (max_n < 0 || max_e < 0 || max_n > (1 << 20) || max_e > (1 << 22)) return 0;
   const int Lc = layers < 2 ? 2 : layers;
-  return sn_lds_bytes(K, hidden, phi_out, Lc, dim_pe, max_n, max_e) <= 160 * 1024 ? 1 : 0;
+  return sn_lds_bytes(K, hidden, phi_out, Lc, dim_pe, max_n, max_e) <= LDS_CU_BYTES ? 1 : 0;
 }
 
 int hscn_signnet_encode(const float* x, const float* eigvecs, const int64_t* edge_index, int64_t E,
@@ -315,11 +315,7 @@ int hscn_signnet_encode(const float* x, const float* eigvecs, const int64_t* edg
   A.F = F; A.K = K; A.Hd = hidden; A.Od = phi_out; A.Lc = Lc; A.R = post_layers; A.dim_pe = dim_pe; A.dx = dim_x;
   A.max_n = max_n; A.max_e = max_e;
   const size_t lds = sn_lds_bytes(K, hidden, phi_out, Lc, dim_pe, max_n, max_e);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)k_signnet_encode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k_signnet_encode<<<(unsigned)B, SN_RT, lds, hscn_stream(stream_)>>>(A);
-  HSCN_RETURN_IF_LAUNCH_FAILED();
-  return 0;
+  return launch_with_lds(k_signnet_encode, (unsigned)B, SN_RT, lds, hscn_stream(stream_), A);
 }
 
 }  // extern "C"

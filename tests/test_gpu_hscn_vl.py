@@ -253,6 +253,22 @@ def test_peptides_shaped_batch_matches_the_referee(F, H, act):
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. layered and one-launch agreement
 # ---------------------------------------------------------------------------------------------------------------------
+def test_forward_only_equals_the_step_below_the_lds_opt_in_line():
+    """Graphs of at most 100 nodes: about 43 KB of LDS at H = 16, L = 3, within the 64 KB a launch gets without asking
+    (every other forward-only launch of this file is above that line; the step has cases on both sides)."""
+    hb = _collate(_peptides(4, 16, seed=3, max_nodes=100))
+    _, pm = _models(9, 16, 10, 3, "elu", seed=7)
+    hbd = hb.to(DEV)
+    assert pm.resident_reason(hbd) is None
+    step = _run_step(pm, hbd, "cross_entropy")
+    pm.engine = "resident"
+    with torch.no_grad():
+        fwd = pm(hbd.x_dict, hbd.edge_index_dict, hbd)
+    torch.cuda.synchronize()
+    assert pm.last_engine == "resident" and int(hbd._resident_meta.flag.item()) == 0
+    assert torch.equal(fwd, step.pred)
+
+
 def test_layered_step_passes_the_referee_and_forward_only_equals_the_step():
     from graph_hscn.loss import criterion
     hb = _collate(_peptides(4, 16, seed=3) + _hand_graphs("cross_entropy")[:2])

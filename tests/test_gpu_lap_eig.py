@@ -274,6 +274,17 @@ def test_tier_boundary(lap):
     _check_large(_boundary_graphs(), lap, {"lds_edge": 7, "global_edge": 7} if lap == "sym" else {})
 
 
+@pytest.mark.parametrize("n", [82, 84])
+def test_lds_opt_in_line(n):
+    """A launch sized for n = 82 asks for 54 448 bytes of dynamic LDS, which with the kernel's 8 832 bytes of static
+    scratch stays within the 64 KB a launch gets unasked; one sized for n = 84 asks for 57 120: over the line with the
+    scratch, under it without.  Each launch: a batch of this graph and a smaller one."""
+    from graph_hscn.loader.synthetic import SHAPES, make_graph
+    rng = np.random.default_rng(n)
+    a, b = make_graph(rng, SHAPES["peptides_func"], n=n), make_graph(rng, SHAPES["peptides_func"], n=n - 3)
+    _check_large({f"n{n}": _data(n, a.edge_index), f"n{n - 3}": _data(n - 3, b.edge_index)}, "sym", {})
+
+
 def test_large_graphs():
     """Peptides' largest (444) and PascalVOC-SP's largest (500) graph through the global tier."""
     _check_large(_large_graphs(), "sym", {})

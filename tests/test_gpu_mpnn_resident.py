@@ -330,6 +330,25 @@ def test_forward_only_equals_train_step_pred_and_eval_epoch():
     assert _refereed(torch.tensor([r_loss]), torch.tensor([l_loss]), torch.tensor([ref]), "eval_epoch loss")
 
 
+def test_forward_only_equals_train_step_pred_below_the_lds_opt_in_line():
+    """Graphs of at most 150 nodes: at most 52 KB of LDS at H = 16, L = 3, within the 64 KB a launch gets without asking
+    (every other forward-only launch of this file is above that line; the step has cases on both sides)."""
+    from graph_hscn.step import MPNNResidentTrainStep
+    graphs = [g for g in _graphs("peptides_func", 70, seed=9) if g.num_nodes <= 150][:16]
+    assert len(graphs) == 16
+    _, pm = _models(9, 16, 10, 3, "tanh", 0.0, seed=9)
+    bd = _dev(_batch(graphs))
+    step = MPNNResidentTrainStep(pm, bd, "cross_entropy")
+    step.run()
+    pm.eval()
+    pm.engine = "resident"
+    with torch.no_grad():
+        pred = pm(bd)
+    torch.cuda.synchronize()
+    assert pm.last_engine == "resident" and int(pm._resident_flag.item()) == 0
+    assert torch.equal(pred, step.pred)
+
+
 def test_accumulating_step_is_the_sum_of_plain_steps():
     from graph_hscn.step import MPNNResidentTrainStep
     b = _batch(_graphs("peptides_struct", 24, seed=4))

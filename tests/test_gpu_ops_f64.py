@@ -967,6 +967,25 @@ def test_mincut_sparse(kk, Fx):
                   sizes, K)
 
 
+@pytest.mark.parametrize("K", [82, 83, 112, 113])
+def test_mincut_sparse_at_the_lds_opt_in_line(K):
+    """Without x, k_mincut_stats asks for (2 K^2 + 34 K + 20) * 4 bytes of LDS and k_mincut_bwd for (K^2 + 32 K + 4) * 4:
+    K = 82 is the last width whose forward stays within the 64 KB a launch gets unasked and 83 the first that opts in;
+    112 / 113 are the same pair for the backward.  Two small graphs; the float64 referee of test_mincut_sparse."""
+    from graph_hscn.nn.functional import MinCutSparseFn
+    from graph_hscn.structure import Relation
+    sizes = [5, 20]
+    ei = _mincut_graphs(sizes, K)
+    N = sum(sizes)
+    logits = torch.randn(N, K, generator=_gen(K * 3)) * 2
+    rel = Relation(ei.to(DEV), N, N)
+    nptr = torch.tensor([0] + torch.tensor(sizes).cumsum(0).tolist(), dtype=torch.int32, device=DEV)
+    ld = logits.to(DEV).requires_grad_()
+    S, mc, oo, px, _ = MinCutSparseFn.apply(ld, None, rel, nptr, len(sizes))
+    (1.3 * mc + 0.7 * oo).backward()
+    _mincut_check("sparse", S.cpu(), mc, oo, None, ld.grad.cpu(), logits, None, ei, sizes, K)
+
+
 def test_mincut_sparse_refuses_k256():
     """K = 256 passes the argument check but its 2 K^2 cluster-space floats exceed the 160 KiB LDS: refused."""
     from graph_hscn.structure import Relation
