@@ -372,6 +372,7 @@ class ScnTrainStep:
                                                                   self.grads.numel())))
         self._one_args = {}
         self._cache = structure_pool.take(N, E, B) if (structure_pool is not None and self.one_launch) else None
+        self._pool = structure_pool        # ``_cache`` holds raw device pointers into the pool's buffers: keep them alive
 
     @property
     def loss(self) -> Tensor:

@@ -135,26 +135,34 @@ CANCELLING = {
 }
 
 
-def _check(what, om, pm, x, consts, gy, gates=None, atol=ATOL, rtol=RTOL, drops=None, steps=1, chain_extra=0):
-    """Forward at (atol, rtol) against the float32 oracle, kink guard on the float64 oracle, every gradient through
-    the referee.  ``drops``: references with one term removed, each a ``consts`` dict or ``(consts, gy)``.  A case
-    without an entry in CANCELLING: every tensor passes the referee, and the HIP result is rejected against the dropped
-    reference for every gradient the term reaches (``teeth``).  A case listed there: its named tensors may take the
-    derived bound, and referee and bound together must reject the dropped reference for them (``bound_teeth``)."""
-    print(f"[layered f64] {what}")
+def _references(what, om, x, consts, gy, gates=None, atol=ATOL, rtol=RTOL, drops=None, steps=1, chain_extra=0,
+                draws=None):
+    """The CPU side of ``_check``, which needs no device and which several engines on the same inputs can share: the
+    float32 and float64 oracle evaluations, the kink guard on the float64 one (asserted here), the float64 evaluations
+    of ``drops``.  ``draws``: further ``consts`` dicts that describe the SAME inputs (``helpers.relabel_graphs``); the
+    float32 oracle is evaluated on each and the referee's yardstick becomes the largest distance over all of them
+    (``helpers.referee``); gradients only -- the forward value is the one of ``consts``."""
     cancelling = CANCELLING.get(what, {})
     assert not cancelling or drops, f"{what}: tensors that may take the derived bound need its teeth"
     o32, g32, _, _ = _oracle_eval(om, x, consts, gy, torch.float32, steps=steps)
     o64, g64, kg, terms = _oracle_eval(om, x, consts, gy, torch.float64, gates, steps, chain_extra, guard=True)
     kg.check(atol, rtol, what)
-    od, gd = _product_eval(pm, x, consts, gy, steps=steps)
-    assert close(od, o32, atol=atol, rtol=rtol), f"{what}: forward outside the bar"
+    if draws:
+        g32 = [g32] + [_oracle_eval(om, x, dc, gy, torch.float32, steps=steps)[1] for dc in draws]
+    dropped = []
+    for d in drops or []:
+        dc, dg = d if isinstance(d, tuple) else (d, gy)
+        dropped.append(_oracle_eval(om, x, dc, dg, torch.float64, steps=steps)[1])
+    return dict(o32=o32, g32=g32, o64=o64, g64=g64, terms=terms, dropped=dropped, cancelling=cancelling)
+
+
+def _judge(what, ref, od, gd, atol=ATOL, rtol=RTOL):
+    """One engine's forward value ``od`` and gradients ``gd`` against the ``_references`` of the case: forward at
+    (atol, rtol), every gradient through the referee, then the teeth.  Returns the worst ratio."""
+    g32, g64, terms, cancelling, dropped = ref["g32"], ref["g64"], ref["terms"], ref["cancelling"], ref["dropped"]
+    assert close(od, ref["o32"], atol=atol, rtol=rtol), f"{what}: forward outside the bar"
     worst = referee_all(gd, g32, g64, what, terms=terms, cancelling=cancelling)
-    if drops:
-        dropped = []
-        for d in drops:
-            dc, dg = d if isinstance(d, tuple) else (d, gy)
-            dropped.append(_oracle_eval(om, x, dc, dg, torch.float64, steps=steps)[1])
+    if dropped:
         if cancelling:
             terms.bound_teeth(gd, g32, g64, dropped, list(cancelling), what)
         else:
@@ -162,7 +170,24 @@ def _check(what, om, pm, x, consts, gy, gates=None, atol=ATOL, rtol=RTOL, drops=
             assert reached, f"{what}: the dropped term reaches no gradient"
             print(f"   teeth: one dropped term reaches {sorted(reached)}; untouched: {sorted(set(g64) - set(reached))}")
             teeth(gd, g32, g64, reached, what)
-    return worst, (o32, g32, o64, g64, od, gd)
+    return worst
+
+
+def _check(what, om, pm, x, consts, gy, gates=None, atol=ATOL, rtol=RTOL, drops=None, steps=1, chain_extra=0,
+           draws=None):
+    """Forward at (atol, rtol) against the float32 oracle, kink guard on the float64 oracle, every gradient through
+    the referee.  ``drops``: references with one term removed, each a ``consts`` dict or ``(consts, gy)``.  A case
+    without an entry in CANCELLING: every tensor passes the referee, and the HIP result is rejected against the dropped
+    reference for every gradient the term reaches (``teeth``).  A case listed there: its named tensors may take the
+    derived bound, and referee and bound together must reject the dropped reference for them (``bound_teeth``).
+    ``draws``: relabelled copies of the inputs for a yardstick over several float32 draws (``_references``); without
+    them the single evaluation is the yardstick, as before."""
+    print(f"[layered f64] {what}")
+    ref = _references(what, om, x, consts, gy, gates, atol, rtol, drops, steps, chain_extra, draws)
+    od, gd = _product_eval(pm, x, consts, gy, steps=steps)
+    worst = _judge(what, ref, od, gd, atol, rtol)
+    g32 = ref["g32"][0] if draws else ref["g32"]
+    return worst, (ref["o32"], g32, ref["o64"], ref["g64"], od, gd)
 
 
 def _drop_edges(ei, extra=(), must=()):
