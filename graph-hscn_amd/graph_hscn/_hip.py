@@ -206,6 +206,13 @@ _SIGNATURES = {
     "hscn_attention_fwd": (c_int, [P, P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
     "hscn_attention_bwd_q": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, P, P, P, P]),
     "hscn_attention_bwd_kv": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, P, P, P]),
+    # GatedGCN's aggregate: edge-gated sums, edge features in and out (csrc/gatedgcn.hip; additive to ABI 24)
+    "hscn_gatedgcn_supported": (c_int, [c_int]),
+    "hscn_gatedgcn_long_row": (c_int, []),
+    "hscn_gatedgcn_chunk": (c_int, []),
+    "hscn_gatedgcn_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
+    "hscn_gatedgcn_bwd_dst": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
+    "hscn_gatedgcn_bwd_src": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
 }
 
 

@@ -12,7 +12,7 @@ from typing import Callable, Optional
 
 from torch.optim import Adagrad, Adam, AdamW
 
-from ..nn.conv import GINE, GATConv, GCNConv
+from ..nn.conv import GINE, GATConv, GatedGCNConv, GCNConv
 from ..nn.functional import Activation
 
 # defaults.py:1-39
@@ -46,7 +46,10 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 # "gine" (extension; "gin" stays absent, as it cannot be built in the reference either): the edge-aware baseline,
 # nn/conv.py GINE = GINEConv over Linear-ReLU-Linear (csrc/gine.hip).  It reads ``batch.edge_attr``, builds the MPNN
 # baseline only (the hetero graph carries no edge features: build_conv_relation refuses it) and runs layered.
-CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE}
+# "gatedgcn" (extension): nn/conv.py GatedGCNConv (csrc/gatedgcn.hip), the edge-gated convolution whose edge features
+# are a state: it reads ``batch.edge_attr``, returns ``(x, e)`` and hands ``e`` to the next layer.  Like "gine" it
+# builds the MPNN baseline and the GPS local branch only, and runs layered.
+CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE, "gatedgcn": GatedGCNConv}
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
 SCHEDULERS = ("cosine_with_warmup", "linear_with_warmup", "step")  # extension: optim.SCHEDULE_KINDS
 TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "graph" only
@@ -99,7 +102,8 @@ GPS_NORMS = ("layer", "batch", None)
 @dataclass
 class GPSConfig:
     """The GPS model (extension; model/gps.py): ``num_layers`` GPS layers of width ``hidden_channels`` -- a local
-    convolution ``local_conv_type`` ("gcn", "gat", "gine" of CONV_DICT, or None: the plain Transformer layer) beside
+    convolution ``local_conv_type`` ("gcn", "gat", "gine", "gatedgcn" of CONV_DICT, or None: the plain Transformer layer;
+    "gatedgcn" is GraphGPS's published pairing: a ``GatedGCNLayer`` that also updates the edge features) beside
     per-graph self-attention of ``num_heads`` heads, then a feed-forward block -- behind a Linear node encoder.  The
     head width ``hidden_channels / num_heads`` must be a multiple of 4 in [4, 64] and ``hidden_channels`` at most 512
     (the attention kernel's envelope, csrc/attention.hip)."""

@@ -51,6 +51,8 @@ class GPS(nn.Module):
         D = int(hidden_channels)
         self.node_encoder = Linear(num_features, D)
         self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act) for _ in range(num_layers))
+        if self.layers[0].updates_edge_attr:        # "gatedgcn": edge features are a state of width D
+            self.edge_encoder = Linear(-1, D)
         self.lin_1 = Linear(D, D)
         self.lin_2 = Linear(D, num_classes)
         self._node_head = NodeHead(self.lin_1, self.lin_2, act)
@@ -77,11 +79,12 @@ class GPS(nn.Module):
 
     # ---- forward -----------------------------------------------------------------------------------------------
     def _edge_attr(self, batch) -> Tensor:
-        """``batch.edge_attr`` for ``local_conv='gine'``: float32 [E, De] on the model's device (``MPNN._edge_attr``)."""
+        """``batch.edge_attr`` for an edge-aware ``local_conv``: float32 [E, De] on the model's device
+        (``MPNN._edge_attr``)."""
         ea = getattr(batch, "edge_attr", None)
         if ea is None:
-            raise ValueError("the model has edge-aware convolutions (local_conv 'gine') and the batch carries no "
-                             "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
+            raise ValueError(f"the model has edge-aware convolutions (local_conv {self.layers[0].local_conv!r}) and "
+                             "the batch carries no edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
         dev = next(self.parameters()).device
         if ea.dtype != torch.float32 or ea.device != dev:
             raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
@@ -97,9 +100,14 @@ class GPS(nn.Module):
         self.last_engine = "layered"
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
         x = self.node_encoder(batch.x)
+        if self.layers[0].updates_edge_attr:
+            edge_attr = self.edge_encoder(edge_attr)
         for i, layer in enumerate(self.layers):
             layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
-            x = layer(x, batch.edge_index, batch, edge_attr)
+            if layer.updates_edge_attr:             # the layer's new edge features feed the next layer
+                x, edge_attr = layer(x, batch.edge_index, batch, edge_attr)
+            else:
+                x = layer(x, batch.edge_index, batch, edge_attr)
         return x
 
     def _head(self, x: Tensor) -> Tensor:

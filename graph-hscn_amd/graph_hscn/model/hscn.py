@@ -247,6 +247,9 @@ class SCN(nn.Module):
 
 def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None) -> nn.Module:
     """hscn.py:117-125.  ``in_channels`` (extension) materialises the lazy ``-1``."""
+    if conv_type.lower() == "gatedgcn":
+        raise ValueError("conv_type 'GatedGCN' needs edge features, and the hetero graph carries no edge features yet "
+                         "(HeteroData has no edge_attr; the MPNN baseline and GPS take 'gatedgcn')")
     if conv_type.lower() == "gine":
         raise ValueError("conv_type 'GINE' needs edge features, and the hetero graph carries no edge features yet "
                          "(HeteroData has no edge_attr; the MPNN baseline takes conv_type 'gine')")

@@ -151,7 +151,8 @@ class MPNN(nn.Module):
         """``batch.edge_attr`` for the layers with ``uses_edge_attr``: float32 [E, De] on the model's device."""
         ea = getattr(batch, "edge_attr", None)
         if ea is None:
-            raise ValueError("the model has edge-aware convolutions (conv_type 'gine') and the batch carries no "
+            kind = "gatedgcn" if any(getattr(c, "updates_edge_attr", False) for c in self.conv_layers) else "gine"
+            raise ValueError(f"the model has edge-aware convolutions (conv_type {kind!r}) and the batch carries no "
                              "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
         dev = next(self.parameters()).device
         if ea.dtype != torch.float32 or ea.device != dev:
@@ -178,7 +179,11 @@ class MPNN(nn.Module):
         edge_attr = self._edge_attr(batch) if any(getattr(c, "uses_edge_attr", False) for c in self.conv_layers) else None
 
         def conv(i, x, **kw):                                               # edge-aware layers also take edge_attr
+            nonlocal edge_attr
             c = self.conv_layers[i]
+            if getattr(c, "updates_edge_attr", False):                      # "gatedgcn": (x, e); e feeds the next layer
+                x, edge_attr = c(x, edge_index, edge_attr, **kw)            # (the last layer's e is dropped)
+                return x
             return c(x, edge_index, edge_attr, **kw) if getattr(c, "uses_edge_attr", False) else c(x, edge_index, **kw)
         act_name = getattr(self.activation, "hscn_name", None)
         for i in range(self.num_layers - 1):

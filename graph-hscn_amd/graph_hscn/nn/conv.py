@@ -270,6 +270,100 @@ class GINE(GINEConv):
         return self.nn[2](self.nn[0](z, act="relu"), act=act)     # the middle ReLU in the first Linear's epilogue
 
 
+class GatedGCNConv(nn.Module):
+    """The bare convolution of GraphGPS's ``GatedGCNLayer`` (residual gated graph ConvNets), edge features in and out:
+
+        e^_k = D x_i + E x_j + C e_k                  j = edge_index[0, k], i = edge_index[1, k]
+        h_i  = A x_i + sum_k sigmoid(e^_k) * B x_j / (sum_k sigmoid(e^_k) + 1e-6)
+
+    every edge as given (loops and repeated edges count).  Five ``Linear`` with bias under GraphGPS's names ``A, B, C,
+    D, E`` (a ``state_dict`` moves across); ``C = Linear(edge_dim, out_channels)``, ``edge_dim=-1`` is materialised on
+    first use.  The five transforms run through ``Linear``; the gates, the two sums and the new edge rows are one HIP
+    launch (csrc/gatedgcn.hip).  ``forward`` returns ``(x_out, e_out)``, ``act`` applied to both; ``edge_attr`` may
+    carry a gradient (the previous layer's edge output, a trainable edge encoder)."""
+
+    uses_edge_attr = True
+    updates_edge_attr = True
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int = -1):
+        super().__init__()
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.A = Linear(in_channels, out_channels)
+        self.B = Linear(in_channels, out_channels)
+        self.C = Linear(edge_dim, out_channels)
+        self.D = Linear(in_channels, out_channels)
+        self.E = Linear(in_channels, out_channels)
+
+    def aggregate(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Tensor) -> Tuple[Tensor, Tensor]:
+        if not isinstance(x, Tensor):
+            raise TypeError("GatedGCNConv takes one node feature tensor")
+        if edge_attr is None:
+            raise ValueError("GatedGCNConv needs edge_attr [E, edge_dim]")
+        if edge_attr.dim() != 2:
+            raise ValueError(f"edge_attr must be [E, edge_dim], got {tuple(edge_attr.shape)}")
+        if not edge_attr.is_floating_point():
+            raise TypeError(f"GatedGCNConv: edge_attr must be float32, got {edge_attr.dtype}")
+        if not Fh.gatedgcn_supported(self.out_channels):
+            raise ValueError(f"GatedGCNConv: width H={self.out_channels} outside the kernel's envelope "
+                             f"(1 <= H <= {Fh.GATEDGCN_MAX_WIDTH})")
+        self.C.materialize(edge_attr.size(-1), x)
+        n = x.size(0)
+        # a gradient w.r.t. Bx or Ex (their weights are parameters) walks the source-keyed CSR
+        rel = _relation(edge_index, n, n, both=torch.is_grad_enabled())
+        if edge_attr.size(0) != rel.num_edges:
+            raise ValueError(f"edge_attr is {tuple(edge_attr.shape)}; the relation has {rel.num_edges} edges")
+        return Fh.GatedGCNAggregateFn.apply(self.A(x), self.B(x), self.D(x), self.E(x), self.C(edge_attr), rel)
+
+    def forward(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Tensor,
+                act: str = "identity") -> Tuple[Tensor, Tensor]:
+        h, e = self.aggregate(x, edge_index, edge_attr)
+        if act != "identity":
+            h, e = Fh.ActFn.apply(h, ACT[act]), Fh.ActFn.apply(e, ACT[act])
+        return h, e
+
+
+class GatedGCNLayer(GatedGCNConv):
+    """GraphGPS's ``GatedGCNLayer``: the convolution, then ``bn_node_x`` / ``bn_edge_e``, the activation and dropout on
+    both the node and the edge output, then the residuals ``x_in + x`` and ``e_in + e`` (when ``residual`` is set and the
+    widths agree).  Parameter names are GraphGPS's: ``A..E``, ``bn_node_x``, ``bn_edge_e``.  ``norm``: what
+    ``nn.gps._norm`` accepts ("batch", "layer", None).  ``dropout_seed`` pins the masks (tests): the node mask draws
+    with ``dropout_seed``, the edge mask with ``dropout_seed + EDGE_SEED_OFFSET``, far outside the consecutive seeds a
+    model hands to its node masks."""
+
+    EDGE_SEED_OFFSET = 1 << 20
+
+    def __init__(self, channels: int, dropout: float = 0.0, residual: bool = True, norm: Optional[str] = "batch",
+                 act: str = "relu", edge_dim: int = -1):
+        super().__init__(channels, channels, edge_dim)
+        from .gps import NORMS, _norm
+        if norm not in NORMS:
+            raise ValueError(f"norm must be 'layer', 'batch' or None, got {norm!r}")
+        if act not in ACT:
+            raise ValueError(f"act must be one of {sorted(ACT)}, got {act!r}")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be in [0, 1), got {dropout}")
+        self.channels, self.dropout, self.residual, self.act = int(channels), float(dropout), bool(residual), act
+        self.dropout_seed: Optional[int] = None
+        self.bn_node_x = _norm(norm, channels)
+        self.bn_edge_e = _norm(norm, channels)
+
+    def forward(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Tensor) -> Tuple[Tensor, Tensor]:
+        h, e = self.aggregate(x, edge_index, edge_attr)
+        if self.bn_node_x is not None:
+            h, e = self.bn_node_x(h), self.bn_edge_e(e)
+        if self.act != "identity":
+            h, e = Fh.ActFn.apply(h, ACT[self.act]), Fh.ActFn.apply(e, ACT[self.act])
+        seed = self.dropout_seed
+        h = Fh.dropout(h, p=self.dropout, training=self.training, seed=seed)
+        e = Fh.dropout(e, p=self.dropout, training=self.training,
+                       seed=None if seed is None else seed + self.EDGE_SEED_OFFSET)
+        if self.residual:
+            h = x + h
+            if edge_attr.size(-1) == self.channels:
+                e = edge_attr + e
+        return h, e
+
+
 class HeteroConv(nn.Module):
     """PyG HeteroConv(aggr='sum'): run each relation's conv in
     ``edge_index_dict`` order, sum the outputs that share a target type."""

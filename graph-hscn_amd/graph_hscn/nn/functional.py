@@ -461,6 +461,92 @@ class GINEAggregateFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# GatedGCN's aggregate: e^_k = Dx_i + Ex_j + Ce_k, h_i = Ax_i + sum_k s_k Bx_j / (sum_k s_k + 1e-6), s = sigmoid(e^)
+# --------------------------------------------------------------------------- #
+# csrc/gatedgcn.hip: a row of more than GATEDGCN_LONG_ROW slots (in-degree in the forward and the backward's target
+# walk, out-degree in the source walk) is summed by a whole workgroup in chunks of GATEDGCN_CHUNK slots; both are the
+# library's constants (hscn_gatedgcn_long_row / hscn_gatedgcn_chunk, pinned equal in tests/test_gatedgcn_host.py).
+GATEDGCN_LONG_ROW = 256
+GATEDGCN_CHUNK = 64
+GATEDGCN_MAX_WIDTH = 512
+
+
+def gatedgcn_supported(H: int) -> bool:
+    return bool(_hip.lib().hscn_gatedgcn_supported(int(H)))
+
+
+class GatedGCNAggregateFn(Function):
+    """(Ax, Bx, Dx, Ex [N, H], Ce [E, H]) -> (h [N, H], e_out [E, H]) over ``rel``, with j = src_k, i = dst_k; row k
+    of ``Ce`` and ``e_out`` belongs to edge k of ``rel.edge_index``.  Forward: one launch; kept for backward are Ax, Bx,
+    the two outputs and den [N, H] (the per-node sum of gates).  Backward: the gates are recomputed from ``e_out``; the
+    target-keyed pass gives the gradients of Ce and Dx, the source-keyed pass (``rel.csr_t``, built only then) those of
+    Bx and Ex; the gradient of Ax is the cotangent of h.  Only what ``needs_input_grad`` asks for is computed; a
+    cotangent that autograd leaves out (the edge output of a stack's last layer) is not materialised."""
+
+    @staticmethod
+    def forward(ctx, Ax: Tensor, Bx: Tensor, Dx: Tensor, Ex: Tensor, Ce: Tensor, rel: Relation):
+        Ax, Bx, Dx, Ex, Ce = _c(Ax), _c(Bx), _c(Dx), _c(Ex), _c(Ce)
+        if Ax.dim() != 2:
+            raise ValueError(f"GatedGCNConv: Ax must be [N, H], got {tuple(Ax.shape)}")
+        N, H = Ax.shape
+        if not _hip.lib().hscn_gatedgcn_supported(H):
+            raise ValueError(f"GatedGCNConv: width H={H} outside the kernel's envelope (1 <= H <= {GATEDGCN_MAX_WIDTH})")
+        for name, t in (("Bx", Bx), ("Dx", Dx), ("Ex", Ex)):
+            if t.shape != Ax.shape:
+                raise ValueError(f"GatedGCNConv: {name} is {tuple(t.shape)}, Ax is {tuple(Ax.shape)}")
+        if rel.num_src != N or rel.num_dst != N:
+            raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, x has {N} rows")
+        E = rel.num_edges
+        if Ce.dim() != 2 or Ce.size(0) != E or Ce.size(1) != H:
+            raise ValueError(f"Ce is {tuple(Ce.shape)}; the relation has {E} edges and the layer is {H} wide")
+        csr = rel.csr
+        dev = Ax.device
+        h = torch.empty(N, H, dtype=torch.float32, device=dev)
+        den = torch.empty(N, H, dtype=torch.float32, device=dev)
+        e_out = torch.empty(E, H, dtype=torch.float32, device=dev)
+        call("hscn_gatedgcn_fwd", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid),
+             ptr(rel.edge_index.contiguous()) if E else None, ptr(Ax), ptr(Bx), ptr(Dx), ptr(Ex),
+             ptr(Ce) if E else None, ptr(h), ptr(e_out) if E else None, ptr(den), N, E, H, ptr(csr.flag), stream())
+        ctx.rel = rel
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(Ax, Bx, h, e_out, den)
+        return h, e_out
+
+    @staticmethod
+    def backward(ctx, gh: Optional[Tensor], ge_out: Optional[Tensor]):
+        Ax, Bx, h, e_out, den = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        N, H = Ax.shape
+        E = rel.num_edges
+        need_a, need_b, need_d, need_e, need_c = ctx.needs_input_grad[:5]
+        gh = torch.zeros_like(Ax) if gh is None else _c(gh)
+        ge_out = _c(ge_out)
+        gBx = gDx = gEx = ge = None
+        edges = need_d or need_e or need_c
+        if edges or need_b:
+            csr = rel.csr
+            gn = torch.empty_like(Ax)
+            if edges:
+                ge = torch.empty(E, H, dtype=torch.float32, device=Ax.device)
+                gDx = torch.empty_like(Ax)
+            call("hscn_gatedgcn_bwd_dst", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid),
+                 ptr(rel.edge_index.contiguous()) if E else None, ptr(Ax), ptr(Bx), ptr(h), ptr(e_out) if E else None,
+                 ptr(den), ptr(gh), ptr(ge_out) if (E and ge_out is not None) else None, ptr(gn),
+                 ptr(ge) if (E and edges) else None, ptr(gDx), N, E, H, ptr(csr.flag), stream())
+            if need_b or need_e:
+                if E:
+                    t = rel.csr_t
+                    gBx = torch.empty_like(Ax) if need_b else None
+                    gEx = torch.empty_like(Ax) if need_e else None
+                    call("hscn_gatedgcn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(e_out), ptr(gn), ptr(ge),
+                         ptr(gBx), ptr(gEx), N, E, H, ptr(csr.flag), stream())
+                else:                               # no edge reaches Bx or Ex: exact zeros, not None
+                    gBx = torch.zeros_like(Ax) if need_b else None
+                    gEx = torch.zeros_like(Ax) if need_e else None
+        return (gh if need_a else None, gBx, gDx if need_d else None, gEx, ge if need_c else None, None)
+
+
+# --------------------------------------------------------------------------- #
 # Global attention: block-diagonal multi-head self-attention over a batch (csrc/attention.hip)
 # --------------------------------------------------------------------------- #
 ATTN_MIN_HEAD_DIM = 4

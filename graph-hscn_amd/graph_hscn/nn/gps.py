@@ -7,6 +7,11 @@ connection, dropout and a normalisation:
     h   = h_l + h_a
     h   = norm(h + drop(Linear(2D -> D)(drop(act(Linear(D -> 2D)(h))))))
 
+``local_conv="gatedgcn"`` is GraphGPS's published pairing: the local branch is a ``GatedGCNLayer``, which does its own
+normalisation, activation, dropout and residual, so the layer adds no second dropout or residual around it
+(``h_l = norm(GatedGCNLayer(x, e))``), and it updates the edge features: such a layer returns ``(h, edge_attr_out)``
+and the model hands the second to the next layer.  Every other layer returns a Tensor.
+
 ``local_conv=None`` leaves the local branch out (``h = h_a``): the plain Transformer layer of the LRGB
 "Transformer + PE" baselines.  Every operator is the package's own HIP one: the registry's convolutions,
 ``MultiheadSelfAttention``, ``Linear`` with the activation in its epilogue, the counter-based dropout and the norms."""
@@ -20,10 +25,10 @@ from torch import Tensor
 from .._hip import ACT
 from . import functional as Fh
 from .attention import MultiheadSelfAttention
-from .conv import Linear
+from .conv import GatedGCNLayer, Linear
 from .norm import BatchNorm1d, LayerNorm
 
-LOCAL_CONVS = ("gcn", "gat", "gine")
+LOCAL_CONVS = ("gcn", "gat", "gine", "gatedgcn")
 NORMS = ("layer", "batch", None)
 
 
@@ -52,7 +57,10 @@ class GPSLayer(nn.Module):
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
         self.channels, self.local_conv, self.act, self.dropout = int(channels), local_conv, act, float(dropout)
         self.dropout_seed: Optional[int] = None     # tests pin the masks; None = nn.functional.dropout's default
-        self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
+        if local_conv == "gatedgcn":        # GraphGPS's layer: batch norm, activation, dropout and residual inside
+            self.conv = GatedGCNLayer(channels, dropout, residual=True, act=act)
+        else:
+            self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
         self.attn = MultiheadSelfAttention(channels, num_heads)
         self.norm1_local = _norm(norm, channels) if local_conv is not None else None
         self.norm1_attn = _norm(norm, channels)
@@ -64,14 +72,20 @@ class GPSLayer(nn.Module):
     def uses_edge_attr(self) -> bool:
         return bool(getattr(self.conv, "uses_edge_attr", False))
 
+    @property
+    def updates_edge_attr(self) -> bool:
+        return bool(getattr(self.conv, "updates_edge_attr", False))
+
     def _drop(self, x: Tensor, k: int) -> Tensor:
         seed = None if self.dropout_seed is None else self.dropout_seed + k
         return Fh.dropout(x, p=self.dropout, training=self.training, seed=seed)
 
     def forward(self, x: Tensor, edge_index, batch=None, edge_attr: Optional[Tensor] = None, *,
-                ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None) -> Tensor:
+                ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None):
         """``batch``: the ``Batch`` (graph boundaries of the attention), or ``ptr32`` and ``max_nodes``.  ``edge_attr``
-        is read by an edge-aware ``local_conv`` ("gine") only."""
+        is read by an edge-aware ``local_conv`` ("gine", "gatedgcn") only.  Returns the node features; with a
+        ``local_conv`` that updates the edge features ("gatedgcn") the pair ``(h, edge_attr_out)``."""
+        edge_out = None
         h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes)
         h_a = x + self._drop(h_a, 1)
         if self.norm1_attn is not None:
@@ -80,11 +94,14 @@ class GPSLayer(nn.Module):
         if self.conv is not None:
             if self.uses_edge_attr:
                 if edge_attr is None:
-                    raise ValueError("local_conv 'gine' needs edge_attr [E, De]")
-                h_l = self.conv(x, edge_index, edge_attr)
+                    raise ValueError(f"local_conv {self.local_conv!r} needs edge_attr [E, De]")
+            if self.updates_edge_attr:
+                self.conv.dropout_seed = self.dropout_seed      # (+ 0: the seed the local branch's dropout has)
+                h_l, edge_out = self.conv(x, edge_index, edge_attr)
+            elif self.uses_edge_attr:
+                h_l = x + self._drop(self.conv(x, edge_index, edge_attr), 0)
             else:
-                h_l = self.conv(x, edge_index)
-            h_l = x + self._drop(h_l, 0)
+                h_l = x + self._drop(self.conv(x, edge_index), 0)
             if self.norm1_local is not None:
                 h_l = self.norm1_local(h_l)
             h = h_l + h_a
@@ -92,4 +109,4 @@ class GPSLayer(nn.Module):
         h = h + self._drop(Fh.linear_wide(self._drop(f, 2), self.ff_linear2.weight, self.ff_linear2.bias), 3)
         if self.norm2 is not None:
             h = self.norm2(h)
-        return h
+        return (h, edge_out) if self.updates_edge_attr else h

@@ -1454,6 +1454,50 @@ int hscn_attention_bwd_kv(const float* qkv, const float* lse, const float* delta
                           const int32_t* ptr32, int64_t N, int64_t B, int max_nodes, int heads, int dh,
                           float* g_qkv /*[N, 3D]*/, int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * GatedGCN's aggregate (GraphGPS GatedGCNLayer, residual gated graph ConvNets; csrc/gatedgcn.hip).  Purely additive
+ * to ABI 24.  With j = src_k, i = dst_k and Ax, Bx, Dx, Ex [N, H], Ce [E, H] already transformed (row k of Ce, e_out
+ * and ge belongs to edge k of the edge list, not to a CSR slot):
+ *
+ *   e_out_k = Dx_i + Ex_j + Ce_k        s_k = 1 / (1 + exp(-e_out_k))
+ *   h_i     = Ax_i + (sum_{k: dst_k = i} s_k * Bx_j) / (den_i + 1e-6),   den_i = sum_{k: dst_k = i} s_k
+ *
+ * Every listed edge counts (loops, repeats).  Sums run in CSR slot order with separately rounded multiply and add; rows
+ * of more than hscn_gatedgcn_long_row() slots are summed by a whole workgroup in chunks of hscn_gatedgcn_chunk()
+ * slots, the partials added in chunk order: a row depends on the row alone, the same input gives the same bits.
+ *
+ * hscn_gatedgcn_fwd: ONE launch over the target-keyed stable CSR; writes h, den [N, H] and e_out [E, H] (plain stores
+ *   at row eid[slot]).  A node without edges gets h_i = Ax_i bit for bit.
+ * hscn_gatedgcn_bwd_dst: ONE launch over the same CSR.  gn_i = gh_i / (den_i + 1e-6) is stored ([N, H]).  With ge and
+ *   gDx given it also walks the edges: ge_k = g_e_out_k + (gn_i Bx_j - gn_i (h_i - Ax_i)) s_k (1 - s_k), stored once
+ *   (the gradient of Ce), and gDx_i = sum ge_k.  g_e_out may be NULL (no cotangent for e_out).  ge = gDx = NULL: gn
+ *   alone (only Bx asks for a gradient).
+ * hscn_gatedgcn_bwd_src: ONE launch over the source-keyed CSR: gBx_j = sum_{k: src_k = j} s_k gn_i and
+ *   gEx_j = sum ge_k; either output may be NULL and is then not computed.  The gradient of Ax is gh itself.
+ *   No float atomics anywhere: every output row has one owner.
+ * flag [1] i32: the CSR's flag word.  It is read: when it is non-zero (hscn_csr_build left an edge out because a node
+ *   id lies outside [0, N)), fwd / bwd_dst store a ZERO row of e_out / ge for every such edge of edge_index, so no
+ *   row of either is left unwritten.  Bit 1 is OR-ed in for a slot with a column outside [0, N) or an eid outside
+ *   [0, E) (the slot adds nothing; hscn_csr_build never produces one).
+ *   HSCN_E_BADARG for null pointers (col / eid / edge_index / Ce / e_out / ge may be NULL when E == 0) and negative
+ *   sizes; HSCN_E_UNSUPPORTED where hscn_gatedgcn_supported is 0 (H outside [1, 512]); both before any launch.
+ *   N = 0 launches nothing.  No workspace, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_gatedgcn_supported(int H);
+int hscn_gatedgcn_long_row(void);
+int hscn_gatedgcn_chunk(void);
+int hscn_gatedgcn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int64_t* edge_index,
+                      const float* Ax, const float* Bx, const float* Dx, const float* Ex, const float* Ce,
+                      float* h /*[N, H]*/, float* e_out /*[E, H]*/, float* den /*[N, H]*/, int64_t N, int64_t E, int H,
+                      int32_t* flag /*[1]*/, void* stream);
+int hscn_gatedgcn_bwd_dst(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int64_t* edge_index,
+                          const float* Ax, const float* Bx, const float* h, const float* e_out, const float* den,
+                          const float* gh, const float* g_e_out, float* gn /*[N, H]*/, float* ge /*[E, H]*/,
+                          float* gDx /*[N, H]*/, int64_t N, int64_t E, int H, int32_t* flag /*[1]*/, void* stream);
+int hscn_gatedgcn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const float* e_out,
+                          const float* gn, const float* ge, float* gBx /*[N, H]*/, float* gEx /*[N, H]*/, int64_t N,
+                          int64_t E, int H, int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
