@@ -213,6 +213,17 @@ _SIGNATURES = {
     "hscn_gatedgcn_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
     "hscn_gatedgcn_bwd_dst": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
     "hscn_gatedgcn_bwd_src": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
+    # categorical encoders: gather-sum, stable counting sort, long-row segment reduce (csrc/catenc.hip; additive to
+    # ABI 24); `card_host`: a host array of F int32 (host_cards)
+    "hscn_catenc_supported": (c_int, [c_int, c_int, c_int]),
+    "hscn_catenc_long_row": (c_int, []),
+    "hscn_catenc_chunk": (c_int, []),
+    "hscn_catenc_sort_chunk": (c_int, []),
+    "hscn_catenc_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, P, P]),
+    "hscn_catenc_index_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "hscn_catenc_index_build": (c_int, [P, P, c_int64, c_int, P, P, P, P, c_size_t, P]),
+    "hscn_catenc_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "hscn_catenc_bwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, P, P, c_size_t, P]),
 }
 
 

@@ -53,6 +53,21 @@ CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE, "gat
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
 SCHEDULERS = ("cosine_with_warmup", "linear_with_warmup", "step")  # extension: optim.SCHEDULE_KINDS
 TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "graph" only
+# extension: categorical input encoders in front of a model (encoder/categorical.py: OGB's AtomEncoder / BondEncoder)
+NODE_ENCODERS = ("atom",)
+EDGE_ENCODERS = ("bond",)
+# conv_type / local_conv_type whose layers read ``edge_attr`` (nn/conv.py ``uses_edge_attr``): what an edge encoder feeds
+EDGE_AWARE_CONVS = ("gine", "gatedgcn")
+
+
+def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
+    if node_encoder not in (None,) + NODE_ENCODERS:
+        raise ValueError(f"node_encoder must be one of {NODE_ENCODERS} or None, got {node_encoder!r}")
+    if edge_encoder not in (None,) + EDGE_ENCODERS:
+        raise ValueError(f"edge_encoder must be one of {EDGE_ENCODERS} or None, got {edge_encoder!r}")
+    if edge_encoder is not None and (conv_type is None or conv_type.lower() not in EDGE_AWARE_CONVS):
+        raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution {EDGE_AWARE_CONVS}, "
+                         f"got {conv_type!r}")
 DATASETS_NUM_FEATURES: dict[str, int] = {"peptides_func": 9, "peptides_struct": 9}
 
 
@@ -85,10 +100,15 @@ class MPNNConfig:  # config.py:49-73
     # extension: "node" = one prediction per node (model/mpnn.py MPNN(task_level="node")); "link" = one score per
     # candidate pair of nodes, num_classes being the embedding width; "graph": the reference
     task_level: str = "graph"
+    # extension: "atom" = an AtomEncoder(hidden_channels) in front (x stays int64; the first convolution is H -> H);
+    # "bond" = a BondEncoder(hidden_channels) whose output the edge-aware convolutions read as edge_attr
+    node_encoder: Optional[str] = None
+    edge_encoder: Optional[str] = None
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        _check_encoders(self.node_encoder, self.edge_encoder, self.conv_type)
         if self.dropout and not (0.0 <= self.dropout <= 1.0):
             raise ValueError(f"{self.dropout} must be between 0.0 and 1.0.")
         for v in (self.num_layers, self.hidden_channels):
@@ -115,10 +135,14 @@ class GPSConfig:
     dropout: float = DROPOUT
     norm: Optional[str] = "layer"
     task_level: str = "graph"
+    # "atom" / "bond": an AtomEncoder / BondEncoder of width hidden_channels in place of the Linear node / edge encoder
+    node_encoder: Optional[str] = None
+    edge_encoder: Optional[str] = None
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        _check_encoders(self.node_encoder, self.edge_encoder, self.local_conv_type)
         if self.dropout and not (0.0 <= self.dropout < 1.0):
             raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
         for v in (self.num_layers, self.hidden_channels, self.num_heads):

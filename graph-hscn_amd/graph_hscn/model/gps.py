@@ -8,7 +8,10 @@
 
 ``local_conv=None`` is the plain Transformer (with a positional encoding in front: LRGB's "Transformer + LapPE").
 The model takes a homogeneous ``Batch`` and offers the surface ``train.batching`` and ``train.train`` use for one.  It
-runs on the layered operators only: there is no one-launch or captured form of global attention."""
+runs on the layered operators only: there is no one-launch or captured form of global attention.
+
+``node_encoder="atom"`` / ``edge_encoder="bond"`` put OGB's categorical encoders (``encoder/categorical.py``) in place of
+the Linear node / edge encoder; ``batch.x`` / ``batch.edge_attr`` are then int64 categories."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -18,6 +21,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from ..config.config import ACT_DICT, GPSConfig
+from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
 from ..nn import functional as Fh
 from ..nn.conv import Linear
 from ..nn.gps import GPSLayer
@@ -33,8 +37,16 @@ class GPS(nn.Module):
 
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
                  local_conv: Optional[str] = "gine", activation: Optional[Callable] = None, dropout: float = 0.0,
-                 norm: Optional[str] = "layer", task_level: str = "graph") -> None:
+                 norm: Optional[str] = "layer", task_level: str = "graph", node_encoder: Optional[str] = None,
+                 edge_encoder: Optional[str] = None) -> None:
+        """``node_encoder="atom"`` / ``edge_encoder="bond"``: an ``AtomEncoder(D)`` / ``BondEncoder(D)`` over int64
+        categories in place of the Linear node / edge encoder (for "gine" the bond encoder supplies the ``edge_attr``
+        the layer's own edge Linear reads).  The defaults build the model as it always was."""
         super().__init__()
+        if node_encoder not in (None,) + tuple(NODE_ENCODERS):
+            raise ValueError(f"node_encoder must be one of {sorted(NODE_ENCODERS)} or None, not {node_encoder!r}")
+        if edge_encoder not in (None,) + tuple(EDGE_ENCODERS):
+            raise ValueError(f"edge_encoder must be one of {sorted(EDGE_ENCODERS)} or None, not {edge_encoder!r}")
         if task_level not in ("graph", "node", "link"):
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
         if num_layers < 1:
@@ -49,9 +61,15 @@ class GPS(nn.Module):
         self.dropout = float(dropout)
         self.dropout_seed: Optional[int] = None     # tests pin the masks (layer i draws with seeds + 4 i .. + 4 i + 3)
         D = int(hidden_channels)
-        self.node_encoder = Linear(num_features, D)
+        self.encoder_kinds = (node_encoder, edge_encoder)
+        self.node_encoder = Linear(num_features, D) if node_encoder is None else NODE_ENCODERS[node_encoder](D)
         self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act) for _ in range(num_layers))
-        if self.layers[0].updates_edge_attr:        # "gatedgcn": edge features are a state of width D
+        if edge_encoder is not None:
+            if not self.layers[0].uses_edge_attr:
+                raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware local_conv ('gine' or 'gatedgcn'), "
+                                 f"not {local_conv!r}")
+            self.edge_encoder = EDGE_ENCODERS[edge_encoder](D)
+        elif self.layers[0].updates_edge_attr:      # "gatedgcn": edge features are a state of width D
             self.edge_encoder = Linear(-1, D)
         self.lin_1 = Linear(D, D)
         self.lin_2 = Linear(D, num_classes)
@@ -62,6 +80,8 @@ class GPS(nn.Module):
 
     # ---- the surface of a homogeneous model (train.batching, train.train) ----------------------------------------
     def resident_reason(self, batch=None, need_grad: bool = False) -> str:
+        if any(self.encoder_kinds):
+            return RESIDENT_REASON + "; " + encoder_reason(*self.encoder_kinds)
         return RESIDENT_REASON
 
     def supported(self, batch=None) -> bool:
@@ -76,6 +96,8 @@ class GPS(nn.Module):
         ``max_nodes`` (``nn.functional.check_attention``).  ``train.train_epoch`` / ``eval_epoch`` call it once per
         epoch, beside the read of the epoch's loss."""
         Fh.check_attention(next(self.parameters()).device)
+        if any(self.encoder_kinds):                # and the categorical encoders' (an index outside its column)
+            Fh.check_categorical(next(self.parameters()).device)
 
     # ---- forward -----------------------------------------------------------------------------------------------
     def _edge_attr(self, batch) -> Tensor:
@@ -86,6 +108,8 @@ class GPS(nn.Module):
             raise ValueError(f"the model has edge-aware convolutions (local_conv {self.layers[0].local_conv!r}) and "
                              "the batch carries no edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
         dev = next(self.parameters()).device
+        if self.encoder_kinds[1] is not None:       # int64 categories: the bond encoder checks them itself
+            return ea
         if ea.dtype != torch.float32 or ea.device != dev:
             raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
                             f"{ea.device} (train.batching.to_device casts integer bond features)")
@@ -100,7 +124,7 @@ class GPS(nn.Module):
         self.last_engine = "layered"
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
         x = self.node_encoder(batch.x)
-        if self.layers[0].updates_edge_attr:
+        if self.layers[0].updates_edge_attr or self.encoder_kinds[1] is not None:
             edge_attr = self.edge_encoder(edge_attr)
         for i, layer in enumerate(self.layers):
             layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
@@ -138,4 +162,4 @@ class GPS(nn.Module):
 def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:
     return GPS(num_features, model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.num_heads,
                model_cfg.local_conv_type, ACT_DICT[model_cfg.activation.lower()], model_cfg.dropout, model_cfg.norm,
-               model_cfg.task_level)
+               model_cfg.task_level, getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None))

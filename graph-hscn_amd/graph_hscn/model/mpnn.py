@@ -20,6 +20,7 @@ from torch import Tensor
 
 from .. import _hip
 from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig
+from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
 from ..nn.conv import GCNConv
 from ..nn import functional as Fh
 from ..nn.norm import BatchNorm1d, LayerNorm
@@ -29,16 +30,37 @@ from ..nn.pool import global_mean_pool
 class MPNN(nn.Module):
     def __init__(self, conv: type, activation: Callable, num_features: int, hidden_channels: int,
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
-                 use_layer_norm: bool = False, task_level: str = "graph") -> None:
+                 use_layer_norm: bool = False, task_level: str = "graph", node_encoder: Optional[str] = None,
+                 edge_encoder: Optional[str] = None) -> None:
         """``task_level`` (extension; the default "graph" is the reference's model): "node" returns the last
         convolution's ``[N, C]`` without the per-graph mean.  "link": ``num_classes`` is the embedding width D,
         ``embed`` is that node-level output and ``forward`` scores the batch's candidate pairs
-        ``batch.edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P]."""
+        ``batch.edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P].
+
+        ``node_encoder="atom"`` (extension): ``batch.x`` holds int64 categories, an ``AtomEncoder(hidden_channels)``
+        embeds them and the first convolution is ``H -> H``.  ``edge_encoder="bond"``: a ``BondEncoder(hidden_channels)``
+        embeds the int64 ``batch.edge_attr`` for the edge-aware convolutions.  Either makes the model layered-only."""
         super().__init__()
         if task_level not in ("graph", "node", "link"):
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
+        if node_encoder not in (None,) + tuple(NODE_ENCODERS):
+            raise ValueError(f"node_encoder must be one of {sorted(NODE_ENCODERS)} or None, not {node_encoder!r}")
+        if edge_encoder not in (None,) + tuple(EDGE_ENCODERS):
+            raise ValueError(f"edge_encoder must be one of {sorted(EDGE_ENCODERS)} or None, not {edge_encoder!r}")
+        if edge_encoder is not None and not getattr(conv, "uses_edge_attr", False):
+            raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution (conv_type 'gine' or "
+                             f"'gatedgcn'), not {getattr(conv, '__name__', conv)}")
         self.task_level = task_level
         self.num_layers = num_layers
+        self.encoder_kinds = (node_encoder, edge_encoder)
+        if node_encoder is not None or edge_encoder is not None:
+            # train.batching.refuse_layered_only: the resident and device-dataset entry points refuse this model by name
+            self.layered_only = True
+        if node_encoder is not None:
+            self.node_encoder = NODE_ENCODERS[node_encoder](hidden_channels)
+            num_features = hidden_channels
+        if edge_encoder is not None:
+            self.edge_encoder = EDGE_ENCODERS[edge_encoder](hidden_channels)
         self.conv_layers = nn.ModuleList()                                  # mpnn.py:27-32
         self.conv_layers.append(conv(num_features, hidden_channels))
         for _ in range(num_layers - 2):
@@ -62,6 +84,8 @@ class MPNN(nn.Module):
 
     def resident_reason(self, batch=None, need_grad: bool = False) -> Optional[str]:
         """Why this model (and ``batch``, if given) cannot take the one-launch MPNN kernels, or None when it can."""
+        if any(self.encoder_kinds):
+            return encoder_reason(*self.encoder_kinds)
         if self.task_level == "node":
             return ("a node-level head (task_level='node'): the one-launch kernels end in the per-graph mean, a "
                     "per-node prediction runs on the layered operators")
@@ -147,14 +171,24 @@ class MPNN(nn.Module):
             raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
         return self._forward(batch)
 
+    def check_flags(self) -> None:
+        """Synchronising, for a model with a categorical encoder only: raises ``IndexError`` if a launch since the last
+        check met a category outside its column's range (``nn.functional.check_categorical``).  ``train.train_epoch``
+        / ``eval_epoch`` call it once per epoch; a model without an encoder has no flag word and nothing is read."""
+        if any(self.encoder_kinds):
+            Fh.check_categorical(next(self.parameters()).device)
+
     def _edge_attr(self, batch) -> Tensor:
-        """``batch.edge_attr`` for the layers with ``uses_edge_attr``: float32 [E, De] on the model's device."""
+        """``batch.edge_attr`` for the layers with ``uses_edge_attr``: float32 [E, De] on the model's device (with an
+        edge encoder: the int64 categories, embedded)."""
         ea = getattr(batch, "edge_attr", None)
         if ea is None:
             kind = "gatedgcn" if any(getattr(c, "updates_edge_attr", False) for c in self.conv_layers) else "gine"
             raise ValueError(f"the model has edge-aware convolutions (conv_type {kind!r}) and the batch carries no "
                              "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
         dev = next(self.parameters()).device
+        if self.encoder_kinds[1] is not None:
+            return self.edge_encoder(ea)
         if ea.dtype != torch.float32 or ea.device != dev:
             raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
                             f"{ea.device} (train.batching.to_device casts integer bond features)")
@@ -163,7 +197,7 @@ class MPNN(nn.Module):
     def _forward(self, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
-        if self.engine == "resident" and self.task_level != "graph":
+        if self.engine == "resident" and (self.task_level != "graph" or any(self.encoder_kinds)):
             raise RuntimeError(f"engine='resident' does not take this model: {self.resident_reason()}")
         if self.engine != "layered" and not torch.is_grad_enabled():
             reason = self.resident_reason(batch)
@@ -176,6 +210,8 @@ class MPNN(nn.Module):
                 raise RuntimeError(f"engine='resident' requested but the model / batch does not qualify: {reason}")
         self.last_engine = "layered"
         x, edge_index, batch_vec = batch.x, batch.edge_index, batch.batch   # mpnn.py:50
+        if self.encoder_kinds[0] is not None:
+            x = self.node_encoder(x)
         edge_attr = self._edge_attr(batch) if any(getattr(c, "uses_edge_attr", False) for c in self.conv_layers) else None
 
         def conv(i, x, **kw):                                               # edge-aware layers also take edge_attr
@@ -207,4 +243,5 @@ class MPNN(nn.Module):
 def build_mpnn(model_cfg: MPNNConfig, num_features: int, num_classes: int) -> MPNN:  # mpnn.py:65-78
     return MPNN(CONV_DICT[model_cfg.conv_type.lower()], ACT_DICT[model_cfg.activation.lower()], num_features,
                 model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.dropout,
-                model_cfg.use_batch_norm, model_cfg.use_layer_norm, getattr(model_cfg, "task_level", "graph"))
+                model_cfg.use_batch_norm, model_cfg.use_layer_norm, getattr(model_cfg, "task_level", "graph"),
+                getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None))

@@ -15,7 +15,7 @@ from torch.autograd import Function
 
 from .. import _hip
 from .._hip import ACT, call, ptr, stream
-from ..structure import CSR, Relation
+from ..structure import CSR, Relation, category_index_of, host_cards
 
 
 def _c(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -630,6 +630,114 @@ class SelfAttentionFn(Function):
         call("hscn_attention_bwd_kv", ptr(qkv), ptr(lse), ptr(delta), ptr(g_out), ptr(ptr32), N, B, max_nodes, heads,
              dh, ptr(g_qkv), ptr(flag), stream())
         return g_qkv, None, None, None
+
+
+# --------------------------------------------------------------------------- #
+# Categorical encoders: out[i] = sum_c W[off_c + idx[i, c]] in column order (csrc/catenc.hip)
+# --------------------------------------------------------------------------- #
+# the kernels' envelope (hscn_catenc_supported; pinned equal in tests/test_categorical_host.py)
+CATENC_MAX_WIDTH = 512
+CATENC_MAX_COLUMNS = 16
+CATENC_MAX_ROWS = 4096
+CATENC_ENVELOPE = (f"emb_dim a multiple of 4 in [4, {CATENC_MAX_WIDTH}], at most {CATENC_MAX_COLUMNS} columns, "
+                   f"at most {CATENC_MAX_ROWS} categories in all")
+CATENC_BAD_INDEX = 1              # flag bit 0: an index outside [0, cardinality) of its column (its term is skipped)
+
+_CATENC_FLAGS = {}
+
+
+def catenc_supported(D: int, F: int, R: int) -> bool:
+    """``hscn_catenc_supported`` restated on the host (a module is built before any device is touched)."""
+    return (4 <= D <= CATENC_MAX_WIDTH and D % 4 == 0 and 1 <= F <= CATENC_MAX_COLUMNS and F <= R <= CATENC_MAX_ROWS)
+
+
+def categorical_flags(device) -> Tensor:
+    """The device's flag word [1] int32 that every categorical-encoder launch ORs into; ``check_categorical`` reads
+    and clears it."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    t = _CATENC_FLAGS.get(device)
+    if t is None:
+        t = _CATENC_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def check_categorical(device) -> None:
+    """Synchronising: ``IndexError`` if a categorical-encoder launch since the last check met an index outside
+    [0, cardinality) of its column (the term was skipped, nothing was read out of bounds)."""
+    word = categorical_flags(device)
+    f = int(word.item())
+    if f:
+        word.zero_()
+        raise IndexError("categorical encoder: a feature holds an index outside [0, cardinality) of its column "
+                         "(its embedding was left out of the sum)")
+
+
+def categorical_embed_reference(weight: Tensor, idx: Tensor, cardinalities) -> Tensor:
+    """The plain-torch restatement (OGB's loop): ``index_select`` per column out of the column's own block (so that
+    torch's bounds check is the column's), added in column order."""
+    out, off = 0, 0
+    for c, card in enumerate(cardinalities):
+        out = out + weight.narrow(0, off, int(card)).index_select(0, idx[:, c])
+        off += int(card)
+    return out
+
+
+class CategoricalEmbedFn(Function):
+    """(weight [R, D], idx int64 [n, F], cardinalities) -> out [n, D] = sum_c weight[off_c + idx[i, c]], the adds in
+    column order.  On a CPU weight it is ``categorical_embed_reference`` with autograd's own backward (the oracle of
+    the tests).  On the device: one gather launch; the backward builds the ``CategoryIndex`` of ``idx`` (cached per
+    tensor) and sums each table row's cotangent rows in item order -- no float atomics, the same bits every run."""
+
+    @staticmethod
+    def forward(ctx, weight: Tensor, idx: Tensor, cardinalities):
+        cards = tuple(int(c) for c in cardinalities)
+        if idx.dtype != torch.int64:
+            raise TypeError(f"categorical features must be int64, got {idx.dtype}")
+        if weight.dim() != 2 or idx.dim() != 2 or idx.size(1) != len(cards) or weight.size(0) != sum(cards):
+            raise ValueError(f"weight {tuple(weight.shape)} / idx {tuple(idx.shape)} do not fit the cardinalities "
+                             f"{cards} (weight [{sum(cards)}, D], idx [n, {len(cards)}])")
+        ctx.cards = cards
+        if not weight.is_cuda:
+            with torch.enable_grad():
+                w = weight.detach().requires_grad_(True)
+                out = categorical_embed_reference(w, idx, cards)
+            ctx.cpu = (w, out)
+            return out.detach()
+        n, F, (R, D) = int(idx.size(0)), len(cards), weight.shape
+        if not _hip.lib().hscn_catenc_supported(D, F, R):
+            raise ValueError(f"categorical encoder: D={D}, F={F}, R={R} outside the kernel's envelope ({CATENC_ENVELOPE})")
+        if idx.device != weight.device:
+            raise RuntimeError(f"idx is on {idx.device}, the table on {weight.device}")
+        weight = _c(weight)
+        out = torch.empty(n, D, dtype=torch.float32, device=weight.device)
+        call("hscn_catenc_fwd", ptr(weight), ptr(idx.contiguous()) if n else None, host_cards(cards), ptr(out), n, F, D,
+             ptr(categorical_flags(weight.device)), stream())
+        ctx.idx = idx
+        ctx.dims = (n, F, R, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out: Tensor):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        if hasattr(ctx, "cpu"):
+            w, out = ctx.cpu
+            return torch.autograd.grad(out, w, g_out)[0], None, None
+        n, F, R, D = ctx.dims
+        index = category_index_of(ctx.idx, ctx.cards)
+        g_out = _c(g_out)
+        gW = torch.empty(R, D, dtype=torch.float32, device=g_out.device)
+        ws_bytes = int(_hip.lib().hscn_catenc_bwd_workspace_bytes(n, F, R, D))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g_out.device)
+        call("hscn_catenc_bwd", ptr(index.rowptr), ptr(index.item), ptr(g_out) if n else None, ptr(gW), n, F, R, D,
+             ptr(categorical_flags(g_out.device)), ptr(ws), ws_bytes, stream())
+        return gW, None, None
+
+
+def categorical_embed(weight: Tensor, idx: Tensor, cardinalities) -> Tensor:
+    return CategoricalEmbedFn.apply(weight, idx, tuple(cardinalities))
 
 
 # --------------------------------------------------------------------------- #

@@ -208,9 +208,79 @@ def self_loop_relation_of(edge_index: Tensor, num_nodes: int, both: bool = False
     return rel
 
 
+def host_cards(cardinalities):
+    """The ``card_host`` argument of the hscn_catenc_* entry points: a host array of F int32."""
+    import ctypes
+    return (ctypes.c_int32 * len(cardinalities))(*[int(c) for c in cardinalities])
+
+
+@dataclass
+class CategoryIndex:
+    """The inverted index of an integer feature tensor ``idx`` [n, F] over the rows of a categorical encoder's table
+    (column c owns rows off_c .. off_c + card_c - 1): slots ``rowptr[r] .. rowptr[r + 1]`` of ``item`` hold the ids
+    i with ``off_c + idx[i, c] == r`` in ascending order.  What the encoder's backward sums over."""
+    rowptr: Tensor   # int32 [R + 1]
+    item: Tensor     # int32 [max(n F, 1)]; slots past rowptr[R] are unwritten
+    flag: Tensor     # int32 [1]; non-zero if an index was outside its column and left out
+    num_items: int   # n
+    cardinalities: Tuple[int, ...]
+    idx: Tensor      # the tensor it was built for (keeps the cache key's pointer alive)
+
+    @property
+    def num_rows(self) -> int:
+        return int(sum(self.cardinalities))
+
+    def check(self) -> None:
+        """Synchronising validity check (out-of-range categories)."""
+        if int(self.flag.item()) != 0:
+            raise IndexError("a categorical feature holds an index outside [0, cardinality) of its column")
+
+
+def build_category_index(idx: Tensor, cardinalities) -> CategoryIndex:
+    """int64 [n, F] -> CategoryIndex through hscn_catenc_index_build (a stable counting sort; no host round trip)."""
+    if idx.dtype != torch.int64:
+        raise TypeError("categorical features must be int64")
+    cards = tuple(int(c) for c in cardinalities)
+    if idx.dim() != 2 or idx.size(1) != len(cards):
+        raise ValueError(f"categorical features must be [n, {len(cards)}], got {tuple(idx.shape)}")
+    src = idx.contiguous()
+    dev = idx.device
+    n, F, R = int(idx.size(0)), len(cards), sum(cards)
+    rowptr = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    item = torch.empty(max(n * F, 1), dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(_hip.lib().hscn_catenc_index_workspace_bytes(n, F, R))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    _hip.call("hscn_catenc_index_build", _hip.ptr(src) if n else None, host_cards(cards), n, F, _hip.ptr(rowptr),
+              _hip.ptr(item), _hip.ptr(flag), _hip.ptr(ws), ws_bytes, _hip.stream())
+    return CategoryIndex(rowptr, item, flag, n, cards, idx)
+
+
+_CAT_CACHE: "OrderedDict[Tuple, CategoryIndex]" = OrderedDict()
+
+
+def category_index_of(idx: Tensor, cardinalities, cache: bool = True) -> CategoryIndex:
+    """CategoryIndex for ``idx``; cached per tensor (pointer, shape, strides, version) as ``relation_of`` caches a
+    Relation, so repeated epochs over the same batch build it once."""
+    if not cache:
+        return build_category_index(idx, cardinalities)
+    cards = tuple(int(c) for c in cardinalities)
+    key = (idx.data_ptr(), tuple(idx.shape), tuple(idx.stride()), idx._version, str(idx.device), cards)
+    hit = _CAT_CACHE.get(key)
+    if hit is not None and hit.idx is idx:
+        _CAT_CACHE.move_to_end(key)
+        return hit
+    hit = build_category_index(idx, cards)
+    _CAT_CACHE[key] = hit
+    while len(_CAT_CACHE) > _CACHE_MAX:
+        _CAT_CACHE.popitem(last=False)
+    return hit
+
+
 def clear_cache() -> None:
     _LOOP_CACHE.clear()
     _CACHE.clear()
+    _CAT_CACHE.clear()
 
 
 def segments_from_batch(batch: Tensor, num_segments: Optional[int] = None) -> CSR:

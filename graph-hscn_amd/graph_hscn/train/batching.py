@@ -111,11 +111,20 @@ def to_device(model, batch, device):
     """A loader's batch where the HIP operators can take it."""
     batch = batch.to(device)
     if not is_hetero(model):
-        batch.x = batch.x.float()
+        # a categorical encoder (model.encoder_kinds: node, edge) reads its tensor as int64 categories
+        node_enc, edge_enc = getattr(model, "encoder_kinds", (None, None))
+        batch.x = batch.x.float() if node_enc is None else _categories(batch.x, "x")
         edge_attr = getattr(batch, "edge_attr", None)
         if edge_attr is not None:                   # OGB bond features are integers
-            batch.edge_attr = edge_attr.float()
+            batch.edge_attr = edge_attr.float() if edge_enc is None else _categories(edge_attr, "edge_attr")
     return batch
+
+
+def _categories(t: Tensor, name: str) -> Tensor:
+    if t.is_floating_point():
+        raise TypeError(f"the model has a categorical encoder for {name}, which reads integer categories; the batch "
+                        f"carries {t.dtype}")
+    return t.long()
 
 
 def collate(model, graphs: Sequence, device):

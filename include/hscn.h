@@ -1498,6 +1498,48 @@ int hscn_gatedgcn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const i
                           const float* gn, const float* ge, float* gBx /*[N, H]*/, float* gEx /*[N, H]*/, int64_t N,
                           int64_t E, int H, int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Categorical encoders (OGB AtomEncoder / BondEncoder; csrc/catenc.hip).  Purely additive to ABI 24.  F integer
+ * columns share ONE table W [R, D] float32, R = sum_c card_c; column c owns rows off_c .. off_c + card_c - 1 with
+ * off_c = card_0 + .. + card_{c-1}.  idx is int64 [n, F], row-major.  card_host [F] is read on the HOST during the
+ * call (it travels as a launch argument), every other pointer is device memory.
+ *
+ * hscn_catenc_supported: 1 for D a multiple of 4 in [4, 512], 1 <= F <= 16, F <= R <= 4096.
+ * hscn_catenc_fwd: ONE launch.  out[i] = ((0 + W[off_0 + idx[i,0]]) + W[off_1 + idx[i,1]]) + ..., the adds in column
+ *   order, each rounded separately.  An index outside [0, card_c) is never dereferenced: its term is skipped and bit 0
+ *   of flag is OR-ed in.  n = 0 launches nothing.
+ * hscn_catenc_index_build: four launches, a stable counting sort of the n F items (i, c) by table row
+ *   off_c + idx[i, c]: rowptr [R + 1] (rowptr[R] = the items kept) and item [n F], the ids i of each table row in
+ *   ascending order.  Items with an index outside its column are left out and bit 0 of flag is OR-ed in; item beyond
+ *   rowptr[R] is left unwritten.  Work O(n F + chunks R) with chunks = ceil(n F / hscn_catenc_sort_chunk()); counts
+ *   are integers, nothing depends on an arrival order.  n = 0: rowptr is zeroed.
+ * hscn_catenc_bwd: two launches.  dW[r] = sum over slots p in [rowptr[r], rowptr[r+1]) of dOut[item[p]], every row of
+ *   dW written (a row without items gets exact zeros).  A row of at most hscn_catenc_long_row() slots is summed in
+ *   slot order from zero; a longer one is cut into chunks of hscn_catenc_chunk() slots counted from its first slot,
+ *   each summed in slot order from zero -- by whichever workgroup takes it -- and the partials are added in chunk order
+ *   from zero.  No float atomics: the bits of a row depend on its values in slot order alone, not on the launch
+ *   geometry or on the rest of the batch.  A slot with an id outside [0, n), or a rowptr outside [0, n F], adds
+ *   nothing and ORs bit 1 into flag (hscn_catenc_index_build produces neither).
+ * Workspaces: hscn_catenc_index_workspace_bytes (the per-chunk histograms, R ints per chunk) and
+ *   hscn_catenc_bwd_workspace_bytes = (ceil(n F / chunk) + R) * D floats; neither needs initialising.
+ * HSCN_E_BADARG for null pointers, negative sizes, an empty column or n F beyond INT32_MAX; HSCN_E_UNSUPPORTED outside
+ *   the envelope; HSCN_E_WORKSPACE for a workspace that is too small; all before any launch.  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_catenc_supported(int D, int F, int R);
+int hscn_catenc_long_row(void);
+int hscn_catenc_chunk(void);
+int hscn_catenc_sort_chunk(void);
+int hscn_catenc_fwd(const float* W /*[R, D]*/, const int64_t* idx /*[n, F]*/, const int32_t* card_host /*[F], host*/,
+                    float* out /*[n, D]*/, int64_t n, int F, int D, int32_t* flag /*[1]*/, void* stream);
+size_t hscn_catenc_index_workspace_bytes(int64_t n, int F, int R);
+int hscn_catenc_index_build(const int64_t* idx /*[n, F]*/, const int32_t* card_host /*[F], host*/, int64_t n, int F,
+                            int32_t* rowptr /*[R + 1]*/, int32_t* item /*[n F]*/, int32_t* flag /*[1]*/,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t hscn_catenc_bwd_workspace_bytes(int64_t n, int F, int R, int D);
+int hscn_catenc_bwd(const int32_t* rowptr /*[R + 1]*/, const int32_t* item /*[n F]*/, const float* dOut /*[n, D]*/,
+                    float* dW /*[R, D]*/, int64_t n, int F, int R, int D, int32_t* flag /*[1]*/, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
