@@ -50,6 +50,8 @@ _SIGNATURES = {
     "hscn_segment_mean_bwd": (c_int, [P, P, P, P, c_int64, c_int, P]),
     "hscn_mincut_sparse_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int, P]),
     "hscn_mincut_sparse_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P]),
+    "hscn_dmon_sparse_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int, P]),
+    "hscn_dmon_sparse_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P]),
     "hscn_bgemm_f32": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
                                c_int64, c_int, P]),
     "hscn_mincut_dense_fwd": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P]),

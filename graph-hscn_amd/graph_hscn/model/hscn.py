@@ -26,7 +26,7 @@ from torch import Tensor
 from ..config.config import ACT_DICT, CONV_DICT, HSCNConfig
 from ..nn import GATConv, GCNConv, GraphConv, HeteroConv, Linear
 from ..nn import functional as Fh
-from ..nn.pool import (global_mean_pool, mincut_pool_sparse, to_dense_adj, to_dense_adj_batched,
+from ..nn.pool import (dmon_pool_sparse, global_mean_pool, mincut_pool_sparse, to_dense_adj, to_dense_adj_batched,
                        to_dense_adj_ragged)
 from ..structure import Relation, relation_of
 from .. import engine as _engine
@@ -65,19 +65,34 @@ class _MessagePassingStack(nn.Module):
 
 class SCN(nn.Module):
     def __init__(self, mp_units: list, mp_act: str, num_features: int, num_clusters: int,
-                 mlp_units: list = [], mlp_act: str = "identity", mincut_route: str = "sparse"):
+                 mlp_units: list = [], mlp_act: str = "identity", mincut_route: str = "sparse",
+                 pool: str = "mincut"):
         """``mincut_route`` (extension): how ``dense_mincut_pool``'s contractions are evaluated.
         "sparse" -- on the edge list, A never densified (tr(S^T A S) = sum over edges of s_i . s_j; the fused
         graph-resident launch when the model has the reference's shape);
         "dense"  -- the reference's literal sequence ``to_dense_adj`` -> ``dense_mincut_pool`` (model/hscn.py:61-63)
         with the [B,n,n] adjacency materialised and A S, S^T (A S), S^T S, S^T X on the matrix cores (csrc/dense.hip,
         exact-fp32 MFMA): BASELINE.json configs[3], PascalVOC-SP with 64 clusters;
-        "auto"   -- dense from 64 clusters on.  Same values either way (tests/test_gpu_models.py)."""
+        "auto"   -- dense from 64 clusters on.  Same values either way (tests/test_gpu_models.py).
+
+        ``pool`` (extension): the objective the assignment is fitted with.  "mincut" (default) is the reference's
+        ``dense_mincut_pool`` pair, cut ratio + orthogonality.  "dmon" is DMoN (PyG ``dense_dmon_pool``): modularity
+        with the degree null model, the same orthogonality term and a collapse regulariser on the cluster sizes
+        (``nn.pool.dmon_pool_sparse``, csrc/dmon.hip).  It exists on the edge-list route and the layered operators
+        only: ``forward`` then returns ``(S, spectral_loss, ortho_loss, cluster_loss, adj)`` and ``forward_graphs``
+        ``(S, spectral, ortho, cluster[, total])`` with ``total`` the plain sum of the three."""
         super().__init__()
         if mincut_route not in ("sparse", "dense", "auto"):
             raise ValueError(f"mincut_route must be 'sparse', 'dense' or 'auto', not {mincut_route!r}")
+        if pool not in ("mincut", "dmon"):
+            raise ValueError(f"pool must be 'mincut' or 'dmon', not {pool!r}")
         self.mincut_route = mincut_route
+        self.pool = pool
         self.num_clusters = int(num_clusters)
+        if pool == "dmon" and self._dense():
+            raise ValueError(f"pool='dmon': DMoN runs on the edge-list route only, there is no dense route for it "
+                             f"(mincut_route={mincut_route!r} with {self.num_clusters} clusters selects the dense "
+                             f"route; pass mincut_route='sparse')")
         if _act_name(mp_act) not in ACT_DICT or _act_name(mlp_act) not in ACT_DICT:
             raise KeyError(f"unknown activation {mp_act!r}/{mlp_act!r}")  # ACT_DICT[...] at hscn.py:34,53
         self.mp = _MessagePassingStack(num_features, mp_units, _act_name(mp_act))
@@ -113,6 +128,8 @@ class SCN(nn.Module):
         """Can ``forward_graphs`` take the fused graph-resident path for this input?"""
         if self._dense():
             return False          # the dense route is the layered operators + the MFMA contractions
+        if self.pool != "mincut":
+            return False          # the one-launch stage-A kernels compute MinCUT's losses and nothing else
         layers = list(self.mlp)
         if self.mp.num != 1 or len(layers) != 1:
             return False
@@ -161,6 +178,9 @@ class SCN(nn.Module):
         if not self._dense():
             ei, ew = gcn_norm(raw_ei, None, N, add_self_loops=True)
             node_ptr = data.ptr.to(dev).to(torch.int32) if batched else None
+            if self.pool == "dmon":
+                S, sp, o, cl, _ = self.forward(data.x.to(dev).float(), ei, ew, node_ptr=node_ptr)
+                return (S, sp, o, cl, sp + o + cl) if with_total else (S, sp, o, cl)
             S, mc, o, _ = self.forward(data.x.to(dev).float(), ei, ew, node_ptr=node_ptr)
             return (S, mc, o, mc + o) if with_total else (S, mc, o)
         # dense route: gcn_norm(add_self_loops=True) in its static-shape form and A + I straight from the raw edges --
@@ -240,6 +260,10 @@ class SCN(nn.Module):
             self.last_route = "dense"
             return S.view(n, -1), mc_loss, o_loss, (adj if node_ptr is None else None)
         self.last_route = "sparse"
+        if self.pool == "dmon":
+            S, _, _, sp_loss, o_loss, cl_loss = dmon_pool_sparse(x, rel, s, node_ptr)
+            adj = to_dense_adj(edge_index, n) if node_ptr is None else None
+            return S, sp_loss, o_loss, cl_loss, adj
         S, _, _, mc_loss, o_loss = mincut_pool_sparse(x, rel, s, node_ptr)
         adj = to_dense_adj(edge_index, n) if node_ptr is None else None
         return S, mc_loss, o_loss, adj

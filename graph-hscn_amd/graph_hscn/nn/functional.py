@@ -811,15 +811,64 @@ class MinCutSparseFn(Function):
         return g_logits, None, None, None, None
 
 
-def _pack_loss_grads(g_mc: Optional[Tensor], g_o: Optional[Tensor], dev) -> Tensor:
+def _pack_loss_grads(g_mc: Optional[Tensor], g_o: Optional[Tensor], dev, *more: Optional[Tensor]) -> Tensor:
     """[dL/dmincut, dL/dortho] as one device pair: the two losses are separate autograd outputs (slicing
-    one [2] output costs six fill / copy / add launches in the backward), packing their scalar gradients is one."""
-    if g_mc is None and g_o is None:
-        return torch.zeros(2, dtype=torch.float32, device=dev)
+    one [2] output costs six fill / copy / add launches in the backward), packing their scalar gradients is one.
+    ``more``: further scalar gradients behind the pair (DMoN's third loss)."""
+    gs = (g_mc, g_o) + more
+    if all(g is None for g in gs):
+        return torch.zeros(len(gs), dtype=torch.float32, device=dev)
     z = None
-    if g_mc is None or g_o is None:
+    if any(g is None for g in gs):
         z = torch.zeros((), dtype=torch.float32, device=dev)
-    return torch.stack([(g_mc if g_mc is not None else z).reshape(()), (g_o if g_o is not None else z).reshape(())])
+    return torch.stack([(g if g is not None else z).reshape(()) for g in gs])
+
+
+# --------------------------------------------------------------------------- #
+# DMoN pooling losses on the edge-list route
+# --------------------------------------------------------------------------- #
+DMON_STATS = 8     # floats per graph in hscn_dmon_sparse_fwd's statistics row (include/hscn.h)
+
+
+class DMoNSparseFn(Function):
+    """(logits, x) -> (S, spectral, ortho, cluster, pooled_x, pooled_adj): ``MinCutSparseFn``'s sibling for
+    dense_dmon_pool (csrc/dmon.hip).  Gradients flow from the three losses to ``logits`` only."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, x: Optional[Tensor], rel: Relation, node_ptr: Tensor, num_graphs: int):
+        logits, x = _c(logits), _c(x)
+        n, K = logits.shape
+        dev = logits.device
+        Fx = x.shape[1] if x is not None else 0
+        S = torch.empty_like(logits)
+        stats = torch.empty(num_graphs, DMON_STATS, dtype=torch.float32, device=dev)
+        ss = torch.empty(num_graphs, K, K, dtype=torch.float32, device=dev)
+        vec = torch.empty(num_graphs, 2, K, dtype=torch.float32, device=dev)
+        px = torch.empty(num_graphs, K, max(Fx, 1), dtype=torch.float32, device=dev) if x is not None else None
+        padj = torch.empty(num_graphs, K, K, dtype=torch.float32, device=dev)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        row_csr = rel.csr_t  # keyed by edge ROW (= source side of edge_index)
+        call("hscn_dmon_sparse_fwd", ptr(logits), ptr(x), ptr(row_csr.rowptr), ptr(row_csr.col), ptr(node_ptr),
+             ptr(S), ptr(stats), ptr(ss), ptr(vec), ptr(px), ptr(padj), ptr(losses), n, num_graphs, K, Fx, stream())
+        ctx.rel, ctx.G = rel, num_graphs
+        ctx.save_for_backward(S, stats, ss, vec, node_ptr)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(S, padj)
+        if px is not None:
+            ctx.mark_non_differentiable(px)
+        return S, losses[0], losses[1], losses[2], px, padj
+
+    @staticmethod
+    def backward(ctx, gS, g_sp, g_o, g_cl, g_px, g_padj):
+        S, stats, ss, vec, node_ptr = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        gl = _pack_loss_grads(g_sp, g_o, S.device, g_cl)
+        g_logits = torch.empty_like(S)
+        row_csr, col_csr = rel.csr_t, rel.csr
+        call("hscn_dmon_sparse_bwd", ptr(S), ptr(stats), ptr(ss), ptr(vec), ptr(row_csr.rowptr), ptr(row_csr.col),
+             ptr(col_csr.rowptr), ptr(col_csr.col), ptr(node_ptr), ptr(gl), ptr(g_logits), S.shape[0], ctx.G,
+             S.shape[1], stream())
+        return g_logits, None, None, None, None
 
 
 # --------------------------------------------------------------------------- #

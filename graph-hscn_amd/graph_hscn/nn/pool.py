@@ -151,6 +151,26 @@ def mincut_pool_sparse(x: Optional[Tensor], edge_index: Union[Tensor, Relation],
     return S, px, padj, mc, o
 
 
+def dmon_pool_sparse(x: Optional[Tensor], edge_index: Union[Tensor, Relation], s: Tensor,
+                     node_ptr: Optional[Tensor] = None):
+    """torch_geometric.nn.dense_dmon_pool semantics (DMoN: Tsitsulin et al., "Graph Clustering with Graph Neural
+    Networks") evaluated on the edge list, the sibling of ``mincut_pool_sparse`` with the same inputs: ``A`` is the
+    edge list with multiplicities, ``d`` its out-degrees, ``2m = sum d``;
+    ``spectral = -(tr(S^T A S) - |d^T S|^2 / 2m) / 2m``, MinCUT's orthogonality term, and the collapse regulariser
+    ``|sum_i S_i| sqrt(K) / n - 1``; each loss is the mean over the graphs ``node_ptr`` (int32 ``[G+1]``) delimits.
+    A graph without edges contributes ``spectral = 0`` with zero gradient (PyG divides by zero there).
+
+    Returns ``(S, pooled_x [G,K,F] = selu(S^T X), pooled_adj [G,K,K], spectral_loss, ortho_loss, cluster_loss)``;
+    gradients flow from the three losses to ``s``."""
+    n = s.size(0)
+    rel = edge_index if isinstance(edge_index, Relation) else relation_of(edge_index, n, n)
+    if node_ptr is None:
+        node_ptr = torch.tensor([0, n], dtype=torch.int32, device=s.device)
+    G = int(node_ptr.numel()) - 1
+    S, sp, o, cl, px, padj = Fh.DMoNSparseFn.apply(s, x, rel, node_ptr.to(torch.int32).contiguous(), G)
+    return S, px, padj, sp, o, cl
+
+
 def dense_mincut_pool(x: Tensor, adj: Tensor, s: Tensor, mask: Optional[Tensor] = None):
     """torch_geometric.nn.dense_mincut_pool (reference model/hscn.py:63) on a
     DENSE adjacency ``[B,n,n]`` (2-D inputs are treated as batch 1): the cluster-assignment

@@ -1,6 +1,8 @@
 """Stage A driver: fit the spectral-clustering net with MinCUT + orthogonality
 losses, then hard-assign every node (reference
-/root/reference/graph_hscn/train/train_clustering.py:20-70).
+/root/reference/graph_hscn/train/train_clustering.py:20-70).  An ``SCN(pool="dmon")``
+is fitted with DMoN's spectral + orthogonality + cluster losses instead, on the
+autograd loop over the layered operators (the direct loop declines it).
 
 ``batch_graphs=1`` (default) is the reference's trajectory: ``gcn_norm`` with self
 loops, one optimizer step PER GRAPH (:36-50), then an assignment pass (:57-69, run
@@ -34,6 +36,15 @@ def _assign(S: torch.Tensor) -> torch.Tensor:
 def _forward(model: SCN, graphs: Sequence, device, cache: dict = None, key=None) -> tuple:
     # fused graph-resident path (gcn_norm folded into the kernel) whenever the model/graphs qualify
     hit = cache.get(key) if cache is not None else None
+    if model.pool == "dmon" and cache is not None and (hit is not None or
+                                                       getattr(graphs[0], "edge_weight", None) is None):
+        # DMoN: the layered operators through forward_graphs (the one-launch kernels know MinCUT only); the collated
+        # batch stays on the device between visits like the resident path's.  (S, spectral, ortho, cluster, total)
+        if hit is None:
+            data = graphs[0] if len(graphs) == 1 else Batch.from_data_list(list(graphs))
+            hit = cache[key] = (data.to(device), None if len(graphs) == 1 else data.ptr)
+            hit[0].x = hit[0].x.float()
+        return model.forward_graphs(hit[0], with_total=True), hit[1]
     if hit is not None:
         S, mc, o, total = model.forward_graphs(hit[0], with_total=True)
         return (S, mc, o, total), hit[1]
@@ -71,6 +82,8 @@ def _train_clustering_direct(logger, dataset, model: SCN, model_cfg, optim_cfg, 
     from ..optim import FlatAdam
     from ..replay import capture_optimizer_step
     from ..step import ScnEpochRunner, ScnStructurePool, ScnTrainStep, ScnWorkspace
+    if model.pool != "mincut":
+        return None                          # the one-launch kernels compute MinCUT's losses only
     n = len(dataset)
     if batch_graphs == 1 and epoch_kernel and flat_optimizer and n > 0 and \
             not any(getattr(dataset[j], "edge_weight", None) is not None for j in range(n)):
@@ -173,10 +186,16 @@ def train_clustering(logger, dataset, model: SCN, model_cfg, optim_cfg, training
         for i in range(0, n, batch_graphs):
             graphs = [dataset[j] for j in range(i, min(i + batch_graphs, n))]
             optimizer.zero_grad()
-            (_, mc_loss, o_loss, total), _ = _forward(model, graphs, device, resident, i)
-            # train_clustering.py:48  loss = mc_loss + o_loss (the fused launch already holds the sum;
-            # on the layered path the 4th slot is the dense adjacency placeholder, not a loss)
-            loss = total if model.last_engine == "resident" and total is not None else mc_loss + o_loss
+            out, _ = _forward(model, graphs, device, resident, i)
+            if model.pool == "dmon":
+                # DMoN's objective: spectral + ortho + cluster, the sum PyG's example optimises (MinCUT's sum below
+                # would leave the collapse regulariser out)
+                loss = out[1] + out[2] + out[3]
+            else:
+                _, mc_loss, o_loss, total = out
+                # train_clustering.py:48  loss = mc_loss + o_loss (the fused launch already holds the sum;
+                # on the layered path the 4th slot is the dense adjacency placeholder, not a loss)
+                loss = total if model.last_engine == "resident" and total is not None else mc_loss + o_loss
             loss.backward(root_grad(loss.device))      # no ones_like fill launch
             optimizer.step()
     cluster_all_lst: List[np.ndarray] = []
@@ -185,8 +204,8 @@ def train_clustering(logger, dataset, model: SCN, model_cfg, optim_cfg, training
     with torch.no_grad():
         for i in range(0, n, batch_graphs):
             graphs = [dataset[j] for j in range(i, min(i + batch_graphs, n))]
-            (S, _, _, _), ptr = _forward(model, graphs, device, resident, i)
-            ids = _assign(S).cpu().numpy()
+            out, ptr = _forward(model, graphs, device, resident, i)
+            ids = _assign(out[0]).cpu().numpy()
             if ptr is None:
                 cluster_all_lst.append(ids)
             else:

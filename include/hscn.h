@@ -246,6 +246,39 @@ int hscn_segment_mean_bwd(const int32_t* rowptr, const int64_t* batch /*[num_nod
                           float* g_x, int64_t num_nodes, int width, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * DMoN modularity pooling (Tsitsulin et al., "Graph Clustering with Graph Neural Networks"; PyG dense_dmon_pool)
+ * on the same edge-list route and with the same operands as a6: A = the edge list with multiplicities, never
+ * densified; d_i = out-degree of i (|row i| of the CSR keyed by edge ROW), 2m = sum_i d_i, S = softmax(logits).
+ *   spectral_g = -( sum_i S_i . (A S)_i - sum_k (d^T S)_k^2 / 2m ) / 2m     (0 for a graph with 2m = 0)
+ *   ortho_g    = | S^T S / |S^T S|_F - I / sqrt(K) |_F                       (a6's term)
+ *   cluster_g  = | sum_i S_i |_2 sqrt(K) / n - 1
+ * Per graph outputs (pooled_x / pooled_adj may be NULL):
+ *   S        [N,K]
+ *   stats    [G,8]   {sum_i S_i.(A S)_i, 2m, sum_k (d^T S)_k^2 / 2m, |S^T S|_F, ortho_g, |sum_i S_i|_2,
+ *                     spectral_g, cluster_g}
+ *   ss       [G,K,K] S^T S
+ *   vec      [G,2,K] {d^T S, sum_i S_i}, kept for the backward
+ *   pooled_x [G,K,Fx] selu(S^T X)
+ *   pooled_adj[G,K,K] normalised S^T A S (zero diagonal, d^-1/2 scaling)
+ *   losses   [3]     means over the graphs {spectral, ortho, cluster}
+ * K in [1,256]; HSCN_E_UNSUPPORTED when one graph's accumulators exceed a CU's LDS:
+ *   forward  (2 K^2 + K Fx + 35 K + 16 Fx + 20) * 4 bytes,  backward (K^2 + 34 K + 20) * 4 bytes.
+ * Every check precedes the first launch.  A graph without nodes is outside the contract.
+ * ------------------------------------------------------------------------- */
+int hscn_dmon_sparse_fwd(const float* logits, const float* x /*or NULL*/,
+                         const int32_t* rowptr, const int32_t* col, const int32_t* node_ptr,
+                         float* S, float* stats, float* ss, float* vec, float* pooled_x, float* pooled_adj,
+                         float* losses, int64_t num_nodes, int64_t num_graphs, int K, int Fx, void* stream);
+
+/* dL/dlogits [N,K] (written once, plain stores) given g_losses = {dL/dspectral, dL/dortho, dL/dcluster} on the
+ * device.  rowptr/col keyed by ROW, rowptr_t/col_t keyed by COL: A need not be symmetric. */
+int hscn_dmon_sparse_bwd(const float* S, const float* stats, const float* ss, const float* vec,
+                         const int32_t* rowptr, const int32_t* col,
+                         const int32_t* rowptr_t, const int32_t* col_t, const int32_t* node_ptr,
+                         const float* g_losses /*[3] device*/, float* g_logits,
+                         int64_t num_nodes, int64_t num_graphs, int K, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * a6  dense_mincut_pool on the sparse (edge list) route
  * (reference model/hscn.py:61-63).  A = sum_e E[row_e, col_e]
  * is never densified: tr(S^T A S) = sum_e s_row . s_col,
