@@ -100,6 +100,29 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T* late_args(
 // global memory, so waiting for the LDS / scalar counter is enough.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Global -> LDS without a stop in a register (gfx950 global_load_lds_dword / _dwordx4).  Contract:
+//   * the destination is WAVE-LINEAR: lane i of the wave writes BYTES bytes at lds_wave_base + i * BYTES, whatever
+//     address the lane passes as `src` (every irregularity -- row pitch, transposition -- sits on the source side);
+//     lds_wave_base is the same for all lanes of the wave;
+//   * a lane that is masked off (a divergent `if` around the call) writes nothing: its LDS word keeps what it held;
+//   * the operation counts in vmcnt, in issue order with plain loads: loads issued BEFORE it can be consumed while it
+//     is still in flight;
+//   * nothing but the issuing wave's `s_waitcnt vmcnt(0)` followed by a barrier that the reader has passed orders the
+//     LDS write before a read: the issuing wave reaches lds_barrier_vm() in front of the first reader, and the words
+//     are read one phase after that barrier, never in the phase that waits for them.
+template <int BYTES>
+__device__ __forceinline__ void glds(const void* src, void* lds_wave_base) {
+  static_assert(BYTES == 4 || BYTES == 16, "global_load_lds_dword / global_load_lds_dwordx4");
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  if constexpr (BYTES == 4) __builtin_amdgcn_global_load_lds(src, (lds_ptr)lds_wave_base, 4, 0, 0);
+  else __builtin_amdgcn_global_load_lds(src, (lds_ptr)lds_wave_base, 16, 0, 0);
+}
+// lds_barrier() for the one barrier that closes a phase in which glds() operations were issued: the vector-memory
+// counter drains too (everything this wave has requested, plain loads included).
+__device__ __forceinline__ void lds_barrier_vm() {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // A wave group: a contiguous range of waves of the workgroup that works on its own arrays
 // between the workgroup-wide barriers (every group executes the same barrier sequence).
 struct Grp {

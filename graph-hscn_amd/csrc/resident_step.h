@@ -222,6 +222,15 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       }
     }
   }
+  // float storage: features, weights, head and target row go STRAIGHT to their LDS words (glds(): no register holds
+  // them over the structure build, no LDS store pass behind it); the padding words -- the words the lane masks skip --
+  // are zeroed here with plain LDS stores (other addresses than any glds() writes).  Issued behind the edge loads
+  // (the vector-memory counter retires in order) -- but the compiler books a glds() as a pending LDS write and puts
+  // vmcnt(0) in front of the first use of an edge word and of the first ds_read behind it: the edges are staged when
+  // the last prologue byte has arrived.  Measured, that costs less than the park did.  Half
+  // storage converts on the way in (ldf), which needs the register.
+  constexpr bool DIRECT = sizeof(TS) == 4;
+  float* const x0 = buf(0);
 #pragma unroll
   for (int i = 0; i < XPT; ++i) {
     const int idx = threadIdx.x + i * RT;
@@ -229,7 +238,12 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     const bool ok = idx < n * H && k < F;
     xr[i] = 0.f;
     if (wbase + i * RT < n * H) {
-      xr[i] = ldf(xl_g, ok ? (size_t)(n0 + r) * F + k : 0);   // (raw: the padding is applied where the word is parked)
+      if constexpr (DIRECT) {
+        if (ok) glds<4>(xl_g + ((size_t)(n0 + r) * F + k), x0 + (wbase + i * RT));
+        else if (idx < n * H) x0[idx] = 0.f;
+      } else {
+        xr[i] = ldf(xl_g, ok ? (size_t)(n0 + r) * F + k : 0);   // (raw: the padding is applied where the word is parked)
+      }
     }
   }
   // all layers' local->local weights, transposed on the way in: slot d = l*WL + k*H + o  <-  W_l[o][k]; bias behind
@@ -247,8 +261,20 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       const bool isb = q >= H * H;
       const int k = q / H, o = q - k * H;
       const bool ok = inb && (isb || k < fin);
-      const float* src = isb ? A.b_ll[ll] + (q - H * H) : A.W_ll[ll] + (ok ? o * fin + k : 0);
-      wr[i] = *(ok ? src : A.b_ll[0]);   // (raw, as the features)
+      // the layer's base pointers by a select chain over wave-uniform values: a per-lane index into the argument
+      // block's pointer tables is a VECTOR load, and the wait for it drained every request issued in front of it --
+      // edges and features -- plus a round trip of its own, before the edges could be staged
+      const float *Wp = A.W_ll[0], *bp = A.b_ll[0];
+#pragma unroll
+      for (int j = 1; j < MAXL; ++j)
+        if (j < L && ll == j) { Wp = A.W_ll[j]; bp = A.b_ll[j]; }
+      const float* src = isb ? bp + (q - H * H) : Wp + (ok ? o * fin + k : 0);
+      if constexpr (DIRECT) {
+        if (ok) glds<4>(src, wt + (wbase + i * RT));
+        else if (inb) wt[d] = 0.f;
+      } else {
+        wr[i] = *(ok ? src : A.b_ll[0]);   // (raw, as the features)
+      }
     }
   }
   // head weights W1 [H][H] | b1 [H] | W2 [C][H] | b2 [C] (natural layout), then this graph's target row
@@ -265,12 +291,21 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     return A.target + (size_t)g * C + (idx < C ? idx : 0);
   };
   const int HTT = HT + C;
-  float hw0 = *haddr((int)threadIdx.x < HTT ? (int)threadIdx.x : 0);
-  float hw1 = *haddr((int)threadIdx.x + RT < HTT ? (int)threadIdx.x + RT : 0);
-  // ---- consume: validate + stage the edges ONLY.  Features, weights and head stay in registers over the structure
-  // build -- nothing computes on them before (a select on a loaded word would put its wait here) -- and are parked
-  // behind it (park_inputs, as hscn_fwd_body does): the build starts when the edges have arrived, not when the
-  // last prologue byte has.  None of their LDS words is touched by a build. ----------------------------------
+  float hw0 = 0.f, hw1 = 0.f;
+  if constexpr (DIRECT) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (wbase + i * RT < HTT && (int)threadIdx.x + i * RT < HTT)
+        glds<4>(haddr((int)threadIdx.x + i * RT), headw + (wbase + i * RT));
+  } else {
+    hw0 = *haddr((int)threadIdx.x < HTT ? (int)threadIdx.x : 0);
+    hw1 = *haddr((int)threadIdx.x + RT < HTT ? (int)threadIdx.x + RT : 0);
+  }
+  // ---- consume: validate + stage the edges ONLY.  Nothing computes on features, weights or head before the
+  // structure is built.  Float storage: they are on their way into LDS (see above for what the compiler waits for) and
+  // the barrier that closes the build orders them in front of their first reader (lds_barrier_vm).  Half storage: they
+  // stay in registers over the build and are parked behind it (park_inputs; a select on a loaded word would put its
+  // wait here), so the build starts when the edges have arrived.  None of their LDS words is touched by a build. ----
   if (pre) {
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
@@ -309,22 +344,25 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   }
   for (int i = threadIdx.x; i <= n; i += RT) { (ib + Y.cntA)[i] = 0; (ib + Y.cntT)[i] = 0; }
   if (threadIdx.x == 0) { (ib + Y.wsum)[0] = 0; (ib + Y.wsum)[1] = 0; (ib + Y.ovf)[0] = 0; }   // fold sign-offs (H = 16 backward), export sign-offs
-  auto park_inputs = [&]() {
-    float* x0 = buf(0);
+  auto park_inputs = [&]() {   // (float storage: only what lies beyond the prologue's fixed share)
+    if constexpr (!DIRECT) {
 #pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const int idx = threadIdx.x + i * RT;
-      if (idx < n * H) x0[idx] = idx % H < F ? xr[i] : 0.f;
+      for (int i = 0; i < XPT; ++i) {
+        const int idx = threadIdx.x + i * RT;
+        if (idx < n * H) x0[idx] = idx % H < F ? xr[i] : 0.f;
+      }
     }
     for (int idx = threadIdx.x + XPT * RT; idx < n * H; idx += RT) {
       const int r = idx / H, k = idx - r * H;
       x0[idx] = k < F ? ldf(xl_g, (size_t)(n0 + r) * F + k) : 0.f;
     }
+    if constexpr (!DIRECT) {
 #pragma unroll
-    for (int i = 0; i < WPT; ++i) {
-      const int d = threadIdx.x + i * RT;
-      const int l = d / WL, q = d - l * WL;
-      if (d < WTOT) wt[d] = (q >= H * H || q / H < (l == 0 ? F : H)) ? wr[i] : 0.f;
+      for (int i = 0; i < WPT; ++i) {
+        const int d = threadIdx.x + i * RT;
+        const int l = d / WL, q = d - l * WL;
+        if (d < WTOT) wt[d] = (q >= H * H || q / H < (l == 0 ? F : H)) ? wr[i] : 0.f;
+      }
     }
     for (int d = threadIdx.x + WPT * RT; d < WTOT; d += RT) {
       const int l = d / WL, q = d - l * WL;
@@ -332,8 +370,10 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
       const int k = q / H, o = q - k * H;
       wt[d] = q >= H * H ? A.b_ll[l][q - H * H] : (k < fin ? A.W_ll[l][o * fin + k] : 0.f);
     }
-    if ((int)threadIdx.x < HTT) headw[threadIdx.x] = hw0;
-    if ((int)threadIdx.x + RT < HTT) headw[threadIdx.x + RT] = hw1;
+    if constexpr (!DIRECT) {
+      if ((int)threadIdx.x < HTT) headw[threadIdx.x] = hw0;
+      if ((int)threadIdx.x + RT < HTT) headw[threadIdx.x + RT] = hw1;
+    }
     for (int idx = threadIdx.x + 2 * RT; idx < HTT; idx += RT) headw[idx] = *haddr(idx);
   };
   lds_barrier();
@@ -373,7 +413,8 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
     }
   }
   park_inputs();
-  lds_barrier();
+  if constexpr (DIRECT) lds_barrier_vm();   // the prologue's glds() words have landed: first read in the next phase
+  else lds_barrier();
   STAMP(3);
   // ---- forward layers: A[l] -> A[l + 1], one barrier each ----------------------------------------------------
   // Hand-off of a_1 .. a_{L-1} to the virtual workgroup.  Write-through (sc1) stores need > 2 us to complete, and
