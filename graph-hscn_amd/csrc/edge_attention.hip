@@ -1,0 +1,450 @@
+// Multi-head scaled dot-product attention over the in-edges of every node: the message / aggregate of PyG's
+// TransformerConv (dropout = 0), Hd heads of width C, with optional edge features added to keys and values.
+//
+//   s_k   = scale * sum_c q[i,h,c] * (k[j,h,c] + e[k,h,c])        j = src_k, i = dst_k, scale = 1 / sqrt(C)
+//   a_k   = softmax of s over the in-edges of i, per head
+//   out_i = sum_k a_k * (v[j,h,:] + e[k,h,:])                      (0 for a node without in-edges)
+//
+// q is [Nd, Hd*C], k and v are [Ns, Hd*C] (the relation may be bipartite), e is [E, Hd*C] or absent.  Row k of e / de
+// belongs to edge k of the edge list, not to CSR slot k: every slot goes through eid[slot].  Every listed edge counts
+// (loops, repeats).
+//
+// Work unit: one (row, head), owned by G consecutive lanes (G a power of two, at most 64), VEC = 4 columns per lane
+// and pass (16-byte accesses) where C % 4 == 0 and every pointer is 16-byte aligned, VEC = 1 otherwise; a head wider
+// than G * VEC takes NP <= 8 / VEC passes, all of them held in registers (8 floats per lane and operand).  With the
+// in-degree 2..4 of a molecular graph and C = 16 a wave therefore carries 16 (row, head) units, none of them idle; the
+// heads of one row are neighbouring lane groups, so a row of k / v is read by consecutive lanes.  The dot products
+// are reduced over the lane group by xor shuffles (every lane of a group ends with the same bits).
+//
+// One kernel, three walks (k_edge_attn<VEC, MODE>):
+//   MODE 0, target-keyed CSR (forward):  online softmax in CSR slot order -- the running maximum is subtracted before
+//                                        every exp; stores out and ONE log-sum-exp per (node, head), kept as the pair
+//                                        (m_i, log sum_k exp(s_k - m_i)) with m_i the row's largest logit.  No [E, Hd]
+//                                        tensor of weights exists: the backward recomputes a_k = exp((s_k - m_i) - log sum)
+//                                        from the same logit bits, so a logit of magnitude 10^3 (integer atom features)
+//                                        costs the weights nothing -- a single rounded m + log sum would cost them
+//                                        2^-24 |lse| relative, 6e-5 there.
+//   MODE 1, target-keyed CSR (backward): delta_i = sum_c dout_i out_i per head (stored for MODE 2),
+//                                        ds_k = a_k (dout_i . (v_j + e_k) - delta_i),
+//                                        dq_i = sum_k scale ds_k (k_j + e_k),
+//                                        de_k = a_k dout_i + scale ds_k q_i   stored once at eid[slot] (one writer)
+//   MODE 2, source-keyed CSR (backward): dk_j = sum_{k: src_k = j} scale ds_k q_i,   dv_j = sum a_k dout_i
+// Owner-computes, sums in CSR slot order, no float atomics: the same input gives the same bits.
+//
+// Long rows: rows of more than EA_LONG_ROW slots are left out of the serial walk and taken by the WHOLE workgroup
+// afterwards in chunks of EA_CHUNK slots, one lane group per chunk.  The forward's chunk partials are (max, sum,
+// accumulator) triples merged in chunk order, the backward's are plain sums added in chunk order: the result depends
+// on the row alone, so it is bitwise reproducible and independent of the row's place in a batch.
+#include "hscn_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int EA_THREADS = 256;
+constexpr int EA_LONG_ROW = 256;   // rows with MORE slots than this are split (hscn_edge_attn_long_row)
+constexpr int EA_CHUNK = 64;       // slots per chunk of a split row (hscn_edge_attn_chunk)
+constexpr int EA_MAX_WIDTH = 512;  // heads * head_dim
+constexpr int EA_NC = 8;           // floats a lane holds of one operand row: (8 / VEC) passes of VEC columns
+
+template <int VEC>
+struct EV;
+template <>
+struct EV<4> {
+  using T = float4;
+  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
+  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
+  static __device__ __forceinline__ float get(const T& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+  static __device__ __forceinline__ T make(const float* a) { return make_float4(a[0], a[1], a[2], a[3]); }
+};
+template <>
+struct EV<1> {
+  using T = float;
+  static __device__ __forceinline__ T load(const float* p) { return *p; }
+  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
+  static __device__ __forceinline__ float get(const T& v, int) { return v; }
+  static __device__ __forceinline__ T make(const float* a) { return a[0]; }
+};
+
+struct EAArgs {
+  const int32_t* rowptr;   // the walked CSR: keyed by target (MODE 0, 1) or by source (MODE 2)
+  const int32_t* col;
+  const int32_t* eid;
+  const float* q;          // [Nd, HC]
+  const float* k;          // [Ns, HC]
+  const float* v;          // [Ns, HC]
+  const float* e;          // [E, HC] or NULL
+  const float* go;         // [Nd, HC]   MODE 1, 2: cotangent of out
+  float* out;              // [Nd, HC]   MODE 0 out, MODE 1 in
+  float* lse;              // [Nd, Hd, 2] (row maximum, log of the shifted sum)   MODE 0 out, MODE 1 / 2 in
+  float* delta;            // [Nd, Hd]   MODE 1 out, MODE 2 in
+  float* g0;               // MODE 1: dq [Nd, HC] or NULL;  MODE 2: dk [Ns, HC] or NULL
+  float* g1;               // MODE 1: de [E, HC] or NULL;   MODE 2: dv [Ns, HC] or NULL
+  int64_t rows, cols, E;   // rows of the walked CSR, range of its col, edges
+  int Hd, C, HC;
+  int G, UPB, NP;          // lanes per unit, units per workgroup, column passes
+  float scale;
+  int walk;                // MODE 1: 0 = delta alone, every row taken as empty (neither dq nor de is wanted)
+  int32_t* flag;
+};
+
+// pass p gives lane lg of a group the columns [c, c + VEC), c = (p * G + lg) * VEC; only p < NP is visited and a lane
+// with c >= C idles (C % VEC == 0, so a vector never straddles the end of a head)
+template <int VEC>
+__device__ __forceinline__ void load_cols(const EAArgs& A, const float* row, int lg, float (&x)[EA_NC]) {
+  using V = EV<VEC>;
+#pragma unroll
+  for (int i = 0; i < EA_NC; ++i) x[i] = 0.f;
+#pragma unroll
+  for (int p = 0; p < EA_NC / VEC; ++p) {
+    const int c = (p * A.G + lg) * VEC;
+    if (p < A.NP && c < A.C) {
+      const typename V::T t = V::load(row + c);
+#pragma unroll
+      for (int u = 0; u < VEC; ++u) x[p * VEC + u] = V::get(t, u);
+    }
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_cols(const EAArgs& A, float* row, int lg, const float (&x)[EA_NC]) {
+  using V = EV<VEC>;
+#pragma unroll
+  for (int p = 0; p < EA_NC / VEC; ++p) {
+    const int c = (p * A.G + lg) * VEC;
+    if (p < A.NP && c < A.C) V::store(row + c, V::make(&x[p * VEC]));
+  }
+}
+
+__device__ __forceinline__ float dot8(const float (&a)[EA_NC], const float (&b)[EA_NC]) {
+  float s = 0.f;                     // (columns a lane does not own hold zeros)
+#pragma unroll
+  for (int i = 0; i < EA_NC; ++i) s = fmaf(a[i], b[i], s);
+  return s;
+}
+
+// what a lane keeps of its (row, head) while it walks the slots
+struct UnitCtx {
+  float a[EA_NC];    // MODE 0, 1: q_i;  MODE 2: k_j
+  float b[EA_NC];    // MODE 1: dout_i;  MODE 2: v_j
+  float m, logl, delta;  // MODE 1
+};
+
+// the running state of a walk: MODE 0 (m, l, acc0) of the online softmax; MODE 1 acc0 = dq; MODE 2 acc0 = dk, acc1 = dv
+struct UnitAcc {
+  float m, l;
+  float acc0[EA_NC];
+  float acc1[EA_NC];
+};
+
+__device__ __forceinline__ void acc_clear(UnitAcc& S) {
+  S.m = -INFINITY;
+  S.l = 0.f;
+#pragma unroll
+  for (int i = 0; i < EA_NC; ++i) S.acc0[i] = S.acc1[i] = 0.f;
+}
+
+template <int VEC, int MODE>
+__device__ __forceinline__ void unit_begin(const EAArgs& A, int64_t r, int h, int lg, UnitCtx& U) {
+  const size_t at = (size_t)r * A.HC + (size_t)h * A.C;
+  if (MODE == 0) {
+    load_cols<VEC>(A, A.q + at, lg, U.a);
+  } else if (MODE == 1) {
+    float o[EA_NC];
+    load_cols<VEC>(A, A.q + at, lg, U.a);
+    load_cols<VEC>(A, A.go + at, lg, U.b);
+    load_cols<VEC>(A, A.out + at, lg, o);
+    U.delta = group_sum(dot8(U.b, o), A.G);
+    U.m = A.lse[2 * ((size_t)r * A.Hd + h)];
+    U.logl = A.lse[2 * ((size_t)r * A.Hd + h) + 1];
+  } else {
+    load_cols<VEC>(A, A.k + at, lg, U.a);
+    load_cols<VEC>(A, A.v + at, lg, U.b);
+  }
+}
+
+// slots [s, t) of one row for head h, the running state continued in S
+template <int VEC, int MODE>
+__device__ __forceinline__ void walk_slots(const EAArgs& A, const UnitCtx& U, int h, int lg, int s, int t, UnitAcc& S) {
+  const size_t hoff = (size_t)h * A.C;
+  for (int p = s; p < t; ++p) {
+    const int j = A.col[p];
+    const int kx = A.eid[p];
+    if (j < 0 || j >= A.cols || kx < 0 || kx >= A.E) {   // never produced by hscn_csr_build; a foreign CSR is flagged
+      atomicOr(A.flag, 2);
+      continue;
+    }
+    float ee[EA_NC];
+    if (A.e) {
+      load_cols<VEC>(A, A.e + (size_t)kx * A.HC + hoff, lg, ee);
+    } else {
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) ee[i] = 0.f;
+    }
+    const size_t nj = (size_t)j * A.HC + hoff;
+    if (MODE == 0) {
+      float kk[EA_NC], vv[EA_NC];
+      load_cols<VEC>(A, A.k + nj, lg, kk);
+      load_cols<VEC>(A, A.v + nj, lg, vv);
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) kk[i] += ee[i], vv[i] += ee[i];
+      const float sc = group_sum(dot8(U.a, kk), A.G) * A.scale;
+      if (sc > S.m) {                                    // a new running maximum: rescale what was summed under the old
+        const float corr = expf(S.m - sc);
+        S.l *= corr;
+#pragma unroll
+        for (int i = 0; i < EA_NC; ++i) S.acc0[i] *= corr;
+        S.m = sc;
+      }
+      const float w = expf(sc - S.m);
+      S.l += w;
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) S.acc0[i] = fmaf(w, vv[i], S.acc0[i]);
+    } else if (MODE == 1) {
+      float kk[EA_NC], vv[EA_NC];
+      load_cols<VEC>(A, A.k + nj, lg, kk);
+      load_cols<VEC>(A, A.v + nj, lg, vv);
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) kk[i] += ee[i], vv[i] += ee[i];
+      const float sc = group_sum(dot8(U.a, kk), A.G) * A.scale;
+      const float dp = group_sum(dot8(U.b, vv), A.G);
+      const float a = expf((sc - U.m) - U.logl);
+      const float ds = a * (dp - U.delta) * A.scale;
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) S.acc0[i] = fmaf(ds, kk[i], S.acc0[i]);
+      if (A.g1) {
+        float de[EA_NC];
+#pragma unroll
+        for (int i = 0; i < EA_NC; ++i) de[i] = fmaf(ds, U.a[i], a * U.b[i]);
+        store_cols<VEC>(A, A.g1 + (size_t)kx * A.HC + hoff, lg, de);
+      }
+    } else {
+      float qq[EA_NC], gg[EA_NC], kk[EA_NC], vv[EA_NC];   // (j is the target here, the row is the source)
+      load_cols<VEC>(A, A.q + nj, lg, qq);
+      load_cols<VEC>(A, A.go + nj, lg, gg);
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) kk[i] = U.a[i] + ee[i], vv[i] = U.b[i] + ee[i];
+      const float sc = group_sum(dot8(qq, kk), A.G) * A.scale;
+      const float dp = group_sum(dot8(gg, vv), A.G);
+      const size_t ih = (size_t)j * A.Hd + h;
+      const float a = expf((sc - A.lse[2 * ih]) - A.lse[2 * ih + 1]);
+      const float ds = a * (dp - A.delta[ih]) * A.scale;
+#pragma unroll
+      for (int i = 0; i < EA_NC; ++i) {
+        S.acc0[i] = fmaf(ds, qq[i], S.acc0[i]);
+        S.acc1[i] = fmaf(a, gg[i], S.acc1[i]);
+      }
+    }
+  }
+}
+
+template <int VEC, int MODE>
+__device__ __forceinline__ void unit_finish(const EAArgs& A, const UnitCtx& U, int64_t r, int h, int lg, const UnitAcc& S) {
+  const size_t at = (size_t)r * A.HC + (size_t)h * A.C;
+  if (MODE == 0) {
+    float o[EA_NC];
+    const bool any = S.l > 0.f || S.l != S.l;            // (a NaN sum is shown, not hidden)
+#pragma unroll
+    for (int i = 0; i < EA_NC; ++i) o[i] = any ? S.acc0[i] / S.l : 0.f;
+    store_cols<VEC>(A, A.out + at, lg, o);
+    if (lg == 0) {
+      A.lse[2 * ((size_t)r * A.Hd + h)] = any ? S.m : 0.f;
+      A.lse[2 * ((size_t)r * A.Hd + h) + 1] = any ? logf(S.l) : 0.f;
+    }
+  } else if (MODE == 1) {
+    if (lg == 0) A.delta[(size_t)r * A.Hd + h] = U.delta;
+    if (A.g0) store_cols<VEC>(A, A.g0 + at, lg, S.acc0);
+  } else {
+    if (A.g0) store_cols<VEC>(A, A.g0 + at, lg, S.acc0);
+    if (A.g1) store_cols<VEC>(A, A.g1 + at, lg, S.acc1);
+  }
+}
+
+template <int VEC, int MODE>
+__global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
+  constexpr int NACC = MODE == 2 ? 2 : 1;
+  __shared__ float part[NACC * EA_THREADS * EA_NC];      // chunk partials of a long row, [accumulator][thread][EA_NC]
+  __shared__ float part_m[EA_THREADS], part_l[EA_THREADS];
+  const bool walk = MODE != 1 || A.walk != 0;
+  const int ul = threadIdx.x / A.G;                      // unit of this lane group within the workgroup's tile
+  const int lg = threadIdx.x - ul * A.G;
+  const int64_t units = A.rows * A.Hd;
+  const int64_t tiles = (units + A.UPB - 1) / A.UPB;
+  int any_long = 0;
+  // ---- rows of at most EA_LONG_ROW slots: one lane group per (row, head), serially ------------------------------
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t u = tile * A.UPB + ul;
+    if (u >= units) continue;
+    const int64_t r = u / A.Hd;
+    const int h = (int)(u - r * A.Hd);
+    const int s = A.rowptr[r], t = walk ? A.rowptr[r + 1] : s;
+    if (t - s > EA_LONG_ROW) { any_long = 1; continue; }
+    UnitCtx U;
+    UnitAcc S;
+    unit_begin<VEC, MODE>(A, r, h, lg, U);
+    acc_clear(S);
+    walk_slots<VEC, MODE>(A, U, h, lg, s, t, S);
+    unit_finish<VEC, MODE>(A, U, r, h, lg, S);
+  }
+  if (!__syncthreads_or(any_long)) return;
+  // ---- the long rows among this workgroup's tiles: a lane group per chunk, partials merged in chunk order --------
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    for (int i = 0; i < A.UPB; ++i) {
+      const int64_t u = tile * A.UPB + i;
+      if (u >= units) break;
+      const int64_t r = u / A.Hd;
+      const int h = (int)(u - r * A.Hd);
+      const int s = A.rowptr[r], t = A.rowptr[r + 1];    // workgroup-uniform
+      if (t - s <= EA_LONG_ROW) continue;
+      const int chunks = (t - s + EA_CHUNK - 1) / EA_CHUNK;
+      UnitCtx U;
+      UnitAcc T;                                         // the merged state (used by lane group 0)
+      unit_begin<VEC, MODE>(A, r, h, lg, U);
+      acc_clear(T);
+      for (int c0 = 0; c0 < chunks; c0 += A.UPB) {
+        const int c = c0 + ul;
+        if (c < chunks) {
+          const int cs = s + c * EA_CHUNK;
+          const int ct = cs + EA_CHUNK < t ? cs + EA_CHUNK : t;
+          UnitAcc S;
+          acc_clear(S);
+          walk_slots<VEC, MODE>(A, U, h, lg, cs, ct, S);
+#pragma unroll
+          for (int x = 0; x < EA_NC; ++x) {
+            part[threadIdx.x * EA_NC + x] = S.acc0[x];
+            if (MODE == 2) part[(EA_THREADS + threadIdx.x) * EA_NC + x] = S.acc1[x];
+          }
+          if (MODE == 0) part_m[threadIdx.x] = S.m, part_l[threadIdx.x] = S.l;
+        }
+        __syncthreads();
+        if (ul == 0) {
+          const int n = chunks - c0 < A.UPB ? chunks - c0 : A.UPB;
+          for (int g = 0; g < n; ++g) {
+            const int src = g * A.G + lg;
+            float f = 1.f;
+            if (MODE == 0) {
+              const float pm = part_m[src], pl = part_l[src];
+              if (pm > T.m) {
+                const float corr = expf(T.m - pm);
+                T.l *= corr;
+#pragma unroll
+                for (int x = 0; x < EA_NC; ++x) T.acc0[x] *= corr;
+                T.m = pm;
+              }
+              f = expf(pm - T.m);
+              T.l = fmaf(pl, f, T.l);
+            }
+#pragma unroll
+            for (int x = 0; x < EA_NC; ++x) {
+              if (MODE == 0) T.acc0[x] = fmaf(part[src * EA_NC + x], f, T.acc0[x]);
+              else T.acc0[x] += part[src * EA_NC + x];
+              if (MODE == 2) T.acc1[x] += part[(EA_THREADS + src) * EA_NC + x];
+            }
+          }
+        }
+        __syncthreads();
+      }
+      if (ul == 0) unit_finish<VEC, MODE>(A, U, r, h, lg, T);
+    }
+  }
+}
+
+bool ea_supported(int heads, int head_dim) {
+  return heads >= 1 && head_dim >= 1 && (int64_t)heads * head_dim <= EA_MAX_WIDTH;
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+template <int MODE>
+int launch_walk(EAArgs A, hipStream_t st) {
+  const void* ptrs[] = {A.q, A.k, A.v, A.e, A.go, A.out, A.g0, A.g1};
+  bool vec = A.C % 4 == 0;
+  for (const void* p : ptrs) vec = vec && aligned16(p);  // (NULL counts as aligned)
+  const int VEC = vec ? 4 : 1;
+  const int need = (A.C + VEC - 1) / VEC;                // lanes a head asks for
+  int G = 1;
+  while (G < need && G < HSCN_WAVE) G <<= 1;
+  A.G = G;
+  A.UPB = EA_THREADS / G;
+  A.NP = (need + G - 1) / G;                             // <= 2 (VEC = 4), <= 8 (VEC = 1) for C <= 512
+  const int64_t units = A.rows * A.Hd;
+  int64_t nb = (units + A.UPB - 1) / A.UPB;
+  if (nb > 16384) nb = 16384;
+  if (VEC == 4) k_edge_attn<4, MODE><<<(unsigned)nb, EA_THREADS, 0, st>>>(A);
+  else k_edge_attn<1, MODE><<<(unsigned)nb, EA_THREADS, 0, st>>>(A);
+  HSCN_RETURN_IF_LAUNCH_FAILED();
+  return 0;
+}
+
+int check_common(int64_t Nd, int64_t Ns, int64_t E, int heads, int head_dim) {
+  if (Nd < 0 || Ns < 0 || E < 0 || heads < 1 || head_dim < 1) return HSCN_E_BADARG;
+  if (Nd > INT32_MAX || Ns > INT32_MAX || E > INT32_MAX) return HSCN_E_BADARG;   // CSR indices are int32
+  if (!ea_supported(heads, head_dim)) return HSCN_E_UNSUPPORTED;
+  return 0;
+}
+
+void set_shape(EAArgs& A, int64_t rows, int64_t cols, int64_t E, int heads, int head_dim) {
+  A.rows = rows, A.cols = cols, A.E = E;
+  A.Hd = heads, A.C = head_dim, A.HC = heads * head_dim;
+  A.scale = 1.0f / sqrtf((float)head_dim);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hscn_edge_attn_supported(int heads, int head_dim) { return ea_supported(heads, head_dim) ? 1 : 0; }
+int hscn_edge_attn_long_row(void) { return EA_LONG_ROW; }
+int hscn_edge_attn_chunk(void) { return EA_CHUNK; }
+
+int hscn_edge_attn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* q, const float* k,
+                       const float* v, const float* e, float* out, float* lse, int64_t Nd, int64_t Ns, int64_t E,
+                       int heads, int head_dim, int32_t* flag, void* stream_) {
+  if (int rc = check_common(Nd, Ns, E, heads, head_dim)) return rc;
+  if (!rowptr || !flag || (Nd > 0 && (!q || !out || !lse))) return HSCN_E_BADARG;
+  if (E > 0 && (!col || !eid || !k || !v)) return HSCN_E_BADARG;
+  if (Nd == 0) return 0;
+  EAArgs A{};
+  A.rowptr = rowptr, A.col = col, A.eid = eid;
+  A.q = q, A.k = k, A.v = v, A.e = E > 0 ? e : nullptr;
+  A.out = out, A.lse = lse, A.flag = flag;
+  set_shape(A, Nd, Ns, E, heads, head_dim);
+  return launch_walk<0>(A, hscn_stream(stream_));
+}
+
+int hscn_edge_attn_bwd_dst(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* q, const float* k,
+                           const float* v, const float* e, const float* out, const float* lse, const float* g_out,
+                           float* delta, float* dq, float* de, int64_t Nd, int64_t Ns, int64_t E, int heads,
+                           int head_dim, int32_t* flag, void* stream_) {
+  if (int rc = check_common(Nd, Ns, E, heads, head_dim)) return rc;
+  if (!rowptr || !flag || (Nd > 0 && (!q || !out || !lse || !g_out || !delta))) return HSCN_E_BADARG;
+  if (E > 0 && (!col || !eid || !k || !v)) return HSCN_E_BADARG;
+  if (de && E > 0 && !e) return HSCN_E_BADARG;           // a gradient for edge features that were not given
+  if (Nd == 0) return 0;
+  EAArgs A{};
+  A.rowptr = rowptr, A.col = col, A.eid = eid;
+  A.q = q, A.k = k, A.v = v, A.e = E > 0 ? e : nullptr, A.go = g_out;
+  A.out = const_cast<float*>(out), A.lse = const_cast<float*>(lse), A.delta = delta;
+  A.g0 = dq, A.g1 = E > 0 ? de : nullptr, A.walk = (dq || de) ? 1 : 0;
+  A.flag = flag;
+  set_shape(A, Nd, Ns, E, heads, head_dim);
+  return launch_walk<1>(A, hscn_stream(stream_));
+}
+
+int hscn_edge_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const float* q,
+                           const float* k, const float* v, const float* e, const float* lse, const float* delta,
+                           const float* g_out, float* dk, float* dv, int64_t Nd, int64_t Ns, int64_t E, int heads,
+                           int head_dim, int32_t* flag, void* stream_) {
+  if (int rc = check_common(Nd, Ns, E, heads, head_dim)) return rc;
+  if (!rowptr_t || !flag || (Ns > 0 && (!k || !v))) return HSCN_E_BADARG;
+  if (E > 0 && (!col_t || !eid_t || !q || !lse || !delta || !g_out)) return HSCN_E_BADARG;
+  if (Ns == 0 || (!dk && !dv)) return 0;
+  EAArgs A{};
+  A.rowptr = rowptr_t, A.col = col_t, A.eid = eid_t;
+  A.q = q, A.k = k, A.v = v, A.e = E > 0 ? e : nullptr, A.go = g_out;
+  A.lse = const_cast<float*>(lse), A.delta = const_cast<float*>(delta);
+  A.g0 = dk, A.g1 = dv, A.flag = flag;
+  set_shape(A, Ns, Nd, E, heads, head_dim);
+  return launch_walk<2>(A, hscn_stream(stream_));
+}
+
+}  // extern "C"

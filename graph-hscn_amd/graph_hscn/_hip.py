@@ -226,6 +226,15 @@ _SIGNATURES = {
     "hscn_catenc_index_build": (c_int, [P, P, c_int64, c_int, P, P, P, P, c_size_t, P]),
     "hscn_catenc_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "hscn_catenc_bwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, P, P, c_size_t, P]),
+    # edge attention: TransformerConv's multi-head softmax over in-edges (csrc/edge_attention.hip; additive to ABI 24)
+    "hscn_edge_attn_supported": (c_int, [c_int, c_int]),
+    "hscn_edge_attn_long_row": (c_int, []),
+    "hscn_edge_attn_chunk": (c_int, []),
+    "hscn_edge_attn_fwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P, P]),
+    "hscn_edge_attn_bwd_dst": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int,
+                                       P, P]),
+    "hscn_edge_attn_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int,
+                                       P, P]),
 }
 
 

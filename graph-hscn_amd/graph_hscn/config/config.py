@@ -12,7 +12,7 @@ from typing import Callable, Optional
 
 from torch.optim import Adagrad, Adam, AdamW
 
-from ..nn.conv import GINE, GATConv, GatedGCNConv, GCNConv
+from ..nn.conv import GINE, EdgeTransformerConv, GATConv, GatedGCNConv, GCNConv, TransformerConv
 from ..nn.functional import Activation
 
 # defaults.py:1-39
@@ -49,7 +49,15 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 # "gatedgcn" (extension): nn/conv.py GatedGCNConv (csrc/gatedgcn.hip), the edge-gated convolution whose edge features
 # are a state: it reads ``batch.edge_attr``, returns ``(x, e)`` and hands ``e`` to the next layer.  Like "gine" it
 # builds the MPNN baseline and the GPS local branch only, and runs layered.
-CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE, "gatedgcn": GatedGCNConv}
+# "transformerconv" / "transformerconv_edge" (extension): nn/conv.py TransformerConv / EdgeTransformerConv
+# (csrc/edge_attention.hip), multi-head dot-product attention over the in-edges; the second adds ``batch.edge_attr`` to
+# keys and values.  They take ``heads`` (MPNNConfig.heads, GPSConfig.num_heads, HSCNConfig.heads), run layered, and the
+# first also builds HSCN's relations (build_conv_relation "TransformerConv").  The key is not "transformer": that name
+# stays refused (GPS's plain Transformer layer is local_conv_type=None).
+CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE, "gatedgcn": GatedGCNConv,
+                              "transformerconv": TransformerConv, "transformerconv_edge": EdgeTransformerConv}
+# conv_type whose layers are built with ``heads``
+MULTI_HEAD_CONVS = ("transformerconv", "transformerconv_edge")
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
 SCHEDULERS = ("cosine_with_warmup", "linear_with_warmup", "step")  # extension: optim.SCHEDULE_KINDS
 TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "graph" only
@@ -57,7 +65,7 @@ TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "grap
 NODE_ENCODERS = ("atom",)
 EDGE_ENCODERS = ("bond",)
 # conv_type / local_conv_type whose layers read ``edge_attr`` (nn/conv.py ``uses_edge_attr``): what an edge encoder feeds
-EDGE_AWARE_CONVS = ("gine", "gatedgcn")
+EDGE_AWARE_CONVS = ("gine", "gatedgcn", "transformerconv_edge")
 
 
 def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
@@ -68,6 +76,17 @@ def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
     if edge_encoder is not None and (conv_type is None or conv_type.lower() not in EDGE_AWARE_CONVS):
         raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution {EDGE_AWARE_CONVS}, "
                          f"got {conv_type!r}")
+
+
+def check_heads(heads, hidden_channels, conv_type) -> None:
+    if not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"heads must be a positive int, got {heads!r}")
+    if heads != 1 and (conv_type is None or conv_type.lower() not in MULTI_HEAD_CONVS):
+        raise ValueError(f"heads={heads} needs a multi-head convolution {MULTI_HEAD_CONVS}, got {conv_type!r}")
+    if hidden_channels % heads:
+        raise ValueError(f"hidden_channels {hidden_channels} must be divisible by heads {heads}.")
+
+
 DATASETS_NUM_FEATURES: dict[str, int] = {"peptides_func": 9, "peptides_struct": 9}
 
 
@@ -104,11 +123,15 @@ class MPNNConfig:  # config.py:49-73
     # "bond" = a BondEncoder(hidden_channels) whose output the edge-aware convolutions read as edge_attr
     node_encoder: Optional[str] = None
     edge_encoder: Optional[str] = None
+    # extension: attention heads of conv_type "transformerconv" / "transformerconv_edge": the hidden layers are
+    # conv(in, hidden_channels // heads, heads=heads), the last one has one head of width num_classes
+    heads: int = 1
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         _check_encoders(self.node_encoder, self.edge_encoder, self.conv_type)
+        check_heads(self.heads, self.hidden_channels, self.conv_type)
         if self.dropout and not (0.0 <= self.dropout <= 1.0):
             raise ValueError(f"{self.dropout} must be between 0.0 and 1.0.")
         for v in (self.num_layers, self.hidden_channels):
@@ -122,8 +145,9 @@ GPS_NORMS = ("layer", "batch", None)
 @dataclass
 class GPSConfig:
     """The GPS model (extension; model/gps.py): ``num_layers`` GPS layers of width ``hidden_channels`` -- a local
-    convolution ``local_conv_type`` ("gcn", "gat", "gine", "gatedgcn" of CONV_DICT, or None: the plain Transformer layer;
-    "gatedgcn" is GraphGPS's published pairing: a ``GatedGCNLayer`` that also updates the edge features) beside
+    convolution ``local_conv_type`` ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge" of
+    CONV_DICT, or None: the plain Transformer layer; "gatedgcn" is GraphGPS's published pairing: a ``GatedGCNLayer``
+    that also updates the edge features; the two TransformerConv keys take ``num_heads`` heads as well) beside
     per-graph self-attention of ``num_heads`` heads, then a feed-forward block -- behind a Linear node encoder.  The
     head width ``hidden_channels / num_heads`` must be a multiple of 4 in [4, 64] and ``hidden_channels`` at most 512
     (the attention kernel's envelope, csrc/attention.hip)."""
@@ -175,6 +199,8 @@ class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent
     # local node (model/hscn.py HSCN(task_level="node")); "link" = one score per candidate pair of local nodes,
     # num_classes being the embedding width; "graph": the reference
     task_level: str = field(default="graph", kw_only=True)
+    # extension: attention heads of the relations built as "TransformerConv" (model/hscn.py build_conv_relation)
+    heads: int = field(default=1, kw_only=True)
     # extension: the ("virtual", "to", "local") relation the reference never wired up (None: the reference's model,
     # whose virtual branch does not reach the prediction; "GAT": model/hscn.py HSCN(vl_conv="GAT"))
     vl_conv_type: Optional[str] = None
@@ -182,6 +208,13 @@ class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        if not isinstance(self.heads, int) or self.heads < 1:
+            raise ValueError(f"heads must be a positive int, got {self.heads!r}")
+        convs = (self.lv_conv_type, self.ll_conv_type, self.vv_conv_type)
+        if self.heads != 1 and not any(str(c).lower() == "transformerconv" for c in convs):
+            raise ValueError(f"heads={self.heads} needs a relation built as 'TransformerConv', got {convs}")
+        if self.hidden_channels % self.heads:
+            raise ValueError(f"hidden_channels {self.hidden_channels} must be divisible by heads {self.heads}.")
         for v in (self.num_layers, self.hidden_channels):
             if v < 0:
                 raise ValueError(f"{v} must be non-negative.")

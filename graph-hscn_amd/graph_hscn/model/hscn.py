@@ -24,7 +24,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from ..config.config import ACT_DICT, CONV_DICT, HSCNConfig
-from ..nn import GATConv, GCNConv, GraphConv, HeteroConv, Linear
+from ..nn import GATConv, GCNConv, GraphConv, HeteroConv, Linear, TransformerConv
 from ..nn import functional as Fh
 from ..nn.pool import (dmon_pool_sparse, global_mean_pool, mincut_pool_sparse, to_dense_adj, to_dense_adj_batched,
                        to_dense_adj_ragged)
@@ -269,8 +269,20 @@ class SCN(nn.Module):
         return S, mc_loss, o_loss, adj
 
 
-def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None) -> nn.Module:
-    """hscn.py:117-125.  ``in_channels`` (extension) materialises the lazy ``-1``."""
+def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None, heads: int = 1) -> nn.Module:
+    """hscn.py:117-125.  ``in_channels`` (extension) materialises the lazy ``-1``.  ``heads`` (extension): the attention
+    heads of "TransformerConv", ``heads`` heads of width ``hidden_channels // heads``."""
+    if conv_type.lower() == "transformerconv_edge":
+        raise ValueError("conv_type 'TransformerConv_edge' needs edge features, and the hetero graph carries no edge "
+                         "features yet (HeteroData has no edge_attr; the MPNN baseline and GPS take "
+                         "'transformerconv_edge', the relations take 'TransformerConv')")
+    if heads != 1 and conv_type.lower() != "transformerconv":
+        raise ValueError(f"heads={heads} needs conv_type 'TransformerConv', not {conv_type!r}")
+    if conv_type.lower() == "transformerconv":
+        if heads < 1 or hidden_channels % heads:
+            raise ValueError(f"hidden_channels {hidden_channels} must be divisible by heads {heads}")
+        dim = -1 if in_channels is None else (in_channels, in_channels)
+        return TransformerConv(dim, hidden_channels // heads, heads=heads)     # (no add_self_loops / cached: not its)
     if conv_type.lower() == "gatedgcn":
         raise ValueError("conv_type 'GatedGCN' needs edge features, and the hetero graph carries no edge features yet "
                          "(HeteroData has no edge_attr; the MPNN baseline and GPS take 'gatedgcn')")
@@ -287,8 +299,11 @@ def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None) 
 class HSCN(nn.Module):
     def __init__(self, lv_conv: str, ll_conv: str, vv_conv: str, activation: Callable, num_features: int,
                  hidden_channels: int, num_classes: int, num_layers: int, vl_conv: Optional[str] = None,
-                 task_level: str = "graph") -> None:
-        """``task_level`` (extension; the default "graph" is the reference's model): "node" skips the mean pool and
+                 task_level: str = "graph", heads: int = 1) -> None:
+        """``heads`` (extension): the attention heads of the relations built as "TransformerConv" (lv, ll, vv; ``heads``
+        heads of width ``hidden_channels // heads``); such a model runs on the layered operators.
+
+        ``task_level`` (extension; the default "graph" is the reference's model): "node" skips the mean pool and
         applies the head ``lin_2(act(lin_1(.)))`` to every local node, returning ``[N, C]`` (``nn.head.NodeHead``: the
         one-launch head where ``hscn_node_head_supported`` says so, else the two ``Linear`` modules).  The convolution
         stack runs on the layered operators; the graph-resident launches, which end in the pooled head, refuse such a
@@ -309,16 +324,22 @@ class HSCN(nn.Module):
             raise ValueError(f"vl_conv must be None or 'GAT', not {vl_conv!r} (a bipartite GCNConv does not exist)")
         if task_level not in ("graph", "node", "link"):
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
+        if heads != 1 and not any(c.lower() == "transformerconv" for c in (lv_conv, ll_conv, vv_conv)):
+            raise ValueError(f"heads={heads} needs a relation built as 'TransformerConv'")
         self.vl_conv = vl_conv
         self.task_level = task_level
+        self.heads = int(heads)
+
+        def rel_heads(conv_type):
+            return self.heads if conv_type.lower() == "transformerconv" else 1
         self.activation = activation
         self.convs = nn.ModuleList()
         for layer in range(num_layers):
             fin = num_features if layer == 0 else hidden_channels
             rels = {
-                LV: build_conv_relation(lv_conv, hidden_channels, fin),
-                LL: build_conv_relation(ll_conv, hidden_channels, fin),
-                VV: build_conv_relation(vv_conv, hidden_channels, fin),
+                LV: build_conv_relation(lv_conv, hidden_channels, fin, heads=rel_heads(lv_conv)),
+                LL: build_conv_relation(ll_conv, hidden_channels, fin, heads=rel_heads(ll_conv)),
+                VV: build_conv_relation(vv_conv, hidden_channels, fin, heads=rel_heads(vv_conv)),
             }
             if vl_conv is not None:
                 rels[VL] = build_conv_relation(vl_conv, hidden_channels, fin)
@@ -624,4 +645,5 @@ def build_hscn(model_cfg: HSCNConfig, num_features: int, num_classes: int) -> HS
         model_cfg.num_layers,
         getattr(model_cfg, "vl_conv_type", None),
         getattr(model_cfg, "task_level", "graph"),
+        getattr(model_cfg, "heads", 1),
     )

@@ -21,7 +21,7 @@ from torch import Tensor
 from .. import _hip
 from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig
 from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
-from ..nn.conv import GCNConv
+from ..nn.conv import GCNConv, TransformerConv
 from ..nn import functional as Fh
 from ..nn.norm import BatchNorm1d, LayerNorm
 from ..nn.pool import global_mean_pool
@@ -31,8 +31,12 @@ class MPNN(nn.Module):
     def __init__(self, conv: type, activation: Callable, num_features: int, hidden_channels: int,
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
                  use_layer_norm: bool = False, task_level: str = "graph", node_encoder: Optional[str] = None,
-                 edge_encoder: Optional[str] = None) -> None:
-        """``task_level`` (extension; the default "graph" is the reference's model): "node" returns the last
+                 edge_encoder: Optional[str] = None, heads: int = 1) -> None:
+        """``heads`` (extension): with a multi-head ``conv`` (``TransformerConv`` / ``EdgeTransformerConv``) the hidden
+        layers are ``conv(in, hidden_channels // heads, heads=heads)`` and the last one ``conv(hidden, num_classes,
+        heads=1)``; such a model is layered-only.
+
+        ``task_level`` (extension; the default "graph" is the reference's model): "node" returns the last
         convolution's ``[N, C]`` without the per-graph mean.  "link": ``num_classes`` is the embedding width D,
         ``embed`` is that node-level output and ``forward`` scores the batch's candidate pairs
         ``batch.edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P].
@@ -48,12 +52,21 @@ class MPNN(nn.Module):
         if edge_encoder not in (None,) + tuple(EDGE_ENCODERS):
             raise ValueError(f"edge_encoder must be one of {sorted(EDGE_ENCODERS)} or None, not {edge_encoder!r}")
         if edge_encoder is not None and not getattr(conv, "uses_edge_attr", False):
-            raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution (conv_type 'gine' or "
-                             f"'gatedgcn'), not {getattr(conv, '__name__', conv)}")
+            raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution (conv_type 'gine', "
+                             f"'gatedgcn' or 'transformerconv_edge'), not {getattr(conv, '__name__', conv)}")
+        multi_head = isinstance(conv, type) and issubclass(conv, TransformerConv)
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, not {heads!r}")
+        if heads != 1 and not multi_head:
+            raise ValueError(f"heads={heads} needs a multi-head convolution (conv_type 'transformerconv' or "
+                             f"'transformerconv_edge'), not {getattr(conv, '__name__', conv)}")
+        if hidden_channels % heads:
+            raise ValueError(f"hidden_channels {hidden_channels} must be divisible by heads {heads}")
+        self.heads = heads
         self.task_level = task_level
         self.num_layers = num_layers
         self.encoder_kinds = (node_encoder, edge_encoder)
-        if node_encoder is not None or edge_encoder is not None:
+        if node_encoder is not None or edge_encoder is not None or multi_head:
             # train.batching.refuse_layered_only: the resident and device-dataset entry points refuse this model by name
             self.layered_only = True
         if node_encoder is not None:
@@ -62,10 +75,16 @@ class MPNN(nn.Module):
         if edge_encoder is not None:
             self.edge_encoder = EDGE_ENCODERS[edge_encoder](hidden_channels)
         self.conv_layers = nn.ModuleList()                                  # mpnn.py:27-32
-        self.conv_layers.append(conv(num_features, hidden_channels))
-        for _ in range(num_layers - 2):
-            self.conv_layers.append(conv(hidden_channels, hidden_channels))
-        self.conv_layers.append(conv(hidden_channels, num_classes))
+        if multi_head:
+            self.conv_layers.append(conv(num_features, hidden_channels // heads, heads=heads))
+            for _ in range(num_layers - 2):
+                self.conv_layers.append(conv(hidden_channels, hidden_channels // heads, heads=heads))
+            self.conv_layers.append(conv(hidden_channels, num_classes, heads=1))
+        else:
+            self.conv_layers.append(conv(num_features, hidden_channels))
+            for _ in range(num_layers - 2):
+                self.conv_layers.append(conv(hidden_channels, hidden_channels))
+            self.conv_layers.append(conv(hidden_channels, num_classes))
         self.use_batch_norm = use_batch_norm
         if use_layer_norm:                                                  # mpnn.py:35-38 (sic: not use_batch_norm)
             self.bns = nn.ModuleList(BatchNorm1d(hidden_channels) for _ in range(num_layers - 1))
@@ -84,6 +103,10 @@ class MPNN(nn.Module):
 
     def resident_reason(self, batch=None, need_grad: bool = False) -> Optional[str]:
         """Why this model (and ``batch``, if given) cannot take the one-launch MPNN kernels, or None when it can."""
+        for c in self.conv_layers:
+            if isinstance(c, TransformerConv):
+                return (f"convolution {type(c).__name__} (multi-head attention over the in-edges has no one-launch, "
+                        "resident or captured form; the model runs on the layered operators)")
         if any(self.encoder_kinds):
             return encoder_reason(*self.encoder_kinds)
         if self.task_level == "node":
@@ -183,7 +206,8 @@ class MPNN(nn.Module):
         edge encoder: the int64 categories, embedded)."""
         ea = getattr(batch, "edge_attr", None)
         if ea is None:
-            kind = "gatedgcn" if any(getattr(c, "updates_edge_attr", False) for c in self.conv_layers) else "gine"
+            kind = "gatedgcn" if any(getattr(c, "updates_edge_attr", False) for c in self.conv_layers) else \
+                ("transformerconv_edge" if isinstance(self.conv_layers[0], TransformerConv) else "gine")
             raise ValueError(f"the model has edge-aware convolutions (conv_type {kind!r}) and the batch carries no "
                              "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
         dev = next(self.parameters()).device
@@ -197,7 +221,7 @@ class MPNN(nn.Module):
     def _forward(self, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
-        if self.engine == "resident" and (self.task_level != "graph" or any(self.encoder_kinds)):
+        if self.engine == "resident" and (self.task_level != "graph" or getattr(self, "layered_only", False)):
             raise RuntimeError(f"engine='resident' does not take this model: {self.resident_reason()}")
         if self.engine != "layered" and not torch.is_grad_enabled():
             reason = self.resident_reason(batch)
@@ -244,4 +268,5 @@ def build_mpnn(model_cfg: MPNNConfig, num_features: int, num_classes: int) -> MP
     return MPNN(CONV_DICT[model_cfg.conv_type.lower()], ACT_DICT[model_cfg.activation.lower()], num_features,
                 model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.dropout,
                 model_cfg.use_batch_norm, model_cfg.use_layer_norm, getattr(model_cfg, "task_level", "graph"),
-                getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None))
+                getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None),
+                getattr(model_cfg, "heads", 1))

@@ -364,6 +364,87 @@ class GatedGCNLayer(GatedGCNConv):
         return h, e
 
 
+class TransformerConv(nn.Module):
+    """PyG TransformerConv with ``concat=True``, ``beta=False``, ``dropout=0``: multi-head scaled dot-product attention
+    over the in-edges of every node, every edge as given (loops and repeated edges count),
+
+        a_k   = softmax_k( lin_query(x_i) . (lin_key(x_j) + lin_edge(e_k)) / sqrt(C) )     per head, over dst_k = i
+        out_i = sum_k a_k (lin_value(x_j) + lin_edge(e_k))  +  lin_skip(x_i)
+
+    with ``heads`` heads of width ``C = out_channels`` (the output is ``[N, heads * out_channels]``).  Parameters and
+    ``state_dict`` keys are PyG's: ``lin_key``, ``lin_query``, ``lin_value`` (bias), ``lin_edge`` (no bias, only with
+    ``edge_dim``; ``-1`` is materialised on first use), ``lin_skip`` (only with ``root_weight``; ``bias`` is its
+    bias).  Called with one Tensor or a pair ``(x_src, x_dst)``; ``in_channels`` may be an int, a pair, and ``-1`` is
+    lazy.  The transforms run through ``Linear``, the softmax and both sums are one HIP launch
+    (csrc/edge_attention.hip).  ``edge_attr`` may carry a gradient.
+
+    Not provided, refused by name: ``concat=False``, ``beta=True`` and ``dropout > 0``."""
+
+    def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, heads: int = 1,
+                 concat: bool = True, beta: bool = False, dropout: float = 0.0, edge_dim: Optional[int] = None,
+                 bias: bool = True, root_weight: bool = True):
+        super().__init__()
+        if not concat:
+            raise NotImplementedError("TransformerConv(concat=False): the mean over heads is not provided")
+        if beta:
+            raise NotImplementedError("TransformerConv(beta=True): the gated skip connection is not provided")
+        if dropout:
+            raise NotImplementedError("TransformerConv(dropout > 0): dropout on the attention weights is not provided")
+        heads, out_channels = int(heads), int(out_channels)
+        if heads < 1 or out_channels < 1:
+            raise ValueError(f"TransformerConv: heads = {heads} and out_channels = {out_channels} must be positive")
+        if heads * out_channels > Fh.EDGE_ATTN_MAX_WIDTH:       # (the library's answer is asked at the first launch)
+            raise ValueError(f"TransformerConv: heads * out_channels = {heads * out_channels} outside the kernel's "
+                             f"envelope ({Fh.EDGE_ATTN_ENVELOPE})")
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        self.in_channels, self.out_channels, self.heads = tuple(in_channels), out_channels, heads
+        self.concat, self.beta, self.dropout = True, False, 0.0
+        self.edge_dim, self.root_weight = edge_dim, bool(root_weight)
+        width = heads * out_channels
+        self.lin_key = Linear(in_channels[0], width)
+        self.lin_query = Linear(in_channels[1], width)
+        self.lin_value = Linear(in_channels[0], width)
+        self.lin_edge = Linear(edge_dim, width, bias=False) if edge_dim is not None else None
+        self.lin_skip = Linear(in_channels[1], width, bias=bias) if root_weight else None
+
+    def forward(self, x: Union[Tensor, Tuple[Tensor, Tensor]], edge_index: Union[Tensor, Relation],
+                edge_attr: Optional[Tensor] = None, act: str = "identity") -> Tensor:
+        x_src, x_dst = (x, x) if isinstance(x, Tensor) else x
+        if self.lin_edge is not None:
+            if edge_attr is None:
+                raise ValueError("TransformerConv(edge_dim=...) needs edge_attr [E, edge_dim]")
+            if edge_attr.dim() != 2:
+                raise ValueError(f"edge_attr must be [E, edge_dim], got {tuple(edge_attr.shape)}")
+            if not edge_attr.is_floating_point():
+                raise TypeError(f"TransformerConv: edge_attr must be float32, got {edge_attr.dtype}")
+        elif edge_attr is not None:
+            raise ValueError("TransformerConv was built without edge_dim and cannot take edge_attr")
+        # a gradient w.r.t. k or v (their weights are parameters) walks the source-keyed CSR
+        rel = _relation(edge_index, x_src.size(0), x_dst.size(0), both=torch.is_grad_enabled())
+        if edge_attr is not None and edge_attr.size(0) != rel.num_edges:
+            raise ValueError(f"edge_attr is {tuple(edge_attr.shape)}; the relation has {rel.num_edges} edges")
+        q, k, v = self.lin_query(x_dst), self.lin_key(x_src), self.lin_value(x_src)
+        e = self.lin_edge(edge_attr) if self.lin_edge is not None else None
+        out = Fh.EdgeAttentionFn.apply(q, k, v, e, rel, self.heads)
+        if self.lin_skip is not None:
+            out = out + self.lin_skip(x_dst)
+        if act != "identity":
+            out = Fh.ActFn.apply(out, ACT[act])
+        return out
+
+
+class EdgeTransformerConv(TransformerConv):
+    """The edge-aware ``TransformerConv``, constructible from ``(in, out)`` like the other registry entries (as ``GINE``
+    is for ``GINEConv``): ``edge_dim=-1``, so ``lin_edge`` takes its input width from the first ``edge_attr``."""
+
+    uses_edge_attr = True
+
+    def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, heads: int = 1, **kwargs):
+        kwargs.setdefault("edge_dim", -1)
+        super().__init__(in_channels, out_channels, heads=heads, **kwargs)
+
+
 class HeteroConv(nn.Module):
     """PyG HeteroConv(aggr='sum'): run each relation's conv in
     ``edge_index_dict`` order, sum the outputs that share a target type."""

@@ -547,6 +547,105 @@ class GatedGCNAggregateFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# Edge attention (TransformerConv's message + aggregate): multi-head softmax(q_i . (k_j + e_k) / sqrt(C)) over in-edges
+# --------------------------------------------------------------------------- #
+# csrc/edge_attention.hip: a row of more than EDGE_ATTN_LONG_ROW slots (in-degree in the forward and the backward's
+# target walk, out-degree in the source walk) is taken by a whole workgroup in chunks of EDGE_ATTN_CHUNK slots; both
+# are the library's constants (hscn_edge_attn_long_row / hscn_edge_attn_chunk, pinned equal in
+# tests/test_transformerconv_host.py).
+EDGE_ATTN_LONG_ROW = 256
+EDGE_ATTN_CHUNK = 64
+EDGE_ATTN_MAX_WIDTH = 512
+EDGE_ATTN_ENVELOPE = f"heads >= 1, head width >= 1 and heads * head width <= {EDGE_ATTN_MAX_WIDTH}"
+
+
+def edge_attn_supported(heads: int, head_dim: int) -> bool:
+    """hscn_edge_attn_supported: the one statement of the kernel's envelope."""
+    return bool(_hip.lib().hscn_edge_attn_supported(int(heads), int(head_dim)))
+
+
+class EdgeAttentionFn(Function):
+    """(q [Nd, Hd*C], k, v [Ns, Hd*C], e [E, Hd*C] or None) -> out [Nd, Hd*C] over ``rel`` (j = src_k, i = dst_k; row k
+    of ``e`` belongs to edge k of ``rel.edge_index``): per head, ``out_i = sum_k softmax_k(q_i . (k_j + e_k) / sqrt(C))
+    (v_j + e_k)`` over the in-edges of i, zeros for a node without any.  Forward: one launch; kept for backward are
+    the inputs, the output and ONE log-sum-exp per (node, head), as its two summands (row maximum, log of the shifted
+    sum) -- the attention weights are recomputed, never stored.
+    Backward: the target-keyed pass gives dq, de and the per-(node, head) ``sum(dout * out)``; the source-keyed pass
+    (``rel.csr_t``, built only then) gives dk and dv.  Only what ``needs_input_grad`` asks for is computed."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, e: Optional[Tensor], rel: Relation, heads: int):
+        heads = int(heads)
+        for name, t in (("q", q), ("k", k), ("v", v), ("e", e)):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError(f"edge attention: {name} must be float32, got {t.dtype}")
+            if t is not None and t.dim() != 2:
+                raise ValueError(f"edge attention: {name} must be 2-D [rows, heads * C], got {tuple(t.shape)}")
+        Nd, HC = q.shape
+        if heads < 1 or HC % heads:
+            raise ValueError(f"edge attention: width {HC} is not a multiple of heads = {heads}")
+        C = HC // heads
+        if k.shape != v.shape or k.size(1) != HC:
+            raise ValueError(f"edge attention: k is {tuple(k.shape)}, v is {tuple(v.shape)}, q is {tuple(q.shape)}")
+        Ns = k.size(0)
+        if rel.num_src != Ns or rel.num_dst != Nd:
+            raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, k has {Ns} rows and q has {Nd}")
+        E = rel.num_edges
+        if e is not None and (e.size(0) != E or e.size(1) != HC):
+            raise ValueError(f"e is {tuple(e.shape)}; the relation has {E} edges and the layer is {HC} wide")
+        if not edge_attn_supported(heads, C):
+            raise ValueError(f"edge attention: heads = {heads}, head width = {C} outside the kernel's envelope "
+                             f"({EDGE_ATTN_ENVELOPE})")
+        for t in (q, k, v, e):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("edge attention takes HIP device tensors only (got a CPU tensor): the hot path has "
+                                   "no CPU fallback")
+        q, k, v, e = _c(q), _c(k), _c(v), _c(e)
+        csr = rel.csr
+        dev = q.device
+        out = torch.empty(Nd, HC, dtype=torch.float32, device=dev)
+        lse = torch.empty(Nd, heads, 2, dtype=torch.float32, device=dev)   # (row maximum, log of the shifted sum)
+        call("hscn_edge_attn_fwd", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(q), ptr(k), ptr(v),
+             ptr(e) if E else None, ptr(out), ptr(lse), Nd, Ns, E, heads, C, ptr(csr.flag), stream())
+        ctx.rel, ctx.heads = rel, heads
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, k, v, e, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, go: Optional[Tensor]):
+        q, k, v, e, out, lse = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        heads = ctx.heads
+        need_q, need_k, need_v, need_e = ctx.needs_input_grad[:4]
+        need_e = need_e and e is not None
+        if go is None or not (need_q or need_k or need_v or need_e):
+            return None, None, None, None, None, None
+        go = _c(go)
+        Nd, HC = q.shape
+        Ns, E, C = k.size(0), rel.num_edges, HC // heads
+        csr = rel.csr
+        delta = torch.empty(Nd, heads, dtype=torch.float32, device=q.device)
+        dq = torch.empty_like(q) if need_q else None
+        de = torch.empty_like(e) if need_e else None
+        dk = dv = None
+        call("hscn_edge_attn_bwd_dst", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(q), ptr(k), ptr(v),
+             ptr(e) if E else None, ptr(out), ptr(lse), ptr(go), ptr(delta), ptr(dq), ptr(de) if E else None,
+             Nd, Ns, E, heads, C, ptr(csr.flag), stream())
+        if need_k or need_v:
+            if E:
+                t = rel.csr_t
+                dk = torch.empty_like(k) if need_k else None
+                dv = torch.empty_like(v) if need_v else None
+                call("hscn_edge_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(q), ptr(k), ptr(v), ptr(e),
+                     ptr(lse), ptr(delta), ptr(go), ptr(dk), ptr(dv), Nd, Ns, E, heads, C, ptr(csr.flag), stream())
+            else:                                   # no edge reaches k or v: exact zeros, not None
+                dk = torch.zeros_like(k) if need_k else None
+                dv = torch.zeros_like(v) if need_v else None
+        return dq, dk, dv, de, None, None
+
+
+# --------------------------------------------------------------------------- #
 # Global attention: block-diagonal multi-head self-attention over a batch (csrc/attention.hip)
 # --------------------------------------------------------------------------- #
 ATTN_MIN_HEAD_DIM = 4

@@ -28,7 +28,7 @@ from .attention import MultiheadSelfAttention
 from .conv import GatedGCNLayer, Linear
 from .norm import BatchNorm1d, LayerNorm
 
-LOCAL_CONVS = ("gcn", "gat", "gine", "gatedgcn")
+LOCAL_CONVS = ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge")
 NORMS = ("layer", "batch", None)
 
 
@@ -59,6 +59,10 @@ class GPSLayer(nn.Module):
         self.dropout_seed: Optional[int] = None     # tests pin the masks; None = nn.functional.dropout's default
         if local_conv == "gatedgcn":        # GraphGPS's layer: batch norm, activation, dropout and residual inside
             self.conv = GatedGCNLayer(channels, dropout, residual=True, act=act)
+        elif local_conv in ("transformerconv", "transformerconv_edge"):     # num_heads heads of width channels / num_heads
+            if channels % num_heads:
+                raise ValueError(f"channels {channels} must be divisible by num_heads {num_heads}")
+            self.conv = CONV_DICT[local_conv](channels, channels // num_heads, heads=num_heads)
         else:
             self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
         self.attn = MultiheadSelfAttention(channels, num_heads)
@@ -83,7 +87,7 @@ class GPSLayer(nn.Module):
     def forward(self, x: Tensor, edge_index, batch=None, edge_attr: Optional[Tensor] = None, *,
                 ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None):
         """``batch``: the ``Batch`` (graph boundaries of the attention), or ``ptr32`` and ``max_nodes``.  ``edge_attr``
-        is read by an edge-aware ``local_conv`` ("gine", "gatedgcn") only.  Returns the node features; with a
+        is read by an edge-aware ``local_conv`` ("gine", "gatedgcn", "transformerconv_edge") only.  Returns the node features; with a
         ``local_conv`` that updates the edge features ("gatedgcn") the pair ``(h, edge_attr_out)``."""
         edge_out = None
         h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes)

@@ -1573,6 +1573,54 @@ int hscn_catenc_bwd(const int32_t* rowptr /*[R + 1]*/, const int32_t* item /*[n 
                     float* dW /*[R, D]*/, int64_t n, int F, int R, int D, int32_t* flag /*[1]*/, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Edge attention: the message / aggregate of PyG's TransformerConv with dropout = 0 (csrc/edge_attention.hip).  Purely
+ * additive to ABI 24.  `heads` heads of width `head_dim` (HC = heads * head_dim), q [Nd, HC], k and v [Ns, HC], e
+ * [E, HC] or NULL; with j = src_k, i = dst_k and scale = 1 / sqrt(head_dim), per head h:
+ *
+ *   s_k   = scale * sum_c q[i,h,c] * (k[j,h,c] + e[k,h,c])
+ *   a_k   = exp(s_k - lse_i),   lse_i = log sum_{k: dst_k = i} exp(s_k) = m_i + log sum_k exp(s_k - m_i),  m_i = max_k s_k
+ *   out_i = sum_{k: dst_k = i} a_k * (v[j,h,:] + e[k,h,:])                  (exact zeros for a node without in-edges)
+ *
+ * Every listed edge counts (loops, repeats); row k of e and de belongs to edge k of the edge list, not to a CSR slot
+ * (every slot goes through eid).  The relation may be bipartite.  Sums run in CSR slot order; a row of more than
+ * hscn_edge_attn_long_row() slots is taken by a whole workgroup in chunks of hscn_edge_attn_chunk() slots whose
+ * partials -- (max, sum, accumulator) triples in the forward, plain sums in the backward -- are merged in chunk
+ * order: a row depends on the row alone, the same input gives the same bits.  No float atomics, no [E, heads] tensor.
+ *
+ * hscn_edge_attn_supported: 1 for heads >= 1, head_dim >= 1, heads * head_dim <= 512.  16-byte accesses are used where
+ *   head_dim % 4 == 0 and every tensor is 16-byte aligned, 4-byte accesses otherwise.
+ * hscn_edge_attn_fwd: ONE launch over the target-keyed stable CSR; writes out [Nd, HC] and lse [Nd, heads, 2]: the one
+ *   log-sum-exp per (node, head) as its two summands (m_i, log sum_k exp(s_k - m_i)), so that the backward's
+ *   exp((s_k - m_i) - log sum) loses nothing to the magnitude of the logits; (0, 0) for a node without in-edges.
+ * hscn_edge_attn_bwd_dst: ONE launch over the same CSR.  delta_i = sum_c g_out_i out_i per head is stored
+ *   ([Nd, heads]).  With ds_k = a_k (g_out_i . (v_j + e_k) - delta_i):  dq_i = sum_k scale ds_k (k_j + e_k) and
+ *   de_k = a_k g_out_i + scale ds_k q_i, the latter stored once at row eid[slot].  dq, de may each be NULL and are
+ *   then not computed (both NULL: delta alone).  de needs e.
+ * hscn_edge_attn_bwd_src: ONE launch over the source-keyed CSR: dk_j = sum_{k: src_k = j} scale ds_k q_i and
+ *   dv_j = sum a_k g_out_i; either may be NULL and is then not computed (both NULL: nothing is launched).
+ * flag [1] i32: the CSR's flag word; bit 1 is OR-ed in for a slot with a column outside its range or an eid outside
+ *   [0, E) (the slot adds nothing; hscn_csr_build never produces one).
+ *   HSCN_E_BADARG for null pointers (col / eid / k / v may be NULL when E == 0, e always) and negative sizes;
+ *   HSCN_E_UNSUPPORTED where hscn_edge_attn_supported is 0; both before any launch.  No workspace, no host
+ *   synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_edge_attn_supported(int heads, int head_dim);
+int hscn_edge_attn_long_row(void);
+int hscn_edge_attn_chunk(void);
+int hscn_edge_attn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* q, const float* k,
+                       const float* v, const float* e, float* out /*[Nd, HC]*/, float* lse /*[Nd, heads, 2]*/, int64_t Nd,
+                       int64_t Ns, int64_t E, int heads, int head_dim, int32_t* flag /*[1]*/, void* stream);
+int hscn_edge_attn_bwd_dst(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* q,
+                           const float* k, const float* v, const float* e, const float* out, const float* lse,
+                           const float* g_out, float* delta /*[Nd, heads]*/, float* dq /*[Nd, HC]*/,
+                           float* de /*[E, HC]*/, int64_t Nd, int64_t Ns, int64_t E, int heads, int head_dim,
+                           int32_t* flag /*[1]*/, void* stream);
+int hscn_edge_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const float* q,
+                           const float* k, const float* v, const float* e, const float* lse, const float* delta,
+                           const float* g_out, float* dk /*[Ns, HC]*/, float* dv /*[Ns, HC]*/, int64_t Nd, int64_t Ns,
+                           int64_t E, int heads, int head_dim, int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
