@@ -235,6 +235,16 @@ _SIGNATURES = {
                                        P, P]),
     "hscn_edge_attn_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int,
                                        P, P]),
+    # shortest-path buckets and the attention they bias (csrc/spd.hip, csrc/attention_bias.hip; additive to ABI 24)
+    "hscn_spd_supported": (c_int, [c_int, c_int]),
+    "hscn_spd_buckets": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, P, P, P]),
+    "hscn_attention_bias_supported": (c_int, [c_int, c_int, c_int]),
+    "hscn_attention_bias_fwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, P, P, P,
+                                        P]),
+    "hscn_attention_bias_bwd_q": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int,
+                                          P, P, P, P, c_int64, P, P]),
+    "hscn_attention_bias_bwd_kv": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+                                           c_int, P, P, P]),
 }
 
 

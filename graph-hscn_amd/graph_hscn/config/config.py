@@ -162,11 +162,20 @@ class GPSConfig:
     # "atom" / "bond": an AtomEncoder / BondEncoder of width hidden_channels in place of the Linear node / edge encoder
     node_encoder: Optional[str] = None
     edge_encoder: Optional[str] = None
+    # "spd": Graphormer's spatial encoding -- a learned bias per (shortest-path bucket, head) in every layer's attention,
+    # distances of spd_max_dist hops and beyond (and unreachable pairs) sharing the last bucket
+    attn_bias: Optional[str] = None
+    spd_max_dist: int = 20
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         _check_encoders(self.node_encoder, self.edge_encoder, self.local_conv_type)
+        if self.attn_bias not in (None, "spd"):
+            raise ValueError(f"attn_bias must be 'spd' or None, got {self.attn_bias!r}")
+        if isinstance(self.spd_max_dist, bool) or not isinstance(self.spd_max_dist, int) or \
+                not 1 <= self.spd_max_dist <= 63:
+            raise ValueError(f"spd_max_dist must be an integer in [1, 63], got {self.spd_max_dist!r}")
         if self.dropout and not (0.0 <= self.dropout < 1.0):
             raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
         for v in (self.num_layers, self.hidden_channels, self.num_heads):

@@ -38,8 +38,13 @@ class GPS(nn.Module):
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
                  local_conv: Optional[str] = "gine", activation: Optional[Callable] = None, dropout: float = 0.0,
                  norm: Optional[str] = "layer", task_level: str = "graph", node_encoder: Optional[str] = None,
-                 edge_encoder: Optional[str] = None) -> None:
-        """``node_encoder="atom"`` / ``edge_encoder="bond"``: an ``AtomEncoder(D)`` / ``BondEncoder(D)`` over int64
+                 edge_encoder: Optional[str] = None, attn_bias: Optional[str] = None, spd_max_dist: int = 20) -> None:
+        """``attn_bias="spd"``: Graphormer's spatial encoding -- every layer's attention owns a table
+        ``layers.i.attn.spd_bias.weight`` [spd_max_dist + 1, num_heads] added to its logits by shortest-path bucket; the
+        model builds the batch's buckets once per forward (``nn.functional.shortest_path_buckets``, cached on the
+        batch per ``spd_max_dist``) and hands them to all layers.
+
+        ``node_encoder="atom"`` / ``edge_encoder="bond"``: an ``AtomEncoder(D)`` / ``BondEncoder(D)`` over int64
         categories in place of the Linear node / edge encoder (for "gine" the bond encoder supplies the ``edge_attr``
         the layer's own edge Linear reads).  The defaults build the model as it always was."""
         super().__init__()
@@ -51,6 +56,12 @@ class GPS(nn.Module):
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
         if num_layers < 1:
             raise ValueError("GPS needs at least one layer")
+        if attn_bias not in (None, "spd"):
+            raise ValueError(f"attn_bias must be 'spd' or None, not {attn_bias!r}")
+        if attn_bias is not None and not Fh.SPD_MIN_DIST <= int(spd_max_dist) <= Fh.SPD_MAX_DIST:
+            raise ValueError(f"spd_max_dist must be in [{Fh.SPD_MIN_DIST}, {Fh.SPD_MAX_DIST}], got {spd_max_dist}")
+        self.attn_bias = attn_bias
+        self.spd_max_dist = int(spd_max_dist)
         activation = ACT_DICT["relu"] if activation is None else activation
         act = getattr(activation, "hscn_name", None)
         if act is None:
@@ -63,7 +74,9 @@ class GPS(nn.Module):
         D = int(hidden_channels)
         self.encoder_kinds = (node_encoder, edge_encoder)
         self.node_encoder = Linear(num_features, D) if node_encoder is None else NODE_ENCODERS[node_encoder](D)
-        self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act) for _ in range(num_layers))
+        spd_buckets = self.spd_max_dist + 1 if attn_bias == "spd" else None
+        self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, spd_buckets=spd_buckets)
+                                    for _ in range(num_layers))
         if edge_encoder is not None:
             if not self.layers[0].uses_edge_attr:
                 raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware local_conv ('gine' or 'gatedgcn'), "
@@ -96,6 +109,8 @@ class GPS(nn.Module):
         ``max_nodes`` (``nn.functional.check_attention``).  ``train.train_epoch`` / ``eval_epoch`` call it once per
         epoch, beside the read of the epoch's loss."""
         Fh.check_attention(next(self.parameters()).device)
+        if self.attn_bias == "spd":                 # and the bucket launches' (an edge outside its graph, max_nodes)
+            Fh.check_spd(next(self.parameters()).device)
         if any(self.encoder_kinds):                # and the categorical encoders' (an index outside its column)
             Fh.check_categorical(next(self.parameters()).device)
 
@@ -115,6 +130,18 @@ class GPS(nn.Module):
                             f"{ea.device} (train.batching.to_device casts integer bond features)")
         return ea
 
+    def _spd(self, batch):
+        """The batch's ``SPDBuckets`` at ``spd_max_dist``, built once: kept on the batch object, in a dict that
+        ``train.batching.to_device`` hands on by reference, keyed by ``(max_dist, device)`` -- a batch reused across
+        epochs (resident on the device, or moved there every step from the same host batch) is not computed again."""
+        if self.attn_bias != "spd":
+            return None
+        cache = getattr(batch, "__dict__", {}).setdefault("_spd_cache", {})
+        key = (self.spd_max_dist, str(batch.ptr32.device))
+        if key not in cache:
+            cache[key] = Fh.shortest_path_buckets(batch, self.spd_max_dist)
+        return cache[key]
+
     def _nodes(self, batch) -> Tensor:
         """[N, D] after the last GPS layer."""
         if self.engine not in ("layered", "auto", "resident"):
@@ -122,6 +149,7 @@ class GPS(nn.Module):
         if self.engine == "resident":
             raise RuntimeError(f"engine='resident' does not take this model: {RESIDENT_REASON}")
         self.last_engine = "layered"
+        spd = self._spd(batch)                      # once per forward, for all layers (None without attn_bias)
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
         x = self.node_encoder(batch.x)
         if self.layers[0].updates_edge_attr or self.encoder_kinds[1] is not None:
@@ -129,9 +157,9 @@ class GPS(nn.Module):
         for i, layer in enumerate(self.layers):
             layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
             if layer.updates_edge_attr:             # the layer's new edge features feed the next layer
-                x, edge_attr = layer(x, batch.edge_index, batch, edge_attr)
+                x, edge_attr = layer(x, batch.edge_index, batch, edge_attr, spd=spd)
             else:
-                x = layer(x, batch.edge_index, batch, edge_attr)
+                x = layer(x, batch.edge_index, batch, edge_attr, spd=spd)
         return x
 
     def _head(self, x: Tensor) -> Tensor:
@@ -162,4 +190,5 @@ class GPS(nn.Module):
 def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:
     return GPS(num_features, model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.num_heads,
                model_cfg.local_conv_type, ACT_DICT[model_cfg.activation.lower()], model_cfg.dropout, model_cfg.norm,
-               model_cfg.task_level, getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None))
+               model_cfg.task_level, getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None),
+               getattr(model_cfg, "attn_bias", None), getattr(model_cfg, "spd_max_dist", 20))

@@ -34,17 +34,35 @@ class _OutProj(nn.Module):
         return Fh.linear_wide(x, self.weight, self.bias)
 
 
+class _SPDBias(nn.Module):
+    """Graphormer's spatial encoding: ``weight`` [num_buckets, num_heads], one learned scalar per (shortest-path bucket,
+    head), added to the attention logit (an ``nn.Embedding``'s key, ``spd_bias.weight``)."""
+
+    def __init__(self, num_buckets: int, num_heads: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(num_buckets, num_heads))
+
+
 class MultiheadSelfAttention(nn.Module):
     """``forward(x, batch)``: x [N, D] float32 on the device, ``batch`` a ``graph_hscn.data.Batch`` (its ``ptr32`` and
     ``max_nodes`` say which rows form a graph) -> [N, D].  ``forward(x, ptr32=..., max_nodes=...)`` takes the two
     directly.
 
-    Not provided, refused by name: dropout on the attention weights, ``need_weights``, an attention bias or any mask
-    other than the graph boundary, an ``embed_dim`` that ``num_heads`` does not divide, a head width outside the
-    kernel's envelope, CPU tensors."""
+    ``spd_buckets=K`` adds Graphormer's spatial encoding: the module owns ``spd_bias.weight`` [K, num_heads] (drawn
+    normal(0, 0.02) after every other parameter) and ``forward(x, batch, spd=...)`` takes the batch's ``SPDBuckets``
+    (``nn.functional.shortest_path_buckets``) with ``max_dist + 1 == K``; logit (i, j) of head h gains
+    ``spd_bias.weight[bucket_ij, h]`` (csrc/attention_bias.hip).  Without it the module is what it always was.
 
-    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, dropout: float = 0.0):
+    Not provided, refused by name: dropout on the attention weights, ``need_weights``, a dense attention bias tensor or
+    any mask other than the graph boundary, ``spd=`` on a module without ``spd_buckets``, an ``embed_dim`` that
+    ``num_heads`` does not divide, a head width outside the kernel's envelope, CPU tensors."""
+
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, dropout: float = 0.0,
+                 spd_buckets: Optional[int] = None):
         super().__init__()
+        if spd_buckets is not None and not 2 <= int(spd_buckets) <= Fh.ATTN_MAX_BUCKETS:
+            raise ValueError(f"MultiheadSelfAttention: spd_buckets must be max_dist + 1 with max_dist in "
+                             f"[{Fh.SPD_MIN_DIST}, {Fh.SPD_MAX_DIST}], got {spd_buckets}")
         if embed_dim <= 0 or num_heads <= 0:
             raise ValueError(f"embed_dim and num_heads must be greater than 0, got embed_dim={embed_dim} and "
                              f"num_heads={num_heads} instead")
@@ -67,6 +85,9 @@ class MultiheadSelfAttention(nn.Module):
         else:
             self.register_parameter("in_proj_bias", None)
         self.out_proj = _OutProj(embed_dim, bias)
+        self.spd_buckets = None if spd_buckets is None else int(spd_buckets)
+        if self.spd_buckets is not None:        # after every parameter of before: today's state_dict order first
+            self.spd_bias = _SPDBias(self.spd_buckets, self.num_heads)
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -80,9 +101,11 @@ class MultiheadSelfAttention(nn.Module):
         if self.in_proj_bias is not None:
             nn.init.constant_(self.in_proj_bias, 0.0)
             nn.init.constant_(self.out_proj.bias, 0.0)
+        if self.spd_buckets is not None:        # drawn last: the draws above are those of a module without the table
+            nn.init.normal_(self.spd_bias.weight, mean=0.0, std=0.02)
 
     def forward(self, x: Tensor, batch=None, *, ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None,
-                need_weights: bool = False, attn_mask=None, key_padding_mask=None, attn_bias=None) -> Tensor:
+                need_weights: bool = False, attn_mask=None, key_padding_mask=None, attn_bias=None, spd=None) -> Tensor:
         if need_weights:
             raise NotImplementedError("MultiheadSelfAttention(need_weights=True): the attention weights are streamed "
                                       "through LDS and never exist in memory")
@@ -101,6 +124,20 @@ class MultiheadSelfAttention(nn.Module):
             raise ValueError("MultiheadSelfAttention needs the graph boundaries: a Batch, or ptr32 and max_nodes")
         if x.dim() != 2 or x.size(1) != self.embed_dim:
             raise ValueError(f"x must be [N, {self.embed_dim}], got {tuple(x.shape)}")
+        if self.spd_buckets is None:
+            if spd is not None:
+                raise ValueError("MultiheadSelfAttention(spd=...): this module has no shortest-path bias table; build "
+                                 "it with spd_buckets=max_dist + 1")
+        else:
+            if not isinstance(spd, Fh.SPDBuckets):
+                raise ValueError(f"MultiheadSelfAttention(spd_buckets={self.spd_buckets}) needs spd=: the SPDBuckets "
+                                 "of this batch (nn.functional.shortest_path_buckets)")
+            if spd.num_buckets != self.spd_buckets:
+                raise ValueError(f"MultiheadSelfAttention: spd has max_dist + 1 = {spd.num_buckets} buckets, the "
+                                 f"module's table has spd_buckets = {self.spd_buckets}")
         qkv = Fh.linear_wide(x, self.in_proj_weight, self.in_proj_bias)
-        out = Fh.SelfAttentionFn.apply(qkv, ptr32, int(max_nodes), self.num_heads)
+        if self.spd_buckets is None:
+            out = Fh.SelfAttentionFn.apply(qkv, ptr32, int(max_nodes), self.num_heads)
+        else:
+            out = Fh.BiasedSelfAttentionFn.apply(qkv, self.spd_bias.weight, spd, ptr32, int(max_nodes), self.num_heads)
         return self.out_proj(out)

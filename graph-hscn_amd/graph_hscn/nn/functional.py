@@ -682,6 +682,9 @@ def check_attention(device) -> None:
         word.zero_()
     if f & ATTN_GRAPH_TOO_LARGE:
         raise ValueError("self-attention: a graph has more nodes than the batch's max_nodes says; its rows are NaN")
+    if f & 8:           # ATTN_BUCKETS_OUT_OF_RANGE (the biased operator below)
+        raise ValueError("biased self-attention: a graph's bucket range lies outside the bucket tensor (the SPDBuckets "
+                         "belong to another batch); its rows are NaN")
 
 
 class SelfAttentionFn(Function):
@@ -729,6 +732,196 @@ class SelfAttentionFn(Function):
         call("hscn_attention_bwd_kv", ptr(qkv), ptr(lse), ptr(delta), ptr(g_out), ptr(ptr32), N, B, max_nodes, heads,
              dh, ptr(g_qkv), ptr(flag), stream())
         return g_qkv, None, None, None
+
+
+# --------------------------------------------------------------------------- #
+# Shortest-path buckets (csrc/spd.hip) and the self-attention they bias (csrc/attention_bias.hip): Graphormer's
+# spatial encoding inside the global attention
+# --------------------------------------------------------------------------- #
+SPD_MIN_DIST = 1
+SPD_MAX_DIST = 63
+SPD_EDGE_OUT_OF_RANGE = 1         # flag bit 0: an edge with an end outside its graph (skipped)
+SPD_GRAPH_TOO_LARGE = 2           # flag bit 1: a graph with more than max_nodes nodes (its buckets are all max_dist)
+ATTN_MAX_BUCKETS = 64
+ATTN_BUCKETS_OUT_OF_RANGE = 8     # attention flag bit 3: a graph's bucket range leaves the bucket tensor (rows NaN)
+
+_SPD_FLAGS = {}
+
+
+def spd_supported(max_nodes: int, max_dist: int) -> bool:
+    """hscn_spd_supported: the one statement of the bucket kernel's envelope (a host function: no device needed)."""
+    return bool(_hip.lib().hscn_spd_supported(int(max_nodes), int(max_dist)))
+
+
+def spd_flags(device) -> Tensor:
+    """The device's flag word [1] int32 that every bucket launch ORs into; ``check_spd`` reads and clears it."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    t = _SPD_FLAGS.get(device)
+    if t is None:
+        t = _SPD_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def check_spd(device) -> None:
+    """Synchronising: ``ValueError`` if a bucket launch since the last check met an edge with an end outside its graph
+    (skipped) or a graph larger than the ``max_nodes`` it was given (all its buckets are ``max_dist``)."""
+    word = spd_flags(device)
+    f = int(word.item())
+    if f:
+        word.zero_()
+    if f & SPD_EDGE_OUT_OF_RANGE:
+        raise ValueError("shortest_path_buckets: an edge has an end outside its graph's node range; it was skipped")
+    if f & SPD_GRAPH_TOO_LARGE:
+        raise ValueError("shortest_path_buckets: a graph has more nodes than max_nodes says; its buckets are all max_dist")
+
+
+class SPDBuckets:
+    """What ``shortest_path_buckets`` answers: ``bucket`` [sum n_g^2] uint8 (graph g's [n_g, n_g] matrix row-major, row =
+    query, column = key, at ``spd_ptr[g]``), ``spd_ptr`` [B + 1] int64 on the same device, and the ``max_dist`` and
+    ``max_nodes`` it was built with.  ``max_dist + 1`` bucket values."""
+    __slots__ = ("bucket", "spd_ptr", "max_dist", "max_nodes")
+
+    def __init__(self, bucket: Tensor, spd_ptr: Tensor, max_dist: int, max_nodes: int):
+        self.bucket, self.spd_ptr, self.max_dist, self.max_nodes = bucket, spd_ptr, int(max_dist), int(max_nodes)
+
+    @property
+    def num_buckets(self) -> int:
+        return self.max_dist + 1
+
+    def __repr__(self) -> str:
+        return (f"SPDBuckets(bucket=[{self.bucket.numel()}], graphs={self.spd_ptr.numel() - 1}, "
+                f"max_dist={self.max_dist}, max_nodes={self.max_nodes})")
+
+
+def shortest_path_buckets(batch, max_dist: int, *, sizes=None) -> SPDBuckets:
+    """Shortest-path distance buckets of every graph of a collated batch (``hscn_spd_buckets``): ``bucket(i, j)`` = the
+    fewest edges on a directed path i -> j where that is below ``max_dist``, ``max_dist`` otherwise.
+
+    ``batch``: a ``graph_hscn.data.Batch`` on the device, or the tuple ``(edge_index, ptr32, eptr32, max_nodes)``.  The
+    layout needs every graph's node count ON THE HOST: ``train.batching.to_device`` takes them from the collated
+    batch's ``ptr`` while it is on the host and keeps them beside the device copy; with a tuple, or a batch moved
+    otherwise, pass ``sizes`` (a sequence of ints).  Nothing is read back from the device.  No CPU fallback."""
+    max_dist = int(max_dist)
+    if not SPD_MIN_DIST <= max_dist <= SPD_MAX_DIST:
+        raise ValueError(f"shortest_path_buckets: max_dist must be in [{SPD_MIN_DIST}, {SPD_MAX_DIST}], got {max_dist}")
+    if isinstance(batch, (tuple, list)):
+        if len(batch) != 4:
+            raise ValueError("shortest_path_buckets takes a Batch or (edge_index, ptr32, eptr32, max_nodes)")
+        edge_index, ptr32, eptr32, max_nodes = batch
+    else:
+        for attr in ("edge_index", "ptr32", "eptr32", "max_nodes"):
+            if not hasattr(batch, attr):
+                raise ValueError(f"the batch carries no {attr} (graph_hscn.data.Batch.from_data_list builds it)")
+        edge_index, ptr32, eptr32, max_nodes = batch.edge_index, batch.ptr32, batch.eptr32, batch.max_nodes
+        if sizes is None:
+            sizes = getattr(batch, "__dict__", {}).get("_host_sizes")
+    max_nodes = int(max_nodes)
+    if not spd_supported(max_nodes, max_dist):
+        raise ValueError(f"shortest_path_buckets: a graph of {max_nodes} nodes is outside the kernel's envelope (adjacency "
+                         "and two reachability bitsets of one graph within 160 KB of LDS: at most 646 nodes)")
+    if sizes is None:
+        raise ValueError("shortest_path_buckets needs every graph's node count on the host: a Batch moved by "
+                         "train.batching.to_device carries them, otherwise pass sizes=[n_0, n_1, ...]")
+    sizes = [int(n) for n in sizes]
+    B = ptr32.numel() - 1
+    if len(sizes) != B or any(n < 0 for n in sizes):
+        raise ValueError(f"shortest_path_buckets: {len(sizes)} sizes for {B} graphs")
+    if ptr32.dtype != torch.int32 or eptr32.dtype != torch.int32 or eptr32.numel() != B + 1:
+        raise TypeError("ptr32 and eptr32 must be int32 [B + 1] tensors (graph_hscn.data.Batch)")
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise TypeError("edge_index must be an int64 [2, E] tensor")
+    dev = ptr32.device
+    if not ptr32.is_cuda:
+        raise RuntimeError("shortest_path_buckets takes HIP device tensors only (got a CPU tensor): there is no CPU "
+                           "fallback -- move the batch to the device")
+    if edge_index.device != dev or eptr32.device != dev:
+        raise RuntimeError(f"edge_index is on {edge_index.device}, eptr32 on {eptr32.device}, ptr32 on {dev}")
+    host_ptr = torch.zeros(B + 1, dtype=torch.int64)
+    if B:
+        host_ptr[1:] = torch.cumsum(torch.as_tensor(sizes, dtype=torch.int64) ** 2, 0)
+    total = int(host_ptr[-1])
+    spd_ptr = host_ptr.to(dev)
+    bucket = torch.empty(total, dtype=torch.uint8, device=dev)
+    edge_index = edge_index.contiguous()
+    N, E = sum(sizes), int(edge_index.size(1))
+    call("hscn_spd_buckets", ptr(edge_index) if E else None, ptr(ptr32), ptr(eptr32), ptr(spd_ptr), N, E, B, total,
+         max_nodes, max_dist, ptr(bucket) if total else None, ptr(spd_flags(dev)), stream())
+    return SPDBuckets(bucket, spd_ptr, max_dist, max_nodes)
+
+
+def attention_bias_supported(heads: int, head_dim: int, num_buckets: int) -> bool:
+    return bool(_hip.lib().hscn_attention_bias_supported(int(heads), int(head_dim), int(num_buckets)))
+
+
+class BiasedSelfAttentionFn(Function):
+    """(qkv [N, 3D], table [num_buckets, heads], spd: SPDBuckets, ptr32, max_nodes, heads) -> out [N, D]:
+    ``SelfAttentionFn`` with ``table[bucket_ij, h]`` added to the logit of query i and key j in head h.  Forward: one
+    launch.  Backward: the query-keyed launch where ``qkv`` or ``table`` needs a gradient (with the table's ordered
+    fold behind it where ``table`` does), the key-keyed launch where ``qkv`` does.  No host read anywhere."""
+
+    @staticmethod
+    def forward(ctx, qkv: Tensor, table: Tensor, spd: SPDBuckets, ptr32: Tensor, max_nodes: int, heads: int):
+        qkv, table = _c(qkv), _c(table)
+        if qkv.dim() != 2 or qkv.size(1) % (3 * heads) != 0:
+            raise ValueError(f"qkv must be [N, 3 * heads * head_dim], got {tuple(qkv.shape)} for {heads} heads")
+        if not isinstance(spd, SPDBuckets):
+            raise TypeError("spd must be the SPDBuckets nn.functional.shortest_path_buckets answers")
+        N, D = qkv.size(0), qkv.size(1) // 3
+        dh = D // heads
+        if table.dim() != 2 or table.size(1) != heads or table.size(0) != spd.num_buckets:
+            raise ValueError(f"biased self-attention: the table must be [{spd.num_buckets}, {heads}] (max_dist + 1 "
+                             f"buckets by heads), got {tuple(table.shape)}")
+        nb = int(table.size(0))
+        if not attention_bias_supported(heads, dh, nb):
+            raise ValueError(f"biased self-attention: {heads} heads of width {dh} with {nb} buckets are outside the "
+                             f"kernel's envelope ({ATTN_ENVELOPE}, at most {ATTN_MAX_BUCKETS} buckets)")
+        if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
+            raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
+        for name, t in (("ptr32", ptr32), ("table", table), ("spd.bucket", spd.bucket), ("spd.spd_ptr", spd.spd_ptr)):
+            if t.device != qkv.device:
+                raise RuntimeError(f"{name} is on {t.device}, qkv on {qkv.device}: move the batch to the device once "
+                                   "(Batch.to); the operator does not copy it on every call")
+        B = ptr32.numel() - 1
+        if spd.spd_ptr.numel() != B + 1:
+            raise ValueError(f"spd holds {spd.spd_ptr.numel() - 1} graphs, ptr32 {B}")
+        total = int(spd.bucket.numel())
+        out = torch.empty(N, D, dtype=torch.float32, device=qkv.device)
+        lse = torch.empty(N, heads, dtype=torch.float32, device=qkv.device)
+        flag = attention_flags(qkv.device) if qkv.is_cuda else None
+        call("hscn_attention_bias_fwd", ptr(qkv), ptr(table), ptr(spd.bucket) if total else None, ptr(spd.spd_ptr),
+             ptr(ptr32), N, B, total, int(max_nodes), heads, dh, nb, ptr(out), ptr(lse), ptr(flag), stream())
+        ctx.dims = (N, B, total, int(max_nodes), heads, dh, nb)
+        ctx.save_for_backward(qkv, table, spd.bucket, spd.spd_ptr, ptr32, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out: Tensor):
+        need_qkv, need_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_qkv or need_table):
+            return None, None, None, None, None, None
+        qkv, table, bucket, spd_ptr, ptr32, out, lse = ctx.saved_tensors
+        N, B, total, max_nodes, heads, dh, nb = ctx.dims
+        g_out = _c(g_out)
+        g_qkv = torch.empty_like(qkv) if need_qkv else None
+        delta = torch.empty_like(lse)
+        g_table = work = None
+        floats = 0
+        if need_table:
+            g_table = torch.empty_like(table)
+            tile = int(_hip.lib().hscn_attention_tile())
+            floats = B * max(1, -(-max_nodes // tile)) * heads * nb
+            work = torch.empty(max(floats, 1), dtype=torch.float32, device=qkv.device)
+        flag = attention_flags(qkv.device)
+        pb = ptr(bucket) if total else None
+        call("hscn_attention_bias_bwd_q", ptr(qkv), ptr(out), ptr(lse), ptr(g_out), ptr(table), pb, ptr(spd_ptr),
+             ptr(ptr32), N, B, total, max_nodes, heads, dh, nb, ptr(g_qkv), ptr(delta), ptr(g_table), ptr(work), floats,
+             ptr(flag), stream())
+        if need_qkv:
+            call("hscn_attention_bias_bwd_kv", ptr(qkv), ptr(lse), ptr(delta), ptr(g_out), ptr(table), pb, ptr(spd_ptr),
+                 ptr(ptr32), N, B, total, max_nodes, heads, dh, nb, ptr(g_qkv), ptr(flag), stream())
+        return g_qkv, g_table, None, None, None, None
 
 
 # --------------------------------------------------------------------------- #

@@ -42,7 +42,7 @@ def _norm(kind: Optional[str], channels: int) -> Optional[nn.Module]:
 
 class GPSLayer(nn.Module):
     def __init__(self, channels: int, local_conv: Optional[str], num_heads: int, dropout: float = 0.0,
-                 norm: Optional[str] = "layer", act: str = "relu"):
+                 norm: Optional[str] = "layer", act: str = "relu", spd_buckets: Optional[int] = None):
         super().__init__()
         from ..config.config import CONV_DICT
         if local_conv is not None:
@@ -65,7 +65,8 @@ class GPSLayer(nn.Module):
             self.conv = CONV_DICT[local_conv](channels, channels // num_heads, heads=num_heads)
         else:
             self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
-        self.attn = MultiheadSelfAttention(channels, num_heads)
+        # spd_buckets: the attention's own shortest-path bias table (Graphormer's spatial encoding); None: as before
+        self.attn = MultiheadSelfAttention(channels, num_heads, spd_buckets=spd_buckets)
         self.norm1_local = _norm(norm, channels) if local_conv is not None else None
         self.norm1_attn = _norm(norm, channels)
         self.ff_linear1 = Linear(channels, 2 * channels)
@@ -85,12 +86,16 @@ class GPSLayer(nn.Module):
         return Fh.dropout(x, p=self.dropout, training=self.training, seed=seed)
 
     def forward(self, x: Tensor, edge_index, batch=None, edge_attr: Optional[Tensor] = None, *,
-                ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None):
-        """``batch``: the ``Batch`` (graph boundaries of the attention), or ``ptr32`` and ``max_nodes``.  ``edge_attr``
+                ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None, spd=None):
+        """``batch``: the ``Batch`` (graph boundaries of the attention), or ``ptr32`` and ``max_nodes``.  ``spd``: the
+        batch's ``SPDBuckets``, for a layer built with ``spd_buckets`` (refused by name otherwise).  ``edge_attr``
         is read by an edge-aware ``local_conv`` ("gine", "gatedgcn", "transformerconv_edge") only.  Returns the node features; with a
         ``local_conv`` that updates the edge features ("gatedgcn") the pair ``(h, edge_attr_out)``."""
         edge_out = None
-        h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes)
+        if spd is None:                             # (the call of before, word for word)
+            h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes)
+        else:
+            h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes, spd=spd)
         h_a = x + self._drop(h_a, 1)
         if self.norm1_attn is not None:
             h_a = self.norm1_attn(h_a)

@@ -109,7 +109,9 @@ def forward(model, batch) -> Tuple[Tensor, Tensor]:
 
 def to_device(model, batch, device):
     """A loader's batch where the HIP operators can take it."""
+    host = batch
     batch = batch.to(device)
+    _carry_host_side(host, batch)
     if not is_hetero(model):
         # a categorical encoder (model.encoder_kinds: node, edge) reads its tensor as int64 categories
         node_enc, edge_enc = getattr(model, "encoder_kinds", (None, None))
@@ -118,6 +120,23 @@ def to_device(model, batch, device):
         if edge_attr is not None:                   # OGB bond features are integers
             batch.edge_attr = edge_attr.float() if edge_enc is None else _categories(edge_attr, "edge_attr")
     return batch
+
+
+def _carry_host_side(src, dst) -> None:
+    """What a homogeneous batch keeps on the host beside its keys, handed from ``src`` to its copy ``dst``: every graph's
+    node count (from ``ptr`` while that still lies on the host: integer work on the host, nothing read back) and the
+    dict of what a model derives from the batch's structure once (model/gps.py: the shortest-path buckets, keyed by
+    (max_dist, device)) -- ONE dict for the loader's batch and every copy made of it here, so a batch reused across
+    epochs is computed once."""
+    if not hasattr(src, "__dict__") or not hasattr(dst, "__dict__") or "ptr" not in getattr(src, "_d", {}):
+        return
+    sizes = src.__dict__.get("_host_sizes")
+    if sizes is None and isinstance(src.ptr, Tensor) and not src.ptr.is_cuda:
+        sizes = tuple(int(n) for n in (src.ptr[1:] - src.ptr[:-1]).tolist())
+        src.__dict__["_host_sizes"] = sizes
+    if sizes is not None:
+        dst.__dict__["_host_sizes"] = sizes
+    dst.__dict__["_spd_cache"] = src.__dict__.setdefault("_spd_cache", {})
 
 
 def _categories(t: Tensor, name: str) -> Tensor:

@@ -1621,6 +1621,65 @@ int hscn_edge_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const 
                            const float* g_out, float* dk /*[Ns, HC]*/, float* dv /*[Ns, HC]*/, int64_t Nd, int64_t Ns,
                            int64_t E, int heads, int head_dim, int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Shortest-path buckets (csrc/spd.hip) and the self-attention they bias (csrc/attention_bias.hip): Graphormer's
+ * spatial encoding inside the global attention above.  Purely additive to ABI 24; the unbiased entry points are
+ * unchanged.
+ *
+ * hscn_spd_buckets: ONE launch, one workgroup per graph.  d(i, j) = the fewest edges on a directed path i -> j inside
+ *   graph g, following edge_index [2, E] i64 as source -> target (the edges of graph g are the columns
+ *   [eptr32[g], eptr32[g + 1]), its nodes [ptr32[g], ptr32[g + 1])); d(i, i) = 0; self-loops and parallel edges change
+ *   nothing.  bucket(i, j) = d(i, j) where d(i, j) < max_dist and max_dist otherwise (farther and unreachable alike):
+ *   max_dist + 1 values, uint8, graph g's [n_g, n_g] matrix row-major (row = query i, column = key j) at
+ *   bucket + spd_ptr[g]; spd_ptr [B + 1] i64 and total = the bucket tensor's length come from the caller (the running
+ *   sums of n_g^2).  Adjacency and two reachability matrices are bitsets in LDS, breadth-first levels run one word (32
+ *   targets) at a time for up to max_dist - 1 levels and stop when a level finds nothing.  Integers: the same result
+ *   on every run, wherever the graph stands.  flag [1] i32, only ever OR-ed into: bit 0 = an edge with an end outside
+ *   its graph (skipped), bit 1 = a graph with more than max_nodes nodes (all its buckets are max_dist) or whose range
+ *   [spd_ptr[g], spd_ptr[g] + n_g^2) leaves [0, total) (not written).
+ * hscn_spd_supported: 1 for max_dist in [1, 63] and 3 * max_nodes * ceil(max_nodes / 32) * 4 bytes + 1 KB within a
+ *   CU's 160 KB of LDS (max_nodes <= 646).
+ *   HSCN_E_BADARG for null pointers (edge_index may be NULL when E == 0), negative sizes, N, E or B beyond 2^31 - 1;
+ *   HSCN_E_UNSUPPORTED where hscn_spd_supported is 0; both before any launch.  N = 0 or B = 0 launches nothing.
+ *
+ * hscn_attention_bias_fwd / _bwd_q / _bwd_kv: hscn_attention_fwd / _bwd_q / _bwd_kv with
+ *     s_ij = scale <q_i, k_j> + table[bucket_ij, h]
+ *   table [num_buckets, heads] f32, num_buckets <= 64; bucket / spd_ptr / total as above (a bucket value >=
+ *   num_buckets is read as num_buckets - 1).  The same tiles, chunks, online softmax, lse and determinism; the logit is
+ *   computed as the unbiased kernels compute it and the bias is added to it, so an all-zero table gives out, lse and
+ *   g_qkv bit-equal to the unbiased entry points'.  The bucket bytes of a tile x chunk are staged through LDS by the
+ *   whole wave along the key index.
+ *   hscn_attention_bias_bwd_q also gives g_table [num_buckets, heads] (or NULL: not wanted): g_table[b, h] = sum over
+ *   the pairs with bucket_ij = b of p_ij (<g_out_i, v_j> - delta_i).  No float atomics: a lane sums its row's terms per
+ *   bucket in key order, a tile sums its lanes in lane order into workspace [B * tiles, heads, num_buckets] f32
+ *   (tiles = max(1, ceil(max_nodes / hscn_attention_tile())); workspace_floats says how many floats it holds), and a
+ *   second launch adds the tiles in tile order: bit-identical between runs.  g_qkv may be NULL there (the Q third is
+ *   then not written; g_table must be given).  N = 0 or B = 0 with a g_table writes zeros to it.
+ *   flag: the attention operator's word; bit 2 as above, bit 3 = a graph whose bucket range leaves [0, total): its
+ *   rows are NaN too, and g_table with them.
+ *   HSCN_E_BADARG / HSCN_E_UNSUPPORTED as the unbiased entry points, with hscn_attention_bias_supported =
+ *   hscn_attention_supported and 1 <= num_buckets <= 64; HSCN_E_WORKSPACE for a workspace that is too small; all before
+ *   any launch.  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_spd_supported(int max_nodes, int max_dist);
+int hscn_spd_buckets(const int64_t* edge_index, const int32_t* ptr32, const int32_t* eptr32, const int64_t* spd_ptr,
+                     int64_t N, int64_t E, int64_t B, int64_t total, int max_nodes, int max_dist,
+                     uint8_t* bucket /*[total]*/, int32_t* flag /*[1]*/, void* stream);
+int hscn_attention_bias_supported(int heads, int dh, int num_buckets);
+int hscn_attention_bias_fwd(const float* qkv, const float* table, const uint8_t* bucket, const int64_t* spd_ptr,
+                            const int32_t* ptr32, int64_t N, int64_t B, int64_t total, int max_nodes, int heads, int dh,
+                            int num_buckets, float* out /*[N, D]*/, float* lse /*[N, heads]*/, int32_t* flag /*[1]*/,
+                            void* stream);
+int hscn_attention_bias_bwd_q(const float* qkv, const float* out, const float* lse, const float* g_out,
+                              const float* table, const uint8_t* bucket, const int64_t* spd_ptr, const int32_t* ptr32,
+                              int64_t N, int64_t B, int64_t total, int max_nodes, int heads, int dh, int num_buckets,
+                              float* g_qkv /*[N, 3D]*/, float* delta /*[N, heads]*/, float* g_table, float* workspace,
+                              int64_t workspace_floats, int32_t* flag /*[1]*/, void* stream);
+int hscn_attention_bias_bwd_kv(const float* qkv, const float* lse, const float* delta, const float* g_out,
+                               const float* table, const uint8_t* bucket, const int64_t* spd_ptr, const int32_t* ptr32,
+                               int64_t N, int64_t B, int64_t total, int max_nodes, int heads, int dh, int num_buckets,
+                               float* g_qkv /*[N, 3D]*/, int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
