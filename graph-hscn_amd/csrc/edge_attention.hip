@@ -46,25 +46,6 @@ constexpr int EA_CHUNK = 64;       // slots per chunk of a split row (hscn_edge_
 constexpr int EA_MAX_WIDTH = 512;  // heads * head_dim
 constexpr int EA_NC = 8;           // floats a lane holds of one operand row: (8 / VEC) passes of VEC columns
 
-template <int VEC>
-struct EV;
-template <>
-struct EV<4> {
-  using T = float4;
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
-  static __device__ __forceinline__ float get(const T& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
-  static __device__ __forceinline__ T make(const float* a) { return make_float4(a[0], a[1], a[2], a[3]); }
-};
-template <>
-struct EV<1> {
-  using T = float;
-  static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-  static __device__ __forceinline__ float get(const T& v, int) { return v; }
-  static __device__ __forceinline__ T make(const float* a) { return a[0]; }
-};
-
 struct EAArgs {
   const int32_t* rowptr;   // the walked CSR: keyed by target (MODE 0, 1) or by source (MODE 2)
   const int32_t* col;
@@ -91,7 +72,7 @@ struct EAArgs {
 // with c >= C idles (C % VEC == 0, so a vector never straddles the end of a head)
 template <int VEC>
 __device__ __forceinline__ void load_cols(const EAArgs& A, const float* row, int lg, float (&x)[EA_NC]) {
-  using V = EV<VEC>;
+  using V = GV<VEC>;
 #pragma unroll
   for (int i = 0; i < EA_NC; ++i) x[i] = 0.f;
 #pragma unroll
@@ -107,7 +88,7 @@ __device__ __forceinline__ void load_cols(const EAArgs& A, const float* row, int
 
 template <int VEC>
 __device__ __forceinline__ void store_cols(const EAArgs& A, float* row, int lg, const float (&x)[EA_NC]) {
-  using V = EV<VEC>;
+  using V = GV<VEC>;
 #pragma unroll
   for (int p = 0; p < EA_NC / VEC; ++p) {
     const int c = (p * A.G + lg) * VEC;
@@ -351,8 +332,6 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
 bool ea_supported(int heads, int head_dim) {
   return heads >= 1 && head_dim >= 1 && (int64_t)heads * head_dim <= EA_MAX_WIDTH;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <int MODE>
 int launch_walk(EAArgs A, hipStream_t st) {

@@ -32,27 +32,6 @@ constexpr int GINE_CHUNK = 64;       // slots per chunk of a split row (hscn_gin
 constexpr int GINE_MAX_F = 512;
 constexpr int GINE_MAX_DE = 64;
 
-template <int VEC>
-struct GV;
-template <>
-struct GV<4> {
-  using T = float4;
-  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
-  static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  static __device__ __forceinline__ float get(const T& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
-  static __device__ __forceinline__ T make(const float* a) { return make_float4(a[0], a[1], a[2], a[3]); }
-};
-template <>
-struct GV<1> {
-  using T = float;
-  static __device__ __forceinline__ T load(const float* p) { return *p; }
-  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
-  static __device__ __forceinline__ T zero() { return 0.f; }
-  static __device__ __forceinline__ float get(const T& v, int) { return v; }
-  static __device__ __forceinline__ T make(const float* a) { return a[0]; }
-};
-
 // The lane's VEC rows of lin.weight and lin.bias.  DREG > 0: De <= DREG, the rows live in registers (columns past De
 // are zero and meet a zero edge feature).  DREG == 0: any De, the rows are read through the cache per edge.
 template <int VEC, int DREG>

@@ -20,6 +20,9 @@ static inline unsigned hscn_blocks(int64_t work, int per_block) {
   return (unsigned)(b < 1 ? 1 : b);
 }
 
+// what the float4 paths ask of a pointer
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // LDS of a gfx950 CU, the most one workgroup can be given; and the LDS (static + dynamic) a kernel gets without asking
 constexpr size_t LDS_CU_BYTES = 160 * 1024;
 constexpr size_t LDS_NO_OPT_IN_BYTES = 64 * 1024;
@@ -47,6 +50,29 @@ static int launch_with_lds(void (*kernel)(KA...), unsigned grid, int threads, si
 // round(w*x) followed by round(acc + .) (torch index_add_), never a fused fma.
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+
+// VEC = 4 or 1 feature columns a lane: float4 where width and pointers allow, float otherwise (the row-walk kernels of
+// gine.hip, gatedgcn.hip and edge_attention.hip)
+template <int VEC>
+struct GV;
+template <>
+struct GV<4> {
+  using T = float4;
+  static __device__ __forceinline__ T load(const float* p) { return *reinterpret_cast<const float4*>(p); }
+  static __device__ __forceinline__ void store(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
+  static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  static __device__ __forceinline__ float get(const T& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+  static __device__ __forceinline__ T make(const float* a) { return make_float4(a[0], a[1], a[2], a[3]); }
+};
+template <>
+struct GV<1> {
+  using T = float;
+  static __device__ __forceinline__ T load(const float* p) { return *p; }
+  static __device__ __forceinline__ void store(float* p, T v) { *p = v; }
+  static __device__ __forceinline__ T zero() { return 0.f; }
+  static __device__ __forceinline__ float get(const T& v, int) { return v; }
+  static __device__ __forceinline__ T make(const float* a) { return a[0]; }
+};
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {

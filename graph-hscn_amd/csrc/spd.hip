@@ -1,5 +1,5 @@
 // All-pairs shortest-path buckets per graph of a collated batch (Graphormer's spatial encoding, the index of the
-// attention bias of csrc/attention_bias.hip).
+// attention bias of csrc/attention.hip).
 //
 //   d(i, j) = the fewest edges on a directed path i -> j inside graph g (edge_index = [source; target]), d(i, i) = 0;
 //   bucket(i, j) = d(i, j) where d(i, j) < max_dist, max_dist otherwise ("farther" and "unreachable" alike):

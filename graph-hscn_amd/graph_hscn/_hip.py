@@ -235,7 +235,7 @@ _SIGNATURES = {
                                        P, P]),
     "hscn_edge_attn_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int,
                                        P, P]),
-    # shortest-path buckets and the attention they bias (csrc/spd.hip, csrc/attention_bias.hip; additive to ABI 24)
+    # shortest-path buckets and the attention they bias (csrc/spd.hip, csrc/attention.hip; additive to ABI 24)
     "hscn_spd_supported": (c_int, [c_int, c_int]),
     "hscn_spd_buckets": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, P, P, P]),
     "hscn_attention_bias_supported": (c_int, [c_int, c_int, c_int]),
@@ -354,3 +354,28 @@ def check(rc: int, name: str) -> None:
 
 def call(name: str, *args) -> None:
     check(getattr(lib(), name)(*args), name)
+
+
+class FlagWord:
+    """One kernel family's flag word: per device a zero-initialised [1] int32 tensor that its launches OR bits into."""
+
+    def __init__(self):
+        self._words = {}
+
+    def of(self, device) -> torch.Tensor:
+        """The word of ``device`` (a device without an index is the current one)."""
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device(device.type, torch.cuda.current_device())
+        t = self._words.get(device)
+        if t is None:
+            t = self._words[device] = torch.zeros(1, dtype=torch.int32, device=device)
+        return t
+
+    def take(self, device) -> int:
+        """Synchronising: read the word of ``device`` and clear it."""
+        word = self.of(device)
+        f = int(word.item())
+        if f:
+            word.zero_()
+        return f

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from ._hip import call, lib, ptr, stream
+from ._hip import FlagWord, call, lib, ptr, stream
 
 
 class LazyScaled(torch.Tensor):
@@ -205,18 +205,12 @@ class _CriterionFn(Function):
 # bits of hscn_softmax_nll_fwd's ``flags`` (include/hscn.h).  Only the first becomes an error here: a NaN prediction
 # makes the loss itself NaN, as in torch, so NAN_PRED is there for a caller that reads the word, nothing raises on it
 TARGET_OUT_OF_RANGE, NAN_PRED = 1, 2
-_NLL_FLAGS = {}
+_NLL_FLAGS = FlagWord()
 
 
 def class_target_flags(device) -> torch.Tensor:
     """The device's flag word [1] int32 that every multiclass ``criterion`` call ORs its bits into."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device(device.type, torch.cuda.current_device())
-    t = _NLL_FLAGS.get(device)
-    if t is None:
-        t = _NLL_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
+    return _NLL_FLAGS.of(device)
 
 
 def raise_for_class_flags(flags: int) -> None:
@@ -228,11 +222,7 @@ def check_class_targets(device) -> None:
     """Synchronising: read and clear the device's flag word; ``IndexError`` if a multiclass ``criterion`` call since
     the last check met a class index outside ``[0, C)`` (torch's own error for it, raised late).  A ``NAN_PRED`` bit
     is cleared with it and raises nothing: the loss of that call is NaN already."""
-    word = class_target_flags(device)
-    f = int(word.item())
-    if f:
-        word.zero_()
-    raise_for_class_flags(f)
+    raise_for_class_flags(_NLL_FLAGS.take(device))
 
 
 def softmax_nll_workspace(R: int, C: int, device):

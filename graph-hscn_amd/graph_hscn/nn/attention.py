@@ -51,7 +51,7 @@ class MultiheadSelfAttention(nn.Module):
     ``spd_buckets=K`` adds Graphormer's spatial encoding: the module owns ``spd_bias.weight`` [K, num_heads] (drawn
     normal(0, 0.02) after every other parameter) and ``forward(x, batch, spd=...)`` takes the batch's ``SPDBuckets``
     (``nn.functional.shortest_path_buckets``) with ``max_dist + 1 == K``; logit (i, j) of head h gains
-    ``spd_bias.weight[bucket_ij, h]`` (csrc/attention_bias.hip).  Without it the module is what it always was.
+    ``spd_bias.weight[bucket_ij, h]`` (csrc/attention.hip).  Without it the module is what it always was.
 
     Not provided, refused by name: dropout on the attention weights, ``need_weights``, a dense attention bias tensor or
     any mask other than the graph boundary, ``spd=`` on a module without ``spd_buckets``, an ``embed_dim`` that

@@ -655,7 +655,7 @@ ATTN_GRAPH_TOO_LARGE = 4          # flag bit 2: a graph with more than max_nodes
 ATTN_ENVELOPE = (f"head width embed_dim / num_heads a multiple of 4 in [{ATTN_MIN_HEAD_DIM}, {ATTN_MAX_HEAD_DIM}], "
                  f"num_heads >= 1, embed_dim <= {ATTN_MAX_WIDTH}")
 
-_ATTN_FLAGS = {}
+_ATTN_FLAGS = _hip.FlagWord()
 
 
 def attention_supported(heads: int, head_dim: int) -> bool:
@@ -664,27 +664,36 @@ def attention_supported(heads: int, head_dim: int) -> bool:
 
 def attention_flags(device) -> Tensor:
     """The device's flag word [1] int32 that every attention launch ORs into; ``check_attention`` reads and clears it."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device(device.type, torch.cuda.current_device())
-    t = _ATTN_FLAGS.get(device)
-    if t is None:
-        t = _ATTN_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
+    return _ATTN_FLAGS.of(device)
 
 
 def check_attention(device) -> None:
     """Synchronising: ``ValueError`` if an attention launch since the last check met a graph larger than the
     ``max_nodes`` it was given (that graph's rows are NaN)."""
-    word = attention_flags(device)
-    f = int(word.item())
-    if f:
-        word.zero_()
+    f = _ATTN_FLAGS.take(device)
     if f & ATTN_GRAPH_TOO_LARGE:
         raise ValueError("self-attention: a graph has more nodes than the batch's max_nodes says; its rows are NaN")
     if f & 8:           # ATTN_BUCKETS_OUT_OF_RANGE (the biased operator below)
         raise ValueError("biased self-attention: a graph's bucket range lies outside the bucket tensor (the SPDBuckets "
                          "belong to another batch); its rows are NaN")
+
+
+def _attention_dims(qkv: Tensor, ptr32: Tensor, heads: int, operands):
+    """What both attention operators check of ``qkv`` and ``ptr32`` -> (N, D, dh, B).  ``operands(dh)`` holds the
+    operator's own checks (the envelope, its further arguments); it runs between those of ``qkv`` and of ``ptr32``,
+    raises, or answers the (name, tensor) pairs that must sit on ``qkv``'s device beside ``ptr32``."""
+    if qkv.dim() != 2 or qkv.size(1) % (3 * heads) != 0:
+        raise ValueError(f"qkv must be [N, 3 * heads * head_dim], got {tuple(qkv.shape)} for {heads} heads")
+    N, D = qkv.size(0), qkv.size(1) // 3
+    dh = D // heads
+    others = operands(dh)
+    if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
+        raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
+    for name, t in (("ptr32", ptr32), *others):
+        if t.device != qkv.device:
+            raise RuntimeError(f"{name} is on {t.device}, qkv on {qkv.device}: move the batch to the device once "
+                               "(Batch.to); the operator does not copy it on every call")
+    return N, D, dh, ptr32.numel() - 1
 
 
 class SelfAttentionFn(Function):
@@ -695,19 +704,14 @@ class SelfAttentionFn(Function):
     @staticmethod
     def forward(ctx, qkv: Tensor, ptr32: Tensor, max_nodes: int, heads: int):
         qkv = _c(qkv)
-        if qkv.dim() != 2 or qkv.size(1) % (3 * heads) != 0:
-            raise ValueError(f"qkv must be [N, 3 * heads * head_dim], got {tuple(qkv.shape)} for {heads} heads")
-        N, D = qkv.size(0), qkv.size(1) // 3
-        dh = D // heads
-        if not attention_supported(heads, dh):
-            raise ValueError(f"self-attention: {heads} heads of width {dh} are outside the kernel's envelope "
-                             f"({ATTN_ENVELOPE})")
-        if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
-            raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
-        if ptr32.device != qkv.device:
-            raise RuntimeError(f"ptr32 is on {ptr32.device}, qkv on {qkv.device}: move the batch to the device once "
-                               "(Batch.to); the operator does not copy it on every call")
-        B = ptr32.numel() - 1
+
+        def operands(dh):
+            if not attention_supported(heads, dh):
+                raise ValueError(f"self-attention: {heads} heads of width {dh} are outside the kernel's envelope "
+                                 f"({ATTN_ENVELOPE})")
+            return ()
+
+        N, D, dh, B = _attention_dims(qkv, ptr32, heads, operands)
         out = torch.empty(N, D, dtype=torch.float32, device=qkv.device)
         lse = torch.empty(N, heads, dtype=torch.float32, device=qkv.device)
         flag = attention_flags(qkv.device) if qkv.is_cuda else None
@@ -735,7 +739,7 @@ class SelfAttentionFn(Function):
 
 
 # --------------------------------------------------------------------------- #
-# Shortest-path buckets (csrc/spd.hip) and the self-attention they bias (csrc/attention_bias.hip): Graphormer's
+# Shortest-path buckets (csrc/spd.hip) and the self-attention they bias (csrc/attention.hip, BiasArgs): Graphormer's
 # spatial encoding inside the global attention
 # --------------------------------------------------------------------------- #
 SPD_MIN_DIST = 1
@@ -745,7 +749,7 @@ SPD_GRAPH_TOO_LARGE = 2           # flag bit 1: a graph with more than max_nodes
 ATTN_MAX_BUCKETS = 64
 ATTN_BUCKETS_OUT_OF_RANGE = 8     # attention flag bit 3: a graph's bucket range leaves the bucket tensor (rows NaN)
 
-_SPD_FLAGS = {}
+_SPD_FLAGS = _hip.FlagWord()
 
 
 def spd_supported(max_nodes: int, max_dist: int) -> bool:
@@ -755,22 +759,13 @@ def spd_supported(max_nodes: int, max_dist: int) -> bool:
 
 def spd_flags(device) -> Tensor:
     """The device's flag word [1] int32 that every bucket launch ORs into; ``check_spd`` reads and clears it."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device(device.type, torch.cuda.current_device())
-    t = _SPD_FLAGS.get(device)
-    if t is None:
-        t = _SPD_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
+    return _SPD_FLAGS.of(device)
 
 
 def check_spd(device) -> None:
     """Synchronising: ``ValueError`` if a bucket launch since the last check met an edge with an end outside its graph
     (skipped) or a graph larger than the ``max_nodes`` it was given (all its buckets are ``max_dist``)."""
-    word = spd_flags(device)
-    f = int(word.item())
-    if f:
-        word.zero_()
+    f = _SPD_FLAGS.take(device)
     if f & SPD_EDGE_OUT_OF_RANGE:
         raise ValueError("shortest_path_buckets: an edge has an end outside its graph's node range; it was skipped")
     if f & SPD_GRAPH_TOO_LARGE:
@@ -864,26 +859,20 @@ class BiasedSelfAttentionFn(Function):
     @staticmethod
     def forward(ctx, qkv: Tensor, table: Tensor, spd: SPDBuckets, ptr32: Tensor, max_nodes: int, heads: int):
         qkv, table = _c(qkv), _c(table)
-        if qkv.dim() != 2 or qkv.size(1) % (3 * heads) != 0:
-            raise ValueError(f"qkv must be [N, 3 * heads * head_dim], got {tuple(qkv.shape)} for {heads} heads")
-        if not isinstance(spd, SPDBuckets):
-            raise TypeError("spd must be the SPDBuckets nn.functional.shortest_path_buckets answers")
-        N, D = qkv.size(0), qkv.size(1) // 3
-        dh = D // heads
-        if table.dim() != 2 or table.size(1) != heads or table.size(0) != spd.num_buckets:
-            raise ValueError(f"biased self-attention: the table must be [{spd.num_buckets}, {heads}] (max_dist + 1 "
-                             f"buckets by heads), got {tuple(table.shape)}")
+
+        def operands(dh):
+            if not isinstance(spd, SPDBuckets):
+                raise TypeError("spd must be the SPDBuckets nn.functional.shortest_path_buckets answers")
+            if table.dim() != 2 or table.size(1) != heads or table.size(0) != spd.num_buckets:
+                raise ValueError(f"biased self-attention: the table must be [{spd.num_buckets}, {heads}] (max_dist + 1 "
+                                 f"buckets by heads), got {tuple(table.shape)}")
+            if not attention_bias_supported(heads, dh, int(table.size(0))):
+                raise ValueError(f"biased self-attention: {heads} heads of width {dh} with {table.size(0)} buckets are "
+                                 f"outside the kernel's envelope ({ATTN_ENVELOPE}, at most {ATTN_MAX_BUCKETS} buckets)")
+            return ("table", table), ("spd.bucket", spd.bucket), ("spd.spd_ptr", spd.spd_ptr)
+
+        N, D, dh, B = _attention_dims(qkv, ptr32, heads, operands)
         nb = int(table.size(0))
-        if not attention_bias_supported(heads, dh, nb):
-            raise ValueError(f"biased self-attention: {heads} heads of width {dh} with {nb} buckets are outside the "
-                             f"kernel's envelope ({ATTN_ENVELOPE}, at most {ATTN_MAX_BUCKETS} buckets)")
-        if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
-            raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
-        for name, t in (("ptr32", ptr32), ("table", table), ("spd.bucket", spd.bucket), ("spd.spd_ptr", spd.spd_ptr)):
-            if t.device != qkv.device:
-                raise RuntimeError(f"{name} is on {t.device}, qkv on {qkv.device}: move the batch to the device once "
-                                   "(Batch.to); the operator does not copy it on every call")
-        B = ptr32.numel() - 1
         if spd.spd_ptr.numel() != B + 1:
             raise ValueError(f"spd holds {spd.spd_ptr.numel() - 1} graphs, ptr32 {B}")
         total = int(spd.bucket.numel())
@@ -935,7 +924,7 @@ CATENC_ENVELOPE = (f"emb_dim a multiple of 4 in [4, {CATENC_MAX_WIDTH}], at most
                    f"at most {CATENC_MAX_ROWS} categories in all")
 CATENC_BAD_INDEX = 1              # flag bit 0: an index outside [0, cardinality) of its column (its term is skipped)
 
-_CATENC_FLAGS = {}
+_CATENC_FLAGS = _hip.FlagWord()
 
 
 def catenc_supported(D: int, F: int, R: int) -> bool:
@@ -946,22 +935,13 @@ def catenc_supported(D: int, F: int, R: int) -> bool:
 def categorical_flags(device) -> Tensor:
     """The device's flag word [1] int32 that every categorical-encoder launch ORs into; ``check_categorical`` reads
     and clears it."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device(device.type, torch.cuda.current_device())
-    t = _CATENC_FLAGS.get(device)
-    if t is None:
-        t = _CATENC_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
+    return _CATENC_FLAGS.of(device)
 
 
 def check_categorical(device) -> None:
     """Synchronising: ``IndexError`` if a categorical-encoder launch since the last check met an index outside
     [0, cardinality) of its column (the term was skipped, nothing was read out of bounds)."""
-    word = categorical_flags(device)
-    f = int(word.item())
-    if f:
-        word.zero_()
+    if _CATENC_FLAGS.take(device):
         raise IndexError("categorical encoder: a feature holds an index outside [0, cardinality) of its column "
                          "(its embedding was left out of the sum)")
 

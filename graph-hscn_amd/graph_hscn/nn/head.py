@@ -186,29 +186,19 @@ def pair_dot_bwd_raw(z: Tensor, st: PairStructure, g_score: Tensor, scale: Optio
     return g_z
 
 
-_PAIR_FLAGS = {}
+_PAIR_FLAGS = _hip.FlagWord()
 PAIR_ID_OUT_OF_RANGE = 1          # include/hscn.h: HSCN_PAIR_ID_OUT_OF_RANGE
 
 
 def pair_flags(device) -> Tensor:
     """The device's flag word [1] int32 that every ``pair_dot`` forward ORs into (a pair id outside ``[0, N)``: its
     score is 0).  ``check_pair_ids`` reads and clears it."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device(device.type, torch.cuda.current_device())
-    t = _PAIR_FLAGS.get(device)
-    if t is None:
-        t = _PAIR_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
+    return _PAIR_FLAGS.of(device)
 
 
 def check_pair_ids(device) -> None:
     """Synchronising: ``IndexError`` if a ``pair_dot`` call since the last check met a node id outside ``[0, N)``."""
-    word = pair_flags(device)
-    f = int(word.item())
-    if f:
-        word.zero_()
-    if f & PAIR_ID_OUT_OF_RANGE:
+    if _PAIR_FLAGS.take(device) & PAIR_ID_OUT_OF_RANGE:
         raise IndexError("edge_label_index holds node ids outside [0, num_nodes)")
 
 

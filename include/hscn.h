@@ -1622,7 +1622,7 @@ int hscn_edge_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const 
                            int64_t E, int heads, int head_dim, int32_t* flag /*[1]*/, void* stream);
 
 /* ------------------------------------------------------------------------- *
- * Shortest-path buckets (csrc/spd.hip) and the self-attention they bias (csrc/attention_bias.hip): Graphormer's
+ * Shortest-path buckets (csrc/spd.hip) and the self-attention they bias (csrc/attention.hip, BiasArgs): Graphormer's
  * spatial encoding inside the global attention above.  Purely additive to ABI 24; the unbiased entry points are
  * unchanged.
  *

@@ -1,4 +1,4 @@
-"""Shortest-path attention bias on the HIP path (csrc/spd.hip, csrc/attention_bias.hip, nn/attention.py, nn/gps.py,
+"""Shortest-path attention bias on the HIP path (csrc/spd.hip, csrc/attention.hip, nn/attention.py, nn/gps.py,
 model/gps.py) against the plain-torch restatement of tests/attention_bias_oracle.py.
 
 Buckets are integers: bit-exact against the oracle's BFS.  The operator, the module, the layer and the model go by

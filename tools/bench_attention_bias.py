@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Shortest-path attention bias (graph_hscn/nn/functional.py shortest_path_buckets / BiasedSelfAttentionFn, csrc/spd.hip,
-csrc/attention_bias.hip): three times per case, on the same device batches --
+csrc/attention.hip): three times per case, on the same device batches --
 * ``buckets``: the bucket build of every batch (one launch per batch; in a model it runs once per batch object);
 * ``biased``: forward plus backward of the biased operator (gradients for qkv and the table);
 * ``unbiased``: forward plus backward of ``SelfAttentionFn`` on the same qkv, the same cotangent.
