@@ -31,18 +31,14 @@
 //   MODE 2, source-keyed CSR (backward): dk_j = sum_{k: src_k = j} scale ds_k q_i,   dv_j = sum a_k dout_i
 // Owner-computes, sums in CSR slot order, no float atomics: the same input gives the same bits.
 //
-// Long rows: rows of more than EA_LONG_ROW slots are left out of the serial walk and taken by the WHOLE workgroup
-// afterwards in chunks of EA_CHUNK slots, one lane group per chunk.  The forward's chunk partials are (max, sum,
-// accumulator) triples merged in chunk order, the backward's are plain sums added in chunk order: the result depends
-// on the row alone, so it is bitwise reproducible and independent of the row's place in a batch.
-#include "hscn_common.h"
+// Long rows: the two-phase scheme described in csrc/row_walk.h with a (row, head) pair as the unit; the forward's chunk
+// partials are (max, sum, accumulator) triples merged in chunk order, the backward's plain sums added in chunk order.
+#include "row_walk.h"
 #include <math.h>
 
 namespace {
 
 constexpr int EA_THREADS = 256;
-constexpr int EA_LONG_ROW = 256;   // rows with MORE slots than this are split (hscn_edge_attn_long_row)
-constexpr int EA_CHUNK = 64;       // slots per chunk of a split row (hscn_edge_attn_chunk)
 constexpr int EA_MAX_WIDTH = 512;  // heads * head_dim
 constexpr int EA_NC = 8;           // floats a lane holds of one operand row: (8 / VEC) passes of VEC columns
 
@@ -251,14 +247,14 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
   const int64_t units = A.rows * A.Hd;
   const int64_t tiles = (units + A.UPB - 1) / A.UPB;
   int any_long = 0;
-  // ---- rows of at most EA_LONG_ROW slots: one lane group per (row, head), serially ------------------------------
+  // ---- rows of at most ROW_WALK_LONG_ROW slots: one lane group per (row, head), serially ------------------------
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t u = tile * A.UPB + ul;
     if (u >= units) continue;
     const int64_t r = u / A.Hd;
     const int h = (int)(u - r * A.Hd);
     const int s = A.rowptr[r], t = walk ? A.rowptr[r + 1] : s;
-    if (t - s > EA_LONG_ROW) { any_long = 1; continue; }
+    if (t - s > ROW_WALK_LONG_ROW) { any_long = 1; continue; }
     UnitCtx U;
     UnitAcc S;
     unit_begin<VEC, MODE>(A, r, h, lg, U);
@@ -275,8 +271,8 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
       const int64_t r = u / A.Hd;
       const int h = (int)(u - r * A.Hd);
       const int s = A.rowptr[r], t = A.rowptr[r + 1];    // workgroup-uniform
-      if (t - s <= EA_LONG_ROW) continue;
-      const int chunks = (t - s + EA_CHUNK - 1) / EA_CHUNK;
+      if (t - s <= ROW_WALK_LONG_ROW) continue;
+      const int chunks = (t - s + ROW_WALK_CHUNK - 1) / ROW_WALK_CHUNK;
       UnitCtx U;
       UnitAcc T;                                         // the merged state (used by lane group 0)
       unit_begin<VEC, MODE>(A, r, h, lg, U);
@@ -284,8 +280,8 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
       for (int c0 = 0; c0 < chunks; c0 += A.UPB) {
         const int c = c0 + ul;
         if (c < chunks) {
-          const int cs = s + c * EA_CHUNK;
-          const int ct = cs + EA_CHUNK < t ? cs + EA_CHUNK : t;
+          const int cs = s + c * ROW_WALK_CHUNK;
+          const int ct = cs + ROW_WALK_CHUNK < t ? cs + ROW_WALK_CHUNK : t;
           UnitAcc S;
           acc_clear(S);
           walk_slots<VEC, MODE>(A, U, h, lg, cs, ct, S);
@@ -340,23 +336,17 @@ int launch_walk(EAArgs A, hipStream_t st) {
   for (const void* p : ptrs) vec = vec && aligned16(p);  // (NULL counts as aligned)
   const int VEC = vec ? 4 : 1;
   const int need = (A.C + VEC - 1) / VEC;                // lanes a head asks for
-  int G = 1;
-  while (G < need && G < HSCN_WAVE) G <<= 1;
-  A.G = G;
-  A.UPB = EA_THREADS / G;
-  A.NP = (need + G - 1) / G;                             // <= 2 (VEC = 4), <= 8 (VEC = 1) for C <= 512
-  const int64_t units = A.rows * A.Hd;
-  int64_t nb = (units + A.UPB - 1) / A.UPB;
-  if (nb > 16384) nb = 16384;
-  if (VEC == 4) k_edge_attn<4, MODE><<<(unsigned)nb, EA_THREADS, 0, st>>>(A);
-  else k_edge_attn<1, MODE><<<(unsigned)nb, EA_THREADS, 0, st>>>(A);
+  A.G = pow2_lanes(need, true);
+  A.UPB = EA_THREADS / A.G;
+  A.NP = (need + A.G - 1) / A.G;                         // <= 2 (VEC = 4), <= 8 (VEC = 1) for C <= 512
+  const unsigned nb = capped_grid(A.rows * A.Hd, A.UPB, 16384);
+  dispatch_vec(VEC, [&](auto v) { k_edge_attn<decltype(v)::value, MODE><<<nb, EA_THREADS, 0, st>>>(A); });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
 int check_common(int64_t Nd, int64_t Ns, int64_t E, int heads, int head_dim) {
-  if (Nd < 0 || Ns < 0 || E < 0 || heads < 1 || head_dim < 1) return HSCN_E_BADARG;
-  if (Nd > INT32_MAX || Ns > INT32_MAX || E > INT32_MAX) return HSCN_E_BADARG;   // CSR indices are int32
+  if (!check_csr_sizes({Nd, Ns, E}) || heads < 1 || head_dim < 1) return HSCN_E_BADARG;
   if (!ea_supported(heads, head_dim)) return HSCN_E_UNSUPPORTED;
   return 0;
 }
@@ -372,8 +362,8 @@ void set_shape(EAArgs& A, int64_t rows, int64_t cols, int64_t E, int heads, int 
 extern "C" {
 
 int hscn_edge_attn_supported(int heads, int head_dim) { return ea_supported(heads, head_dim) ? 1 : 0; }
-int hscn_edge_attn_long_row(void) { return EA_LONG_ROW; }
-int hscn_edge_attn_chunk(void) { return EA_CHUNK; }
+int hscn_edge_attn_long_row(void) { return ROW_WALK_LONG_ROW; }
+int hscn_edge_attn_chunk(void) { return ROW_WALK_CHUNK; }
 
 int hscn_edge_attn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* q, const float* k,
                        const float* v, const float* e, float* out, float* lse, int64_t Nd, int64_t Ns, int64_t E,

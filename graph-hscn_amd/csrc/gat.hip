@@ -7,29 +7,12 @@
 // 64/LPR edge slots x LPR feature lanes for the weighted sum, slot partials are
 // folded with __shfl_xor.  HBM traffic: every gathered h_src row once, alpha
 // written once for the backward.
-#include "hscn_common.h"
+#include "row_walk.h"
 
 namespace {
 
 constexpr int GAT_THREADS = 256;
 constexpr int GAT_WAVES = GAT_THREADS / 64;
-
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
-
-template <int VEC>
-__device__ __forceinline__ void ld(const float* p, float (&v)[VEC]) {
-  if (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void st(float* p, const float (&v)[VEC]) {
-  if (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
 
 // LPRp: power of two >= ceil(width/VEC), <= 64
 template <int VEC>
@@ -48,22 +31,22 @@ k_gat_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, c
     const int s = rowptr[v], t = rowptr[v + 1];
     const float ad = a_dst[v];
     float m = -INFINITY;
-    for (int p = s + lane; p < t; p += 64) m = fmaxf(m, leaky(a_src[col[p]] + ad, slope));
+    for (int p = s + lane; p < t; p += 64) m = fmaxf(m, rw_leaky(a_src[col[p]] + ad, slope));
     m = wave_max(m);
     float sum = 0.f;
-    for (int p = s + lane; p < t; p += 64) sum += expf(leaky(a_src[col[p]] + ad, slope) - m);
+    for (int p = s + lane; p < t; p += 64) sum += expf(rw_leaky(a_src[col[p]] + ad, slope) - m);
     sum = wave_sum(sum);
     const float denom = sum + 1e-16f;
-    for (int p = s + lane; p < t; p += 64) alpha[p] = expf(leaky(a_src[col[p]] + ad, slope) - m) / denom;
+    for (int p = s + lane; p < t; p += 64) alpha[p] = expf(rw_leaky(a_src[col[p]] + ad, slope) - m) / denom;
     float acc[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
     for (int p = s + slot; p < t; p += S) {
       const int j = col[p];
-      const float a = expf(leaky(a_src[j] + ad, slope) - m) / denom;
+      const float a = expf(rw_leaky(a_src[j] + ad, slope) - m) / denom;
       if (flive) {
         float hv[VEC];
-        ld<VEC>(h_src + (size_t)j * width + f, hv);
+        rw_load<VEC>(h_src + (size_t)j * width + f, hv);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = fmaf(a, hv[k], acc[k]);
       }
@@ -76,19 +59,19 @@ k_gat_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, c
       float o[VEC];
       if (bias) {
         float b[VEC];
-        ld<VEC>(bias + f, b);
+        rw_load<VEC>(bias + f, b);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] += b[k];
       }
       if (accumulate) {
         float pv[VEC];
-        ld<VEC>(out + (size_t)v * width + f, pv);
+        rw_load<VEC>(out + (size_t)v * width + f, pv);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] += pv[k];
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = apply_act(acc[k], act);
-      st<VEC>(out + (size_t)v * width + f, o);
+      rw_store<VEC>(out + (size_t)v * width + f, o);
     }
   }
 }
@@ -113,7 +96,7 @@ k_gat_bwd_dst(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ co
     float gv[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) gv[k] = 0.f;
-    if (flive) ld<VEC>(g + (size_t)v * width + f, gv);
+    if (flive) rw_load<VEC>(g + (size_t)v * width + f, gv);
     float tsum = 0.f;
     // pass 1: dot_p = g[v,:] . h_src[col[p],:], parked in g_pre[p] by the slot leader
     for (int p0 = s; p0 < t; p0 += S) {
@@ -121,7 +104,7 @@ k_gat_bwd_dst(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ co
       float d = 0.f;
       if (p < t && flive) {
         float hv[VEC];
-        ld<VEC>(h_src + (size_t)col[p] * width + f, hv);
+        rw_load<VEC>(h_src + (size_t)col[p] * width + f, hv);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) d = fmaf(gv[k], hv[k], d);
       }
@@ -172,23 +155,17 @@ k_gat_bwd_src(const int32_t* __restrict__ rowptr_t, const int32_t* __restrict__ 
       gas = add_rn(gas, g_pre[p]);
       const float a = alpha[p];
       float gv[VEC];
-      ld<VEC>(g + (size_t)v * width + f, gv);
+      rw_load<VEC>(g + (size_t)v * width + f, gv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = add_rn(acc[k], mul_rn(a, gv[k]));
     }
     float at[VEC];
-    ld<VEC>(att_src + f, at);
+    rw_load<VEC>(att_src + f, at);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = fmaf(gas, at[k], acc[k]);
-    st<VEC>(g_h_src + (size_t)j * width + f, acc);
+    rw_store<VEC>(g_h_src + (size_t)j * width + f, acc);
     if (fl == 0) g_a_src[j] = gas;
   }
-}
-
-inline int pow2ceil(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 }  // namespace
@@ -202,17 +179,14 @@ int hscn_gat_segment_fwd(const int32_t* rowptr, const int32_t* col, const float*
   if (num_dst == 0) return 0;
   if (!rowptr || !col || !a_src || !a_dst || !h_src || !alpha || !out) return HSCN_E_BADARG;
   const int VEC = (width % 4 == 0) ? 4 : 1;
-  const int LPRp = pow2ceil((width + VEC - 1) / VEC);
-  if (LPRp > 64) return HSCN_E_UNSUPPORTED;
-  int64_t nb = (num_dst + GAT_WAVES - 1) / GAT_WAVES;
-  if (nb > 8192) nb = 8192;
+  const int LPRp = pow2_lanes((width + VEC - 1) / VEC, false);
+  if (LPRp == 0) return HSCN_E_UNSUPPORTED;
+  const unsigned nb = capped_grid(num_dst, GAT_WAVES, 8192);
   hipStream_t stt = hscn_stream(stream_);
-  if (VEC == 4)
-    k_gat_fwd<4><<<(unsigned)nb, GAT_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h_src, bias, alpha, out,
-                                                        num_dst, width, slope, accumulate, act, LPRp);
-  else
-    k_gat_fwd<1><<<(unsigned)nb, GAT_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h_src, bias, alpha, out,
-                                                        num_dst, width, slope, accumulate, act, LPRp);
+  dispatch_vec(VEC, [&](auto v) {
+    k_gat_fwd<decltype(v)::value><<<nb, GAT_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h_src, bias, alpha, out,
+                                                              num_dst, width, slope, accumulate, act, LPRp);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -224,17 +198,14 @@ int hscn_gat_segment_bwd_dst(const int32_t* rowptr, const int32_t* col, const fl
   if (num_dst == 0) return 0;
   if (!rowptr || !col || !a_src || !a_dst || !h_src || !alpha || !g || !g_pre || !g_a_dst) return HSCN_E_BADARG;
   const int VEC = (width % 4 == 0) ? 4 : 1;
-  const int LPRp = pow2ceil((width + VEC - 1) / VEC);
-  if (LPRp > 64) return HSCN_E_UNSUPPORTED;
-  int64_t nb = (num_dst + GAT_WAVES - 1) / GAT_WAVES;
-  if (nb > 8192) nb = 8192;
+  const int LPRp = pow2_lanes((width + VEC - 1) / VEC, false);
+  if (LPRp == 0) return HSCN_E_UNSUPPORTED;
+  const unsigned nb = capped_grid(num_dst, GAT_WAVES, 8192);
   hipStream_t stt = hscn_stream(stream_);
-  if (VEC == 4)
-    k_gat_bwd_dst<4><<<(unsigned)nb, GAT_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h_src, alpha, g, g_pre,
-                                                            g_a_dst, num_dst, width, slope, LPRp);
-  else
-    k_gat_bwd_dst<1><<<(unsigned)nb, GAT_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h_src, alpha, g, g_pre,
-                                                            g_a_dst, num_dst, width, slope, LPRp);
+  dispatch_vec(VEC, [&](auto v) {
+    k_gat_bwd_dst<decltype(v)::value><<<nb, GAT_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h_src, alpha, g, g_pre,
+                                                                  g_a_dst, num_dst, width, slope, LPRp);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -250,15 +221,12 @@ int hscn_gat_segment_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, cons
   const int LPR = width / VEC;
   if (LPR > GAT_THREADS) return HSCN_E_UNSUPPORTED;
   const int RPB = GAT_THREADS / LPR;
-  int64_t nb = (num_src + RPB - 1) / RPB;
-  if (nb > 8192) nb = 8192;
+  const unsigned nb = capped_grid(num_src, RPB, 8192);
   hipStream_t stt = hscn_stream(stream_);
-  if (VEC == 4)
-    k_gat_bwd_src<4><<<(unsigned)nb, GAT_THREADS, 0, stt>>>(rowptr_t, col_t, pos_t, alpha, g_pre, g, att_src,
-                                                            g_a_src, g_h_src, num_src, width, LPR, RPB);
-  else
-    k_gat_bwd_src<1><<<(unsigned)nb, GAT_THREADS, 0, stt>>>(rowptr_t, col_t, pos_t, alpha, g_pre, g, att_src,
-                                                            g_a_src, g_h_src, num_src, width, LPR, RPB);
+  dispatch_vec(VEC, [&](auto v) {
+    k_gat_bwd_src<decltype(v)::value><<<nb, GAT_THREADS, 0, stt>>>(rowptr_t, col_t, pos_t, alpha, g_pre, g, att_src,
+                                                                  g_a_src, g_h_src, num_src, width, LPR, RPB);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -21,43 +21,11 @@
 // are correct for rows of any degree (every loop is bounded by rowptr), but a group walks its row serially, so
 // one hub row holds its wave for deg gathers in a row; a relation whose largest in-degree exceeds
 // GAT_NARROW_MAX_DEGREE goes to the wave-per-row kernels of gat.hip over the explicit-loop relation instead.
-#include "hscn_common.h"
+#include "row_walk.h"
 
 namespace {
 
 constexpr int GL_THREADS = 256;
-
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
-
-template <int VEC>
-__device__ __forceinline__ void ld(const float* p, float (&v)[VEC]) {
-  if (VEC == 4) {
-    float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void st(float* p, const float (&v)[VEC]) {
-  if (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
-// sum over the G lanes of a group (G a power of two, groups aligned to G inside the wave); every lane of the
-// group is active whenever one is, so each butterfly partner is live
-__device__ __forceinline__ float group_sum(float v, int G) {
-  for (int off = G >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-template <int VEC>
-__device__ __forceinline__ float dot(const float (&a)[VEC], const float (&b)[VEC]) {
-  float d = 0.f;
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) d = fmaf(a[k], b[k], d);
-  return d;
-}
 
 // G lanes per row, RPB = GL_THREADS / G rows per block
 template <int VEC>
@@ -73,11 +41,11 @@ k_gat_loop_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ c
   for (int64_t v = (int64_t)blockIdx.x * RPB + rl; v < n; v += (int64_t)gridDim.x * RPB) {
     const int s = rowptr[v], t = rowptr[v + 1];
     const float ad = a_dst[v];
-    const float zself = leaky(a_src[v] + ad, slope);
+    const float zself = rw_leaky(a_src[v] + ad, slope);
     float m = zself;
     for (int p = s; p < t; ++p) {
       const int j = col[p];
-      if (j != (int)v) m = fmaxf(m, leaky(a_src[j] + ad, slope));
+      if (j != (int)v) m = fmaxf(m, rw_leaky(a_src[j] + ad, slope));
     }
     float sum = 0.f;
     float acc[VEC];
@@ -86,11 +54,11 @@ k_gat_loop_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ c
     for (int p = s; p < t; ++p) {
       const int j = col[p];
       if (j == (int)v) continue;
-      const float e = expf(leaky(a_src[j] + ad, slope) - m);
+      const float e = expf(rw_leaky(a_src[j] + ad, slope) - m);
       sum += e;
       if (flive) {
         float hv[VEC];
-        ld<VEC>(h + (size_t)j * width + f, hv);
+        rw_load<VEC>(h + (size_t)j * width + f, hv);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = fmaf(e, hv[k], acc[k]);
       }
@@ -104,18 +72,18 @@ k_gat_loop_fwd(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ c
     }
     if (flive) {
       float hv[VEC], o[VEC];
-      ld<VEC>(h + (size_t)v * width + f, hv);
+      rw_load<VEC>(h + (size_t)v * width + f, hv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = fmaf(es, hv[k], acc[k]) / denom;
       if (bias) {
         float b[VEC];
-        ld<VEC>(bias + f, b);
+        rw_load<VEC>(bias + f, b);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] += b[k];
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) o[k] = apply_act(acc[k], act);
-      st<VEC>(out + (size_t)v * width + f, o);
+      rw_store<VEC>(out + (size_t)v * width + f, o);
     }
   }
 }
@@ -140,31 +108,31 @@ k_gat_loop_bwd_dst(const int32_t* __restrict__ rowptr, const int32_t* __restrict
     float gv[VEC], hv[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) gv[k] = 0.f, hv[k] = 0.f;
-    if (flive) ld<VEC>(g + (size_t)v * width + f, gv);
+    if (flive) rw_load<VEC>(g + (size_t)v * width + f, gv);
     // pass 1: the alpha-weighted mean of the dots
     float ts = 0.f;
     for (int p = s; p < t; ++p) {
       const int j = col[p];
       if (j == (int)v) continue;
-      if (flive) ld<VEC>(h + (size_t)j * width + f, hv);
-      const float d = group_sum(dot<VEC>(gv, hv), G);
-      const float a = expf(leaky(a_src[j] + ad, slope) - m) / denom;
+      if (flive) rw_load<VEC>(h + (size_t)j * width + f, hv);
+      const float d = group_sum(rw_dot<VEC>(gv, hv), G);
+      const float a = expf(rw_leaky(a_src[j] + ad, slope) - m) / denom;
       ts = fmaf(a, d, ts);
     }
     const float pre_self = a_src[v] + ad;
-    const float a_self = expf(leaky(pre_self, slope) - m) / denom;
-    if (flive) ld<VEC>(h + (size_t)v * width + f, hv);
-    const float d_self = group_sum(dot<VEC>(gv, hv), G);
+    const float a_self = expf(rw_leaky(pre_self, slope) - m) / denom;
+    if (flive) rw_load<VEC>(h + (size_t)v * width + f, hv);
+    const float d_self = group_sum(rw_dot<VEC>(gv, hv), G);
     ts = fmaf(a_self, d_self, ts);
     // pass 2: softmax and leaky-ReLU derivatives per entry (the rows are L1/L2-resident from pass 1)
     float gad = 0.f;
     for (int p = s; p < t; ++p) {
       const int j = col[p];
       if (j == (int)v) continue;
-      if (flive) ld<VEC>(h + (size_t)j * width + f, hv);
-      const float d = group_sum(dot<VEC>(gv, hv), G);
+      if (flive) rw_load<VEC>(h + (size_t)j * width + f, hv);
+      const float d = group_sum(rw_dot<VEC>(gv, hv), G);
       const float pre = a_src[j] + ad;
-      const float gl = expf(leaky(pre, slope) - m) / denom * (d - ts);
+      const float gl = expf(rw_leaky(pre, slope) - m) / denom * (d - ts);
       gad += pre > 0.f ? gl : gl * slope;
     }
     const float gls = a_self * (d_self - ts);
@@ -196,15 +164,15 @@ k_gat_loop_bwd_src(const int32_t* __restrict__ rowptr_t, const int32_t* __restri
     float hv[VEC], gv[VEC], acc[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) hv[k] = 0.f, gv[k] = 0.f, acc[k] = 0.f;
-    if (flive) ld<VEC>(h + (size_t)j * width + f, hv);
+    if (flive) rw_load<VEC>(h + (size_t)j * width + f, hv);
     float gas = 0.f;
     for (int q = s; q <= t; ++q) {           // q == t: the loop j -> j, last
       const int v = q < t ? col_t[q] : (int)j;
       if (q < t && v == (int)j) continue;
-      if (flive) ld<VEC>(g + (size_t)v * width + f, gv);
-      const float d = group_sum(dot<VEC>(gv, hv), G);
+      if (flive) rw_load<VEC>(g + (size_t)v * width + f, gv);
+      const float d = group_sum(rw_dot<VEC>(gv, hv), G);
       const float pre = as + a_dst[v];
-      const float a = expf(leaky(pre, slope) - stat[2 * (size_t)v]) / stat[2 * (size_t)v + 1];
+      const float a = expf(rw_leaky(pre, slope) - stat[2 * (size_t)v]) / stat[2 * (size_t)v + 1];
       const float gl = a * (d - tsum[v]);
       gas += pre > 0.f ? gl : gl * slope;
 #pragma unroll
@@ -212,31 +180,17 @@ k_gat_loop_bwd_src(const int32_t* __restrict__ rowptr_t, const int32_t* __restri
     }
     if (flive) {
       float at[VEC];
-      ld<VEC>(att_src + f, at);
+      rw_load<VEC>(att_src + f, at);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = fmaf(gas, at[k], acc[k]);
       const float gad = g_a[2 * j + 1];
-      ld<VEC>(att_dst + f, at);
+      rw_load<VEC>(att_dst + f, at);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = fmaf(gad, at[k], acc[k]);
-      st<VEC>(g_h + (size_t)j * width + f, acc);
+      rw_store<VEC>(g_h + (size_t)j * width + f, acc);
     }
     if (fl == 0) g_a[2 * j] = gas;
   }
-}
-
-// lanes per row: the power of two >= ceil(width / VEC); 0 when it would not fit a wave
-inline int group_lanes(int width, int VEC) {
-  const int need = (width + VEC - 1) / VEC;
-  int G = 1;
-  while (G < need) G <<= 1;
-  return G <= 64 ? G : 0;
-}
-
-inline unsigned grid_for(int64_t n, int G) {
-  const int RPB = GL_THREADS / G;
-  int64_t nb = (n + RPB - 1) / RPB;
-  return (unsigned)(nb > 8192 ? 8192 : nb);
 }
 
 }  // namespace
@@ -250,15 +204,14 @@ int hscn_gat_loop_fwd(const int32_t* rowptr, const int32_t* col, const float* a_
   if (num_nodes == 0) return 0;
   if (!rowptr || !col || !a_src || !a_dst || !h || !stat || !out) return HSCN_E_BADARG;
   const int VEC = (width % 4 == 0) ? 4 : 1;
-  const int G = group_lanes(width, VEC);
+  const int G = pow2_lanes((width + VEC - 1) / VEC, false);      // lanes per row; wider than a wave is refused
   if (G == 0) return HSCN_E_UNSUPPORTED;
+  const unsigned nb = capped_grid(num_nodes, GL_THREADS / G, 8192);
   hipStream_t stt = hscn_stream(stream_);
-  if (VEC == 4)
-    k_gat_loop_fwd<4><<<grid_for(num_nodes, G), GL_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h, bias, stat, out,
-                                                                     num_nodes, width, slope, act, G);
-  else
-    k_gat_loop_fwd<1><<<grid_for(num_nodes, G), GL_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h, bias, stat, out,
-                                                                     num_nodes, width, slope, act, G);
+  dispatch_vec(VEC, [&](auto v) {
+    k_gat_loop_fwd<decltype(v)::value><<<nb, GL_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h, bias, stat, out,
+                                                                  num_nodes, width, slope, act, G);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -270,15 +223,14 @@ int hscn_gat_loop_bwd_dst(const int32_t* rowptr, const int32_t* col, const float
   if (num_nodes == 0) return 0;
   if (!rowptr || !col || !a_src || !a_dst || !h || !stat || !g || !tsum || !g_a) return HSCN_E_BADARG;
   const int VEC = (width % 4 == 0) ? 4 : 1;
-  const int G = group_lanes(width, VEC);
+  const int G = pow2_lanes((width + VEC - 1) / VEC, false);      // lanes per row; wider than a wave is refused
   if (G == 0) return HSCN_E_UNSUPPORTED;
+  const unsigned nb = capped_grid(num_nodes, GL_THREADS / G, 8192);
   hipStream_t stt = hscn_stream(stream_);
-  if (VEC == 4)
-    k_gat_loop_bwd_dst<4><<<grid_for(num_nodes, G), GL_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h, stat, g, tsum,
-                                                                         g_a, num_nodes, width, slope, G);
-  else
-    k_gat_loop_bwd_dst<1><<<grid_for(num_nodes, G), GL_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h, stat, g, tsum,
-                                                                         g_a, num_nodes, width, slope, G);
+  dispatch_vec(VEC, [&](auto v) {
+    k_gat_loop_bwd_dst<decltype(v)::value><<<nb, GL_THREADS, 0, stt>>>(rowptr, col, a_src, a_dst, h, stat, g, tsum, g_a,
+                                                                      num_nodes, width, slope, G);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -292,17 +244,15 @@ int hscn_gat_loop_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const f
   if (!rowptr_t || !col_t || !a_src || !a_dst || !h || !stat || !tsum || !g || !att_src || !att_dst || !g_a || !g_h)
     return HSCN_E_BADARG;
   const int VEC = (width % 4 == 0) ? 4 : 1;
-  const int G = group_lanes(width, VEC);
+  const int G = pow2_lanes((width + VEC - 1) / VEC, false);      // lanes per row; wider than a wave is refused
   if (G == 0) return HSCN_E_UNSUPPORTED;
+  const unsigned nb = capped_grid(num_nodes, GL_THREADS / G, 8192);
   hipStream_t stt = hscn_stream(stream_);
-  if (VEC == 4)
-    k_gat_loop_bwd_src<4><<<grid_for(num_nodes, G), GL_THREADS, 0, stt>>>(rowptr_t, col_t, a_src, a_dst, h, stat, tsum,
-                                                                         g, att_src, att_dst, g_a, g_h, num_nodes,
-                                                                         width, slope, G);
-  else
-    k_gat_loop_bwd_src<1><<<grid_for(num_nodes, G), GL_THREADS, 0, stt>>>(rowptr_t, col_t, a_src, a_dst, h, stat, tsum,
-                                                                         g, att_src, att_dst, g_a, g_h, num_nodes,
-                                                                         width, slope, G);
+  dispatch_vec(VEC, [&](auto v) {
+    k_gat_loop_bwd_src<decltype(v)::value><<<nb, GL_THREADS, 0, stt>>>(rowptr_t, col_t, a_src, a_dst, h, stat, tsum, g,
+                                                                      att_src, att_dst, g_a, g_h, num_nodes, width,
+                                                                      slope, G);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

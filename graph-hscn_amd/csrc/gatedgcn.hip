@@ -22,19 +22,16 @@
 // s_k is recomputed from the saved e^ (an output, kept anyway) by the same device function in all three.  No float
 // atomics: every output row has one owner.
 //
-// Long rows: rows of more than GATED_LONG_ROW slots are left out of the serial walk and taken by the WHOLE workgroup
-// afterwards in chunks of GATED_CHUNK slots, the chunk partials added in chunk order (as csrc/gine.hip): the result
-// depends on the row alone, so it is bitwise reproducible and independent of the row's place in a batch.
+// Long rows: the two-phase scheme described in csrc/row_walk.h; both running sums of a chunk are parked, and added in
+// chunk order with a separately rounded add.
 //
 // Edges that hscn_csr_build left out (an endpoint outside [0, N): the flag word is non-zero) own no slot; when the flag
 // word is set, MODE 0 / MODE 1 sweep the edge list once and store a zero row of e^ / ge for each of them.
-#include "hscn_common.h"
+#include "row_walk.h"
 
 namespace {
 
 constexpr int GG_THREADS = 256;
-constexpr int GATED_LONG_ROW = 256;   // rows with MORE slots than this are split (hscn_gatedgcn_long_row)
-constexpr int GATED_CHUNK = 64;       // slots per chunk of a split row (hscn_gatedgcn_chunk)
 constexpr int GATED_MAX_H = 512;
 constexpr float GATED_EPS = 1e-6f;
 
@@ -188,14 +185,14 @@ __global__ void __launch_bounds__(GG_THREADS) k_gated_walk(const GatedArgs A) {
   const int span = A.LPR * VEC;                         // columns of one pass
   const int64_t tiles = (A.N + A.RPB - 1) / A.RPB;
   int any_long = 0;
-  // ---- rows of at most GATED_LONG_ROW slots: one lane group each, serially --------------------------------------
+  // ---- rows of at most ROW_WALK_LONG_ROW slots: one lane group each, serially --------------------------------------
   if (member) {
     for (int f = lg * VEC; f < A.H; f += span) {        // (one pass up to 64 * VEC columns)
       for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t r = tile * A.RPB + rl;
         if (r >= A.N) continue;
         const int s = A.rowptr[r], t = walk ? A.rowptr[r + 1] : s;
-        if (t - s > GATED_LONG_ROW) { any_long = 1; continue; }
+        if (t - s > ROW_WALK_LONG_ROW) { any_long = 1; continue; }
         RowCtx<VEC> R;
         row_begin<VEC, MODE>(A, r, f, R);
         float acc0[VEC], acc1[VEC];
@@ -215,8 +212,8 @@ __global__ void __launch_bounds__(GG_THREADS) k_gated_walk(const GatedArgs A) {
       const int64_t r = tile * A.RPB + i;
       if (r >= A.N) break;
       const int s = A.rowptr[r], t = A.rowptr[r + 1];   // block-uniform
-      if (t - s <= GATED_LONG_ROW) continue;
-      const int chunks = (t - s + GATED_CHUNK - 1) / GATED_CHUNK;
+      if (t - s <= ROW_WALK_LONG_ROW) continue;
+      const int chunks = (t - s + ROW_WALK_CHUNK - 1) / ROW_WALK_CHUNK;
       for (int f0 = 0; f0 < A.H; f0 += span) {
         const int f = f0 + lg * VEC;
         const bool live = member && f < A.H;
@@ -228,8 +225,8 @@ __global__ void __launch_bounds__(GG_THREADS) k_gated_walk(const GatedArgs A) {
         for (int c0 = 0; c0 < chunks; c0 += A.RPB) {
           const int c = c0 + rl;
           if (live && c < chunks) {
-            const int cs = s + c * GATED_CHUNK;
-            const int ct = cs + GATED_CHUNK < t ? cs + GATED_CHUNK : t;
+            const int cs = s + c * ROW_WALK_CHUNK;
+            const int ct = cs + ROW_WALK_CHUNK < t ? cs + ROW_WALK_CHUNK : t;
             float acc0[VEC], acc1[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc0[v] = acc1[v] = 0.f;
@@ -262,21 +259,16 @@ bool gated_supported(int H) { return H >= 1 && H <= GATED_MAX_H; }
 
 template <int MODE>
 int launch_walk(GatedArgs A, hipStream_t st) {
-  const int VEC = (A.H % 4 == 0) ? 4 : 1;
-  A.LPR = (A.H + VEC - 1) / VEC;
-  if (A.LPR > HSCN_WAVE) A.LPR = HSCN_WAVE;
-  A.RPB = GG_THREADS / A.LPR;
-  int64_t nb = (A.N + A.RPB - 1) / A.RPB;
-  if (nb > 8192) nb = 8192;
-  if (VEC == 4) k_gated_walk<4, MODE><<<(unsigned)nb, GG_THREADS, 0, st>>>(A);
-  else k_gated_walk<1, MODE><<<(unsigned)nb, GG_THREADS, 0, st>>>(A);
+  int VEC;
+  lane_groups(A.H, GG_THREADS, VEC, A.LPR, A.RPB);
+  const unsigned nb = capped_grid(A.N, A.RPB, 8192);
+  dispatch_vec(VEC, [&](auto v) { k_gated_walk<decltype(v)::value, MODE><<<nb, GG_THREADS, 0, st>>>(A); });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
 int check_common(int64_t N, int64_t E, int H) {
-  if (N < 0 || E < 0 || H < 1) return HSCN_E_BADARG;
-  if (N > INT32_MAX || E > INT32_MAX) return HSCN_E_BADARG;      // CSR indices are int32
+  if (!check_csr_sizes({N, E}) || H < 1) return HSCN_E_BADARG;
   if (!gated_supported(H)) return HSCN_E_UNSUPPORTED;
   return 0;
 }
@@ -286,8 +278,8 @@ int check_common(int64_t N, int64_t E, int H) {
 extern "C" {
 
 int hscn_gatedgcn_supported(int H) { return gated_supported(H) ? 1 : 0; }
-int hscn_gatedgcn_long_row(void) { return GATED_LONG_ROW; }
-int hscn_gatedgcn_chunk(void) { return GATED_CHUNK; }
+int hscn_gatedgcn_long_row(void) { return ROW_WALK_LONG_ROW; }
+int hscn_gatedgcn_chunk(void) { return ROW_WALK_CHUNK; }
 
 int hscn_gatedgcn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int64_t* edge_index,
                       const float* Ax, const float* Bx, const float* Dx, const float* Ex, const float* Ce, float* h,

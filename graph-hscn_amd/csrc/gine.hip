@@ -14,21 +14,16 @@
 //   MODE 0, target-keyed CSR:  out_i = (1+eps) x_i  + sum_slots relu(x[col] + t_eid)               (forward, z)
 //   MODE 1, source-keyed CSR:  out_j = (1+eps) gz_j + sum_slots [x_j + t_eid > 0] gz[col]          (backward, gx)
 //
-// Long rows: a lane group walks its row serially, so a hub of thousands of edges would hold its wave while every
-// other row is done.  Rows of more than GINE_LONG_ROW slots are left out of the serial walk and taken by the WHOLE
-// workgroup afterwards: the row is cut into chunks of GINE_CHUNK slots, the block's lane groups sum one chunk each
-// (slot order inside the chunk), and the chunk partials are added in chunk order.  The result depends on the row alone
-// (not on the grid or on which rows share a block), so it is bitwise reproducible.
+// Long rows: the two-phase scheme described in csrc/row_walk.h; the chunk partials are added in chunk order with a
+// separately rounded add.
 //
 // The parameter gradients go through one [E, F] buffer written once with plain stores (k_gine_msg_grad, edge-parallel,
 // gm_k = gate_k * gz[dst_k]) and the existing two-stage ordered hscn_linear_bwd_w(gm, edge_attr): no float atomics.
-#include "hscn_common.h"
+#include "row_walk.h"
 
 namespace {
 
 constexpr int GI_THREADS = 256;
-constexpr int GINE_LONG_ROW = 256;   // rows with MORE slots than this are split (hscn_gine_long_row)
-constexpr int GINE_CHUNK = 64;       // slots per chunk of a split row (hscn_gine_chunk)
 constexpr int GINE_MAX_F = 512;
 constexpr int GINE_MAX_DE = 64;
 
@@ -145,7 +140,7 @@ __global__ void __launch_bounds__(GI_THREADS) k_gine_walk(const GineArgs A) {
   const int span = A.LPR * VEC;                         // columns of one pass
   const int64_t tiles = (A.N + A.RPB - 1) / A.RPB;
   int any_long = 0;
-  // ---- rows of at most GINE_LONG_ROW slots: one lane group each, serially --------------------------------------
+  // ---- rows of at most ROW_WALK_LONG_ROW slots: one lane group each, serially --------------------------------------
   if (member) {
     for (int f = lg * VEC; f < A.F; f += span) {        // (one pass up to 64 * VEC columns)
       EdgeLin<VEC, DREG> L;
@@ -154,7 +149,7 @@ __global__ void __launch_bounds__(GI_THREADS) k_gine_walk(const GineArgs A) {
         const int64_t r = tile * A.RPB + rl;
         if (r >= A.N) continue;
         const int s = A.rowptr[r], t = A.rowptr[r + 1];
-        if (t - s > GINE_LONG_ROW) { any_long = 1; continue; }
+        if (t - s > ROW_WALK_LONG_ROW) { any_long = 1; continue; }
         typename V::T xr = V::zero();
         if (MODE == 1) xr = V::load(A.x + (size_t)r * A.F + f);
         finish_row<VEC>(A, MODE, r, f, walk_slots<VEC, DREG, MODE>(A, L, s, t, f, xr, V::zero()));
@@ -168,8 +163,8 @@ __global__ void __launch_bounds__(GI_THREADS) k_gine_walk(const GineArgs A) {
       const int64_t r = tile * A.RPB + i;
       if (r >= A.N) break;
       const int s = A.rowptr[r], t = A.rowptr[r + 1];   // block-uniform
-      if (t - s <= GINE_LONG_ROW) continue;
-      const int chunks = (t - s + GINE_CHUNK - 1) / GINE_CHUNK;
+      if (t - s <= ROW_WALK_LONG_ROW) continue;
+      const int chunks = (t - s + ROW_WALK_CHUNK - 1) / ROW_WALK_CHUNK;
       for (int f0 = 0; f0 < A.F; f0 += span) {
         const int f = f0 + lg * VEC;
         const bool live = member && f < A.F;
@@ -183,8 +178,8 @@ __global__ void __launch_bounds__(GI_THREADS) k_gine_walk(const GineArgs A) {
         for (int c0 = 0; c0 < chunks; c0 += A.RPB) {
           const int c = c0 + rl;
           if (live && c < chunks) {
-            const int cs = s + c * GINE_CHUNK;
-            const int ct = cs + GINE_CHUNK < t ? cs + GINE_CHUNK : t;
+            const int cs = s + c * ROW_WALK_CHUNK;
+            const int ct = cs + ROW_WALK_CHUNK < t ? cs + ROW_WALK_CHUNK : t;
             V::store(part + (size_t)threadIdx.x * VEC, walk_slots<VEC, DREG, MODE>(A, L, cs, ct, f, xr, V::zero()));
           }
           __syncthreads();
@@ -243,38 +238,30 @@ k_gine_msg_grad(const int64_t* __restrict__ ei, const float* __restrict__ x, con
 
 bool gine_supported(int F, int De) { return F >= 1 && F <= GINE_MAX_F && De >= 1 && De <= GINE_MAX_DE; }
 
-void lane_groups(int F, int& VEC, int& LPR, int& RPB) {
-  VEC = (F % 4 == 0) ? 4 : 1;
-  LPR = (F + VEC - 1) / VEC;
-  if (LPR > HSCN_WAVE) LPR = HSCN_WAVE;
-  RPB = GI_THREADS / LPR;
+// f(VEC, DREG) as integral constants: 16-byte lanes where F allows, lin's rows in 4 or 8 registers where De allows
+template <class Fn>
+void dispatch_vec_dreg(int VEC, int De, Fn&& f) {
+  dispatch_vec(VEC, [&](auto v) {
+    if (De <= 4) f(v, std::integral_constant<int, 4>{});
+    else if (De <= 8) f(v, std::integral_constant<int, 8>{});
+    else f(v, std::integral_constant<int, 0>{});
+  });
 }
 
 template <int MODE>
 int launch_walk(GineArgs A, hipStream_t st) {
   int VEC;
-  lane_groups(A.F, VEC, A.LPR, A.RPB);
-  int64_t nb = (A.N + A.RPB - 1) / A.RPB;
-  if (nb > 8192) nb = 8192;
-  const int dreg = A.De <= 4 ? 4 : (A.De <= 8 ? 8 : 0);
-#define HSCN_GINE_WALK(V_, D_) k_gine_walk<V_, D_, MODE><<<(unsigned)nb, GI_THREADS, 0, st>>>(A)
-  if (VEC == 4) {
-    if (dreg == 4) HSCN_GINE_WALK(4, 4);
-    else if (dreg == 8) HSCN_GINE_WALK(4, 8);
-    else HSCN_GINE_WALK(4, 0);
-  } else {
-    if (dreg == 4) HSCN_GINE_WALK(1, 4);
-    else if (dreg == 8) HSCN_GINE_WALK(1, 8);
-    else HSCN_GINE_WALK(1, 0);
-  }
-#undef HSCN_GINE_WALK
+  lane_groups(A.F, GI_THREADS, VEC, A.LPR, A.RPB);
+  const unsigned nb = capped_grid(A.N, A.RPB, 8192);
+  dispatch_vec_dreg(VEC, A.De, [&](auto v, auto d) {
+    k_gine_walk<decltype(v)::value, decltype(d)::value, MODE><<<nb, GI_THREADS, 0, st>>>(A);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
 int check_common(int64_t N, int64_t E, int F, int De) {
-  if (N < 0 || E < 0 || F < 1 || De < 1) return HSCN_E_BADARG;
-  if (N > INT32_MAX || E > INT32_MAX) return HSCN_E_BADARG;      // CSR indices are int32
+  if (!check_csr_sizes({N, E}) || F < 1 || De < 1) return HSCN_E_BADARG;
   if (!gine_supported(F, De)) return HSCN_E_UNSUPPORTED;
   return 0;
 }
@@ -284,8 +271,8 @@ int check_common(int64_t N, int64_t E, int F, int De) {
 extern "C" {
 
 int hscn_gine_supported(int F, int De) { return gine_supported(F, De) ? 1 : 0; }
-int hscn_gine_long_row(void) { return GINE_LONG_ROW; }
-int hscn_gine_chunk(void) { return GINE_CHUNK; }
+int hscn_gine_long_row(void) { return ROW_WALK_LONG_ROW; }
+int hscn_gine_chunk(void) { return ROW_WALK_CHUNK; }
 
 int hscn_gine_aggregate_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* x,
                             const float* edge_attr, const float* W, const float* bias, float eps, float* z, int64_t N,
@@ -316,23 +303,13 @@ int hscn_gine_aggregate_bwd_msg(const int64_t* edge_index, const float* x, const
   if (E == 0) return 0;
   if (!edge_index || !x || !edge_attr || !W || !bias || !gz || !gm || !flag) return HSCN_E_BADARG;
   int VEC, LPR, RPB;
-  lane_groups(F, VEC, LPR, RPB);
-  int64_t nb = (E + RPB - 1) / RPB;
-  if (nb > 8192) nb = 8192;
+  lane_groups(F, GI_THREADS, VEC, LPR, RPB);
+  const unsigned nb = capped_grid(E, RPB, 8192);
   hipStream_t st = hscn_stream(stream_);
-  const int dreg = De <= 4 ? 4 : (De <= 8 ? 8 : 0);
-#define HSCN_GINE_MSG(V_, D_) \
-  k_gine_msg_grad<V_, D_><<<(unsigned)nb, GI_THREADS, 0, st>>>(edge_index, x, edge_attr, W, bias, gz, gm, N, E, F, De, LPR, RPB, flag)
-  if (VEC == 4) {
-    if (dreg == 4) HSCN_GINE_MSG(4, 4);
-    else if (dreg == 8) HSCN_GINE_MSG(4, 8);
-    else HSCN_GINE_MSG(4, 0);
-  } else {
-    if (dreg == 4) HSCN_GINE_MSG(1, 4);
-    else if (dreg == 8) HSCN_GINE_MSG(1, 8);
-    else HSCN_GINE_MSG(1, 0);
-  }
-#undef HSCN_GINE_MSG
+  dispatch_vec_dreg(VEC, De, [&](auto v, auto d) {
+    k_gine_msg_grad<decltype(v)::value, decltype(d)::value><<<nb, GI_THREADS, 0, st>>>(
+        edge_index, x, edge_attr, W, bias, gz, gm, N, E, F, De, LPR, RPB, flag);
+  });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
