@@ -245,6 +245,24 @@ _SIGNATURES = {
                                           P, P, P, P, c_int64, P, P]),
     "hscn_attention_bias_bwd_kv": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int,
                                            c_int, P, P, P]),
+    "hscn_expander_max_nodes": (c_int, []),
+    "hscn_expander_max_degree": (c_int, []),
+    "hscn_expander_build": (c_int, [P, P, c_int64, c_int64, c_int, c_uint64, c_int, P, P, P]),
+    "hscn_exph_attn_supported": (c_int, [c_int, c_int]),
+    "hscn_exph_attn_long_row": (c_int, []),
+    "hscn_exph_attn_chunk": (c_int, []),
+    "hscn_exph_type_long_row": (c_int, []),
+    "hscn_exph_type_chunk": (c_int, []),
+    "hscn_exph_max_types": (c_int, []),
+    "hscn_exph_attn_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_int, P,
+                                   P]),
+    "hscn_exph_attn_bwd_dst": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int,
+                                       c_int, c_int, P, P]),
+    "hscn_exph_attn_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int,
+                                       c_int, c_int, P, P]),
+    "hscn_exph_type_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "hscn_exph_attn_bwd_type": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, P, P,
+                                        c_size_t, P]),
 }
 
 

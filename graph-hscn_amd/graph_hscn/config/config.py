@@ -166,6 +166,14 @@ class GPSConfig:
     # distances of spd_max_dist hops and beyond (and unreachable pairs) sharing the last bucket
     attn_bias: Optional[str] = None
     spd_max_dist: int = 20
+    # "exphormer": sparse attention over the batch's own edges (add_local_edges), a random expander of even degree
+    # expander_degree drawn under expander_seed, and num_virtual_nodes virtual nodes per graph, in place of the dense
+    # per-graph attention; the four further keys are read by "exphormer" only
+    global_model: str = "attention"
+    expander_degree: int = 6
+    num_virtual_nodes: int = 1
+    add_local_edges: bool = True
+    expander_seed: int = 0
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
@@ -173,6 +181,20 @@ class GPSConfig:
         _check_encoders(self.node_encoder, self.edge_encoder, self.local_conv_type)
         if self.attn_bias not in (None, "spd"):
             raise ValueError(f"attn_bias must be 'spd' or None, got {self.attn_bias!r}")
+        if self.global_model not in ("attention", "exphormer"):
+            raise ValueError(f"global_model must be 'attention' or 'exphormer', got {self.global_model!r}")
+        if self.global_model == "exphormer" and self.attn_bias is not None:
+            raise ValueError(f"global_model='exphormer' and attn_bias={self.attn_bias!r} do not go together: the "
+                             "shortest-path bias belongs to the dense attention (attn_bias must be None)")
+        d, nv = self.expander_degree, self.num_virtual_nodes
+        if isinstance(d, bool) or not isinstance(d, int) or d % 2 or not 2 <= d <= 32:
+            raise ValueError(f"expander_degree must be an even integer in [2, 32], got {d!r}")
+        if isinstance(nv, bool) or not isinstance(nv, int) or not 0 <= nv <= 4:
+            raise ValueError(f"num_virtual_nodes must be an integer in [0, 4], got {nv!r}")
+        if not isinstance(self.add_local_edges, bool):
+            raise ValueError(f"add_local_edges must be a bool, got {self.add_local_edges!r}")
+        if isinstance(self.expander_seed, bool) or not isinstance(self.expander_seed, int) or self.expander_seed < 0:
+            raise ValueError(f"expander_seed must be a non-negative integer, got {self.expander_seed!r}")
         if isinstance(self.spd_max_dist, bool) or not isinstance(self.spd_max_dist, int) or \
                 not 1 <= self.spd_max_dist <= 63:
             raise ValueError(f"spd_max_dist must be an integer in [1, 63], got {self.spd_max_dist!r}")

@@ -27,9 +27,30 @@ from ..nn.conv import Linear
 from ..nn.gps import GPSLayer
 from ..nn.head import NodeHead
 from ..nn.pool import global_mean_pool
+from ..structure import ExphormerStructure
 
+EXPHORMER_RESIDENT_REASON = ("Exphormer's sparse attention (model/gps.py GPS, global_model='exphormer'): typed edge "
+                            "attention over the union of local, expander and virtual-node edges has no one-launch, "
+                            "resident or captured form; the model runs on the layered operators")
 RESIDENT_REASON = ("global attention (model/gps.py GPS): per-graph multi-head self-attention has no one-launch, "
                    "resident or captured form; the model runs on the layered operators")
+
+
+def _check_exphormer(expander_degree, num_virtual_nodes) -> None:
+    d, nv = expander_degree, num_virtual_nodes
+    if isinstance(d, bool) or not isinstance(d, int) or d % 2 or not 2 <= d <= Fh.EXPANDER_MAX_DEGREE:
+        raise ValueError(f"expander_degree must be an even integer in [2, {Fh.EXPANDER_MAX_DEGREE}], got {d!r}")
+    if isinstance(nv, bool) or not isinstance(nv, int) or not 0 <= nv <= Fh.EXPH_MAX_VIRTUAL_NODES:
+        raise ValueError(f"num_virtual_nodes must be an integer in [0, {Fh.EXPH_MAX_VIRTUAL_NODES}], got {nv!r}")
+
+
+class _Table(nn.Module):
+    """A learned table ``weight`` [rows, D], drawn normal(0, 1) as an ``nn.Embedding`` is."""
+
+    def __init__(self, rows: int, channels: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(rows, channels))
+        nn.init.normal_(self.weight)
 
 
 class GPS(nn.Module):
@@ -38,8 +59,22 @@ class GPS(nn.Module):
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
                  local_conv: Optional[str] = "gine", activation: Optional[Callable] = None, dropout: float = 0.0,
                  norm: Optional[str] = "layer", task_level: str = "graph", node_encoder: Optional[str] = None,
-                 edge_encoder: Optional[str] = None, attn_bias: Optional[str] = None, spd_max_dist: int = 20) -> None:
-        """``attn_bias="spd"``: Graphormer's spatial encoding -- every layer's attention owns a table
+                 edge_encoder: Optional[str] = None, attn_bias: Optional[str] = None, spd_max_dist: int = 20,
+                 global_model: str = "attention", expander_degree: int = 6, num_virtual_nodes: int = 1,
+                 add_local_edges: bool = True, expander_seed: int = 0) -> None:
+        """``global_model="exphormer"``: every layer's global branch is ``nn.attention.ExphormerAttention`` over the
+        union of the batch's own edges (``add_local_edges``), a random ``expander_degree``-regular expander drawn under
+        ``expander_seed`` and ``num_virtual_nodes`` virtual nodes per graph.  The model then owns
+        ``virt_node_emb.weight`` [nv, D] (the virtual rows every graph starts from) and ``edge_type_emb.weight``
+        [2 + 2 nv, D] (the features of the edges that have none of their own), builds the batch's
+        ``structure.ExphormerStructure`` once (kept on the batch, ``graph_ids = arange(B)``), carries the virtual rows
+        from layer to layer and hands heads and pooling the node rows only.  The local edges' own features reach the
+        attention where the model encodes edge features to width D: the ``edge_encoder`` ("bond") or "gatedgcn"'s
+        edge state as they are, and for the other edge-aware convolutions ("gine", "transformerconv_edge") a
+        ``Linear(-1, D)`` of the attention's own, ``exph_edge_encoder``; without an edge-aware ``local_conv`` the local
+        edges share type 0 of the table.  The four further arguments are read by "exphormer" only.
+
+        ``attn_bias="spd"``: Graphormer's spatial encoding -- every layer's attention owns a table
         ``layers.i.attn.spd_bias.weight`` [spd_max_dist + 1, num_heads] added to its logits by shortest-path bucket; the
         model builds the batch's buckets once per forward (``nn.functional.shortest_path_buckets``, cached on the
         batch per ``spd_max_dist``) and hands them to all layers.
@@ -60,6 +95,16 @@ class GPS(nn.Module):
             raise ValueError(f"attn_bias must be 'spd' or None, not {attn_bias!r}")
         if attn_bias is not None and not Fh.SPD_MIN_DIST <= int(spd_max_dist) <= Fh.SPD_MAX_DIST:
             raise ValueError(f"spd_max_dist must be in [{Fh.SPD_MIN_DIST}, {Fh.SPD_MAX_DIST}], got {spd_max_dist}")
+        if global_model not in ("attention", "exphormer"):
+            raise ValueError(f"global_model must be 'attention' or 'exphormer', not {global_model!r}")
+        self.global_model = global_model
+        if global_model == "exphormer":
+            if attn_bias is not None:
+                raise ValueError(f"global_model='exphormer' and attn_bias={attn_bias!r} do not go together: the "
+                                 "shortest-path bias belongs to the dense attention (attn_bias must be None)")
+            _check_exphormer(expander_degree, num_virtual_nodes)
+        self.expander_degree, self.num_virtual_nodes = int(expander_degree), int(num_virtual_nodes)
+        self.add_local_edges, self.expander_seed = bool(add_local_edges), int(expander_seed)
         self.attn_bias = attn_bias
         self.spd_max_dist = int(spd_max_dist)
         activation = ACT_DICT["relu"] if activation is None else activation
@@ -75,8 +120,12 @@ class GPS(nn.Module):
         self.encoder_kinds = (node_encoder, edge_encoder)
         self.node_encoder = Linear(num_features, D) if node_encoder is None else NODE_ENCODERS[node_encoder](D)
         spd_buckets = self.spd_max_dist + 1 if attn_bias == "spd" else None
-        self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, spd_buckets=spd_buckets)
-                                    for _ in range(num_layers))
+        if global_model == "exphormer":
+            self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, global_model="exphormer",
+                                                 num_virtual_nodes=self.num_virtual_nodes) for _ in range(num_layers))
+        else:
+            self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, spd_buckets=spd_buckets)
+                                        for _ in range(num_layers))
         if edge_encoder is not None:
             if not self.layers[0].uses_edge_attr:
                 raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware local_conv ('gine' or 'gatedgcn'), "
@@ -87,15 +136,21 @@ class GPS(nn.Module):
         self.lin_1 = Linear(D, D)
         self.lin_2 = Linear(D, num_classes)
         self._node_head = NodeHead(self.lin_1, self.lin_2, act)
+        if global_model == "exphormer":             # after every parameter of before
+            self.virt_node_emb = _Table(self.num_virtual_nodes, D)
+            self.edge_type_emb = _Table(2 + 2 * self.num_virtual_nodes, D)
+            if self.layers[0].uses_edge_attr and not hasattr(self, "edge_encoder") and self.add_local_edges:
+                self.exph_edge_encoder = Linear(-1, D)
         # "layered"; "auto" runs layered too; "resident" raises with the reason when the model is called
         self.engine = "layered"
         self.last_engine: Optional[str] = None
 
     # ---- the surface of a homogeneous model (train.batching, train.train) ----------------------------------------
     def resident_reason(self, batch=None, need_grad: bool = False) -> str:
+        reason = EXPHORMER_RESIDENT_REASON if self.global_model == "exphormer" else RESIDENT_REASON
         if any(self.encoder_kinds):
-            return RESIDENT_REASON + "; " + encoder_reason(*self.encoder_kinds)
-        return RESIDENT_REASON
+            return reason + "; " + encoder_reason(*self.encoder_kinds)
+        return reason
 
     def supported(self, batch=None) -> bool:
         return False
@@ -109,6 +164,8 @@ class GPS(nn.Module):
         ``max_nodes`` (``nn.functional.check_attention``).  ``train.train_epoch`` / ``eval_epoch`` call it once per
         epoch, beside the read of the epoch's loss."""
         Fh.check_attention(next(self.parameters()).device)
+        if self.global_model == "exphormer":        # and the expander launches' (a graph beyond max_nodes)
+            Fh.check_expander(next(self.parameters()).device)
         if self.attn_bias == "spd":                 # and the bucket launches' (an edge outside its graph, max_nodes)
             Fh.check_spd(next(self.parameters()).device)
         if any(self.encoder_kinds):                # and the categorical encoders' (an index outside its column)
@@ -147,8 +204,11 @@ class GPS(nn.Module):
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
         if self.engine == "resident":
-            raise RuntimeError(f"engine='resident' does not take this model: {RESIDENT_REASON}")
+            raise RuntimeError("engine='resident' does not take this model: "
+                               f"{EXPHORMER_RESIDENT_REASON if self.global_model == 'exphormer' else RESIDENT_REASON}")
         self.last_engine = "layered"
+        if self.global_model == "exphormer":
+            return self._nodes_exphormer(batch)
         spd = self._spd(batch)                      # once per forward, for all layers (None without attn_bias)
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
         x = self.node_encoder(batch.x)
@@ -160,6 +220,29 @@ class GPS(nn.Module):
                 x, edge_attr = layer(x, batch.edge_index, batch, edge_attr, spd=spd)
             else:
                 x = layer(x, batch.edge_index, batch, edge_attr, spd=spd)
+        return x
+
+    def _nodes_exphormer(self, batch) -> Tensor:
+        """``_nodes`` with the sparse global model: the virtual rows travel beside the node rows and stay behind."""
+        edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
+        x = self.node_encoder(batch.x)
+        if self.layers[0].updates_edge_attr or self.encoder_kinds[1] is not None:
+            edge_attr = self.edge_encoder(edge_attr)
+        # the local edges' own features reach the attention at width D (see __init__); otherwise they share type 0
+        wide = hasattr(self, "edge_encoder") and self.layers[0].uses_edge_attr
+        own = self.add_local_edges and (wide or hasattr(self, "exph_edge_encoder"))
+        struct = ExphormerStructure.of(batch, self.expander_degree, self.num_virtual_nodes, self.add_local_edges,
+                                       self.expander_seed, edge_features=own)
+        e_static = self.exph_edge_encoder(edge_attr) if own and not wide else None
+        virt = self.virt_node_emb.weight.repeat(struct.num_graphs, 1)      # graph-major: row g nv + t = weight[t]
+        e_type = self.edge_type_emb.weight
+        for i, layer in enumerate(self.layers):
+            layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
+            e_edge = (edge_attr if wide else e_static) if own else None
+            if layer.updates_edge_attr:             # the layer's new edge features feed the next layer
+                x, edge_attr, virt = layer(x, batch.edge_index, batch, edge_attr, exph=(struct, virt, e_edge, e_type))
+            else:
+                x, virt = layer(x, batch.edge_index, batch, edge_attr, exph=(struct, virt, e_edge, e_type))
         return x
 
     def _head(self, x: Tensor) -> Tensor:
@@ -191,4 +274,7 @@ def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:
     return GPS(num_features, model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.num_heads,
                model_cfg.local_conv_type, ACT_DICT[model_cfg.activation.lower()], model_cfg.dropout, model_cfg.norm,
                model_cfg.task_level, getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None),
-               getattr(model_cfg, "attn_bias", None), getattr(model_cfg, "spd_max_dist", 20))
+               getattr(model_cfg, "attn_bias", None), getattr(model_cfg, "spd_max_dist", 20),
+               getattr(model_cfg, "global_model", "attention"), getattr(model_cfg, "expander_degree", 6),
+               getattr(model_cfg, "num_virtual_nodes", 1), getattr(model_cfg, "add_local_edges", True),
+               getattr(model_cfg, "expander_seed", 0))

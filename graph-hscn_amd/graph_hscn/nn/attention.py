@@ -141,3 +141,66 @@ class MultiheadSelfAttention(nn.Module):
         else:
             out = Fh.BiasedSelfAttentionFn.apply(qkv, self.spd_bias.weight, spd, ptr32, int(max_nodes), self.num_heads)
         return self.out_proj(out)
+
+
+class _Proj(nn.Module):
+    """A ``Linear(channels, channels)`` of ``ExphormerAttention`` (torch's ``nn.Linear`` keys and initialisation),
+    through ``linear_wide``."""
+
+    def __init__(self, channels: int, bias: bool):
+        super().__init__()
+        self.in_features = self.out_features = channels
+        self.weight = nn.Parameter(torch.empty(channels, channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(channels))
+        else:
+            self.register_parameter("bias", None)
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if bias:
+            bound = 1.0 / math.sqrt(channels)
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return Fh.linear_wide(x, self.weight, self.bias)
+
+
+class ExphormerAttention(nn.Module):
+    """Exphormer's sparse attention (Shirzad et al., "Exphormer: Sparse Transformers for Graphs", 2023) over the union
+    of a batch's own edges, an expander and ``num_virtual_nodes`` virtual nodes per graph
+    (``structure.ExphormerStructure``), on the HIP path (csrc/exphormer.hip).
+
+    ``forward(x, struct, e_edge, e_type)``: ``x`` [N + B nv, channels] -- the node rows, then the virtual rows;
+    ``e_edge`` [E_local, channels] the encoded features of the local edges (None when the structure names none);
+    ``e_type`` [2 + 2 nv, channels] the edge-type embeddings.  ``Q``, ``K``, ``V`` project ``x``; ``E`` projects
+    ``e_edge`` and ``e_type`` alike, so the typed edges cost T rows of GEMM, not E_union.  Returns
+    ``(out_proj(attention[:N]), attention[N:])``: the virtual rows leave the layer as the raw attention output.
+
+    Not provided: dropout on the attention weights, a shortest-path bias, CPU tensors."""
+
+    def __init__(self, channels: int, num_heads: int, num_virtual_nodes: int, use_bias: bool = False):
+        super().__init__()
+        if channels <= 0 or num_heads <= 0 or channels % num_heads:
+            raise ValueError(f"channels must be a positive multiple of num_heads, got channels={channels} and "
+                             f"num_heads={num_heads}")
+        if not 0 <= int(num_virtual_nodes) <= Fh.EXPH_MAX_VIRTUAL_NODES:
+            raise ValueError(f"num_virtual_nodes must be in [0, {Fh.EXPH_MAX_VIRTUAL_NODES}], got {num_virtual_nodes}")
+        if channels > Fh.EXPH_MAX_WIDTH:
+            raise ValueError(f"ExphormerAttention: channels={channels} is outside the kernel's envelope "
+                             f"({Fh.EXPH_ENVELOPE})")
+        self.channels, self.num_heads, self.num_virtual_nodes = int(channels), int(num_heads), int(num_virtual_nodes)
+        self.Q = _Proj(channels, use_bias)
+        self.K = _Proj(channels, use_bias)
+        self.V = _Proj(channels, use_bias)
+        self.E = _Proj(channels, use_bias)
+        self.out_proj = _Proj(channels, True)
+
+    def forward(self, x: Tensor, struct, e_edge: Optional[Tensor], e_type: Tensor):
+        if x.dim() != 2 or x.size(1) != self.channels:
+            raise ValueError(f"x must be [N + B * nv, {self.channels}], got {tuple(x.shape)}")
+        if struct.num_virtual_nodes != self.num_virtual_nodes:
+            raise ValueError(f"the structure has {struct.num_virtual_nodes} virtual nodes per graph, the module "
+                             f"{self.num_virtual_nodes}")
+        ee = None if e_edge is None else self.E(e_edge)
+        out = Fh.ExphormerAttentionFn.apply(self.Q(x), self.K(x), self.V(x), ee, self.E(e_type), struct, self.num_heads)
+        N = struct.num_nodes
+        return self.out_proj(out[:N]), out[N:]

@@ -646,6 +646,170 @@ class EdgeAttentionFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# Exphormer: expander edges (csrc/expander.hip) and typed sparse attention over the union graph (csrc/exphormer.hip)
+# --------------------------------------------------------------------------- #
+EXPANDER_MAX_NODES = 2048
+EXPANDER_MAX_DEGREE = 32
+EXPANDER_GRAPH_TOO_LARGE = 1      # flag bit 0: a graph with more than max_nodes nodes (its edges are -1)
+EXPH_MAX_VIRTUAL_NODES = 4
+EXPH_MAX_WIDTH = 512
+EXPH_ENVELOPE = f"heads >= 1, head width >= 1 and heads * head width <= {EXPH_MAX_WIDTH}"
+
+_EXPANDER_FLAGS = _hip.FlagWord()
+
+
+def expander_flags(device) -> Tensor:
+    """The device's flag word [1] int32 that every expander launch ORs into; ``check_expander`` reads and clears it."""
+    return _EXPANDER_FLAGS.of(device)
+
+
+def check_expander(device) -> None:
+    """Synchronising: ``ValueError`` if an expander launch since the last check met a graph larger than the
+    ``max_nodes`` it was given (that graph's edges are -1, the other graphs' are as always)."""
+    f = _EXPANDER_FLAGS.take(device)
+    if f & EXPANDER_GRAPH_TOO_LARGE:
+        raise ValueError("expander_edges: a graph has more nodes than max_nodes says (or than the kernel's "
+                         f"{EXPANDER_MAX_NODES}); its expander edges are -1")
+
+
+def expander_edges(ptr32: Tensor, degree: int, seed: int, graph_ids: Optional[Tensor] = None, *, max_nodes: int,
+                   num_nodes: Optional[int] = None) -> Tensor:
+    """Exphormer's expander for every graph of a batch (``hscn_expander_build``, one launch): int64 [2, degree * N],
+    graph g's ``n_g * degree`` edges at column ``degree * ptr32[g]`` -- ``degree / 2`` random Hamiltonian cycles in both
+    directions, drawn from Philox under ``seed`` and the graph's id (``graph_ids[g]``, or g): a graph's expander does
+    not depend on its place in the batch.  Loops (n = 1) and repeats (n = 2) are kept.  ``num_nodes``: N on the host
+    (``Batch.num_nodes``); without it ``ptr32[-1]`` is read back once.  No CPU fallback."""
+    degree, max_nodes = int(degree), int(max_nodes)
+    if degree < 2 or degree % 2 or degree > EXPANDER_MAX_DEGREE:
+        raise ValueError(f"expander_edges: degree must be even in [2, {EXPANDER_MAX_DEGREE}], got {degree}")
+    if not 0 <= max_nodes <= EXPANDER_MAX_NODES:
+        raise ValueError(f"expander_edges: a graph of {max_nodes} nodes is outside the kernel's envelope (one graph's "
+                         f"sort keys in LDS: at most {EXPANDER_MAX_NODES} nodes)")
+    if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
+        raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
+    if not ptr32.is_cuda:
+        raise RuntimeError("expander_edges takes HIP device tensors only (got a CPU tensor): there is no CPU "
+                           "fallback -- move the batch to the device")
+    B = ptr32.numel() - 1
+    dev = ptr32.device
+    if graph_ids is not None:
+        if graph_ids.dim() != 1 or graph_ids.numel() != B or graph_ids.is_floating_point():
+            raise ValueError(f"graph_ids must be {B} integers, one per graph")
+        if graph_ids.device != dev:
+            raise RuntimeError(f"graph_ids is on {graph_ids.device}, ptr32 on {dev}")
+        graph_ids = graph_ids.to(torch.int32).contiguous()
+    N = int(ptr32[-1].item()) if num_nodes is None else int(num_nodes)
+    out = torch.empty(2, degree * N, dtype=torch.int64, device=dev)
+    call("hscn_expander_build", ptr(ptr32.contiguous()), ptr(graph_ids), N, B, degree, int(seed) & (2 ** 64 - 1),
+         max_nodes, ptr(out) if N else None, ptr(expander_flags(dev)), stream())
+    return out
+
+
+def exph_attn_supported(heads: int, head_dim: int) -> bool:
+    """hscn_exph_attn_supported: the one statement of the kernel's envelope."""
+    return bool(_hip.lib().hscn_exph_attn_supported(int(heads), int(head_dim)))
+
+
+class ExphormerAttentionFn(Function):
+    """(q, k, v [N', Hd*C], e_edge [E_local, Hd*C] or None, e_type [T, Hd*C]) -> out [N', Hd*C] over the union graph of
+    ``struct`` (``structure.ExphormerStructure``): per head ``w_k = exp(clamp(q_i . (k_j * e_k) / sqrt(C), -5, 5))`` and
+    ``out_i = sum_k w_k v_j / (sum_k w_k + 1e-6)`` over the in-edges of i, zeros for a row without any.  ``e_k`` is row
+    ``erow[k]`` of ``e_edge`` or row ``erow[k] - E_local`` of ``e_type``.  Forward: one launch; kept are the inputs, the
+    output and ONE float per (row, head), the sum of the weights -- the weights are recomputed, never stored.
+    Backward: the target-keyed pass gives dq, de_edge and the per-(row, head) ``sum(dout * out)``; the source-keyed pass
+    gives dk and dv; the type-keyed pass gives de_type, every type's slots summed in fixed chunks in list order (two
+    launches, no float atomics).  Only what ``needs_input_grad`` asks for is computed."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, e_edge: Optional[Tensor], e_type: Tensor, struct, heads: int):
+        heads = int(heads)
+        for name, t in (("q", q), ("k", k), ("v", v), ("e_edge", e_edge), ("e_type", e_type)):
+            if t is not None and t.dtype != torch.float32:
+                raise TypeError(f"exphormer attention: {name} must be float32, got {t.dtype}")
+            if t is not None and t.dim() != 2:
+                raise ValueError(f"exphormer attention: {name} must be 2-D [rows, heads * C], got {tuple(t.shape)}")
+        N, HC = q.shape
+        if heads < 1 or HC % heads:
+            raise ValueError(f"exphormer attention: width {HC} is not a multiple of heads = {heads}")
+        C = HC // heads
+        if k.shape != q.shape or v.shape != q.shape:
+            raise ValueError(f"exphormer attention: k is {tuple(k.shape)}, v is {tuple(v.shape)}, q is {tuple(q.shape)}")
+        if struct.num_rows != N:
+            raise ValueError(f"the union graph has {struct.num_rows} rows (nodes + virtual nodes), q has {N}")
+        El, T, E = struct.num_edge_rows, struct.num_types, struct.num_edges
+        if e_edge is None and El:
+            raise ValueError(f"the union graph names {El} per-edge feature rows and e_edge is None")
+        if e_edge is not None and (e_edge.size(0) != El or e_edge.size(1) != HC):
+            raise ValueError(f"e_edge is {tuple(e_edge.shape)}; the union graph names {El} per-edge rows and the layer "
+                             f"is {HC} wide")
+        if e_type.size(0) != T or e_type.size(1) != HC:
+            raise ValueError(f"e_type is {tuple(e_type.shape)}; the union graph has {T} edge types and the layer is "
+                             f"{HC} wide")
+        if not exph_attn_supported(heads, C):
+            raise ValueError(f"exphormer attention: heads = {heads}, head width = {C} outside the kernel's envelope "
+                             f"({EXPH_ENVELOPE})")
+        for t in (q, k, v, e_edge, e_type):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("exphormer attention takes HIP device tensors only (got a CPU tensor): the hot path "
+                                   "has no CPU fallback")
+        q, k, v, e_edge, e_type = _c(q), _c(k), _c(v), _c(e_edge), _c(e_type)
+        csr = struct.rel.csr
+        dev = q.device
+        out = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        z = torch.empty(N, heads, dtype=torch.float32, device=dev)
+        call("hscn_exph_attn_fwd", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(struct.erow), ptr(q), ptr(k),
+             ptr(v), ptr(e_edge) if El else None, ptr(e_type), ptr(out), ptr(z), N, E, El, T, heads, C, ptr(csr.flag),
+             stream())
+        ctx.struct, ctx.heads = struct, heads
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, k, v, e_edge, e_type, out, z)
+        return out
+
+    @staticmethod
+    def backward(ctx, go: Optional[Tensor]):
+        q, k, v, e_edge, e_type, out, z = ctx.saved_tensors
+        struct, heads = ctx.struct, ctx.heads
+        need_q, need_k, need_v, need_e, need_t = ctx.needs_input_grad[:5]
+        need_e = need_e and e_edge is not None
+        if go is None or not (need_q or need_k or need_v or need_e or need_t):
+            return None, None, None, None, None, None, None
+        go = _c(go)
+        N, HC = q.shape
+        C = HC // heads
+        El, T, E = struct.num_edge_rows, struct.num_types, struct.num_edges
+        rel = struct.rel
+        csr = rel.csr
+        delta = torch.empty(N, heads, dtype=torch.float32, device=q.device)
+        dq = torch.empty_like(q) if need_q else None
+        # every e_edge row is named by exactly one union edge (the structure checks it): each row is written once
+        de = torch.empty_like(e_edge) if need_e else None
+        dk = dv = dt = None
+        call("hscn_exph_attn_bwd_dst", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(struct.erow), ptr(q), ptr(k),
+             ptr(v), ptr(e_edge) if El else None, ptr(e_type), ptr(out), ptr(z), ptr(go), ptr(delta), ptr(dq),
+             ptr(de) if El else None, N, E, El, T, heads, C, ptr(csr.flag), stream())
+        if need_k or need_v:
+            if E:
+                t = rel.csr_t
+                dk = torch.empty_like(k) if need_k else None
+                dv = torch.empty_like(v) if need_v else None
+                call("hscn_exph_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(struct.erow), ptr(q), ptr(k),
+                     ptr(v), ptr(e_edge) if El else None, ptr(e_type), ptr(z), ptr(delta), ptr(go), ptr(dk), ptr(dv),
+                     N, E, El, T, heads, C, ptr(csr.flag), stream())
+            else:                                   # no edge reaches k or v: exact zeros, not None
+                dk = torch.zeros_like(k) if need_k else None
+                dv = torch.zeros_like(v) if need_v else None
+        if need_t:
+            dt = torch.empty_like(e_type)
+            trowptr, titem = struct.type_slots
+            ws_bytes = int(_hip.lib().hscn_exph_type_workspace_bytes(E, T, heads, C))
+            ws = torch.empty(max(ws_bytes // 4, 4), dtype=torch.float32, device=q.device)
+            call("hscn_exph_attn_bwd_type", ptr(trowptr), ptr(titem), ptr(struct.edge_index) if E else None, ptr(q),
+                 ptr(k), ptr(v), ptr(e_type), ptr(z), ptr(delta), ptr(go), ptr(dt), N, E, T, heads, C, ptr(csr.flag),
+                 ptr(ws), ws.numel() * 4, stream())
+        return dq, dk, dv, de, dt, None, None
+
+
+# --------------------------------------------------------------------------- #
 # Global attention: block-diagonal multi-head self-attention over a batch (csrc/attention.hip)
 # --------------------------------------------------------------------------- #
 ATTN_MIN_HEAD_DIM = 4

@@ -12,6 +12,9 @@ normalisation, activation, dropout and residual, so the layer adds no second dro
 (``h_l = norm(GatedGCNLayer(x, e))``), and it updates the edge features: such a layer returns ``(h, edge_attr_out)``
 and the model hands the second to the next layer.  Every other layer returns a Tensor.
 
+``global_model="exphormer"`` puts ``ExphormerAttention`` -- sparse attention over the batch's own edges, an expander and
+virtual nodes -- where ``MultiheadSelfAttention`` stands; the virtual rows travel beside ``x`` (``forward(exph=...)``).
+
 ``local_conv=None`` leaves the local branch out (``h = h_a``): the plain Transformer layer of the LRGB
 "Transformer + PE" baselines.  Every operator is the package's own HIP one: the registry's convolutions,
 ``MultiheadSelfAttention``, ``Linear`` with the activation in its epilogue, the counter-based dropout and the norms."""
@@ -19,17 +22,19 @@ from __future__ import annotations
 
 from typing import Optional
 
+import torch
 import torch.nn as nn
 from torch import Tensor
 
 from .._hip import ACT
 from . import functional as Fh
-from .attention import MultiheadSelfAttention
+from .attention import ExphormerAttention, MultiheadSelfAttention
 from .conv import GatedGCNLayer, Linear
 from .norm import BatchNorm1d, LayerNorm
 
 LOCAL_CONVS = ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge")
 NORMS = ("layer", "batch", None)
+GLOBAL_MODELS = ("attention", "exphormer")
 
 
 def _norm(kind: Optional[str], channels: int) -> Optional[nn.Module]:
@@ -42,8 +47,14 @@ def _norm(kind: Optional[str], channels: int) -> Optional[nn.Module]:
 
 class GPSLayer(nn.Module):
     def __init__(self, channels: int, local_conv: Optional[str], num_heads: int, dropout: float = 0.0,
-                 norm: Optional[str] = "layer", act: str = "relu", spd_buckets: Optional[int] = None):
+                 norm: Optional[str] = "layer", act: str = "relu", spd_buckets: Optional[int] = None,
+                 global_model: str = "attention", num_virtual_nodes: int = 0):
         super().__init__()
+        if global_model not in GLOBAL_MODELS:
+            raise ValueError(f"global_model must be one of {GLOBAL_MODELS}, got {global_model!r}")
+        if global_model == "exphormer" and spd_buckets is not None:
+            raise ValueError("global_model='exphormer' has no shortest-path bias (spd_buckets must be None)")
+        self.global_model = global_model
         from ..config.config import CONV_DICT
         if local_conv is not None:
             local_conv = local_conv.lower()
@@ -66,7 +77,10 @@ class GPSLayer(nn.Module):
         else:
             self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
         # spd_buckets: the attention's own shortest-path bias table (Graphormer's spatial encoding); None: as before
-        self.attn = MultiheadSelfAttention(channels, num_heads, spd_buckets=spd_buckets)
+        if global_model == "exphormer":     # sparse attention over the union graph in the dense attention's place
+            self.attn = ExphormerAttention(channels, num_heads, num_virtual_nodes)
+        else:
+            self.attn = MultiheadSelfAttention(channels, num_heads, spd_buckets=spd_buckets)
         self.norm1_local = _norm(norm, channels) if local_conv is not None else None
         self.norm1_attn = _norm(norm, channels)
         self.ff_linear1 = Linear(channels, 2 * channels)
@@ -86,13 +100,26 @@ class GPSLayer(nn.Module):
         return Fh.dropout(x, p=self.dropout, training=self.training, seed=seed)
 
     def forward(self, x: Tensor, edge_index, batch=None, edge_attr: Optional[Tensor] = None, *,
-                ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None, spd=None):
+                ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None, spd=None, exph=None):
         """``batch``: the ``Batch`` (graph boundaries of the attention), or ``ptr32`` and ``max_nodes``.  ``spd``: the
         batch's ``SPDBuckets``, for a layer built with ``spd_buckets`` (refused by name otherwise).  ``edge_attr``
         is read by an edge-aware ``local_conv`` ("gine", "gatedgcn", "transformerconv_edge") only.  Returns the node features; with a
-        ``local_conv`` that updates the edge features ("gatedgcn") the pair ``(h, edge_attr_out)``."""
-        edge_out = None
-        if spd is None:                             # (the call of before, word for word)
+        ``local_conv`` that updates the edge features ("gatedgcn") the pair ``(h, edge_attr_out)``.
+
+        ``global_model="exphormer"``: ``exph = (struct, virt, e_edge, e_type)`` -- the batch's ``ExphormerStructure``,
+        the virtual rows [B nv, D] as the previous layer left them, the encoded local edge features (or None) and the
+        edge-type embeddings.  The attention sees ``cat(x, virt)``; everything else of the layer runs on the node rows
+        only, and the new virtual rows are appended to what the layer returns: ``(h, virt_out)`` or
+        ``(h, edge_attr_out, virt_out)``."""
+        edge_out = virt_out = None
+        if self.global_model == "exphormer":
+            if exph is None:
+                raise ValueError("GPSLayer(global_model='exphormer') needs exph=(struct, virt, e_edge, e_type)")
+            struct, virt, e_edge, e_type = exph
+            h_a, virt_out = self.attn(torch.cat([x, virt], 0) if virt.size(0) else x, struct, e_edge, e_type)
+        elif exph is not None:
+            raise ValueError("exph= belongs to a layer built with global_model='exphormer'")
+        elif spd is None:                           # (the call of before, word for word)
             h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes)
         else:
             h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes, spd=spd)
@@ -118,4 +145,6 @@ class GPSLayer(nn.Module):
         h = h + self._drop(Fh.linear_wide(self._drop(f, 2), self.ff_linear2.weight, self.ff_linear2.bias), 3)
         if self.norm2 is not None:
             h = self.norm2(h)
+        if self.global_model == "exphormer":
+            return (h, edge_out, virt_out) if self.updates_edge_attr else (h, virt_out)
         return (h, edge_out) if self.updates_edge_attr else h

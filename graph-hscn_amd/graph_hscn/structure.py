@@ -277,6 +277,134 @@ def category_index_of(idx: Tensor, cardinalities, cache: bool = True) -> Categor
     return hit
 
 
+EXPH_TYPE_LOCAL = 0          # a local edge of a batch without edge features
+EXPH_TYPE_EXPANDER = 1
+EXPH_MAX_VIRTUAL_NODES = 4
+
+
+class ExphormerStructure:
+    """The union graph Exphormer's sparse attention runs over, for one batch.
+
+    Rows: ``N' = N + B * nv`` -- the real nodes, then the virtual nodes graph-major (row ``N + g * nv + t``).
+    Edges, in this order: the local edges (``add_local_edges``), the expander edges, then for node i (ascending) and
+    virtual node t of its graph the edge i -> virtual at ``i * nv + t`` of one block and virtual -> i at the same place
+    of the next.  ``erow`` int32 [E_union] names every edge's feature row: a value below ``num_edge_rows`` (= E_local
+    when the local edges carry features, else 0) is that row of the per-edge tensor, ``num_edge_rows + tau`` is type
+    tau of the table: 0 = local without features, 1 = expander, 2 + t = node -> virtual t, 2 + nv + t = virtual t ->
+    node; ``num_types = 2 + 2 nv``.
+
+    The index tensors are plain torch index arithmetic on whatever device the inputs are on (no reduction, no host
+    read).  ``rel`` (both CSRs through ``hscn_csr_build_pair``) and ``type_slots`` (the type-keyed edge list the table
+    gradient walks: ``hscn_catenc_index_build``, a stable counting sort, no launch of its own) need the device and are
+    built on first use."""
+
+    def __init__(self, edge_index: Tensor, batch_vec: Tensor, num_graphs: int, expander_edge_index: Optional[Tensor],
+                 num_virtual_nodes: int, add_local_edges: bool = True, edge_features: bool = True):
+        nv = int(num_virtual_nodes)
+        if not 0 <= nv <= EXPH_MAX_VIRTUAL_NODES:
+            raise ValueError(f"num_virtual_nodes must be in [0, {EXPH_MAX_VIRTUAL_NODES}], got {num_virtual_nodes}")
+        if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+            raise TypeError("edge_index must be an int64 [2, E] tensor")
+        dev = edge_index.device
+        N, B = int(batch_vec.numel()), int(num_graphs)
+        i64 = dict(dtype=torch.int64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        parts, rows = [], []
+        E_local = int(edge_index.size(1))
+        self.num_edge_rows = E_local if (add_local_edges and edge_features) else 0
+        El = self.num_edge_rows
+        if add_local_edges:
+            parts.append(edge_index)
+            rows.append(torch.arange(E_local, **i32) if El else torch.full((E_local,), EXPH_TYPE_LOCAL, **i32))
+        if expander_edge_index is not None:
+            if expander_edge_index.dtype != torch.int64 or expander_edge_index.dim() != 2 or \
+                    expander_edge_index.size(0) != 2 or expander_edge_index.device != dev:
+                raise TypeError(f"the expander edges must be an int64 [2, E] tensor on {dev}")
+            parts.append(expander_edge_index)
+            rows.append(torch.full((int(expander_edge_index.size(1)),), El + EXPH_TYPE_EXPANDER, **i32))
+        if nv:
+            node = torch.arange(N, **i64).repeat_interleave(nv)                      # i * nv + t -> i
+            t = torch.arange(nv, **i64).repeat(N)                                    #            -> t
+            virt = N + batch_vec.to(torch.int64).repeat_interleave(nv) * nv + t
+            parts += [torch.stack([node, virt]), torch.stack([virt, node])]
+            rows += [(El + 2 + t).to(torch.int32), (El + 2 + nv + t).to(torch.int32)]
+        self.num_nodes, self.num_graphs, self.num_virtual_nodes = N, B, nv
+        self.num_rows = N + B * nv
+        self.num_types = 2 + 2 * nv
+        self.edge_index = torch.cat(parts, 1).contiguous() if parts else torch.zeros(2, 0, **i64)
+        self.erow = torch.cat(rows).contiguous() if rows else torch.zeros(0, **i32)
+        self.num_edges = int(self.edge_index.size(1))
+        self._rel: Optional[Relation] = None
+        self._type_slots = None
+
+    @classmethod
+    def from_parts(cls, edge_index: Tensor, erow: Tensor, num_nodes: int, num_graphs: int, num_virtual_nodes: int,
+                   num_edge_rows: int) -> "ExphormerStructure":
+        """A union graph the caller has put together: ``edge_index`` int64 [2, E] over ``num_nodes + num_graphs *
+        num_virtual_nodes`` rows in any order, ``erow`` [E] as above.  Every per-edge row below ``num_edge_rows`` must
+        be named by exactly one edge (the attention's backward writes each row's gradient once); this is checked here,
+        with one read of the device."""
+        nv = int(num_virtual_nodes)
+        if not 0 <= nv <= EXPH_MAX_VIRTUAL_NODES:
+            raise ValueError(f"num_virtual_nodes must be in [0, {EXPH_MAX_VIRTUAL_NODES}], got {num_virtual_nodes}")
+        if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
+            raise TypeError("edge_index must be an int64 [2, E] tensor")
+        El, T = int(num_edge_rows), 2 + 2 * nv
+        if erow.dim() != 1 or erow.numel() != edge_index.size(1) or erow.is_floating_point():
+            raise ValueError("erow must hold one integer per edge")
+        own = erow[erow < El].to(torch.int64)
+        if erow.numel() and (int(erow.min()) < 0 or int(erow.max()) >= El + T):
+            raise ValueError(f"erow holds a row outside [0, {El} + {T})")
+        if own.numel() != El or (El and not bool((torch.bincount(own, minlength=El) == 1).all())):
+            raise ValueError(f"every per-edge feature row in [0, {El}) must be named by exactly one edge")
+        self = cls.__new__(cls)
+        self.num_edge_rows, self.num_nodes, self.num_graphs, self.num_virtual_nodes = El, int(num_nodes), int(num_graphs), nv
+        self.num_rows, self.num_types = self.num_nodes + self.num_graphs * nv, T
+        self.edge_index = edge_index.contiguous()
+        self.erow = erow.to(torch.int32).contiguous()
+        self.num_edges = int(edge_index.size(1))
+        self._rel, self._type_slots = None, None
+        return self
+
+    @property
+    def rel(self) -> Relation:
+        if self._rel is None:
+            self._rel = Relation(self.edge_index, self.num_rows, self.num_rows, both=True)
+        return self._rel
+
+    @property
+    def type_slots(self) -> Tuple[Tensor, Tensor]:
+        """(rowptr int32 [T + 1], item int32): slots ``rowptr[tau] .. rowptr[tau + 1]`` of ``item`` hold the union edge
+        ids of type tau, ascending."""
+        if self._type_slots is None:
+            key = (self.erow.to(torch.int64) - (self.num_edge_rows - 1)).clamp_(min=0).unsqueeze(1)   # 0: a per-edge row
+            idx = build_category_index(key, (self.num_types + 1,))
+            self._type_slots = (idx.rowptr[1:], idx.item, idx)
+        return self._type_slots[:2]
+
+    @classmethod
+    def of(cls, batch, degree: int, num_virtual_nodes: int, add_local_edges: bool = True, seed: int = 0,
+           edge_features: Optional[bool] = None, graph_ids: Optional[Tensor] = None) -> "ExphormerStructure":
+        """The structure of a collated ``Batch`` on the device, built once and kept on the batch object (in the dict
+        that ``train.batching.to_device`` hands on by reference, beside the shortest-path buckets).  The expander is
+        drawn by ``nn.functional.expander_edges`` with ``graph_ids`` (default ``arange(B)``): a reshuffled loader draws
+        a new one per batch, a batch object that is reused keeps its own."""
+        from .nn.functional import expander_edges
+        if edge_features is None:
+            edge_features = getattr(batch, "edge_attr", None) is not None
+        cache = getattr(batch, "__dict__", {}).setdefault("_spd_cache", {})
+        key = ("exphormer", int(degree), int(num_virtual_nodes), bool(add_local_edges), int(seed), bool(edge_features),
+               None if graph_ids is None else graph_ids.data_ptr(), str(batch.ptr32.device))
+        if key not in cache:
+            B = int(batch.ptr32.numel()) - 1
+            N = int(batch.batch.numel())
+            if graph_ids is None:
+                graph_ids = torch.arange(B, dtype=torch.int32, device=batch.ptr32.device)
+            ex = expander_edges(batch.ptr32, degree, seed, graph_ids, max_nodes=batch.max_nodes, num_nodes=N)
+            cache[key] = cls(batch.edge_index, batch.batch, B, ex, num_virtual_nodes, add_local_edges, edge_features)
+        return cache[key]
+
+
 def clear_cache() -> None:
     _LOOP_CACHE.clear()
     _CACHE.clear()

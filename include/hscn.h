@@ -1680,6 +1680,78 @@ int hscn_attention_bias_bwd_kv(const float* qkv, const float* lse, const float* 
                                int64_t N, int64_t B, int64_t total, int max_nodes, int heads, int dh, int num_buckets,
                                float* g_qkv /*[N, 3D]*/, int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Exphormer: expander edges (csrc/expander.hip) and typed sparse attention (csrc/exphormer.hip).  Purely additive to
+ * ABI 24.
+ *
+ * hscn_expander_build: ONE launch, one workgroup per graph.  degree is even, in [2, hscn_expander_max_degree() = 32].
+ *   Graph g of n nodes gets degree / 2 random Hamiltonian cycles, each in both directions: n * degree edges at column
+ *   degree * ptr32[g] of edge_index i64 [2, degree * N].  Cycle r: node t (local id) has the key
+ *   (philox4x32_10(seed, ctr)[0] << 32) | t with ctr = (gid << 32) | (r << 16) | t, gid = graph_ids[g] (i32 [B]) or g
+ *   when graph_ids is NULL; pi = the local ids in ascending key order (bitonic sort in LDS); block r holds
+ *   pi[i] -> pi[(i + 1) mod n] for i = 0 .. n - 1 and then their reverses.  n = 1 gives loops, n = 2 repeats; nothing
+ *   is rejected.  flag [1] i32, only OR-ed into: bit 0 = a graph with more than max_nodes nodes (its edges are -1) or
+ *   a ptr32 that leaves [0, N] (nothing written for that graph).  max_nodes <= hscn_expander_max_nodes() = 2048.
+ *   HSCN_E_BADARG for null pointers, negative sizes, an odd degree or one below 2; HSCN_E_UNSUPPORTED beyond the two
+ *   limits; both before any launch.  N = 0 or B = 0 launches nothing.
+ *
+ * hscn_exph_attn_*: per head, over the in-edges of row i of a union graph with N rows and E edges,
+ *     s_k = scale <q_i, k_j * e_k>,  w_k = exp(clamp(s_k, -5, 5)),  Z_i = sum_k w_k,
+ *     out_i = (sum_k w_k v_j) / (Z_i + 1e-6)              scale = 1 / sqrt(head_dim), j = src_k
+ *   e_k is row erow[k] of e_edge [El, HC] where erow[k] < El and row erow[k] - El of the table e_type [T, HC] otherwise
+ *   (erow i32 [E], indexed by the union edge, reached from a CSR slot through eid; T <= hscn_exph_max_types() = 10;
+ *   e_edge may be NULL with El = 0).  The CSR conventions, lane layout, long-row scheme and its two constants
+ *   (hscn_exph_attn_long_row / _chunk) are those of hscn_edge_attn_*; q, k, v share the N rows.
+ * hscn_exph_attn_fwd: ONE launch; out [N, HC] and z [N, heads] = Z_i (no shift: w <= e^5); zeros for an empty row.
+ * hscn_exph_attn_bwd_dst: ONE launch over the same CSR; stores delta_i = sum_c g_out_i out_i [N, heads], and with
+ *   ds_k = w_k (g_out_i . v_j - delta_i) / (Z_i + 1e-6) [-5 < s_k < 5]:  dq_i = scale sum_k ds_k (k_j * e_k) and, for
+ *   slots with erow < El, de_edge[erow] = scale ds_k (q_i * k_j) (one writer: the caller lists each e_edge row once).
+ *   dq, de_edge may be NULL (both NULL: delta alone).
+ * hscn_exph_attn_bwd_src: ONE launch over the source-keyed CSR: dk_j = scale sum ds_k (q_i * e_k), dv_j =
+ *   sum w_k g_out_i / (Z_i + 1e-6); either may be NULL (both: nothing is launched).
+ * hscn_exph_attn_bwd_type: TWO launches; de_type[tau] = scale sum ds_k (q_i * k_j) over the union edges listed for
+ *   type tau in trowptr [T + 1] / titem (edge ids in list order; edge_index i64 [2, E] names their ends).  A type of
+ *   more than hscn_exph_type_long_row() slots is cut into chunks of hscn_exph_type_chunk() slots from its first
+ *   slot; every chunk is a serial sum from zero stored as a partial, the second launch adds a type's partials in chunk
+ *   order: the bits depend on the type's slots in list order alone.  A type without slots gets zeros.  workspace:
+ *   hscn_exph_type_workspace_bytes = (E / chunk + T) * HC floats, not initialised by the caller.
+ * No float atomics anywhere.  flag [1] i32: bit 1 is OR-ed in for a slot whose column, edge id, feature row or list
+ *   range is out of range (the slot adds nothing).  HSCN_E_BADARG for null pointers and negative sizes,
+ *   HSCN_E_UNSUPPORTED where hscn_exph_attn_supported is 0 (heads * head_dim > 512) or T > 10, HSCN_E_WORKSPACE for a
+ *   short workspace; all before any launch.  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_expander_max_nodes(void);
+int hscn_expander_max_degree(void);
+int hscn_expander_build(const int32_t* ptr32 /*[B + 1]*/, const int32_t* graph_ids /*[B] or NULL*/, int64_t N, int64_t B,
+                        int degree, uint64_t seed, int max_nodes, int64_t* edge_index /*[2, degree N]*/,
+                        int32_t* flag /*[1]*/, void* stream);
+int hscn_exph_attn_supported(int heads, int head_dim);
+int hscn_exph_attn_long_row(void);
+int hscn_exph_attn_chunk(void);
+int hscn_exph_type_long_row(void);
+int hscn_exph_type_chunk(void);
+int hscn_exph_max_types(void);
+int hscn_exph_attn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* erow /*[E]*/,
+                       const float* q, const float* k, const float* v, const float* e_edge /*[El, HC] or NULL*/,
+                       const float* e_type /*[T, HC]*/, float* out /*[N, HC]*/, float* z /*[N, heads]*/, int64_t N,
+                       int64_t E, int64_t El, int T, int heads, int head_dim, int32_t* flag /*[1]*/, void* stream);
+int hscn_exph_attn_bwd_dst(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* erow,
+                           const float* q, const float* k, const float* v, const float* e_edge, const float* e_type,
+                           const float* out, const float* z, const float* g_out, float* delta /*[N, heads]*/,
+                           float* dq /*[N, HC]*/, float* de_edge /*[El, HC]*/, int64_t N, int64_t E, int64_t El, int T,
+                           int heads, int head_dim, int32_t* flag /*[1]*/, void* stream);
+int hscn_exph_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const int32_t* erow,
+                           const float* q, const float* k, const float* v, const float* e_edge, const float* e_type,
+                           const float* z, const float* delta, const float* g_out, float* dk /*[N, HC]*/,
+                           float* dv /*[N, HC]*/, int64_t N, int64_t E, int64_t El, int T, int heads, int head_dim,
+                           int32_t* flag /*[1]*/, void* stream);
+size_t hscn_exph_type_workspace_bytes(int64_t E, int T, int heads, int head_dim);
+int hscn_exph_attn_bwd_type(const int32_t* trowptr /*[T + 1]*/, const int32_t* titem, const int64_t* edge_index /*[2, E]*/,
+                            const float* q, const float* k, const float* v, const float* e_type, const float* z,
+                            const float* delta, const float* g_out, float* de_type /*[T, HC]*/, int64_t N, int64_t E,
+                            int T, int heads, int head_dim, int32_t* flag /*[1]*/, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
