@@ -9,9 +9,8 @@
 // belongs to edge k of the edge list, not to CSR slot k: every slot goes through eid[slot].  Every listed edge counts
 // (loops, repeats).
 //
-// Work unit: one (row, head), owned by G consecutive lanes (G a power of two, at most 64), VEC = 4 columns per lane
-// and pass (16-byte accesses) where C % 4 == 0 and every pointer is 16-byte aligned, VEC = 1 otherwise; a head wider
-// than G * VEC takes NP <= 8 / VEC passes, all of them held in registers (8 floats per lane and operand).  With the
+// Work unit: one (row, head), owned by G consecutive lanes, in the layout of csrc/row_walk.h's head-unit layer (VEC = 4
+// columns per lane and pass where the width and the pointers allow, 8 floats per lane and operand).  With the
 // in-degree 2..4 of a molecular graph and C = 16 a wave therefore carries 16 (row, head) units, none of them idle; the
 // heads of one row are neighbouring lane groups, so a row of k / v is read by consecutive lanes.  The dot products
 // are reduced over the lane group by xor shuffles (every lane of a group ends with the same bits).
@@ -34,13 +33,8 @@
 // Long rows: the two-phase scheme described in csrc/row_walk.h with a (row, head) pair as the unit; the forward's chunk
 // partials are (max, sum, accumulator) triples merged in chunk order, the backward's plain sums added in chunk order.
 #include "row_walk.h"
-#include <math.h>
 
 namespace {
-
-constexpr int EA_THREADS = 256;
-constexpr int EA_MAX_WIDTH = 512;  // heads * head_dim
-constexpr int EA_NC = 8;           // floats a lane holds of one operand row: (8 / VEC) passes of VEC columns
 
 struct EAArgs {
   const int32_t* rowptr;   // the walked CSR: keyed by target (MODE 0, 1) or by source (MODE 2)
@@ -64,78 +58,43 @@ struct EAArgs {
   int32_t* flag;
 };
 
-// pass p gives lane lg of a group the columns [c, c + VEC), c = (p * G + lg) * VEC; only p < NP is visited and a lane
-// with c >= C idles (C % VEC == 0, so a vector never straddles the end of a head)
-template <int VEC>
-__device__ __forceinline__ void load_cols(const EAArgs& A, const float* row, int lg, float (&x)[EA_NC]) {
-  using V = GV<VEC>;
-#pragma unroll
-  for (int i = 0; i < EA_NC; ++i) x[i] = 0.f;
-#pragma unroll
-  for (int p = 0; p < EA_NC / VEC; ++p) {
-    const int c = (p * A.G + lg) * VEC;
-    if (p < A.NP && c < A.C) {
-      const typename V::T t = V::load(row + c);
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) x[p * VEC + u] = V::get(t, u);
-    }
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_cols(const EAArgs& A, float* row, int lg, const float (&x)[EA_NC]) {
-  using V = GV<VEC>;
-#pragma unroll
-  for (int p = 0; p < EA_NC / VEC; ++p) {
-    const int c = (p * A.G + lg) * VEC;
-    if (p < A.NP && c < A.C) V::store(row + c, V::make(&x[p * VEC]));
-  }
-}
-
-__device__ __forceinline__ float dot8(const float (&a)[EA_NC], const float (&b)[EA_NC]) {
-  float s = 0.f;                     // (columns a lane does not own hold zeros)
-#pragma unroll
-  for (int i = 0; i < EA_NC; ++i) s = fmaf(a[i], b[i], s);
-  return s;
-}
-
 // what a lane keeps of its (row, head) while it walks the slots
 struct UnitCtx {
-  float a[EA_NC];    // MODE 0, 1: q_i;  MODE 2: k_j
-  float b[EA_NC];    // MODE 1: dout_i;  MODE 2: v_j
+  float a[HEAD_NC];    // MODE 0, 1: q_i;  MODE 2: k_j
+  float b[HEAD_NC];    // MODE 1: dout_i;  MODE 2: v_j
   float m, logl, delta;  // MODE 1
 };
 
 // the running state of a walk: MODE 0 (m, l, acc0) of the online softmax; MODE 1 acc0 = dq; MODE 2 acc0 = dk, acc1 = dv
 struct UnitAcc {
   float m, l;
-  float acc0[EA_NC];
-  float acc1[EA_NC];
+  float acc0[HEAD_NC];
+  float acc1[HEAD_NC];
 };
 
 __device__ __forceinline__ void acc_clear(UnitAcc& S) {
   S.m = -INFINITY;
   S.l = 0.f;
 #pragma unroll
-  for (int i = 0; i < EA_NC; ++i) S.acc0[i] = S.acc1[i] = 0.f;
+  for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] = S.acc1[i] = 0.f;
 }
 
 template <int VEC, int MODE>
 __device__ __forceinline__ void unit_begin(const EAArgs& A, int64_t r, int h, int lg, UnitCtx& U) {
   const size_t at = (size_t)r * A.HC + (size_t)h * A.C;
   if (MODE == 0) {
-    load_cols<VEC>(A, A.q + at, lg, U.a);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.q + at, lg, U.a);
   } else if (MODE == 1) {
-    float o[EA_NC];
-    load_cols<VEC>(A, A.q + at, lg, U.a);
-    load_cols<VEC>(A, A.go + at, lg, U.b);
-    load_cols<VEC>(A, A.out + at, lg, o);
-    U.delta = group_sum(dot8(U.b, o), A.G);
+    float o[HEAD_NC];
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.q + at, lg, U.a);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.go + at, lg, U.b);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.out + at, lg, o);
+    U.delta = group_sum(rw_dot8(U.b, o), A.G);
     U.m = A.lse[2 * ((size_t)r * A.Hd + h)];
     U.logl = A.lse[2 * ((size_t)r * A.Hd + h) + 1];
   } else {
-    load_cols<VEC>(A, A.k + at, lg, U.a);
-    load_cols<VEC>(A, A.v + at, lg, U.b);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.k + at, lg, U.a);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.v + at, lg, U.b);
   }
 }
 
@@ -150,63 +109,63 @@ __device__ __forceinline__ void walk_slots(const EAArgs& A, const UnitCtx& U, in
       atomicOr(A.flag, 2);
       continue;
     }
-    float ee[EA_NC];
+    float ee[HEAD_NC];
     if (A.e) {
-      load_cols<VEC>(A, A.e + (size_t)kx * A.HC + hoff, lg, ee);
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.e + (size_t)kx * A.HC + hoff, lg, ee);
     } else {
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) ee[i] = 0.f;
+      for (int i = 0; i < HEAD_NC; ++i) ee[i] = 0.f;
     }
     const size_t nj = (size_t)j * A.HC + hoff;
     if (MODE == 0) {
-      float kk[EA_NC], vv[EA_NC];
-      load_cols<VEC>(A, A.k + nj, lg, kk);
-      load_cols<VEC>(A, A.v + nj, lg, vv);
+      float kk[HEAD_NC], vv[HEAD_NC];
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.k + nj, lg, kk);
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.v + nj, lg, vv);
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) kk[i] += ee[i], vv[i] += ee[i];
-      const float sc = group_sum(dot8(U.a, kk), A.G) * A.scale;
+      for (int i = 0; i < HEAD_NC; ++i) kk[i] += ee[i], vv[i] += ee[i];
+      const float sc = group_sum(rw_dot8(U.a, kk), A.G) * A.scale;
       if (sc > S.m) {                                    // a new running maximum: rescale what was summed under the old
         const float corr = expf(S.m - sc);
         S.l *= corr;
 #pragma unroll
-        for (int i = 0; i < EA_NC; ++i) S.acc0[i] *= corr;
+        for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] *= corr;
         S.m = sc;
       }
       const float w = expf(sc - S.m);
       S.l += w;
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) S.acc0[i] = fmaf(w, vv[i], S.acc0[i]);
+      for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] = fmaf(w, vv[i], S.acc0[i]);
     } else if (MODE == 1) {
-      float kk[EA_NC], vv[EA_NC];
-      load_cols<VEC>(A, A.k + nj, lg, kk);
-      load_cols<VEC>(A, A.v + nj, lg, vv);
+      float kk[HEAD_NC], vv[HEAD_NC];
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.k + nj, lg, kk);
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.v + nj, lg, vv);
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) kk[i] += ee[i], vv[i] += ee[i];
-      const float sc = group_sum(dot8(U.a, kk), A.G) * A.scale;
-      const float dp = group_sum(dot8(U.b, vv), A.G);
+      for (int i = 0; i < HEAD_NC; ++i) kk[i] += ee[i], vv[i] += ee[i];
+      const float sc = group_sum(rw_dot8(U.a, kk), A.G) * A.scale;
+      const float dp = group_sum(rw_dot8(U.b, vv), A.G);
       const float a = expf((sc - U.m) - U.logl);
       const float ds = a * (dp - U.delta) * A.scale;
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) S.acc0[i] = fmaf(ds, kk[i], S.acc0[i]);
+      for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] = fmaf(ds, kk[i], S.acc0[i]);
       if (A.g1) {
-        float de[EA_NC];
+        float de[HEAD_NC];
 #pragma unroll
-        for (int i = 0; i < EA_NC; ++i) de[i] = fmaf(ds, U.a[i], a * U.b[i]);
-        store_cols<VEC>(A, A.g1 + (size_t)kx * A.HC + hoff, lg, de);
+        for (int i = 0; i < HEAD_NC; ++i) de[i] = fmaf(ds, U.a[i], a * U.b[i]);
+        rw_store_cols<VEC>(A.G, A.NP, A.C, A.g1 + (size_t)kx * A.HC + hoff, lg, de);
       }
     } else {
-      float qq[EA_NC], gg[EA_NC], kk[EA_NC], vv[EA_NC];   // (j is the target here, the row is the source)
-      load_cols<VEC>(A, A.q + nj, lg, qq);
-      load_cols<VEC>(A, A.go + nj, lg, gg);
+      float qq[HEAD_NC], gg[HEAD_NC], kk[HEAD_NC], vv[HEAD_NC];   // (j is the target here, the row is the source)
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.q + nj, lg, qq);
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.go + nj, lg, gg);
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) kk[i] = U.a[i] + ee[i], vv[i] = U.b[i] + ee[i];
-      const float sc = group_sum(dot8(qq, kk), A.G) * A.scale;
-      const float dp = group_sum(dot8(gg, vv), A.G);
+      for (int i = 0; i < HEAD_NC; ++i) kk[i] = U.a[i] + ee[i], vv[i] = U.b[i] + ee[i];
+      const float sc = group_sum(rw_dot8(qq, kk), A.G) * A.scale;
+      const float dp = group_sum(rw_dot8(gg, vv), A.G);
       const size_t ih = (size_t)j * A.Hd + h;
       const float a = expf((sc - A.lse[2 * ih]) - A.lse[2 * ih + 1]);
       const float ds = a * (dp - A.delta[ih]) * A.scale;
 #pragma unroll
-      for (int i = 0; i < EA_NC; ++i) {
+      for (int i = 0; i < HEAD_NC; ++i) {
         S.acc0[i] = fmaf(ds, qq[i], S.acc0[i]);
         S.acc1[i] = fmaf(a, gg[i], S.acc1[i]);
       }
@@ -218,29 +177,29 @@ template <int VEC, int MODE>
 __device__ __forceinline__ void unit_finish(const EAArgs& A, const UnitCtx& U, int64_t r, int h, int lg, const UnitAcc& S) {
   const size_t at = (size_t)r * A.HC + (size_t)h * A.C;
   if (MODE == 0) {
-    float o[EA_NC];
+    float o[HEAD_NC];
     const bool any = S.l > 0.f || S.l != S.l;            // (a NaN sum is shown, not hidden)
 #pragma unroll
-    for (int i = 0; i < EA_NC; ++i) o[i] = any ? S.acc0[i] / S.l : 0.f;
-    store_cols<VEC>(A, A.out + at, lg, o);
+    for (int i = 0; i < HEAD_NC; ++i) o[i] = any ? S.acc0[i] / S.l : 0.f;
+    rw_store_cols<VEC>(A.G, A.NP, A.C, A.out + at, lg, o);
     if (lg == 0) {
       A.lse[2 * ((size_t)r * A.Hd + h)] = any ? S.m : 0.f;
       A.lse[2 * ((size_t)r * A.Hd + h) + 1] = any ? logf(S.l) : 0.f;
     }
   } else if (MODE == 1) {
     if (lg == 0) A.delta[(size_t)r * A.Hd + h] = U.delta;
-    if (A.g0) store_cols<VEC>(A, A.g0 + at, lg, S.acc0);
+    if (A.g0) rw_store_cols<VEC>(A.G, A.NP, A.C, A.g0 + at, lg, S.acc0);
   } else {
-    if (A.g0) store_cols<VEC>(A, A.g0 + at, lg, S.acc0);
-    if (A.g1) store_cols<VEC>(A, A.g1 + at, lg, S.acc1);
+    if (A.g0) rw_store_cols<VEC>(A.G, A.NP, A.C, A.g0 + at, lg, S.acc0);
+    if (A.g1) rw_store_cols<VEC>(A.G, A.NP, A.C, A.g1 + at, lg, S.acc1);
   }
 }
 
 template <int VEC, int MODE>
-__global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
+__global__ void __launch_bounds__(HEAD_THREADS) k_edge_attn(const EAArgs A) {
   constexpr int NACC = MODE == 2 ? 2 : 1;
-  __shared__ float part[NACC * EA_THREADS * EA_NC];      // chunk partials of a long row, [accumulator][thread][EA_NC]
-  __shared__ float part_m[EA_THREADS], part_l[EA_THREADS];
+  __shared__ float part[NACC * HEAD_THREADS * HEAD_NC];  // chunk partials of a long row, [accumulator][thread][HEAD_NC]
+  __shared__ float part_m[HEAD_THREADS], part_l[HEAD_THREADS];
   const bool walk = MODE != 1 || A.walk != 0;
   const int ul = threadIdx.x / A.G;                      // unit of this lane group within the workgroup's tile
   const int lg = threadIdx.x - ul * A.G;
@@ -286,9 +245,9 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
           acc_clear(S);
           walk_slots<VEC, MODE>(A, U, h, lg, cs, ct, S);
 #pragma unroll
-          for (int x = 0; x < EA_NC; ++x) {
-            part[threadIdx.x * EA_NC + x] = S.acc0[x];
-            if (MODE == 2) part[(EA_THREADS + threadIdx.x) * EA_NC + x] = S.acc1[x];
+          for (int x = 0; x < HEAD_NC; ++x) {
+            part[threadIdx.x * HEAD_NC + x] = S.acc0[x];
+            if (MODE == 2) part[(HEAD_THREADS + threadIdx.x) * HEAD_NC + x] = S.acc1[x];
           }
           if (MODE == 0) part_m[threadIdx.x] = S.m, part_l[threadIdx.x] = S.l;
         }
@@ -304,17 +263,17 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
                 const float corr = expf(T.m - pm);
                 T.l *= corr;
 #pragma unroll
-                for (int x = 0; x < EA_NC; ++x) T.acc0[x] *= corr;
+                for (int x = 0; x < HEAD_NC; ++x) T.acc0[x] *= corr;
                 T.m = pm;
               }
               f = expf(pm - T.m);
               T.l = fmaf(pl, f, T.l);
             }
 #pragma unroll
-            for (int x = 0; x < EA_NC; ++x) {
-              if (MODE == 0) T.acc0[x] = fmaf(part[src * EA_NC + x], f, T.acc0[x]);
-              else T.acc0[x] += part[src * EA_NC + x];
-              if (MODE == 2) T.acc1[x] += part[(EA_THREADS + src) * EA_NC + x];
+            for (int x = 0; x < HEAD_NC; ++x) {
+              if (MODE == 0) T.acc0[x] = fmaf(part[src * HEAD_NC + x], f, T.acc0[x]);
+              else T.acc0[x] += part[src * HEAD_NC + x];
+              if (MODE == 2) T.acc1[x] += part[(HEAD_THREADS + src) * HEAD_NC + x];
             }
           }
         }
@@ -325,43 +284,32 @@ __global__ void __launch_bounds__(EA_THREADS) k_edge_attn(const EAArgs A) {
   }
 }
 
-bool ea_supported(int heads, int head_dim) {
-  return heads >= 1 && head_dim >= 1 && (int64_t)heads * head_dim <= EA_MAX_WIDTH;
-}
-
 template <int MODE>
 int launch_walk(EAArgs A, hipStream_t st) {
-  const void* ptrs[] = {A.q, A.k, A.v, A.e, A.go, A.out, A.g0, A.g1};
-  bool vec = A.C % 4 == 0;
-  for (const void* p : ptrs) vec = vec && aligned16(p);  // (NULL counts as aligned)
-  const int VEC = vec ? 4 : 1;
-  const int need = (A.C + VEC - 1) / VEC;                // lanes a head asks for
-  A.G = pow2_lanes(need, true);
-  A.UPB = EA_THREADS / A.G;
-  A.NP = (need + A.G - 1) / A.G;                         // <= 2 (VEC = 4), <= 8 (VEC = 1) for C <= 512
+  const int VEC = lane_layout(A.C, {A.q, A.k, A.v, A.e, A.go, A.out, A.g0, A.g1}, A.G, A.UPB, A.NP);
   const unsigned nb = capped_grid(A.rows * A.Hd, A.UPB, 16384);
-  dispatch_vec(VEC, [&](auto v) { k_edge_attn<decltype(v)::value, MODE><<<nb, EA_THREADS, 0, st>>>(A); });
+  dispatch_vec(VEC, [&](auto v) { k_edge_attn<decltype(v)::value, MODE><<<nb, HEAD_THREADS, 0, st>>>(A); });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
 
 int check_common(int64_t Nd, int64_t Ns, int64_t E, int heads, int head_dim) {
   if (!check_csr_sizes({Nd, Ns, E}) || heads < 1 || head_dim < 1) return HSCN_E_BADARG;
-  if (!ea_supported(heads, head_dim)) return HSCN_E_UNSUPPORTED;
+  if (!head_walk_supported(heads, head_dim)) return HSCN_E_UNSUPPORTED;
   return 0;
 }
 
 void set_shape(EAArgs& A, int64_t rows, int64_t cols, int64_t E, int heads, int head_dim) {
   A.rows = rows, A.cols = cols, A.E = E;
   A.Hd = heads, A.C = head_dim, A.HC = heads * head_dim;
-  A.scale = 1.0f / sqrtf((float)head_dim);
+  A.scale = head_scale(head_dim);
 }
 
 }  // namespace
 
 extern "C" {
 
-int hscn_edge_attn_supported(int heads, int head_dim) { return ea_supported(heads, head_dim) ? 1 : 0; }
+int hscn_edge_attn_supported(int heads, int head_dim) { return head_walk_supported(heads, head_dim) ? 1 : 0; }
 int hscn_edge_attn_long_row(void) { return ROW_WALK_LONG_ROW; }
 int hscn_edge_attn_chunk(void) { return ROW_WALK_CHUNK; }
 

@@ -11,9 +11,10 @@
 // row tau of the table e_type [T, Hd*C] (T <= 10 rows that all expander / virtual edges share; they stay in L1 / L2).
 // Every slot goes through eid[slot] first, as in edge_attention.hip.  Every listed edge counts (loops, repeats).
 //
-// Layout, lane groups, VEC and the 8 floats a lane holds per operand are those of csrc/edge_attention.hip; long rows
-// use the two-phase scheme of csrc/row_walk.h with its two constants (a virtual node's in-row is a whole graph: long
-// rows are the normal case here).  The skeleton is spelt here once more, as row_walk.h explains.
+// Layout, lane groups, VEC and the 8 floats a lane holds per operand are the head-unit layer of csrc/row_walk.h (shared
+// with csrc/edge_attention.hip); long rows use the two-phase scheme of the same file with its two constants (a virtual
+// node's in-row is a whole graph: long rows are the normal case here).  The skeleton is spelt here once more, as
+// row_walk.h explains.
 //
 // One kernel, three walks (k_exph_attn<VEC, MODE>):
 //   MODE 0, target-keyed CSR (forward):  stores out and ONE float per (row, head), Z_i.  w <= e^5, so a row of 2^20
@@ -35,13 +36,9 @@
 // depend on the type's slots in list order alone, not on the grid.  A type without slots gets exact zeros.
 // Owner-computes everywhere, no float atomics: the same input gives the same bits.
 #include "row_walk.h"
-#include <math.h>
 
 namespace {
 
-constexpr int XA_THREADS = 256;
-constexpr int XA_MAX_WIDTH = 512;        // heads * head_dim
-constexpr int XA_NC = 8;                 // floats a lane holds of one operand row: (8 / VEC) passes of VEC columns
 constexpr int XA_MAX_TYPES = 10;         // 2 + 2 * nv, nv <= 4
 constexpr int EXPH_TYPE_LONG_ROW = 64;   // types with MORE slots than this are split (hscn_exph_type_long_row)
 constexpr int EXPH_TYPE_CHUNK = 64;      // slots per chunk of a split type (hscn_exph_type_chunk)
@@ -75,84 +72,49 @@ struct XAArgs {
   int32_t* flag;
 };
 
-// pass p gives lane lg of a group the columns [c, c + VEC), c = (p * G + lg) * VEC; only p < NP is visited and a lane
-// with c >= C idles (C % VEC == 0, so a vector never straddles the end of a head)
-template <int VEC>
-__device__ __forceinline__ void load_cols(int G, int NP, int C, const float* row, int lg, float (&x)[XA_NC]) {
-  using V = GV<VEC>;
-#pragma unroll
-  for (int i = 0; i < XA_NC; ++i) x[i] = 0.f;
-#pragma unroll
-  for (int p = 0; p < XA_NC / VEC; ++p) {
-    const int c = (p * G + lg) * VEC;
-    if (p < NP && c < C) {
-      const typename V::T t = V::load(row + c);
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) x[p * VEC + u] = V::get(t, u);
-    }
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_cols(int G, int NP, int C, float* row, int lg, const float (&x)[XA_NC]) {
-  using V = GV<VEC>;
-#pragma unroll
-  for (int p = 0; p < XA_NC / VEC; ++p) {
-    const int c = (p * G + lg) * VEC;
-    if (p < NP && c < C) V::store(row + c, V::make(&x[p * VEC]));
-  }
-}
-
-__device__ __forceinline__ float dot8(const float (&a)[XA_NC], const float (&b)[XA_NC]) {
-  float s = 0.f;                     // (columns a lane does not own hold zeros)
-#pragma unroll
-  for (int i = 0; i < XA_NC; ++i) s = fmaf(a[i], b[i], s);
-  return s;
-}
-
 // the logit of one slot from q and (k * e), the product rounded first: every pass and the table kernel call this with
 // the same lane layout, so they see the same bits
-__device__ __forceinline__ float logit(const float (&q)[XA_NC], const float (&ke)[XA_NC], int G, float scale) {
-  return group_sum(dot8(q, ke), G) * scale;
+__device__ __forceinline__ float logit(const float (&q)[HEAD_NC], const float (&ke)[HEAD_NC], int G, float scale) {
+  return group_sum(rw_dot8(q, ke), G) * scale;
 }
 __device__ __forceinline__ float weight_of(float s) { return expf(fminf(fmaxf(s, -XA_CLAMP), XA_CLAMP)); }
 __device__ __forceinline__ float gate_of(float s) { return (s > -XA_CLAMP && s < XA_CLAMP) ? 1.f : 0.f; }
 
 // what a lane keeps of its (row, head) while it walks the slots
 struct UnitCtx {
-  float a[XA_NC];    // MODE 0, 1: q_i;  MODE 2: k_j
-  float b[XA_NC];    // MODE 1: dout_i;  MODE 2: v_j
+  float a[HEAD_NC];    // MODE 0, 1: q_i;  MODE 2: k_j
+  float b[HEAD_NC];    // MODE 1: dout_i;  MODE 2: v_j
   float r, delta;    // MODE 1
 };
 
 // the running state of a walk: MODE 0 (l = Z, acc0); MODE 1 acc0 = dq; MODE 2 acc0 = dk, acc1 = dv
 struct UnitAcc {
   float l;
-  float acc0[XA_NC];
-  float acc1[XA_NC];
+  float acc0[HEAD_NC];
+  float acc1[HEAD_NC];
 };
 
 __device__ __forceinline__ void acc_clear(UnitAcc& S) {
   S.l = 0.f;
 #pragma unroll
-  for (int i = 0; i < XA_NC; ++i) S.acc0[i] = S.acc1[i] = 0.f;
+  for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] = S.acc1[i] = 0.f;
 }
 
 template <int VEC, int MODE>
 __device__ __forceinline__ void unit_begin(const XAArgs& A, int64_t r, int h, int lg, UnitCtx& U) {
   const size_t at = (size_t)r * A.HC + (size_t)h * A.C;
   if (MODE == 0) {
-    load_cols<VEC>(A.G, A.NP, A.C, A.q + at, lg, U.a);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.q + at, lg, U.a);
   } else if (MODE == 1) {
-    float o[XA_NC];
-    load_cols<VEC>(A.G, A.NP, A.C, A.q + at, lg, U.a);
-    load_cols<VEC>(A.G, A.NP, A.C, A.go + at, lg, U.b);
-    load_cols<VEC>(A.G, A.NP, A.C, A.out + at, lg, o);
-    U.delta = group_sum(dot8(U.b, o), A.G);
+    float o[HEAD_NC];
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.q + at, lg, U.a);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.go + at, lg, U.b);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.out + at, lg, o);
+    U.delta = group_sum(rw_dot8(U.b, o), A.G);
     U.r = 1.0f / (A.z[(size_t)r * A.Hd + h] + XA_EPS);
   } else {
-    load_cols<VEC>(A.G, A.NP, A.C, A.k + at, lg, U.a);
-    load_cols<VEC>(A.G, A.NP, A.C, A.v + at, lg, U.b);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.k + at, lg, U.a);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.v + at, lg, U.b);
   }
 }
 
@@ -187,7 +149,7 @@ __device__ __forceinline__ void slot_rows(const XAArgs& A, SlotIdx<AH>& I) {
 // what a lane holds of AH slots: the feature rows, MODE 0 / 1 k_j and v_j, MODE 2 q_i and dout_i with Z_i and delta_i
 template <int AH>
 struct SlotData {
-  float ee[AH][XA_NC], x0[AH][XA_NC], x1[AH][XA_NC], zz[AH], dd[AH];
+  float ee[AH][HEAD_NC], x0[AH][HEAD_NC], x1[AH][HEAD_NC], zz[AH], dd[AH];
 };
 
 template <int VEC, int MODE, int AH>
@@ -200,9 +162,9 @@ __device__ __forceinline__ void batch_load(const XAArgs& A, int h, int lg, SlotI
     const int er = I.er[u];
     const float* erp = er < A.El ? A.e_edge + (size_t)er * A.HC : A.e_type + (size_t)(er - A.El) * A.HC;
     const size_t nj = (size_t)I.j[u] * A.HC + hoff;
-    load_cols<VEC>(A.G, A.NP, A.C, erp + hoff, lg, D.ee[u]);
-    load_cols<VEC>(A.G, A.NP, A.C, (MODE == 2 ? A.q : A.k) + nj, lg, D.x0[u]);
-    load_cols<VEC>(A.G, A.NP, A.C, (MODE == 2 ? A.go : A.v) + nj, lg, D.x1[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, erp + hoff, lg, D.ee[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, (MODE == 2 ? A.q : A.k) + nj, lg, D.x0[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, (MODE == 2 ? A.go : A.v) + nj, lg, D.x1[u]);
     if (MODE == 2) D.zz[u] = A.z[(size_t)I.j[u] * A.Hd + h], D.dd[u] = A.delta[(size_t)I.j[u] * A.Hd + h];
   }
 }
@@ -219,36 +181,36 @@ __device__ __forceinline__ void batch_accumulate(const XAArgs& A, const UnitCtx&
     }
     if (MODE == 0) {
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) D.x0[u][i] *= D.ee[u][i];
+      for (int i = 0; i < HEAD_NC; ++i) D.x0[u][i] *= D.ee[u][i];
       const float w = weight_of(logit(U.a, D.x0[u], A.G, A.scale));
       S.l += w;
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) S.acc0[i] = fmaf(w, D.x1[u][i], S.acc0[i]);
+      for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] = fmaf(w, D.x1[u][i], S.acc0[i]);
     } else if (MODE == 1) {
-      float ke[XA_NC];
+      float ke[HEAD_NC];
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) ke[i] = D.x0[u][i] * D.ee[u][i];
+      for (int i = 0; i < HEAD_NC; ++i) ke[i] = D.x0[u][i] * D.ee[u][i];
       const float sc = logit(U.a, ke, A.G, A.scale);
-      const float dp = group_sum(dot8(U.b, D.x1[u]), A.G);
+      const float dp = group_sum(rw_dot8(U.b, D.x1[u]), A.G);
       const float ds = weight_of(sc) * U.r * (dp - U.delta) * gate_of(sc) * A.scale;
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) S.acc0[i] = fmaf(ds, ke[i], S.acc0[i]);
+      for (int i = 0; i < HEAD_NC; ++i) S.acc0[i] = fmaf(ds, ke[i], S.acc0[i]);
       if (A.g1 && I.er[u] < A.El) {                        // a row of e_edge: this slot is its one writer
-        float de[XA_NC];
+        float de[HEAD_NC];
 #pragma unroll
-        for (int i = 0; i < XA_NC; ++i) de[i] = ds * (U.a[i] * D.x0[u][i]);
-        store_cols<VEC>(A.G, A.NP, A.C, A.g1 + (size_t)I.er[u] * A.HC + hoff, lg, de);
+        for (int i = 0; i < HEAD_NC; ++i) de[i] = ds * (U.a[i] * D.x0[u][i]);
+        rw_store_cols<VEC>(A.G, A.NP, A.C, A.g1 + (size_t)I.er[u] * A.HC + hoff, lg, de);
       }
     } else {                                               // (j is the target here, the row is the source)
-      float ke[XA_NC];
+      float ke[HEAD_NC];
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) ke[i] = U.a[i] * D.ee[u][i];
+      for (int i = 0; i < HEAD_NC; ++i) ke[i] = U.a[i] * D.ee[u][i];
       const float sc = logit(D.x0[u], ke, A.G, A.scale);
-      const float dp = group_sum(dot8(D.x1[u], U.b), A.G);
+      const float dp = group_sum(rw_dot8(D.x1[u], U.b), A.G);
       const float wr = weight_of(sc) * (1.0f / (D.zz[u] + XA_EPS));
       const float ds = wr * (dp - D.dd[u]) * gate_of(sc) * A.scale;
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) {
+      for (int i = 0; i < HEAD_NC; ++i) {
         S.acc0[i] = fmaf(ds, D.x0[u][i] * D.ee[u][i], S.acc0[i]);
         S.acc1[i] = fmaf(wr, D.x1[u][i], S.acc1[i]);
       }
@@ -291,26 +253,26 @@ template <int VEC, int MODE>
 __device__ __forceinline__ void unit_finish(const XAArgs& A, const UnitCtx& U, int64_t r, int h, int lg, const UnitAcc& S) {
   const size_t at = (size_t)r * A.HC + (size_t)h * A.C;
   if (MODE == 0) {
-    float o[XA_NC];
+    float o[HEAD_NC];
     const float inv = 1.0f / (S.l + XA_EPS);
 #pragma unroll
-    for (int i = 0; i < XA_NC; ++i) o[i] = S.acc0[i] * inv;
-    store_cols<VEC>(A.G, A.NP, A.C, A.out + at, lg, o);
+    for (int i = 0; i < HEAD_NC; ++i) o[i] = S.acc0[i] * inv;
+    rw_store_cols<VEC>(A.G, A.NP, A.C, A.out + at, lg, o);
     if (lg == 0) A.z[(size_t)r * A.Hd + h] = S.l;
   } else if (MODE == 1) {
     if (lg == 0) A.delta[(size_t)r * A.Hd + h] = U.delta;
-    if (A.g0) store_cols<VEC>(A.G, A.NP, A.C, A.g0 + at, lg, S.acc0);
+    if (A.g0) rw_store_cols<VEC>(A.G, A.NP, A.C, A.g0 + at, lg, S.acc0);
   } else {
-    if (A.g0) store_cols<VEC>(A.G, A.NP, A.C, A.g0 + at, lg, S.acc0);
-    if (A.g1) store_cols<VEC>(A.G, A.NP, A.C, A.g1 + at, lg, S.acc1);
+    if (A.g0) rw_store_cols<VEC>(A.G, A.NP, A.C, A.g0 + at, lg, S.acc0);
+    if (A.g1) rw_store_cols<VEC>(A.G, A.NP, A.C, A.g1 + at, lg, S.acc1);
   }
 }
 
 template <int VEC, int MODE>
-__global__ void __launch_bounds__(XA_THREADS) k_exph_attn(const XAArgs A) {
+__global__ void __launch_bounds__(HEAD_THREADS) k_exph_attn(const XAArgs A) {
   constexpr int NACC = MODE == 2 ? 2 : 1;
-  __shared__ float part[NACC * XA_THREADS * XA_NC];      // chunk partials of a long row, [accumulator][thread][XA_NC]
-  __shared__ float part_l[XA_THREADS];
+  __shared__ float part[NACC * HEAD_THREADS * HEAD_NC];  // chunk partials of a long row, [accumulator][thread][HEAD_NC]
+  __shared__ float part_l[HEAD_THREADS];
   const bool walk = MODE != 1 || A.walk != 0;
   const int ul = threadIdx.x / A.G;                      // unit of this lane group within the workgroup's tile
   const int lg = threadIdx.x - ul * A.G;
@@ -362,9 +324,9 @@ __global__ void __launch_bounds__(XA_THREADS) k_exph_attn(const XAArgs A) {
           acc_clear(S);
           walk_slots<VEC, MODE>(A, U, h, lg, cs, ct, S);
 #pragma unroll
-          for (int x = 0; x < XA_NC; ++x) {
-            part[threadIdx.x * XA_NC + x] = S.acc0[x];
-            if (MODE == 2) part[(XA_THREADS + threadIdx.x) * XA_NC + x] = S.acc1[x];
+          for (int x = 0; x < HEAD_NC; ++x) {
+            part[threadIdx.x * HEAD_NC + x] = S.acc0[x];
+            if (MODE == 2) part[(HEAD_THREADS + threadIdx.x) * HEAD_NC + x] = S.acc1[x];
           }
           if (MODE == 0) part_l[threadIdx.x] = S.l;
         }
@@ -375,9 +337,9 @@ __global__ void __launch_bounds__(XA_THREADS) k_exph_attn(const XAArgs A) {
             const int src = g * A.G + lg;
             if (MODE == 0) T.l += part_l[src];
 #pragma unroll
-            for (int x = 0; x < XA_NC; ++x) {
-              T.acc0[x] += part[src * XA_NC + x];
-              if (MODE == 2) T.acc1[x] += part[(XA_THREADS + src) * XA_NC + x];
+            for (int x = 0; x < HEAD_NC; ++x) {
+              T.acc0[x] += part[src * HEAD_NC + x];
+              if (MODE == 2) T.acc1[x] += part[(HEAD_THREADS + src) * HEAD_NC + x];
             }
           }
         }
@@ -426,8 +388,8 @@ __device__ __forceinline__ void type_range(const XTArgs& A, int tau, int& s, int
 // edge ids, then their ends, then the four rows of every slot are in flight together).  A slot with an edge id or an
 // end out of range reads row 0, adds nothing and sets bit 1 (hscn_csr_build left that edge out of both CSRs as well).
 template <int VEC, int AH>
-__device__ __forceinline__ void type_batch(const XTArgs& A, int h, int lg, int p, const float (&ee)[XA_NC],
-                                           float (&acc)[XA_NC]) {
+__device__ __forceinline__ void type_batch(const XTArgs& A, int h, int lg, int p, const float (&ee)[HEAD_NC],
+                                           float (&acc)[HEAD_NC]) {
   const size_t hoff = (size_t)h * A.C;
   int kx[AH];
   int64_t i[AH], j[AH];
@@ -439,15 +401,15 @@ __device__ __forceinline__ void type_batch(const XTArgs& A, int h, int lg, int p
     ok[u] = kx[u] >= 0 && kx[u] < A.E;
     j[u] = A.src[ok[u] ? kx[u] : 0], i[u] = A.dst[ok[u] ? kx[u] : 0];
   }
-  float qq[AH][XA_NC], gg[AH][XA_NC], kk[AH][XA_NC], vv[AH][XA_NC], zz[AH], dd[AH];
+  float qq[AH][HEAD_NC], gg[AH][HEAD_NC], kk[AH][HEAD_NC], vv[AH][HEAD_NC], zz[AH], dd[AH];
 #pragma unroll
   for (int u = 0; u < AH; ++u) {
     ok[u] = ok[u] && j[u] >= 0 && j[u] < A.N && i[u] >= 0 && i[u] < A.N;
     if (!ok[u]) i[u] = j[u] = 0;
-    load_cols<VEC>(A.G, A.NP, A.C, A.q + (size_t)i[u] * A.HC + hoff, lg, qq[u]);
-    load_cols<VEC>(A.G, A.NP, A.C, A.go + (size_t)i[u] * A.HC + hoff, lg, gg[u]);
-    load_cols<VEC>(A.G, A.NP, A.C, A.k + (size_t)j[u] * A.HC + hoff, lg, kk[u]);
-    load_cols<VEC>(A.G, A.NP, A.C, A.v + (size_t)j[u] * A.HC + hoff, lg, vv[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.q + (size_t)i[u] * A.HC + hoff, lg, qq[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.go + (size_t)i[u] * A.HC + hoff, lg, gg[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.k + (size_t)j[u] * A.HC + hoff, lg, kk[u]);
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.v + (size_t)j[u] * A.HC + hoff, lg, vv[u]);
     zz[u] = A.z[(size_t)i[u] * A.Hd + h], dd[u] = A.delta[(size_t)i[u] * A.Hd + h];
   }
 #pragma unroll
@@ -456,20 +418,20 @@ __device__ __forceinline__ void type_batch(const XTArgs& A, int h, int lg, int p
       atomicOr(A.flag, 2);
       continue;
     }
-    float ke[XA_NC];
+    float ke[HEAD_NC];
 #pragma unroll
-    for (int x = 0; x < XA_NC; ++x) ke[x] = kk[u][x] * ee[x];
+    for (int x = 0; x < HEAD_NC; ++x) ke[x] = kk[u][x] * ee[x];
     const float sc = logit(qq[u], ke, A.G, A.scale);
-    const float dp = group_sum(dot8(gg[u], vv[u]), A.G);
+    const float dp = group_sum(rw_dot8(gg[u], vv[u]), A.G);
     const float ds = weight_of(sc) * (1.0f / (zz[u] + XA_EPS)) * (dp - dd[u]) * gate_of(sc) * A.scale;
 #pragma unroll
-    for (int x = 0; x < XA_NC; ++x) acc[x] = fmaf(ds, qq[u][x] * kk[u][x], acc[x]);
+    for (int x = 0; x < HEAD_NC; ++x) acc[x] = fmaf(ds, qq[u][x] * kk[u][x], acc[x]);
   }
 }
 
 // lane group (cu, h): chunk cu of the list's chunks, counted type by type -> one partial [C] at part[cu, h]
 template <int VEC>
-__global__ void __launch_bounds__(XA_THREADS) k_exph_type_partial(const XTArgs A) {
+__global__ void __launch_bounds__(HEAD_THREADS) k_exph_type_partial(const XTArgs A) {
   const int ul = threadIdx.x / A.G;
   const int lg = threadIdx.x - ul * A.G;
   const int64_t units = A.max_chunks * A.Hd;
@@ -492,20 +454,20 @@ __global__ void __launch_bounds__(XA_THREADS) k_exph_type_partial(const XTArgs A
     }
     if (tau < 0) continue;                                // past the last chunk of the last type
     const size_t hoff = (size_t)h * A.C;
-    float ee[XA_NC], acc[XA_NC];
-    load_cols<VEC>(A.G, A.NP, A.C, A.e_type + (size_t)tau * A.HC + hoff, lg, ee);
+    float ee[HEAD_NC], acc[HEAD_NC];
+    rw_load_cols<VEC>(A.G, A.NP, A.C, A.e_type + (size_t)tau * A.HC + hoff, lg, ee);
 #pragma unroll
-    for (int i = 0; i < XA_NC; ++i) acc[i] = 0.f;
+    for (int i = 0; i < HEAD_NC; ++i) acc[i] = 0.f;
     int p = cs;
     for (; p + XA_AHEAD <= ct; p += XA_AHEAD) type_batch<VEC, XA_AHEAD>(A, h, lg, p, ee, acc);
     for (; p < ct; ++p) type_batch<VEC, 1>(A, h, lg, p, ee, acc);
-    store_cols<VEC>(A.G, A.NP, A.C, A.part + (size_t)cu * A.HC + hoff, lg, acc);
+    rw_store_cols<VEC>(A.G, A.NP, A.C, A.part + (size_t)cu * A.HC + hoff, lg, acc);
   }
 }
 
 // lane group (tau, h): the type's partials added in chunk order, from zero
 template <int VEC>
-__global__ void __launch_bounds__(XA_THREADS) k_exph_type_combine(const XTArgs A) {
+__global__ void __launch_bounds__(HEAD_THREADS) k_exph_type_combine(const XTArgs A) {
   const int ul = threadIdx.x / A.G;
   const int lg = threadIdx.x - ul * A.G;
   const int64_t units = (int64_t)A.T * A.Hd;
@@ -525,51 +487,36 @@ __global__ void __launch_bounds__(XA_THREADS) k_exph_type_combine(const XTArgs A
       nc = 0;
     }
     const size_t hoff = (size_t)h * A.C;
-    float tot[XA_NC];
+    float tot[HEAD_NC];
 #pragma unroll
-    for (int i = 0; i < XA_NC; ++i) tot[i] = 0.f;
+    for (int i = 0; i < HEAD_NC; ++i) tot[i] = 0.f;
     int c = 0;
     for (; c + 16 <= nc; c += 16) {                       // sixteen partials in flight, added in chunk order
-      float pp[16][XA_NC];
+      float pp[16][HEAD_NC];
 #pragma unroll
-      for (int u = 0; u < 16; ++u) load_cols<VEC>(A.G, A.NP, A.C, A.part + (size_t)(base + c + u) * A.HC + hoff, lg, pp[u]);
+      for (int u = 0; u < 16; ++u)
+        rw_load_cols<VEC>(A.G, A.NP, A.C, A.part + (size_t)(base + c + u) * A.HC + hoff, lg, pp[u]);
 #pragma unroll
       for (int u = 0; u < 16; ++u)
 #pragma unroll
-        for (int i = 0; i < XA_NC; ++i) tot[i] += pp[u][i];
+        for (int i = 0; i < HEAD_NC; ++i) tot[i] += pp[u][i];
     }
     for (; c < nc; ++c) {
-      float pp[XA_NC];
-      load_cols<VEC>(A.G, A.NP, A.C, A.part + (size_t)(base + c) * A.HC + hoff, lg, pp);
+      float pp[HEAD_NC];
+      rw_load_cols<VEC>(A.G, A.NP, A.C, A.part + (size_t)(base + c) * A.HC + hoff, lg, pp);
 #pragma unroll
-      for (int i = 0; i < XA_NC; ++i) tot[i] += pp[i];
+      for (int i = 0; i < HEAD_NC; ++i) tot[i] += pp[i];
     }
-    store_cols<VEC>(A.G, A.NP, A.C, A.de_type + (size_t)tau * A.HC + hoff, lg, tot);
+    rw_store_cols<VEC>(A.G, A.NP, A.C, A.de_type + (size_t)tau * A.HC + hoff, lg, tot);
   }
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-bool xa_supported(int heads, int head_dim) {
-  return heads >= 1 && head_dim >= 1 && (int64_t)heads * head_dim <= XA_MAX_WIDTH;
-}
-
-// VEC, G, UPB, NP for a head of width C: `ptrs` are the float tensors the launch touches (NULL counts as aligned)
-int lane_layout(int C, std::initializer_list<const void*> ptrs, int& G, int& UPB, int& NP) {
-  bool vec = C % 4 == 0;
-  for (const void* p : ptrs) vec = vec && aligned16(p);
-  const int VEC = vec ? 4 : 1;
-  const int need = (C + VEC - 1) / VEC;                  // lanes a head asks for
-  G = pow2_lanes(need, true);
-  UPB = XA_THREADS / G;
-  NP = (need + G - 1) / G;                               // <= 2 (VEC = 4), <= 8 (VEC = 1) for C <= 512
-  return VEC;
-}
-
 template <int MODE>
 int launch_walk(XAArgs A, hipStream_t st) {
   const int VEC = lane_layout(A.C, {A.q, A.k, A.v, A.e_edge, A.e_type, A.go, A.out, A.g0, A.g1}, A.G, A.UPB, A.NP);
   const unsigned nb = capped_grid(A.rows * A.Hd, A.UPB, 16384);
-  dispatch_vec(VEC, [&](auto v) { k_exph_attn<decltype(v)::value, MODE><<<nb, XA_THREADS, 0, st>>>(A); });
+  dispatch_vec(VEC, [&](auto v) { k_exph_attn<decltype(v)::value, MODE><<<nb, HEAD_THREADS, 0, st>>>(A); });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }
@@ -577,14 +524,14 @@ int launch_walk(XAArgs A, hipStream_t st) {
 int check_common(int64_t N, int64_t E, int64_t El, int T, int heads, int head_dim) {
   if (!check_csr_sizes({N, E, El}) || heads < 1 || head_dim < 1 || T < 1) return HSCN_E_BADARG;
   if (El + T > INT32_MAX) return HSCN_E_BADARG;
-  if (!xa_supported(heads, head_dim) || T > XA_MAX_TYPES) return HSCN_E_UNSUPPORTED;
+  if (!head_walk_supported(heads, head_dim) || T > XA_MAX_TYPES) return HSCN_E_UNSUPPORTED;
   return 0;
 }
 
 void set_shape(XAArgs& A, int64_t N, int64_t E, int64_t El, int T, int heads, int head_dim) {
   A.rows = N, A.E = E, A.El = El, A.T = T;
   A.Hd = heads, A.C = head_dim, A.HC = heads * head_dim;
-  A.scale = 1.0f / sqrtf((float)head_dim);
+  A.scale = head_scale(head_dim);
 }
 
 int64_t type_max_chunks(int64_t E, int T) { return E / EXPH_TYPE_CHUNK + T; }
@@ -593,7 +540,7 @@ int64_t type_max_chunks(int64_t E, int T) { return E / EXPH_TYPE_CHUNK + T; }
 
 extern "C" {
 
-int hscn_exph_attn_supported(int heads, int head_dim) { return xa_supported(heads, head_dim) ? 1 : 0; }
+int hscn_exph_attn_supported(int heads, int head_dim) { return head_walk_supported(heads, head_dim) ? 1 : 0; }
 int hscn_exph_attn_long_row(void) { return ROW_WALK_LONG_ROW; }
 int hscn_exph_attn_chunk(void) { return ROW_WALK_CHUNK; }
 int hscn_exph_type_long_row(void) { return EXPH_TYPE_LONG_ROW; }
@@ -674,15 +621,15 @@ int hscn_exph_attn_bwd_type(const int32_t* trowptr, const int32_t* titem, const 
   A.part = static_cast<float*>(workspace), A.de_type = de_type;
   A.N = N, A.E = E, A.max_chunks = type_max_chunks(E, T);
   A.T = T, A.Hd = heads, A.C = head_dim, A.HC = heads * head_dim;
-  A.scale = 1.0f / sqrtf((float)head_dim);
+  A.scale = head_scale(head_dim);
   A.flag = flag;
   const int VEC = lane_layout(A.C, {A.q, A.k, A.v, A.e_type, A.go, A.part, A.de_type}, A.G, A.UPB, A.NP);
   hipStream_t st = hscn_stream(stream_);
   const unsigned nb = capped_grid(A.max_chunks * A.Hd, A.UPB, 16384);
-  dispatch_vec(VEC, [&](auto v) { k_exph_type_partial<decltype(v)::value><<<nb, XA_THREADS, 0, st>>>(A); });
+  dispatch_vec(VEC, [&](auto v) { k_exph_type_partial<decltype(v)::value><<<nb, HEAD_THREADS, 0, st>>>(A); });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   const unsigned nc = capped_grid((int64_t)T * A.Hd, A.UPB, 16384);
-  dispatch_vec(VEC, [&](auto v) { k_exph_type_combine<decltype(v)::value><<<nc, XA_THREADS, 0, st>>>(A); });
+  dispatch_vec(VEC, [&](auto v) { k_exph_type_combine<decltype(v)::value><<<nc, HEAD_THREADS, 0, st>>>(A); });
   HSCN_RETURN_IF_LAUNCH_FAILED();
   return 0;
 }

@@ -19,14 +19,17 @@
 // in the tile, rowptr of that row, the pass, the round), and everything lane-dependent (member, live, c < chunks,
 // lane group 0) is tested inside them.
 //
-// Each of the three kernels spells this skeleton itself: as one inlined function template the same statements reach
-// the backend in another order, and it then allocates k_gine_walk<4, 4, 1> 73 VGPRs instead of 71, one occupancy step
-// less (profiles/row_walk_driver_resources.txt).
+// Each of the three kernels, and k_exph_attn (exphormer.hip) as the fourth, spells this skeleton itself: as one inlined
+// function template the same statements reach the backend in another order, and it then allocates
+// k_gine_walk<4, 4, 1> 73 VGPRs instead of 71, one occupancy step less (profiles/row_walk_driver_resources.txt).
+// What k_edge_attn and k_exph_attn do share is the head-unit layer at the end of this file: the constants, the column
+// helpers and the lane layout of a (row, head) unit (profiles/head_walk_resources.txt: all their kernels unchanged).
 // csrc/catenc.hip has a LONG_ROW / CHUNK pair of its own for a different scheme (a second combine kernel, a look-ahead
 // window).
 #pragma once
 #include "hscn_common.h"
 #include <initializer_list>
+#include <math.h>
 #include <type_traits>
 
 constexpr int ROW_WALK_LONG_ROW = 256;   // rows with MORE slots than this are split (hscn_*_long_row)
@@ -88,3 +91,66 @@ static inline void dispatch_vec(int VEC, F&& f) {
   if (VEC == 4) f(std::integral_constant<int, 4>{});
   else f(std::integral_constant<int, 1>{});
 }
+
+// ---- the head-unit layer: a (row, head) unit walked by a lane group (edge_attention.hip, exphormer.hip) -----------
+// One (row, head) is owned by G consecutive lanes (G a power of two, at most 64), VEC = 4 columns per lane and pass
+// (16-byte accesses) where C % 4 == 0 and every pointer is 16-byte aligned, VEC = 1 otherwise; a head wider than
+// G * VEC takes NP <= HEAD_NC / VEC passes, all of them held in registers.
+constexpr int HEAD_THREADS = 256;
+constexpr int HEAD_MAX_WIDTH = 512;  // heads * head_dim
+constexpr int HEAD_NC = 8;           // floats a lane holds of one operand row: (8 / VEC) passes of VEC columns
+
+// pass p gives lane lg of a group the columns [c, c + VEC), c = (p * G + lg) * VEC; only p < NP is visited and a lane
+// with c >= C idles (C % VEC == 0, so a vector never straddles the end of a head)
+template <int VEC>
+__device__ __forceinline__ void rw_load_cols(int G, int NP, int C, const float* row, int lg, float (&x)[HEAD_NC]) {
+  using V = GV<VEC>;
+#pragma unroll
+  for (int i = 0; i < HEAD_NC; ++i) x[i] = 0.f;
+#pragma unroll
+  for (int p = 0; p < HEAD_NC / VEC; ++p) {
+    const int c = (p * G + lg) * VEC;
+    if (p < NP && c < C) {
+      const typename V::T t = V::load(row + c);
+#pragma unroll
+      for (int u = 0; u < VEC; ++u) x[p * VEC + u] = V::get(t, u);
+    }
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void rw_store_cols(int G, int NP, int C, float* row, int lg, const float (&x)[HEAD_NC]) {
+  using V = GV<VEC>;
+#pragma unroll
+  for (int p = 0; p < HEAD_NC / VEC; ++p) {
+    const int c = (p * G + lg) * VEC;
+    if (p < NP && c < C) V::store(row + c, V::make(&x[p * VEC]));
+  }
+}
+
+__device__ __forceinline__ float rw_dot8(const float (&a)[HEAD_NC], const float (&b)[HEAD_NC]) {
+  float s = 0.f;                     // (columns a lane does not own hold zeros)
+#pragma unroll
+  for (int i = 0; i < HEAD_NC; ++i) s = fmaf(a[i], b[i], s);
+  return s;
+}
+
+// the envelope of both operators (hscn_edge_attn_supported, hscn_exph_attn_supported)
+static inline bool head_walk_supported(int heads, int head_dim) {
+  return heads >= 1 && head_dim >= 1 && (int64_t)heads * head_dim <= HEAD_MAX_WIDTH;
+}
+
+// VEC, G, UPB, NP for a head of width C: `ptrs` are the float tensors the launch touches (NULL counts as aligned)
+static inline int lane_layout(int C, std::initializer_list<const void*> ptrs, int& G, int& UPB, int& NP) {
+  bool vec = C % 4 == 0;
+  for (const void* p : ptrs) vec = vec && aligned16(p);
+  const int VEC = vec ? 4 : 1;
+  const int need = (C + VEC - 1) / VEC;                  // lanes a head asks for
+  G = pow2_lanes(need, true);
+  UPB = HEAD_THREADS / G;
+  NP = (need + G - 1) / G;                               // <= 2 (VEC = 4), <= 8 (VEC = 1) for C <= 512
+  return VEC;
+}
+
+// the logits' scale 1 / sqrt(C)
+static inline float head_scale(int head_dim) { return 1.0f / sqrtf((float)head_dim); }

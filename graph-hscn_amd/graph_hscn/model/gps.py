@@ -4,7 +4,7 @@
   * "graph": ``global_mean_pool -> Linear(D, D) -> activation -> Linear(D, C)`` (HSCN's head shape);
   * "node":  the same two Linears per node, through ``nn.head.NodeHead`` where its kernels apply;
   * "link":  ``embed()`` is the [N, C] output of the two Linears and ``forward`` scores ``batch.edge_label_index`` by
-    ``nn.head.pair_dot``, exactly as ``MPNN`` does.
+    ``nn.head.pair_dot``: ``model/_common.py LinkLevel``, which ``MPNN`` shares.
 
 ``local_conv=None`` is the plain Transformer (with a positional encoding in front: LRGB's "Transformer + LapPE").
 The model takes a homogeneous ``Batch`` and offers the surface ``train.batching`` and ``train.train`` use for one.  It
@@ -22,6 +22,7 @@ from torch import Tensor
 
 from ..config.config import ACT_DICT, GPSConfig
 from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
+from ._common import LinkLevel, check_encoders, check_task_level, float_edge_attr
 from ..nn import functional as Fh
 from ..nn.conv import Linear
 from ..nn.gps import GPSLayer
@@ -53,7 +54,7 @@ class _Table(nn.Module):
         nn.init.normal_(self.weight)
 
 
-class GPS(nn.Module):
+class GPS(LinkLevel, nn.Module):
     layered_only = True      # train.batching.refuse_layered_only: the resident entry points refuse this model by name
 
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
@@ -83,12 +84,8 @@ class GPS(nn.Module):
         categories in place of the Linear node / edge encoder (for "gine" the bond encoder supplies the ``edge_attr``
         the layer's own edge Linear reads).  The defaults build the model as it always was."""
         super().__init__()
-        if node_encoder not in (None,) + tuple(NODE_ENCODERS):
-            raise ValueError(f"node_encoder must be one of {sorted(NODE_ENCODERS)} or None, not {node_encoder!r}")
-        if edge_encoder not in (None,) + tuple(EDGE_ENCODERS):
-            raise ValueError(f"edge_encoder must be one of {sorted(EDGE_ENCODERS)} or None, not {edge_encoder!r}")
-        if task_level not in ("graph", "node", "link"):
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
+        check_encoders(node_encoder, edge_encoder)
+        check_task_level(task_level)
         if num_layers < 1:
             raise ValueError("GPS needs at least one layer")
         if attn_bias not in (None, "spd"):
@@ -179,13 +176,9 @@ class GPS(nn.Module):
         if ea is None:
             raise ValueError(f"the model has edge-aware convolutions (local_conv {self.layers[0].local_conv!r}) and "
                              "the batch carries no edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
-        dev = next(self.parameters()).device
         if self.encoder_kinds[1] is not None:       # int64 categories: the bond encoder checks them itself
             return ea
-        if ea.dtype != torch.float32 or ea.device != dev:
-            raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
-                            f"{ea.device} (train.batching.to_device casts integer bond features)")
-        return ea
+        return float_edge_attr(ea, next(self.parameters()).device)
 
     def _spd(self, batch):
         """The batch's ``SPDBuckets`` at ``spd_max_dist``, built once: kept on the batch object, in a dict that
@@ -207,42 +200,32 @@ class GPS(nn.Module):
             raise RuntimeError("engine='resident' does not take this model: "
                                f"{EXPHORMER_RESIDENT_REASON if self.global_model == 'exphormer' else RESIDENT_REASON}")
         self.last_engine = "layered"
-        if self.global_model == "exphormer":
-            return self._nodes_exphormer(batch)
-        spd = self._spd(batch)                      # once per forward, for all layers (None without attn_bias)
+        sparse = self.global_model == "exphormer"
+        glob = {"spd": self._spd(batch)}            # the global branch's keywords, once per forward for all layers
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
         x = self.node_encoder(batch.x)
         if self.layers[0].updates_edge_attr or self.encoder_kinds[1] is not None:
             edge_attr = self.edge_encoder(edge_attr)
+        if sparse:                                  # the virtual rows travel beside the node rows and stay behind
+            # the local edges' own features reach the attention at width D (see __init__); otherwise they share type 0
+            wide = hasattr(self, "edge_encoder") and self.layers[0].uses_edge_attr
+            own = self.add_local_edges and (wide or hasattr(self, "exph_edge_encoder"))
+            struct = ExphormerStructure.of(batch, self.expander_degree, self.num_virtual_nodes, self.add_local_edges,
+                                           self.expander_seed, edge_features=own)
+            e_static = self.exph_edge_encoder(edge_attr) if own and not wide else None
+            virt = self.virt_node_emb.weight.repeat(struct.num_graphs, 1)  # graph-major: row g nv + t = weight[t]
+            e_type = self.edge_type_emb.weight
         for i, layer in enumerate(self.layers):
             layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
+            if sparse:                              # (a layer that updates the edge features hands on the new ones)
+                glob = {"exph": (struct, virt, (edge_attr if wide else e_static) if own else None, e_type)}
+            out = layer(x, batch.edge_index, batch, edge_attr, **glob)
+            out = out if isinstance(out, tuple) else (out,)                 # h; (h, e); (h, virt); (h, e, virt)
+            x = out[0]
             if layer.updates_edge_attr:             # the layer's new edge features feed the next layer
-                x, edge_attr = layer(x, batch.edge_index, batch, edge_attr, spd=spd)
-            else:
-                x = layer(x, batch.edge_index, batch, edge_attr, spd=spd)
-        return x
-
-    def _nodes_exphormer(self, batch) -> Tensor:
-        """``_nodes`` with the sparse global model: the virtual rows travel beside the node rows and stay behind."""
-        edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
-        x = self.node_encoder(batch.x)
-        if self.layers[0].updates_edge_attr or self.encoder_kinds[1] is not None:
-            edge_attr = self.edge_encoder(edge_attr)
-        # the local edges' own features reach the attention at width D (see __init__); otherwise they share type 0
-        wide = hasattr(self, "edge_encoder") and self.layers[0].uses_edge_attr
-        own = self.add_local_edges and (wide or hasattr(self, "exph_edge_encoder"))
-        struct = ExphormerStructure.of(batch, self.expander_degree, self.num_virtual_nodes, self.add_local_edges,
-                                       self.expander_seed, edge_features=own)
-        e_static = self.exph_edge_encoder(edge_attr) if own and not wide else None
-        virt = self.virt_node_emb.weight.repeat(struct.num_graphs, 1)      # graph-major: row g nv + t = weight[t]
-        e_type = self.edge_type_emb.weight
-        for i, layer in enumerate(self.layers):
-            layer.dropout_seed = None if self.dropout_seed is None else self.dropout_seed + 4 * i
-            e_edge = (edge_attr if wide else e_static) if own else None
-            if layer.updates_edge_attr:             # the layer's new edge features feed the next layer
-                x, edge_attr, virt = layer(x, batch.edge_index, batch, edge_attr, exph=(struct, virt, e_edge, e_type))
-            else:
-                x, virt = layer(x, batch.edge_index, batch, edge_attr, exph=(struct, virt, e_edge, e_type))
+                edge_attr = out[1]
+            if sparse:
+                virt = out[-1]
         return x
 
     def _head(self, x: Tensor) -> Tensor:
@@ -255,19 +238,6 @@ class GPS(nn.Module):
             x = global_mean_pool(x, batch.batch, getattr(batch, "num_graphs", None))
             return self._head(x)
         return self._node_head(x) if self._node_head.supported() else self._head(x)
-
-    def forward(self, batch) -> Tensor:
-        out = self._forward(batch)
-        if self.task_level == "link":
-            from ..nn.head import PairStructure, pair_dot
-            return pair_dot(out, batch.edge_label_index, PairStructure.of(batch, out.size(0)))
-        return out
-
-    def embed(self, batch) -> Tensor:
-        """The [N, C] node embeddings a link-level model scores pairs with."""
-        if self.task_level != "link":
-            raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
-        return self._forward(batch)
 
 
 def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:

@@ -30,6 +30,7 @@ from ..nn.pool import (dmon_pool_sparse, global_mean_pool, mincut_pool_sparse, t
                        to_dense_adj_ragged)
 from ..structure import Relation, relation_of
 from .. import engine as _engine
+from ._common import check_task_level
 
 LL = ("local", "to", "local")
 VV = ("virtual", "to", "virtual")
@@ -322,8 +323,7 @@ class HSCN(nn.Module):
         super().__init__()
         if vl_conv is not None and vl_conv != "GAT":
             raise ValueError(f"vl_conv must be None or 'GAT', not {vl_conv!r} (a bipartite GCNConv does not exist)")
-        if task_level not in ("graph", "node", "link"):
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
+        check_task_level(task_level)
         if heads != 1 and not any(c.lower() == "transformerconv" for c in (lv_conv, ll_conv, vv_conv)):
             raise ValueError(f"heads={heads} needs a relation built as 'TransformerConv'")
         self.vl_conv = vl_conv

@@ -25,9 +25,10 @@ from ..nn.conv import GCNConv, TransformerConv
 from ..nn import functional as Fh
 from ..nn.norm import BatchNorm1d, LayerNorm
 from ..nn.pool import global_mean_pool
+from ._common import LinkLevel, check_encoders, check_task_level, float_edge_attr
 
 
-class MPNN(nn.Module):
+class MPNN(LinkLevel, nn.Module):
     def __init__(self, conv: type, activation: Callable, num_features: int, hidden_channels: int,
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
                  use_layer_norm: bool = False, task_level: str = "graph", node_encoder: Optional[str] = None,
@@ -39,18 +40,15 @@ class MPNN(nn.Module):
         ``task_level`` (extension; the default "graph" is the reference's model): "node" returns the last
         convolution's ``[N, C]`` without the per-graph mean.  "link": ``num_classes`` is the embedding width D,
         ``embed`` is that node-level output and ``forward`` scores the batch's candidate pairs
-        ``batch.edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P].
+        ``batch.edge_label_index`` by the dot product of their embeddings (``nn.head.pair_dot``), giving [P]; both are
+        ``model/_common.py LinkLevel``'s.
 
         ``node_encoder="atom"`` (extension): ``batch.x`` holds int64 categories, an ``AtomEncoder(hidden_channels)``
         embeds them and the first convolution is ``H -> H``.  ``edge_encoder="bond"``: a ``BondEncoder(hidden_channels)``
         embeds the int64 ``batch.edge_attr`` for the edge-aware convolutions.  Either makes the model layered-only."""
         super().__init__()
-        if task_level not in ("graph", "node", "link"):
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', not {task_level!r}")
-        if node_encoder not in (None,) + tuple(NODE_ENCODERS):
-            raise ValueError(f"node_encoder must be one of {sorted(NODE_ENCODERS)} or None, not {node_encoder!r}")
-        if edge_encoder not in (None,) + tuple(EDGE_ENCODERS):
-            raise ValueError(f"edge_encoder must be one of {sorted(EDGE_ENCODERS)} or None, not {edge_encoder!r}")
+        check_task_level(task_level)
+        check_encoders(node_encoder, edge_encoder)
         if edge_encoder is not None and not getattr(conv, "uses_edge_attr", False):
             raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution (conv_type 'gine', "
                              f"'gatedgcn' or 'transformerconv_edge'), not {getattr(conv, '__name__', conv)}")
@@ -181,19 +179,6 @@ class MPNN(nn.Module):
         self._resident_flag = flag     # nonzero: an edge outside its graph / a graph beyond the batch's maxima
         return pred
 
-    def forward(self, batch) -> Tensor:
-        out = self._forward(batch)
-        if self.task_level == "link":                  # one score per candidate pair of the batch
-            from ..nn.head import PairStructure, pair_dot
-            return pair_dot(out, batch.edge_label_index, PairStructure.of(batch, out.size(0)))
-        return out
-
-    def embed(self, batch) -> Tensor:
-        """The [N, D] node embeddings a link-level model scores pairs with: the node-level model's forward."""
-        if self.task_level != "link":
-            raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
-        return self._forward(batch)
-
     def check_flags(self) -> None:
         """Synchronising, for a model with a categorical encoder only: raises ``IndexError`` if a launch since the last
         check met a category outside its column's range (``nn.functional.check_categorical``).  ``train.train_epoch``
@@ -210,13 +195,9 @@ class MPNN(nn.Module):
                 ("transformerconv_edge" if isinstance(self.conv_layers[0], TransformerConv) else "gine")
             raise ValueError(f"the model has edge-aware convolutions (conv_type {kind!r}) and the batch carries no "
                              "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
-        dev = next(self.parameters()).device
         if self.encoder_kinds[1] is not None:
             return self.edge_encoder(ea)
-        if ea.dtype != torch.float32 or ea.device != dev:
-            raise TypeError(f"edge_attr must be float32 on the model's device ({dev}); got {ea.dtype} on "
-                            f"{ea.device} (train.batching.to_device casts integer bond features)")
-        return ea
+        return float_edge_attr(ea, next(self.parameters()).device)
 
     def _forward(self, batch) -> Tensor:
         if self.engine not in ("layered", "auto", "resident"):

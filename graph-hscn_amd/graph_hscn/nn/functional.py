@@ -475,6 +475,16 @@ def gatedgcn_supported(H: int) -> bool:
     return bool(_hip.lib().hscn_gatedgcn_supported(int(H)))
 
 
+def _source_grads(E: int, a: Tensor, b: Tensor, need_a: bool, need_b: bool, walk):
+    """The two gradients of a source-keyed walk, each like its operand, None where not needed: ``walk(ga, gb)`` fills
+    them when the relation has edges; otherwise no edge reaches the operands: exact zeros, not None."""
+    new = torch.empty_like if E else torch.zeros_like
+    ga, gb = new(a) if need_a else None, new(b) if need_b else None
+    if E and (need_a or need_b):
+        walk(ga, gb)
+    return ga, gb
+
+
 class GatedGCNAggregateFn(Function):
     """(Ax, Bx, Dx, Ex [N, H], Ce [E, H]) -> (h [N, H], e_out [E, H]) over ``rel``, with j = src_k, i = dst_k; row k
     of ``Ce`` and ``e_out`` belongs to edge k of ``rel.edge_index``.  Forward: one launch; kept for backward are Ax, Bx,
@@ -533,16 +543,13 @@ class GatedGCNAggregateFn(Function):
                  ptr(rel.edge_index.contiguous()) if E else None, ptr(Ax), ptr(Bx), ptr(h), ptr(e_out) if E else None,
                  ptr(den), ptr(gh), ptr(ge_out) if (E and ge_out is not None) else None, ptr(gn),
                  ptr(ge) if (E and edges) else None, ptr(gDx), N, E, H, ptr(csr.flag), stream())
-            if need_b or need_e:
-                if E:
-                    t = rel.csr_t
-                    gBx = torch.empty_like(Ax) if need_b else None
-                    gEx = torch.empty_like(Ax) if need_e else None
-                    call("hscn_gatedgcn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(e_out), ptr(gn), ptr(ge),
-                         ptr(gBx), ptr(gEx), N, E, H, ptr(csr.flag), stream())
-                else:                               # no edge reaches Bx or Ex: exact zeros, not None
-                    gBx = torch.zeros_like(Ax) if need_b else None
-                    gEx = torch.zeros_like(Ax) if need_e else None
+
+            def walk(gBx, gEx):
+                t = rel.csr_t
+                call("hscn_gatedgcn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(e_out), ptr(gn), ptr(ge),
+                     ptr(gBx), ptr(gEx), N, E, H, ptr(csr.flag), stream())
+
+            gBx, gEx = _source_grads(E, Ax, Ax, need_b, need_e, walk)
         return (gh if need_a else None, gBx, gDx if need_d else None, gEx, ge if need_c else None, None)
 
 
@@ -564,6 +571,28 @@ def edge_attn_supported(heads: int, head_dim: int) -> bool:
     return bool(_hip.lib().hscn_edge_attn_supported(int(heads), int(head_dim)))
 
 
+def _head_attention_dims(op: str, operands, heads: int, shapes, supported, envelope: str):
+    """What both sparse attention operators check of their named ``operands`` (the first is q) -> (rows, HC, C): float32
+    and 2-D, ``heads | width``, then ``shapes(rows, HC)`` -- the operator's own checks of its relation or structure --
+    then the kernel's envelope and the device.  ``op`` names the operator in every message."""
+    for name, t in operands:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{op}: {name} must be float32, got {t.dtype}")
+        if t is not None and t.dim() != 2:
+            raise ValueError(f"{op}: {name} must be 2-D [rows, heads * C], got {tuple(t.shape)}")
+    rows, HC = operands[0][1].shape
+    if heads < 1 or HC % heads:
+        raise ValueError(f"{op}: width {HC} is not a multiple of heads = {heads}")
+    C = HC // heads
+    shapes(rows, HC)
+    if not supported(heads, C):
+        raise ValueError(f"{op}: heads = {heads}, head width = {C} outside the kernel's envelope ({envelope})")
+    for _, t in operands:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{op} takes HIP device tensors only (got a CPU tensor): the hot path has no CPU fallback")
+    return rows, HC, C
+
+
 class EdgeAttentionFn(Function):
     """(q [Nd, Hd*C], k, v [Ns, Hd*C], e [E, Hd*C] or None) -> out [Nd, Hd*C] over ``rel`` (j = src_k, i = dst_k; row k
     of ``e`` belongs to edge k of ``rel.edge_index``): per head, ``out_i = sum_k softmax_k(q_i . (k_j + e_k) / sqrt(C))
@@ -576,30 +605,20 @@ class EdgeAttentionFn(Function):
     @staticmethod
     def forward(ctx, q: Tensor, k: Tensor, v: Tensor, e: Optional[Tensor], rel: Relation, heads: int):
         heads = int(heads)
-        for name, t in (("q", q), ("k", k), ("v", v), ("e", e)):
-            if t is not None and t.dtype != torch.float32:
-                raise TypeError(f"edge attention: {name} must be float32, got {t.dtype}")
-            if t is not None and t.dim() != 2:
-                raise ValueError(f"edge attention: {name} must be 2-D [rows, heads * C], got {tuple(t.shape)}")
-        Nd, HC = q.shape
-        if heads < 1 or HC % heads:
-            raise ValueError(f"edge attention: width {HC} is not a multiple of heads = {heads}")
-        C = HC // heads
-        if k.shape != v.shape or k.size(1) != HC:
-            raise ValueError(f"edge attention: k is {tuple(k.shape)}, v is {tuple(v.shape)}, q is {tuple(q.shape)}")
-        Ns = k.size(0)
-        if rel.num_src != Ns or rel.num_dst != Nd:
-            raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, k has {Ns} rows and q has {Nd}")
         E = rel.num_edges
-        if e is not None and (e.size(0) != E or e.size(1) != HC):
-            raise ValueError(f"e is {tuple(e.shape)}; the relation has {E} edges and the layer is {HC} wide")
-        if not edge_attn_supported(heads, C):
-            raise ValueError(f"edge attention: heads = {heads}, head width = {C} outside the kernel's envelope "
-                             f"({EDGE_ATTN_ENVELOPE})")
-        for t in (q, k, v, e):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("edge attention takes HIP device tensors only (got a CPU tensor): the hot path has "
-                                   "no CPU fallback")
+
+        def shapes(Nd, HC):
+            if k.shape != v.shape or k.size(1) != HC:
+                raise ValueError(f"edge attention: k is {tuple(k.shape)}, v is {tuple(v.shape)}, q is {tuple(q.shape)}")
+            if rel.num_src != k.size(0) or rel.num_dst != Nd:
+                raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, k has {k.size(0)} rows and q "
+                                 f"has {Nd}")
+            if e is not None and (e.size(0) != E or e.size(1) != HC):
+                raise ValueError(f"e is {tuple(e.shape)}; the relation has {E} edges and the layer is {HC} wide")
+
+        Nd, HC, C = _head_attention_dims("edge attention", (("q", q), ("k", k), ("v", v), ("e", e)), heads, shapes,
+                                         edge_attn_supported, EDGE_ATTN_ENVELOPE)
+        Ns = k.size(0)
         q, k, v, e = _c(q), _c(k), _c(v), _c(e)
         csr = rel.csr
         dev = q.device
@@ -628,20 +647,16 @@ class EdgeAttentionFn(Function):
         delta = torch.empty(Nd, heads, dtype=torch.float32, device=q.device)
         dq = torch.empty_like(q) if need_q else None
         de = torch.empty_like(e) if need_e else None
-        dk = dv = None
         call("hscn_edge_attn_bwd_dst", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(q), ptr(k), ptr(v),
              ptr(e) if E else None, ptr(out), ptr(lse), ptr(go), ptr(delta), ptr(dq), ptr(de) if E else None,
              Nd, Ns, E, heads, C, ptr(csr.flag), stream())
-        if need_k or need_v:
-            if E:
-                t = rel.csr_t
-                dk = torch.empty_like(k) if need_k else None
-                dv = torch.empty_like(v) if need_v else None
-                call("hscn_edge_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(q), ptr(k), ptr(v), ptr(e),
-                     ptr(lse), ptr(delta), ptr(go), ptr(dk), ptr(dv), Nd, Ns, E, heads, C, ptr(csr.flag), stream())
-            else:                                   # no edge reaches k or v: exact zeros, not None
-                dk = torch.zeros_like(k) if need_k else None
-                dv = torch.zeros_like(v) if need_v else None
+
+        def walk(dk, dv):
+            t = rel.csr_t
+            call("hscn_edge_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(q), ptr(k), ptr(v), ptr(e),
+                 ptr(lse), ptr(delta), ptr(go), ptr(dk), ptr(dv), Nd, Ns, E, heads, C, ptr(csr.flag), stream())
+
+        dk, dv = _source_grads(E, k, v, need_k, need_v, walk)
         return dq, dk, dv, de, None, None
 
 
@@ -723,35 +738,25 @@ class ExphormerAttentionFn(Function):
     @staticmethod
     def forward(ctx, q: Tensor, k: Tensor, v: Tensor, e_edge: Optional[Tensor], e_type: Tensor, struct, heads: int):
         heads = int(heads)
-        for name, t in (("q", q), ("k", k), ("v", v), ("e_edge", e_edge), ("e_type", e_type)):
-            if t is not None and t.dtype != torch.float32:
-                raise TypeError(f"exphormer attention: {name} must be float32, got {t.dtype}")
-            if t is not None and t.dim() != 2:
-                raise ValueError(f"exphormer attention: {name} must be 2-D [rows, heads * C], got {tuple(t.shape)}")
-        N, HC = q.shape
-        if heads < 1 or HC % heads:
-            raise ValueError(f"exphormer attention: width {HC} is not a multiple of heads = {heads}")
-        C = HC // heads
-        if k.shape != q.shape or v.shape != q.shape:
-            raise ValueError(f"exphormer attention: k is {tuple(k.shape)}, v is {tuple(v.shape)}, q is {tuple(q.shape)}")
-        if struct.num_rows != N:
-            raise ValueError(f"the union graph has {struct.num_rows} rows (nodes + virtual nodes), q has {N}")
         El, T, E = struct.num_edge_rows, struct.num_types, struct.num_edges
-        if e_edge is None and El:
-            raise ValueError(f"the union graph names {El} per-edge feature rows and e_edge is None")
-        if e_edge is not None and (e_edge.size(0) != El or e_edge.size(1) != HC):
-            raise ValueError(f"e_edge is {tuple(e_edge.shape)}; the union graph names {El} per-edge rows and the layer "
-                             f"is {HC} wide")
-        if e_type.size(0) != T or e_type.size(1) != HC:
-            raise ValueError(f"e_type is {tuple(e_type.shape)}; the union graph has {T} edge types and the layer is "
-                             f"{HC} wide")
-        if not exph_attn_supported(heads, C):
-            raise ValueError(f"exphormer attention: heads = {heads}, head width = {C} outside the kernel's envelope "
-                             f"({EXPH_ENVELOPE})")
-        for t in (q, k, v, e_edge, e_type):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("exphormer attention takes HIP device tensors only (got a CPU tensor): the hot path "
-                                   "has no CPU fallback")
+
+        def shapes(N, HC):
+            if k.shape != q.shape or v.shape != q.shape:
+                raise ValueError(f"exphormer attention: k is {tuple(k.shape)}, v is {tuple(v.shape)}, q is "
+                                 f"{tuple(q.shape)}")
+            if struct.num_rows != N:
+                raise ValueError(f"the union graph has {struct.num_rows} rows (nodes + virtual nodes), q has {N}")
+            if e_edge is None and El:
+                raise ValueError(f"the union graph names {El} per-edge feature rows and e_edge is None")
+            if e_edge is not None and (e_edge.size(0) != El or e_edge.size(1) != HC):
+                raise ValueError(f"e_edge is {tuple(e_edge.shape)}; the union graph names {El} per-edge rows and the "
+                                 f"layer is {HC} wide")
+            if e_type.size(0) != T or e_type.size(1) != HC:
+                raise ValueError(f"e_type is {tuple(e_type.shape)}; the union graph has {T} edge types and the layer is "
+                                 f"{HC} wide")
+
+        operands = (("q", q), ("k", k), ("v", v), ("e_edge", e_edge), ("e_type", e_type))
+        N, HC, C = _head_attention_dims("exphormer attention", operands, heads, shapes, exph_attn_supported, EXPH_ENVELOPE)
         q, k, v, e_edge, e_type = _c(q), _c(k), _c(v), _c(e_edge), _c(e_type)
         csr = struct.rel.csr
         dev = q.device
@@ -783,21 +788,18 @@ class ExphormerAttentionFn(Function):
         dq = torch.empty_like(q) if need_q else None
         # every e_edge row is named by exactly one union edge (the structure checks it): each row is written once
         de = torch.empty_like(e_edge) if need_e else None
-        dk = dv = dt = None
+        dt = None
         call("hscn_exph_attn_bwd_dst", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(struct.erow), ptr(q), ptr(k),
              ptr(v), ptr(e_edge) if El else None, ptr(e_type), ptr(out), ptr(z), ptr(go), ptr(delta), ptr(dq),
              ptr(de) if El else None, N, E, El, T, heads, C, ptr(csr.flag), stream())
-        if need_k or need_v:
-            if E:
-                t = rel.csr_t
-                dk = torch.empty_like(k) if need_k else None
-                dv = torch.empty_like(v) if need_v else None
-                call("hscn_exph_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(struct.erow), ptr(q), ptr(k),
-                     ptr(v), ptr(e_edge) if El else None, ptr(e_type), ptr(z), ptr(delta), ptr(go), ptr(dk), ptr(dv),
-                     N, E, El, T, heads, C, ptr(csr.flag), stream())
-            else:                                   # no edge reaches k or v: exact zeros, not None
-                dk = torch.zeros_like(k) if need_k else None
-                dv = torch.zeros_like(v) if need_v else None
+
+        def walk(dk, dv):
+            t = rel.csr_t
+            call("hscn_exph_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(struct.erow), ptr(q), ptr(k),
+                 ptr(v), ptr(e_edge) if El else None, ptr(e_type), ptr(z), ptr(delta), ptr(go), ptr(dk), ptr(dv),
+                 N, E, El, T, heads, C, ptr(csr.flag), stream())
+
+        dk, dv = _source_grads(E, k, v, need_k, need_v, walk)
         if need_t:
             dt = torch.empty_like(e_type)
             trowptr, titem = struct.type_slots

@@ -119,10 +119,8 @@ class GPSLayer(nn.Module):
             h_a, virt_out = self.attn(torch.cat([x, virt], 0) if virt.size(0) else x, struct, e_edge, e_type)
         elif exph is not None:
             raise ValueError("exph= belongs to a layer built with global_model='exphormer'")
-        elif spd is None:                           # (the call of before, word for word)
-            h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes)
-        else:
-            h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes, spd=spd)
+        else:                                       # (without buckets the call is that of before: no spd keyword)
+            h_a = self.attn(x, batch, ptr32=ptr32, max_nodes=max_nodes, **({} if spd is None else {"spd": spd}))
         h_a = x + self._drop(h_a, 1)
         if self.norm1_attn is not None:
             h_a = self.norm1_attn(h_a)
