@@ -48,6 +48,11 @@ class _MP(nn.Module):
         return x
 
 
+def _stored(store: Callable, t: Tensor, name: str, layer: int) -> Tensor:
+    """``store(t)``, or ``store(t, name, layer)`` for a callable that asks for it (``store.tagged``)."""
+    return store(t, name, layer) if getattr(store, "tagged", False) else store(t)
+
+
 class SCN(nn.Module):
     """model/hscn.py:19-64.  ``mlp_units`` must be empty-compatible with the
     reference's (buggy, :50-53) loop: each hidden Linear is ``out_channels ->
@@ -78,12 +83,13 @@ class SCN(nn.Module):
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor], store: Optional[Callable] = None):
         """``store``: reduced-precision storage emulation (see ``HSCN.forward``): applied to the input features
-        and to the message-passing stack's output (the hidden activation the backward re-reads)."""
+        and to the message-passing stack's output (the hidden activation the backward re-reads).  A ``store`` with a
+        true ``tagged`` attribute is told which tensor it is handed: ``store(t, "x", -1)`` / ``store(t, "y", 0)``."""
         if store is not None:
-            x = store(x)
+            x = _stored(store, x, "x", -1)
         x = self.mp(x, edge_index, edge_weight)
         if store is not None:
-            x = store(x)
+            x = _stored(store, x, "y", 0)
         s = self._run_mlp(x)
         adj = P.to_dense_adj(edge_index)
         _, _, mc_loss, o_loss = P.dense_mincut_pool(x, adj, s)
@@ -128,14 +134,16 @@ class HSCN(nn.Module):
         """``store``: emulation of a reduced-precision STORAGE type for node features and inter-layer activations
         (BASELINE.json configs[4]; the reference itself has no such mode): applied to the input features and to
         every layer's output of both node types -- the points at which the HIP kernels round -- with float32
-        arithmetic in between (``half_storage`` below).  ``keep``: a dict that receives the final ``x_dict``."""
+        arithmetic in between (``half_storage`` below).  A ``store`` with a true ``tagged`` attribute is told which
+        tensor it is handed: ``store(t, node_type, layer)``, layer -1 for the input features.  ``keep``: a dict that
+        receives the final ``x_dict``."""
         if store is not None:
-            x_dict = {k: store(v) for k, v in x_dict.items()}
-        for conv in self.convs:
+            x_dict = {k: _stored(store, v, k, -1) for k, v in x_dict.items()}
+        for layer, conv in enumerate(self.convs):
             x_dict = conv(x_dict, edge_index_dict)
             x_dict = {k: v.relu() for k, v in x_dict.items()}
             if store is not None:
-                x_dict = {k: store(v) for k, v in x_dict.items()}
+                x_dict = {k: _stored(store, v, k, layer) for k, v in x_dict.items()}
         if keep is not None:
             keep.update(x_dict)
         x = P.global_mean_pool(x_dict["local"], batch_local, num_graphs)

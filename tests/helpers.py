@@ -538,3 +538,71 @@ def scn_step_in_dtype(m, x, edge_index):
     s = m._run_mlp(h)
     _, _, mc, o = P.dense_mincut_pool(h, P.to_dense_adj(ei2).to(dt), s)
     return torch.softmax(s, dim=-1), mc, o
+
+
+# --------------------------------------------------------------------------- #
+# half-precision STORAGE against float64 (tests/test_gpu_f16_edges.py): the window a correctly rounded store must fall
+# into, and an oracle forced onto the stored values so that a rounding flip cannot propagate
+# --------------------------------------------------------------------------- #
+def to_half(t):
+    """float64 (or float32) -> IEEE half in ONE round-to-nearest-even step (numpy converts the double's bits directly;
+    double -> float -> half would round twice and can cross a tie).  Overflow gives inf, NaN stays NaN."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return torch.from_numpy(t.detach().cpu().numpy().astype(np.float16))
+
+
+def half_window(r64, o32):
+    """The halves a correct store of the tensor may hold.  ``r64``: the float64 oracle's value BEFORE storage, ``o32``
+    the float32 oracle's from the same inputs.  With ``referee``'s bar unchanged, b = 2 max|o32 - r64| + 8 * 2^-23 *
+    max|r64|, a float32 evaluation d32 with |d32 - r64| <= b stores half(d32), and rounding is monotone:
+
+        half(r64 - b)  <=  stored  <=  half(r64 + b)          element by element,
+
+    both ends rounded once (``to_half``).  Returns (lo, hi, b): half tensors and the bar."""
+    r = r64.detach().cpu().double()
+    b = 2.0 * float((o32.detach().cpu().double() - r).abs().max()) + 8.0 * 2.0 ** -23 * float(r.abs().max()) \
+        if r.numel() else 0.0
+    return to_half(r - b), to_half(r + b), b
+
+
+def in_half_window(d, lo, hi):
+    """Element-wise verdict for stored halves ``d``: lo <= d <= hi, an infinite end admits (lo = +inf: demands) an
+    infinity of its sign, and where the window is NaN the stored value must be NaN."""
+    d, lo, hi = d.detach().cpu().double(), lo.double(), hi.double()
+    nan = torch.isnan(lo) | torch.isnan(hi)
+    return torch.where(nan, torch.isnan(d), (lo <= d) & (d <= hi))
+
+
+def window_shares(r64, lo, hi, b):
+    """How sharp the window is, over the positive elements of ``r64``: the share determined to the bit (lo == hi), the
+    share whose window spans more than two adjacent halves (among those with r64 - b > 0, where the bit patterns of
+    both ends are ordered like their values), the share that are half subnormals (0 < r64 < 2^-14)."""
+    r = r64.detach().cpu().double()
+    pos = r > 0
+    if not bool(pos.any()):
+        return dict(determined=1.0, wide=0.0, subnormal=0.0, positive=0)
+    span = (hi.view(torch.int16).int() - lo.view(torch.int16).int())[pos & (r - b > 0) & torch.isfinite(hi.double())]
+    return dict(determined=float((lo == hi)[pos].double().mean()),
+                wide=float((span > 1).double().mean()) if span.numel() else 0.0,
+                subnormal=float((r[pos] < 2.0 ** -14).double().mean()), positive=int(pos.sum()))
+
+
+class ForcedStore:
+    """A ``store`` callable for ``oracle.models.HSCN.forward`` / ``SCN.forward`` (tagged: it is told which tensor it is
+    handed) that FORCES the oracle onto the values the device stored: ``forced[(name, layer)]`` replaces the tensor's
+    value, t + (forced - t).detach(), and the gradient passes straight through -- the HIP backward treats the stored
+    value as the activation.  The float32 and the float64 oracle then see the very activations the kernel's backward
+    read, so a rounding flip of one evaluation cannot reach the next layer.  Tensors without a forced value (input
+    features, which are halves already, and the virtual rows, which never reach the prediction) round as
+    ``oracle.models.half_storage`` does."""
+    tagged = True
+
+    def __init__(self, forced):
+        self.forced = {k: v.detach().cpu() for k, v in forced.items()}
+
+    def __call__(self, t, name, layer):
+        f = self.forced.get((name, layer))
+        if f is None:
+            return t + (to_half(t).to(t.dtype) - t).detach()
+        assert f.shape == t.shape, (name, layer, tuple(f.shape), tuple(t.shape))
+        return t + (f.to(t.dtype) - t).detach()
