@@ -263,6 +263,13 @@ _SIGNATURES = {
     "hscn_exph_type_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "hscn_exph_attn_bwd_type": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int, c_int, P, P,
                                         c_size_t, P]),
+    # LapPE node encoder, DeepSet model: fused chain + masked sum over the frequencies (csrc/lappe.hip; additive to
+    # ABI 24); `params_host`: a host array of 2 * layers device pointers (engine._ptr_table)
+    "hscn_lappe_supported": (c_int, [c_int, c_int, c_int]),
+    "hscn_lappe_tile": (c_int, []),
+    "hscn_lappe_workspace_floats": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "hscn_lappe_fwd": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_int, c_uint64, P, P]),
+    "hscn_lappe_bwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, c_int, c_uint64, P, P, c_int64, P]),
 }
 
 

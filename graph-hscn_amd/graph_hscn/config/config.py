@@ -78,6 +78,15 @@ def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
                          f"got {conv_type!r}")
 
 
+def _check_pos_enc(pos_enc, hidden_channels) -> None:
+    if pos_enc is None:
+        return
+    if not isinstance(pos_enc, (LapPEConfig, RWSEConfig)):
+        raise ValueError(f"pos_enc must be a LapPEConfig, an RWSEConfig or None, got {type(pos_enc).__name__}")
+    if pos_enc.dim_emb != hidden_channels:
+        raise ValueError(f"pos_enc.dim_emb ({pos_enc.dim_emb}) must equal hidden_channels ({hidden_channels})")
+
+
 def check_heads(heads, hidden_channels, conv_type) -> None:
     if not isinstance(heads, int) or heads < 1:
         raise ValueError(f"heads must be a positive int, got {heads!r}")
@@ -126,11 +135,16 @@ class MPNNConfig:  # config.py:49-73
     # extension: attention heads of conv_type "transformerconv" / "transformerconv_edge": the hidden layers are
     # conv(in, hidden_channels // heads, heads=heads), the last one has one head of width num_classes
     heads: int = 1
+    # extension: a trainable positional encoder inside the model (model/_common.py PosEnc): a LapPEConfig or an
+    # RWSEConfig whose dim_emb is hidden_channels; pe_undirected: the edge lists hold both directions
+    pos_enc: Optional[object] = None
+    pe_undirected: bool = True
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         _check_encoders(self.node_encoder, self.edge_encoder, self.conv_type)
+        _check_pos_enc(self.pos_enc, self.hidden_channels)
         check_heads(self.heads, self.hidden_channels, self.conv_type)
         if self.dropout and not (0.0 <= self.dropout <= 1.0):
             raise ValueError(f"{self.dropout} must be between 0.0 and 1.0.")
@@ -174,11 +188,16 @@ class GPSConfig:
     num_virtual_nodes: int = 1
     add_local_edges: bool = True
     expander_seed: int = 0
+    # a trainable positional encoder inside the model (model/_common.py PosEnc): a LapPEConfig or an RWSEConfig whose
+    # dim_emb is hidden_channels; pe_undirected: the edge lists hold both directions
+    pos_enc: Optional[object] = None
+    pe_undirected: bool = True
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         _check_encoders(self.node_encoder, self.edge_encoder, self.local_conv_type)
+        _check_pos_enc(self.pos_enc, self.hidden_channels)
         if self.attn_bias not in (None, "spd"):
             raise ValueError(f"attn_bias must be 'spd' or None, got {self.attn_bias!r}")
         if self.global_model not in ("attention", "exphormer"):
@@ -323,6 +342,52 @@ class RWSEConfig:
             raise ValueError(f"raw_norm must be 'none' or 'batchnorm', got {self.raw_norm!r}.")
         if self.dim_emb - self.dim_pe < 1:
             raise ValueError(f"RWSE size {self.dim_pe} is too large for desired embedding size of {self.dim_emb}.")
+
+
+@dataclass
+class LapPEConfig:
+    """Laplacian positional encoding, GraphGPS's ``LapPENodeEncoder`` with the DeepSet model (encoder/lappe.py,
+    csrc/lappe.hip): per node the ``eigen_max_freqs`` (eigenvector entry, eigenvalue) pairs go through ``layers``
+    Linear + ReLU (2 -> 2 dim_pe -> ... -> dim_pe), the frequencies that exist are summed and ``post_layers`` Linear +
+    ReLU follow; in training mode ``sign_flip`` flips the sign of whole eigenvector columns at random.  The three
+    eigen-settings are read by ``transform.compute_posenc_stats_device``; ``compute_posenc`` and the models' ``pos_enc``
+    dispatch on the config's type."""
+    dim_in: int
+    dim_emb: int
+    dim_pe: int
+    model: str = "DeepSet"
+    layers: int = 2
+    post_layers: int = 0
+    eigen_max_freqs: int = 10
+    eigvec_norm: str = "L2"
+    eigen_laplacian_norm: str = "none"
+    raw_norm: str = "none"
+    sign_flip: bool = True
+    pass_as_var: bool = False
+
+    def __post_init__(self) -> None:
+        from ..nn.functional import LAPPE_ENVELOPE, lappe_supported
+        if self.model == "Transformer":
+            raise ValueError("model='Transformer' (the Transformer variant of the LapPE encoder) is not built; "
+                             "model must be 'DeepSet'.")
+        if self.model != "DeepSet":
+            raise ValueError(f"model must be 'DeepSet', got {self.model!r}.")
+        if self.raw_norm == "batchnorm":
+            raise ValueError("raw_norm='batchnorm' is not built for the LapPE encoder (the fused operator reads the "
+                             "raw statistics); raw_norm must be 'none'.")
+        if self.raw_norm != "none":
+            raise ValueError(f"raw_norm must be 'none', got {self.raw_norm!r}.")
+        for name in ("eigen_max_freqs", "dim_pe", "layers", "post_layers"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an int, got {v!r}.")
+        if not lappe_supported(self.eigen_max_freqs, self.dim_pe, self.layers):
+            raise ValueError(f"eigen_max_freqs={self.eigen_max_freqs}, dim_pe={self.dim_pe}, layers={self.layers} "
+                             f"outside the LapPE kernel's envelope ({LAPPE_ENVELOPE}).")
+        if self.post_layers < 0:
+            raise ValueError("post_layers must be non-negative.")
+        if self.dim_emb - self.dim_pe < 1:
+            raise ValueError(f"LapPE size {self.dim_pe} is too large for desired embedding size of {self.dim_emb}.")
 
 
 @dataclass

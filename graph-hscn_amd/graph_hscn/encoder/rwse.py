@@ -36,16 +36,21 @@ class RWSENodeEncoder(nn.Module):
         self.pe_encoder = nn.ModuleList(Linear(i, o) for i, o in zip(widths[:-1], widths[1:]))
         self._act = "identity" if cfg.model == "linear" else "relu"       # the linear kernel's epilogue
 
-    def forward(self, batch):
-        if getattr(batch, "rwse", None) is None:
-            raise ValueError("Precomputed random-walk statistics are required for RWSENodeEncoder; "
-                             "transform.compute_rwse_stats_device(batch, is_undirected, cfg) attaches batch.rwse")
-        pe = batch.rwse.to(torch.float32)
+    def pe(self, rwse):
+        """[N, dim_pe] from the random-walk statistics ``rwse`` [N, ksteps]."""
+        pe = rwse.to(torch.float32)
         if self.raw_norm is not None:
             pe = self.raw_norm(pe)
         for fc in self.pe_encoder:
             pe = fc(pe, act=self._act)
-        h = self.linear_x(batch.x.to(torch.float32)) if self.expand_x else batch.x
+        return pe
+
+    def forward(self, batch):
+        if getattr(batch, "rwse", None) is None:
+            raise ValueError("Precomputed random-walk statistics are required for RWSENodeEncoder; "
+                             "transform.compute_rwse_stats_device(batch, is_undirected, cfg) attaches batch.rwse")
+        pe = self.pe(batch.rwse)
+        h =self.linear_x(batch.x.to(torch.float32)) if self.expand_x else batch.x
         batch.x = torch.cat((h, pe), 1)
         if self.pass_as_var:
             batch.pe_rwse = pe

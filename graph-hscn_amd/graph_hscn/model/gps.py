@@ -22,7 +22,7 @@ from torch import Tensor
 
 from ..config.config import ACT_DICT, GPSConfig
 from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
-from ._common import LinkLevel, check_encoders, check_task_level, float_edge_attr
+from ._common import POSENC_RESIDENT_REASON, LinkLevel, PosEnc, check_encoders, check_task_level, float_edge_attr
 from ..nn import functional as Fh
 from ..nn.conv import Linear
 from ..nn.gps import GPSLayer
@@ -54,7 +54,7 @@ class _Table(nn.Module):
         nn.init.normal_(self.weight)
 
 
-class GPS(LinkLevel, nn.Module):
+class GPS(LinkLevel, PosEnc, nn.Module):
     layered_only = True      # train.batching.refuse_layered_only: the resident entry points refuse this model by name
 
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
@@ -62,8 +62,14 @@ class GPS(LinkLevel, nn.Module):
                  norm: Optional[str] = "layer", task_level: str = "graph", node_encoder: Optional[str] = None,
                  edge_encoder: Optional[str] = None, attn_bias: Optional[str] = None, spd_max_dist: int = 20,
                  global_model: str = "attention", expander_degree: int = 6, num_virtual_nodes: int = 1,
-                 add_local_edges: bool = True, expander_seed: int = 0) -> None:
-        """``global_model="exphormer"``: every layer's global branch is ``nn.attention.ExphormerAttention`` over the
+                 add_local_edges: bool = True, expander_seed: int = 0, pos_enc=None, pe_undirected: bool = True) -> None:
+        """``pos_enc`` (a ``config.LapPEConfig`` or ``config.RWSEConfig`` with ``dim_emb = hidden_channels``): the model
+        owns a trainable positional encoder ``pe_encoder`` (``model/_common.py PosEnc``); the node encoder is built at
+        width ``D - dim_pe`` and the layers see ``[h | pe]``.  The statistics are the batch's own or computed once per
+        batch on the device (``pe_undirected``: the edge list holds both directions).  It combines with ``attn_bias``
+        and ``global_model`` freely.
+
+        ``global_model="exphormer"``: every layer's global branch is ``nn.attention.ExphormerAttention`` over the
         union of the batch's own edges (``add_local_edges``), a random ``expander_degree``-regular expander drawn under
         ``expander_seed`` and ``num_virtual_nodes`` virtual nodes per graph.  The model then owns
         ``virt_node_emb.weight`` [nv, D] (the virtual rows every graph starts from) and ``edge_type_emb.weight``
@@ -115,7 +121,8 @@ class GPS(LinkLevel, nn.Module):
         self.dropout_seed: Optional[int] = None     # tests pin the masks (layer i draws with seeds + 4 i .. + 4 i + 3)
         D = int(hidden_channels)
         self.encoder_kinds = (node_encoder, edge_encoder)
-        self.node_encoder = Linear(num_features, D) if node_encoder is None else NODE_ENCODERS[node_encoder](D)
+        Dx = self._init_pos_enc(pos_enc, pe_undirected, D)             # D - dim_pe with a positional encoder
+        self.node_encoder = Linear(num_features, Dx) if node_encoder is None else NODE_ENCODERS[node_encoder](Dx)
         spd_buckets = self.spd_max_dist + 1 if attn_bias == "spd" else None
         if global_model == "exphormer":
             self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, global_model="exphormer",
@@ -138,6 +145,7 @@ class GPS(LinkLevel, nn.Module):
             self.edge_type_emb = _Table(2 + 2 * self.num_virtual_nodes, D)
             if self.layers[0].uses_edge_attr and not hasattr(self, "edge_encoder") and self.add_local_edges:
                 self.exph_edge_encoder = Linear(-1, D)
+        self._build_pos_encoder(D)                  # after every parameter of before
         # "layered"; "auto" runs layered too; "resident" raises with the reason when the model is called
         self.engine = "layered"
         self.last_engine: Optional[str] = None
@@ -145,6 +153,8 @@ class GPS(LinkLevel, nn.Module):
     # ---- the surface of a homogeneous model (train.batching, train.train) ----------------------------------------
     def resident_reason(self, batch=None, need_grad: bool = False) -> str:
         reason = EXPHORMER_RESIDENT_REASON if self.global_model == "exphormer" else RESIDENT_REASON
+        if self.pos_enc is not None:
+            reason = reason + "; " + POSENC_RESIDENT_REASON
         if any(self.encoder_kinds):
             return reason + "; " + encoder_reason(*self.encoder_kinds)
         return reason
@@ -167,6 +177,7 @@ class GPS(LinkLevel, nn.Module):
             Fh.check_spd(next(self.parameters()).device)
         if any(self.encoder_kinds):                # and the categorical encoders' (an index outside its column)
             Fh.check_categorical(next(self.parameters()).device)
+        self._check_pe_flags()                      # and the positional encoder's statistics launches'
 
     # ---- forward -----------------------------------------------------------------------------------------------
     def _edge_attr(self, batch) -> Tensor:
@@ -179,6 +190,9 @@ class GPS(LinkLevel, nn.Module):
         if self.encoder_kinds[1] is not None:       # int64 categories: the bond encoder checks them itself
             return ea
         return float_edge_attr(ea, next(self.parameters()).device)
+
+    def _embed_x(self, batch) -> Tensor:
+        return self.node_encoder(batch.x)
 
     def _spd(self, batch):
         """The batch's ``SPDBuckets`` at ``spd_max_dist``, built once: kept on the batch object, in a dict that
@@ -197,13 +211,15 @@ class GPS(LinkLevel, nn.Module):
         if self.engine not in ("layered", "auto", "resident"):
             raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
         if self.engine == "resident":
-            raise RuntimeError("engine='resident' does not take this model: "
-                               f"{EXPHORMER_RESIDENT_REASON if self.global_model == 'exphormer' else RESIDENT_REASON}")
+            reason = EXPHORMER_RESIDENT_REASON if self.global_model == "exphormer" else RESIDENT_REASON
+            if self.pos_enc is not None:
+                reason = self.resident_reason()
+            raise RuntimeError(f"engine='resident' does not take this model: {reason}")
         self.last_engine = "layered"
         sparse = self.global_model == "exphormer"
         glob = {"spd": self._spd(batch)}            # the global branch's keywords, once per forward for all layers
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
-        x = self.node_encoder(batch.x)
+        x = self.encode_nodes(batch)
         if self.layers[0].updates_edge_attr or self.encoder_kinds[1] is not None:
             edge_attr = self.edge_encoder(edge_attr)
         if sparse:                                  # the virtual rows travel beside the node rows and stay behind
@@ -247,4 +263,5 @@ def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:
                getattr(model_cfg, "attn_bias", None), getattr(model_cfg, "spd_max_dist", 20),
                getattr(model_cfg, "global_model", "attention"), getattr(model_cfg, "expander_degree", 6),
                getattr(model_cfg, "num_virtual_nodes", 1), getattr(model_cfg, "add_local_edges", True),
-               getattr(model_cfg, "expander_seed", 0))
+               getattr(model_cfg, "expander_seed", 0), getattr(model_cfg, "pos_enc", None),
+               getattr(model_cfg, "pe_undirected", True))

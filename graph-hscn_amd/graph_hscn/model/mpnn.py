@@ -21,19 +21,25 @@ from torch import Tensor
 from .. import _hip
 from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig
 from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
-from ..nn.conv import GCNConv, TransformerConv
+from ..nn.conv import GCNConv, Linear, TransformerConv
 from ..nn import functional as Fh
 from ..nn.norm import BatchNorm1d, LayerNorm
 from ..nn.pool import global_mean_pool
-from ._common import LinkLevel, check_encoders, check_task_level, float_edge_attr
+from ._common import POSENC_RESIDENT_REASON, LinkLevel, PosEnc, check_encoders, check_task_level, float_edge_attr
 
 
-class MPNN(LinkLevel, nn.Module):
+class MPNN(LinkLevel, PosEnc, nn.Module):
     def __init__(self, conv: type, activation: Callable, num_features: int, hidden_channels: int,
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
                  use_layer_norm: bool = False, task_level: str = "graph", node_encoder: Optional[str] = None,
-                 edge_encoder: Optional[str] = None, heads: int = 1) -> None:
-        """``heads`` (extension): with a multi-head ``conv`` (``TransformerConv`` / ``EdgeTransformerConv``) the hidden
+                 edge_encoder: Optional[str] = None, heads: int = 1, pos_enc=None, pe_undirected: bool = True) -> None:
+        """``pos_enc`` (extension; a ``config.LapPEConfig`` or ``config.RWSEConfig`` with ``dim_emb = hidden_channels``):
+        the model owns a trainable positional encoder ``pe_encoder`` (``model/_common.py PosEnc``).  The node features
+        are embedded to ``hidden_channels - dim_pe`` columns -- by the ``AtomEncoder`` of ``node_encoder="atom"``, else
+        by a new ``linear_x = Linear(F, H - dim_pe)`` -- the encoder's ``dim_pe`` columns are appended and the first
+        convolution is ``H -> H``, the shape ``node_encoder="atom"`` already gives it.  Such a model is layered-only.
+
+        ``heads`` (extension): with a multi-head ``conv`` (``TransformerConv`` / ``EdgeTransformerConv``) the hidden
         layers are ``conv(in, hidden_channels // heads, heads=heads)`` and the last one ``conv(hidden, num_classes,
         heads=1)``; such a model is layered-only.
 
@@ -67,8 +73,11 @@ class MPNN(LinkLevel, nn.Module):
         if node_encoder is not None or edge_encoder is not None or multi_head:
             # train.batching.refuse_layered_only: the resident and device-dataset entry points refuse this model by name
             self.layered_only = True
+        x_width = self._init_pos_enc(pos_enc, pe_undirected, hidden_channels)     # H - dim_pe with a positional encoder
+        in_features = num_features
         if node_encoder is not None:
-            self.node_encoder = NODE_ENCODERS[node_encoder](hidden_channels)
+            self.node_encoder = NODE_ENCODERS[node_encoder](x_width)
+        if node_encoder is not None or pos_enc is not None:
             num_features = hidden_channels
         if edge_encoder is not None:
             self.edge_encoder = EDGE_ENCODERS[edge_encoder](hidden_channels)
@@ -98,9 +107,15 @@ class MPNN(LinkLevel, nn.Module):
         # fused training step is step.MPNNResidentTrainStep (autograd passes through the layered kernels).
         self.engine = "layered"
         self.last_engine: Optional[str] = None
+        if pos_enc is not None:                     # after every parameter of before
+            if node_encoder is None:
+                self.linear_x = Linear(in_features, x_width)
+            self._build_pos_encoder(hidden_channels)
 
     def resident_reason(self, batch=None, need_grad: bool = False) -> Optional[str]:
         """Why this model (and ``batch``, if given) cannot take the one-launch MPNN kernels, or None when it can."""
+        if self.pos_enc is not None:
+            return POSENC_RESIDENT_REASON + ("; " + encoder_reason(*self.encoder_kinds) if any(self.encoder_kinds) else "")
         for c in self.conv_layers:
             if isinstance(c, TransformerConv):
                 return (f"convolution {type(c).__name__} (multi-head attention over the in-edges has no one-launch, "
@@ -185,6 +200,12 @@ class MPNN(LinkLevel, nn.Module):
         / ``eval_epoch`` call it once per epoch; a model without an encoder has no flag word and nothing is read."""
         if any(self.encoder_kinds):
             Fh.check_categorical(next(self.parameters()).device)
+        self._check_pe_flags()                      # the positional encoder's statistics launches, where there is one
+
+    def _embed_x(self, batch) -> Tensor:
+        if self.encoder_kinds[0] is not None:
+            return self.node_encoder(batch.x)
+        return self.linear_x(batch.x) if self.pos_enc is not None else batch.x
 
     def _edge_attr(self, batch) -> Tensor:
         """``batch.edge_attr`` for the layers with ``uses_edge_attr``: float32 [E, De] on the model's device (with an
@@ -214,9 +235,8 @@ class MPNN(LinkLevel, nn.Module):
             if self.engine == "resident":
                 raise RuntimeError(f"engine='resident' requested but the model / batch does not qualify: {reason}")
         self.last_engine = "layered"
-        x, edge_index, batch_vec = batch.x, batch.edge_index, batch.batch   # mpnn.py:50
-        if self.encoder_kinds[0] is not None:
-            x = self.node_encoder(x)
+        edge_index, batch_vec = batch.edge_index, batch.batch               # mpnn.py:50
+        x = self.encode_nodes(batch)                                        # batch.x, or [embedded x | pe]
         edge_attr = self._edge_attr(batch) if any(getattr(c, "uses_edge_attr", False) for c in self.conv_layers) else None
 
         def conv(i, x, **kw):                                               # edge-aware layers also take edge_attr
@@ -250,4 +270,5 @@ def build_mpnn(model_cfg: MPNNConfig, num_features: int, num_classes: int) -> MP
                 model_cfg.hidden_channels, num_classes, model_cfg.num_layers, model_cfg.dropout,
                 model_cfg.use_batch_norm, model_cfg.use_layer_norm, getattr(model_cfg, "task_level", "graph"),
                 getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None),
-                getattr(model_cfg, "heads", 1))
+                getattr(model_cfg, "heads", 1), getattr(model_cfg, "pos_enc", None),
+                getattr(model_cfg, "pe_undirected", True))

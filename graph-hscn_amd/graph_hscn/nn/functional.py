@@ -141,7 +141,6 @@ def dropout(x: Tensor, p: float = 0.5, training: bool = True, seed: Optional[int
     from the library's counter-based generator, keyed by ``seed`` (default: ``torch.initial_seed()`` mixed
     with a per-call counter, so ``torch.manual_seed`` makes a run repeatable); it is NOT the mask torch's
     own generator would draw.  The default seed is a host value: a captured hipGraph replays one mask."""
-    global _dropout_calls
     if p < 0.0 or p > 1.0:
         raise ValueError(f"dropout probability has to be between 0 and 1, but got {p}")
     if not training or p == 0.0:
@@ -149,9 +148,16 @@ def dropout(x: Tensor, p: float = 0.5, training: bool = True, seed: Optional[int
     if p == 1.0:
         return x * 0.0
     if seed is None:
-        _dropout_calls += 1
-        seed = (torch.initial_seed() * 0x9E3779B97F4A7C15 + _dropout_calls) & 0xFFFFFFFFFFFFFFFF
+        seed = default_seed()
     return DropoutFn.apply(x, p, seed)
+
+
+def default_seed() -> int:
+    """The next seed of the host generator behind ``dropout``'s default: ``torch.initial_seed()`` mixed with a per-call
+    counter (``nn.functional.LapPEDeepSetFn``'s sign flips draw from it too)."""
+    global _dropout_calls
+    _dropout_calls += 1
+    return (torch.initial_seed() * 0x9E3779B97F4A7C15 + _dropout_calls) & 0xFFFFFFFFFFFFFFFF
 
 
 # --------------------------------------------------------------------------- #
@@ -180,6 +186,98 @@ def linear(x: Tensor, W: Tensor, bias: Optional[Tensor] = None, act: str = "iden
     lead = x.shape[:-1]
     y = LinearFn.apply(x.reshape(-1, x.shape[-1]), W, bias, ACT[act])
     return y.view(*lead, W.shape[0])
+
+
+# --------------------------------------------------------------------------- #
+# LapPE node encoder, DeepSet model (csrc/lappe.hip)
+# --------------------------------------------------------------------------- #
+LAPPE_MAX_FREQS = 64
+LAPPE_MAX_LAYERS = 4
+LAPPE_ENVELOPE = (f"1 <= max_freqs <= {LAPPE_MAX_FREQS}, dim_pe a multiple of 4 in [4, 32] and "
+                  f"1 <= layers <= {LAPPE_MAX_LAYERS}")
+
+
+def lappe_supported(max_freqs: int, dim_pe: int, layers: int) -> bool:
+    """The kernels' envelope (include/hscn.h: hscn_lappe_supported), restated so that a config validates without the
+    library; tests/test_lappe_host.py pins the two to each other."""
+    return 1 <= max_freqs <= LAPPE_MAX_FREQS and 4 <= dim_pe <= 32 and dim_pe % 4 == 0 and 1 <= layers <= LAPPE_MAX_LAYERS
+
+
+def lappe_widths(dim_pe: int, layers: int):
+    """[2, 2 dim_pe, ..., 2 dim_pe, dim_pe]: the DeepSet chain's widths (``layers`` Linears)."""
+    return [2] + [2 * dim_pe] * (layers - 1) + [dim_pe]
+
+
+class LapPEDeepSetFn(Function):
+    """``apply(vec, val, weights, biases, seed_or_None) -> pe_sum [N, dim_pe]``: the LapPE DeepSet chain and its masked
+    sum over the frequencies as ONE launch (hscn_lappe_fwd); ``seed``: an int flips the sign of whole frequency columns
+    by Philox (training), None leaves them.  Gradients go to ``weights`` / ``biases`` only, through hscn_lappe_bwd, which
+    regenerates the signs from the seed; ``vec`` / ``val`` are constants and one that requires grad is refused."""
+
+    @classmethod
+    def apply(cls, vec: Tensor, val: Tensor, weights, biases, seed: Optional[int] = None) -> Tensor:
+        weights, biases = list(weights), list(biases)
+        for name, t in (("vec", vec), ("val", val)):
+            if t.requires_grad:
+                raise ValueError(f"LapPEDeepSetFn: {name} requires grad, but the Laplacian statistics are constants "
+                                 "of this operator (gradients go to the parameters only)")
+        if vec.dim() != 2 or vec.shape != val.shape:
+            raise ValueError(f"LapPEDeepSetFn: vec and val must both be [N, max_freqs], got {tuple(vec.shape)} and "
+                             f"{tuple(val.shape)}")
+        if not weights or len(weights) != len(biases):
+            raise ValueError("LapPEDeepSetFn: one bias per weight, at least one layer")
+        L, dim_pe = len(weights), int(weights[-1].shape[0])
+        if not lappe_supported(int(vec.shape[1]), dim_pe, L):
+            raise ValueError(f"LapPEDeepSetFn: max_freqs={int(vec.shape[1])}, dim_pe={dim_pe}, layers={L} outside the "
+                             f"kernel's envelope ({LAPPE_ENVELOPE})")
+        widths = lappe_widths(dim_pe, L)
+        for l, (W, b) in enumerate(zip(weights, biases)):
+            if tuple(W.shape) != (widths[l + 1], widths[l]) or tuple(b.shape) != (widths[l + 1],):
+                raise ValueError(f"LapPEDeepSetFn: layer {l} must be [{widths[l + 1]}, {widths[l]}] with a bias of "
+                                 f"{widths[l + 1]}, got {tuple(W.shape)} and {tuple(b.shape)}")
+        flat = [t for wb in zip(weights, biases) for t in wb]
+        return super().apply(vec, val, None if seed is None else int(seed), *flat)
+
+    @staticmethod
+    def _table(params):
+        import ctypes
+        return (ctypes.c_void_p * len(params))(*[ptr(t) for t in params])
+
+    @staticmethod
+    def forward(ctx, vec: Tensor, val: Tensor, seed: Optional[int], *params: Tensor):
+        vec, val = _c(vec), _c(val)
+        params = [_c(t.detach()) for t in params]
+        N, K = vec.shape
+        L, dim_pe = len(params) // 2, int(params[-1].shape[0])
+        out = torch.empty(N, dim_pe, dtype=torch.float32, device=vec.device)
+        flip, seed = (0, 0) if seed is None else (1, seed & 0xFFFFFFFFFFFFFFFF)
+        if N:
+            call("hscn_lappe_fwd", ptr(vec), ptr(val), LapPEDeepSetFn._table(params), N, K, dim_pe, L, flip, seed,
+                 ptr(out), stream())
+        ctx.flip, ctx.seed = flip, seed
+        ctx.save_for_backward(vec, val, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        vec, val, *params = ctx.saved_tensors
+        N, K = vec.shape
+        L, dim_pe = len(params) // 2, int(params[-1].shape[0])
+        total = sum(p.numel() for p in params)
+        if N == 0:
+            gflat = torch.zeros(total, dtype=torch.float32, device=vec.device)
+        else:
+            g = _c(g)
+            gflat = torch.empty(total, dtype=torch.float32, device=vec.device)
+            need = int(_hip.lib().hscn_lappe_workspace_floats(N, K, dim_pe, L))
+            ws = torch.empty(max(need, 1), dtype=torch.float32, device=vec.device)
+            call("hscn_lappe_bwd", ptr(vec), ptr(val), ptr(g), LapPEDeepSetFn._table(params), N, K, dim_pe, L, ctx.flip,
+                 ctx.seed, ptr(gflat), ptr(ws), need, stream())
+        grads, off = [], 0
+        for i, p in enumerate(params):                 # g_params is flat in the parameters' own order and layout
+            grads.append(gflat[off:off + p.numel()].view(p.shape) if ctx.needs_input_grad[3 + i] else None)
+            off += p.numel()
+        return (None, None, None, *grads)
 
 
 # hscn_linear_fwd keeps the whole [O, I] weight in LDS and answers HSCN_E_UNSUPPORTED above 160 KB (csrc/linear.hip:

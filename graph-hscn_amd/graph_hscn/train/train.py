@@ -51,19 +51,29 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
     A ``config.RWSEConfig`` as ``pe_cfg`` selects the random-walk structural encoding instead: the encoder is ONE
     ``RWSENodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb)``, and a batch that arrives without ``rwse`` gets it from
     ``transform.compute_rwse_stats_device`` right before the encoder runs, under ``stats=None`` and ``stats="device"``
-    alike (there is no precomputed-only mode: the statistics are one cheap launch).  Everything else is the same."""
+    alike (there is no precomputed-only mode: the statistics are one cheap launch).  Everything else is the same.
+
+    A ``config.LapPEConfig`` selects the Laplacian positional encoding with the DeepSet model: ONE
+    ``LapPENodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb)`` in eval mode (a frozen pre-stage flips no signs), and a
+    batch without ``eigvecs_sn`` gets its statistics from ``transform.compute_posenc_stats_device`` under ``stats=None``
+    and ``stats="device"`` alike.  (The trainable form is the models' own ``pos_enc``: model/_common.py.)"""
     if stats not in (None, "device"):
         raise ValueError(f"stats must be None or 'device', got {stats!r}")
-    from ..config.config import RWSEConfig
+    from ..config.config import LapPEConfig, RWSEConfig
     from ..data import DataLoader
     from ..encoder.signnet import SignNetNodeEncoder
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     rwse = isinstance(pe_cfg, RWSEConfig)
+    lappe = isinstance(pe_cfg, LapPEConfig)
     if rwse:
         from ..encoder.rwse import RWSENodeEncoder
         from ..transform.rwse import compute_rwse_stats_device
         enc = RWSENodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
+    elif lappe:
+        from ..encoder.lappe import LapPENodeEncoder
+        enc = LapPENodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
+        enc.eval()                                 # a frozen pre-stage: no sign flips
     else:
         enc = SignNetNodeEncoder(pe_cfg, num_features, pe_cfg.dim_emb).to(device)
         enc.engine = "auto"
@@ -80,7 +90,7 @@ def compute_posenc(loaders, data_cfg, num_features: int, pe_cfg, logger=None, de
                 if rwse:
                     if getattr(batch, "rwse", None) is None:
                         compute_rwse_stats_device(batch, is_undirected, pe_cfg)
-                elif stats == "device" and getattr(batch, "eigvecs_sn", None) is None:
+                elif (lappe or stats == "device") and getattr(batch, "eigvecs_sn", None) is None:
                     from ..transform.posenc import compute_posenc_stats_device
                     compute_posenc_stats_device(batch, is_undirected, pe_cfg)
                 data_list.append(enc(batch))

@@ -1752,6 +1752,46 @@ int hscn_exph_attn_bwd_type(const int32_t* trowptr /*[T + 1]*/, const int32_t* t
                             int T, int heads, int head_dim, int32_t* flag /*[1]*/, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * LapPE node encoder, DeepSet model (csrc/lappe.hip).  Purely additive to ABI 24.
+ *
+ * vec, val f32 [N, K] (K = max_freqs): eigenvector entry and eigenvalue per node and frequency, what
+ * hscn_lap_eig_stats writes; a NaN in vec[i, k] marks padding.  params_host: a HOST array of 2 * layers device
+ * pointers W_0, b_0, W_1, b_1, ... with W_l f32 [H_l, H_{l-1}] row-major, b_l [H_l], H_{-1} = 2, H_l = 2 * dim_pe
+ * for l < layers - 1 and H_{layers-1} = dim_pe (layers = 1: one 2 -> dim_pe Linear).
+ *     u_ik = (s_k vec[i,k], val[i,k])                          NaN entries read as 0
+ *     a^0 = relu(W_0 u + b_0),  a^l = relu(W_l a^{l-1} + b_l)
+ *     out[i] = sum over the k with vec[i,k] not NaN of a^{layers-1}_ik        [N, dim_pe]; all NaN: zeros
+ *   s_k = -1 iff flip != 0 and word 0 of philox4x32_10(seed, ctr = k) is >= 2^31, else +1: one sign per frequency
+ *   column for the whole call, computed in the kernels from seed (no sign tensor).
+ * hscn_lappe_fwd: ONE launch; a workgroup is four waves over the same hscn_lappe_tile() = 64 nodes, one node per lane,
+ *   wave q taking the frequencies k = q, q + 4, ...; the parameters are staged in LDS and read as broadcasts, the chain
+ *   stays in registers (widths are template parameters): no [N, K, H] tensor exists.  Every pre-activation starts at
+ *   the bias and takes fmaf(input_i, W[o][i], .) for i ascending; a lane adds its frequencies in ascending k and wave 0
+ *   adds the four waves' sums in wave order.  out[i] depends on row i of vec / val and the parameters alone: bitwise
+ *   independent of N, of the row's place and of the grid.  out must be 16-byte aligned.
+ * hscn_lappe_bwd: TWO launches; gradients for the parameters only (the statistics are constants).  g_params f32
+ *   [sum_l (H_{l-1} + 1) H_l], flat in the order W_0, b_0, W_1, b_1, ... as the tensors are laid out.  The first launch
+ *   recomputes the chain from vec, val and seed in the forward's order (the ReLU gates are the forward's) and stores
+ *   one partial gradient per workgroup to workspace -- a workgroup walks a contiguous range of the N * K (node,
+ *   frequency) samples, up to 256 per pass in sample order, parameters and activations of the pass in LDS -- and the
+ *   second adds the partials in workgroup order in a fixed tree.  No float atomics: two runs give the same bits.
+ *   workspace: hscn_lappe_workspace_floats(N, max_freqs, dim_pe, layers) floats (min(512, ceil(N K / 256)) partials),
+ *   not initialised by the caller.
+ * hscn_lappe_supported: 1 for 1 <= max_freqs <= 64, dim_pe a multiple of 4 in [4, 32], 1 <= layers <= 4.
+ *   HSCN_E_BADARG for null pointers and negative N, HSCN_E_UNSUPPORTED where hscn_lappe_supported is 0,
+ *   HSCN_E_WORKSPACE for a short workspace; all before any launch.  N = 0 launches nothing (g_params is then not
+ *   written).  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_lappe_supported(int max_freqs, int dim_pe, int layers);
+int hscn_lappe_tile(void);
+int64_t hscn_lappe_workspace_floats(int64_t N, int max_freqs, int dim_pe, int layers);
+int hscn_lappe_fwd(const float* vec, const float* val, const void* const* params_host, int64_t N, int max_freqs,
+                   int dim_pe, int layers, int flip, uint64_t seed, float* out /*[N, dim_pe]*/, void* stream);
+int hscn_lappe_bwd(const float* vec, const float* val, const float* g_out /*[N, dim_pe]*/,
+                   const void* const* params_host, int64_t N, int max_freqs, int dim_pe, int layers, int flip,
+                   uint64_t seed, float* g_params, float* workspace, int64_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
