@@ -650,22 +650,40 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
   // partial layout: per layer {W_ll [H*fin], b_ll [H]}, then W1 [H*H], b1 [H], W2 [C*H], b2 [C], loss column
   int off_head = 0;
   for (int l = 0; l < L; ++l) off_head += H * (l == 0 ? F : H) + H;
-  const int oW1 = off_head, ob1 = oW1 + H * H, oW2 = ob1 + H, ob2 = oW2 + C * H;
-  for (int idx = threadIdx.x; idx < C * H; idx += RT) {
-    const int c = idx / H, k = idx - c * H;
-    part[oW2 + idx] = gpl[c] * zz[k];
+  // The head's four outer-product partials (gpl (x) zz, gpl, gz (x) pol, gz: ~440 global stores).  The compile-time
+  // layout at H = 16 (PLATE: 16 waves, C <= StepLCaps::C) writes them from waves NW/2 .. NW/2 + 3 behind their row tile
+  // of the first backward layer: waves that own one tile or none in every layer and fold nothing, so the stores stand
+  // in nobody's chain; no partial has more elements than those 256 threads, so it is one predicated store per partial
+  // and thread, without loop state in scalar registers inside the layer loop.  The operands sit in `vec` / `headw`,
+  // which nobody rewrites during the backward.  Every other form writes them here, with all threads.
+  constexpr bool PLATE = H == 16 && NW >= 8 && LFIX;
+  constexpr int PW0 = NW / 2, PNW = 4;
+  static_assert(!PLATE || (StepLCaps::C * H <= PNW * 64 && H * H <= PNW * 64), "one element per thread and partial");
+  auto head_partials_late = [&](const int t) {   // t: 0 .. PNW * 64 - 1
+    const int oW1 = off_head, ob1 = oW1 + H * H, oW2 = ob1 + H, ob2 = oW2 + C * H;
+    if (t < C * H) part[oW2 + t] = gpl[t / H] * zz[t % H];
+    if (t < C) part[ob2 + t] = gpl[t];
+    if (t < H * H) part[oW1 + t] = gz[t / H] * pol[t % H];
+    if (t < H) part[ob1 + t] = gz[t];
+  };
+  if (!PLATE) {
+    const int oW1 = off_head, ob1 = oW1 + H * H, oW2 = ob1 + H, ob2 = oW2 + C * H;
+    for (int idx = threadIdx.x; idx < C * H; idx += RT) {
+      const int c = idx / H, k = idx - c * H;
+      part[oW2 + idx] = gpl[c] * zz[k];
+    }
+    for (int c = threadIdx.x; c < C; c += RT) part[ob2 + c] = gpl[c];
+    for (int idx = threadIdx.x; idx < H * H; idx += RT) {
+      const int o = idx / H, k = idx - o * H;
+      part[oW1 + idx] = gz[o] * pol[k];
+    }
+    if (threadIdx.x < H) part[ob1 + threadIdx.x] = gz[threadIdx.x];
   }
-  for (int c = threadIdx.x; c < C; c += RT) part[ob2 + c] = gpl[c];
   if (!fast_head && threadIdx.x == RT - 64) {   // the graph's loss terms, summed in class order
     float sl = 0.f;
     for (int c = 0; c < C; ++c) sl += ltl[c];
     part[A.Pn] = sl;
   }
-  for (int idx = threadIdx.x; idx < H * H; idx += RT) {
-    const int o = idx / H, k = idx - o * H;
-    part[oW1 + idx] = gz[o] * pol[k];
-  }
-  if (threadIdx.x < H) part[ob1 + threadIdx.x] = gz[threadIdx.x];
   float* G = aL;                  // gradient of the current layer's output, masked in place
   float* GH = L >= 2 ? buf(0) : buf(2);
   if constexpr (H != 16) {
@@ -858,6 +876,7 @@ __device__ __forceinline__ void hscn_step_local(const StepArgs& A, const int g) 
         }
         finish(rt, z);
       }
+      if (PLATE && it == 0 && wave >= PW0 && wave < PW0 + PNW) head_partials_late((int)threadIdx.x - PW0 * 64);
       if (it > 0) {   // the folders of the previous layer's partial tiles have signed off (see above)
         while (__hip_atomic_load(fold_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < it * NFW)
           __builtin_amdgcn_s_sleep(1);

@@ -44,7 +44,7 @@ def main():
     torch.cuda.synchronize()
     cols = ["prologue", "build", "pro+build", "start->fwdL0 end", "head", "head bwd", "head+bwd", "local total",
             "virt ->L0 reduce", "virt total", "max local", "max virtual",
-            "virt L0 begin", "virt L1 begin", "virt L2 begin"]
+            "virt L0 begin", "virt L1 begin", "virt L2 begin", "bwd layer 2", "bwd layer 1", "bwd layer 0"]
     out = []
     for _ in range(N):
         buf.zero_()
@@ -54,7 +54,8 @@ def main():
         l, v = st[g], st[B + g]
         out.append([l[1] - l[0], l[3] - l[1], l[3] - l[0], l[5] - l[0], l[13] - l[12], l[14] - l[13], l[14] - l[12],
                     l[61] - l[0], v[5] - v[0], v[62] - v[0], (st[:B, 61] - st[:B, 0]).max(),
-                    (st[B:, 62] - st[B:, 0]).max(), v[4] - v[0], v[8] - v[0], v[12] - v[0]])
+                    (st[B:, 62] - st[B:, 0]).max(), v[4] - v[0], v[8] - v[0], v[12] - v[0],
+                    l[22] - l[14], l[19] - l[22], l[16] - l[19]])
     a = np.array(out)
     print(f"graph {g} n={sizes[g]}, {ids}, {N} launches: median (min - max) cycles")
     for j, c in enumerate(cols):
