@@ -270,6 +270,15 @@ _SIGNATURES = {
     "hscn_lappe_workspace_floats": (c_int64, [c_int64, c_int, c_int, c_int]),
     "hscn_lappe_fwd": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_int, c_uint64, P, P]),
     "hscn_lappe_bwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, c_int, c_uint64, P, P, c_int64, P]),
+    # PNAConv's aggregate: mean / min / max / sum / std under degree scalers (csrc/pna.hip; additive to ABI 24);
+    # `aggregators_host` / `scalers_host`: host arrays of int32 codes (nn.functional.PNA_AGGREGATORS / PNA_SCALERS)
+    "hscn_pna_supported": (c_int, [c_int, c_int, c_int]),
+    "hscn_pna_long_row": (c_int, []),
+    "hscn_pna_chunk": (c_int, []),
+    "hscn_pna_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, c_int, P, c_int, c_float, P, P]),
+    "hscn_pna_bwd_fold": (c_int, [P, P, P, P, P, c_int64, c_int, P, c_int, P, c_int, c_float, P]),
+    "hscn_pna_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
+    "hscn_pna_bwd_edge": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
 }
 
 

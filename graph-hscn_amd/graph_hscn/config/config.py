@@ -12,7 +12,7 @@ from typing import Callable, Optional
 
 from torch.optim import Adagrad, Adam, AdamW
 
-from ..nn.conv import GINE, EdgeTransformerConv, GATConv, GatedGCNConv, GCNConv, TransformerConv
+from ..nn.conv import GINE, PNA, EdgeTransformerConv, GATConv, GatedGCNConv, GCNConv, PNAEdge, TransformerConv
 from ..nn.functional import Activation
 
 # defaults.py:1-39
@@ -54,8 +54,14 @@ ACT_DICT: dict[str, Callable] = {  # config.py:13-18
 # keys and values.  They take ``heads`` (MPNNConfig.heads, GPSConfig.num_heads, HSCNConfig.heads), run layered, and the
 # first also builds HSCN's relations (build_conv_relation "TransformerConv").  The key is not "transformer": that name
 # stays refused (GPS's plain Transformer layer is local_conv_type=None).
+# "pna" / "pna_edge" (extension): nn/conv.py PNA / PNAEdge = PyG's PNAConv with one tower (csrc/pna.hip), several
+# aggregators of the in-edge messages under degree scalers; the second feeds ``batch.edge_attr`` through its
+# ``edge_encoder`` into the messages.  Which aggregators and scalers, and the training set's ``avg_deg_log``, come from
+# a ``PNAConfig`` (MPNNConfig.pna / GPSConfig.pna; None: mean, min, max, std under the identity scaler).  They build the
+# MPNN baseline and the GPS local branch, run layered, and HSCN's relations do not take them yet.
 CONV_DICT: dict[str, type] = {"gcn": GCNConv, "gat": GATConv, "gine": GINE, "gatedgcn": GatedGCNConv,
-                              "transformerconv": TransformerConv, "transformerconv_edge": EdgeTransformerConv}
+                              "transformerconv": TransformerConv, "transformerconv_edge": EdgeTransformerConv,
+                              "pna": PNA, "pna_edge": PNAEdge}
 # conv_type whose layers are built with ``heads``
 MULTI_HEAD_CONVS = ("transformerconv", "transformerconv_edge")
 OPTIM_DICT: dict[str, type] = {"adagrad": Adagrad, "adam": Adam, "adamW": AdamW}  # config.py:24-28
@@ -65,7 +71,9 @@ TASK_LEVELS = ("graph", "node", "link")  # extension: the reference serves "grap
 NODE_ENCODERS = ("atom",)
 EDGE_ENCODERS = ("bond",)
 # conv_type / local_conv_type whose layers read ``edge_attr`` (nn/conv.py ``uses_edge_attr``): what an edge encoder feeds
-EDGE_AWARE_CONVS = ("gine", "gatedgcn", "transformerconv_edge")
+EDGE_AWARE_CONVS = ("gine", "gatedgcn", "transformerconv_edge", "pna_edge")
+# conv_type / local_conv_type whose layers are built from a PNAConfig
+PNA_CONVS = ("pna", "pna_edge")
 
 
 def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
@@ -94,6 +102,63 @@ def check_heads(heads, hidden_channels, conv_type) -> None:
         raise ValueError(f"heads={heads} needs a multi-head convolution {MULTI_HEAD_CONVS}, got {conv_type!r}")
     if hidden_channels % heads:
         raise ValueError(f"hidden_channels {hidden_channels} must be divisible by heads {heads}.")
+
+
+@dataclass
+class PNAConfig:
+    """What the "pna" / "pna_edge" layers of a model are built with (nn/conv.py PNAConv): ``aggregators`` out of mean,
+    min, max, sum, std; ``scalers`` out of identity, amplification, attenuation; ``avg_deg_log``, the training set's mean
+    of ``log(in-degree + 1)``, required beside a scaler other than identity (``from_graphs`` computes it)."""
+    aggregators: tuple = ("mean", "min", "max", "std")
+    scalers: tuple = ("identity",)
+    avg_deg_log: Optional[float] = None
+
+    def __post_init__(self) -> None:
+        from ..nn.functional import pna_codes
+        for name in ("aggregators", "scalers"):
+            v = getattr(self, name)
+            if isinstance(v, str) or not isinstance(v, (tuple, list)):
+                raise ValueError(f"{name} must be a tuple of names, got {v!r}")
+            setattr(self, name, tuple(v))
+        for s in self.scalers:
+            if s in ("linear", "inverse_linear"):
+                raise ValueError(f"the scaler {s!r} is not provided (identity, amplification, attenuation are)")
+        pna_codes(self.aggregators, self.scalers)
+        a = self.avg_deg_log
+        if a is not None and (isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 < float(a) < float("inf")):
+            raise ValueError(f"avg_deg_log must be a positive, finite number or None, got {a!r}")
+        if a is None and any(s != "identity" for s in self.scalers):
+            raise ValueError(f"scalers {self.scalers} need avg_deg_log (PNAConfig.from_graphs computes it from the "
+                             "training graphs)")
+
+    @staticmethod
+    def avg_deg_log_of(graphs) -> float:
+        """The mean of ``log(in-degree + 1)`` over every node of ``graphs`` (``Data`` with ``edge_index`` and
+        ``num_nodes``): PyG's ``avg_deg['log']`` of the training set, on the host in float64."""
+        import torch
+        total, nodes = 0.0, 0
+        for g in graphs:
+            n = int(g.num_nodes)
+            deg = torch.bincount(g.edge_index[1].cpu(), minlength=n).to(torch.float64)
+            total += float(torch.log(deg + 1.0).sum())
+            nodes += n
+        if nodes == 0:
+            raise ValueError("avg_deg_log needs at least one node")
+        return total / nodes
+
+    @classmethod
+    def from_graphs(cls, graphs, aggregators=("mean", "min", "max", "std"),
+                    scalers=("identity", "amplification", "attenuation")) -> "PNAConfig":
+        return cls(tuple(aggregators), tuple(scalers), cls.avg_deg_log_of(graphs))
+
+
+def _check_pna(pna, conv_type) -> None:
+    if pna is None:
+        return
+    if not isinstance(pna, PNAConfig):
+        raise ValueError(f"pna must be a PNAConfig or None, got {type(pna).__name__}")
+    if conv_type is None or conv_type.lower() not in PNA_CONVS:
+        raise ValueError(f"pna=PNAConfig(...) needs a PNA convolution {PNA_CONVS}, got {conv_type!r}")
 
 
 DATASETS_NUM_FEATURES: dict[str, int] = {"peptides_func": 9, "peptides_struct": 9}
@@ -139,11 +204,14 @@ class MPNNConfig:  # config.py:49-73
     # RWSEConfig whose dim_emb is hidden_channels; pe_undirected: the edge lists hold both directions
     pos_enc: Optional[object] = None
     pe_undirected: bool = True
+    # extension: aggregators, scalers and avg_deg_log of conv_type "pna" / "pna_edge" (None: PNAConfig's defaults)
+    pna: Optional[PNAConfig] = None
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         _check_encoders(self.node_encoder, self.edge_encoder, self.conv_type)
+        _check_pna(self.pna, self.conv_type)
         _check_pos_enc(self.pos_enc, self.hidden_channels)
         check_heads(self.heads, self.hidden_channels, self.conv_type)
         if self.dropout and not (0.0 <= self.dropout <= 1.0):
@@ -159,8 +227,8 @@ GPS_NORMS = ("layer", "batch", None)
 @dataclass
 class GPSConfig:
     """The GPS model (extension; model/gps.py): ``num_layers`` GPS layers of width ``hidden_channels`` -- a local
-    convolution ``local_conv_type`` ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge" of
-    CONV_DICT, or None: the plain Transformer layer; "gatedgcn" is GraphGPS's published pairing: a ``GatedGCNLayer``
+    convolution ``local_conv_type`` ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge", "pna",
+    "pna_edge" of CONV_DICT, or None: the plain Transformer layer; "gatedgcn" is GraphGPS's published pairing: a ``GatedGCNLayer``
     that also updates the edge features; the two TransformerConv keys take ``num_heads`` heads as well) beside
     per-graph self-attention of ``num_heads`` heads, then a feed-forward block -- behind a Linear node encoder.  The
     head width ``hidden_channels / num_heads`` must be a multiple of 4 in [4, 64] and ``hidden_channels`` at most 512
@@ -192,11 +260,14 @@ class GPSConfig:
     # dim_emb is hidden_channels; pe_undirected: the edge lists hold both directions
     pos_enc: Optional[object] = None
     pe_undirected: bool = True
+    # aggregators, scalers and avg_deg_log of local_conv_type "pna" / "pna_edge" (None: PNAConfig's defaults)
+    pna: Optional[PNAConfig] = None
 
     def __post_init__(self):
         if self.task_level not in TASK_LEVELS:
             raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
         _check_encoders(self.node_encoder, self.edge_encoder, self.local_conv_type)
+        _check_pna(self.pna, self.local_conv_type)
         _check_pos_enc(self.pos_enc, self.hidden_channels)
         if self.attn_bias not in (None, "spd"):
             raise ValueError(f"attn_bias must be 'spd' or None, got {self.attn_bias!r}")

@@ -62,8 +62,12 @@ class GPS(LinkLevel, PosEnc, nn.Module):
                  norm: Optional[str] = "layer", task_level: str = "graph", node_encoder: Optional[str] = None,
                  edge_encoder: Optional[str] = None, attn_bias: Optional[str] = None, spd_max_dist: int = 20,
                  global_model: str = "attention", expander_degree: int = 6, num_virtual_nodes: int = 1,
-                 add_local_edges: bool = True, expander_seed: int = 0, pos_enc=None, pe_undirected: bool = True) -> None:
-        """``pos_enc`` (a ``config.LapPEConfig`` or ``config.RWSEConfig`` with ``dim_emb = hidden_channels``): the model
+                 add_local_edges: bool = True, expander_seed: int = 0, pos_enc=None, pe_undirected: bool = True,
+                 pna=None) -> None:
+        """``pna`` (a ``config.PNAConfig`` or None): the aggregators, scalers and ``avg_deg_log`` of every layer's local
+        branch with ``local_conv`` "pna" / "pna_edge" (None: the layer's defaults).
+
+        ``pos_enc`` (a ``config.LapPEConfig`` or ``config.RWSEConfig`` with ``dim_emb = hidden_channels``): the model
         owns a trainable positional encoder ``pe_encoder`` (``model/_common.py PosEnc``); the node encoder is built at
         width ``D - dim_pe`` and the layers see ``[h | pe]``.  The statistics are the batch's own or computed once per
         batch on the device (``pe_undirected``: the edge list holds both directions).  It combines with ``attn_bias``
@@ -126,13 +130,15 @@ class GPS(LinkLevel, PosEnc, nn.Module):
         spd_buckets = self.spd_max_dist + 1 if attn_bias == "spd" else None
         if global_model == "exphormer":
             self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, global_model="exphormer",
-                                                 num_virtual_nodes=self.num_virtual_nodes) for _ in range(num_layers))
-        else:
-            self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, spd_buckets=spd_buckets)
+                                                 num_virtual_nodes=self.num_virtual_nodes, pna=pna)
                                         for _ in range(num_layers))
+        else:
+            self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, spd_buckets=spd_buckets,
+                                                 pna=pna) for _ in range(num_layers))
         if edge_encoder is not None:
             if not self.layers[0].uses_edge_attr:
-                raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware local_conv ('gine' or 'gatedgcn'), "
+                raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware local_conv ('gine', 'gatedgcn', "
+                                 f"'transformerconv_edge' or 'pna_edge'), "
                                  f"not {local_conv!r}")
             self.edge_encoder = EDGE_ENCODERS[edge_encoder](D)
         elif self.layers[0].updates_edge_attr:      # "gatedgcn": edge features are a state of width D
@@ -264,4 +270,4 @@ def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:
                getattr(model_cfg, "global_model", "attention"), getattr(model_cfg, "expander_degree", 6),
                getattr(model_cfg, "num_virtual_nodes", 1), getattr(model_cfg, "add_local_edges", True),
                getattr(model_cfg, "expander_seed", 0), getattr(model_cfg, "pos_enc", None),
-               getattr(model_cfg, "pe_undirected", True))
+               getattr(model_cfg, "pe_undirected", True), getattr(model_cfg, "pna", None))

@@ -287,6 +287,9 @@ def build_conv_relation(conv_type: str, hidden_channels: int, in_channels=None, 
     if conv_type.lower() == "gatedgcn":
         raise ValueError("conv_type 'GatedGCN' needs edge features, and the hetero graph carries no edge features yet "
                          "(HeteroData has no edge_attr; the MPNN baseline and GPS take 'gatedgcn')")
+    if conv_type.lower() in ("pna", "pna_edge"):
+        raise ValueError(f"conv_type {conv_type!r}: HSCN's relations do not take PNAConv yet (the MPNN baseline and GPS "
+                         "take 'pna' and 'pna_edge')")
     if conv_type.lower() == "gine":
         raise ValueError("conv_type 'GINE' needs edge features, and the hetero graph carries no edge features yet "
                          "(HeteroData has no edge_attr; the MPNN baseline takes conv_type 'gine')")

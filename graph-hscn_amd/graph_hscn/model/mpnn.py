@@ -21,7 +21,7 @@ from torch import Tensor
 from .. import _hip
 from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig
 from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
-from ..nn.conv import GCNConv, Linear, TransformerConv
+from ..nn.conv import GCNConv, Linear, PNAConv, TransformerConv
 from ..nn import functional as Fh
 from ..nn.norm import BatchNorm1d, LayerNorm
 from ..nn.pool import global_mean_pool
@@ -32,8 +32,13 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
     def __init__(self, conv: type, activation: Callable, num_features: int, hidden_channels: int,
                  num_classes: int, num_layers: int, dropout: float = 0.0, use_batch_norm: bool = False,
                  use_layer_norm: bool = False, task_level: str = "graph", node_encoder: Optional[str] = None,
-                 edge_encoder: Optional[str] = None, heads: int = 1, pos_enc=None, pe_undirected: bool = True) -> None:
-        """``pos_enc`` (extension; a ``config.LapPEConfig`` or ``config.RWSEConfig`` with ``dim_emb = hidden_channels``):
+                 edge_encoder: Optional[str] = None, heads: int = 1, pos_enc=None, pe_undirected: bool = True,
+                 pna=None) -> None:
+        """``pna`` (extension; a ``config.PNAConfig`` or None): with a PNA ``conv`` (``PNA`` / ``PNAEdge``) every layer is
+        built with its aggregators, scalers and ``avg_deg_log`` (None: the layer's defaults); such a model is
+        layered-only.
+
+        ``pos_enc`` (extension; a ``config.LapPEConfig`` or ``config.RWSEConfig`` with ``dim_emb = hidden_channels``):
         the model owns a trainable positional encoder ``pe_encoder`` (``model/_common.py PosEnc``).  The node features
         are embedded to ``hidden_channels - dim_pe`` columns -- by the ``AtomEncoder`` of ``node_encoder="atom"``, else
         by a new ``linear_x = Linear(F, H - dim_pe)`` -- the encoder's ``dim_pe`` columns are appended and the first
@@ -57,8 +62,12 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
         check_encoders(node_encoder, edge_encoder)
         if edge_encoder is not None and not getattr(conv, "uses_edge_attr", False):
             raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution (conv_type 'gine', "
-                             f"'gatedgcn' or 'transformerconv_edge'), not {getattr(conv, '__name__', conv)}")
+                             f"'gatedgcn', 'transformerconv_edge' or 'pna_edge'), not {getattr(conv, '__name__', conv)}")
         multi_head = isinstance(conv, type) and issubclass(conv, TransformerConv)
+        is_pna = isinstance(conv, type) and issubclass(conv, PNAConv)
+        if pna is not None and not is_pna:
+            raise ValueError(f"pna=PNAConfig(...) needs a PNA convolution (conv_type 'pna' or 'pna_edge'), not "
+                             f"{getattr(conv, '__name__', conv)}")
         if not isinstance(heads, int) or heads < 1:
             raise ValueError(f"heads must be a positive int, not {heads!r}")
         if heads != 1 and not multi_head:
@@ -70,7 +79,7 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
         self.task_level = task_level
         self.num_layers = num_layers
         self.encoder_kinds = (node_encoder, edge_encoder)
-        if node_encoder is not None or edge_encoder is not None or multi_head:
+        if node_encoder is not None or edge_encoder is not None or multi_head or is_pna:
             # train.batching.refuse_layered_only: the resident and device-dataset entry points refuse this model by name
             self.layered_only = True
         x_width = self._init_pos_enc(pos_enc, pe_undirected, hidden_channels)     # H - dim_pe with a positional encoder
@@ -88,10 +97,11 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
                 self.conv_layers.append(conv(hidden_channels, hidden_channels // heads, heads=heads))
             self.conv_layers.append(conv(hidden_channels, num_classes, heads=1))
         else:
-            self.conv_layers.append(conv(num_features, hidden_channels))
+            kw = {} if pna is None else dict(aggregators=pna.aggregators, scalers=pna.scalers, avg_deg_log=pna.avg_deg_log)
+            self.conv_layers.append(conv(num_features, hidden_channels, **kw))
             for _ in range(num_layers - 2):
-                self.conv_layers.append(conv(hidden_channels, hidden_channels))
-            self.conv_layers.append(conv(hidden_channels, num_classes))
+                self.conv_layers.append(conv(hidden_channels, hidden_channels, **kw))
+            self.conv_layers.append(conv(hidden_channels, num_classes, **kw))
         self.use_batch_norm = use_batch_norm
         if use_layer_norm:                                                  # mpnn.py:35-38 (sic: not use_batch_norm)
             self.bns = nn.ModuleList(BatchNorm1d(hidden_channels) for _ in range(num_layers - 1))
@@ -119,6 +129,9 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
         for c in self.conv_layers:
             if isinstance(c, TransformerConv):
                 return (f"convolution {type(c).__name__} (multi-head attention over the in-edges has no one-launch, "
+                        "resident or captured form; the model runs on the layered operators)")
+            if isinstance(c, PNAConv):
+                return ("convolution PNAConv (the multi-aggregator reduction over the in-edges has no one-launch, "
                         "resident or captured form; the model runs on the layered operators)")
         if any(self.encoder_kinds):
             return encoder_reason(*self.encoder_kinds)
@@ -213,7 +226,8 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
         ea = getattr(batch, "edge_attr", None)
         if ea is None:
             kind = "gatedgcn" if any(getattr(c, "updates_edge_attr", False) for c in self.conv_layers) else \
-                ("transformerconv_edge" if isinstance(self.conv_layers[0], TransformerConv) else "gine")
+                ("transformerconv_edge" if isinstance(self.conv_layers[0], TransformerConv) else
+                 ("pna_edge" if isinstance(self.conv_layers[0], PNAConv) else "gine"))
             raise ValueError(f"the model has edge-aware convolutions (conv_type {kind!r}) and the batch carries no "
                              "edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
         if self.encoder_kinds[1] is not None:
@@ -271,4 +285,4 @@ def build_mpnn(model_cfg: MPNNConfig, num_features: int, num_classes: int) -> MP
                 model_cfg.use_batch_norm, model_cfg.use_layer_norm, getattr(model_cfg, "task_level", "graph"),
                 getattr(model_cfg, "node_encoder", None), getattr(model_cfg, "edge_encoder", None),
                 getattr(model_cfg, "heads", 1), getattr(model_cfg, "pos_enc", None),
-                getattr(model_cfg, "pe_undirected", True))
+                getattr(model_cfg, "pe_undirected", True), getattr(model_cfg, "pna", None))

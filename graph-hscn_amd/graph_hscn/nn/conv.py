@@ -270,6 +270,153 @@ class GINE(GINEConv):
         return self.nn[2](self.nn[0](z, act="relu"), act=act)     # the middle ReLU in the first Linear's epilogue
 
 
+def pna_avg_deg_log(deg) -> float:
+    """PyG's ``avg_deg['log']`` from an in-degree histogram (``deg[d]`` = number of training nodes of in-degree d):
+    the mean of ``log(d + 1)`` over the nodes, on the host in float64."""
+    hist = [float(v) for v in (deg.tolist() if hasattr(deg, "tolist") else deg)]
+    nodes = sum(hist)
+    if not hist or any(v < 0 for v in hist) or nodes <= 0:
+        raise ValueError("PNAConv: deg must be a histogram of in-degrees with at least one node")
+    return sum(math.log(d + 1.0) * n for d, n in enumerate(hist)) / nodes
+
+
+class PNAConv(nn.Module):
+    """PyG PNAConv with ``towers=1, pre_layers=1, post_layers=1, divide_input=False`` (GraphGPS's configuration):
+
+        m_k   = pre_nn(cat[x_i, x_j, edge_encoder(e_k)])          j = edge_index[0, k], i = edge_index[1, k]
+        agg_i = cat over scalers s, aggregators x of  scaler_s(deg_i) * aggregator_x({m_k: dst_k = i})
+        out_i = lin(post_nn(cat[x_i, agg_i]))
+
+    every edge as given (loops and repeated edges count).  ``aggregators``: out of mean, min, max, sum, std
+    (``sqrt(relu(mean(m^2) - mean(m)^2) + 1e-5)``); a node without in-edges gets 0, and ``sqrt(1e-5)`` for std.
+    ``scalers``: identity, amplification ``log(d + 1) / avg_deg_log``, attenuation (its inverse), ``d = max(deg_i, 1)``;
+    ``avg_deg_log`` is the training set's mean of ``log(deg + 1)``, given directly or through ``deg``, PyG's in-degree
+    histogram, and required only beside a scaler other than identity.  Parameters and ``state_dict`` keys are PyG's:
+    ``pre_nns.0.0`` = Linear(3F, F) (2F without ``edge_dim``), ``post_nns.0.0`` = Linear((S A + 1) F, out), ``lin`` =
+    Linear(out, out), ``edge_encoder`` = Linear(edge_dim, F) (``-1`` is materialised on first use).
+
+    The message is linear in its three parts, so the column blocks of the one ``pre_nns.0.0.weight`` are applied to
+    the nodes and edges separately (``Linear``) and the reductions are one HIP launch that never writes the [E, F]
+    messages (csrc/pna.hip).  min / max ties go to the first edge of the row in CSR order, and the gradient with
+    them (torch's ``scatter_reduce`` splits it evenly).  ``edge_attr`` may carry a gradient.
+
+    Not provided, refused by name: ``towers != 1``, ``pre_layers != 1``, ``post_layers != 1``, ``divide_input=True``,
+    ``train_norm=True`` and the scalers ``linear`` and ``inverse_linear``."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggregators, scalers, deg=None,
+                 edge_dim: Optional[int] = None, avg_deg_log: Optional[float] = None, towers: int = 1,
+                 pre_layers: int = 1, post_layers: int = 1, divide_input: bool = False, train_norm: bool = False):
+        super().__init__()
+        if towers != 1:
+            raise NotImplementedError(f"PNAConv(towers={towers}): one tower is provided (towers=1)")
+        if pre_layers != 1:
+            raise NotImplementedError(f"PNAConv(pre_layers={pre_layers}): the message is one Linear (pre_layers=1), "
+                                      "which is what lets the operator reduce its three parts separately")
+        if post_layers != 1:
+            raise NotImplementedError(f"PNAConv(post_layers={post_layers}): one post Linear is provided (post_layers=1)")
+        if divide_input:
+            raise NotImplementedError("PNAConv(divide_input=True) splits the input between towers; one tower is provided")
+        if train_norm:
+            raise NotImplementedError("PNAConv(train_norm=True): a trainable avg_deg is not provided")
+        aggregators, scalers = tuple(aggregators), tuple(scalers)
+        for s in scalers:
+            if s in ("linear", "inverse_linear"):
+                raise NotImplementedError(f"PNAConv: the scaler {s!r} is not provided "
+                                          f"(scalers are out of {Fh.PNA_SCALERS})")
+        Fh.pna_codes(aggregators, scalers)
+        in_channels, out_channels = int(in_channels), int(out_channels)
+        if not 1 <= in_channels <= Fh.PNA_MAX_WIDTH:            # (the library's answer is asked at the first launch)
+            raise ValueError(f"PNAConv: in_channels = {in_channels} outside the kernel's envelope ({Fh.PNA_ENVELOPE})")
+        if avg_deg_log is None and deg is not None:
+            avg_deg_log = pna_avg_deg_log(deg)
+        if any(s != "identity" for s in scalers):
+            if avg_deg_log is None:
+                raise ValueError(f"PNAConv: scalers {scalers} need deg (the in-degree histogram of the training set) "
+                                 "or avg_deg_log")
+            if not 0.0 < float(avg_deg_log) < float("inf"):
+                raise ValueError(f"PNAConv: avg_deg_log must be positive and finite, got {avg_deg_log!r}")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.aggregators, self.scalers = aggregators, scalers
+        self.avg_deg_log = None if avg_deg_log is None else float(avg_deg_log)
+        self.edge_dim = edge_dim
+        self.towers, self.divide_input = 1, False
+        F = in_channels
+        self.edge_encoder = Linear(edge_dim, F) if edge_dim is not None else None
+        self.pre_nns = nn.ModuleList([nn.Sequential(Linear((3 if edge_dim is not None else 2) * F, F))])
+        self.post_nns = nn.ModuleList([nn.Sequential(Linear((len(aggregators) * len(scalers) + 1) * F, out_channels))])
+        self.lin = Linear(out_channels, out_channels)
+
+    def aggregate(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Optional[Tensor] = None) -> Tensor:
+        """[N, S A F]: the scaled aggregators of the messages."""
+        if not isinstance(x, Tensor):
+            raise TypeError("PNAConv takes one node feature tensor")
+        if x.dim() != 2 or x.size(1) != self.in_channels:
+            raise ValueError(f"PNAConv: x must be [N, {self.in_channels}], got {tuple(x.shape)}")
+        if self.edge_encoder is not None:
+            if edge_attr is None:
+                raise ValueError("PNAConv(edge_dim=...) needs edge_attr [E, edge_dim]")
+            if edge_attr.dim() != 2:
+                raise ValueError(f"edge_attr must be [E, edge_dim], got {tuple(edge_attr.shape)}")
+            if not edge_attr.is_floating_point():
+                raise TypeError(f"PNAConv: edge_attr must be float32, got {edge_attr.dtype}")
+            self.edge_encoder.materialize(edge_attr.size(-1), x)
+        elif edge_attr is not None:
+            raise ValueError("PNAConv was built without edge_dim and cannot take edge_attr")
+        n, F = x.size(0), self.in_channels
+        grad = torch.is_grad_enabled()
+        rel = _relation(edge_index, n, n, both=grad)
+        if grad:
+            rel.csr_t                       # (a relation built elsewhere without it: the source walk needs it)
+        if edge_attr is not None and edge_attr.size(0) != rel.num_edges:
+            raise ValueError(f"edge_attr is {tuple(edge_attr.shape)}; the relation has {rel.num_edges} edges")
+        pre = self.pre_nns[0][0]
+        a = Fh.linear_wide(x, pre.weight[:, :F], pre.bias)
+        b = Fh.linear_wide(x, pre.weight[:, F:2 * F])
+        t = None
+        if self.edge_encoder is not None:
+            e = Fh.linear_wide(edge_attr, self.edge_encoder.weight, self.edge_encoder.bias)
+            t = Fh.linear_wide(e, pre.weight[:, 2 * F:])
+        return Fh.PNAAggregateFn.apply(a, b, t, rel, self.aggregators, self.scalers, self.avg_deg_log)
+
+    def forward(self, x: Tensor, edge_index: Union[Tensor, Relation], edge_attr: Optional[Tensor] = None,
+                act: str = "identity") -> Tensor:
+        agg = self.aggregate(x, edge_index, edge_attr)
+        post = self.post_nns[0][0]
+        h = Fh.linear_wide(torch.cat([x, agg], -1), post.weight, post.bias)
+        return Fh.linear_wide(h, self.lin.weight, self.lin.bias, act)
+
+
+# what the registry's PNA layers are built with when no ``config.PNAConfig`` says otherwise
+PNA_DEFAULT_AGGREGATORS = ("mean", "min", "max", "std")
+PNA_DEFAULT_SCALERS = ("identity",)
+
+
+class PNA(PNAConv):
+    """GraphGPS's PNA layer without edge features, constructible from ``(in, out)`` like the other registry entries;
+    ``aggregators`` / ``scalers`` / ``avg_deg_log`` are what a ``config.PNAConfig`` hands the model.  ``act`` is applied
+    in the last Linear's epilogue."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggregators=PNA_DEFAULT_AGGREGATORS,
+                 scalers=PNA_DEFAULT_SCALERS, avg_deg_log: Optional[float] = None, deg=None):
+        super().__init__(in_channels, out_channels, aggregators, scalers, deg=deg, edge_dim=None,
+                         avg_deg_log=avg_deg_log)
+
+    def forward(self, x: Tensor, edge_index: Union[Tensor, Relation], act: str = "identity") -> Tensor:
+        return super().forward(x, edge_index, None, act)
+
+
+class PNAEdge(PNAConv):
+    """The edge-aware PNA layer of the registry (as ``GINE`` is for ``GINEConv``): ``edge_dim=-1``, so ``edge_encoder``
+    takes its input width from the first ``edge_attr``."""
+
+    uses_edge_attr = True
+
+    def __init__(self, in_channels: int, out_channels: int, edge_dim: int = -1, aggregators=PNA_DEFAULT_AGGREGATORS,
+                 scalers=PNA_DEFAULT_SCALERS, avg_deg_log: Optional[float] = None, deg=None):
+        super().__init__(in_channels, out_channels, aggregators, scalers, deg=deg, edge_dim=edge_dim,
+                         avg_deg_log=avg_deg_log)
+
+
 class GatedGCNConv(nn.Module):
     """The bare convolution of GraphGPS's ``GatedGCNLayer`` (residual gated graph ConvNets), edge features in and out:
 

@@ -559,6 +559,140 @@ class GINEAggregateFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# PNAConv's aggregate: mean / min / max / sum / std of m_k = a[dst_k] + b[src_k] + t_k under degree scalers
+# --------------------------------------------------------------------------- #
+# csrc/pna.hip: the codes of include/hscn.h in the order of the library's enums; long rows as in GINE's aggregate
+# (hscn_pna_long_row / hscn_pna_chunk, pinned equal in tests/test_pna_host.py).
+PNA_AGGREGATORS = ("mean", "min", "max", "sum", "std")
+PNA_SCALERS = ("identity", "amplification", "attenuation")
+PNA_LONG_ROW = 256
+PNA_CHUNK = 64
+PNA_MAX_WIDTH = 512
+PNA_ENVELOPE = (f"1 <= F <= {PNA_MAX_WIDTH}, aggregators a non-empty subset of {PNA_AGGREGATORS} and scalers a "
+                f"non-empty subset of {PNA_SCALERS}")
+
+
+def pna_supported(F: int, num_aggregators: int = 1, num_scalers: int = 1) -> bool:
+    """hscn_pna_supported: the one statement of the kernel's envelope."""
+    return bool(_hip.lib().hscn_pna_supported(int(F), int(num_aggregators), int(num_scalers)))
+
+
+def pna_codes(aggregators, scalers):
+    """The two name lists as the library's codes; a name outside the lists, a repeat or an empty list is a ValueError."""
+    out = []
+    for what, names, known in (("aggregators", aggregators, PNA_AGGREGATORS), ("scalers", scalers, PNA_SCALERS)):
+        names = tuple(names)
+        if not names:
+            raise ValueError(f"PNA: {what} must name at least one of {known}")
+        for n in names:
+            if n not in known:
+                raise ValueError(f"PNA: unknown entry {n!r} in {what}; known: {known}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"PNA: {what} {names} repeats an entry")
+        out.append(tuple(known.index(n) for n in names))
+    return out[0], out[1]
+
+
+def _codes_host(codes):
+    import ctypes
+    return (ctypes.c_int32 * len(codes))(*codes)
+
+
+class PNAAggregateFn(Function):
+    """(a [N, F], b [N, F], t [E, F] or None) -> [N, S A F] over ``rel`` (row k of ``t`` belongs to edge k of
+    ``rel.edge_index``): the aggregators of the messages ``m_k = a[dst_k] + b[src_k] + t_k`` over every node's
+    in-edges, each under every scaler, columns scaler-major, then aggregator-major, then F (PyG's
+    ``DegreeScalerAggregation``).  ``aggregators`` / ``scalers``: names out of ``PNA_AGGREGATORS`` / ``PNA_SCALERS``;
+    ``avg_deg_log``: the training set's mean of ``log(deg + 1)``, read by "amplification" and "attenuation" only.
+    min / max ties go to the first slot of the row in CSR order, and the whole gradient with them.
+
+    Forward: one launch; the [E, F] messages are never written.  Kept for backward: b, t and -- only what the named
+    aggregators need -- the row means and stds [N, F] and the argmin / argmax edge ids [N, 2F].  Backward: one
+    elementwise launch folds the scalers into the cotangent and gives ``g_a``; ``g_b`` walks the source-keyed CSR,
+    ``g_t`` is edge-parallel; only what ``needs_input_grad`` asks for is computed.  No float atomics."""
+
+    @staticmethod
+    def forward(ctx, a: Tensor, b: Tensor, t: Optional[Tensor], rel: Relation, aggregators, scalers,
+                avg_deg_log: Optional[float] = None):
+        aggr, scal = pna_codes(aggregators, scalers)
+        for name, x in (("a", a), ("b", b), ("t", t)):
+            if x is None:
+                continue
+            if x.dtype != torch.float32:
+                raise TypeError(f"PNAAggregateFn: {name} must be float32, got {x.dtype}")
+            if x.dim() != 2:
+                raise ValueError(f"PNAAggregateFn: {name} must be 2-D, got {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise ValueError(f"PNAAggregateFn: {name} must be contiguous")
+        N, F = a.shape
+        if b.shape != a.shape:
+            raise ValueError(f"PNAAggregateFn: b is {tuple(b.shape)}, a is {tuple(a.shape)}")
+        if rel.num_src != N or rel.num_dst != N:
+            raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, a has {N} rows")
+        E = rel.num_edges
+        if t is not None and tuple(t.shape) != (E, F):
+            raise ValueError(f"PNAAggregateFn: t is {tuple(t.shape)}; the relation has {E} edges and the messages are "
+                             f"{F} wide")
+        if any(s != 0 for s in scal):
+            if avg_deg_log is None or not (float(avg_deg_log) > 0.0 and float(avg_deg_log) < float("inf")):
+                raise ValueError(f"PNAAggregateFn: scalers {tuple(scalers)} need a positive, finite avg_deg_log, got "
+                                 f"{avg_deg_log!r}")
+        if not pna_supported(F, len(aggr), len(scal)):
+            raise ValueError(f"PNAAggregateFn: width F={F} outside the kernel's envelope ({PNA_ENVELOPE})")
+        for name, x in (("a", a), ("b", b), ("t", t)):
+            if x is not None and not x.is_cuda:
+                raise RuntimeError(f"PNAAggregateFn takes HIP device tensors only ({name} is a CPU tensor): the hot "
+                                   "path has no CPU fallback")
+        need_a, need_b, need_t = ctx.needs_input_grad[:3]
+        if (need_b or need_t) and rel._csr_t is None:
+            raise ValueError("PNAAggregateFn: b or t requires a gradient and the relation carries the target-keyed CSR "
+                             "only; build it with both=True (Relation(edge_index, N, N, both=True))")
+        dev = a.device
+        avg = float(avg_deg_log) if avg_deg_log is not None else 0.0
+        keep = need_a or need_b or need_t
+        walk = need_b or need_t
+        out = torch.empty(N, len(scal) * len(aggr) * F, dtype=torch.float32, device=dev)
+        has_std, has_arg = 4 in aggr, (1 in aggr or 2 in aggr)
+        mean = torch.empty(N, F, dtype=torch.float32, device=dev) if (walk and has_std) else None
+        std = torch.empty(N, F, dtype=torch.float32, device=dev) if (keep and has_std) else None
+        arg = torch.empty(N, 2 * F, dtype=torch.int32, device=dev) if (walk and has_arg) else None
+        csr = rel.csr
+        call("hscn_pna_fwd", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(a), ptr(b), ptr(t), ptr(out), ptr(mean),
+             ptr(std), ptr(arg), N, E, F, _codes_host(aggr), len(aggr), _codes_host(scal), len(scal), avg,
+             ptr(csr.flag), stream())
+        ctx.rel, ctx.spec = rel, (aggr, scal, avg)
+        ctx.has_t = t is not None
+        ctx.save_for_backward(b, t, mean, std, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out: Tensor):
+        b, t, mean, std, arg = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        aggr, scal, avg = ctx.spec
+        need_a, need_b, need_t = ctx.needs_input_grad[:3]
+        g_out = _c(g_out)
+        N, F = b.shape
+        E = rel.num_edges
+        dev = b.device
+        gw = torch.empty(N, 4, F, dtype=torch.float32, device=dev)
+        g_a = torch.empty(N, F, dtype=torch.float32, device=dev) if need_a else None
+        call("hscn_pna_bwd_fold", ptr(rel.csr.rowptr), ptr(g_out), ptr(std), ptr(gw), ptr(g_a), N, F, _codes_host(aggr),
+             len(aggr), _codes_host(scal), len(scal), avg, stream())
+        g_b = g_t = None
+        if need_b:
+            ct = rel.csr_t
+            g_b = torch.empty(N, F, dtype=torch.float32, device=dev)
+            call("hscn_pna_bwd_src", ptr(ct.rowptr), ptr(ct.col), ptr(ct.eid), ptr(b), ptr(t), ptr(gw), ptr(mean),
+                 ptr(arg), ptr(g_b), N, E, F, ptr(rel.csr.flag), stream())
+        if need_t and ctx.has_t:
+            g_t = torch.empty(E, F, dtype=torch.float32, device=dev)
+            call("hscn_pna_bwd_edge", ptr(rel.edge_index.contiguous()) if E else None, ptr(b), ptr(t), ptr(gw),
+                 ptr(mean), ptr(arg), ptr(g_t), N, E, F, ptr(rel.csr.flag), stream())
+        return g_a, g_b, g_t, None, None, None, None
+
+
+# --------------------------------------------------------------------------- #
 # GatedGCN's aggregate: e^_k = Dx_i + Ex_j + Ce_k, h_i = Ax_i + sum_k s_k Bx_j / (sum_k s_k + 1e-6), s = sigmoid(e^)
 # --------------------------------------------------------------------------- #
 # csrc/gatedgcn.hip: a row of more than GATEDGCN_LONG_ROW slots (in-degree in the forward and the backward's target

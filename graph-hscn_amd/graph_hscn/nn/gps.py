@@ -32,7 +32,7 @@ from .attention import ExphormerAttention, MultiheadSelfAttention
 from .conv import GatedGCNLayer, Linear
 from .norm import BatchNorm1d, LayerNorm
 
-LOCAL_CONVS = ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge")
+LOCAL_CONVS = ("gcn", "gat", "gine", "gatedgcn", "transformerconv", "transformerconv_edge", "pna", "pna_edge")
 NORMS = ("layer", "batch", None)
 GLOBAL_MODELS = ("attention", "exphormer")
 
@@ -48,7 +48,7 @@ def _norm(kind: Optional[str], channels: int) -> Optional[nn.Module]:
 class GPSLayer(nn.Module):
     def __init__(self, channels: int, local_conv: Optional[str], num_heads: int, dropout: float = 0.0,
                  norm: Optional[str] = "layer", act: str = "relu", spd_buckets: Optional[int] = None,
-                 global_model: str = "attention", num_virtual_nodes: int = 0):
+                 global_model: str = "attention", num_virtual_nodes: int = 0, pna=None):
         super().__init__()
         if global_model not in GLOBAL_MODELS:
             raise ValueError(f"global_model must be one of {GLOBAL_MODELS}, got {global_model!r}")
@@ -66,6 +66,8 @@ class GPSLayer(nn.Module):
             raise ValueError(f"act must be one of {sorted(ACT)}, got {act!r}")
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
+        if pna is not None and local_conv not in ("pna", "pna_edge"):
+            raise ValueError(f"pna=PNAConfig(...) needs local_conv 'pna' or 'pna_edge', got {local_conv!r}")
         self.channels, self.local_conv, self.act, self.dropout = int(channels), local_conv, act, float(dropout)
         self.dropout_seed: Optional[int] = None     # tests pin the masks; None = nn.functional.dropout's default
         if local_conv == "gatedgcn":        # GraphGPS's layer: batch norm, activation, dropout and residual inside
@@ -74,6 +76,9 @@ class GPSLayer(nn.Module):
             if channels % num_heads:
                 raise ValueError(f"channels {channels} must be divisible by num_heads {num_heads}")
             self.conv = CONV_DICT[local_conv](channels, channels // num_heads, heads=num_heads)
+        elif local_conv in ("pna", "pna_edge"):     # pna: a config.PNAConfig (aggregators, scalers, avg_deg_log) or None
+            kw = {} if pna is None else dict(aggregators=pna.aggregators, scalers=pna.scalers, avg_deg_log=pna.avg_deg_log)
+            self.conv = CONV_DICT[local_conv](channels, channels, **kw)
         else:
             self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
         # spd_buckets: the attention's own shortest-path bias table (Graphormer's spatial encoding); None: as before
@@ -103,7 +108,7 @@ class GPSLayer(nn.Module):
                 ptr32: Optional[Tensor] = None, max_nodes: Optional[int] = None, spd=None, exph=None):
         """``batch``: the ``Batch`` (graph boundaries of the attention), or ``ptr32`` and ``max_nodes``.  ``spd``: the
         batch's ``SPDBuckets``, for a layer built with ``spd_buckets`` (refused by name otherwise).  ``edge_attr``
-        is read by an edge-aware ``local_conv`` ("gine", "gatedgcn", "transformerconv_edge") only.  Returns the node features; with a
+        is read by an edge-aware ``local_conv`` ("gine", "gatedgcn", "transformerconv_edge", "pna_edge") only.  Returns the node features; with a
         ``local_conv`` that updates the edge features ("gatedgcn") the pair ``(h, edge_attr_out)``.
 
         ``global_model="exphormer"``: ``exph = (struct, virt, e_edge, e_type)`` -- the batch's ``ExphormerStructure``,

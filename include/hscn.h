@@ -1792,6 +1792,57 @@ int hscn_lappe_bwd(const float* vec, const float* val, const float* g_out /*[N, 
                    const void* const* params_host, int64_t N, int max_freqs, int dim_pe, int layers, int flip,
                    uint64_t seed, float* g_params, float* workspace, int64_t workspace_floats, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * PNAConv's aggregate: mean / min / max / sum / std of a node's in-edge messages under degree scalers
+ * (PyG PNAConv with towers = 1; csrc/pna.hip).  Purely additive to ABI 24.
+ *
+ * The message of edge k (j = src_k -> i = dst_k) is m_k = a[i] + b[j] + t[k]: a, b f32 [N, F], t f32 [E, F] in the
+ * order of the edge list, or NULL (no edge features).  aggregators_host / scalers_host: HOST arrays of codes, each a
+ * non-empty list without repeats, in the order of the output's column blocks:
+ *     aggregators  0 mean, 1 min, 2 max, 3 sum, 4 std = sqrt(relu(mean(m^2) - mean(m)^2) + 1e-5)
+ *     scalers      0 identity, 1 amplification log(d + 1) / avg_deg_log, 2 attenuation avg_deg_log / log(d + 1),
+ *                  d = max(deg_i, 1); avg_deg_log is read (and must be finite and positive) only beside a code 1 or 2
+ *     out[i, (s A + x) F + f] = scaler_s(i) * aggregator_x(i, f)                    f32 [N, S A F]
+ *   A node without in-edges: 0 for mean, min, max and sum, sqrt(1e-5) for std.
+ * hscn_pna_fwd: ONE launch over the target-keyed stable CSR.  A row is owned by a lane group (4 columns a lane where
+ *   F % 4 == 0), reduces r_k = b[j] + t[k] in slot order and adds a[i] at the end (deg a[i] to sum, nothing to std).
+ *   min / max ties go to the first slot in CSR order.  Rows of more than hscn_pna_long_row() slots are cut into
+ *   chunks of hscn_pna_chunk() slots merged in chunk order (sums by a separately rounded add, min / max by comparison,
+ *   the earlier chunk keeping a tie): a row's result depends on its own slots alone.  Optional outputs for the
+ *   backward, each may be NULL: mean [N, F] (mean of r), stdv [N, F] (the std where the variance is positive, else 0),
+ *   arg int32 [N, 2 F] (edge id of the argmin | argmax, -1 for an empty row).
+ * hscn_pna_bwd_fold: ONE elementwise launch.  g_out f32 [N, S A F] -> gw f32 [N, 4, F] = {G_mean / deg + G_sum, G_min,
+ *   G_max, [var > 0] G_std / (deg std)} (G_x: the cotangent of aggregator x with the scalers folded in; zeros for an
+ *   empty row) and g_a [N, F] = G_mean + G_min + G_max + deg G_sum (may be NULL).  rowptr: the target-keyed CSR's; stdv:
+ *   what the forward wrote (required with aggregator 4).
+ *   Then, for edge k:  dm_k = gw0[i] + [k = argmin_i] gw1[i] + [k = argmax_i] gw2[i] + gw3[i] (r_k - mean_i).
+ * hscn_pna_bwd_src: g_b [N, F], g_b[j] = sum of dm_k over the out-edges of j: ONE launch over the source-keyed stable
+ *   CSR, slot order, long rows as in the forward.  mean may be NULL without aggregator 4, arg without 1 and 2.
+ * hscn_pna_bwd_edge: g_t [E, F], g_t[k] = dm_k in edge order (edge_index int64 [2, E]); plain stores.
+ *   No float atomics anywhere: two runs give the same bits.  flag: the relation's flag word; an edge with a node id
+ *   outside [0, N) is in no CSR row, gets a zero row of g_t and raises bit 0; a foreign CSR entry raises bit 1.
+ * hscn_pna_supported: 1 for 1 <= F <= 512, 1 <= num_aggregators <= 5, 1 <= num_scalers <= 3.
+ *   HSCN_E_BADARG for null pointers (col / eid may be NULL when E == 0, t always), negative sizes, F < 1, a list that
+ *   is empty, too long, repeats a code or holds an unknown one, or an avg_deg_log that is needed and not positive;
+ *   HSCN_E_UNSUPPORTED for F > 512; both before any launch.  No workspace, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_pna_supported(int F, int num_aggregators, int num_scalers);
+int hscn_pna_long_row(void);
+int hscn_pna_chunk(void);
+int hscn_pna_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const float* a, const float* b,
+                 const float* t, float* out, float* mean, float* stdv, int32_t* arg, int64_t N, int64_t E, int F,
+                 const int32_t* aggregators_host, int num_aggregators, const int32_t* scalers_host, int num_scalers,
+                 float avg_deg_log, int32_t* flag /*[1]*/, void* stream);
+int hscn_pna_bwd_fold(const int32_t* rowptr, const float* g_out, const float* stdv, float* gw, float* g_a, int64_t N,
+                      int F, const int32_t* aggregators_host, int num_aggregators, const int32_t* scalers_host,
+                      int num_scalers, float avg_deg_log, void* stream);
+int hscn_pna_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const float* b,
+                     const float* t, const float* gw, const float* mean, const int32_t* arg, float* g_b, int64_t N,
+                     int64_t E, int F, int32_t* flag /*[1]*/, void* stream);
+int hscn_pna_bwd_edge(const int64_t* edge_index, const float* b, const float* t, const float* gw, const float* mean,
+                      const int32_t* arg, float* g_t, int64_t N, int64_t E, int F, int32_t* flag /*[1]*/,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
