@@ -279,6 +279,14 @@ _SIGNATURES = {
     "hscn_pna_bwd_fold": (c_int, [P, P, P, P, P, c_int64, c_int, P, c_int, P, c_int, c_float, P]),
     "hscn_pna_bwd_src": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
     "hscn_pna_bwd_edge": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int, P, P]),
+    # SAN's attention over real and fake edges (csrc/san.hip; additive to ABI 24)
+    "hscn_san_attn_supported": (c_int, [c_int, c_int, c_int]),
+    "hscn_san_attn_fwd": (c_int, [P] * 12 + [c_int64, c_int64, c_int64, c_int, c_int, c_int, ctypes.c_double, c_int, P,
+                                            P]),
+    "hscn_san_attn_bwd_dst": (c_int, [P] * 17 + [c_int64, c_int64, c_int64, c_int, c_int, c_int, ctypes.c_double, c_int,
+                                                 P, P]),
+    "hscn_san_attn_bwd_src": (c_int, [P] * 16 + [c_int64, c_int64, c_int64, c_int, c_int, c_int, ctypes.c_double, c_int,
+                                                 P, P]),
 }
 
 

@@ -306,6 +306,62 @@ class GPSConfig:
 
 
 @dataclass
+class SANConfig:
+    """The SAN model (extension; model/san.py): ``num_layers`` SAN layers of width ``hidden_channels`` -- attention of
+    ``num_heads`` heads over every ordered pair of a graph, the listed edges ("real") through one set of projections
+    and their encoded features, all other pairs ("fake") through a second set and one learned row, mixed by the fixed
+    ``gamma`` >= 0 -- behind a node encoder (Linear or "atom") and an edge encoder (Linear or "bond").  The batches must
+    carry ``edge_attr``.  ``full_graph=False`` keeps the real pairs alone.  The head width ``hidden_channels /
+    num_heads`` must be a multiple of 4 in [4, 64] and ``hidden_channels`` at most 512 (the kernel's envelope,
+    csrc/san.hip).  ``activation`` is the head's; the layers' feed-forward block is ReLU.  A learned gamma and dropout on
+    the attention weights are not built (``SAN(gamma_learn=...)`` / ``SAN(attn_dropout=...)`` refuse them by name)."""
+    activation: str
+    hidden_channels: int = HIDDEN_CHANNELS
+    num_layers: int = NUM_LAYERS
+    num_heads: int = 4
+    dropout: float = DROPOUT
+    norm: Optional[str] = "layer"
+    task_level: str = "graph"
+    node_encoder: Optional[str] = None
+    edge_encoder: Optional[str] = None
+    gamma: float = 1e-1
+    full_graph: bool = True
+    # a trainable positional encoder inside the model (model/_common.py PosEnc): a LapPEConfig or an RWSEConfig whose
+    # dim_emb is hidden_channels; pe_undirected: the edge lists hold both directions
+    pos_enc: Optional[object] = None
+    pe_undirected: bool = True
+
+    def __post_init__(self):
+        if self.task_level not in TASK_LEVELS:
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        if self.activation.lower() not in ACT_DICT:
+            raise ValueError(f"activation must be one of {sorted(ACT_DICT)}, got {self.activation!r}")
+        if self.node_encoder not in (None,) + NODE_ENCODERS:
+            raise ValueError(f"node_encoder must be one of {NODE_ENCODERS} or None, got {self.node_encoder!r}")
+        if self.edge_encoder not in (None,) + EDGE_ENCODERS:
+            raise ValueError(f"edge_encoder must be one of {EDGE_ENCODERS} or None, got {self.edge_encoder!r}")
+        _check_pos_enc(self.pos_enc, self.hidden_channels)
+        g = self.gamma
+        if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0.0 <= float(g) < float("inf"):
+            raise ValueError(f"gamma must be a finite number >= 0, got {g!r}")
+        if not isinstance(self.full_graph, bool):
+            raise ValueError(f"full_graph must be a bool, got {self.full_graph!r}")
+        if self.dropout and not (0.0 <= self.dropout < 1.0):
+            raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
+        for v in (self.num_layers, self.hidden_channels, self.num_heads):
+            if v < 1:
+                raise ValueError(f"{v} must be positive.")
+        if self.norm not in GPS_NORMS:
+            raise ValueError(f"norm must be 'layer', 'batch' or None, got {self.norm!r}")
+        if self.hidden_channels % self.num_heads:
+            raise ValueError(f"hidden_channels {self.hidden_channels} must be divisible by num_heads {self.num_heads}.")
+        dh = self.hidden_channels // self.num_heads
+        if dh % 4 or not 4 <= dh <= 64 or self.hidden_channels > 512:
+            raise ValueError(f"head width {dh} (hidden_channels / num_heads) must be a multiple of 4 in [4, 64] and "
+                             f"hidden_channels at most 512.")
+
+
+@dataclass
 class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent there)
     activation: str
     lv_conv_type: str = "GAT"
@@ -463,7 +519,8 @@ class LapPEConfig:
 
 @dataclass
 class TrainingConfig:  # config.py:133-152
-    # "hscn" / "mpnn" (the reference's two: HSCNConfig / MPNNConfig) or "gps" (extension: GPSConfig, model/gps.py)
+    # "hscn" / "mpnn" (the reference's two: HSCNConfig / MPNNConfig), "gps" (extension: GPSConfig, model/gps.py) or
+    # "san" (extension: SANConfig, model/san.py)
     model_type: str
     loss_fn: str
     # "ap" / "mae" (the reference's two), "accuracy" / "f1_macro" for class-index targets, or "mrr" / "hits@1" /

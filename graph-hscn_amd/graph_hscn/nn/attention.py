@@ -204,3 +204,83 @@ class ExphormerAttention(nn.Module):
         out = Fh.ExphormerAttentionFn.apply(self.Q(x), self.K(x), self.V(x), ee, self.E(e_type), struct, self.num_heads)
         N = struct.num_nodes
         return self.out_proj(out[:N]), out[N:]
+
+
+class SANAttention(nn.Module):
+    """SAN's multi-head attention (Kreuzer et al., "Rethinking Graph Transformers with Spectral Attention", 2021, in
+    GraphGPS's ``SANLayer`` form) on the HIP path (csrc/san.hip): every node attends to its in-neighbours through ``Q``,
+    ``K`` and the edge features ``E(edge_attr)``, and -- with ``full_graph`` -- to every other node of its graph (itself
+    included, unless it has a self-loop) through ``Q_2``, ``K_2`` and ``E_2`` of ONE learned "fake edge" row; the two
+    kinds are mixed by ``gamma`` under one denominator (``nn.functional.SANAttentionFn``).  ``V`` serves both kinds.
+    All projections are bias-free ``channels -> channels`` Linears under GraphGPS's names.
+
+    ``forward(x, edge_index, edge_attr, batch, fake_edge_row)``: ``x`` [N, channels], ``edge_attr`` [E, channels] (the
+    encoded edge features, one row per edge), ``batch`` the ``Batch`` (``ptr32``, ``max_nodes``; or ``ptr32=`` and
+    ``max_nodes=``), ``fake_edge_row`` [1, channels] the model's ``fake_edge_emb.weight`` (read with ``full_graph``
+    only).  ``K_2(x) * E_2(fake_edge_row)`` is a row broadcast in plain torch, so autograd carries ``K_2``, ``E_2`` and
+    the row.  Returns [N, channels]: the heads side by side, no output projection (the layer's ``O_h`` follows).
+
+    Not provided, refused by name: a learned gamma (``gamma_learn``), dropout on the attention weights, a batch without
+    edge features, widths outside the kernel's envelope, CPU tensors."""
+
+    def __init__(self, channels: int, num_heads: int, gamma: float = 1e-1, full_graph: bool = True,
+                 attn_dropout: float = 0.0, gamma_learn: bool = False):
+        super().__init__()
+        if channels <= 0 or num_heads <= 0 or channels % num_heads:
+            raise ValueError(f"channels must be a positive multiple of num_heads, got channels={channels} and "
+                             f"num_heads={num_heads}")
+        if gamma_learn:
+            raise NotImplementedError("SANAttention(gamma_learn=True): a learned gamma is not implemented; gamma is a "
+                                      "fixed hyperparameter")
+        if attn_dropout != 0.0:
+            raise NotImplementedError("SANAttention(attn_dropout > 0): dropout on the attention weights is not "
+                                      "implemented (the weights never exist in memory); drop the layer's output instead")
+        head_dim = channels // num_heads
+        if not (head_dim % 4 == 0 and Fh.SAN_MIN_HEAD_DIM <= head_dim <= Fh.SAN_MAX_HEAD_DIM
+                and channels <= Fh.SAN_MAX_WIDTH):
+            raise ValueError(f"SANAttention: channels={channels} with num_heads={num_heads} (head width {head_dim}) is "
+                             f"outside the kernel's envelope ({Fh.SAN_ENVELOPE})")
+        self.channels, self.num_heads = int(channels), int(num_heads)
+        self.full_graph = bool(full_graph)
+        self.gamma = Fh._check_gamma(gamma)
+        self.Q = _Proj(channels, False)
+        self.K = _Proj(channels, False)
+        self.E = _Proj(channels, False)
+        if self.full_graph:
+            self.Q_2 = _Proj(channels, False)
+            self.K_2 = _Proj(channels, False)
+            self.E_2 = _Proj(channels, False)
+        self.V = _Proj(channels, False)
+
+    def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Optional[Tensor], batch=None,
+                fake_edge_row: Optional[Tensor] = None, *, ptr32: Optional[Tensor] = None,
+                max_nodes: Optional[int] = None) -> Tensor:
+        from ..structure import relation_of
+        if x.dim() != 2 or x.size(1) != self.channels:
+            raise ValueError(f"x must be [N, {self.channels}], got {tuple(x.shape)}")
+        if edge_attr is None:
+            raise ValueError("SANAttention needs edge_attr [E, channels]: the real pairs' score is multiplicative in "
+                             "the edge features (a batch without edge features is not taken)")
+        if edge_attr.dim() != 2 or edge_attr.size(0) != edge_index.size(1) or edge_attr.size(1) != self.channels:
+            raise ValueError(f"edge_attr must be [E, {self.channels}] with one row per edge (E = {edge_index.size(1)}), "
+                             f"got {tuple(edge_attr.shape)}")
+        if batch is not None:
+            if ptr32 is not None or max_nodes is not None:
+                raise ValueError("pass a Batch, or ptr32 and max_nodes, not both")
+            for attr in ("ptr32", "max_nodes"):
+                if not hasattr(batch, attr):
+                    raise ValueError(f"the batch carries no {attr} (graph_hscn.data.Batch.from_data_list builds it)")
+            ptr32, max_nodes = batch.ptr32, batch.max_nodes
+        if ptr32 is None or max_nodes is None:
+            raise ValueError("SANAttention needs the graph boundaries: a Batch, or ptr32 and max_nodes")
+        q2 = k2e = None
+        if self.full_graph:
+            if fake_edge_row is None or tuple(fake_edge_row.shape) != (1, self.channels):
+                raise ValueError(f"SANAttention(full_graph=True) needs fake_edge_row [1, {self.channels}] (the model's "
+                                 "fake_edge_emb.weight)")
+            q2 = self.Q_2(x)
+            k2e = self.K_2(x) * self.E_2(fake_edge_row)
+        rel = relation_of(edge_index, x.size(0), x.size(0))
+        out, _ = Fh.SANAttentionFn.apply(self.Q(x), self.K(x), self.V(x), self.E(edge_attr), q2, k2e, rel, ptr32,
+                                         int(max_nodes), self.num_heads, self.gamma, self.full_graph)
+        return out

@@ -1044,6 +1044,145 @@ class ExphormerAttentionFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# SAN: full-graph attention over real and fake edges (csrc/san.hip)
+# --------------------------------------------------------------------------- #
+SAN_MIN_HEAD_DIM = 4
+SAN_MAX_HEAD_DIM = 64
+SAN_MAX_WIDTH = 512
+SAN_MAX_NODES = 4096
+SAN_EDGE_OUT_OF_GRAPH = 1         # flag bit 0: an edge with an end outside its target's graph (skipped; the pair is fake)
+SAN_GRAPH_TOO_LARGE = 2           # flag bit 1: a graph with more than max_nodes nodes (its rows are NaN)
+SAN_ENVELOPE = (f"head width a multiple of 4 in [{SAN_MIN_HEAD_DIM}, {SAN_MAX_HEAD_DIM}], heads >= 1, heads * head "
+                f"width <= {SAN_MAX_WIDTH}, graphs of at most {SAN_MAX_NODES} nodes")
+
+_SAN_FLAGS = _hip.FlagWord()
+
+
+def san_attn_supported(heads: int, head_dim: int, max_nodes: int = 0) -> bool:
+    """hscn_san_attn_supported: the one statement of the kernel's envelope."""
+    return bool(_hip.lib().hscn_san_attn_supported(int(heads), int(head_dim), int(max_nodes)))
+
+
+def san_flags(device) -> Tensor:
+    """The device's flag word [1] int32 that every SAN attention launch ORs into; ``check_san`` reads and clears it."""
+    return _SAN_FLAGS.of(device)
+
+
+def check_san(device) -> None:
+    """Synchronising: ``ValueError`` if a SAN attention launch since the last check met an edge that names a node
+    outside its target's graph (the edge was skipped and the pair counted as fake) or a graph larger than the
+    ``max_nodes`` it was given (that graph's rows are NaN)."""
+    f = _SAN_FLAGS.take(device)
+    if f & SAN_EDGE_OUT_OF_GRAPH:
+        raise ValueError("SAN attention: an edge names a node outside its target's graph (or an edge id outside the "
+                         "edge list); it was skipped and the pair counted as fake")
+    if f & SAN_GRAPH_TOO_LARGE:
+        raise ValueError("SAN attention: a graph has more nodes than the batch's max_nodes says; its rows are NaN")
+
+
+def _check_gamma(gamma) -> float:
+    gamma = float(gamma)
+    if not (gamma >= 0.0 and gamma != float("inf")):
+        raise ValueError(f"SAN attention: gamma must be finite and >= 0, got {gamma!r}")
+    return gamma
+
+
+class SANAttentionFn(Function):
+    """(q, k, v [N, Hd*C], e [E, Hd*C], q2, k2e [N, Hd*C] or None) -> (out [N, Hd*C], z [N, Hd]) over ``rel`` (j =
+    src_x, i = dst_x; row x of ``e`` belongs to edge x of ``rel.edge_index``) and the graphs of ``ptr32``: per head every
+    listed edge j -> i inside a graph weighs ``a exp(clamp(q_i . (k_j * e_x) / sqrt(C), -5, 5))``, every other ordered
+    pair (j, i) of a graph, j = i included, ``b exp(clamp(q2_i . k2e_j / sqrt(C), -5, 5))`` with ``a = 1 / (1 + gamma)``,
+    ``b = gamma / (1 + gamma)``; ``z`` is the sum of a row's weights and ``out = sum w v_j / (z + 1e-6)``.
+    ``full_graph=False``: the edges alone with a = 1 (``q2`` and ``k2e`` are None), zeros for a node without in-edges.
+    Forward: one launch; kept are the inputs, ``out`` and ``z`` -- the weights are recomputed, never stored.  Backward:
+    the query-keyed pass gives dq, de, dq2 and the per-(row, head) ``sum(dout * out)``, the key-keyed pass (``rel.csr_t``,
+    built only then) dk, dv and dk2e.  Only what ``needs_input_grad`` asks for is computed; ``z`` carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, e: Tensor, q2: Optional[Tensor], k2e: Optional[Tensor],
+                rel: Relation, ptr32: Tensor, max_nodes: int, heads: int, gamma: float, full_graph: bool):
+        heads, max_nodes, full_graph = int(heads), int(max_nodes), bool(full_graph)
+        gamma = _check_gamma(gamma) if full_graph else 0.0
+        E = rel.num_edges
+        if e is None:
+            raise ValueError("SAN attention: e is None; every edge needs a feature row (e must be [E, heads * C])")
+        if full_graph and (q2 is None or k2e is None):
+            raise ValueError("SAN attention: full_graph needs q2 and k2e")
+        if not full_graph and (q2 is not None or k2e is not None):
+            raise ValueError("SAN attention: q2 and k2e belong to full_graph=True (pass None)")
+
+        def shapes(N, HC):
+            for name, t in (("k", k), ("v", v), ("q2", q2), ("k2e", k2e)):
+                if t is not None and t.shape != q.shape:
+                    raise ValueError(f"SAN attention: {name} is {tuple(t.shape)}, q is {tuple(q.shape)}")
+            if rel.num_src != N or rel.num_dst != N:
+                raise ValueError(f"the relation is {rel.num_src} -> {rel.num_dst} nodes, q has {N} rows")
+            if e.size(0) != E or e.size(1) != HC:
+                raise ValueError(f"e is {tuple(e.shape)}; the relation has {E} edges (one row per edge) and the layer "
+                                 f"is {HC} wide")
+            if ptr32.dtype != torch.int32 or ptr32.dim() != 1 or ptr32.numel() < 1:
+                raise TypeError("ptr32 must be an int32 [B + 1] tensor (graph_hscn.data.Batch.ptr32)")
+            if max_nodes < 0:
+                raise ValueError(f"max_nodes must be >= 0, got {max_nodes}")
+
+        operands = (("q", q), ("k", k), ("v", v), ("e", e), ("q2", q2), ("k2e", k2e))
+        N, HC, C = _head_attention_dims("SAN attention", operands, heads, shapes,
+                                        lambda h, c: san_attn_supported(h, c, max_nodes), SAN_ENVELOPE)
+        if ptr32.device != q.device:
+            raise RuntimeError(f"ptr32 is on {ptr32.device}, q on {q.device}: move the batch to the device once")
+        q, k, v, e, q2, k2e = _c(q), _c(k), _c(v), _c(e), _c(q2), _c(k2e)
+        ptr32 = ptr32.contiguous()
+        B = ptr32.numel() - 1
+        csr = rel.csr
+        dev = q.device
+        out = torch.empty(N, HC, dtype=torch.float32, device=dev)
+        z = torch.empty(N, heads, dtype=torch.float32, device=dev)
+        call("hscn_san_attn_fwd", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(ptr32), ptr(q), ptr(k), ptr(v),
+             ptr(e) if E else None, ptr(q2), ptr(k2e), ptr(out), ptr(z), N, E, B, max_nodes, heads, C, gamma,
+             int(full_graph), ptr(san_flags(dev)), stream())
+        ctx.rel, ctx.dims = rel, (N, E, B, max_nodes, heads, C, gamma, full_graph)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(z)
+        ctx.save_for_backward(q, k, v, e, q2, k2e, ptr32, out, z)
+        return out, z
+
+    @staticmethod
+    def backward(ctx, go: Optional[Tensor], _gz=None):
+        q, k, v, e, q2, k2e, ptr32, out, z = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        N, E, B, max_nodes, heads, C, gamma, full = ctx.dims
+        need_q, need_k, need_v, need_e, need_q2, need_k2 = ctx.needs_input_grad[:6]
+        need_q2, need_k2 = need_q2 and full, need_k2 and full
+        none = (None,) * 12
+        if go is None or not (need_q or need_k or need_v or need_e or need_q2 or need_k2):
+            return none
+        go = _c(go)
+        csr = rel.csr
+        flag = san_flags(q.device)
+        delta = torch.empty(N, heads, dtype=torch.float32, device=q.device)
+        # without edges no real pair reaches q: exact zeros; de: a skipped edge's row is not written
+        dq = (torch.empty_like(q) if E else torch.zeros_like(q)) if need_q else None
+        de = torch.zeros_like(e) if need_e else None
+        dq2 = torch.empty_like(q2) if need_q2 else None
+        tail = (N, E, B, max_nodes, heads, C, gamma, int(full), ptr(flag), stream())
+        call("hscn_san_attn_bwd_dst", ptr(csr.rowptr), ptr(csr.col), ptr(csr.eid), ptr(ptr32), ptr(q), ptr(k), ptr(v),
+             ptr(e) if E else None, ptr(q2), ptr(k2e), ptr(out), ptr(z), ptr(go), ptr(delta), ptr(dq),
+             ptr(de) if E else None, ptr(dq2), *tail)
+        dk = dv = dk2 = None
+        if need_k or need_v or need_k2:
+            # dk is the real term's alone (zeros without edges); dv and dk2e also see the fake pairs
+            dk = (torch.empty_like(k) if E else torch.zeros_like(k)) if need_k else None
+            dv = (torch.empty_like(v) if (E or full) else torch.zeros_like(v)) if need_v else None
+            dk2 = torch.empty_like(k2e) if need_k2 else None
+            if E or full:
+                t = rel.csr_t
+                call("hscn_san_attn_bwd_src", ptr(t.rowptr), ptr(t.col), ptr(t.eid), ptr(ptr32), ptr(q), ptr(k),
+                     ptr(v), ptr(e) if E else None, ptr(q2), ptr(k2e), ptr(z), ptr(delta), ptr(go), ptr(dk), ptr(dv),
+                     ptr(dk2), *tail)
+        return (dq, dk, dv, de, dq2, dk2) + (None,) * 6
+
+
+# --------------------------------------------------------------------------- #
 # Global attention: block-diagonal multi-head self-attention over a batch (csrc/attention.hip)
 # --------------------------------------------------------------------------- #
 ATTN_MIN_HEAD_DIM = 4

@@ -1843,6 +1843,57 @@ int hscn_pna_bwd_edge(const int64_t* edge_index, const float* b, const float* t,
                       const int32_t* arg, float* g_t, int64_t N, int64_t E, int F, int32_t* flag /*[1]*/,
                       void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * SAN's attention over real and fake edges (csrc/san.hip).  Purely additive to ABI 24.
+ *
+ * q, k, v, q2, k2e f32 [N, HC] (HC = heads * head_dim = heads * C), e f32 [E, HC] in the order of the edge list, ptr32
+ * int32 [B + 1] the graph boundaries, (rowptr, col, eid) the target-keyed stable CSR of the edge list
+ * (hscn_csr_build), (rowptr_t, col_t, eid_t) the source-keyed one.  Per head, target i of graph g, scale = 1/sqrt(C):
+ *     real  every listed edge x = (j -> i) with both ends in g, in CSR order:
+ *             w_x   = a exp(clamp(scale sum_c q[i,c] (k[j,c] e[x,c]), -5, 5))
+ *     fake  every node j of g, j = i included, without a listed edge j -> i, in key order:
+ *             w2_ij = b exp(clamp(scale sum_c q2[i,c] k2e[j,c], -5, 5))
+ *     a = 1 / (1 + gamma), b = gamma / (1 + gamma) (computed in double, rounded once)
+ *     z[i] = sum w_x + sum w2_ij      out[i] = (sum w_x v[j] + sum w2_ij v[j]) / (z[i] + 1e-6)
+ *   full_graph = 0: the real term alone with a = 1 (q2, k2e, dq2, dk2e NULL, gamma not read); a node without
+ *   in-edges gets zeros.  The relation is directed.
+ * hscn_san_attn_fwd: ONE launch, one wave per 64 rows of one (graph, head), a row per lane; the tile's adjacency is a
+ *   bitset in LDS filled from the CSR, k2e and v stream through LDS in chunks of 32 rows.  Writes out [N, HC] and
+ *   z [N, heads]; no weight, no [n, n] and no [E, heads] tensor exists.
+ * hscn_san_attn_bwd_dst: ONE launch keyed by query: delta [N, heads] = sum_c g_out out (always), dq [N, HC], de [E, HC]
+ *   (one writer per edge; rows of skipped edges are not written: hand in zeros), dq2 [N, HC]; each may be NULL.
+ * hscn_san_attn_bwd_src: ONE launch keyed by key over the source-keyed CSR: dk, dv, dk2e [N, HC], each may be NULL
+ *   (all NULL: nothing is launched).  The gradient through the clamp is zero outside (-5, 5).
+ *   No float atomics, plain stores: two runs give the same bits, and a graph's rows have the same bits wherever the
+ *   graph stands in the batch.
+ * flag: bit 0 = a slot whose other end lies outside its row's graph or whose edge id lies outside [0, E): left out of
+ *   the real term and of the bitset (the pair counts as fake); bit 1 = a graph with more than max_nodes nodes: NaN in
+ *   all its rows of every output of the launch but de.
+ * hscn_san_attn_supported: 1 for head_dim a multiple of 4 in [4, 64], heads >= 1, heads * head_dim <= 512 and
+ *   0 <= max_nodes <= 4096 (the bitset row of a lane: ceil(max_nodes / 32) | 1 words, 32.3 KB a tile at 4096).
+ *   HSCN_E_BADARG for null or misaligned (16 bytes) pointers, negative sizes, N or E beyond int32, and with
+ *   full_graph a gamma that is negative or not finite; HSCN_E_UNSUPPORTED where hscn_san_attn_supported is 0; both
+ *   before any launch.  N = 0 or B = 0 launches nothing.  No workspace, no host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_san_attn_supported(int heads, int head_dim, int max_nodes);
+int hscn_san_attn_fwd(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* ptr32,
+                      const float* q, const float* k, const float* v, const float* e, const float* q2,
+                      const float* k2e, float* out /*[N, HC]*/, float* z /*[N, heads]*/, int64_t N, int64_t E,
+                      int64_t B, int max_nodes, int heads, int head_dim, double gamma, int full_graph,
+                      int32_t* flag /*[1]*/, void* stream);
+int hscn_san_attn_bwd_dst(const int32_t* rowptr, const int32_t* col, const int32_t* eid, const int32_t* ptr32,
+                          const float* q, const float* k, const float* v, const float* e, const float* q2,
+                          const float* k2e, const float* out, const float* z, const float* g_out,
+                          float* delta /*[N, heads]*/, float* dq /*[N, HC]*/, float* de /*[E, HC]*/,
+                          float* dq2 /*[N, HC]*/, int64_t N, int64_t E, int64_t B, int max_nodes, int heads,
+                          int head_dim, double gamma, int full_graph, int32_t* flag /*[1]*/, void* stream);
+int hscn_san_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const int32_t* ptr32,
+                          const float* q, const float* k, const float* v, const float* e, const float* q2,
+                          const float* k2e, const float* z, const float* delta, const float* g_out,
+                          float* dk /*[N, HC]*/, float* dv /*[N, HC]*/, float* dk2e /*[N, HC]*/, int64_t N, int64_t E,
+                          int64_t B, int max_nodes, int heads, int head_dim, double gamma, int full_graph,
+                          int32_t* flag /*[1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
