@@ -287,6 +287,14 @@ _SIGNATURES = {
                                                  P, P]),
     "hscn_san_attn_bwd_src": (c_int, [P] * 16 + [c_int64, c_int64, c_int64, c_int, c_int, c_int, ctypes.c_double, c_int,
                                                  P, P]),
+    # GCNII's layer, PyG GCN2Conv: gather, mix, weight product and epilogue as one launch (csrc/gcn2.hip; additive to
+    # ABI 24)
+    "hscn_gcn2_supported": (c_int, [c_int]),
+    "hscn_gcn2_plan": (c_int, [c_int, c_int, P]),
+    "hscn_gcn2_fwd": (c_int, [P] * 9 + [c_int64, c_int, ctypes.c_double, ctypes.c_double, c_int, P]),
+    "hscn_gcn2_bwd": (c_int, [P] * 7 + [c_int64, c_int, ctypes.c_double, ctypes.c_double, c_int, P]),
+    "hscn_gcn2_bwd_w_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "hscn_gcn2_bwd_w": (c_int, [P] * 5 + [c_int64, c_int, ctypes.c_double, P, c_size_t, P]),
 }
 
 

@@ -7,6 +7,7 @@ is optional here (the reference makes it mandatory, config.py:146-152).
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Callable, Optional
 
@@ -362,6 +363,58 @@ class SANConfig:
 
 
 @dataclass
+class GCNIIConfig:
+    """The GCNII model (extension; model/gcnii.py, LRGB's GCNII baseline): ``num_layers`` ``GCN2Conv`` layers of width
+    ``hidden_channels`` -- each reads the running representation and the encoder's output x_0, mixed by ``alpha``, through
+    a weight whose share ``beta_l = log(theta / l + 1)`` decays with depth (``theta=None``: 1) -- with ReLU and dropout
+    after each, ``residual`` adding the layer's input, behind a node encoder (Linear or "atom").  ``edge_attr`` is not
+    read.  ``hidden_channels`` must be a multiple of 4 in [4, 512] (the kernel's envelope, csrc/gcn2.hip).
+    ``activation`` is the head's."""
+    activation: str
+    hidden_channels: int = HIDDEN_CHANNELS
+    num_layers: int = NUM_LAYERS
+    dropout: float = DROPOUT
+    alpha: float = 0.1
+    theta: Optional[float] = 0.5
+    shared_weights: bool = True
+    residual: bool = False
+    task_level: str = "graph"
+    node_encoder: Optional[str] = None
+    # a trainable positional encoder inside the model (model/_common.py PosEnc): a LapPEConfig or an RWSEConfig whose
+    # dim_emb is hidden_channels; pe_undirected: the edge lists hold both directions
+    pos_enc: Optional[object] = None
+    pe_undirected: bool = True
+
+    def __post_init__(self):
+        from ..nn.functional import GCN2_ENVELOPE, gcn2_supported
+        if self.task_level not in TASK_LEVELS:
+            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        if self.activation.lower() not in ACT_DICT:
+            raise ValueError(f"activation must be one of {sorted(ACT_DICT)}, got {self.activation!r}")
+        if self.node_encoder not in (None,) + NODE_ENCODERS:
+            raise ValueError(f"node_encoder must be one of {NODE_ENCODERS} or None, got {self.node_encoder!r}")
+        _check_pos_enc(self.pos_enc, self.hidden_channels)
+        a, t = self.alpha, self.theta
+        if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) <= 1.0:
+            raise ValueError(f"alpha must be a number in [0, 1], got {a!r}")
+        if t is not None and (isinstance(t, bool) or not isinstance(t, (int, float))
+                              or not 0.0 < float(t) < float("inf")):
+            raise ValueError(f"theta must be a positive, finite number or None, got {t!r}")
+        for name in ("shared_weights", "residual"):
+            if not isinstance(getattr(self, name), bool):
+                raise ValueError(f"{name} must be a bool, got {getattr(self, name)!r}")
+        if self.dropout and not (0.0 <= self.dropout < 1.0):
+            raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
+        if isinstance(self.num_layers, bool) or not isinstance(self.num_layers, int) or self.num_layers < 1:
+            raise ValueError(f"num_layers must be an int >= 1, got {self.num_layers!r}")
+        h = self.hidden_channels
+        if isinstance(h, bool) or not isinstance(h, int) or not gcn2_supported(h):
+            raise ValueError(f"hidden_channels = {h!r} outside the GCN2Conv kernel's envelope ({GCN2_ENVELOPE}).")
+        if t is not None and math.log(float(t) + 1.0) > 1.0:
+            raise ValueError(f"theta = {t!r} gives beta_1 = log(theta + 1) > 1; theta must be at most e - 1")
+
+
+@dataclass
 class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent there)
     activation: str
     lv_conv_type: str = "GAT"
@@ -519,8 +572,8 @@ class LapPEConfig:
 
 @dataclass
 class TrainingConfig:  # config.py:133-152
-    # "hscn" / "mpnn" (the reference's two: HSCNConfig / MPNNConfig), "gps" (extension: GPSConfig, model/gps.py) or
-    # "san" (extension: SANConfig, model/san.py)
+    # "hscn" / "mpnn" (the reference's two: HSCNConfig / MPNNConfig), "gps" (extension: GPSConfig, model/gps.py),
+    # "san" (extension: SANConfig, model/san.py) or "gcnii" (extension: GCNIIConfig, model/gcnii.py)
     model_type: str
     loss_fn: str
     # "ap" / "mae" (the reference's two), "accuracy" / "f1_macro" for class-index targets, or "mrr" / "hits@1" /

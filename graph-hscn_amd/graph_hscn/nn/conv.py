@@ -126,6 +126,81 @@ class GCNConv(nn.Module):
         return Fh.GCNConvFn.apply(x, self.lin.weight, self.bias, rel, ACT[act])
 
 
+class GCN2Conv(nn.Module):
+    """PyG GCN2Conv (GCNII; Chen et al. 2020), ``add_self_loops=True``, ``normalize=True``, unit edge weights:
+
+        p   = A_hat x                                    A_hat: GCNConv's symmetric normalisation with self loops
+        out = (1 - beta) h + beta h weight1,             h = (1 - alpha) p + alpha x_0               (shared_weights)
+        out = (1 - beta) h + beta ((1 - alpha) p weight1 + alpha x_0 weight2)                        (otherwise)
+
+    ``beta = log(theta / layer + 1)``, or 1 when ``theta`` or ``layer`` is None.  Parameters and ``state_dict`` keys
+    are PyG's: ``weight1`` [channels, channels] and, with ``shared_weights=False``, ``weight2``; glorot; no bias.
+    ``forward(x, x_0, edge_index_or_Relation, act=...)``: ``x_0`` may be longer than ``x`` (its first N rows are read, as
+    PyG slices them); a ``Relation`` is the self-loop relation already built (``structure.self_loop_relation_of``),
+    which a model's layers share.  The layer is ONE launch (csrc/gcn2.hip), ``act`` ("identity" or "relu") applied in
+    its epilogue.
+
+    Not provided, refused by name: ``edge_weight=``, ``cached=True``, ``normalize=False``, ``add_self_loops=False``."""
+
+    def __init__(self, channels: int, alpha: float, theta: Optional[float] = None, layer: Optional[int] = None,
+                 shared_weights: bool = True, cached: bool = False, add_self_loops: bool = True,
+                 normalize: bool = True):
+        super().__init__()
+        if cached:
+            raise NotImplementedError("GCN2Conv(cached=True): the normalised structure is cached per edge_index tensor "
+                                      "already (structure.self_loop_relation_of); cached must be False")
+        if not normalize:
+            raise NotImplementedError("GCN2Conv(normalize=False): the operator applies GCNConv's symmetric "
+                                      "normalisation; an unnormalised propagation is not provided")
+        if not add_self_loops:
+            raise NotImplementedError("GCN2Conv(add_self_loops=False): the operator runs over the relation with one "
+                                      "loop per node, as GCNConv(add_self_loops=True) builds it")
+        channels = int(channels)
+        if not Fh.gcn2_supported(channels):
+            raise ValueError(f"GCN2Conv: channels = {channels} outside the kernel's envelope ({Fh.GCN2_ENVELOPE})")
+        if (theta is not None and not float(theta) > 0.0) or (layer is not None and int(layer) < 1):
+            raise ValueError(f"GCN2Conv: theta must be positive and layer >= 1 (or None), got {theta!r}, {layer!r}")
+        self.channels, self.theta, self.layer = channels, theta, layer
+        self.beta = 1.0 if theta is None or layer is None else math.log(float(theta) / int(layer) + 1.0)
+        self.alpha, self.beta = Fh._check_gcn2_coeffs(alpha, self.beta)
+        self.shared_weights = bool(shared_weights)
+        self.weight1 = nn.Parameter(torch.empty(channels, channels))
+        if self.shared_weights:
+            self.register_parameter("weight2", None)
+        else:
+            self.weight2 = nn.Parameter(torch.empty(channels, channels))
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        _glorot(self.weight1)
+        if self.weight2 is not None:
+            _glorot(self.weight2)
+
+    def forward(self, x: Tensor, x_0: Tensor, edge_index: Union[Tensor, Relation], edge_weight: Optional[Tensor] = None,
+                act: str = "identity") -> Tensor:
+        if edge_weight is not None:
+            raise NotImplementedError("GCN2Conv(edge_weight=...): the operator propagates unit edge weights; "
+                                      "edge_weight must be None")
+        if act not in Fh.GCN2_ACTS:
+            raise ValueError(f"GCN2Conv: act must be one of {Fh.GCN2_ACTS}, got {act!r}")
+        if not isinstance(x, Tensor) or x.dim() != 2 or x.size(1) != self.channels:
+            raise ValueError(f"GCN2Conv: x must be [N, {self.channels}], got {tuple(getattr(x, 'shape', ()))}")
+        n = x.size(0)
+        if x_0.dim() != 2 or x_0.size(1) != self.channels or x_0.size(0) < n:
+            raise ValueError(f"GCN2Conv: x_0 must be [>= {n}, {self.channels}], got {tuple(x_0.shape)}")
+        x_0 = x_0[:n]
+        if n == 0:
+            rel = None                            # nothing to propagate over and nothing to launch
+        elif isinstance(edge_index, Relation):
+            rel = edge_index                      # the caller built the structure, loops included
+        else:
+            rel = self_loop_relation_of(edge_index, n, both=torch.is_grad_enabled() and x.requires_grad)
+        return Fh.GCN2ConvFn.apply(x, x_0, self.weight1, self.weight2, rel, self.alpha, self.beta, ACT[act])
+
+    def __repr__(self) -> str:
+        return f"GCN2Conv({self.channels}, alpha={self.alpha}, beta={self.beta})"
+
+
 class GATConv(nn.Module):
     """PyG GATConv, heads=1, negative_slope=0.2, dropout=0, in its two uses:
 

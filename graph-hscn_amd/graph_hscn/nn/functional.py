@@ -329,6 +329,137 @@ class GCNConvFn(Function):
 
 
 # --------------------------------------------------------------------------- #
+# GCNII's layer, PyG GCN2Conv (csrc/gcn2.hip)
+# --------------------------------------------------------------------------- #
+GCN2_MIN_WIDTH = 4
+GCN2_MAX_WIDTH = 512
+GCN2_ENVELOPE = f"channels a multiple of 4 in [{GCN2_MIN_WIDTH}, {GCN2_MAX_WIDTH}]"
+GCN2_ROW_TILE = 32                 # rows a workgroup of the forward owns at a time; with two weights (two LDS tiles):
+GCN2_ROW_TILE_TWO = 16
+GCN2_RESIDENT_BYTES = 96 * 1024    # tile(s) + whole weight(s) within this: the weight stays in LDS
+GCN2_TWO_WG_BYTES = 80 * 1024      # a streamed panel is chosen to leave room for two workgroups a CU, where one does
+GCN2_LDS_BYTES = 160 * 1024
+GCN2_PANELS = (64, 32, 16)
+GCN2_ACTS = ("identity", "relu")
+
+
+def gcn2_supported(H: int) -> bool:
+    """The kernel's envelope (include/hscn.h: hscn_gcn2_supported), restated so that a config validates without the
+    library; tests/test_gcn2_host.py pins the two to each other."""
+    return GCN2_MIN_WIDTH <= H <= GCN2_MAX_WIDTH and H % 4 == 0
+
+
+def gcn2_plan(H: int, shared_weights: bool = True) -> dict:
+    """What the forward launch chooses for width ``H`` (hscn_gcn2_plan's arithmetic; the host test pins the two):
+    ``row_tile``, ``panel`` (weight columns in LDS at a time), ``resident`` (the whole weight stays in LDS) and ``lds``
+    bytes."""
+    if not gcn2_supported(H):
+        raise ValueError(f"GCN2Conv: width H={H} outside the kernel's envelope ({GCN2_ENVELOPE})")
+    nw = 1 if shared_weights else 2
+    rt = GCN2_ROW_TILE if shared_weights else GCN2_ROW_TILE_TWO
+    tiles = nw * rt * (H + 2) * 4
+    hp32 = (H + 31) // 32 * 32
+    if tiles + nw * H * hp32 * 4 <= GCN2_RESIDENT_BYTES:
+        return {"row_tile": rt, "panel": hp32, "resident": True, "lds": tiles + nw * H * hp32 * 4}
+    for budget in (GCN2_TWO_WG_BYTES, GCN2_LDS_BYTES):
+        for pw in GCN2_PANELS:
+            if tiles + nw * H * pw * 4 <= budget:
+                return {"row_tile": rt, "panel": pw, "resident": False, "lds": tiles + nw * H * pw * 4}
+    raise ValueError(f"GCN2Conv: no LDS plan for H={H}")
+
+
+def gcn2_resident_max_width(shared_weights: bool = True) -> int:
+    """The widest H whose weight(s) stay in LDS: the weight-panel edge (128; 96 with two weights)."""
+    return max(H for H in range(GCN2_MIN_WIDTH, GCN2_MAX_WIDTH + 1, 4) if gcn2_plan(H, shared_weights)["resident"])
+
+
+def _check_gcn2_coeffs(alpha, beta) -> Tuple[float, float]:
+    for name, v in (("alpha", alpha), ("beta", beta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"GCN2Conv: {name} must be a number, got {v!r}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"GCN2Conv: alpha must be in [0, 1], got {alpha!r}")
+    if not 0.0 < float(beta) <= 1.0:
+        raise ValueError(f"GCN2Conv: beta must be in (0, 1], got {beta!r}")
+    return float(alpha), float(beta)
+
+
+class GCN2ConvFn(Function):
+    """``apply(x, x0, W1, W2_or_None, rel, alpha, beta, act) -> out [N, H]``: one GCNII layer over ``rel`` (the
+    self-loop relation ``GCNConv`` builds, with its ``dinv``) as ONE launch (hscn_gcn2_fwd):
+
+        p = A_hat x;   W2 None: h = (1 - alpha) p + alpha x0,  y = (1 - beta) h + beta h W1
+                       else:    y = (1 - beta) ((1 - alpha) p + alpha x0) + beta ((1 - alpha) p W1 + alpha x0 W2)
+        out = act(y)
+
+    ``W1`` / ``W2`` are [H, H] in PyG's layout.  The backward is at most three calls: hscn_gcn2_bwd (the cotangent of y,
+    the products with the transposed weights, the gradient of x0), hscn_gcn2_bwd_w (the weight gradients through
+    ``linear``'s ordered two-stage reduction) and the gather over ``rel.csr_t`` (hscn_spmm_csr_gcn) for the gradient of
+    x; only what ``needs_input_grad`` asks for is computed, and with ``alpha == 1`` the gradient of x is exact zeros
+    without a gather."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, x0: Tensor, W1: Tensor, W2: Optional[Tensor], rel: Relation, alpha: float, beta: float,
+                act: int):
+        alpha, beta = _check_gcn2_coeffs(alpha, beta)
+        if act not in (ACT["identity"], ACT["relu"]):
+            raise ValueError(f"GCN2Conv: the epilogue is one of {GCN2_ACTS} (got code {act})")
+        x, x0, W1, W2 = _c(x), _c(x0), _c(W1), _c(W2)
+        if x.dim() != 2 or x0.shape != x.shape:
+            raise ValueError(f"GCN2Conv: x and x0 must both be [N, H], got {tuple(x.shape)} and {tuple(x0.shape)}")
+        N, H = x.shape
+        if not gcn2_supported(H):
+            raise ValueError(f"GCN2Conv: width H={H} outside the kernel's envelope ({GCN2_ENVELOPE})")
+        for name, W in (("weight1", W1), ("weight2", W2)):
+            if W is not None and tuple(W.shape) != (H, H):
+                raise ValueError(f"GCN2Conv: {name} must be [{H}, {H}], got {tuple(W.shape)}")
+        if N and (rel.num_src != N or rel.num_dst != N):
+            raise ValueError(f"GCN2Conv: the relation is {rel.num_src} -> {rel.num_dst} nodes, x has {N} rows")
+        out = torch.empty(N, H, dtype=torch.float32, device=x.device)
+        h = torch.empty(N, H, dtype=torch.float32, device=x.device)
+        if N:
+            call("hscn_gcn2_fwd", ptr(rel.csr.rowptr), ptr(rel.csr.col), ptr(rel.dinv), ptr(x), ptr(x0), ptr(W1), ptr(W2),
+                 ptr(out), ptr(h), N, H, alpha, beta, act, stream())
+        ctx.rel, ctx.alpha, ctx.beta, ctx.act, ctx.two = rel, alpha, beta, act, W2 is not None
+        ctx.save_for_backward(x0, W1, W2, out, h)
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x0, W1, W2, out, h = ctx.saved_tensors
+        rel: Relation = ctx.rel
+        N, H = out.shape
+        need_x, need_x0, need_w1, need_w2 = ctx.needs_input_grad[:4]
+        need_w2 = need_w2 and ctx.two
+        dev = out.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        zeros = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        if N == 0:
+            return (zeros(0, H) if need_x else None, zeros(0, H) if need_x0 else None, zeros(H, H) if need_w1 else None,
+                    zeros(H, H) if need_w2 else None, None, None, None, None)
+        g = _c(g)
+        gather = need_x and ctx.alpha != 1.0
+        gyb = new(N, H) if (need_w1 or need_w2) else None
+        gp = new(N, H) if gather else None
+        gx0 = new(N, H) if need_x0 else None
+        if gyb is not None or gp is not None or gx0 is not None:
+            call("hscn_gcn2_bwd", ptr(g), ptr(out), ptr(W1), ptr(W2), ptr(gyb), ptr(gp), ptr(gx0), N, H, ctx.alpha,
+                 ctx.beta, ctx.act, stream())
+        gW1 = gW2 = None
+        if gyb is not None:
+            gW1 = new(H, H) if need_w1 else None
+            gW2 = new(H, H) if need_w2 else None
+            nbytes = int(_hip.lib().hscn_gcn2_bwd_w_workspace_bytes(N, H))
+            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+            call("hscn_gcn2_bwd_w", ptr(gyb), ptr(h), ptr(x0) if need_w2 else None, ptr(gW1), ptr(gW2), N, H, ctx.alpha,
+                 ptr(ws), nbytes, stream())
+        gx = None
+        if need_x:
+            gx = spmm_gcn_raw(rel.csr_t, rel.dinv, rel.dinv, gp) if gather else zeros(N, H)
+        return gx, gx0, gW1, gW2, None, None, None, None
+
+
+# --------------------------------------------------------------------------- #
 # GraphConv (edge-weighted sum aggregation)
 # --------------------------------------------------------------------------- #
 class GraphConvFn(Function):

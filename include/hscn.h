@@ -1894,6 +1894,47 @@ int hscn_san_attn_bwd_src(const int32_t* rowptr_t, const int32_t* col_t, const i
                           int64_t B, int max_nodes, int heads, int head_dim, double gamma, int full_graph,
                           int32_t* flag /*[1]*/, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * GCNII's layer, PyG GCN2Conv (csrc/gcn2.hip).  Purely additive to ABI 24.
+ *
+ * x, x0, out, h f32 [N, H]; W1, W2 f32 [H, H] in PyG's layout (h @ W1, no transpose), W2 NULL = shared weights;
+ * (rowptr, col) the target-keyed stable CSR of the edge list WITH one loop per node appended
+ * (structure.self_loop_relation_of) and dinv f32 [N] its in-degree^-1/2 (hscn_gcn_dinv): unit edge weights, symmetric
+ * normalisation, a graph's repeated edges count as often as they occur.  alpha in [0, 1], beta in (0, 1].
+ *     p_i = sum over the row's CSR slots j of (dinv_i dinv_j) x_j      slot order, product and sum rounded separately
+ *     W2 == NULL:  h = (1 - alpha) p + alpha x0,  y = (1 - beta) h + beta (h W1)                       saved: h
+ *     else:        pa = (1 - alpha) p, xa = alpha x0,  y = (1 - beta) (pa + xa) + beta (pa W1 + xa W2)  saved: pa
+ *     out = act(y)     act: HSCN_ACT_IDENTITY or HSCN_ACT_RELU
+ * hscn_gcn2_fwd: ONE launch.  A workgroup owns a tile of rows (hscn_gcn2_plan: 32; 16 with two weights), gathers it
+ *   into LDS, multiplies it by the weight on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain per element) and writes
+ *   out and the saved tile `h`; no other [N, H] value reaches memory.  The weight stays in LDS where tile and weight fit
+ *   96 KB (H <= 128; H <= 96 with two weights); wider, it passes through LDS in column panels of 64 / 32 / 16 columns
+ *   inside the same launch.
+ * hscn_gcn2_bwd: ONE launch over gy = act'(out) g: gyb = beta gy [N, H] (the cotangent the weight gradients multiply),
+ *   gp = (1 - alpha) ((1 - beta) gy + beta gy W1^T) [N, H] (whose gather over the source-keyed CSR,
+ *   hscn_spmm_csr_gcn, is the gradient of x) and gx0 = alpha ((1 - beta) gy + beta gy Wx^T), Wx = W1 shared, W2 else;
+ *   each may be NULL and is then not computed.
+ * hscn_gcn2_bwd_w: gW1 [H, H] = h^T gyb and, with two weights, gW2 = alpha x0^T gyb, each through hscn_linear_bwd_w's
+ *   ordered two-stage reduction (row chunks in row order, chunks folded in a fixed tree), either may be NULL.
+ *   No float atomics: two runs give the same bits.
+ * hscn_gcn2_supported: 1 for H a multiple of 4 in [4, 512].  hscn_gcn2_plan: plan[4] = {rows per tile of the forward,
+ *   weight columns in LDS at a time, 1 if the weight stays in LDS, LDS bytes} (host arithmetic).
+ *   HSCN_E_BADARG for null or misaligned (16 bytes) pointers, N negative or beyond int32, alpha or beta out of range;
+ *   HSCN_E_UNSUPPORTED for a width outside the envelope or another act; both before any launch.  N = 0 launches
+ *   nothing.  No host synchronisation.
+ * ------------------------------------------------------------------------- */
+int hscn_gcn2_supported(int H);
+int hscn_gcn2_plan(int H, int two_weights, int32_t* plan /*[4]*/);
+int hscn_gcn2_fwd(const int32_t* rowptr, const int32_t* col, const float* dinv, const float* x, const float* x0,
+                  const float* W1, const float* W2, float* out /*[N, H]*/, float* h /*[N, H]*/, int64_t N, int H,
+                  double alpha, double beta, int act, void* stream);
+int hscn_gcn2_bwd(const float* g, const float* out, const float* W1, const float* W2, float* gyb /*[N, H]*/,
+                  float* gp /*[N, H]*/, float* gx0 /*[N, H]*/, int64_t N, int H, double alpha, double beta, int act,
+                  void* stream);
+size_t hscn_gcn2_bwd_w_workspace_bytes(int64_t N, int H);
+int hscn_gcn2_bwd_w(const float* gyb, const float* h, const float* x0, float* gW1 /*[H, H]*/, float* gW2 /*[H, H]*/,
+                    int64_t N, int H, double alpha, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
