@@ -77,11 +77,66 @@ EDGE_AWARE_CONVS = ("gine", "gatedgcn", "transformerconv_edge", "pna_edge")
 PNA_CONVS = ("pna", "pna_edge")
 
 
-def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
+GPS_NORMS = ("layer", "batch", None)
+
+
+def _check_task_level(task_level) -> None:
+    if task_level not in TASK_LEVELS:
+        raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {task_level!r}")
+
+
+def _check_activation(activation) -> None:
+    if activation.lower() not in ACT_DICT:
+        raise ValueError(f"activation must be one of {sorted(ACT_DICT)}, got {activation!r}")
+
+
+def _check_encoder_names(node_encoder, edge_encoder=None) -> None:
+    """The names alone: SAN and GCNII have no ``conv_type`` to tie an edge encoder to (``_check_encoders`` does)."""
     if node_encoder not in (None,) + NODE_ENCODERS:
         raise ValueError(f"node_encoder must be one of {NODE_ENCODERS} or None, got {node_encoder!r}")
     if edge_encoder not in (None,) + EDGE_ENCODERS:
         raise ValueError(f"edge_encoder must be one of {EDGE_ENCODERS} or None, got {edge_encoder!r}")
+
+
+def _check_dropout(dropout) -> None:
+    """[0, 1): the layered-only models' rule (MPNNConfig keeps the reference's, which admits 1.0)."""
+    if dropout and not (0.0 <= dropout < 1.0):
+        raise ValueError(f"{dropout} must be in [0.0, 1.0).")
+
+
+def _check_positive(*values) -> None:
+    for v in values:
+        if v < 1:
+            raise ValueError(f"{v} must be positive.")
+
+
+def _check_norm(norm) -> None:
+    if norm not in GPS_NORMS:
+        raise ValueError(f"norm must be 'layer', 'batch' or None, got {norm!r}")
+
+
+def _check_attention_width(hidden_channels, num_heads) -> None:
+    """The envelope GPS's and SAN's attention kernels share (csrc/attention.hip, csrc/san.hip)."""
+    if hidden_channels % num_heads:
+        raise ValueError(f"hidden_channels {hidden_channels} must be divisible by num_heads {num_heads}.")
+    dh = hidden_channels // num_heads
+    if dh % 4 or not 4 <= dh <= 64 or hidden_channels > 512:
+        raise ValueError(f"head width {dh} (hidden_channels / num_heads) must be a multiple of 4 in [4, 64] and "
+                         f"hidden_channels at most 512.")
+
+
+def check_exphormer(expander_degree, num_virtual_nodes) -> None:
+    """Exphormer's two sizes against the kernels' bounds: what ``GPSConfig`` and ``model.gps.GPS`` both ask."""
+    from ..nn.functional import EXPANDER_MAX_DEGREE, EXPH_MAX_VIRTUAL_NODES
+    d, nv = expander_degree, num_virtual_nodes
+    if isinstance(d, bool) or not isinstance(d, int) or d % 2 or not 2 <= d <= EXPANDER_MAX_DEGREE:
+        raise ValueError(f"expander_degree must be an even integer in [2, {EXPANDER_MAX_DEGREE}], got {d!r}")
+    if isinstance(nv, bool) or not isinstance(nv, int) or not 0 <= nv <= EXPH_MAX_VIRTUAL_NODES:
+        raise ValueError(f"num_virtual_nodes must be an integer in [0, {EXPH_MAX_VIRTUAL_NODES}], got {nv!r}")
+
+
+def _check_encoders(node_encoder, edge_encoder, conv_type) -> None:
+    _check_encoder_names(node_encoder, edge_encoder)
     if edge_encoder is not None and (conv_type is None or conv_type.lower() not in EDGE_AWARE_CONVS):
         raise ValueError(f"edge_encoder={edge_encoder!r} needs an edge-aware convolution {EDGE_AWARE_CONVS}, "
                          f"got {conv_type!r}")
@@ -153,6 +208,11 @@ class PNAConfig:
         return cls(tuple(aggregators), tuple(scalers), cls.avg_deg_log_of(graphs))
 
 
+def pna_kwargs(pna: Optional[PNAConfig]) -> dict:
+    """The keywords a "pna" / "pna_edge" layer is built with (None: the layer's defaults)."""
+    return {} if pna is None else dict(aggregators=pna.aggregators, scalers=pna.scalers, avg_deg_log=pna.avg_deg_log)
+
+
 def _check_pna(pna, conv_type) -> None:
     if pna is None:
         return
@@ -209,8 +269,7 @@ class MPNNConfig:  # config.py:49-73
     pna: Optional[PNAConfig] = None
 
     def __post_init__(self):
-        if self.task_level not in TASK_LEVELS:
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        _check_task_level(self.task_level)
         _check_encoders(self.node_encoder, self.edge_encoder, self.conv_type)
         _check_pna(self.pna, self.conv_type)
         _check_pos_enc(self.pos_enc, self.hidden_channels)
@@ -220,9 +279,6 @@ class MPNNConfig:  # config.py:49-73
         for v in (self.num_layers, self.hidden_channels):
             if v < 0:
                 raise ValueError(f"{v} must be non-negative.")
-
-
-GPS_NORMS = ("layer", "batch", None)
 
 
 @dataclass
@@ -265,8 +321,7 @@ class GPSConfig:
     pna: Optional[PNAConfig] = None
 
     def __post_init__(self):
-        if self.task_level not in TASK_LEVELS:
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        _check_task_level(self.task_level)
         _check_encoders(self.node_encoder, self.edge_encoder, self.local_conv_type)
         _check_pna(self.pna, self.local_conv_type)
         _check_pos_enc(self.pos_enc, self.hidden_channels)
@@ -277,11 +332,7 @@ class GPSConfig:
         if self.global_model == "exphormer" and self.attn_bias is not None:
             raise ValueError(f"global_model='exphormer' and attn_bias={self.attn_bias!r} do not go together: the "
                              "shortest-path bias belongs to the dense attention (attn_bias must be None)")
-        d, nv = self.expander_degree, self.num_virtual_nodes
-        if isinstance(d, bool) or not isinstance(d, int) or d % 2 or not 2 <= d <= 32:
-            raise ValueError(f"expander_degree must be an even integer in [2, 32], got {d!r}")
-        if isinstance(nv, bool) or not isinstance(nv, int) or not 0 <= nv <= 4:
-            raise ValueError(f"num_virtual_nodes must be an integer in [0, 4], got {nv!r}")
+        check_exphormer(self.expander_degree, self.num_virtual_nodes)
         if not isinstance(self.add_local_edges, bool):
             raise ValueError(f"add_local_edges must be a bool, got {self.add_local_edges!r}")
         if isinstance(self.expander_seed, bool) or not isinstance(self.expander_seed, int) or self.expander_seed < 0:
@@ -289,21 +340,12 @@ class GPSConfig:
         if isinstance(self.spd_max_dist, bool) or not isinstance(self.spd_max_dist, int) or \
                 not 1 <= self.spd_max_dist <= 63:
             raise ValueError(f"spd_max_dist must be an integer in [1, 63], got {self.spd_max_dist!r}")
-        if self.dropout and not (0.0 <= self.dropout < 1.0):
-            raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
-        for v in (self.num_layers, self.hidden_channels, self.num_heads):
-            if v < 1:
-                raise ValueError(f"{v} must be positive.")
+        _check_dropout(self.dropout)
+        _check_positive(self.num_layers, self.hidden_channels, self.num_heads)
         if self.local_conv_type is not None and self.local_conv_type.lower() not in CONV_DICT:
             raise ValueError(f"local_conv_type must be one of {sorted(CONV_DICT)} or None, got {self.local_conv_type!r}")
-        if self.norm not in GPS_NORMS:
-            raise ValueError(f"norm must be 'layer', 'batch' or None, got {self.norm!r}")
-        if self.hidden_channels % self.num_heads:
-            raise ValueError(f"hidden_channels {self.hidden_channels} must be divisible by num_heads {self.num_heads}.")
-        dh = self.hidden_channels // self.num_heads
-        if dh % 4 or not 4 <= dh <= 64 or self.hidden_channels > 512:
-            raise ValueError(f"head width {dh} (hidden_channels / num_heads) must be a multiple of 4 in [4, 64] and "
-                             f"hidden_channels at most 512.")
+        _check_norm(self.norm)
+        _check_attention_width(self.hidden_channels, self.num_heads)
 
 
 @dataclass
@@ -333,33 +375,19 @@ class SANConfig:
     pe_undirected: bool = True
 
     def __post_init__(self):
-        if self.task_level not in TASK_LEVELS:
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
-        if self.activation.lower() not in ACT_DICT:
-            raise ValueError(f"activation must be one of {sorted(ACT_DICT)}, got {self.activation!r}")
-        if self.node_encoder not in (None,) + NODE_ENCODERS:
-            raise ValueError(f"node_encoder must be one of {NODE_ENCODERS} or None, got {self.node_encoder!r}")
-        if self.edge_encoder not in (None,) + EDGE_ENCODERS:
-            raise ValueError(f"edge_encoder must be one of {EDGE_ENCODERS} or None, got {self.edge_encoder!r}")
+        _check_task_level(self.task_level)
+        _check_activation(self.activation)
+        _check_encoder_names(self.node_encoder, self.edge_encoder)
         _check_pos_enc(self.pos_enc, self.hidden_channels)
         g = self.gamma
         if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0.0 <= float(g) < float("inf"):
             raise ValueError(f"gamma must be a finite number >= 0, got {g!r}")
         if not isinstance(self.full_graph, bool):
             raise ValueError(f"full_graph must be a bool, got {self.full_graph!r}")
-        if self.dropout and not (0.0 <= self.dropout < 1.0):
-            raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
-        for v in (self.num_layers, self.hidden_channels, self.num_heads):
-            if v < 1:
-                raise ValueError(f"{v} must be positive.")
-        if self.norm not in GPS_NORMS:
-            raise ValueError(f"norm must be 'layer', 'batch' or None, got {self.norm!r}")
-        if self.hidden_channels % self.num_heads:
-            raise ValueError(f"hidden_channels {self.hidden_channels} must be divisible by num_heads {self.num_heads}.")
-        dh = self.hidden_channels // self.num_heads
-        if dh % 4 or not 4 <= dh <= 64 or self.hidden_channels > 512:
-            raise ValueError(f"head width {dh} (hidden_channels / num_heads) must be a multiple of 4 in [4, 64] and "
-                             f"hidden_channels at most 512.")
+        _check_dropout(self.dropout)
+        _check_positive(self.num_layers, self.hidden_channels, self.num_heads)
+        _check_norm(self.norm)
+        _check_attention_width(self.hidden_channels, self.num_heads)
 
 
 @dataclass
@@ -387,12 +415,9 @@ class GCNIIConfig:
 
     def __post_init__(self):
         from ..nn.functional import GCN2_ENVELOPE, gcn2_supported
-        if self.task_level not in TASK_LEVELS:
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
-        if self.activation.lower() not in ACT_DICT:
-            raise ValueError(f"activation must be one of {sorted(ACT_DICT)}, got {self.activation!r}")
-        if self.node_encoder not in (None,) + NODE_ENCODERS:
-            raise ValueError(f"node_encoder must be one of {NODE_ENCODERS} or None, got {self.node_encoder!r}")
+        _check_task_level(self.task_level)
+        _check_activation(self.activation)
+        _check_encoder_names(self.node_encoder)
         _check_pos_enc(self.pos_enc, self.hidden_channels)
         a, t = self.alpha, self.theta
         if isinstance(a, bool) or not isinstance(a, (int, float)) or not 0.0 <= float(a) <= 1.0:
@@ -403,8 +428,7 @@ class GCNIIConfig:
         for name in ("shared_weights", "residual"):
             if not isinstance(getattr(self, name), bool):
                 raise ValueError(f"{name} must be a bool, got {getattr(self, name)!r}")
-        if self.dropout and not (0.0 <= self.dropout < 1.0):
-            raise ValueError(f"{self.dropout} must be in [0.0, 1.0).")
+        _check_dropout(self.dropout)
         if isinstance(self.num_layers, bool) or not isinstance(self.num_layers, int) or self.num_layers < 1:
             raise ValueError(f"num_layers must be an int >= 1, got {self.num_layers!r}")
         h = self.hidden_channels
@@ -436,8 +460,7 @@ class HSCNConfig:  # config.py:76-93 (+ mp_units, read at main.py:102 but absent
     vl_conv_type: Optional[str] = None
 
     def __post_init__(self):
-        if self.task_level not in TASK_LEVELS:
-            raise ValueError(f"task_level must be 'graph', 'node' or 'link', got {self.task_level!r}")
+        _check_task_level(self.task_level)
         if not isinstance(self.heads, int) or self.heads < 1:
             raise ValueError(f"heads must be a positive int, got {self.heads!r}")
         convs = (self.lv_conv_type, self.ll_conv_type, self.vv_conv_type)

@@ -1,12 +1,26 @@
-"""What the models spell alike, stated once: the validation of ``task_level`` (MPNN, GPS, HSCN) and of the categorical
-encoders' names, the float ``edge_attr`` check and the link-level ``forward`` / ``embed`` pair of the two homogeneous
-models (model/mpnn.py MPNN, model/gps.py GPS)."""
+"""What the models spell alike, stated once: the validation of ``task_level`` (every model) and of the categorical
+encoders' names, the float ``edge_attr`` check, the trainable positional encoder (``PosEnc``) and the link-level
+``forward`` / ``embed`` pair (``LinkLevel``) of the homogeneous models, and ``LayeredModel``: the base of the
+homogeneous models that run on the layered operators only (model/gps.py GPS, model/san.py SAN, model/gcnii.py GCNII) --
+their construction steps, the surface ``train.batching`` and ``train.train`` use, the graph-level mean pool and the
+head.  A further model of that kind subclasses it and writes its own arguments, its layer stack and ``_nodes``."""
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
+import torch.nn as nn
 from torch import Tensor
 
-from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS
+from ..config.config import ACT_DICT
+from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
+from ..nn import functional as Fh
+from ..nn.conv import Linear
+from ..nn.head import NodeHead
+from ..nn.pool import global_mean_pool
+
+# hscn_segment_mean_fwd (csrc/pool.hip) gives a row at most 64 lanes of four columns
+POOL_MAX_WIDTH = 256
 
 
 def check_task_level(task_level) -> None:
@@ -142,3 +156,141 @@ class LinkLevel:
         if self.task_level != "link":
             raise RuntimeError("embed() belongs to a link-level model (task_level='link')")
         return self._forward(batch)
+
+
+class _Table(nn.Module):
+    """A learned table ``weight`` [rows, D], drawn normal(0, 1) as an ``nn.Embedding`` is."""
+
+    def __init__(self, rows: int, channels: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(rows, channels))
+        nn.init.normal_(self.weight)
+
+
+class LayeredModel(LinkLevel, PosEnc, nn.Module):
+    """A homogeneous model that runs on the layered operators only: a node encoder (Linear or "atom", with ``pos_enc``
+    beside it), a stack ``layers`` of the subclass's own and one head per task level -- "graph": mean pool, ``Linear(D,
+    D)``, activation, ``Linear(D, C)``; "node": the two Linears per node, through ``nn.head.NodeHead`` where its kernels
+    apply; "link": the node level's output as embeddings (``LinkLevel``).
+
+    A subclass's ``__init__`` calls the construction steps below in the order its ``state_dict`` and its RNG draws
+    ask for -- ``_check_args``, its own checks, ``_record``, ``_build_node_encoder``, its layers and encoders,
+    ``_build_head``, whatever it creates behind the head, ``_build_pos_encoder`` last -- and it writes ``_nodes`` and
+    ``_own_reason``, and ``_check_launch_flags`` / ``_edge_attr_reader`` where it has launch flags / reads
+    ``edge_attr``."""
+    layered_only = True      # train.batching.refuse_layered_only: the resident entry points refuse the model by name
+
+    # ---- construction steps ------------------------------------------------------------------------------------------
+    def _check_args(self, node_encoder, edge_encoder, task_level, num_layers) -> None:
+        check_encoders(node_encoder, edge_encoder)
+        check_task_level(task_level)
+        if num_layers < 1:
+            raise ValueError(f"{type(self).__name__} needs at least one layer")
+
+    def _record(self, task_level, num_layers, activation, dropout, node_encoder, edge_encoder) -> None:
+        """Validates ``activation`` (None: ReLU) and records what every such model keeps."""
+        activation = ACT_DICT["relu"] if activation is None else activation
+        if getattr(activation, "hscn_name", None) is None:
+            raise ValueError("activation must be one of config.ACT_DICT's (it runs in a Linear's epilogue)")
+        self.task_level = task_level
+        self.num_layers = int(num_layers)
+        self.activation = activation
+        self.dropout = float(dropout)
+        self.dropout_seed: Optional[int] = None     # tests pin the masks (the subclass numbers its layers' seeds)
+        self.encoder_kinds = (node_encoder, edge_encoder)
+        # "layered"; "auto" runs layered too; "resident" raises with the reason when the model is called
+        self.engine = "layered"
+        self.last_engine: Optional[str] = None
+
+    def _build_node_encoder(self, num_features, hidden, pos_enc, pe_undirected) -> None:
+        width = self._init_pos_enc(pos_enc, pe_undirected, hidden)     # hidden - dim_pe with a positional encoder
+        kind = self.encoder_kinds[0]
+        self.node_encoder = Linear(num_features, width) if kind is None else NODE_ENCODERS[kind](width)
+
+    def _build_head(self, hidden, num_classes) -> None:
+        self.lin_1 = Linear(hidden, hidden)
+        self.lin_2 = Linear(hidden, num_classes)
+        self._node_head = NodeHead(self.lin_1, self.lin_2, self.activation.hscn_name)
+
+    # ---- what a subclass supplies ------------------------------------------------------------------------------------
+    def _own_reason(self) -> str:
+        """Why the model's own layers have no one-launch, resident or captured form."""
+        raise NotImplementedError
+
+    def _check_launch_flags(self, dev) -> None:
+        """The ``nn.functional.check_*`` of the flag words the model's own launches write (none by default)."""
+
+    def _edge_attr_reader(self) -> str:
+        """The opening of the missing-``edge_attr`` message: what in the model reads the edge features."""
+        raise NotImplementedError
+
+    def _nodes(self, batch) -> Tensor:
+        """[N, D] after the last layer."""
+        raise NotImplementedError
+
+    # ---- the surface of a homogeneous model (train.batching, train.train) --------------------------------------------
+    def resident_reason(self, batch=None, need_grad: bool = False) -> str:
+        reason = self._own_reason()
+        if self.pos_enc is not None:
+            reason = reason + "; " + POSENC_RESIDENT_REASON
+        if any(self.encoder_kinds):
+            reason = reason + "; " + encoder_reason(*self.encoder_kinds)
+        return reason
+
+    def supported(self, batch=None) -> bool:
+        return False
+
+    def head_width(self) -> int:
+        """Columns of the prediction (what ``batching.score_width`` asks for class-index targets)."""
+        return int(self.lin_2.out_channels)
+
+    def check_flags(self) -> None:
+        """Synchronising: raises for a nonzero flag word of a launch since the last check -- the model's own
+        (``_check_launch_flags``), the categorical encoders' (an index outside its column) and the positional encoder's
+        statistics launches'.  ``train.train_epoch`` / ``eval_epoch`` call it once per epoch, beside the read of the
+        epoch's loss."""
+        dev = next(self.parameters()).device
+        self._check_launch_flags(dev)
+        if any(self.encoder_kinds):
+            Fh.check_categorical(dev)
+        self._check_pe_flags()
+
+    # ---- forward -----------------------------------------------------------------------------------------------------
+    def _edge_attr(self, batch) -> Tensor:
+        """``batch.edge_attr`` as the model's edge encoder or layers read it: int64 categories for a categorical edge
+        encoder (which checks them itself), else float32 [E, De] on the model's device."""
+        ea = getattr(batch, "edge_attr", None)
+        if ea is None:
+            raise ValueError(f"{self._edge_attr_reader()} and the batch carries no edge_attr "
+                             "(Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
+        if self.encoder_kinds[1] is not None:
+            return ea
+        return float_edge_attr(ea, next(self.parameters()).device)
+
+    def _embed_x(self, batch) -> Tensor:
+        return self.node_encoder(batch.x)
+
+    def _pool(self, x: Tensor, batch) -> Tensor:
+        """[B, D] graph means.  The mean pool's kernel takes ``POOL_MAX_WIDTH`` columns: a wider x (300, the LRGB
+        width) is pooled in column slices of that many, a column's mean being the same sum either way."""
+        num_graphs = getattr(batch, "num_graphs", None)
+        if x.size(1) <= POOL_MAX_WIDTH:
+            return global_mean_pool(x, batch.batch, num_graphs)
+        parts = [global_mean_pool(x[:, c:c + POOL_MAX_WIDTH].contiguous(), batch.batch, num_graphs)
+                 for c in range(0, x.size(1), POOL_MAX_WIDTH)]
+        return torch.cat(parts, 1)
+
+    def _head(self, x: Tensor) -> Tensor:
+        h = Fh.linear_wide(x, self.lin_1.weight, self.lin_1.bias, self.activation.hscn_name)
+        return Fh.linear_wide(h, self.lin_2.weight, self.lin_2.bias)
+
+    def _forward(self, batch) -> Tensor:
+        if self.engine not in ("layered", "auto", "resident"):
+            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
+        if self.engine == "resident":
+            raise RuntimeError(f"engine='resident' does not take this model: {self.resident_reason()}")
+        self.last_engine = "layered"
+        x = self._nodes(batch)
+        if self.task_level == "graph":
+            return self._head(self._pool(x, batch))
+        return self._node_head(x) if self._node_head.supported() else self._head(x)

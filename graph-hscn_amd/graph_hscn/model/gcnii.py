@@ -22,23 +22,16 @@ import torch.nn as nn
 from torch import Tensor
 
 from ..config.config import ACT_DICT, GCNIIConfig
-from ..encoder.categorical import NODE_ENCODERS, resident_reason as encoder_reason
-from ._common import POSENC_RESIDENT_REASON, LinkLevel, PosEnc, check_encoders, check_task_level
+from ._common import POOL_MAX_WIDTH, LayeredModel  # noqa: F401  (POOL_MAX_WIDTH stays importable from here)
 from ..nn import functional as Fh
-from ..nn.conv import GCN2Conv, Linear
-from ..nn.head import NodeHead
-from ..nn.pool import global_mean_pool
+from ..nn.conv import GCN2Conv
 from ..structure import self_loop_relation_of
 
-# hscn_segment_mean_fwd (csrc/pool.hip) gives a row at most 64 lanes of four columns
-POOL_MAX_WIDTH = 256
 RESIDENT_REASON = ("GCNII's layers (model/gcnii.py GCNII): a GCN2Conv stack that reads the initial representation in "
                    "every layer has no one-launch, resident or captured form; the model runs on the layered operators")
 
 
-class GCNII(LinkLevel, PosEnc, nn.Module):
-    layered_only = True      # train.batching.refuse_layered_only: the resident entry points refuse this model by name
-
+class GCNII(LayeredModel):
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int,
                  activation: Optional[Callable] = None, dropout: float = 0.0, alpha: float = 0.1,
                  theta: Optional[float] = 0.5, shared_weights: bool = True, residual: bool = False,
@@ -46,69 +39,24 @@ class GCNII(LinkLevel, PosEnc, nn.Module):
                  pe_undirected: bool = True) -> None:
         """``activation``: the head's (the layers' is ReLU, as LRGB's GCN2ConvLayer has it)."""
         super().__init__()
-        check_encoders(node_encoder, None)
-        check_task_level(task_level)
-        if num_layers < 1:
-            raise ValueError("GCNII needs at least one layer")
+        self._check_args(node_encoder, None, task_level, num_layers)
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
-        activation = ACT_DICT["relu"] if activation is None else activation
-        act = getattr(activation, "hscn_name", None)
-        if act is None:
-            raise ValueError("activation must be one of config.ACT_DICT's (it runs in a Linear's epilogue)")
-        self.task_level = task_level
-        self.num_layers = int(num_layers)
-        self.activation = activation
-        self.dropout = float(dropout)
-        self.dropout_seed: Optional[int] = None     # tests pin the masks (layer l = 1 .. L draws with seed + l)
+        # (pinned masks: layer l = 1 .. L draws with dropout_seed + l)
+        self._record(task_level, num_layers, activation, dropout, node_encoder, None)
         self.residual = bool(residual)
         H = int(hidden_channels)
-        self.encoder_kinds = (node_encoder, None)
-        Hx = self._init_pos_enc(pos_enc, pe_undirected, H)             # H - dim_pe with a positional encoder
-        self.node_encoder = Linear(num_features, Hx) if node_encoder is None else NODE_ENCODERS[node_encoder](Hx)
+        self._build_node_encoder(num_features, H, pos_enc, pe_undirected)
         self.layers = nn.ModuleList(GCN2Conv(H, alpha, theta, l, shared_weights) for l in range(1, num_layers + 1))
-        self.lin_1 = Linear(H, H)
-        self.lin_2 = Linear(H, num_classes)
-        self._node_head = NodeHead(self.lin_1, self.lin_2, act)
+        self._build_head(H, num_classes)
         self._build_pos_encoder(H)                  # after every parameter of before
-        # "layered"; "auto" runs layered too; "resident" raises with the reason when the model is called
-        self.engine = "layered"
-        self.last_engine: Optional[str] = None
 
-    # ---- the surface of a homogeneous model (train.batching, train.train) ----------------------------------------
-    def resident_reason(self, batch=None, need_grad: bool = False) -> str:
-        reason = RESIDENT_REASON
-        if self.pos_enc is not None:
-            reason = reason + "; " + POSENC_RESIDENT_REASON
-        if any(self.encoder_kinds):
-            return reason + "; " + encoder_reason(*self.encoder_kinds)
-        return reason
-
-    def supported(self, batch=None) -> bool:
-        return False
-
-    def head_width(self) -> int:
-        """Columns of the prediction (what ``batching.score_width`` asks for class-index targets)."""
-        return int(self.lin_2.out_channels)
-
-    def check_flags(self) -> None:
-        """Synchronising: raises for a flag word of the categorical encoder (an index outside its column) or of the
-        positional encoder's statistics launches; the GCN2Conv launches have none."""
-        if any(self.encoder_kinds):
-            Fh.check_categorical(next(self.parameters()).device)
-        self._check_pe_flags()
+    def _own_reason(self) -> str:                   # (the GCN2Conv launches have no flag word: no _check_launch_flags)
+        return RESIDENT_REASON
 
     # ---- forward -----------------------------------------------------------------------------------------------
-    def _embed_x(self, batch) -> Tensor:
-        return self.node_encoder(batch.x)
-
     def _nodes(self, batch) -> Tensor:
         """[N, H] after the last layer."""
-        if self.engine not in ("layered", "auto", "resident"):
-            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
-        if self.engine == "resident":
-            raise RuntimeError(f"engine='resident' does not take this model: {self.resident_reason()}")
-        self.last_engine = "layered"
         x = x0 = self.encode_nodes(batch)
         rel = self_loop_relation_of(batch.edge_index, x.size(0), both=torch.is_grad_enabled())   # ONE for all layers
         for l, conv in enumerate(self.layers, start=1):
@@ -119,26 +67,6 @@ class GCNII(LinkLevel, PosEnc, nn.Module):
             if self.residual:
                 x = x_in + x
         return x
-
-    def _pool(self, x: Tensor, batch) -> Tensor:
-        """[B, H] graph means.  The mean pool's kernel takes ``POOL_MAX_WIDTH`` columns: a wider x (H = 300, the LRGB
-        width) is pooled in column slices of that many, a column's mean being the same sum either way."""
-        num_graphs = getattr(batch, "num_graphs", None)
-        if x.size(1) <= POOL_MAX_WIDTH:
-            return global_mean_pool(x, batch.batch, num_graphs)
-        parts = [global_mean_pool(x[:, c:c + POOL_MAX_WIDTH].contiguous(), batch.batch, num_graphs)
-                 for c in range(0, x.size(1), POOL_MAX_WIDTH)]
-        return torch.cat(parts, 1)
-
-    def _head(self, x: Tensor) -> Tensor:
-        h = Fh.linear_wide(x, self.lin_1.weight, self.lin_1.bias, self.activation.hscn_name)
-        return Fh.linear_wide(h, self.lin_2.weight, self.lin_2.bias)
-
-    def _forward(self, batch) -> Tensor:
-        x = self._nodes(batch)
-        if self.task_level == "graph":
-            return self._head(self._pool(x, batch))
-        return self._node_head(x) if self._node_head.supported() else self._head(x)
 
 
 def build_gcnii(model_cfg: GCNIIConfig, num_features: int, num_classes: int) -> GCNII:

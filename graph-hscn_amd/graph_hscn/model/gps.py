@@ -16,18 +16,15 @@ from __future__ import annotations
 
 from typing import Callable, Optional
 
-import torch
 import torch.nn as nn
 from torch import Tensor
 
-from ..config.config import ACT_DICT, GPSConfig
-from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
-from ._common import POSENC_RESIDENT_REASON, LinkLevel, PosEnc, check_encoders, check_task_level, float_edge_attr
+from ..config.config import ACT_DICT, GPSConfig, check_exphormer
+from ..encoder.categorical import EDGE_ENCODERS
+from ._common import LayeredModel, _Table  # noqa: F401  (_Table stays importable from here)
 from ..nn import functional as Fh
 from ..nn.conv import Linear
 from ..nn.gps import GPSLayer
-from ..nn.head import NodeHead
-from ..nn.pool import global_mean_pool
 from ..structure import ExphormerStructure
 
 EXPHORMER_RESIDENT_REASON = ("Exphormer's sparse attention (model/gps.py GPS, global_model='exphormer'): typed edge "
@@ -37,26 +34,7 @@ RESIDENT_REASON = ("global attention (model/gps.py GPS): per-graph multi-head se
                    "resident or captured form; the model runs on the layered operators")
 
 
-def _check_exphormer(expander_degree, num_virtual_nodes) -> None:
-    d, nv = expander_degree, num_virtual_nodes
-    if isinstance(d, bool) or not isinstance(d, int) or d % 2 or not 2 <= d <= Fh.EXPANDER_MAX_DEGREE:
-        raise ValueError(f"expander_degree must be an even integer in [2, {Fh.EXPANDER_MAX_DEGREE}], got {d!r}")
-    if isinstance(nv, bool) or not isinstance(nv, int) or not 0 <= nv <= Fh.EXPH_MAX_VIRTUAL_NODES:
-        raise ValueError(f"num_virtual_nodes must be an integer in [0, {Fh.EXPH_MAX_VIRTUAL_NODES}], got {nv!r}")
-
-
-class _Table(nn.Module):
-    """A learned table ``weight`` [rows, D], drawn normal(0, 1) as an ``nn.Embedding`` is."""
-
-    def __init__(self, rows: int, channels: int):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(rows, channels))
-        nn.init.normal_(self.weight)
-
-
-class GPS(LinkLevel, PosEnc, nn.Module):
-    layered_only = True      # train.batching.refuse_layered_only: the resident entry points refuse this model by name
-
+class GPS(LayeredModel):
     def __init__(self, num_features: int, hidden_channels: int, num_classes: int, num_layers: int, num_heads: int = 4,
                  local_conv: Optional[str] = "gine", activation: Optional[Callable] = None, dropout: float = 0.0,
                  norm: Optional[str] = "layer", task_level: str = "graph", node_encoder: Optional[str] = None,
@@ -94,10 +72,7 @@ class GPS(LinkLevel, PosEnc, nn.Module):
         categories in place of the Linear node / edge encoder (for "gine" the bond encoder supplies the ``edge_attr``
         the layer's own edge Linear reads).  The defaults build the model as it always was."""
         super().__init__()
-        check_encoders(node_encoder, edge_encoder)
-        check_task_level(task_level)
-        if num_layers < 1:
-            raise ValueError("GPS needs at least one layer")
+        self._check_args(node_encoder, edge_encoder, task_level, num_layers)
         if attn_bias not in (None, "spd"):
             raise ValueError(f"attn_bias must be 'spd' or None, not {attn_bias!r}")
         if attn_bias is not None and not Fh.SPD_MIN_DIST <= int(spd_max_dist) <= Fh.SPD_MAX_DIST:
@@ -109,24 +84,16 @@ class GPS(LinkLevel, PosEnc, nn.Module):
             if attn_bias is not None:
                 raise ValueError(f"global_model='exphormer' and attn_bias={attn_bias!r} do not go together: the "
                                  "shortest-path bias belongs to the dense attention (attn_bias must be None)")
-            _check_exphormer(expander_degree, num_virtual_nodes)
+            check_exphormer(expander_degree, num_virtual_nodes)
         self.expander_degree, self.num_virtual_nodes = int(expander_degree), int(num_virtual_nodes)
         self.add_local_edges, self.expander_seed = bool(add_local_edges), int(expander_seed)
         self.attn_bias = attn_bias
         self.spd_max_dist = int(spd_max_dist)
-        activation = ACT_DICT["relu"] if activation is None else activation
-        act = getattr(activation, "hscn_name", None)
-        if act is None:
-            raise ValueError("activation must be one of config.ACT_DICT's (it runs in a Linear's epilogue)")
-        self.task_level = task_level
-        self.num_layers = int(num_layers)
-        self.activation = activation
-        self.dropout = float(dropout)
-        self.dropout_seed: Optional[int] = None     # tests pin the masks (layer i draws with seeds + 4 i .. + 4 i + 3)
+        # (pinned masks: layer i draws with dropout_seed + 4 i .. + 4 i + 3)
+        self._record(task_level, num_layers, activation, dropout, node_encoder, edge_encoder)
+        act = self.activation.hscn_name
         D = int(hidden_channels)
-        self.encoder_kinds = (node_encoder, edge_encoder)
-        Dx = self._init_pos_enc(pos_enc, pe_undirected, D)             # D - dim_pe with a positional encoder
-        self.node_encoder = Linear(num_features, Dx) if node_encoder is None else NODE_ENCODERS[node_encoder](Dx)
+        self._build_node_encoder(num_features, D, pos_enc, pe_undirected)
         spd_buckets = self.spd_max_dist + 1 if attn_bias == "spd" else None
         if global_model == "exphormer":
             self.layers = nn.ModuleList(GPSLayer(D, local_conv, num_heads, dropout, norm, act, global_model="exphormer",
@@ -143,63 +110,30 @@ class GPS(LinkLevel, PosEnc, nn.Module):
             self.edge_encoder = EDGE_ENCODERS[edge_encoder](D)
         elif self.layers[0].updates_edge_attr:      # "gatedgcn": edge features are a state of width D
             self.edge_encoder = Linear(-1, D)
-        self.lin_1 = Linear(D, D)
-        self.lin_2 = Linear(D, num_classes)
-        self._node_head = NodeHead(self.lin_1, self.lin_2, act)
+        self._build_head(D, num_classes)
         if global_model == "exphormer":             # after every parameter of before
             self.virt_node_emb = _Table(self.num_virtual_nodes, D)
             self.edge_type_emb = _Table(2 + 2 * self.num_virtual_nodes, D)
             if self.layers[0].uses_edge_attr and not hasattr(self, "edge_encoder") and self.add_local_edges:
                 self.exph_edge_encoder = Linear(-1, D)
         self._build_pos_encoder(D)                  # after every parameter of before
-        # "layered"; "auto" runs layered too; "resident" raises with the reason when the model is called
-        self.engine = "layered"
-        self.last_engine: Optional[str] = None
 
-    # ---- the surface of a homogeneous model (train.batching, train.train) ----------------------------------------
-    def resident_reason(self, batch=None, need_grad: bool = False) -> str:
-        reason = EXPHORMER_RESIDENT_REASON if self.global_model == "exphormer" else RESIDENT_REASON
-        if self.pos_enc is not None:
-            reason = reason + "; " + POSENC_RESIDENT_REASON
-        if any(self.encoder_kinds):
-            return reason + "; " + encoder_reason(*self.encoder_kinds)
-        return reason
+    # ---- what LayeredModel asks of the model ---------------------------------------------------------------------
+    def _own_reason(self) -> str:
+        return EXPHORMER_RESIDENT_REASON if self.global_model == "exphormer" else RESIDENT_REASON
 
-    def supported(self, batch=None) -> bool:
-        return False
-
-    def head_width(self) -> int:
-        """Columns of the prediction (what ``batching.score_width`` asks for class-index targets)."""
-        return int(self.lin_2.out_channels)
-
-    def check_flags(self) -> None:
-        """Synchronising: raises if an attention launch since the last check met a graph larger than its batch's
-        ``max_nodes`` (``nn.functional.check_attention``).  ``train.train_epoch`` / ``eval_epoch`` call it once per
-        epoch, beside the read of the epoch's loss."""
-        Fh.check_attention(next(self.parameters()).device)
+    def _check_launch_flags(self, dev) -> None:
+        """An attention launch that met a graph larger than its batch's ``max_nodes``."""
+        Fh.check_attention(dev)
         if self.global_model == "exphormer":        # and the expander launches' (a graph beyond max_nodes)
-            Fh.check_expander(next(self.parameters()).device)
+            Fh.check_expander(dev)
         if self.attn_bias == "spd":                 # and the bucket launches' (an edge outside its graph, max_nodes)
-            Fh.check_spd(next(self.parameters()).device)
-        if any(self.encoder_kinds):                # and the categorical encoders' (an index outside its column)
-            Fh.check_categorical(next(self.parameters()).device)
-        self._check_pe_flags()                      # and the positional encoder's statistics launches'
+            Fh.check_spd(dev)
+
+    def _edge_attr_reader(self) -> str:
+        return f"the model has edge-aware convolutions (local_conv {self.layers[0].local_conv!r})"
 
     # ---- forward -----------------------------------------------------------------------------------------------
-    def _edge_attr(self, batch) -> Tensor:
-        """``batch.edge_attr`` for an edge-aware ``local_conv``: float32 [E, De] on the model's device
-        (``MPNN._edge_attr``)."""
-        ea = getattr(batch, "edge_attr", None)
-        if ea is None:
-            raise ValueError(f"the model has edge-aware convolutions (local_conv {self.layers[0].local_conv!r}) and "
-                             "the batch carries no edge_attr (Data(edge_attr=[E, De]); make_dataset(..., edge_features=True))")
-        if self.encoder_kinds[1] is not None:       # int64 categories: the bond encoder checks them itself
-            return ea
-        return float_edge_attr(ea, next(self.parameters()).device)
-
-    def _embed_x(self, batch) -> Tensor:
-        return self.node_encoder(batch.x)
-
     def _spd(self, batch):
         """The batch's ``SPDBuckets`` at ``spd_max_dist``, built once: kept on the batch object, in a dict that
         ``train.batching.to_device`` hands on by reference, keyed by ``(max_dist, device)`` -- a batch reused across
@@ -214,14 +148,6 @@ class GPS(LinkLevel, PosEnc, nn.Module):
 
     def _nodes(self, batch) -> Tensor:
         """[N, D] after the last GPS layer."""
-        if self.engine not in ("layered", "auto", "resident"):
-            raise ValueError(f"engine must be 'layered', 'auto' or 'resident', got {self.engine!r}")
-        if self.engine == "resident":
-            reason = EXPHORMER_RESIDENT_REASON if self.global_model == "exphormer" else RESIDENT_REASON
-            if self.pos_enc is not None:
-                reason = self.resident_reason()
-            raise RuntimeError(f"engine='resident' does not take this model: {reason}")
-        self.last_engine = "layered"
         sparse = self.global_model == "exphormer"
         glob = {"spd": self._spd(batch)}            # the global branch's keywords, once per forward for all layers
         edge_attr = self._edge_attr(batch) if self.layers[0].uses_edge_attr else None
@@ -249,17 +175,6 @@ class GPS(LinkLevel, PosEnc, nn.Module):
             if sparse:
                 virt = out[-1]
         return x
-
-    def _head(self, x: Tensor) -> Tensor:
-        h = Fh.linear_wide(x, self.lin_1.weight, self.lin_1.bias, self.activation.hscn_name)
-        return Fh.linear_wide(h, self.lin_2.weight, self.lin_2.bias)
-
-    def _forward(self, batch) -> Tensor:
-        x = self._nodes(batch)
-        if self.task_level == "graph":
-            x = global_mean_pool(x, batch.batch, getattr(batch, "num_graphs", None))
-            return self._head(x)
-        return self._node_head(x) if self._node_head.supported() else self._head(x)
 
 
 def build_gps(model_cfg: GPSConfig, num_features: int, num_classes: int) -> GPS:

@@ -19,7 +19,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _hip
-from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig
+from ..config.config import ACT_DICT, CONV_DICT, MPNNConfig, pna_kwargs
 from ..encoder.categorical import EDGE_ENCODERS, NODE_ENCODERS, resident_reason as encoder_reason
 from ..nn.conv import GCNConv, Linear, PNAConv, TransformerConv
 from ..nn import functional as Fh
@@ -97,7 +97,7 @@ class MPNN(LinkLevel, PosEnc, nn.Module):
                 self.conv_layers.append(conv(hidden_channels, hidden_channels // heads, heads=heads))
             self.conv_layers.append(conv(hidden_channels, num_classes, heads=1))
         else:
-            kw = {} if pna is None else dict(aggregators=pna.aggregators, scalers=pna.scalers, avg_deg_log=pna.avg_deg_log)
+            kw = pna_kwargs(pna)
             self.conv_layers.append(conv(num_features, hidden_channels, **kw))
             for _ in range(num_layers - 2):
                 self.conv_layers.append(conv(hidden_channels, hidden_channels, **kw))

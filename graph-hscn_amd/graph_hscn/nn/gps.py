@@ -55,7 +55,7 @@ class GPSLayer(nn.Module):
         if global_model == "exphormer" and spd_buckets is not None:
             raise ValueError("global_model='exphormer' has no shortest-path bias (spd_buckets must be None)")
         self.global_model = global_model
-        from ..config.config import CONV_DICT
+        from ..config.config import CONV_DICT, pna_kwargs
         if local_conv is not None:
             local_conv = local_conv.lower()
             if local_conv not in LOCAL_CONVS:
@@ -77,8 +77,7 @@ class GPSLayer(nn.Module):
                 raise ValueError(f"channels {channels} must be divisible by num_heads {num_heads}")
             self.conv = CONV_DICT[local_conv](channels, channels // num_heads, heads=num_heads)
         elif local_conv in ("pna", "pna_edge"):     # pna: a config.PNAConfig (aggregators, scalers, avg_deg_log) or None
-            kw = {} if pna is None else dict(aggregators=pna.aggregators, scalers=pna.scalers, avg_deg_log=pna.avg_deg_log)
-            self.conv = CONV_DICT[local_conv](channels, channels, **kw)
+            self.conv = CONV_DICT[local_conv](channels, channels, **pna_kwargs(pna))
         else:
             self.conv = CONV_DICT[local_conv](channels, channels) if local_conv is not None else None
         # spd_buckets: the attention's own shortest-path bias table (Graphormer's spatial encoding); None: as before
