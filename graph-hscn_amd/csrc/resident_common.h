@@ -3,6 +3,7 @@
 // parameter-gradient reduction, and the diagnostic phase stamps.
 #pragma once
 #include "hscn_common.h"
+#include "row_sort6.h"
 
 namespace {
 
@@ -431,17 +432,21 @@ __device__ bool build_csr_pair_ell(const int* ek, const int* eo, int ne, int nro
 // order as uint16 (unused slots hold r itself: a valid row to read with weight zero), the count in the top half of the
 // last word.  A consumer reads a row's whole neighbourhood with ONE 16-byte LDS load, where rowptr -> col takes two
 // dependent ones -- and the build needs no prefix sum: phase 1 as build_csr_pair_ell (slots drawn by LDS atomics), phase 2
-// a thread per row (rank the <= 6 edge numbers in registers, store the record).  rec_a: rows keyed by ek, neighbours eo;
-// rec_t: rows keyed by eo, neighbours ek.  cnt_*, ovf zero on entry.  Returns false (for every thread alike) when a row
-// holds more than ELL_D edges: the caller takes the general CSR build then.
+// a thread per row.  An edge leaves the packed key (edge number << 16 | neighbour id) in the slot it draws, so the row's
+// thread needs the slots alone: it sorts the six keys (unused = 0xffffffff) through a 12-comparator network of
+// min / max pairs (row_sort6.h) -- ascending key order is ascending edge order -- and masks the ids out: no pairwise
+// ranking, no routing, and no second LDS trip to the edge list.  rec_a: rows keyed by ek, neighbours eo; rec_t: rows
+// keyed by eo, neighbours ek.  cnt_*, ovf zero on entry.  Returns false (for every thread alike) when a row holds more
+// than ELL_D edges, or when ne or nrows does not fit a key's 16-bit fields: the caller takes the general CSR build then.
 __device__ bool build_ell16_pair(const int* ek, const int* eo, int ne, int nrows, uint4* rec_a, uint4* rec_t, float* dinv,
                                  int* cnt_a, int* ell_a, int* cnt_t, int* ell_t, int* ovf, int RTn) {
+  if (ne > 65535 || nrows > 65535) return false;
   for (int e = threadIdx.x; e < ne; e += RTn) {
     const int k = ek[e], o = eo[e];
     if (k >= 0) {
       const int pa = atomicAdd(&cnt_a[k], 1), pt = atomicAdd(&cnt_t[o], 1);
-      if (pa < ELL_D) ell_a[k * ELL_D + pa] = e; else ovf[0] = 1;
-      if (pt < ELL_D) ell_t[o * ELL_D + pt] = e; else ovf[0] = 1;
+      if (pa < ELL_D) ell_a[k * ELL_D + pa] = (e << 16) | o; else ovf[0] = 1;
+      if (pt < ELL_D) ell_t[o * ELL_D + pt] = (e << 16) | k; else ovf[0] = 1;
     }
   }
   lds_barrier();
@@ -449,32 +454,17 @@ __device__ bool build_ell16_pair(const int* ek, const int* eo, int ne, int nrows
   for (int idx = threadIdx.x; idx < 2 * nrows; idx += RTn) {
     const bool tside = idx >= nrows;
     const int r = tside ? idx - nrows : idx;
-    const int* cnt = tside ? cnt_t : cnt_a;
-    const int* ell = tside ? ell_t : ell_a;
-    const int* other = tside ? ek : eo;
-    const int c = cnt[r];
-    int ev[ELL_D], ov[ELL_D];
+    const int c = (tside ? cnt_t : cnt_a)[r];
+    const int* ell = (tside ? ell_t : ell_a) + r * ELL_D;
+    uint32_t slot[ELL_D], id[ELL_D];
+    // (all six words lie inside the row's own slots; what an unused one holds is masked by the count)
 #pragma unroll
-    for (int j = 0; j < ELL_D; ++j) ev[j] = j < c ? ell[r * ELL_D + j] : 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < ELL_D; ++j) ov[j] = other[j < c ? ev[j] : 0];
-    unsigned id[ELL_D];
-#pragma unroll
-    for (int j = 0; j < ELL_D; ++j) id[j] = (unsigned)r;
-#pragma unroll
-    for (int j = 0; j < ELL_D; ++j) {
-      int rank = 0;
-#pragma unroll
-      for (int m = 0; m < ELL_D; ++m) rank += ev[m] < ev[j] ? 1 : 0;
-      // (edge numbers are distinct, so the ranks of the c real entries are 0 .. c-1)
-#pragma unroll
-      for (int q = 0; q < ELL_D; ++q)
-        if (j < c && rank == q) id[q] = (unsigned)ov[j];
-    }
+    for (int j = 0; j < ELL_D; ++j) slot[j] = (uint32_t)ell[j];
+    row_record_ids(slot, c, (uint32_t)r, id);
     const uint4 rec = make_uint4(id[0] | (id[1] << 16), id[2] | (id[3] << 16), id[4] | (id[5] << 16),
                                  (unsigned)r | ((unsigned)c << 16));
     (tside ? rec_t : rec_a)[r] = rec;
-    if (!tside && dinv) dinv[r] = c > 0 ? 1.0f / sqrtf((float)c) : 0.f;
+    if (!tside && dinv) dinv[r] = row_degree_norm6(c);
   }
   lds_barrier();
   return true;
